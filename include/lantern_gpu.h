@@ -146,6 +146,12 @@ LANTERN_GPU_EXPORT size_t lantern_gpu_cursor_search(lantern_gpu_cursor_t *, cons
                                                     usearch_error_t *);
 LANTERN_GPU_EXPORT size_t lantern_gpu_cursor_seen(lantern_gpu_cursor_t *); /* rows handed out since the last non-streaming call */
 LANTERN_GPU_EXPORT void   lantern_gpu_cursor_close(lantern_gpu_cursor_t *);
+/* lantern_gpu_cursor_search through a filter (lantern_gpu_filter_t: "Filtered search" below): streaming never hands out a row
+ * twice, and every row it hands out is allowed */
+struct lantern_gpu_filter;
+LANTERN_GPU_EXPORT size_t lantern_gpu_cursor_search_filtered(lantern_gpu_cursor_t *, const struct lantern_gpu_filter *, const void *query,
+                                                             usearch_scalar_kind_t, size_t k, size_t ef, bool streaming,
+                                                             usearch_label_t *labels, float *distances, usearch_error_t *);
 /* hnsw.c:317,326,340; product_quantization.c:102,185.  One pair, evaluated on the device. */
 LANTERN_GPU_EXPORT float usearch_distance(const void *a, const void *b, usearch_scalar_kind_t, size_t dims,
                                           usearch_metric_kind_t, usearch_error_t *);
@@ -277,6 +283,58 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_device_strided(usearch_index_t,
                                                                 float *d_distances, uint32_t *d_slots, uint32_t *d_counts,
                                                                 uint64_t *d_dist_evals, uint64_t *d_expansions, void *stream,
                                                                 usearch_error_t *);
+/* ------------------------------------------------------------------------------------------ */
+/* Filtered search: k-NN limited to an allow-set of rows.                       */
+/* PARITY UNPINNED BY THE REFERENCE: the reference's usearch fork is not in the tree; what follows */
+/* is a definition of this library.                                                             */
+/* ------------------------------------------------------------------------------------------ */
+/* A filter is a set of allowed slots of ONE index at ONE size.  For a query, expansion = max(ef or the index's ef, k + skip):
+ *  1. upper levels: greedy descent exactly as the unfiltered search; the filter does not apply on levels >= 1;
+ *  2. base layer, WALK path: two lists ordered by (distance, slot): `top` (at most expansion entries, allowed slots only) and
+ *     `next` (candidates still to expand, at most C entries, C >= expansion; a pop removes the entry).  Start: evaluate the start
+ *     node (D += 1), push it to next, and to top if allowed.  While next is not empty: c = min(next); stop if |top| == expansion
+ *     and worst(top) < c; else pop c (E += 1) and for each neighbour in list order: skip it if visited, else mark it visited and
+ *     evaluate it (D += 1) as key x; if |top| < expansion or x < worst(top), push x to next (a full next keeps its C smallest: x
+ *     replaces the worst entry when smaller and is dropped otherwise; a dropped node stays visited) and, if x's slot is allowed,
+ *     insert x into top (at most expansion entries).  The answer is top[skip, skip + k); it may be shorter than k (the reachable
+ *     part of the graph holds fewer allowed rows);
+ *  3. EXACT path: every allowed slot evaluated, the (distance, slot)-smallest [skip, skip + k) returned; D = allowed count, E = 0;
+ *  4. distances are the walk's per-pair reduction, bit for bit (usearch_distance): a row has the same bits on either path and in
+ *     the unfiltered search.
+ * With an all-allowed filter and C >= expansion the walk path returns exactly the ids, distance bits, D and E of the unfiltered
+ * search.  Deleted rows carry label 0 (hnsw.h:40); the reference skips them only after a search has returned them (scan.c:296-300)
+ * and gives up streaming after 1000 rows (scan.c:249-252), so a selective predicate applied after the index scan returns fewer
+ * than LIMIT rows -- a filter makes the walk itself look for allowed rows.
+ * A filter is refused (an error naming both sizes) on another index, or once the index has grown: it is never extended. */
+typedef struct lantern_gpu_filter lantern_gpu_filter_t;
+#define LANTERN_GPU_FILTER_SKIP_DELETED 1u /* also disallow every slot whose label is 0 */
+/* allowed iff the slot's label is in labels[0..n) (any order, duplicates allowed): sorted and searched on the device -- the form a
+ * backend feeds from a bitmap heap scan's TIDs, which are the labels */
+LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_from_labels(usearch_index_t, const usearch_label_t *labels, size_t n,
+                                                                        uint32_t flags, usearch_error_t *);
+/* a host bitmap over slots: bit s of words[s / 32]; n_words must be ceil(size / 32) */
+LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_from_slot_bitmap(usearch_index_t, const uint32_t *words, size_t n_words,
+                                                                             uint32_t flags, usearch_error_t *);
+LANTERN_GPU_EXPORT size_t lantern_gpu_filter_count(const lantern_gpu_filter_t *, usearch_error_t *); /* allowed slots */
+LANTERN_GPU_EXPORT void   lantern_gpu_filter_free(lantern_gpu_filter_t *);
+/* path: 0 auto, 1 walk, 2 exact.  cand_cap = C (0: max(4 expansion, 256), capped by LDS; below expansion it is raised to it).
+ * Auto takes the exact path when allowed^2 <= exact_factor * ef * n, ef the caller's or else the index's: a walk under a filter of
+ * selectivity s evaluates about D / s rows, the exact path `allowed`.  The rule does not depend on k or skip, so it is stable
+ * across a scan's pages.  Default exact_factor: 5.6, the measured crossover of the two paths (clustered 1M x 768 f32, ef = 64:
+ * DESIGN.md 4.9).  An empty filter returns 0 results without a launch. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_policy(usearch_index_t, int path, size_t cand_cap, double exact_factor, usearch_error_t *);
+/* launches of the two filtered kernels since the index was created */
+LANTERN_GPU_EXPORT void lantern_gpu_filter_stats(usearch_index_t, uint64_t *walk_launches, uint64_t *exact_launches, usearch_error_t *);
+/* lantern_gpu_search_batch through a filter (host buffers; the unused tail of a row is label 0 and +inf) */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered(usearch_index_t, const lantern_gpu_filter_t *, const void *queries, size_t nq,
+                                                          usearch_scalar_kind_t, size_t k, size_t ef, usearch_label_t *labels,
+                                                          float *distances, uint32_t *counts, usearch_error_t *);
+/* lantern_gpu_search_batch_device_strided through a filter */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_device(usearch_index_t, const lantern_gpu_filter_t *, const void *d_queries,
+                                                                 size_t query_stride_bytes, size_t nq, size_t k, size_t ef, size_t skip,
+                                                                 uint64_t *d_labels, float *d_distances, uint32_t *d_slots,
+                                                                 uint32_t *d_counts, uint64_t *d_dist_evals, uint64_t *d_expansions,
+                                                                 void *stream, usearch_error_t *);
 /* kernel shape of the search launch: waves per query (1..8; 0 = automatic: 4 when the batch fills the chip, up to 8 for
  * smaller batches) and resident workgroups (0 = auto) */
 LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_per_query, int max_workgroups,
@@ -523,6 +581,10 @@ LANTERN_GPU_EXPORT bool lantern_scan_gettuple(lantern_scan_t *, usearch_label_t 
  * Writes min(n, cap) values to ks (may be NULL), returns n. */
 LANTERN_GPU_EXPORT size_t lantern_scan_trace(lantern_scan_t *, int *ks, size_t cap);
 LANTERN_GPU_EXPORT void lantern_scan_end(lantern_scan_t *);
+/* Later rescans and gettuples of this scan go through the filter (lantern_gpu_cursor_search_filtered): every row it returns is
+ * allowed, and the 1000-row cap counts allowed rows.  NULL clears it.  Refused on a scan of lantern_scan_begin_client (the
+ * scan-service wire format carries no filter).  The filter must outlive the scan's use of it. */
+LANTERN_GPU_EXPORT void lantern_scan_set_filter(lantern_scan_t *, const struct lantern_gpu_filter *, usearch_error_t *);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Lifecycle of the HBM mirrors of page-resident indexes.  The reference      */

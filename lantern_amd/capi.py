@@ -107,7 +107,13 @@ EXPORTS = [
     # Lantern's node-tape helpers (usearch_storage.hpp:9-23), host-only
     "UsearchNodeBytes", "usearch_init_node", "node_tuple_size", "label_from_node", "level_from_node", "reset_node_label", "get_node_neighbors_mut",
     "lantern_quant_bits_scalar_kind",
+    # filtered search (lantern_gpu.h "Filtered search")
+    "lantern_gpu_filter_from_labels", "lantern_gpu_filter_from_slot_bitmap", "lantern_gpu_filter_count", "lantern_gpu_filter_free",
+    "lantern_gpu_set_filter_policy", "lantern_gpu_filter_stats", "lantern_gpu_search_batch_filtered", "lantern_gpu_search_batch_filtered_device",
+    "lantern_gpu_cursor_search_filtered", "lantern_scan_set_filter",
 ]
+FILTER_SKIP_DELETED = 1  # LANTERN_GPU_FILTER_SKIP_DELETED
+FILTER_PATHS = {"auto": 0, "walk": 1, "exact": 2}
 
 # int fn(void *ctx, const void *queries, size_t nq, size_t vec_bytes, size_t k, size_t ef, u64 *labels, f32 *dists, u32 *counts, const char **err)
 BATCH_SEARCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64),
@@ -261,6 +267,16 @@ def lib() -> C.CDLL:
         "reset_node_label": (None, [vp]),
         "get_node_neighbors_mut": (vp, [C.POINTER(Metadata), vp, u32, C.POINTER(u32)]),
         "lantern_quant_bits_scalar_kind": (i32, [i32, C.c_bool, err]),
+        "lantern_gpu_filter_from_labels": (vp, [vp, vp, sz, u32, err]),
+        "lantern_gpu_filter_from_slot_bitmap": (vp, [vp, vp, sz, u32, err]),
+        "lantern_gpu_filter_count": (sz, [vp, err]),
+        "lantern_gpu_filter_free": (None, [vp]),
+        "lantern_gpu_set_filter_policy": (None, [vp, i32, sz, C.c_double, err]),
+        "lantern_gpu_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), err]),
+        "lantern_gpu_search_batch_filtered": (None, [vp, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
+        "lantern_gpu_cursor_search_filtered": (sz, [vp, vp, vp, i32, sz, sz, C.c_bool, vp, vp, err]),
+        "lantern_scan_set_filter": (None, [vp, vp, err]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = the library does not export what the header declares
@@ -631,6 +647,48 @@ class GpuIndex:
         _call("lantern_gpu_exact_search", self.h, _ptr(Q), Q.shape[0], k, _ptr(slots), _ptr(dists))
         return slots, dists
 
+    # ---- filtered search (lantern_gpu.h "Filtered search") ----
+    def filter_from_labels(self, labels, skip_deleted=False) -> "Filter":
+        """A filter allowing the slots whose label is in `labels` (any order, duplicates allowed)."""
+        L = np.ascontiguousarray(labels, dtype=np.uint64).ravel()
+        h = _call("lantern_gpu_filter_from_labels", self.h, _ptr(L) if L.size else None, L.size, FILTER_SKIP_DELETED if skip_deleted else 0)
+        return Filter(self, h)
+
+    def filter_from_bitmap(self, words, skip_deleted=False) -> "Filter":
+        """A filter from a bitmap over slots: bit s of words[s // 32] (u32 words, ceil(len / 32) of them); a bool array per slot
+        is packed first."""
+        w = np.asarray(words)
+        if w.dtype == np.bool_:
+            w = np.packbits(w.astype(np.uint8), bitorder="little")
+            w = np.concatenate([w, np.zeros((-w.size) % 4, dtype=np.uint8)]).view(np.uint32)
+        W = np.ascontiguousarray(w, dtype=np.uint32).ravel()
+        h = _call("lantern_gpu_filter_from_slot_bitmap", self.h, _ptr(W) if W.size else None, W.size, FILTER_SKIP_DELETED if skip_deleted else 0)
+        return Filter(self, h)
+
+    def set_filter_policy(self, path="auto", cand_cap=0, exact_factor=5.6):
+        """path: "auto" | "walk" | "exact" (or 0 / 1 / 2)."""
+        _call("lantern_gpu_set_filter_policy", self.h, FILTER_PATHS.get(path, path), cand_cap, float(exact_factor))
+
+    def filter_stats(self):
+        w, e = C.c_uint64(), C.c_uint64()
+        _call("lantern_gpu_filter_stats", self.h, C.byref(w), C.byref(e))
+        return {"walk": int(w.value), "exact": int(e.value)}
+
+    def search_batch_filtered(self, filt: "Filter", queries, k, ef=0):
+        Q = _rows(queries, self.metric)
+        nq = Q.shape[0]
+        labels = np.zeros((nq, k), dtype=np.uint64)
+        dists = np.zeros((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _call("lantern_gpu_search_batch_filtered", self.h, filt.h, _ptr(Q), nq, _kind(self.metric), k, ef, _ptr(labels), _ptr(dists), _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_filtered_device(self, filt: "Filter", d_queries, query_stride, nq, k, ef=0, skip=0, d_labels=None, d_dists=None, d_slots=None,
+                                     d_counts=None, d_D=None, d_E=None, stream=None):
+        """search_batch_device through a filter; raw device addresses, the query row stride stated (device_query_rows(...).strides[0])."""
+        _call("lantern_gpu_search_batch_filtered_device", self.h, filt.h, _ptr(d_queries), int(query_stride), nq, k, ef, skip, _ptr(d_labels),
+              _ptr(d_dists), _ptr(d_slots), _ptr(d_counts), _ptr(d_D), _ptr(d_E), _ptr(stream))
+
     def distance_gather(self, query, slots):
         q = _rows(query, self.metric)[0]
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -822,6 +880,14 @@ class Cursor:
         n = _call("lantern_gpu_cursor_search", self.c, _ptr(q), _kind(self.index.metric), k, ef, bool(streaming), _ptr(labels), _ptr(dists))
         return labels[:n], dists[:n]
 
+    def search_filtered(self, filt: "Filter", query, k, ef=0, streaming=False):
+        q = _rows(query, self.index.metric)[0]
+        labels = np.zeros(k, dtype=np.uint64)
+        dists = np.zeros(k, dtype=np.float32)
+        n = _call("lantern_gpu_cursor_search_filtered", self.c, filt.h, _ptr(q), _kind(self.index.metric), k, ef, bool(streaming), _ptr(labels),
+                  _ptr(dists))
+        return labels[:n], dists[:n]
+
     @property
     def seen(self):
         return int(lib().lantern_gpu_cursor_seen(self.c))
@@ -972,6 +1038,29 @@ class Comm:
             pass
 
 
+class Filter:
+    """lantern_gpu_filter_t: an allow-set over the slots of one index at its current size (GpuIndex.filter_from_labels /
+    filter_from_bitmap)."""
+
+    def __init__(self, index: GpuIndex, handle):
+        self.index, self.h = index, handle
+
+    @property
+    def count(self) -> int:
+        return int(_call("lantern_gpu_filter_count", self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().lantern_gpu_filter_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Scan:
     """lantern_scan_*: the amgettuple paging shim (scan.c:24-338)."""
 
@@ -999,6 +1088,11 @@ class Scan:
         ok = lib().lantern_scan_gettuple(self.s, C.byref(label), C.byref(err))
         _check(err)
         return int(label.value) if ok else None
+
+    def set_filter(self, filt: "Filter" = None):
+        """Later rescans / gettuples go through the filter (None clears it); keep the Filter alive while the scan uses it."""
+        self._filter = filt
+        _call("lantern_scan_set_filter", self.s, filt.h if filt is not None else None)
 
     def trace(self):
         """The k of every usearch_search_ef issued since the last rescan ("querying index for %d elements", scan.c:219, :272)."""

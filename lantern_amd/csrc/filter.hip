@@ -1,0 +1,484 @@
+// filter.hip -- filtered k-NN search: building an allow-set over an index's slots, choosing between the filtered walk and the exact
+// pass over the allowed rows, and the C entry points (include/lantern_gpu.h "Filtered search"; semantics: DESIGN.md 4.9).
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "abi_guard.hpp"
+#include "filter.hpp"
+#include "index.hpp"
+
+namespace lgpu {
+
+// ---- building the bitmap on the device ----------------------------------------------------------------------------------
+// one thread per 32 slots: the word of slots [32 w, 32 w + 32).  A slot is allowed iff its label is among the sorted labels
+// (binary search), and -- SKIP_DELETED -- its label is not 0 (INVALID_ELEMENT_LABEL, hnsw.h:40).
+__global__ void k_filter_from_labels(const uint64_t *slot_labels, size_t n, const uint64_t *sorted, size_t m, int skip_deleted, uint32_t *bits,
+                                     size_t words)
+{
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(w >= words) return;
+    uint32_t word = 0;
+    for(uint32_t b = 0; b < 32; ++b) {
+        const size_t slot = w * 32 + b;
+        if(slot >= n) break;
+        const uint64_t l = slot_labels[ slot ];
+        if(skip_deleted && l == 0) continue;
+        size_t lo = 0, hi = m;
+        while(lo < hi) {
+            const size_t mid = (lo + hi) >> 1;
+            if(sorted[ mid ] < l) lo = mid + 1; else hi = mid;
+        }
+        if(lo < m && sorted[ lo ] == l) word |= 1u << b;
+    }
+    bits[ w ] = word;
+}
+// a caller's slot bitmap, uploaded: bits at or past n cleared, SKIP_DELETED applied
+__global__ void k_filter_mask(const uint64_t *slot_labels, size_t n, int skip_deleted, uint32_t *bits, size_t words)
+{
+    const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(w >= words) return;
+    uint32_t word = bits[ w ];
+    for(uint32_t b = 0; b < 32; ++b) {
+        const size_t slot = w * 32 + b;
+        if(slot >= n || (skip_deleted && slot_labels[ slot ] == 0)) word &= ~(1u << b);
+    }
+    bits[ w ] = word;
+}
+
+static const char *kFilterFlags = "lantern_gpu: unknown filter flags (only LANTERN_GPU_FILTER_SKIP_DELETED is defined)";
+
+static void filter_release(Filter *f)
+{
+    if(!f) return;
+    (void)hipSetDevice(f->device);
+    if(f->d_bits) (void)hipFree(f->d_bits);
+    if(f->d_slots) (void)hipFree(f->d_slots);
+    f->magic = 0;
+    delete f;
+}
+
+// the bitmap is in f->d_bits: its popcount and the allowed slots in ascending order (the exact path's work list)
+static bool filter_finish(Index *ix, Filter *f)
+{
+    std::vector<uint32_t> h(f->words);
+    if(hipMemcpy(h.data(), f->d_bits, f->words * 4, hipMemcpyDeviceToHost) != hipSuccess) { set_err(ix, "lantern_gpu: HIP failure building a filter"); return false; }
+    std::vector<uint32_t> slots;
+    for(size_t w = 0; w < f->words; ++w)
+        for(uint32_t x = h[ w ]; x; x &= x - 1) slots.push_back((uint32_t)(w * 32 + (size_t)__builtin_ctz(x)));
+    f->count = slots.size();
+    if(!slots.empty()) {
+        if(hipMalloc((void **)&f->d_slots, slots.size() * 4) != hipSuccess ||
+           hipMemcpy(f->d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            set_err(ix, "lantern_gpu: out of device memory (filter slot list)");
+            return false;
+        }
+    }
+    return true;
+}
+
+static Filter *filter_new(Index *ix)
+{
+    Filter *f = new Filter();
+    f->ix = ix;
+    f->device = ix->device;
+    f->n = ix->n;
+    f->words = ((std::max<size_t>(ix->n, 1) + 31) / 32 + 3) / 4 * 4;
+    if(hipMalloc((void **)&f->d_bits, f->words * 4) != hipSuccess || hipMemset(f->d_bits, 0, f->words * 4) != hipSuccess) {
+        set_err(ix, "lantern_gpu: out of device memory (filter bitmap)");
+        filter_release(f);
+        return nullptr;
+    }
+    return f;
+}
+
+static Filter *filter_from_labels_locked(Index *ix, const uint64_t *labels, size_t m, int skip_deleted)
+{
+    Filter *f = filter_new(ix);
+    if(!f) return nullptr;
+    bool ok = true;
+    if(m > 0 && ix->n > 0) {
+        // the labels sorted on the device (rocPRIM radix sort, as grouping.hip), then one thread per word binary-searches them
+        uint64_t *d_in = nullptr, *d_sorted = nullptr;
+        void     *temp = nullptr;
+        size_t    temp_bytes = 0;
+        ok = hipMalloc((void **)&d_in, m * 8) == hipSuccess && hipMalloc((void **)&d_sorted, m * 8) == hipSuccess &&
+             hipMemcpy(d_in, labels, m * 8, hipMemcpyHostToDevice) == hipSuccess &&
+             rocprim::radix_sort_keys(nullptr, temp_bytes, (const uint64_t *)d_in, d_sorted, m, 0u, 64u, ix->stream) == hipSuccess &&
+             hipMalloc(&temp, std::max<size_t>(temp_bytes, 16)) == hipSuccess &&
+             rocprim::radix_sort_keys(temp, temp_bytes, (const uint64_t *)d_in, d_sorted, m, 0u, 64u, ix->stream) == hipSuccess;
+        if(ok) {
+            const int blocks = (int)((f->words + 255) / 256);
+            hipLaunchKernelGGL(k_filter_from_labels, dim3(blocks), dim3(256), 0, ix->stream, (const uint64_t *)ix->d_labels, ix->n,
+                               (const uint64_t *)d_sorted, m, skip_deleted, f->d_bits, f->words);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ix->stream) == hipSuccess;
+        }
+        if(d_in) (void)hipFree(d_in);
+        if(d_sorted) (void)hipFree(d_sorted);
+        if(temp) (void)hipFree(temp);
+        if(!ok) set_err(ix, "lantern_gpu: HIP failure building a filter from labels");
+    }
+    if(!ok || !filter_finish(ix, f)) {
+        filter_release(f);
+        return nullptr;
+    }
+    return f;
+}
+
+static Filter *filter_from_bitmap_locked(Index *ix, const uint32_t *words, size_t n_words, int skip_deleted)
+{
+    Filter *f = filter_new(ix);
+    if(!f) return nullptr;
+    bool ok = n_words == 0 || hipMemcpy(f->d_bits, words, n_words * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if(ok) {
+        const int blocks = (int)((f->words + 255) / 256);
+        hipLaunchKernelGGL(k_filter_mask, dim3(blocks), dim3(256), 0, ix->stream, (const uint64_t *)ix->d_labels, ix->n, skip_deleted, f->d_bits,
+                           f->words);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ix->stream) == hipSuccess;
+    }
+    if(!ok) set_err(ix, "lantern_gpu: HIP failure building a filter from a slot bitmap");
+    if(!ok || !filter_finish(ix, f)) {
+        filter_release(f);
+        return nullptr;
+    }
+    return f;
+}
+
+// ---- the search ------------------------------------------------------------------------------------------------------------
+constexpr size_t kFilteredLds = 160 * 1024;  // a workgroup's LDS
+constexpr size_t kFilteredLdsTarget = 64 * 1024;  // what the visited set may grow the walk's LDS to (two workgroups per CU)
+constexpr int    kFilteredWaves = 4;
+
+// The caller holds ix->mu and has flushed.  false -> ix->err.
+static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
+                                   float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, hipStream_t stream)
+{
+    if(f->ix != ix) {
+        set_err(ix, "lantern_gpu: the filter belongs to another index (built over " + std::to_string(f->n) + " rows; this index holds " +
+                        std::to_string(ix->n) + ")");
+        return false;
+    }
+    if(f->n != ix->n) {
+        set_err(ix, "lantern_gpu: stale filter: built when the index held " + std::to_string(f->n) + " rows, it now holds " + std::to_string(ix->n) +
+                        " (build the filter again)");
+        return false;
+    }
+    if(ix->pq_compact) {
+        set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
+        return false;
+    }
+    if(nq == 0 || k == 0) return true;
+    const size_t ef_sel = ef ? ef : ix->ef;
+    const size_t exp = std::max(ef_sel, k + skip);
+    if(f->count == 0 || ix->n == 0) {  // nothing allowed: the empty answer, no launch
+        if(d_labels && hipMemsetAsync(d_labels, 0, nq * k * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(d_dists && hipMemsetD32Async((hipDeviceptr_t)d_dists, 0x7F800000, nq * k, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(d_slots && hipMemsetAsync(d_slots, 0xFF, nq * k * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(d_counts && hipMemsetAsync(d_counts, 0, nq * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(d_D && hipMemsetAsync(d_D, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(d_E && hipMemsetAsync(d_E, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        return true;
+    }
+    // the path: forced, or the rule of DESIGN.md 4.9 -- a walk under selectivity s evaluates about D / s rows, the exact pass `allowed`
+    bool exact = ix->filter_path == 2;
+    if(ix->filter_path == 0) exact = (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
+    const int G = group_lanes_for(ix->chunks);
+    FilteredArgs a{};
+    a.view = ix->view();
+    a.queries = d_q;
+    a.nq = (uint32_t)nq;
+    a.k = (uint32_t)k;
+    a.skip = (uint32_t)skip;
+    a.allow_bits = f->d_bits;
+    a.allow_slots = f->d_slots;
+    a.allow_count = (uint32_t)f->count;
+    a.labels = ix->d_labels;
+    a.out_labels = d_labels;
+    a.out_dists = d_dists;
+    a.out_slots = d_slots;
+    a.out_counts = d_counts;
+    a.out_D = d_D;
+    a.out_E = d_E;
+    a.totals = ix->d_totals;
+    size_t lds = 0;
+    if(exact) {
+        a.exp = (uint32_t)(k + skip);
+        a.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / G);
+        lds = filtered_exact_lds_bytes(ix->chunks, a.exp, a.rows_per_round);
+        if(lds > kFilteredLds) {
+            set_err(ix, "lantern_gpu: k + skip exceed the 160 KiB LDS budget of the exact filtered search kernel");
+            return false;
+        }
+    } else {
+        a.exp = (uint32_t)exp;
+        const size_t base = filtered_walk_lds_bytes(ix->chunks, a.exp, 0, ix->M0, 0);
+        if(base + exp * 16 > kFilteredLds) {
+            set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the filtered search kernel");
+            return false;
+        }
+        size_t cap = ix->filter_cand_cap ? std::max(ix->filter_cand_cap, exp) : std::max<size_t>(4 * exp, 256);
+        cap = std::min(cap, (kFilteredLds - base) / 16);
+        if(ix->filter_cand_cap && cap < std::max(ix->filter_cand_cap, exp)) {
+            set_err(ix, "lantern_gpu: the candidate cap exceeds the 160 KiB LDS budget of the filtered search kernel");
+            return false;
+        }
+        a.cand_cap = (uint32_t)cap;
+        uint32_t vis_slots = 2048;
+        while(vis_slots && filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots) > kFilteredLdsTarget)
+            vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
+        if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
+        a.vis_slots = vis_slots;
+        lds = filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots);
+    }
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
+    const int grid = search_grid(ix, nq, kFilteredWaves, kFilteredWaves * per_cu);
+    const int slot = acquire_search_slot(ix, stream, (size_t)grid);  // (orders the launch after inserts; the walk's visited bitmaps)
+    if(slot < 0) return false;
+    a.bitmaps = ix->slot_bitmaps[ slot ];
+    a.bm_words = (uint32_t)ix->slot_words[ slot ];
+    a.undo_cap = vis_undo_cap();
+    a.ticket = next_ticket(ix, nq, grid, stream);
+    const hipError_t e = exact ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
+                               : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
+    if(e != hipSuccess) {
+        set_err(ix, std::string("lantern_gpu: HIP error launching the filtered search: ") + hipGetErrorString(e));
+        return false;
+    }
+    if(!release_search_slot(ix, slot, stream)) return false;
+    (exact ? ix->c_filter_exact : ix->c_filter_walk) += 1;
+    ix->c_search_queries += nq;
+    return true;
+}
+
+// one query through `cur` (streaming: never a row twice): the first k allowed rows not handed out before
+static size_t cursor_search_filtered_locked(Index *ix, const Filter *f, Cursor *cur, const void *query, int kind, size_t k, size_t ef, bool streaming,
+                                            uint64_t *labels, float *distances)
+{
+    if(!streaming) cur->seen.clear();
+    if(ix->n == 0 || k == 0) return 0;
+    const size_t want = std::max<size_t>(1, std::min(cur->seen.size() + k, std::max<size_t>(f->count, 1)));
+    const size_t row = (size_t)ix->chunks * 16;
+    std::vector<uint32_t> padded((size_t)ix->chunks * 4);
+    pad_row(ix, query, kind, padded.data());
+    char *dq = (char *)scratch(ix, 5, row);
+    char *dout = (char *)scratch(ix, 6, want * 16 + 16);
+    if(!dq || !dout) return 0;
+    uint64_t *d_lab = (uint64_t *)dout;
+    float    *d_dist = (float *)(dout + want * 8);
+    uint32_t *d_slot = (uint32_t *)(dout + want * 12);
+    uint32_t *d_cnt = (uint32_t *)(dout + want * 16);
+    bool ok = hipMemcpyAsync(dq, padded.data(), row, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
+    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, 1, want, ef, 0, d_lab, d_dist, d_slot, d_cnt, nullptr, nullptr, ix->stream);
+    std::vector<char> h(want * 16 + 4);
+    ok = ok && hipMemcpyAsync(h.data(), dout, want * 16 + 4, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
+    if(!ok) {
+        if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during filtered search");
+        return 0;
+    }
+    const uint64_t *h_lab = (const uint64_t *)h.data();
+    const float    *h_dist = (const float *)(h.data() + want * 8);
+    const uint32_t *h_slot = (const uint32_t *)(h.data() + want * 12);
+    uint32_t        got;
+    std::memcpy(&got, h.data() + want * 16, 4);
+    size_t out = 0;
+    for(uint32_t i = 0; i < got && out < k; ++i) {
+        if(!cur->seen.insert(h_slot[ i ]).second) continue;
+        labels[ out ] = h_lab[ i ];
+        distances[ out ] = h_dist[ i ];
+        ++out;
+    }
+    return out;
+}
+
+}  // namespace lgpu
+
+// =====================================================================================================
+// C ABI
+// =====================================================================================================
+using namespace lgpu;
+
+// (lantern_gpu_filter_t stays an incomplete type: a handle is a Filter, recognised by its magic word)
+#define CLEAR(e) do { if(e) *(e) = nullptr; } while(0)
+#define FAIL(e, msg) do { if(e) *(e) = (msg); } while(0)
+
+static Index *FH(usearch_index_t h, usearch_error_t *e)
+{
+    if(!h) { FAIL(e, "lantern_gpu: null index handle"); return nullptr; }
+    if(((const Index *)h)->magic != kIndexMagic) { FAIL(e, "lantern_gpu: not an index handle (stale, freed or foreign pointer)"); return nullptr; }
+    (void)hipSetDevice(((Index *)h)->device);
+    return (Index *)h;
+}
+static Filter *FF(const lantern_gpu_filter_t *f, usearch_error_t *e)
+{
+    if(!f) { FAIL(e, "lantern_gpu: null filter handle"); return nullptr; }
+    if(((const Filter *)f)->magic != kFilterMagic) { FAIL(e, "lantern_gpu: not a filter handle (stale, freed or foreign pointer)"); return nullptr; }
+    return (Filter *)f;
+}
+
+extern "C" {
+
+lantern_gpu_filter_t *lantern_gpu_filter_from_labels(usearch_index_t h, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(flags & ~(uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED) { FAIL(e, kFilterFlags); return nullptr; }
+    if(n && !labels) { FAIL(e, "lantern_gpu: null label array"); return nullptr; }
+    Index *ix = FH(h, e);
+    if(!ix) return nullptr;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return nullptr; }
+    ix->err.clear();
+    Filter *f = filter_from_labels_locked(ix, labels, n, (flags & LANTERN_GPU_FILTER_SKIP_DELETED) ? 1 : 0);
+    if(!f) { FAIL(e, ix->err.c_str()); return nullptr; }
+    return (lantern_gpu_filter_t *)f;
+}
+LANTERN_ABI_CATCH(e)
+
+lantern_gpu_filter_t *lantern_gpu_filter_from_slot_bitmap(usearch_index_t h, const uint32_t *words, size_t n_words, uint32_t flags, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(flags & ~(uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED) { FAIL(e, kFilterFlags); return nullptr; }
+    if(n_words && !words) { FAIL(e, "lantern_gpu: null bitmap"); return nullptr; }
+    Index *ix = FH(h, e);
+    if(!ix) return nullptr;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return nullptr; }
+    ix->err.clear();
+    const size_t need = (ix->n + 31) / 32;
+    if(n_words != need) {
+        set_err(ix, "lantern_gpu: the slot bitmap has " + std::to_string(n_words) + " words; an index of " + std::to_string(ix->n) + " rows needs " +
+                        std::to_string(need));
+        FAIL(e, ix->err.c_str());
+        return nullptr;
+    }
+    Filter *f = filter_from_bitmap_locked(ix, words, n_words, (flags & LANTERN_GPU_FILTER_SKIP_DELETED) ? 1 : 0);
+    if(!f) { FAIL(e, ix->err.c_str()); return nullptr; }
+    return (lantern_gpu_filter_t *)f;
+}
+LANTERN_ABI_CATCH(e)
+
+size_t lantern_gpu_filter_count(const lantern_gpu_filter_t *f, usearch_error_t *e)
+try {
+    CLEAR(e);
+    const Filter *ff = FF(f, e);
+    return ff ? ff->count : 0;
+}
+LANTERN_ABI_CATCH(e)
+
+void lantern_gpu_filter_free(lantern_gpu_filter_t *f)
+try {
+    if(!f || ((const Filter *)f)->magic != kFilterMagic) return;
+    filter_release((Filter *)f);
+}
+LANTERN_ABI_CATCH_VOID(nullptr)
+
+void lantern_gpu_set_filter_policy(usearch_index_t h, int path, size_t cand_cap, double exact_factor, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(path < 0 || path > 2) { FAIL(e, "lantern_gpu: filter path must be 0 (auto), 1 (walk) or 2 (exact)"); return; }
+    if(!(exact_factor >= 0) || std::isinf(exact_factor)) { FAIL(e, "lantern_gpu: exact_factor must be a finite number >= 0"); return; }
+    Index *ix = FH(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->filter_path = path;
+    ix->filter_cand_cap = cand_cap;
+    ix->filter_exact_factor = exact_factor;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_filter_stats(usearch_index_t h, uint64_t *walk_launches, uint64_t *exact_launches, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FH(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(walk_launches) *walk_launches = ix->c_filter_walk;
+    if(exact_launches) *exact_launches = ix->c_filter_exact;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_filtered_device(usearch_index_t h, const lantern_gpu_filter_t *filter, const void *d_queries, size_t query_stride_bytes,
+                                              size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels, float *d_distances, uint32_t *d_slots,
+                                              uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, void *stream, usearch_error_t *e)
+try {
+    CLEAR(e);
+    const Filter *f = FF(filter, e);
+    if(!f) return;
+    Index *ix = FH(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)"); return; }
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    if(!filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts, d_D, d_E, (hipStream_t)stream))
+        FAIL(e, ix->err.c_str());
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_filtered(usearch_index_t h, const lantern_gpu_filter_t *filter, const void *queries, size_t nq, usearch_scalar_kind_t kind,
+                                       size_t k, size_t ef, usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    const Filter *f = FF(filter, e);
+    if(!f) return;
+    Index *ix = FH(h, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq == 0 || k == 0) return;
+    if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    const size_t row_words = (size_t)ix->chunks * 4, in_bytes = input_bytes(ix, (int)kind);
+    std::vector<uint32_t> padded(nq * row_words);
+    for(size_t i = 0; i < nq; ++i) pad_row(ix, (const char *)queries + i * in_bytes, (int)kind, padded.data() + i * row_words);
+    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
+    char *dq = (char *)scratch(ix, 5, q_bytes);
+    char *dout = (char *)scratch(ix, 6, out_bytes + 64);
+    if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
+    uint64_t *d_lab = (uint64_t *)dout;
+    float    *d_dist = (float *)(dout + nq * k * 8);
+    uint32_t *d_cnt = (uint32_t *)(dout + nq * k * 12);
+    std::vector<char> h_out(out_bytes);
+    bool ok = hipMemcpyAsync(dq, padded.data(), q_bytes, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
+    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, nq, k, ef, 0, d_lab, d_dist, nullptr, d_cnt, nullptr, nullptr, ix->stream);
+    ok = ok && hipMemcpyAsync(h_out.data(), dout, out_bytes, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
+    if(!ok) {
+        if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during filtered batched search");
+        FAIL(e, ix->err.c_str());
+        return;
+    }
+    std::memcpy(labels, h_out.data(), nq * k * 8);
+    std::memcpy(distances, h_out.data() + nq * k * 8, nq * k * 4);
+    if(counts) std::memcpy(counts, h_out.data() + nq * k * 12, nq * 4);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+size_t lantern_gpu_cursor_search_filtered(lantern_gpu_cursor_t *c, const lantern_gpu_filter_t *filter, const void *query, usearch_scalar_kind_t kind,
+                                          size_t k, size_t ef, bool streaming, usearch_label_t *labels, float *distances, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(!c) { FAIL(e, "lantern_gpu: null cursor"); return 0; }
+    const Filter *f = FF(filter, e);
+    if(!f) return 0;
+    Index *ix = FH(c->ix, e);
+    if(!ix) return 0;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the query does not match the index"); return 0; }
+    if(k == 0) return 0;
+    if(!query || !labels || !distances) { FAIL(e, "lantern_gpu: null query or result pointer"); return 0; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return 0; }
+    ix->err.clear();
+    const size_t out = cursor_search_filtered_locked(ix, f, &c->cur, query, (int)kind, k, ef, streaming, labels, distances);
+    if(!ix->err.empty()) FAIL(e, ix->err.c_str());
+    return out;
+}
+LANTERN_ABI_CATCH(e)
+
+}  // extern "C"

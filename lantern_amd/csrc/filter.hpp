@@ -1,0 +1,63 @@
+// filter.hpp -- filtered k-NN search: the allow-set over the slots of one index and the two kernels that honour it
+// (search_filtered_kernel.hip: the filtered graph walk and the exact pass over the allowed rows; filter.hip: building a filter and
+// the entry points).  Semantics: include/lantern_gpu.h "Filtered search" and DESIGN.md 4.9.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "kernels.hpp"
+
+namespace lgpu {
+
+struct Index;
+
+constexpr uint64_t kFilterMagic = 0x4C414E5446494C54ull;  // "LANTFILT": the first word of every live filter handle
+
+// An allow-set over the slots of ONE index at ONE size (the size after the flush every search performs).  Used on another index,
+// or once the index has grown, it is refused -- never silently extended.
+struct Filter
+{
+    uint64_t  magic = kFilterMagic;
+    Index    *ix = nullptr;
+    int       device = 0;
+    size_t    n = 0;                // the index's size when the filter was built
+    size_t    words = 0;            // 32-bit words of the bitmap (whole multiples of 4)
+    uint32_t *d_bits = nullptr;     // [words]: bit s of word s / 32 = slot s is allowed; bits >= n are zero
+    uint32_t *d_slots = nullptr;    // [count]: the allowed slots, ascending (the exact path's work list)
+    size_t    count = 0;            // popcount of the bitmap
+};
+
+// kernel arguments of both filtered kernels.  Fields are re-read from the kernarg segment at the points of a query that need them
+// (search_kernel.hpp "kernarg re-read").
+struct FilteredArgs
+{
+    View            view;
+    const uint4    *queries;     // [nq][chunks], zero padded
+    uint32_t        nq, k, skip;
+    uint32_t        exp;         // expansion = max(ef, k + skip): the capacity of `top` (walk) / k + skip (exact)
+    uint32_t        cand_cap;    // C: the capacity of `next` (walk only; >= exp)
+    const uint32_t *allow_bits;  // [words] the filter's bitmap
+    const uint32_t *allow_slots; // [allow_count] the allowed slots, ascending (exact only)
+    uint32_t        allow_count;
+    uint32_t        rows_per_round;  // exact only: rows evaluated per round (2 per G-lane group)
+    const uint64_t *labels;      // [n]
+    uint64_t       *out_labels;  // [nq][k] or NULL
+    float          *out_dists;   // [nq][k] or NULL
+    uint32_t       *out_slots;   // [nq][k] or NULL
+    uint32_t       *out_counts;  // [nq] or NULL
+    uint64_t       *out_D;       // [nq] or NULL
+    uint64_t       *out_E;       // [nq] or NULL
+    uint32_t       *bitmaps;     // walk only: the launch slot's visited bitmaps + undo logs (SearchArgs::bitmaps)
+    uint32_t        bm_words;
+    uint32_t        undo_cap;
+    uint32_t        vis_slots;
+    unsigned long long *totals;  // [2] cumulative D, E or NULL
+    uint32_t       *ticket;      // zeroed before the launch, or NULL (static striding)
+};
+
+size_t     filtered_walk_lds_bytes(uint32_t chunks, uint32_t exp, uint32_t cand_cap, uint32_t M0, uint32_t vis_slots);
+size_t     filtered_exact_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_round);
+hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
+hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
+
+}  // namespace lgpu

@@ -271,7 +271,7 @@ bool ensure_bitmaps(Index *ix, size_t slots)
 
 // entries of the bitmaps' undo logs a walk may use: all of them, or LANTERN_GPU_VIS_UNDO (tests of the overflow path: a walk that
 // records more ids than that clears its whole bitmap when it ends)
-static uint32_t vis_undo_cap()
+uint32_t vis_undo_cap()
 {
     static const uint32_t cap = [] {
         const char *e = std::getenv("LANTERN_GPU_VIS_UNDO");
@@ -362,7 +362,7 @@ static void pad_rows(const Index *ix, const void *rows, int kind, size_t count, 
 
 // a zeroed work ticket for one launch on `stream` (ring: concurrent launches on different streams get different slots)
 static const uint32_t kTicketRing = 64;
-static uint32_t *next_ticket(Index *ix, size_t work, int grid, hipStream_t stream)
+uint32_t *next_ticket(Index *ix, size_t work, int grid, hipStream_t stream)
 {
     if(!ix->use_tickets || !ix->d_tickets || work <= (size_t)grid) return nullptr;
     uint32_t *t = ix->d_tickets + (ix->ticket_next++ % kTicketRing);
@@ -2044,12 +2044,7 @@ try {
 }
 LANTERN_ABI_CATCH(e)
 
-// ---- cursors: the per-scan half of usearch_search_ef's streaming contract ------------------------------------------
-struct lantern_gpu_cursor
-{
-    Index *ix;
-    Cursor cur;
-};
+// ---- cursors: the per-scan half of usearch_search_ef's streaming contract (struct lantern_gpu_cursor: index.hpp) -----------
 
 lantern_gpu_cursor_t *lantern_gpu_cursor_open(usearch_index_t h, usearch_error_t *e)
 try {

@@ -185,6 +185,12 @@ struct Index
     // ---- counters ----------------------------------------------------------------------------------
     uint64_t c_search_queries = 0, c_add_vectors = 0, c_add_batches = 0, c_solo_launches = 0;
 
+    // ---- filtered search (filter.hip): the path policy (lantern_gpu_set_filter_policy) and which path each launch took
+    int      filter_path = 0;           // 0 auto, 1 walk, 2 exact
+    size_t   filter_cand_cap = 0;       // 0: max(4 expansion, 256), capped by LDS
+    double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
+    uint64_t c_filter_walk = 0, c_filter_exact = 0;
+
     hipStream_t stream = nullptr;
     int         device = 0;
     int         num_cus = 256;
@@ -206,6 +212,8 @@ void       *scratch(Index *ix, int which, size_t bytes);
 bool        pad_row(const Index *ix, const void *vec, int kind_in, uint32_t *dst);
 size_t      input_bytes(const Index *ix, int kind_in);
 bool        kind_accepted(const Index *ix, int kind_in);
+uint32_t   *next_ticket(Index *ix, size_t work, int grid, hipStream_t stream);  // a zeroed work ticket of a persistent launch, or NULL
+uint32_t    vis_undo_cap();
 int         search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu);
 // `done`: NULL, or a device-visible counter the kernel bumps per finished query; the caller then WAITS ON IT (not on the
 // stream) and no completion event is queued behind the launch
@@ -236,3 +244,10 @@ bool   serialize_stream(Index *ix, const SpanSink &sink);  // the same bytes as 
 bool   deserialize(Index *ix, const char *buf, size_t len);
 
 }  // namespace lgpu
+
+// one scan's share of the streaming contract (lantern_gpu_cursor_*: index.cpp, filter.hip)
+struct lantern_gpu_cursor
+{
+    lgpu::Index *ix;
+    lgpu::Cursor cur;
+};

@@ -23,6 +23,7 @@ struct lantern_scan
     lantern_gpu_cursor_t  *cursor = nullptr;  // what THIS scan has been handed so far: in the reference every scan owns its own
                                               // usearch handle (scan.c:99); here many scans share one resident index
     lantern_scan_client_t *client = nullptr;  // service back end (the connection holds the continuation state)
+    const lantern_gpu_filter_t *filter = nullptr;  // lantern_scan_set_filter: every search of the scan goes through it (local back end only)
     size_t                 client_query_bytes = 0;
     int                    init_k = 10;  // GUC lantern_hnsw.init_k  (options.c:324-348, options.h:44)
     int                    ef = 0;       // GUC lantern_hnsw.ef, 0 = use the index's ef (scan.c:179)
@@ -50,6 +51,9 @@ static size_t scan_search(lantern_scan *s, size_t k, bool streaming, usearch_err
                                                            s->distances.data(), err)
                          : lantern_scan_client_search(s->client, s->query.data(), s->query.size(), k, (size_t)s->ef, s->labels.data(),
                                                       s->distances.data(), err);
+    if(s->filter)
+        return lantern_gpu_cursor_search_filtered(s->cursor, s->filter, s->query.data(), s->scalar, k, (size_t)s->ef, streaming, s->labels.data(),
+                                                  s->distances.data(), err);
     return lantern_gpu_cursor_search(s->cursor, s->query.data(), s->scalar, k, (size_t)s->ef, streaming, s->labels.data(), s->distances.data(), err);
 }
 
@@ -120,8 +124,9 @@ try {
         const int k = s->count * 2;
         if(s->count >= 1000) return false;  // "skipping streaming after loading 1000 elements" (scan.c:249-252)
         if(!s->client) {
-            const size_t index_size = usearch_size(s->index, &err);
-            if((int)index_size == s->current) return false;  // scan.c:254-256
+            // scan.c:254-256; through a filter, every allowed row has been handed out
+            const size_t index_size = s->filter ? lantern_gpu_filter_count(s->filter, &err) : usearch_size(s->index, &err);
+            if((int)index_size == s->current) return false;
         }
         if(k == 0) return false;
         const size_t got = scan_search(s, (size_t)k, true /* streaming */, &err);
@@ -139,6 +144,20 @@ try {
     return false;
 }
 LANTERN_ABI_CATCH(e)
+
+void lantern_scan_set_filter(lantern_scan_t *s, const lantern_gpu_filter_t *filter, usearch_error_t *e)
+try {
+    if(e) *e = nullptr;
+    if(!s) { if(e) *e = "lantern_gpu: null scan"; return; }
+    if(s->client) { if(e) *e = "lantern_gpu: a scan through the scan service cannot be filtered (its wire format carries no filter)"; return; }
+    if(filter) {
+        usearch_error_t err = nullptr;
+        (void)lantern_gpu_filter_count(filter, &err);  // a live filter handle
+        if(err) { if(e) *e = err; return; }
+    }
+    s->filter = filter;
+}
+LANTERN_ABI_CATCH_VOID(e)
 
 size_t lantern_scan_trace(lantern_scan_t *s, int *ks, size_t cap)
 try {

@@ -1,0 +1,397 @@
+// search_filtered_kernel.hip -- filtered k-NN search over an allow-set of slots (filter.hpp).  Two kernels, one workgroup per query,
+// persistent over the batch (work handed out by ticket), kernel arguments re-read from the kernarg segment (search_kernel.hpp):
+//
+//  * k_search_filtered: the base-layer walk with TWO lists in LDS, both ordered by the walk's total order (distance, slot):
+//      top  -- at most `exp` keys, ALLOWED slots only (the answer is top[skip, skip + k));
+//      next -- the candidates still to be expanded, at most C keys, popped at a head index.
+//    Upper levels: greedy_descent exactly as k_search (the filter does not apply there).  Base layer: evaluate the start node, push
+//    it to next (and to top if allowed).  While next is not empty: c = min(next); stop if |top| == exp and worst(top) < c; else pop
+//    c (E += 1), evaluate every unvisited neighbour (D += 1 each, visited set of walk.hpp), and for each key x with |top| < exp or
+//    x < worst(top): push x to next (a full next keeps its C smallest: x replaces the worst entry when smaller, else is dropped; a
+//    dropped node stays visited), and insert x into top if its slot is allowed.
+//    A hop evaluates its neighbours together and admits them against worst(top) AT THE START of the hop, where the definition
+//    admits them one at a time against a radius that may shrink within the hop.  The extra keys this admits are >= the final
+//    radius: they never enter top (it keeps its exp smallest allowed keys either way), and in next they can neither be popped
+//    (next's minimum is >= worst(top) once only they remain: the walk stops) nor push out an entry that could be (an entry evicted
+//    by one of them is larger still).  So the hop's batch gives the keys, D and E of the one-at-a-time definition.
+//    ALL-ALLOWED PROPERTY: with every slot allowed and C >= exp the walk returns exactly the ids, distance bits, D and E of the
+//    unfiltered k_search.  Every entry of next that is smaller than worst(top) is in top (both lists received it, top drops only
+//    entries larger than its worst); so an entry evicted from a full next has at least exp smaller entries in top and would never
+//    have been popped, and the pops are those of the single-list walk ("first unexpanded entry of the ef list": walk.hpp).
+//  * k_search_exact_allowed: every allowed slot (the filter's ascending slot list) evaluated with the walk's row-distance routine --
+//    the same bits as the walk gives the row -- and a rank-merge into an LDS list of k + skip keys.  D = allowed count, E = 0.
+//
+// The allow bit of a slot travels in the LOW bit of its key (the "expanded" flag of the unfiltered walk, unused here): a slot is
+// either allowed or not, so two keys of one slot carry the same bit and the order (distance, slot) is untouched.
+//
+// PARITY UNPINNED BY THE REFERENCE: the reference's usearch fork is not in the tree; these semantics are a definition of this
+// repository (tests/filtered_walk_ref.py restates them on the CPU).
+#include "filter.hpp"
+#include "search_kernel.hpp"
+
+namespace lgpu {
+
+__device__ __forceinline__ uint64_t allow_bit(const uint32_t *bits, uint32_t slot) { return (uint64_t)((bits[ slot >> 5 ] >> (slot & 31)) & 1u); }
+
+// #{j < n : a[j] < k}, every key of a[] taken
+__device__ __forceinline__ int count_below(const uint64_t *a, int n, uint64_t k)
+{
+    int c = 0;
+    for(int j = 0; j < n; ++j) c += a[ j ] < k;
+    return c;
+}
+// #{j < n : a[j] < k and a[j]'s allow bit is set}
+__device__ __forceinline__ int count_below_allowed(const uint64_t *a, int n, uint64_t k)
+{
+    int c = 0;
+    for(int j = 0; j < n; ++j) c += (a[ j ] < k) & (int)(a[ j ] & 1u);
+    return c;
+}
+
+// the carve of the walk's LDS: walk.hpp's (q, top, top merge target, new keys, new ids, scalars, visited set) + next and its merge target
+__device__ __forceinline__ void carve_filtered(unsigned char *p, WalkLds &s, uint64_t *&nx, uint64_t *&nx2, uint32_t chunks, uint32_t exp,
+                                               uint32_t cand_cap, uint32_t M0, uint32_t vis_slots)
+{
+    unsigned char *end = carve_walk(p, s, chunks, exp, M0, vis_slots);
+    end = (unsigned char *)(((size_t)end + 15) & ~(size_t)15);
+    nx = (uint64_t *)end;
+    nx2 = nx + cand_cap;
+}
+size_t filtered_walk_lds_bytes(uint32_t chunks, uint32_t exp, uint32_t cand_cap, uint32_t M0, uint32_t vis_slots)
+{
+    return walk_lds_bytes(chunks, exp, M0, vis_slots) + 16 + (size_t)cand_cap * 16;
+}
+size_t filtered_exact_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_round) { return walk_lds_bytes(chunks, kk, rows_per_round, 0); }
+
+// scalar slots of the filtered walk beyond walk.hpp's (the register-list walk's hand-off slots, unused here): new keys of the hop
+// admitted to next / allowed among them, double-buffered by hop parity like the new-id count (a wave that leaves a hop early without
+// a barrier must not see the next hop's reset)
+enum { S_ADMIT0 = S_FRONT, S_ADMIT1, S_ALLOWED0, S_ALLOWED1 };
+
+// The base layer of the filtered walk.  On return s.keys[0..cnt) holds top, ascending; returns cnt.
+template <int METRIC, int G>
+__device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, uint64_t *nx2, const uint32_t *allow, uint32_t *bitmap,
+                                     uint32_t bm_words, uint32_t start, int exp, int C, uint32_t &D, uint32_t &E)
+{
+    const int  tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
+    const int  lane = tid & 63;
+    const bool wave0 = __builtin_amdgcn_readfirstlane(tid) < 64;
+    for(uint32_t i = tid; i < s.vis_slots; i += T) s.vis[ i ] = EMPTY;
+    const float qn2 = __int_as_float(s.scal[ S_QN2 ]);
+    if(g == 0) {
+        float d = group_dist_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, start), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, start));
+        if(gl == G - 1) {
+            const uint64_t key = make_key(d, start) | allow_bit(allow, start);
+            nx[ 0 ] = key;
+            s.keys[ 0 ] = key;
+            s.scal[ S_CNT ] = (int)(key & 1u);
+        }
+    }
+    D += 1;
+    __syncthreads();
+    int tcnt = s.scal[ S_CNT ];  // |top|
+    int head = 0, ncnt = 1;      // next = nx[head, ncnt)
+    uint32_t viscnt = 0;
+    bool     spilled = false;
+    VisUndo  undo;
+    if(tid == 0) {
+        (void)visit_test_and_set(s, bitmap, start, false);
+        viscnt = s.vis_slots ? 1u : 0u;
+    }
+    viscnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)viscnt);
+    if(wave0 && !s.vis_slots) undo_record(s, undo, lane == 0, start, 1ull, lane);
+    __syncthreads();  // (S_CNT is read by every wave before wave 0 may reuse the scalars)
+    for(int hop = 0;; ++hop) {
+        int *const nnew_slot = &s.scal[ (hop & 1) ? S_NNEW1 : S_NNEW0 ];
+        int *const admit_slot = &s.scal[ (hop & 1) ? S_ADMIT1 : S_ADMIT0 ];
+        int *const allowed_slot = &s.scal[ (hop & 1) ? S_ALLOWED1 : S_ALLOWED0 ];
+        // ---- (1) wave 0: stop test, pop, neighbour list, visited filter
+        if(wave0) {
+            bool     stop = head >= ncnt;
+            uint64_t c = 0;
+            if(!stop) {
+                c = nx[ head ];
+                stop = tcnt == exp && s.keys[ exp - 1 ] < c;
+            }
+            if(stop) {
+                if(lane == 0) *nnew_slot = -1;
+            } else {
+                E += 1;
+                const uint32_t node = key_slot(c);
+                if(s.vis_slots && !spilled && viscnt + v.M0 > s.vis_slots / 4 * 3) spilled = true;
+                uint32_t        cap;
+                const uint32_t *list = neighbors_of(v, node, 0, cap);
+                int             nb_new = 0;
+                for(uint32_t off = 0; off < cap; off += 64) {
+                    const uint32_t           i = off + (uint32_t)lane;
+                    const uint32_t           nb = i < cap ? list[ i ] : EMPTY;
+                    const bool               isnew = hop_is_new(s, bitmap, nb, spilled);
+                    const unsigned long long m = __ballot(isnew);
+                    if(isnew) s.newids[ nb_new + __popcll(m & ((1ull << lane) - 1ull)) ] = nb;
+                    if(spilled || !s.vis_slots) undo_record(s, undo, isnew, nb, m, lane);
+                    nb_new += __popcll(m);
+                }
+                if(s.vis_slots && !spilled) viscnt += (uint32_t)nb_new;
+                if(lane == 0) { *nnew_slot = nb_new; *admit_slot = 0; *allowed_slot = 0; }
+            }
+        }
+        __syncthreads();
+        const int nnew = *nnew_slot;
+        if(nnew < 0) break;
+        head += 1;  // the pop
+        if(nnew == 0) continue;
+        // ---- (2) distances: one G-lane group per row, two rows in flight per group (walk.hpp hop_distances), the allow bit in the key
+        const uint64_t worst = tcnt == exp ? s.keys[ exp - 1 ] : ~0ull;
+        for(int i = g; i < nnew; i += 2 * NG) {
+            const int      j = i + NG;
+            const uint32_t id0 = s.newids[ i ];
+            const uint32_t id1 = j < nnew ? s.newids[ j ] : id0;
+            const uint64_t a0 = allow_bit(allow, id0), a1 = allow_bit(allow, id1);
+            float          d0, d1;
+            group_dist2_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, id0), row_of_m<METRIC>(v, id1), (int)v.chunks, gl, qn2,
+                                     row_norm<METRIC>(v, id0), row_norm<METRIC>(v, id1), d0, d1);
+            if(gl == G - 1) {
+                const uint64_t k0 = make_key(d0, id0) | a0;
+                s.newkeys[ i ] = k0;
+                int adm = k0 < worst, alw = (k0 < worst) & (int)a0;
+                if(j < nnew) {
+                    const uint64_t k1 = make_key(d1, id1) | a1;
+                    s.newkeys[ j ] = k1;
+                    adm += k1 < worst;
+                    alw += (k1 < worst) & (int)a1;
+                }
+                if(adm) atomicAdd(admit_slot, adm);
+                if(alw) atomicAdd(allowed_slot, alw);
+            }
+        }
+        D += (uint32_t)nnew;
+        __syncthreads();
+        const int n_admit = *admit_slot, n_allowed = *allowed_slot;
+        if(n_admit == 0) continue;  // nothing enters either list
+        // ---- (3) rank-merges: top U allowed admitted keys -> keys2 (exp), next U admitted keys -> nx2 (C); the new keys unsorted
+        {
+            const int total = tcnt + nnew;
+            for(int t = tid; t < total; t += T) {
+                if(t < tcnt) {
+                    const uint64_t k = s.keys[ t ];
+                    const int      p = t + count_below_allowed(s.newkeys, nnew, k < worst ? k : worst);
+                    if(p < exp) s.keys2[ p ] = k;
+                } else {
+                    const uint64_t k = s.newkeys[ t - tcnt ];
+                    if(!(k & 1u) || !(k < worst)) continue;
+                    const int p = count_below_allowed(s.newkeys, nnew, k) + lower_bound_keys(s.keys, tcnt, k);
+                    if(p < exp) s.keys2[ p ] = k;
+                }
+            }
+            const uint64_t *nb = nx + head;
+            const int       m = ncnt - head, ntotal = m + nnew;
+            for(int t = tid; t < ntotal; t += T) {
+                if(t < m) {
+                    const uint64_t k = nb[ t ];
+                    const int      p = t + count_below(s.newkeys, nnew, k < worst ? k : worst);
+                    if(p < C) nx2[ p ] = k;
+                } else {
+                    const uint64_t k = s.newkeys[ t - m ];
+                    if(!(k < worst)) continue;
+                    const int p = count_below(s.newkeys, nnew, k) + lower_bound_keys(nb, m, k);
+                    if(p < C) nx2[ p ] = k;
+                }
+            }
+            tcnt = tcnt + n_allowed < exp ? tcnt + n_allowed : exp;
+            ncnt = m + n_admit < C ? m + n_admit : C;
+            head = 0;
+            uint64_t *tmp = s.keys; s.keys = s.keys2; s.keys2 = tmp;
+            tmp = nx; nx = nx2; nx2 = tmp;
+        }
+        __syncthreads();
+    }
+    if(wave0) undo_apply(s, bitmap, bm_words, undo, lane);
+    return tcnt;
+}
+
+#define LGPU_FARG(base, field) LGPU_KARG(base, decltype(FilteredArgs::field), offsetof(FilteredArgs, field))
+
+// the answer of one query: top[skip, skip + k) of the list in s.keys, the unused tail label 0 / +inf / EMPTY; counts, D, E; the ticket
+__device__ __forceinline__ void write_answers(WalkLds &s, uint32_t q, int cnt, uint32_t D, uint32_t E)
+{
+    const int          tid = threadIdx.x, T = blockDim.x;
+    const KernargBytes kb = kernarg_opaque();
+    const uint32_t     k = LGPU_FARG(kb, k), skip = LGPU_FARG(kb, skip);
+    const uint64_t    *labels = LGPU_FARG(kb, labels);
+    uint64_t          *out_labels = LGPU_FARG(kb, out_labels);
+    float             *out_dists = LGPU_FARG(kb, out_dists);
+    uint32_t          *out_slots = LGPU_FARG(kb, out_slots);
+    int                got = cnt - (int)skip;
+    got = got < 0 ? 0 : (got > (int)k ? (int)k : got);
+    for(uint32_t i = tid; i < k; i += T) {
+        const size_t o = (size_t)q * k + i;
+        if((int)i < got) {
+            const uint64_t key = s.keys[ skip + i ];
+            const uint32_t slot = key_slot(key);
+            if(out_labels) out_labels[ o ] = labels[ slot ];
+            if(out_dists) out_dists[ o ] = key_dist(key);
+            if(out_slots) out_slots[ o ] = slot;
+        } else {
+            if(out_labels) out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
+            if(out_dists) out_dists[ o ] = __builtin_inff();
+            if(out_slots) out_slots[ o ] = EMPTY;
+        }
+    }
+    if(tid == 0) {
+        uint32_t *const           out_counts = LGPU_FARG(kb, out_counts);
+        uint64_t *const           out_D = LGPU_FARG(kb, out_D), *const out_E = LGPU_FARG(kb, out_E);
+        unsigned long long *const totals = LGPU_FARG(kb, totals);
+        uint32_t *const           ticket = LGPU_FARG(kb, ticket);
+        if(out_counts) out_counts[ q ] = (uint32_t)got;
+        if(out_D) out_D[ q ] = D;
+        if(out_E) out_E[ q ] = E;
+        if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
+        s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(q + gridDim.x);
+    }
+    __syncthreads();
+}
+
+// the query row into LDS, and ||query||^2 for the cosine metrics (as k_search)
+template <int METRIC, int G> __device__ __forceinline__ void load_query(WalkLds &s, const uint4 *queries, uint32_t q, uint32_t chunks)
+{
+    const int tid = threadIdx.x, T = blockDim.x;
+    for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = queries[ (size_t)q * chunks + i ];
+    __syncthreads();
+    if(kCachedNorms<METRIC>) {
+        if(tid < G) {
+            const float qn = group_norm<METRIC, G>(s.q, (int)chunks, tid);
+            if(tid == G - 1) s.scal[ S_QN2 ] = __float_as_int(qn);
+        }
+        __syncthreads();
+    }
+}
+
+template <int METRIC, int G>
+__global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
+{
+    WalkLds   s;
+    uint64_t *nx, *nx2;
+    {
+        const KernargBytes ka = kernarg_opaque();
+        carve_filtered(lgpu_smem, s, nx, nx2, LGPU_VIEW_ARG(ka, FilteredArgs, chunks), LGPU_FARG(ka, exp), LGPU_FARG(ka, cand_cap),
+                       LGPU_VIEW_ARG(ka, FilteredArgs, M0), LGPU_FARG(ka, vis_slots));
+    }
+    for(uint32_t q = blockIdx.x; q < LGPU_FARG(kernarg_opaque(), nq);) {
+        uint32_t D = 0, E = 0;
+        int      cnt = 0;
+        {
+            const KernargBytes ka = kernarg_opaque();
+            View               v;
+            LGPU_LOAD_VIEW(v, ka, FilteredArgs)
+            const uint32_t bm_words = LGPU_FARG(ka, bm_words);
+            uint32_t      *bitmap = LGPU_FARG(ka, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
+            s.undo = bitmap + bm_words;
+            s.undo_cap = LGPU_FARG(ka, undo_cap);
+            load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
+            if(v.n != 0) {
+                const uint32_t start = greedy_descent<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
+                cnt = search_level_filtered<METRIC, G>(v, s, nx, nx2, LGPU_FARG(ka, allow_bits), bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
+                                                       (int)LGPU_FARG(ka, cand_cap), D, E);
+            }
+        }
+        write_answers(s, q, cnt, D, E);
+        q = (uint32_t)s.scal[ S_POS ];
+        __syncthreads();
+    }
+}
+
+// The exact path: rows_per_round allowed rows per round (two per G-lane group, group_dist2_n as the walk's hops), merged into an
+// LDS list of k + skip keys when any of them beats its worst.
+template <int METRIC, int G>
+__global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
+{
+    const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
+    WalkLds   s;
+    {
+        const KernargBytes ka = kernarg_opaque();
+        carve_walk(lgpu_smem, s, LGPU_VIEW_ARG(ka, FilteredArgs, chunks), LGPU_FARG(ka, exp), LGPU_FARG(ka, rows_per_round), 0);
+    }
+    for(uint32_t q = blockIdx.x; q < LGPU_FARG(kernarg_opaque(), nq);) {
+        int cnt = 0;
+        uint32_t D = 0;
+        {
+            const KernargBytes ka = kernarg_opaque();
+            View               v;
+            LGPU_LOAD_VIEW(v, ka, FilteredArgs)
+            load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
+            const float     qn2 = __int_as_float(s.scal[ S_QN2 ]);
+            const uint32_t *slots = LGPU_FARG(ka, allow_slots);
+            const int       count = (int)LGPU_FARG(ka, allow_count), kk = (int)LGPU_FARG(ka, exp), R = 2 * NG;
+            for(int base = 0, round = 0; base < count; base += R, ++round) {
+                const int      nr = count - base < R ? count - base : R;
+                const uint64_t worst = cnt == kk ? s.keys[ kk - 1 ] : ~0ull;
+                int *const     any_slot = &s.scal[ (round & 1) ? S_ANY1 : S_ANY0 ];  // (by parity: a wave still reading the last round's)
+                if(tid == 0) *any_slot = 0;
+                __syncthreads();
+                if(g < nr) {
+                    const int      i = g, j = g + NG;
+                    const uint32_t id0 = slots[ base + i ];
+                    const uint32_t id1 = j < nr ? slots[ base + j ] : id0;
+                    float          d0, d1;
+                    group_dist2_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, id0), row_of_m<METRIC>(v, id1), (int)v.chunks, gl, qn2,
+                                             row_norm<METRIC>(v, id0), row_norm<METRIC>(v, id1), d0, d1);
+                    if(gl == G - 1) {
+                        const uint64_t k0 = make_key(d0, id0);
+                        s.newkeys[ i ] = k0;
+                        bool any = k0 < worst;
+                        if(j < nr) {
+                            const uint64_t k1 = make_key(d1, id1);
+                            s.newkeys[ j ] = k1;
+                            any |= k1 < worst;
+                        }
+                        if(any) *any_slot = 1;
+                    }
+                }
+                __syncthreads();
+                if(!*any_slot) continue;
+                const int total = cnt + nr;
+                for(int t = tid; t < total; t += T) {
+                    const bool     is_new = t >= cnt;
+                    const uint64_t k = is_new ? s.newkeys[ t - cnt ] : s.keys[ t ];
+                    const int      below = count_below(s.newkeys, nr, k);
+                    const int      p = is_new ? below + lower_bound_keys(s.keys, cnt, k) : t + below;
+                    if(p < kk) s.keys2[ p ] = k;
+                }
+                cnt = total < kk ? total : kk;
+                uint64_t *tmp = s.keys; s.keys = s.keys2; s.keys2 = tmp;
+                __syncthreads();
+            }
+            D = (uint32_t)count;
+        }
+        write_answers(s, q, cnt, D, 0);
+        q = (uint32_t)s.scal[ S_POS ];
+        __syncthreads();
+    }
+}
+
+#define LGPU_LAUNCH_FILTERED(KERNEL, LDS_, MM, GG)                                                   \
+    {                                                                                                \
+        static LdsAttrCache attr_;                                                                   \
+        ensure_dynamic_lds((const void *)KERNEL<MM, GG>, LDS_, attr_);                               \
+        hipLaunchKernelGGL((KERNEL<MM, GG>), dim3(grid), dim3(64 * waves), LDS_, stream, a);         \
+    }
+
+hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
+{
+    const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.vis_slots);
+#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG)
+    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+#undef CALL
+    return hipGetLastError();
+}
+
+hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
+{
+    const size_t lds = filtered_exact_lds_bytes(a.view.chunks, a.exp, a.rows_per_round);
+#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG)
+    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+#undef CALL
+    return hipGetLastError();
+}
+
+}  // namespace lgpu
