@@ -29,6 +29,10 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 #ifndef LGPU_ROW_BLOCK1
 #define LGPU_ROW_BLOCK1 4
 #endif
+// the int8 screen of f32 l2sq rows (walk.hpp hop_distances_screened, kernels.hip k_fill_screen): 0 = never built
+#ifndef LGPU_SCREEN
+#define LGPU_SCREEN 1
+#endif
 
 // values follow usearch_metric_kind_t (include/lantern_gpu.h)
 constexpr int M_COS = 1;
@@ -592,7 +596,19 @@ struct View
     uint32_t        pq_C;         // centroids per subvector
     uint32_t        pq_inv;       // ceil(2^16 / pq_cps): chunk / pq_cps == (chunk * pq_inv) >> 16 for chunk < 2^11 (host-checked)
     uint32_t        pq_row_bytes; // bytes of one code row (num_subvectors padded to 16)
+    // the int8 SCREEN copy of an f32 l2sq index (rows of >= 128 chunks; walk.hpp hop_distances_screened); NULL when off
+    const uint4    *screen;        // [cap][screen_chunks] 16 int8 values per chunk, zero padded
+    const float2   *screen_meta;   // [cap] (s, r): the row's screen values are s * q (f32 multiply), r >= ||row - screen row||
+    uint32_t        screen_chunks; // ceil(chunks / 4)
 };
+
+// ---- the int8 screen of an f32 l2sq row ------------------------------------------------------------------------------
+// Screen value b (0..3) of word w of a screen row with scale s: the f32 product s * q.  k_fill_screen measures r against
+// exactly these values, and the walk's screen distance reads them the same way.
+__host__ __device__ __forceinline__ float screen_val(float s, uint32_t w, int b) { return s * (float)(int)(int8_t)(uint8_t)(w >> (8 * b)); }
+// the screen is built for f32 l2sq rows that the walk reads with 64 lanes (>= 128 chunks: d >= 509)
+__host__ __device__ inline bool screen_rows_for(uint32_t chunks) { return chunks >= 128; }
+__host__ __device__ inline uint32_t screen_chunks_for(uint32_t chunks) { return (chunks + 3) / 4; }
 
 __device__ __forceinline__ const uint4 *row_of(const View &v, uint32_t slot) { return v.vec + (size_t)slot * v.chunks; }
 

@@ -109,6 +109,9 @@ View Index::view() const
     v.upper_nbr = d_upper_nbr;
     v.levels = d_levels;
     v.norm2 = d_norm2;
+    v.screen = d_screen;
+    v.screen_meta = d_screen_meta;
+    v.screen_chunks = d_screen ? screen_chunks_for(chunks) : 0u;
     v.n = (uint32_t)n;
     v.entry = entry;
     v.max_level = max_level;
@@ -123,6 +126,11 @@ static bool reserve_locked(Index *ix, size_t newcap)
     const size_t oc = ix->cap, row = (size_t)ix->chunks * 16;
     if(!dev_grow(ix, (void **)&ix->d_vec, oc * row, newcap * row, -1)) return false;
     if(mcode_base(ix->mcode) == M_COS && !mcode_is_i8(ix->mcode) && !dev_grow(ix, (void **)&ix->d_norm2, oc * 4, newcap * 4, -1)) return false;
+    if(ix->screen) {
+        const size_t srow = (size_t)screen_chunks_for(ix->chunks) * 16;
+        if(!dev_grow(ix, (void **)&ix->d_screen, oc * srow, newcap * srow, 0)) return false;
+        if(!dev_grow(ix, (void **)&ix->d_screen_meta, oc * 8, newcap * 8, 0)) return false;
+    }
     if(ix->pq && !dev_grow(ix, (void **)&ix->d_codes, oc * ix->pq_S, newcap * ix->pq_S, 0)) return false;
     if(!dev_grow(ix, (void **)&ix->d_labels, oc * 8, newcap * 8, -1)) return false;
     if(!dev_grow(ix, (void **)&ix->d_levels, oc, newcap, 0)) return false;
@@ -147,10 +155,12 @@ static bool reserve_upper(Index *ix, size_t need_blocks)
     return true;
 }
 
-bool fill_norms(Index *ix, size_t first, size_t count)
+// Every path that writes rows into d_vec ends here: the data derived from the rows follows them (queued on the index stream).
+bool rows_stored(Index *ix, size_t first, size_t count)
 {
-    if(!ix->d_norm2 || count == 0) return true;
-    HIPCHK(ix, launch_fill_norms(ix->mcode, ix->view(), (uint32_t)first, (uint32_t)count, ix->d_norm2, ix->stream));
+    if(count == 0) return true;
+    if(ix->d_norm2) HIPCHK(ix, launch_fill_norms(ix->mcode, ix->view(), (uint32_t)first, (uint32_t)count, ix->d_norm2, ix->stream));
+    if(ix->d_screen) HIPCHK(ix, launch_fill_screen(ix->view(), (uint32_t)first, (uint32_t)count, ix->d_screen, ix->d_screen_meta, ix->stream));
     return true;
 }
 
@@ -885,7 +895,7 @@ static size_t insert_rows(Index *ix, const uint64_t *labels, const int *levels_i
     auto fail_staged = [&]() { if(staged) (void)hipStreamSynchronize(ix->stream); return fail(); };
     if(!up) { set_err(ix, "lantern_gpu: HIP failure uploading vectors"); return fail_staged(); }
     if(!pq_encode_rows(ix, first, count)) return fail_staged();  // pq = true: the rows become their decodings, the codes go beside them
-    if(!fill_norms(ix, first, count)) return fail_staged();
+    if(!rows_stored(ix, first, count)) return fail_staged();
     const size_t done = run_batches(ix, labels, s, count, nullptr, ok_out);
     if(!*ok_out && staged) (void)hipStreamSynchronize(ix->stream);
     return done;
@@ -942,7 +952,7 @@ bool add_sharded_locked(Index *ix, Comm *comm, const uint64_t *labels, const voi
     HIPCHK(ix, hipMemcpyAsync(all_labels.data(), lab_base, total * 8, hipMemcpyDeviceToHost, ix->stream));
     if(!sync_stream(ix, comm)) return false;
     if(!pq_encode_rows(ix, first, total)) return false;  // every rank quantises all rows: deterministic, the replicas stay identical
-    if(!fill_norms(ix, first, total)) return false;  // every rank over all rows: the replicas stay self-contained
+    if(!rows_stored(ix, first, total)) return false;  // every rank over all rows: the replicas stay self-contained
     bool ok = true;
     run_batches(ix, all_labels.data(), s, total, comm, &ok);
     return ok;
@@ -1121,7 +1131,7 @@ bool add_row_sharded_locked(Index *ix, Comm *comm, const uint64_t *labels, const
             for(int r = 0; r < W; ++r) { off[ (size_t)r ] = at * row; cnt[ (size_t)r ] = sh[ r ] * row; at += sh[ r ]; }
             if(!comm->allgatherv_device((char *)ix->d_vec + first * row, off.data(), cnt.data(), ix->stream)) { set_err(ix, comm->err); return false; }
         }
-        if(!fill_norms(ix, first, b)) return false;
+        if(!rows_stored(ix, first, b)) return false;
         // 2. + 3. candidates from every shard's graph AS IT STOOD BEFORE THIS BATCH (a batch's members are invisible to each other, as
         // in a one-GPU batch: every one of a shard's K answers is usable), selection, reverse links
         if(ix->n == 0) {  // "Do nothing for the first element": it only becomes the entry point
@@ -1247,6 +1257,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
         a.undo_cap = vis_undo_cap();
         a.vis_slots = vis_slots;
         a.totals = ix->d_totals;
+        a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
         a.ticket = next_ticket(ix, nq, grid, stream);
         a.done = done;
         a.done_flags = done_flags;
@@ -1329,6 +1340,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
                     a.vis_slots = (uint32_t)words;   // the LDS bitmap (nothing of the slot's HBM slab is touched)
                     a.spec_cache = ne_log2;
                     a.totals = ix->d_totals;
+                    a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
                     a.ticket = next_ticket(ix, nq, grid, stream);
                     a.done = done;
                     a.done_flags = done_flags;
@@ -1408,6 +1420,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
     a.undo_cap = vis_undo_cap();
     a.vis_slots = vis_slots;
     a.totals = ix->d_totals;
+    a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
     a.ticket = next_ticket(ix, nq, grid, stream);
     // (there is no instrumented instantiation of the decoding walk: a compact pq launch ignores phase_profile)
     const bool prof_walk = ix->phase_profile && !pqd;
@@ -1536,7 +1549,7 @@ bool import_graph_locked(Index *ix, size_t size, const void *vectors, const uint
                                hipMemcpyHostToDevice));
     }
     if(ix->pq && !vectors_are_codes && !pq_encode_rows(ix, 0, size)) return false;  // raw f32 rows: quantise them
-    if(!fill_norms(ix, 0, size)) return false;
+    if(!rows_stored(ix, 0, size)) return false;
     ix->labels.resize(size);
     for(size_t i = 0; i < size; ++i) ix->labels[ i ] = labels ? labels[ i ] : (uint64_t)i;
     ix->levels.assign(levels, levels + size);
@@ -1687,6 +1700,11 @@ try {
             return nullptr;
         }
     }
+    // the int8 screen of the f32 l2sq walk: LGPU_SCREEN builds it in, LANTERN_GPU_SCREEN=0 leaves it out at run time
+    {
+        const char *se = std::getenv("LANTERN_GPU_SCREEN");
+        ix->screen = LGPU_SCREEN && ix->mcode == M_L2SQ && !ix->pq && screen_rows_for(ix->chunks) && !(se && std::atoi(se) == 0);
+    }
     return ix;
 }
 LANTERN_ABI_CATCH(e)
@@ -1696,7 +1714,7 @@ try {
     CLEAR(e);
     Index *ix = H(h, e);
     if(!ix) return;
-    void *ptrs[] = { ix->d_vec, ix->d_norm2, ix->d_labels, ix->d_levels, ix->d_nbr0, ix->d_upper_off, ix->d_upper_nbr, ix->d_bitmaps, ix->d_totals, ix->d_tickets,
+    void *ptrs[] = { ix->d_vec, ix->d_norm2, ix->d_screen, ix->d_screen_meta, ix->d_labels, ix->d_levels, ix->d_nbr0, ix->d_upper_off, ix->d_upper_nbr, ix->d_bitmaps, ix->d_totals, ix->d_tickets,
                      ix->d_radius0, ix->d_radius_upper,
                      ix->d_codebook, ix->d_centers, ix->d_codes, ix->d_codes16, ix->d_touched, ix->d_trace, ix->d_trace_count };
     for(void *p : ptrs)
@@ -2942,6 +2960,24 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
+void lantern_gpu_search_screen_stats(usearch_index_t h, uint64_t *logical, uint64_t *exact, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(logical) *logical = 0;
+    if(exact) *exact = 0;
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    unsigned long long t[ 2 ] = {};
+    if(hipDeviceSynchronize() != hipSuccess || hipMemcpy(t, ix->d_totals + 48, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) {
+        FAIL(e, "lantern_gpu: HIP failure reading the screen counters");
+        return;
+    }
+    if(logical) *logical = t[ 0 ];
+    if(exact) *exact = t[ 1 ];
+}
+LANTERN_ABI_CATCH_VOID(e)
+
 float lantern_gpu_last_gather_ms(usearch_index_t h, usearch_error_t *e)
 try {
     CLEAR(e);
@@ -3096,7 +3132,7 @@ try {
     if(row_bytes) *row_bytes = ix->pq_compact ? std::max<size_t>(ix->n, 1) * ix->pq_S16 : (ix->d_vec ? cap * (size_t)ix->chunks * 16 : 0);
     if(other_bytes)
         *other_bytes = cap * ((size_t)ix->M0 * 4 + 8 + 1 + 4 + 4) + ix->upper_cap * ((size_t)ix->M * 4 + 4) + (ix->d_norm2 ? cap * 4 : 0) +
-                       (ix->pq ? cap * (size_t)ix->pq_S : 0);
+                       (ix->pq ? cap * (size_t)ix->pq_S : 0) + (ix->d_screen ? cap * ((size_t)screen_chunks_for(ix->chunks) * 16 + 8) : 0);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

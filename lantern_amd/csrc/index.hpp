@@ -74,6 +74,11 @@ struct Index
     // ---- HBM ---------------------------------------------------------------------------------------
     uint4    *d_vec = nullptr;
     float    *d_norm2 = nullptr;  // ||row||^2 per stored row, cosine metrics only (device_common.hpp "cached row norms")
+    // the int8 SCREEN copy of every row (f32 l2sq rows of >= 128 chunks; walk.hpp hop_distances_screened): derived data, filled
+    // wherever rows enter d_vec (rows_stored), never serialised.  screen = false (LANTERN_GPU_SCREEN=0, or another kind): not allocated
+    bool      screen = false;
+    uint4    *d_screen = nullptr;       // [cap][screen_chunks_for(chunks)]
+    float2   *d_screen_meta = nullptr;  // [cap] (s, r)
     uint64_t *d_labels = nullptr;
     uint8_t  *d_levels = nullptr;
     uint32_t *d_nbr0 = nullptr;
@@ -207,7 +212,7 @@ bool        pq_encode_rows(Index *ix, size_t first, size_t count);  // raw f32 r
 bool        pq_decode_rows(Index *ix, size_t first, size_t count);  // d_codes -> d_vec
 bool        pq_compact_locked(Index *ix);  // drop the decodings, keep the codes (searches: ADC)
 bool        pq_expand_locked(Index *ix);   // decode them back (no-op unless compact)
-bool        fill_norms(Index *ix, size_t first, size_t count);  // after rows [first, first + count) are in d_vec
+bool        rows_stored(Index *ix, size_t first, size_t count);  // after rows [first, first + count) are in d_vec: their norms, their screen
 void       *scratch(Index *ix, int which, size_t bytes);
 bool        pad_row(const Index *ix, const void *vec, int kind_in, uint32_t *dst);
 size_t      input_bytes(const Index *ix, int kind_in);

@@ -9,6 +9,7 @@
 //                   (all-pairs table, rows in registers, chain form), k_revlink_staged (rows staged whole in LDS),
 //                   k_revlink (rows read from L2: lists longer than 32 entries, rows beyond 2048 f32 dims).
 //   k_fill_norms    sqrt(||row||^2) of newly stored rows for the cosine metrics (device_common.hpp).
+//   k_fill_screen   the int8 screen copy of newly stored f32 l2sq rows (walk.hpp hop_distances_screened).
 //   k_apply_own_links / k_pack_lists / k_apply_lists
 //                   scatter kernels either side of the all-gathers of the work-sharded build (comm.cpp).
 //   k_gather        metric(query, row[slots[i]]) -- the distance kernel on its own (tests, profiling).
@@ -897,6 +898,70 @@ __global__ void __launch_bounds__(256) k_fill_norms(View v, uint32_t first, uint
     }
 }
 
+// k_fill_screen: the int8 SCREEN copy of the f32 l2sq rows [first, first + count) -- once, when the rows enter the index (walk.hpp
+// hop_distances_screened).  One wave per row: s = max |y_i| / 127 (f32), q_i = rint(y_i / s) clamped to [-127, 127], and
+// r = ||y - y'|| over exactly the f32 values the walk reconstructs (screen_val), summed in double and rounded UP into f32.  A row
+// with a non-finite value, or whose s is 0, subnormal or not finite, gets q = 0 and r = +inf: the walk then never rejects it.
+__global__ void __launch_bounds__(256) k_fill_screen(View v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+    const uint32_t chunks = v.chunks, sch = screen_chunks_for(chunks);
+    for(uint32_t i = wid; i < count; i += nw) {
+        const uint32_t slot = first + i;
+        const uint4   *row = row_of(v, slot);
+        float          mx = 0.f;
+        int            bad = 0;
+        for(uint32_t c = lane; c < chunks; c += 64) {
+            const uint4 x = row[ c ];
+            const float f[ 4 ] = { __uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w) };
+#pragma unroll
+            for(int b = 0; b < 4; ++b) {
+                bad |= !__builtin_isfinite(f[ b ]);
+                mx = fmaxf(mx, fabsf(f[ b ]));
+            }
+        }
+        for(int off = 32; off > 0; off >>= 1) {
+            mx = fmaxf(mx, __shfl_xor(mx, off));
+            bad |= __shfl_xor(bad, off);
+        }
+        float      sc = mx / 127.f;
+        const bool ok = !bad && __builtin_isfinite(sc) && sc >= 0x1p-126f;
+        if(!ok) sc = 0.f;
+        double r2 = 0.0;
+        for(uint32_t c = lane; c < sch; c += 64) {
+            uint32_t w[ 4 ] = { 0u, 0u, 0u, 0u };
+#pragma unroll
+            for(int k = 0; k < 4; ++k) {
+                const uint32_t qc = 4 * c + (uint32_t)k;
+                if(qc >= chunks) continue;  // beyond the f32 row: zeros
+                const uint4 x = row[ qc ];
+                const float f[ 4 ] = { __uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w) };
+#pragma unroll
+                for(int b = 0; b < 4; ++b) {
+                    int q = 0;
+                    if(ok) q = (int)fminf(127.f, fmaxf(-127.f, rintf(f[ b ] / sc)));
+                    w[ k ] |= ((uint32_t)q & 255u) << (8 * b);
+                    const double dd = (double)f[ b ] - (double)screen_val(sc, w[ k ], b);  // exact: two f32 values of like magnitude, or y' = 0
+                    r2 = r2 + dd * dd;
+                }
+            }
+            screen[ (size_t)slot * sch + c ] = make_uint4(w[ 0 ], w[ 1 ], w[ 2 ], w[ 3 ]);
+        }
+        for(int off = 32; off > 0; off >>= 1) r2 = r2 + __shfl_xor(r2, off);
+        if(lane == 0) {
+            float r = __builtin_inff();
+            if(ok) {
+                const double rr = sqrt(r2 * (1.0 + 0x1p-40));  // (the margin covers the rounding of the double sum and sqrt)
+                r = (float)rr;
+                if((double)r < rr) r = nextafterf(r, __builtin_inff());
+                if(!__builtin_isfinite(r)) r = __builtin_inff();
+            }
+            meta[ slot ] = make_float2(sc, r);
+        }
+    }
+}
+
 template <int METRIC, int G>
 __global__ void __launch_bounds__(256) k_gather(View v, const uint4 *query, const uint32_t *slots, uint32_t n, float *out)
 {
@@ -1076,6 +1141,15 @@ hipError_t launch_fill_norms(int metric, const View &v, uint32_t first, uint32_t
     if(metric == M_COS) FNG(M_COS) else FNG(M_COS_F16)
 #undef FNG
 #undef FN
+    return hipGetLastError();
+}
+
+hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, hipStream_t stream)
+{
+    if(count == 0) return hipSuccess;
+    uint32_t blocks = (count + 3) / 4;  // four rows (waves) per block
+    if(blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(k_fill_screen, dim3(blocks), dim3(256), 0, stream, v, first, count, screen, meta);
     return hipGetLastError();
 }
 

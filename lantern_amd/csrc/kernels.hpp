@@ -57,6 +57,8 @@ struct SearchArgs
     uint32_t       *trace;       // diagnostics (lantern_gpu_search_row_trace; the instrumented instantiations only): [nq][trace_cap] the
     uint32_t       *trace_count; // memory objects every query asks for, in order (walk.hpp trace_append), and [nq] how many; NULL = off
     uint32_t        trace_cap;
+    unsigned long long *screen_totals;  // [2] cumulative row evaluations and how many of them read the f32 row (the int8 screen:
+                                        // lantern_gpu_search_screen_stats) of the launches whose view has a screen, or NULL
 };                               // launch's queries by phase: pop | list + visited | distances | merge | descent | whole query
 
 // one reverse-link request produced by the insert pass: add `new_slot` to `close`'s list at `level`
@@ -215,6 +217,8 @@ hipError_t launch_store_quantised(const float *src, uint32_t dims, uint32_t coun
 
 // ||row||^2 of rows [first, first + count) into norm2 (cosine metrics only; no-op otherwise)
 hipError_t launch_fill_norms(int metric, const View &v, uint32_t first, uint32_t count, float *norm2, hipStream_t stream);
+// the int8 screen rows and (s, r) of the f32 rows [first, first + count) (walk.hpp hop_distances_screened)
+hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, hipStream_t stream);
 // out[i] = metric(query, row(slots[i]))
 hipError_t launch_gather(int metric, const View &v, const uint4 *query, const uint32_t *slots, uint32_t n, float *out,
                          hipStream_t stream);

@@ -86,6 +86,8 @@ k_search(SearchArgs)
         if constexpr(SPEC != 0) carve_spec(end, sc, LGPU_VIEW_ARG(ka, SearchArgs, M0), LGPU_SEARCH_ARG(ka, spec_prefetch), LGPU_SEARCH_ARG(ka, spec_cache), SPEC == 3 ? 1u : 0u);
         else (void)end;
     }
+    // the int8 screen of the f32 l2sq walk over rows of >= 128 chunks (walk.hpp hop_distances_screened); used iff the view has one
+    constexpr bool SCREEN = LGPU_SCREEN && METRIC == M_L2SQ && G == 64 && !PROF && SPEC == 0 && KPL > 0;
     for(uint32_t q = blockIdx.x; q < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
         uint32_t D = 0, E = 0;
         int      cnt = 0;
@@ -95,6 +97,14 @@ k_search(SearchArgs)
             View               v;
             LGPU_LOAD_VIEW(v, ka, SearchArgs)
             if constexpr(METRIC >= M_PQD) LGPU_LOAD_VIEW_PQD(v, ka, SearchArgs)
+            if constexpr(SCREEN) {  // (walk.hpp S_SCREEN: the screen's tables, and the count of rows it rejects, live in LDS)
+                if(tid == 0) {
+                    uint64_t *const sp = (uint64_t *)&s.scal[ S_SCREEN ];
+                    sp[ 0 ] = (uint64_t)LGPU_VIEW_ARG(ka, SearchArgs, screen);
+                    sp[ 1 ] = (uint64_t)LGPU_VIEW_ARG(ka, SearchArgs, screen_meta);
+                    s.scal[ S_NREJ ] = 0;
+                }
+            }
             const uint32_t chunks = v.chunks, bm_words = LGPU_SEARCH_ARG(ka, bm_words);
             uint32_t      *bitmap = LGPU_SEARCH_ARG(ka, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
             s.undo = bitmap + bm_words;
@@ -133,7 +143,7 @@ k_search(SearchArgs)
                 if constexpr(SPEC != 0)
                     cnt = search_level_spec<METRIC, G, KPL, ROWS, (G == 64 && SPEC == 2 ? 3 : 2), SPEC == 2, PROF>(v, s, sc, bitmap, bm_words, start, ef, D, E,
                                                                                                                      PROF ? LGPU_SEARCH_ARG(ka, phase_cycles) : nullptr);
-                else if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL, PROF, ROWS>(v, s, bitmap, bm_words, start, 0, ef, D, E, pc);
+                else if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL, PROF, ROWS, SCREEN>(v, s, bitmap, bm_words, start, 0, ef, D, E, pc);
                 else cnt = search_level<METRIC, G, PROF, ROWS>(v, s, bitmap, bm_words, start, 0, ef, D, E, pc);
             }
         }
@@ -176,6 +186,10 @@ k_search(SearchArgs)
             if(out_D) out_D[ q ] = D;
             if(out_E) out_E[ q ] = E;
             if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
+            if constexpr(SCREEN) {
+                unsigned long long *const st = LGPU_SEARCH_ARG(kb, screen_totals);
+                if(st) { atomicAdd(&st[ 0 ], (unsigned long long)D); atomicAdd(&st[ 1 ], (unsigned long long)(D - (uint32_t)s.scal[ S_NREJ ])); }
+            }
             // next query: a ticket (walks differ in length by 2x; static striding leaves workgroups idle at the end)
             s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(q + gridDim.x);
         }

@@ -28,7 +28,11 @@ namespace lgpu {
 enum { S_POS = 0, S_NNEW, S_CNT, S_ANY, S_BAD, S_CUR, S_CURD, S_CHANGED, S_VISCNT, S_SPILL, S_QN2, S_NNEW0, S_NNEW1, S_ANY0, S_ANY1,
        S_FRONT = 16, S_WORST = 20,  // two u64 each (by hop parity): search_level_reg's hand-off from the list wave to the visit wave
        S_MASK = 24,                 // two u64 (by hop parity): walk_spec.hpp's "which neighbours of the hop were new"
-       S_SCALARS = 28 };
+       S_SCALARS = 28,
+       // search_level_reg's int8 screen, in slots that walk leaves alone: the screened hop's survivor count, the walk's rejected rows,
+       // and (set by k_search before the walk) two u64: View::screen and View::screen_meta -- in LDS rather than in scalar registers,
+       // which the hop loop has none of to spare
+       S_NSURV = S_ANY0, S_NREJ = S_ANY1, S_SCREEN = S_MASK };
 // S_QN2: ||query||^2 as float bits (cosine metrics; set by the kernel before a walk: device_common.hpp "cached row norms")
 
 struct WalkLds
@@ -37,7 +41,7 @@ struct WalkLds
     uint64_t *keys;     // current list   (ef_cap)
     uint64_t *keys2;    // merge target   (ef_cap)
     uint64_t *newkeys;  // keys of this hop's new neighbours (cap_max)
-    uint64_t *sorted;   // the same, sorted                  (cap_max)
+    uint64_t *sorted;   // the same, sorted                  (cap_max); search_level_reg: the screened hop's survivors (u32)
     uint32_t *newids;   // unvisited neighbour slots         (cap_max)
     int      *scal;     // S_* scalars
     uint32_t *vis;      // visited hash set (vis_slots entries, any multiple of 4; 0 = the HBM bitmap only)
@@ -384,11 +388,16 @@ __device__ uint32_t greedy_descent(const View &v, WalkLds &s, uint32_t start, in
 // neighbour list's arrival, [0] visited filter + compaction (together: wave 0's section) | [1] wait at the first barrier |
 // [2] distances | [3] merge.
 // One hop's distance phase: keys of the nnew unvisited neighbours in s.newids -> s.newkeys.  One G-lane group per row, ROWS rows in
-// flight per group.  ANY: also raise *any_slot when a key beats `worst` (the LDS-list walk skips its merge otherwise).
-template <int METRIC, int G, int ROWS, bool ANY>
-__device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nnew, float qn2, uint64_t worst, int *any_slot)
+// flight per group.  ANY: also raise *any_slot when a key beats `worst` (the LDS-list walk skips its merge otherwise).  SEL: evaluate
+// only the nnew entries sel[0..nnew) name (positions in s.newids / s.newkeys: the survivors of the int8 screen), all when sel is NULL.
+template <int METRIC, int G, int ROWS, bool ANY, bool SEL = false>
+__device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nnew, float qn2, uint64_t worst, int *any_slot,
+                                              const uint32_t *sel = nullptr)
 {
     const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
+    auto at = [&](int j) { if constexpr(SEL) return sel ? (int)sel[ j ] : j; else return j; };
+    // SEL: the positions are read again for the stores rather than kept live across the row loads (the walk has no VGPR to spare)
+    auto reread = [&]() { if constexpr(SEL) asm volatile("" ::: "memory"); };
     if constexpr(ROWS > 2) {
         for(int i = g; i < nnew; i += ROWS * NG) {
             decltype(row_of_m<METRIC>(v, 0u)) rows[ ROWS ];
@@ -397,19 +406,20 @@ __device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nne
 #pragma unroll
             for(int r = 0; r < ROWS; ++r) {
                 const int j = i + r * NG;
-                ids[ r ] = s.newids[ j < nnew ? j : i ];
+                ids[ r ] = s.newids[ at(j < nnew ? j : i) ];
                 rows[ r ] = row_of_m<METRIC>(v, ids[ r ]);
                 n2[ r ] = row_norm<METRIC>(v, ids[ r ]);
             }
             group_distR_n<METRIC, G, ROWS>(walk_query<METRIC>(s), rows, (int)v.chunks, gl, qn2, n2, d);
             if(gl == G - 1) {
                 bool any = false;
+                reread();
 #pragma unroll
                 for(int r = 0; r < ROWS; ++r) {
                     const int j = i + r * NG;
                     if(j < nnew) {
                         const uint64_t k = make_key(d[ r ], ids[ r ]);
-                        s.newkeys[ j ] = k;
+                        s.newkeys[ at(j) ] = k;
                         any |= k < worst;
                     }
                 }
@@ -419,23 +429,94 @@ __device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nne
     } else
     for(int i = g; i < nnew; i += 2 * NG) {
         const int      j = i + NG;
-        const uint32_t id0 = s.newids[ i ];
-        const uint32_t id1 = j < nnew ? s.newids[ j ] : id0;
+        const uint32_t id0 = s.newids[ at(i) ];
+        const uint32_t id1 = j < nnew ? s.newids[ at(j) ] : id0;
         float          d0, d1;
         group_dist2_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, id0), row_of_m<METRIC>(v, id1), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, id0),
                                  row_norm<METRIC>(v, id1), d0, d1);
         if(gl == G - 1) {
+            reread();
             uint64_t k0 = make_key(d0, id0);
-            s.newkeys[ i ] = k0;
+            s.newkeys[ at(i) ] = k0;
             bool any = k0 < worst;
             if(j < nnew) {
                 uint64_t k1 = make_key(d1, id1);
-                s.newkeys[ j ] = k1;
+                s.newkeys[ at(j) ] = k1;
                 any |= k1 < worst;
             }
             if(ANY && any) *any_slot = 1;
         }
     }
+}
+
+// ---- the int8 screen -------------------------------------------------------------------------------------
+// The distance phase of a hop of an f32 l2sq walk whose list is full (radius = the key `worst`): most new rows land outside
+// the radius and are read only to be thrown away.  So first every new row's distance is BOUNDED from below on its int8 screen
+// copy y' = s * q (a quarter of the bytes; View::screen), and only the rows the bound cannot reject pay for the f32 row.
+//   d' = sum (x_i - y'_i)^2 in f32 (any order: every term is >= 0, so the relative error is at most (terms + tree) ulps),
+//   r  >= ||y - y'|| (k_fill_screen: in double, rounded up; +inf for rows with non-finite values or a zero / subnormal scale),
+//   ||x - y|| >= ||x - y'|| - r  (triangle inequality), so  LB = max(0, sqrt(d') (1 - e) - r)^2 <= ||x - y||^2,
+// and the device's f32 distance d of the row is within (1 - e) of its exact value, e = max(2^-12, (2 chunks + 64) 2^-24) being
+// far above the rounding of either sum.  A row is rejected iff LB (1 - e) > dist(worst) -- strictly, and a NaN anywhere fails the
+// test -- so a rejected row's d is strictly above the radius: its exact key could not have entered the list, and since the
+// radius only shrinks it never can.  Its key becomes ~0 (above every radius: the visit wave's choice and the list wave's merge
+// skip it, as they would skip the exact key).  Survivors get the exact evaluation of hop_distances, same chain, same tree, same
+// bits (the caller runs it over the survivors, s.sorted[0..ns), ns returned).
+template <int G, int ROWS>
+__device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s, int nnew, uint64_t worst)
+{
+    constexpr int GS = G / 4 >= 8 ? G / 4 : 8;  // lanes per screen row (a quarter of the bytes of the f32 row)
+    const int       tid = threadIdx.x, T = blockDim.x, gs = tid / GS, gsl = tid % GS, NGS = T / GS;
+    uint32_t *const surv = (uint32_t *)s.sorted;
+    const uint4    *screen = ((const uint4 *const *)&s.scal[ S_SCREEN ])[ 0 ];
+    const float2   *screen_meta = ((const float2 *const *)&s.scal[ S_SCREEN ])[ 1 ];
+    const uint32_t  chunks = v.chunks, sch = screen_chunks_for(chunks);
+    const float     rd = key_dist(worst);
+    const float     ome = 1.f - fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
+    for(int j = gs; j < nnew; j += NGS) {
+        const uint32_t id = s.newids[ j ];
+        const uint4   *row = screen + (size_t)id * sch;
+        const float2   meta = screen_meta[ id ];
+        float          acc = 0.f;
+        constexpr int  B = 2;  // the loads of two steps in flight together
+        for(uint32_t base = (uint32_t)gsl; base < sch; base += B * GS) {
+            uint4 y[ B ];
+#pragma unroll
+            for(int c = 0; c < B; ++c)
+                if(base + c * GS < sch) y[ c ] = row[ base + c * GS ];
+#pragma unroll
+            for(int c = 0; c < B; ++c)
+                if(base + c * GS < sch) {
+                    const uint32_t w[ 4 ] = { y[ c ].x, y[ c ].y, y[ c ].z, y[ c ].w };
+#pragma unroll
+                    for(int k = 0; k < 4; ++k) {  // screen word k covers query chunk 4 (base + c GS) + k (beyond the row: zeros)
+                        const uint32_t qc = 4 * (base + c * GS) + (uint32_t)k;
+                        const uint4    x = qc < chunks ? s.q[ qc ] : make_uint4(0u, 0u, 0u, 0u);
+                        const float    xs[ 4 ] = { __uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w) };
+#pragma unroll
+                        for(int b = 0; b < 4; ++b) {
+                            const float t = xs[ b ] - screen_val(meta.x, w[ k ], b);
+                            acc = __builtin_fmaf(t, t, acc);
+                        }
+                    }
+                }
+        }
+        acc = group_sum<GS>(acc);
+        if(gsl == GS - 1) {
+            bool reject = false;
+            if(__builtin_isfinite(acc)) {
+                const float a = __builtin_sqrtf(acc) * ome - meta.y;
+                const float lb = a > 0.f ? a * a : 0.f;
+                reject = lb > 0x1p-100f && lb * ome > rd;  // (lb > 2^-100: far above what underflow can take from either sum)
+            }
+            if(reject) s.newkeys[ j ] = ~0ull;
+            else surv[ atomicAdd(&s.scal[ S_NSURV ], 1) ] = (uint32_t)j;
+        }
+    }
+    __syncthreads();
+    const int ns = s.scal[ S_NSURV ];
+    if(tid == 0) s.scal[ S_NREJ ] += nnew - ns;
+    return ns;
 }
 
 template <int METRIC, int G, bool PROF = false, int ROWS = 2>
@@ -607,10 +688,15 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l)  // l uniform
             tl = t_;                                                  \
         }                                                             \
     }
-template <int METRIC, int G, int KPL, bool PROF = false, int ROWS = 2>
+// SCREEN (k_search over f32 l2sq rows of >= 128 chunks, never the instrumented walk): level 0 of a split walk whose screen pointer
+// (s.scal[S_SCREEN]) is set runs the hops whose list is full through hop_distances_screened, counting the rows it rejected in
+// s.scal[S_NREJ].
+template <int METRIC, int G, int KPL, bool PROF = false, int ROWS = 2, bool SCREEN = false>
 __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uint32_t bm_words, uint32_t start, int level, int ef,
                                 uint32_t &D, uint32_t &E, unsigned long long *prof = nullptr)
 {
+    static_assert(!SCREEN || (METRIC == M_L2SQ && !PROF), "the screen serves the f32 l2sq walk");
+
     const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G;
     const int lane = tid & 63;
     // Wave roles, as values the compiler KNOWS are wave-uniform (the serial sections then run under uniform control flow: no
@@ -626,6 +712,7 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
     const int  wv = __builtin_amdgcn_readfirstlane(tid) >> 6;
     const bool split = T >= 128;
     const bool visit_wave = wv == 0, list_wave = split ? wv == 1 : wv == 0;  // (which second wave makes no difference: measured)
+    const bool screen_on = SCREEN && split && level == 0 && ((const uint64_t *)&s.scal[ S_SCREEN ])[ 0 ] != 0;  // (the radius is published in the split form only)
     // [r6] Speculative fetch of the FRONT's neighbour list.  The node a hop expands is min(front, best new key of the previous hop); the
     // front is published before the previous hop's distances are even requested, and it IS the next node in 88 % of the hops on
     // clustered data (49 % on i.i.d. Gaussian: scripts/experiments/front_hit_rate.py).  So the visit wave requests the front's list
@@ -807,7 +894,10 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
                     nb_new += __popcll(m);
                 }
                 if(s.vis_slots && !spilled) viscnt += (uint32_t)nb_new;
-                if(lane == 0) *nnew_slot = nb_new;
+                if(lane == 0) {
+                    *nnew_slot = nb_new;
+                    if(SCREEN) s.scal[ S_NSURV ] = 0;  // (the previous hop's survivors were read before the barrier behind its distances)
+                }
             }
         }
         LGPU_MARK(0)
@@ -822,7 +912,15 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
             if(pf_node != EMPTY) pf_nb = (uint32_t)lane < v.M0 ? v.nbr0[ (size_t)pf_node * v.M0 + (uint32_t)lane ] : EMPTY;
         }
         if(nnew == 0) continue;
-        hop_distances<METRIC, G, ROWS, false>(v, s, nnew, qn2, ~0ull, nullptr);
+        // the radius the list wave published before the barrier (~0: the list is not full, nothing can be rejected)
+        if constexpr(SCREEN) {  // one copy of the exact phase: over the screen's survivors, or over all rows
+            const uint64_t radius = screen_on ? worst_pub[ par ^ 1 ] : ~0ull;
+            int            ne = nnew;
+            if(radius != ~0ull) ne = hop_distances_screened<G, ROWS>(v, s, nnew, radius);
+            hop_distances<METRIC, G, ROWS, false, true>(v, s, ne, qn2, ~0ull, nullptr, radius != ~0ull ? (const uint32_t *)s.sorted : nullptr);
+        } else {
+            hop_distances<METRIC, G, ROWS, false>(v, s, nnew, qn2, ~0ull, nullptr);
+        }
         D += (uint32_t)nnew;
         __syncthreads();
         LGPU_MARK(2)
