@@ -342,7 +342,10 @@ LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_
 
 /* Exact k-NN over the index's vectors (the seq-scan `ORDER BY v <op> q LIMIT k`; ground truth
  * for recall, index_autotune/mod.rs:196-203).  Host buffers; slots: nq x k ascending by
- * (distance, slot). */
+ * (distance, slot).  Guarantee: per query the k smallest rows by (exact-order distance, slot) -- the distance in the pair
+ * kernel's reduction order (usearch_distance's bits) -- identical to a brute force in that order.  The fp32-MFMA
+ * pre-selection is certified per query and a query it cannot certify is recomputed in exact order (DESIGN.md 4.5;
+ * lantern_gpu_exact_knn_stats).  k <= 240. */
 LANTERN_GPU_EXPORT void lantern_gpu_exact_search(usearch_index_t, const void *queries, size_t nq, size_t k,
                                                  uint32_t *slots, float *distances, usearch_error_t *);
 
@@ -351,6 +354,10 @@ LANTERN_GPU_EXPORT void lantern_gpu_exact_search(usearch_index_t, const void *qu
  * `cap` records -- ms[i], rows[i] x cols[i] (queries x base rows of the launch), fused[i] (1: the launch with the fused top-k
  * epilogue) -- and returns how many launches were recorded.  Process-wide; any pointer may be NULL. */
 LANTERN_GPU_EXPORT size_t lantern_gpu_dense_profile(int on, float *ms, uint32_t *rows, uint32_t *cols, uint32_t *fused, size_t cap);
+/* Process-wide counters of the exact k-NN (lantern_gpu_exact_search, _assign_to_clusters, PQ encoding), cumulative: queries
+ * answered, how many of them the MFMA pre-selection's certificate passed, and how many took the exact-order fallback
+ * (queries = certified + fallback).  Any pointer may be NULL. */
+LANTERN_GPU_EXPORT void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t *certified, uint64_t *fallback);
 
 /* Diagnostic for the measurement harness: the memory objects every query of a launch asks for, in order (rows evaluated, adjacency
  * lists read) -- the input of the cache model behind bench.py's roofline.frac_dram_model (lantern_amd/tools/cache_model.c).
@@ -383,7 +390,9 @@ LANTERN_GPU_EXPORT void lantern_gpu_distance_matrix(const void *a, size_t na, co
 /* PQ k-means assignment, product_quantization.c:80-124 (assign_to_clusters): for every row i of `dataset`
  * (n rows of row_dims f32) the nearest of k centroids under `metric` over the subvector
  * [subvector_start, subvector_start + subvector_dim); the first minimum wins, as in the reference's
- * strict-< loop.  centers: k x subvector_dim f32.  out_distance may be NULL.  cos / l2sq only. */
+ * strict-< loop.  centers: k x subvector_dim f32.  out_distance may be NULL.  cos / l2sq only.
+ * Guarantee: the smallest centroid by (exact-order distance, index), identical to that loop over usearch_distance -- the
+ * exact k-NN with k = 1, certified or recomputed in exact order per row (lantern_gpu_exact_search). */
 LANTERN_GPU_EXPORT void lantern_gpu_assign_to_clusters(const float *dataset, size_t n, size_t row_dims, size_t subvector_start,
                                                        size_t subvector_dim, const float *centers, size_t k,
                                                        usearch_metric_kind_t metric, uint32_t *out_cluster,

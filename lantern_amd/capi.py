@@ -86,7 +86,7 @@ EXPORTS = [
     "lantern_gpu_version", "lantern_gpu_device_count",
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
-    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_distance_gather",
+    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_distance_gather",
     "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
     "lantern_gpu_export_codes",
@@ -181,6 +181,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_set_search_shape": (None, [vp, i32, i32, err]),
         "lantern_gpu_exact_search": (None, [vp, vp, sz, sz, vp, vp, err]),
         "lantern_gpu_dense_profile": (sz, [i32, vp, vp, vp, vp, sz]),
+        "lantern_gpu_exact_knn_stats": (None, [C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "lantern_gpu_distance_gather": (None, [vp, vp, vp, sz, vp, err]),
         "lantern_gpu_spec_profile": (None, [vp, i32, vp, err]),
         "lantern_gpu_search_unique_rows": (None, [vp, i32, C.POINTER(u64), err]),
@@ -370,6 +371,13 @@ def dense_profile(on: bool):
     ms, rows, cols, fused = np.zeros(cap, np.float32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
     n = min(int(lib().lantern_gpu_dense_profile(0, _ptr(ms), _ptr(rows), _ptr(cols), _ptr(fused), cap)), cap)
     return [{"ms": float(ms[i]), "rows": int(rows[i]), "cols": int(cols[i]), "fused": bool(fused[i])} for i in range(n)]
+
+
+def exact_knn_stats():
+    """lantern_gpu_exact_knn_stats: process-wide {queries, certified, fallback} of the exact k-NN (cumulative)."""
+    q, c, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib().lantern_gpu_exact_knn_stats(C.byref(q), C.byref(c), C.byref(f))
+    return {"queries": int(q.value), "certified": int(c.value), "fallback": int(f.value)}
 
 
 def l2sq_dist(a, b) -> float:

@@ -12,6 +12,8 @@
 //   k_select       per query: merge a chunk of the distance matrix into a running top-k'
 //   k_rerank       recompute the k' survivors in the graph walk's exact reduction order and emit
 //                  the final top-k by (distance, slot)
+//   k_certify      per query: do the k' survivors provably hold the exact top-k?  (the queries it
+//                  refuses are recomputed in exact order: k_gather_rows, k_pairs + k_select, k_emit_topk)
 #include "kernels.hpp"
 #include "walk.hpp"
 
@@ -534,6 +536,96 @@ __global__ void __launch_bounds__(256) k_rerank(const uint4 *Q, const uint4 *B, 
         out_slots[ (size_t)q * k + i ] = key == ~0ull ? EMPTY : (uint32_t)(key & 0xFFFFFFFFu);
         out_dists[ (size_t)q * k + i ] = key == ~0ull ? __builtin_inff() : ord2f((uint32_t)(key >> 32));
     }
+}
+
+// k_certify: did the MFMA pre-selection provably hold every row of the exact answer?  One thread per query:
+// tau = the kk-th MFMA key (every row outside the survivors has a contraction distance >= tau), Dk = the re-ranked k-th
+// exact-order distance.  A row whose exact-order distance is <= Dk has a contraction distance <= bound(q, Dk); the query is
+// certified when tau > bound, strictly.  Bounds in double from the f32 inputs, with the constants of DESIGN.md 4.5:
+//   g(n) = n u / (1 - n u), u = 2^-24, d = f32 scalars contracted (padding included)
+//   l2sq: |q| <= qa = sqrt(qn / (1 - g(d + 8))), delta <= dup = Dk / (1 - g(d + 8)), |b| <= qa + sqrt(dup),
+//         bound = dup + g(d + 8) (qa + |b|)^2 + 4 (d + 8) 2^-126;  refused when (qa + |b|)^2 >= 2^120 (no overflow anywhere)
+//   cos:  bound = Dk + 2 g(2 d + 16) + 2^-100;  refused unless every nonzero norm^2 (query and rows) is in [2^-60, 2^60]
+// flag[q] = 1: certified.  The extra threads of the grid scan the row norms (cosine) and raise flag[nq] when one is out of range.
+__global__ void __launch_bounds__(256) k_certify(int cosine, const uint64_t *best, uint32_t kk, const float *dists, uint32_t k, const float *qn,
+                                                 uint32_t nq, const float *bn, uint32_t nb, uint32_t dims, uint32_t *flag)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    auto           in_range = [](float v) { return v == 0.f || (v >= 0x1p-60f && v <= 0x1p60f); };
+    if(cosine) {
+        bool bad = false;
+        for(uint32_t i = t; i < nb; i += gridDim.x * blockDim.x) bad |= !in_range(bn[ i ]);
+        if(bad) atomicOr(&flag[ nq ], 1u);
+    }
+    if(t >= nq) return;
+    const uint64_t tk = best[ (size_t)t * kk + kk - 1 ];
+    if(tk == ~0ull) {  // fewer than kk rows: every row is a survivor
+        flag[ t ] = 1u;
+        return;
+    }
+    const double tau = (double)ord2f((uint32_t)(tk >> 32)), Dk = (double)dists[ (size_t)t * k + k - 1 ], q2 = (double)qn[ t ];
+    const double u = 0x1p-24;
+    auto         g = [&](double n) { return n * u / (1.0 - n * u); };
+    bool         ok = q2 >= 0.0 && q2 < 0x1p120 && tau == tau && (double)dims * 2.0 + 16.0 < 0x1p20;
+    double       bound = 0.0;
+    if(ok && cosine) {
+        ok = in_range(qn[ t ]) && Dk >= -1.0 && Dk <= 3.0;  // (an exact-order cosine distance may be a little below 0)
+        bound = Dk + 2.0 * g(2.0 * dims + 16.0) + 0x1p-100;
+    } else if(ok && Dk >= 0.0 && Dk < 0x1p120) {
+        const double gd = g(dims + 8.0), qa = sqrt(q2 / (1.0 - gd)), dup = Dk / (1.0 - gd), s = 2.0 * qa + sqrt(dup);
+        ok = s * s < 0x1p120;
+        bound = dup + gd * s * s + 4.0 * (dims + 8.0) * 0x1p-126;
+    } else {
+        ok = false;
+    }
+    flag[ t ] = ok && tau > bound * (1.0 + 0x1p-40) ? 1u : 0u;
+}
+
+hipError_t launch_certify(int metric, const uint64_t *best, uint32_t kk, const float *dists, uint32_t k, const float *qn, uint32_t nq, const float *bn,
+                          uint32_t nb, uint32_t dims, uint32_t *flag, hipStream_t stream)
+{
+    if(nq == 0) return hipSuccess;
+    const int cosine = metric == M_COS ? 1 : 0;
+    uint32_t  blocks = (nq + 255) / 256;
+    if(cosine) blocks = std::max(blocks, std::min<uint32_t>((nb + 4095) / 4096, 1024u));  // (the norm scan: ~16 rows per thread)
+    hipLaunchKernelGGL(k_certify, dim3(blocks), dim3(256), 0, stream, cosine, best, kk, dists, k, qn, nq, bn, nb, dims, flag);
+    return hipGetLastError();
+}
+
+// the exact k-NN's fallback for the queries the certificate refused: their rows gathered, and their exact-order top-k keys
+// (k_select over k_pairs) written back to the caller's rows
+__global__ void __launch_bounds__(256) k_gather_rows(const uint4 *src, uint32_t chunks, const uint32_t *idx, uint32_t n, uint4 *dst)
+{
+    const size_t total = (size_t)n * chunks;
+    for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        dst[ i ] = src[ (size_t)idx[ i / chunks ] * chunks + i % chunks ];
+}
+
+__global__ void __launch_bounds__(256) k_emit_topk(const uint64_t *best, uint32_t k, const uint32_t *idx, uint32_t n, uint32_t *out_slots, float *out_dists)
+{
+    const size_t total = (size_t)n * k;
+    for(size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const uint64_t key = best[ i ];
+        const size_t   at = (size_t)idx[ i / k ] * k + i % k;
+        out_slots[ at ] = key == ~0ull ? EMPTY : (uint32_t)(key & 0xFFFFFFFFu);
+        out_dists[ at ] = key == ~0ull ? __builtin_inff() : ord2f((uint32_t)(key >> 32));
+    }
+}
+
+hipError_t launch_gather_rows(const uint4 *src, uint32_t chunks, const uint32_t *idx, uint32_t n, uint4 *dst, hipStream_t stream)
+{
+    if(n == 0) return hipSuccess;
+    const size_t blocks = std::min<size_t>(((size_t)n * chunks + 255) / 256, 16384);
+    hipLaunchKernelGGL(k_gather_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, src, chunks, idx, n, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_emit_topk(const uint64_t *best, uint32_t k, const uint32_t *idx, uint32_t n, uint32_t *out_slots, float *out_dists, hipStream_t stream)
+{
+    if(n == 0) return hipSuccess;
+    const size_t blocks = std::min<size_t>(((size_t)n * k + 255) / 256, 16384);
+    hipLaunchKernelGGL(k_emit_topk, dim3((uint32_t)blocks), dim3(256), 0, stream, best, k, idx, n, out_slots, out_dists);
+    return hipGetLastError();
 }
 
 // k_merge_parts: the merge step of the row-partitioned search (index.cpp lantern_gpu_search_partitioned): per query, the

@@ -2472,8 +2472,9 @@ try {
 LANTERN_ABI_CATCH_VOID(e)
 
 // Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row):
-// fp32-MFMA contraction in chunks of 64k base rows + running top-(k+16) + exact-order re-rank.
-// Result (device): slots[nq][k] ascending by (distance, slot), dists[nq][k].
+// fp32-MFMA contraction in chunks of 64k base rows + running top-(k+16) + exact-order re-rank, then per query the certificate
+// that the top-(k+16) held the exact answer; the refused queries are recomputed in exact order.
+// Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].
 // `fused`: the f32 contractions (l2sq / cos) keep their distance matrix to themselves -- the tile epilogue appends what can still
 // enter a query's top-kk to a candidate list, folded in after every launch -- once the first kSeedCols columns have given every
 // query a radius the ordinary way.  *overflowed: a candidate list ran out of room (adversarially ordered rows): the caller repeats
@@ -2553,8 +2554,10 @@ struct KnnBlock  // pooled if small, allocated for the call otherwise; released 
 };
 }  // namespace
 
+// certified: one flag per query (1: the certificate of DESIGN.md 4.5 holds -- the result is the exact answer; 0: the caller
+// recomputes the query in exact order, exact_knn_fallback)
 static bool exact_knn_device_impl(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k,
-                                  uint32_t *d_slots, float *d_dists, hipStream_t st, bool fused, bool *overflowed)
+                                  uint32_t *d_slots, float *d_dists, hipStream_t st, bool fused, bool *overflowed, std::vector<uint32_t> &certified)
 try {
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -2582,7 +2585,7 @@ try {
     uint64_t *cand = nullptr;            // fused: [min(nq, QT)][kCandCap] keys, then the counters and the overflow flag
     const size_t nqt_max = std::min(nq, QT);
     // the distance matrix of the unfused launches: a whole chunk, or only the seed columns
-    bool ok = b_aux.get(pool, 0, (nq + nb) * 4 + 8 + nq * kk * 8) && b_dd.get(pool, 1, nqt_max * (fused ? kSeedCols : CH) * 4);
+    bool ok = b_aux.get(pool, 0, (nq + nb) * 4 + 8 + nq * kk * 8 + (nq + 1) * 4) && b_dd.get(pool, 1, nqt_max * (fused ? kSeedCols : CH) * 4);
     aux = (char *)b_aux.ptr;
     dd = (float *)b_dd.ptr;
     if(ok && fused) {
@@ -2632,10 +2635,23 @@ try {
             }
         }
         ok = ok && launch_rerank(mcode, d_q, (uint32_t)nq, d_base, chunks, best, kk, (uint32_t)k, d_slots, d_dists, st) == hipSuccess;
+        // the certificate: 4 bytes per query to the host, behind the synchronisation the call makes anyway.  The popcount metrics
+        // rank on the exact-order distance itself (the same integer arithmetic): their pre-selection is exact by construction.
+        uint32_t *flag = (uint32_t *)(best + nq * kk);
+        certified.assign(nq + 1, bits ? 1u : 0u);
+        certified[ nq ] = 0;
+        if(!bits) {
+            ok = ok && hipMemsetAsync(flag + nq, 0, 4, st) == hipSuccess;
+            ok = ok && launch_certify(base_metric, best, kk, d_dists, (uint32_t)k, qn, (uint32_t)nq, bn, (uint32_t)nb, fchunks * 4, flag, st) == hipSuccess;
+            ok = ok && hipMemcpyAsync(certified.data(), flag, (nq + 1) * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+        }
         uint32_t over = 0;
         if(fused) ok = ok && hipMemcpyAsync(&over, cover, 4, hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = ok && hipStreamSynchronize(st) == hipSuccess;
         if(overflowed) *overflowed = over != 0;
+        if(ok && certified[ nq ])  // a cosine row norm outside the bound's range: nothing is certified
+            std::fill(certified.begin(), certified.end() - 1, 0u);
+        certified.resize(nq);
     }
     if(!ok) (void)hipStreamSynchronize(st);  // nothing queued may still name the pooled blocks when the pool's lock is released
     if(fq) (void)hipFree(fq);
@@ -2644,17 +2660,68 @@ try {
 }
 LANTERN_ABI_CATCH(nullptr)
 
+// lantern_gpu_exact_knn_stats: queries of every exact k-NN of the process, how many the certificate passed, how many took the
+// exact-order fallback
+namespace {
+std::atomic<uint64_t> g_knn_queries{ 0 }, g_knn_certified{ 0 }, g_knn_fallback{ 0 };
+}
+
+// The queries the certificate refused, recomputed in the pair kernel's exact order over every base row: their rows gathered,
+// k_pairs + k_select (top-k by (exact distance, slot)) per block of kFallbackQ queries and chunk of base rows, the keys written
+// over their rows of the result.  nf x nb exact-order evaluations: rare (adversarial data), not fast.
+static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t k, const std::vector<uint32_t> &qidx,
+                               uint32_t *d_slots, float *d_dists, hipStream_t st)
+{
+    const size_t nf = qidx.size(), CH = std::min<size_t>(nb, 65536), kFallbackQ = 256, nfb = std::min(nf, kFallbackQ);
+    void *d_idx = nullptr, *d_rows = nullptr, *d_best = nullptr, *d_dd = nullptr;
+    bool  ok = hipMalloc(&d_idx, nf * 4) == hipSuccess && hipMalloc(&d_rows, nf * (size_t)chunks * 16) == hipSuccess &&
+              hipMalloc(&d_best, nf * k * 8) == hipSuccess && hipMalloc(&d_dd, nfb * CH * 4) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d_idx, qidx.data(), nf * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+    ok = ok && hipMemsetAsync(d_best, 0xFF, nf * k * 8, st) == hipSuccess;
+    ok = ok && launch_gather_rows(d_q, chunks, (const uint32_t *)d_idx, (uint32_t)nf, (uint4 *)d_rows, st) == hipSuccess;
+    for(size_t c0 = 0; ok && c0 < nb; c0 += CH) {
+        const size_t nc = std::min(CH, nb - c0);
+        for(size_t f0 = 0; ok && f0 < nf; f0 += kFallbackQ) {
+            const size_t nft = std::min(kFallbackQ, nf - f0);
+            ok = ok && launch_pairs(mcode, (const uint4 *)d_rows + f0 * chunks, (uint32_t)nft, d_base + c0 * chunks, (uint32_t)nc, chunks, (float *)d_dd,
+                                    st) == hipSuccess;
+            ok = ok && launch_select((const float *)d_dd, (uint32_t)nc, (uint32_t)nft, (uint32_t)nc, (uint32_t)c0, (uint64_t *)d_best + f0 * k, (uint32_t)k,
+                                     st) == hipSuccess;
+        }
+    }
+    ok = ok && launch_emit_topk((const uint64_t *)d_best, (uint32_t)k, (const uint32_t *)d_idx, (uint32_t)nf, d_slots, d_dists, st) == hipSuccess;
+    ok = ok && hipStreamSynchronize(st) == hipSuccess;
+    if(!ok) (void)hipStreamSynchronize(st);
+    for(void *p : { d_idx, d_rows, d_best, d_dd })
+        if(p) (void)hipFree(p);
+    return ok;
+}
+
 static bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k,
                              uint32_t *d_slots, float *d_dists, hipStream_t st)
 try {
     const char *env = std::getenv("LANTERN_GPU_DENSE_FUSED");  // =0: always the unfused path (A/B, tests)
     const bool  want_fused = !(env && std::atoi(env) == 0);
-    bool over = false;
-    if(!exact_knn_device_impl(mcode, chunks, d_base, nb, d_q, nq, k, d_slots, d_dists, st, want_fused, &over)) return false;
-    if(!over) return true;
-    return exact_knn_device_impl(mcode, chunks, d_base, nb, d_q, nq, k, d_slots, d_dists, st, false, nullptr);
+    bool                  over = false;
+    std::vector<uint32_t> certified;
+    if(!exact_knn_device_impl(mcode, chunks, d_base, nb, d_q, nq, k, d_slots, d_dists, st, want_fused, &over, certified)) return false;
+    if(over && !exact_knn_device_impl(mcode, chunks, d_base, nb, d_q, nq, k, d_slots, d_dists, st, false, nullptr, certified)) return false;
+    std::vector<uint32_t> refused;
+    for(size_t q = 0; q < nq; ++q)
+        if(!certified[ q ]) refused.push_back((uint32_t)q);
+    g_knn_queries += nq;
+    g_knn_certified += nq - refused.size();
+    g_knn_fallback += refused.size();
+    return refused.empty() || exact_knn_fallback(mcode, chunks, d_base, nb, d_q, k, refused, d_slots, d_dists, st);
 }
 LANTERN_ABI_CATCH(nullptr)
+
+void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t *certified, uint64_t *fallback)
+{
+    if(queries) *queries = g_knn_queries.load();
+    if(certified) *certified = g_knn_certified.load();
+    if(fallback) *fallback = g_knn_fallback.load();
+}
 
 void lantern_gpu_exact_search(usearch_index_t h, const void *queries, size_t nq, size_t k, uint32_t *slots, float *distances,
                               usearch_error_t *e)

@@ -241,6 +241,12 @@ hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t 
                          hipStream_t stream);
 hipError_t launch_rerank(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
                          uint32_t k, uint32_t *out_slots, float *out_dists, hipStream_t stream);
+// the exact k-NN's certificate (flag[q] = 1: certified; flag[nq] != 0: a cosine row norm out of the bound's range) and the
+// exact-order fallback's row gather / result scatter (bruteforce.hip)
+hipError_t launch_certify(int metric, const uint64_t *best, uint32_t kk, const float *dists, uint32_t k, const float *qn, uint32_t nq, const float *bn,
+                          uint32_t nb, uint32_t dims, uint32_t *flag, hipStream_t stream);
+hipError_t launch_gather_rows(const uint4 *src, uint32_t chunks, const uint32_t *idx, uint32_t n, uint4 *dst, hipStream_t stream);
+hipError_t launch_emit_topk(const uint64_t *best, uint32_t k, const uint32_t *idx, uint32_t n, uint32_t *out_slots, float *out_dists, hipStream_t stream);
 
 size_t search_lds_bytes(uint32_t chunks, uint32_t ef_cap, uint32_t M0, uint32_t vis_slots);
 size_t insert_lds_bytes(uint32_t chunks, uint32_t efc, uint32_t M0, uint32_t vis_slots);
