@@ -325,6 +325,11 @@ LANTERN_GPU_EXPORT void   lantern_gpu_filter_free(lantern_gpu_filter_t *);
 LANTERN_GPU_EXPORT void lantern_gpu_set_filter_policy(usearch_index_t, int path, size_t cand_cap, double exact_factor, usearch_error_t *);
 /* launches of the two filtered kernels since the index was created */
 LANTERN_GPU_EXPORT void lantern_gpu_filter_stats(usearch_index_t, uint64_t *walk_launches, uint64_t *exact_launches, usearch_error_t *);
+/* the shape of the last filtered launch on this index (diagnostic; tests assert the regime a launch ran in):
+ * out[0] path (1 walk, 2 exact), [1] workgroups, [2] expansion (walk: max(ef, k + skip); exact: k + skip), [3] candidate cap C of the walk
+ * (0 on the exact path), [4] LDS visited-set slots of the walk (0 = HBM bitmap only; 0 on the exact path), [5] dynamic LDS bytes per
+ * workgroup.  All zero before the first filtered launch and after a call that launched nothing (an empty filter). */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_launch(usearch_index_t, uint32_t out[6], usearch_error_t *);
 /* lantern_gpu_search_batch through a filter (host buffers; the unused tail of a row is label 0 and +inf) */
 LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered(usearch_index_t, const lantern_gpu_filter_t *, const void *queries, size_t nq,
                                                           usearch_scalar_kind_t, size_t k, size_t ef, usearch_label_t *labels,

@@ -109,7 +109,7 @@ EXPORTS = [
     "lantern_quant_bits_scalar_kind",
     # filtered search (lantern_gpu.h "Filtered search")
     "lantern_gpu_filter_from_labels", "lantern_gpu_filter_from_slot_bitmap", "lantern_gpu_filter_count", "lantern_gpu_filter_free",
-    "lantern_gpu_set_filter_policy", "lantern_gpu_filter_stats", "lantern_gpu_search_batch_filtered", "lantern_gpu_search_batch_filtered_device",
+    "lantern_gpu_set_filter_policy", "lantern_gpu_filter_stats", "lantern_gpu_last_filtered_launch", "lantern_gpu_search_batch_filtered", "lantern_gpu_search_batch_filtered_device",
     "lantern_gpu_cursor_search_filtered", "lantern_scan_set_filter",
 ]
 FILTER_SKIP_DELETED = 1  # LANTERN_GPU_FILTER_SKIP_DELETED
@@ -275,6 +275,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_filter_free": (None, [vp]),
         "lantern_gpu_set_filter_policy": (None, [vp, i32, sz, C.c_double, err]),
         "lantern_gpu_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), err]),
+        "lantern_gpu_last_filtered_launch": (None, [vp, vp, err]),
         "lantern_gpu_search_batch_filtered": (None, [vp, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
         "lantern_gpu_search_batch_filtered_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_cursor_search_filtered": (sz, [vp, vp, vp, i32, sz, sz, C.c_bool, vp, vp, err]),
@@ -688,6 +689,13 @@ class GpuIndex:
         w, e = C.c_uint64(), C.c_uint64()
         _call("lantern_gpu_filter_stats", self.h, C.byref(w), C.byref(e))
         return {"walk": int(w.value), "exact": int(e.value)}
+
+    def last_filtered_launch(self):
+        """The shape of the last filtered launch on this index (all zero before any, and after an empty-filter call)."""
+        out = np.zeros(6, dtype=np.uint32)
+        _call("lantern_gpu_last_filtered_launch", self.h, _ptr(out))
+        path, grid, exp, cap, vis, lds = (int(x) for x in out)
+        return {"path": {0: None, 1: "walk", 2: "exact"}[path], "grid": grid, "expansion": exp, "cand_cap": cap, "vis_slots": vis, "lds_bytes": lds}
 
     def search_batch_filtered(self, filt: "Filter", queries, k, ef=0):
         Q = _rows(queries, self.metric)

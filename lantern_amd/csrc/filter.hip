@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <iterator>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -176,6 +177,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     const size_t ef_sel = ef ? ef : ix->ef;
     const size_t exp = std::max(ef_sel, k + skip);
     if(f->count == 0 || ix->n == 0) {  // nothing allowed: the empty answer, no launch
+        std::fill(std::begin(ix->last_filtered), std::end(ix->last_filtered), 0u);
         if(d_labels && hipMemsetAsync(d_labels, 0, nq * k * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
         if(d_dists && hipMemsetD32Async((hipDeviceptr_t)d_dists, 0x7F800000, nq * k, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
         if(d_slots && hipMemsetAsync(d_slots, 0xFF, nq * k * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
@@ -251,6 +253,8 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     }
     if(!release_search_slot(ix, slot, stream)) return false;
     (exact ? ix->c_filter_exact : ix->c_filter_walk) += 1;
+    const uint32_t shape[ 6 ] = { exact ? 2u : 1u, (uint32_t)grid, a.exp, a.cand_cap, a.vis_slots, (uint32_t)lds };
+    std::copy(std::begin(shape), std::end(shape), ix->last_filtered);
     ix->c_search_queries += nq;
     return true;
 }
@@ -399,6 +403,17 @@ try {
     std::lock_guard<std::mutex> g(ix->mu);
     if(walk_launches) *walk_launches = ix->c_filter_walk;
     if(exact_launches) *exact_launches = ix->c_filter_exact;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_last_filtered_launch(usearch_index_t h, uint32_t out[ 6 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FH(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::copy(std::begin(ix->last_filtered), std::end(ix->last_filtered), out);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

@@ -195,6 +195,7 @@ struct Index
     size_t   filter_cand_cap = 0;       // 0: max(4 expansion, 256), capped by LDS
     double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
     uint64_t c_filter_walk = 0, c_filter_exact = 0;
+    uint32_t last_filtered[ 6 ] = {};  // path, grid, expansion, cand_cap, vis_slots, LDS bytes of the last filtered launch (lantern_gpu_last_filtered_launch)
 
     hipStream_t stream = nullptr;
     int         device = 0;

@@ -1,6 +1,12 @@
 """`python tests/env_switch_probe.py` in a process of its own (several switches are read once per process): a small build, searches in
-the three launch regimes, an exact k-NN, a compact pq index -- and one JSON line of checksums.  tests/test_gpu_env_switches.py runs it
-once with the default environment and once per result-neutral switch and requires the same line."""
+the three launch regimes, an exact k-NN, filtered searches, a compact pq index -- and one JSON line of checksums.
+tests/test_gpu_env_switches.py runs it once with the default environment and once per result-neutral switch and requires the same line.
+
+The filtered leg: a selective walk (10 % allowed), the exact path, and the same walk with two workgroups serving the whole batch, so that
+LANTERN_GPU_VIS_UNDO = 0 / 16 runs the filtered walk's clear-at-the-end path with a next walk behind it in the same bitmap, and
+LANTERN_GPU_TICKETS / WAVES_PER_CU reach the filtered kernels' hand-out and grid.  LANTERN_GPU_VIS_SLOTS does NOT reach the filtered walk
+(filter.hip sizes its LDS visited set from the launch's LDS alone), so those switches are result-neutral there by construction; the
+bitmap-only filtered walk is entered through the candidate cap instead (tests/test_gpu_filtered_regimes.py)."""
 import hashlib
 import json
 import os
@@ -37,6 +43,16 @@ def main():
         out[name + "_search_ef"] = digest(lab1, dist1)
         slots, dists = ix.exact_search(queries[:64], 10)
         out[name + "_exact"] = digest(slots, dists)
+        allowed = np.random.default_rng(n).random(n) < 0.1
+        filt = ix.filter_from_bitmap(allowed)
+        for tag, path, max_wg in (("walk", "walk", 0), ("exact", "exact", 0), ("walk_2wg", "walk", 2)):
+            ix.set_filter_policy(path)
+            ix.set_search_shape(0, max_wg)
+            lab, dist, cnt = ix.search_batch_filtered(filt, queries[:200], 10)
+            out[f"{name}_filtered_{tag}"] = digest(lab, dist, cnt)
+        ix.set_search_shape(0, 0)
+        ix.set_filter_policy("auto")
+        filt.close()
         ix.add(10**6, base[0] * np.float32(0.5))  # one ldb_aminsert-sized insertion on top
         out[name + "_graph_after_insert"] = f"{ix.checksum():016x}"
     # a pq index, expanded and compact

@@ -13,10 +13,15 @@ import numpy as np
 EMPTY = 0xFFFFFFFF
 
 
-def distance_matrix(oracle, base, queries, metric, sum_mode):
-    """[nq][n] float32: oracle.bruteforce with k = n, scattered back to slot order."""
+def distance_matrix(oracle, base, queries, metric, sum_mode, nthreads=1):
+    """[nq][n] float32: oracle.bruteforce with k = n, scattered back to slot order.
+
+    Quantised storage: pass the rows and queries AS STORED and the matching summation order -- oracle.round_f16 of both with
+    SUM_WAVE64_F16, oracle.quantize_i8 of both with SUM_I8, and for a b1 index the packed sign-bit words with metric "hamming" (index
+    metric l2sq) or "cos_b1" (index metric cos) and SUM_SEQ, as tests/test_gpu_quantized_indexes.py does."""
     n = base.shape[0]
-    ids, d = oracle.bruteforce(base, queries, n, metric, sum_mode=sum_mode)
+    ids, d = oracle.bruteforce(base, queries, n, metric, sum_mode, nthreads)
+    assert all(np.array_equal(np.sort(row), np.arange(n, dtype=ids.dtype)) for row in ids), "bruteforce with k = n returns every row once"
     out = np.empty((ids.shape[0], n), dtype=np.float32)
     np.put_along_axis(out, ids.astype(np.int64), d, axis=1)
     return out

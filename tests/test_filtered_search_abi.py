@@ -4,7 +4,7 @@ import ctypes as C
 import pytest
 
 NAMES = ["lantern_gpu_filter_from_labels", "lantern_gpu_filter_from_slot_bitmap", "lantern_gpu_filter_count", "lantern_gpu_filter_free",
-         "lantern_gpu_set_filter_policy", "lantern_gpu_filter_stats", "lantern_gpu_search_batch_filtered",
+         "lantern_gpu_set_filter_policy", "lantern_gpu_filter_stats", "lantern_gpu_last_filtered_launch", "lantern_gpu_search_batch_filtered",
          "lantern_gpu_search_batch_filtered_device", "lantern_gpu_cursor_search_filtered", "lantern_scan_set_filter"]
 
 
@@ -31,7 +31,7 @@ def test_symbols_exported_and_bound(capi):
         assert getattr(capi.lib(), n).argtypes is not None, n
     assert capi.FILTER_SKIP_DELETED == 1
     for m in ("filter_from_labels", "filter_from_bitmap", "search_batch_filtered", "search_batch_filtered_device", "set_filter_policy",
-              "filter_stats"):
+              "filter_stats", "last_filtered_launch"):
         assert callable(getattr(capi.GpuIndex, m)), m
     assert callable(capi.Cursor.search_filtered) and callable(capi.Scan.set_filter)
     assert isinstance(capi.Filter.count, property) and callable(capi.Filter.close)
@@ -50,6 +50,10 @@ def test_null_and_foreign_index_handles_are_refused(capi):
         assert e and "index handle" in e
         _, e = call(capi, "lantern_gpu_set_filter_policy", h, 0, 0, C.c_double(16.0))
         assert e and "index handle" in e
+        shape = (C.c_uint32 * 6)(*([7] * 6))
+        _, e = call(capi, "lantern_gpu_last_filtered_launch", h, shape)
+        assert e and ("null index handle" in e or "not an index handle" in e)
+        assert list(shape) == [7] * 6  # a refused call writes nothing
 
 
 def test_null_and_foreign_filter_handles_are_refused(capi):
