@@ -316,6 +316,7 @@ LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_from_labels(usearch_
 LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_from_slot_bitmap(usearch_index_t, const uint32_t *words, size_t n_words,
                                                                              uint32_t flags, usearch_error_t *);
 LANTERN_GPU_EXPORT size_t lantern_gpu_filter_count(const lantern_gpu_filter_t *, usearch_error_t *); /* allowed slots */
+LANTERN_GPU_EXPORT size_t lantern_gpu_filter_resident_bytes(const lantern_gpu_filter_t *, usearch_error_t *); /* device memory it holds */
 LANTERN_GPU_EXPORT void   lantern_gpu_filter_free(lantern_gpu_filter_t *);
 /* path: 0 auto, 1 walk, 2 exact.  cand_cap = C (0: max(4 expansion, 256), capped by LDS; below expansion it is raised to it).
  * Auto takes the exact path when allowed^2 <= exact_factor * ef * n, ef the caller's or else the index's: a walk under a filter of
@@ -340,6 +341,41 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_device(usearch_index_t
                                                                  uint64_t *d_labels, float *d_distances, uint32_t *d_slots,
                                                                  uint32_t *d_counts, uint64_t *d_dist_evals, uint64_t *d_expansions,
                                                                  void *stream, usearch_error_t *);
+/* PER-QUERY FILTERS: one call, filters[i] the filter of query i (a host array of nq handles).  Per query i:
+ *  - filters[i] a filter: exactly what the single-filter call gives that query with that filter -- the same path rule
+ *    (lantern_gpu_set_filter_policy: forced path, cand_cap, exact_factor, evaluated from THAT filter's count, n and ef), the same ids,
+ *    distance bits, count, D and E;
+ *  - filters[i] == NULL: every row allowed, walk path: by the all-allowed property the ids, bits, D and E of the unfiltered search;
+ *  - an empty filter: count 0, rows of label 0 / +inf / EMPTY slot, D = E = 0.
+ * The queries split into a walk group and an exact group; each group is ONE launch over its own list of queries (the exact group
+ * longest first), whatever the filters are, and every answer lands in the row of its query.  Empty filters have no path: they ride
+ * in the exact launch (in the walk launch when no query takes the exact path), where they touch no row; a call of empty filters
+ * alone is one exact launch.  k, ef and skip -- hence expansion, C and the LDS carve -- are the call's, uniform over its queries.
+ * An entry that is not a live filter handle, belongs to another index or is stale refuses the WHOLE call before anything is
+ * launched or written: the single-filter message plus " (filters[i])", i the first offending position.  Compact pq indexes are
+ * refused as by the single-filter calls.
+ * Lifetime: a filter may be freed by its owner as soon as the call that used it has returned (the host and lane forms), or the
+ * work queued on `stream` has completed (the device form).  The filters[] array itself is read only during the call.
+ * lantern_gpu_filter_stats counts the launches; lantern_gpu_last_filtered_launch is not updated by these calls. */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each(usearch_index_t, const lantern_gpu_filter_t *const *filters, const void *queries,
+                                                               size_t nq, usearch_scalar_kind_t, size_t k, size_t ef, usearch_label_t *labels,
+                                                               float *distances, uint32_t *counts, usearch_error_t *);
+/* lantern_gpu_search_batch_filtered_device with a filter per query */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each_device(usearch_index_t, const lantern_gpu_filter_t *const *filters,
+                                                                      const void *d_queries, size_t query_stride_bytes, size_t nq, size_t k,
+                                                                      size_t ef, size_t skip, uint64_t *d_labels, float *d_distances,
+                                                                      uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_dist_evals,
+                                                                      uint64_t *d_expansions, void *stream, usearch_error_t *);
+/* lantern_gpu_search_batch_lane with a filter per query: the lane's stream and page-locked staging block, the index mutex held only
+ * while the copies and the launches are queued, the wait outside it (what a service that coalesces filtered queries calls) */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each_lane(usearch_index_t, int lane, const lantern_gpu_filter_t *const *filters,
+                                                                    const void *queries, size_t nq, usearch_scalar_kind_t, size_t k, size_t ef,
+                                                                    usearch_label_t *labels, float *distances, uint32_t *counts,
+                                                                    usearch_error_t *);
+/* the last per-query call on this index that passed its checks (diagnostic; tests assert the regime): out[0] queries on the walk
+ * path (the unfiltered ones included), [1] on the exact path, [2] unfiltered (NULL) entries, [3] empty filters, [4] distinct filter
+ * handles in the array, [5] kernel launches made (0 .. 2).  All zero before the first such call. */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each(usearch_index_t, uint32_t out[6], usearch_error_t *);
 /* kernel shape of the search launch: waves per query (1..8; 0 = automatic: 4 when the batch fills the chip, up to 8 for
  * smaller batches) and resident workgroups (0 = auto) */
 LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_per_query, int max_workgroups,
@@ -599,8 +635,9 @@ LANTERN_GPU_EXPORT bool lantern_scan_gettuple(lantern_scan_t *, usearch_label_t 
 LANTERN_GPU_EXPORT size_t lantern_scan_trace(lantern_scan_t *, int *ks, size_t cap);
 LANTERN_GPU_EXPORT void lantern_scan_end(lantern_scan_t *);
 /* Later rescans and gettuples of this scan go through the filter (lantern_gpu_cursor_search_filtered): every row it returns is
- * allowed, and the 1000-row cap counts allowed rows.  NULL clears it.  Refused on a scan of lantern_scan_begin_client (the
- * scan-service wire format carries no filter).  The filter must outlive the scan's use of it. */
+ * allowed, and the 1000-row cap counts allowed rows.  NULL clears it.  The filter must outlive the scan's use of it.
+ * Refused on a scan of lantern_scan_begin_client: a filter handle is local to a process.  Such a scan inherits the filter of its
+ * CONNECTION (lantern_scan_client_set_filter), with the same two properties. */
 LANTERN_GPU_EXPORT void lantern_scan_set_filter(lantern_scan_t *, const struct lantern_gpu_filter *, usearch_error_t *);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -683,6 +720,27 @@ LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start(usearch_inde
 LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_fn(lantern_batch_search_fn, void *ctx, size_t vec_bytes,
                                                                        const char *host, int port, size_t max_batch,
                                                                        unsigned max_wait_us, usearch_error_t *);
+/* FILTERS THROUGH THE SERVICE.  A connection may carry a filter (lantern_scan_client_set_filter: a list of labels, built on the
+ * device by lantern_gpu_filter_from_labels and owned by the server); every later search of that connection goes through it.  Within a
+ * batch's (k, ef) group the unfiltered requests take the path above; the filtered ones -- of whatever connections, with whatever
+ * filters -- go out together in ONE lantern_gpu_search_batch_filtered_each_lane call.  Limits, errors and the wire message:
+ * lantern_amd/csrc/scan_server.cpp.  LANTERN_SCAN_FILTER_BYTES: device memory the resident filters may take (default 1 GiB).
+ * A back end of lantern_scan_server_start_fn has no filters (a filter message gets an error frame); the form below brings its own:
+ * make -> an opaque filter (NULL and *err on failure) with its allowed rows and resident bytes; free; and the batch search with a
+ * filter per query (never NULL entries: unfiltered requests go to the plain function). */
+typedef void *(*lantern_scan_filter_make_fn)(void *ctx, const uint64_t *labels, size_t n, uint32_t flags, uint64_t *allowed,
+                                             uint64_t *resident_bytes, const char **err);
+typedef void (*lantern_scan_filter_free_fn)(void *ctx, void *filter);
+typedef int (*lantern_batch_search_each_fn)(void *ctx, const void *const *filters, const void *queries, size_t nq, size_t vec_bytes, size_t k,
+                                            size_t ef, uint64_t *labels, float *distances, uint32_t *counts, const char **err);
+LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_filtered_fn(lantern_batch_search_fn, lantern_scan_filter_make_fn,
+                                                                                lantern_scan_filter_free_fn, lantern_batch_search_each_fn,
+                                                                                void *ctx, size_t vec_bytes, const char *host, int port,
+                                                                                size_t max_batch, unsigned max_wait_us, usearch_error_t *);
+/* filters set (clears not counted), requests searched through a filter, per-query-filter calls made, the largest number of DISTINCT
+ * filters one such call carried, device bytes of the filters resident now */
+LANTERN_GPU_EXPORT void lantern_scan_server_filter_stats(lantern_scan_server_t *, uint64_t *filters_set, uint64_t *filtered_requests,
+                                                         uint64_t *each_calls, uint64_t *most_distinct_filters, uint64_t *resident_bytes);
 LANTERN_GPU_EXPORT int  lantern_scan_server_port(lantern_scan_server_t *);
 /* queries received, batches formed, search launches (one per distinct (k, ef) of a batch), largest batch so far */
 LANTERN_GPU_EXPORT void lantern_scan_server_stats(lantern_scan_server_t *, uint64_t *requests, uint64_t *batches,
@@ -701,6 +759,12 @@ LANTERN_GPU_EXPORT size_t lantern_scan_client_search(lantern_scan_client_t *, co
  * its last lantern_scan_client_search; the state is the connection's, so concurrent backends never disturb each other */
 LANTERN_GPU_EXPORT size_t lantern_scan_client_search_next(lantern_scan_client_t *, const void *query, size_t query_bytes, size_t k,
                                                           size_t ef, usearch_label_t *labels, float *distances, usearch_error_t *);
+/* Set this connection's filter: allowed are the rows whose label is in labels[0 .. n) (n = 0: nothing is allowed; flags:
+ * LANTERN_GPU_FILTER_SKIP_DELETED).  Returns the allowed rows.  It replaces the connection's previous filter and ends its current
+ * scan; on an error the previous filter stays in force.  clear_filter: the connection is unfiltered again. */
+LANTERN_GPU_EXPORT size_t lantern_scan_client_set_filter(lantern_scan_client_t *, const usearch_label_t *labels, size_t n, uint32_t flags,
+                                                         usearch_error_t *);
+LANTERN_GPU_EXPORT void   lantern_scan_client_clear_filter(lantern_scan_client_t *, usearch_error_t *);
 LANTERN_GPU_EXPORT void   lantern_scan_client_close(lantern_scan_client_t *);
 
 /* ------------------------------------------------------------------------------------------ */

@@ -111,6 +111,9 @@ EXPORTS = [
     "lantern_gpu_filter_from_labels", "lantern_gpu_filter_from_slot_bitmap", "lantern_gpu_filter_count", "lantern_gpu_filter_free",
     "lantern_gpu_set_filter_policy", "lantern_gpu_filter_stats", "lantern_gpu_last_filtered_launch", "lantern_gpu_search_batch_filtered", "lantern_gpu_search_batch_filtered_device",
     "lantern_gpu_cursor_search_filtered", "lantern_scan_set_filter",
+    "lantern_gpu_filter_resident_bytes", "lantern_scan_server_start_filtered_fn", "lantern_scan_server_filter_stats", "lantern_scan_client_set_filter",
+    "lantern_scan_client_clear_filter",
+    "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
 ]
 FILTER_SKIP_DELETED = 1  # LANTERN_GPU_FILTER_SKIP_DELETED
 FILTER_PATHS = {"auto": 0, "walk": 1, "exact": 2}
@@ -118,6 +121,13 @@ FILTER_PATHS = {"auto": 0, "walk": 1, "exact": 2}
 # int fn(void *ctx, const void *queries, size_t nq, size_t vec_bytes, size_t k, size_t ef, u64 *labels, f32 *dists, u32 *counts, const char **err)
 BATCH_SEARCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64),
                               C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
+
+# the filter-aware back end of lantern_scan_server_start_filtered_fn: make / free a filter, the batch search with a filter per query
+FILTER_MAKE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                             C.POINTER(C.c_char_p))
+FILTER_FREE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)
+BATCH_SEARCH_EACH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
 
 # int fn(void *ctx, void *host_buf, const size_t *offsets, const size_t *counts, int world, int rank)
 QUERIES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t)  # lantern_gpu_queries_done_fn
@@ -280,6 +290,16 @@ def lib() -> C.CDLL:
         "lantern_gpu_search_batch_filtered_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_cursor_search_filtered": (sz, [vp, vp, vp, i32, sz, sz, C.c_bool, vp, vp, err]),
         "lantern_scan_set_filter": (None, [vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_each": (None, [vp, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_each_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_each_lane": (None, [vp, i32, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
+        "lantern_gpu_last_filtered_each": (None, [vp, vp, err]),
+        "lantern_gpu_filter_resident_bytes": (sz, [vp, err]),
+        "lantern_scan_server_start_filtered_fn": (vp, [BATCH_SEARCH_FN, FILTER_MAKE_FN, FILTER_FREE_FN, BATCH_SEARCH_EACH_FN, vp, sz, C.c_char_p, i32, sz,
+                                                       C.c_uint, err]),
+        "lantern_scan_server_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "lantern_scan_client_set_filter": (sz, [vp, vp, sz, u32, err]),
+        "lantern_scan_client_clear_filter": (None, [vp, err]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = the library does not export what the header declares
@@ -711,6 +731,55 @@ class GpuIndex:
         """search_batch_device through a filter; raw device addresses, the query row stride stated (device_query_rows(...).strides[0])."""
         _call("lantern_gpu_search_batch_filtered_device", self.h, filt.h, _ptr(d_queries), int(query_stride), nq, k, ef, skip, _ptr(d_labels),
               _ptr(d_dists), _ptr(d_slots), _ptr(d_counts), _ptr(d_D), _ptr(d_E), _ptr(stream))
+
+    @staticmethod
+    def _filter_array(filters, nq):
+        """filters[i] a Filter, None (unfiltered) or a raw address (tests of the refusals) -> a host array of nq handles.  An array made
+        by this function is taken as it is (a caller that repeats a large batch builds it once)."""
+        if isinstance(filters, np.ndarray) and filters.dtype == np.uint64 and filters.shape == (nq,):
+            return np.ascontiguousarray(filters)
+        if len(filters) != nq:
+            raise ValueError("one filter (or None) per query: got %d for %d queries" % (len(filters), nq))
+        if any(isinstance(f, Filter) and not f.h for f in filters):
+            raise ValueError("a closed Filter in the filter array")
+        return np.array([0 if f is None else (f.h if isinstance(f, Filter) else int(f)) for f in filters], dtype=np.uint64)
+
+    def search_batch_filtered_each(self, filters, queries, k, ef=0):
+        """search_batch with a filter PER QUERY: filters[i] a Filter or None (every row allowed) -- one call, at most two launches."""
+        Q = _rows(queries, self.metric)
+        nq = Q.shape[0]
+        F = self._filter_array(filters, nq)
+        labels = np.zeros((nq, k), dtype=np.uint64)
+        dists = np.zeros((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _call("lantern_gpu_search_batch_filtered_each", self.h, _ptr(F), _ptr(Q), nq, _kind(self.metric), k, ef, _ptr(labels), _ptr(dists), _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_filtered_each_lane(self, lane, filters, queries, k, ef=0):
+        """search_batch_filtered_each on a lane (one caller per lane; the lanes' launches overlap on the device)."""
+        Q = _rows(queries, self.metric)
+        nq = Q.shape[0]
+        F = self._filter_array(filters, nq)
+        labels = np.zeros((nq, k), dtype=np.uint64)
+        dists = np.zeros((nq, k), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        _call("lantern_gpu_search_batch_filtered_each_lane", self.h, lane, _ptr(F), _ptr(Q), nq, _kind(self.metric), k, ef, _ptr(labels), _ptr(dists),
+              _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_filtered_each_device(self, filters, d_queries, query_stride, nq, k, ef=0, skip=0, d_labels=None, d_dists=None, d_slots=None,
+                                          d_counts=None, d_D=None, d_E=None, stream=None):
+        """search_batch_filtered_device with a filter per query (a host list of nq Filters / None); raw device addresses."""
+        F = self._filter_array(filters, nq)
+        _call("lantern_gpu_search_batch_filtered_each_device", self.h, _ptr(F), _ptr(d_queries), int(query_stride), nq, k, ef, skip, _ptr(d_labels),
+              _ptr(d_dists), _ptr(d_slots), _ptr(d_counts), _ptr(d_D), _ptr(d_E), _ptr(stream))
+
+    def last_filtered_each(self):
+        """The regime of the last per-query filtered call on this index (lantern_gpu_last_filtered_each)."""
+        out = np.zeros(6, dtype=np.uint32)
+        _call("lantern_gpu_last_filtered_each", self.h, _ptr(out))
+        walk, exact, unfiltered, empty, distinct, launches = (int(x) for x in out)
+        return {"walk": walk, "exact": exact, "unfiltered": unfiltered, "empty": empty, "distinct_filters": distinct, "launches": launches}
 
     def distance_gather(self, query, slots):
         q = _rows(query, self.metric)[0]
@@ -1148,12 +1217,60 @@ class Scan:
 class ScanServer:
     """lantern_scan_server_*: one HBM-resident index serving many backends' queries in batched launches."""
 
-    def __init__(self, index=None, host="127.0.0.1", port=0, max_batch=256, max_wait_us=200, batch_fn=None, vec_bytes=0):
+    def __init__(self, index=None, host="127.0.0.1", port=0, max_batch=256, max_wait_us=200, batch_fn=None, vec_bytes=0, filter_fns=None):
         """index: a GpuIndex (the server runs lantern_gpu_search_batch on it), or batch_fn(queries u8[nq, vec_bytes], k, ef)
-        -> (labels u64[nq, k], dists f32[nq, k], counts u32[nq]) for tests / custom back ends."""
+        -> (labels u64[nq, k], dists f32[nq, k], counts u32[nq]) for tests / custom back ends.  filter_fns, with batch_fn: a back end
+        with filters -- (make(labels u64[n], flags) -> (handle int != 0, allowed, resident_bytes), free(handle),
+        each(filters [nq] of handles, queries, k, ef) -> as batch_fn)."""
         self._keep = None
         self.index = index
-        if batch_fn is not None:
+        if batch_fn is not None and filter_fns is not None:
+            make_fn, free_fn, each_fn = filter_fns
+
+            def fail(ex, errp):
+                self._last_error = C.c_char_p(str(ex).encode())
+                errp[0] = self._last_error
+
+            def tramp(ctx, queries, nq, vb, k, ef, labels, dists, counts, errp):
+                try:
+                    q = np.ctypeslib.as_array(C.cast(queries, C.POINTER(C.c_uint8)), shape=(nq, vb))
+                    lab, dst, cnt = batch_fn(q, int(k), int(ef))
+                    np.ctypeslib.as_array(labels, shape=(nq, k))[:] = lab
+                    np.ctypeslib.as_array(dists, shape=(nq, k))[:] = dst
+                    np.ctypeslib.as_array(counts, shape=(nq,))[:] = cnt
+                    return 0
+                except Exception as ex:  # noqa: BLE001
+                    fail(ex, errp)
+                    return 1
+
+            def tramp_make(ctx, labels, n, flags, allowed, nbytes, errp):
+                try:
+                    lab = np.ctypeslib.as_array(labels, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint64)
+                    h, a, b = make_fn(lab, int(flags))
+                    allowed[0], nbytes[0] = int(a), int(b)
+                    return int(h)
+                except Exception as ex:  # noqa: BLE001 -- becomes the error frame of the filter message
+                    fail(ex, errp)
+                    return None
+
+            def tramp_free(ctx, h):
+                free_fn(int(h))
+
+            def tramp_each(ctx, filters, queries, nq, vb, k, ef, labels, dists, counts, errp):
+                try:
+                    q = np.ctypeslib.as_array(C.cast(queries, C.POINTER(C.c_uint8)), shape=(nq, vb))
+                    lab, dst, cnt = each_fn([int(filters[i] or 0) for i in range(nq)], q, int(k), int(ef))
+                    np.ctypeslib.as_array(labels, shape=(nq, k))[:] = lab
+                    np.ctypeslib.as_array(dists, shape=(nq, k))[:] = dst
+                    np.ctypeslib.as_array(counts, shape=(nq,))[:] = cnt
+                    return 0
+                except Exception as ex:  # noqa: BLE001
+                    fail(ex, errp)
+                    return 1
+
+            self._keep = (BATCH_SEARCH_FN(tramp), FILTER_MAKE_FN(tramp_make), FILTER_FREE_FN(tramp_free), BATCH_SEARCH_EACH_FN(tramp_each))
+            self.s = _call("lantern_scan_server_start_filtered_fn", *self._keep, None, vec_bytes, host.encode(), port, max_batch, max_wait_us)
+        elif batch_fn is not None:
             def tramp(ctx, queries, nq, vb, k, ef, labels, dists, counts, errp):
                 try:
                     q = np.ctypeslib.as_array(C.cast(queries, C.POINTER(C.c_uint8)), shape=(nq, vb))
@@ -1178,6 +1295,11 @@ class ScanServer:
         v = [C.c_uint64() for _ in range(4)]
         lib().lantern_scan_server_stats(self.s, *[C.byref(x) for x in v])
         return dict(zip(("requests", "batches", "launches", "largest_batch"), (int(x.value) for x in v)))
+
+    def filter_stats(self):
+        v = [C.c_uint64() for _ in range(5)]
+        lib().lantern_scan_server_filter_stats(self.s, *[C.byref(x) for x in v])
+        return dict(zip(("filters_set", "filtered_requests", "each_calls", "most_distinct_filters", "resident_bytes"), (int(x.value) for x in v)))
 
     def timing(self):
         """Mean microseconds of a request on the server by leg (cumulative since start) and the number of requests."""
@@ -1217,6 +1339,14 @@ class ScanClient:
         dists = np.zeros(k, dtype=np.float32)
         n = _call("lantern_scan_client_search_next", self.c, _ptr(q), q.nbytes, k, ef, _ptr(labels), _ptr(dists))
         return labels[:n], dists[:n]
+
+    def set_filter(self, labels, skip_deleted=False) -> int:
+        """This connection's filter: the rows whose label is in `labels` (an empty list allows nothing).  Returns the allowed rows."""
+        L = np.ascontiguousarray(labels, dtype=np.uint64).ravel()
+        return int(_call("lantern_scan_client_set_filter", self.c, _ptr(L) if L.size else None, L.size, FILTER_SKIP_DELETED if skip_deleted else 0))
+
+    def clear_filter(self):
+        _call("lantern_scan_client_clear_filter", self.c)
 
     def close(self):
         if self.c:

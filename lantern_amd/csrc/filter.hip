@@ -155,6 +155,43 @@ constexpr size_t kFilteredLds = 160 * 1024;  // a workgroup's LDS
 constexpr size_t kFilteredLdsTarget = 64 * 1024;  // what the visited set may grow the walk's LDS to (two workgroups per CU)
 constexpr int    kFilteredWaves = 4;
 
+// The part of a filtered launch's shape that depends on (k, ef, skip, index) only -- not on the filter: exp, cand_cap, vis_slots /
+// rows_per_round and the LDS bytes.  false -> ix->err.
+static bool filtered_shape(Index *ix, bool exact, size_t k, size_t skip, size_t exp, FilteredArgs &a, size_t &lds)
+{
+    const int G = group_lanes_for(ix->chunks);
+    if(exact) {
+        a.exp = (uint32_t)(k + skip);
+        a.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / G);
+        lds = filtered_exact_lds_bytes(ix->chunks, a.exp, a.rows_per_round);
+        if(lds > kFilteredLds) {
+            set_err(ix, "lantern_gpu: k + skip exceed the 160 KiB LDS budget of the exact filtered search kernel");
+            return false;
+        }
+    } else {
+        a.exp = (uint32_t)exp;
+        const size_t base = filtered_walk_lds_bytes(ix->chunks, a.exp, 0, ix->M0, 0);
+        if(base + exp * 16 > kFilteredLds) {
+            set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the filtered search kernel");
+            return false;
+        }
+        size_t cap = ix->filter_cand_cap ? std::max(ix->filter_cand_cap, exp) : std::max<size_t>(4 * exp, 256);
+        cap = std::min(cap, (kFilteredLds - base) / 16);
+        if(ix->filter_cand_cap && cap < std::max(ix->filter_cand_cap, exp)) {
+            set_err(ix, "lantern_gpu: the candidate cap exceeds the 160 KiB LDS budget of the filtered search kernel");
+            return false;
+        }
+        a.cand_cap = (uint32_t)cap;
+        uint32_t vis_slots = 2048;
+        while(vis_slots && filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots) > kFilteredLdsTarget)
+            vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
+        if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
+        a.vis_slots = vis_slots;
+        lds = filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots);
+    }
+    return true;
+}
+
 // The caller holds ix->mu and has flushed.  false -> ix->err.
 static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
                                    float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, hipStream_t stream)
@@ -189,7 +226,6 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     // the path: forced, or the rule of DESIGN.md 4.9 -- a walk under selectivity s evaluates about D / s rows, the exact pass `allowed`
     bool exact = ix->filter_path == 2;
     if(ix->filter_path == 0) exact = (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
-    const int G = group_lanes_for(ix->chunks);
     FilteredArgs a{};
     a.view = ix->view();
     a.queries = d_q;
@@ -208,35 +244,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     a.out_E = d_E;
     a.totals = ix->d_totals;
     size_t lds = 0;
-    if(exact) {
-        a.exp = (uint32_t)(k + skip);
-        a.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / G);
-        lds = filtered_exact_lds_bytes(ix->chunks, a.exp, a.rows_per_round);
-        if(lds > kFilteredLds) {
-            set_err(ix, "lantern_gpu: k + skip exceed the 160 KiB LDS budget of the exact filtered search kernel");
-            return false;
-        }
-    } else {
-        a.exp = (uint32_t)exp;
-        const size_t base = filtered_walk_lds_bytes(ix->chunks, a.exp, 0, ix->M0, 0);
-        if(base + exp * 16 > kFilteredLds) {
-            set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the filtered search kernel");
-            return false;
-        }
-        size_t cap = ix->filter_cand_cap ? std::max(ix->filter_cand_cap, exp) : std::max<size_t>(4 * exp, 256);
-        cap = std::min(cap, (kFilteredLds - base) / 16);
-        if(ix->filter_cand_cap && cap < std::max(ix->filter_cand_cap, exp)) {
-            set_err(ix, "lantern_gpu: the candidate cap exceeds the 160 KiB LDS budget of the filtered search kernel");
-            return false;
-        }
-        a.cand_cap = (uint32_t)cap;
-        uint32_t vis_slots = 2048;
-        while(vis_slots && filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots) > kFilteredLdsTarget)
-            vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
-        if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
-        a.vis_slots = vis_slots;
-        lds = filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots);
-    }
+    if(!filtered_shape(ix, exact, k, skip, exp, a, lds)) return false;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
     const int grid = search_grid(ix, nq, kFilteredWaves, kFilteredWaves * per_cu);
     const int slot = acquire_search_slot(ix, stream, (size_t)grid);  // (orders the launch after inserts; the walk's visited bitmaps)
@@ -255,6 +263,148 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     (exact ? ix->c_filter_exact : ix->c_filter_walk) += 1;
     const uint32_t shape[ 6 ] = { exact ? 2u : 1u, (uint32_t)grid, a.exp, a.cand_cap, a.vis_slots, (uint32_t)lds };
     std::copy(std::begin(shape), std::end(shape), ix->last_filtered);
+    ix->c_search_queries += nq;
+    return true;
+}
+
+// ---- the per-query form: filters[i] is query i's filter ------------------------------------------------------------------------
+// bytes of the host block filtered_each_locked stages its selection lists and descriptor table in
+static size_t each_table_bytes(size_t nq) { return nq * (sizeof(FilterDesc) + 4) + 16; }
+
+static const char *kNotAFilter = "lantern_gpu: not a filter handle (stale, freed or foreign pointer)";
+
+// Every entry of filters[] is NULL or a live filter of this index at its present size; else ix->err names the first offender.
+static bool each_filters_ok(Index *ix, const Filter *const *filters, size_t nq)
+{
+    for(size_t i = 0; i < nq; ++i) {
+        const Filter *f = filters[ i ];
+        if(!f) continue;
+        if(f->magic != kFilterMagic) {
+            set_err(ix, std::string(kNotAFilter) + " (filters[" + std::to_string(i) + "])");
+            return false;
+        }
+        if(f->ix != ix) {
+            set_err(ix, "lantern_gpu: the filter belongs to another index (built over " + std::to_string(f->n) + " rows; this index holds " +
+                            std::to_string(ix->n) + ") (filters[" + std::to_string(i) + "])");
+            return false;
+        }
+        if(f->n != ix->n) {
+            set_err(ix, "lantern_gpu: stale filter: built when the index held " + std::to_string(f->n) + " rows, it now holds " + std::to_string(ix->n) +
+                            " (build the filter again) (filters[" + std::to_string(i) + "])");
+            return false;
+        }
+    }
+    if(ix->pq_compact) {
+        set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
+        return false;
+    }
+    return true;
+}
+
+// The caller holds ix->mu and has flushed.  The queries split into a walk group and an exact group by the path rule, evaluated per
+// query from its own filter's count; each group is ONE launch over its own selection list, and every answer lands in the caller's
+// row of its query.  Empty filters have no path: they ride in the exact launch (or, when nothing else takes the exact path, in the
+// walk launch), where a descriptor with count 0 gives the empty answer without touching a row.
+// `h_tbl`: a page-locked block of each_table_bytes(nq) that stays untouched until the stream work is done, or NULL (pageable
+// staging: the copies then complete before this returns).  false -> ix->err; nothing has been launched unless the failure is HIP's.
+static bool filtered_each_locked(Index *ix, const Filter *const *filters, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip,
+                                 uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
+                                 hipStream_t stream, char *h_tbl)
+{
+    if(!each_filters_ok(ix, filters, nq)) return false;
+    if(nq == 0 || k == 0) return true;
+    const size_t ef_sel = ef ? ef : ix->ef;
+    const size_t exp = std::max(ef_sel, k + skip);
+    std::vector<uint32_t> walk, exact, empty;
+    uint32_t              n_unfiltered = 0;
+    for(size_t i = 0; i < nq; ++i) {
+        const Filter *f = filters[ i ];
+        if(ix->n == 0 || (f && f->count == 0)) { empty.push_back((uint32_t)i); continue; }
+        if(!f) { n_unfiltered += 1; walk.push_back((uint32_t)i); continue; }
+        bool ex = ix->filter_path == 2;
+        if(ix->filter_path == 0) ex = (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
+        (ex ? exact : walk).push_back((uint32_t)i);
+    }
+    const uint32_t n_walk = (uint32_t)walk.size(), n_exact = (uint32_t)exact.size(), n_empty = (uint32_t)empty.size();
+    // the exact group's queries differ in length by orders of magnitude: longest first, so that the launch's tail is a short one
+    std::stable_sort(exact.begin(), exact.end(), [&](uint32_t x, uint32_t y) { return filters[ x ]->count > filters[ y ]->count; });
+    std::vector<uint32_t> &host = (exact.empty() && !walk.empty()) ? walk : exact;
+    host.insert(host.end(), empty.begin(), empty.end());
+    std::vector<const Filter *> distinct;
+    for(size_t i = 0; i < nq; ++i)
+        if(filters[ i ]) distinct.push_back(filters[ i ]);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+
+    FilteredArgs base{};
+    base.view = ix->view();
+    base.queries = d_q;
+    base.k = (uint32_t)k;
+    base.skip = (uint32_t)skip;
+    base.labels = ix->d_labels;
+    base.out_labels = d_labels;
+    base.out_dists = d_dists;
+    base.out_slots = d_slots;
+    base.out_counts = d_counts;
+    base.out_D = d_D;
+    base.out_E = d_E;
+    base.totals = ix->d_totals;
+    FilteredArgs aw = base, ae = base;
+    size_t       lds_w = 0, lds_e = 0;
+    if(!walk.empty() && !filtered_shape(ix, false, k, skip, exp, aw, lds_w)) return false;
+    if(!exact.empty() && !filtered_shape(ix, true, k, skip, exp, ae, lds_e)) return false;
+
+    // the host block: walk selection list | descriptor table (by query) | exact selection list -- each launch copies its list and
+    // the table in one piece into the scratch of its own launch slot
+    const size_t off_desc = ((size_t)walk.size() * 4 + 7) & ~(size_t)7, off_sel_e = off_desc + nq * sizeof(FilterDesc);
+    const size_t tbl_bytes = off_sel_e + exact.size() * 4;
+    std::vector<char> pageable;
+    if(!h_tbl) { pageable.resize(tbl_bytes); h_tbl = pageable.data(); }
+    if(!walk.empty()) std::memcpy(h_tbl, walk.data(), walk.size() * 4);
+    if(!exact.empty()) std::memcpy(h_tbl + off_sel_e, exact.data(), exact.size() * 4);
+    FilterDesc *const hd = (FilterDesc *)(h_tbl + off_desc);
+    for(size_t i = 0; i < nq; ++i) {
+        const Filter *f = filters[ i ];
+        hd[ i ] = f ? FilterDesc{ f->d_bits, f->d_slots, (uint32_t)f->count, 0u } : FilterDesc{ nullptr, nullptr, 0u, ix->n ? 1u : 0u };
+    }
+
+    uint32_t launches = 0;
+    for(int pass = 0; pass < 2; ++pass) {
+        const bool                   ex = pass == 1;
+        const std::vector<uint32_t> &sel = ex ? exact : walk;
+        if(sel.empty()) continue;
+        FilteredArgs &a = ex ? ae : aw;
+        const size_t  lds = ex ? lds_e : lds_w;
+        a.nq = (uint32_t)sel.size();
+        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
+        const int grid = search_grid(ix, sel.size(), kFilteredWaves, kFilteredWaves * per_cu);
+        const int slot = acquire_search_slot(ix, stream, (size_t)grid);
+        if(slot < 0) return false;
+        const size_t from = ex ? off_desc : 0, bytes = (ex ? tbl_bytes : off_sel_e) - from;
+        char *const  d_tbl = (char *)scratch(ix, 12 + 2 * Index::kLanes + slot, bytes);
+        if(!d_tbl) return false;
+        if(hipMemcpyAsync(d_tbl, h_tbl + from, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+            set_err(ix, "lantern_gpu: HIP failure (per-query filter table)");
+            return false;
+        }
+        a.descs = (const FilterDesc *)(d_tbl + (ex ? 0 : off_desc));
+        a.select = (const uint32_t *)(d_tbl + (ex ? nq * sizeof(FilterDesc) : 0));
+        a.bitmaps = ix->slot_bitmaps[ slot ];
+        a.bm_words = (uint32_t)ix->slot_words[ slot ];
+        a.undo_cap = vis_undo_cap();
+        a.ticket = next_ticket(ix, sel.size(), grid, stream);
+        const hipError_t e = ex ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
+                                : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
+        if(e != hipSuccess) {
+            set_err(ix, std::string("lantern_gpu: HIP error launching the filtered search: ") + hipGetErrorString(e));
+            return false;
+        }
+        if(!release_search_slot(ix, slot, stream)) return false;
+        (ex ? ix->c_filter_exact : ix->c_filter_walk) += 1;
+        launches += 1;
+    }
+    const uint32_t shape[ 6 ] = { n_walk, n_exact, n_unfiltered, n_empty, (uint32_t)distinct.size(), launches };
+    std::copy(std::begin(shape), std::end(shape), ix->last_each);
     ix->c_search_queries += nq;
     return true;
 }
@@ -321,8 +471,26 @@ static Index *FH(usearch_index_t h, usearch_error_t *e)
 static Filter *FF(const lantern_gpu_filter_t *f, usearch_error_t *e)
 {
     if(!f) { FAIL(e, "lantern_gpu: null filter handle"); return nullptr; }
-    if(((const Filter *)f)->magic != kFilterMagic) { FAIL(e, "lantern_gpu: not a filter handle (stale, freed or foreign pointer)"); return nullptr; }
+    if(((const Filter *)f)->magic != kFilterMagic) { FAIL(e, kNotAFilter); return nullptr; }
     return (Filter *)f;
+}
+
+// The handles of a per-query call: the filter array, then the index.  Whether every entry belongs to the index can only be told with the
+// index in hand (each_filters_ok, which names the first offender of any kind); without one, an entry that is no filter at all is
+// still worth naming.
+static Index *FHS(usearch_index_t h, const lantern_gpu_filter_t *const *filters, size_t nq, usearch_error_t *e)
+{
+    static thread_local std::string msg;
+    if(nq && !filters) { FAIL(e, "lantern_gpu: null filter array"); return nullptr; }
+    Index *ix = FH(h, e);
+    if(ix) return ix;
+    for(size_t i = 0; i < nq; ++i) {
+        if(!filters[ i ] || ((const Filter *)filters[ i ])->magic == kFilterMagic) continue;
+        msg = std::string(kNotAFilter) + " (filters[" + std::to_string(i) + "])";
+        FAIL(e, msg.c_str());
+        break;
+    }
+    return nullptr;
 }
 
 extern "C" {
@@ -371,6 +539,14 @@ try {
     CLEAR(e);
     const Filter *ff = FF(f, e);
     return ff ? ff->count : 0;
+}
+LANTERN_ABI_CATCH(e)
+
+size_t lantern_gpu_filter_resident_bytes(const lantern_gpu_filter_t *f, usearch_error_t *e)
+try {
+    CLEAR(e);
+    const Filter *ff = FF(f, e);
+    return ff ? ff->words * 4 + ff->count * 4 : 0;
 }
 LANTERN_ABI_CATCH(e)
 
@@ -472,6 +648,130 @@ try {
     std::memcpy(labels, h_out.data(), nq * k * 8);
     std::memcpy(distances, h_out.data() + nq * k * 8, nq * k * 4);
     if(counts) std::memcpy(counts, h_out.data() + nq * k * 12, nq * 4);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_last_filtered_each(usearch_index_t h, uint32_t out[ 6 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FH(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::copy(std::begin(ix->last_each), std::end(ix->last_each), out);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_filtered_each_device(usearch_index_t h, const lantern_gpu_filter_t *const *filters, const void *d_queries,
+                                                   size_t query_stride_bytes, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
+                                                   float *d_distances, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
+                                                   void *stream, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FHS(h, filters, nq, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)"); return; }
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    if(!filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts,
+                             d_D, d_E, (hipStream_t)stream, nullptr))
+        FAIL(e, ix->err.c_str());
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_filtered_each(usearch_index_t h, const lantern_gpu_filter_t *const *filters, const void *queries, size_t nq,
+                                            usearch_scalar_kind_t kind, size_t k, size_t ef, usearch_label_t *labels, float *distances,
+                                            uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FHS(h, filters, nq, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    if(!each_filters_ok(ix, (const Filter *const *)filters, nq)) { FAIL(e, ix->err.c_str()); return; }
+    if(nq == 0 || k == 0) return;
+    const size_t row_words = (size_t)ix->chunks * 4;
+    std::vector<uint32_t> padded(nq * row_words);
+    pad_rows(ix, queries, (int)kind, nq, padded.data());
+    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
+    char *dq = (char *)scratch(ix, 5, q_bytes);
+    char *dout = (char *)scratch(ix, 6, out_bytes + 64);
+    if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
+    uint64_t *d_lab = (uint64_t *)dout;
+    float    *d_dist = (float *)(dout + nq * k * 8);
+    uint32_t *d_cnt = (uint32_t *)(dout + nq * k * 12);
+    std::vector<char> h_out(out_bytes);
+    bool ok = hipMemcpyAsync(dq, padded.data(), q_bytes, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
+    ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)dq, nq, k, ef, 0, d_lab, d_dist, nullptr, d_cnt, nullptr, nullptr,
+                                    ix->stream, nullptr);
+    ok = ok && hipMemcpyAsync(h_out.data(), dout, out_bytes, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
+    if(!ok) {
+        if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during filtered batched search");
+        FAIL(e, ix->err.c_str());
+        return;
+    }
+    std::memcpy(labels, h_out.data(), nq * k * 8);
+    std::memcpy(distances, h_out.data() + nq * k * 8, nq * k * 4);
+    if(counts) std::memcpy(counts, h_out.data() + nq * k * 12, nq * 4);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+// lantern_gpu_search_batch_lane with a filter per query: the lane's stream and page-locked block (queries | answers | the selection
+// lists and descriptor table), the index mutex held only while the copies and the launches are queued, the wait outside it.
+void lantern_gpu_search_batch_filtered_each_lane(usearch_index_t h, int lane, const lantern_gpu_filter_t *const *filters, const void *queries,
+                                                 size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef, usearch_label_t *labels,
+                                                 float *distances, uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    Index *ix = FHS(h, filters, nq, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null buffer"); return; }
+    static thread_local std::string msg;  // (a lane's error text belongs to the calling thread: lantern_gpu_search_batch_lane)
+    msg.clear();
+    const size_t row_words = (size_t)ix->chunks * 4;
+    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
+    const size_t out_at = (q_bytes + 63) & ~(size_t)63, tbl_at = (out_at + out_bytes + 63) & ~(size_t)63;
+    char        *hs = nullptr;
+    if(nq && k) {
+        hs = host_stage(ix, lane, tbl_at + each_table_bytes(nq));
+        if(!hs) { FAIL(e, "lantern_gpu: cannot allocate the lane's page-locked staging block"); return; }
+        pad_rows(ix, queries, (int)kind, nq, (uint32_t *)hs);
+    }
+    hipStream_t st = nullptr;
+    bool        ok = true;
+    {
+        std::lock_guard<std::mutex> g(ix->mu);
+        if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        ix->err.clear();
+        if(!each_filters_ok(ix, (const Filter *const *)filters, nq)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        if(nq == 0 || k == 0) return;
+        if(!ix->lane_stream[ lane ] && hipStreamCreateWithFlags(&ix->lane_stream[ lane ], hipStreamNonBlocking) != hipSuccess) {
+            FAIL(e, "lantern_gpu: cannot create the lane's stream");
+            return;
+        }
+        st = ix->lane_stream[ lane ];
+        char *dq = (char *)scratch(ix, 12 + 2 * lane, q_bytes);
+        char *dout = (char *)scratch(ix, 13 + 2 * lane, out_bytes + 64);
+        if(!dq || !dout) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        ok = hipMemcpyAsync(dq, hs, q_bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+        ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)dq, nq, k, ef, 0, (uint64_t *)dout, (float *)(dout + nq * k * 8),
+                                        nullptr, (uint32_t *)(dout + nq * k * 12), nullptr, nullptr, st, hs + tbl_at);
+        ok = ok && hipMemcpyAsync(hs + out_at, dout, out_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if(!ok) msg = ix->err.empty() ? "lantern_gpu: HIP failure during filtered batched search" : ix->err;
+    }
+    // (whatever was queued is waited for even after a failure: the filters may be freed once this returns)
+    if(hipStreamSynchronize(st) != hipSuccess && ok) { ok = false; msg = "lantern_gpu: HIP failure during filtered batched search"; }
+    if(!ok) { FAIL(e, msg.c_str()); return; }
+    std::memcpy(labels, hs + out_at, nq * k * 8);
+    std::memcpy(distances, hs + out_at + nq * k * 8, nq * k * 4);
+    if(counts) std::memcpy(counts, hs + out_at + nq * k * 12, nq * 4);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

@@ -27,6 +27,15 @@ struct Filter
     size_t    count = 0;            // popcount of the bitmap
 };
 
+// One query's filter in the per-query form of the two kernels (FilteredArgs::descs): what FilteredArgs::allow_* are to a whole launch.
+struct FilterDesc
+{
+    const uint32_t *bits;        // the filter's bitmap (unused when `unfiltered`)
+    const uint32_t *slots;       // [count] the allowed slots, ascending (exact only)
+    uint32_t        count;       // allowed slots; 0 without `unfiltered`: an empty filter, the empty answer
+    uint32_t        unfiltered;  // != 0: every slot is allowed and there is no bitmap (a NULL entry of the caller's filter array)
+};
+
 // kernel arguments of both filtered kernels.  Fields are re-read from the kernarg segment at the points of a query that need them
 // (search_kernel.hpp "kernarg re-read").
 struct FilteredArgs
@@ -53,6 +62,10 @@ struct FilteredArgs
     uint32_t        vis_slots;
     unsigned long long *totals;  // [2] cumulative D, E or NULL
     uint32_t       *ticket;      // zeroed before the launch, or NULL (static striding)
+    // the per-query form (descs != NULL; allow_* unused): `nq` counts the entries of `select`, every output row is indexed by the
+    // query a position selects, and that query's filter is descs[query]
+    const FilterDesc *descs;     // [queries of the call]
+    const uint32_t   *select;    // [nq] ticket position -> query
 };
 
 size_t     filtered_walk_lds_bytes(uint32_t chunks, uint32_t exp, uint32_t cand_cap, uint32_t M0, uint32_t vis_slots);

@@ -349,7 +349,7 @@ bool pad_row(const Index *ix, const void *vec, int kind_in, uint32_t *dst)
 // `count` caller rows into their padded, stored form (pad_row each).  A batch in the thousands is the host's largest share of a
 // lantern_gpu_search_batch call -- 8192 x 768-d rows are 25 MB through one core: 2.5 ms beside a 6.6 ms search -- so large batches are
 // split over a few short-lived threads (rows are independent; measured in round 5: one call at a time 0.77 -> see DESIGN.md 4.6b).
-static void pad_rows(const Index *ix, const void *rows, int kind, size_t count, uint32_t *padded)
+void pad_rows(const Index *ix, const void *rows, int kind, size_t count, uint32_t *padded)
 {
     const size_t row_words = (size_t)ix->chunks * 4, in_bytes = input_bytes(ix, kind);
     auto span = [&](size_t lo, size_t hi) {
@@ -2141,7 +2141,7 @@ try {
 LANTERN_ABI_CATCH_VOID(e)
 
 // the page-locked staging block `which` (0 .. kLanes - 1: the lanes, kLanes: lantern_gpu_search_batch), grown on demand; nullptr on failure
-static char *host_stage(Index *ix, int which, size_t need)
+extern "C++" char *lgpu::host_stage(Index *ix, int which, size_t need)
 try {
     if(ix->lane_host_bytes[ which ] < need) {
         if(ix->lane_host[ which ]) (void)hipHostFree(ix->lane_host[ which ]);

@@ -95,8 +95,10 @@ struct Index
 
     // scratch (grown on demand)
     static const int kLanes = 8;  // lantern_gpu_search_batch_lane: batches one caller each may keep in flight side by side
-    void  *d_scratch[ 12 + 2 * kLanes ] = {};  // [12 ..]: queries / answers of the lanes of lantern_gpu_search_batch_lane
-    size_t scratch_bytes[ 12 + 2 * kLanes ] = {};
+    // [12 ..]: queries / answers of the lanes of lantern_gpu_search_batch_lane; [12 + 2 kLanes ..]: one per launch slot (kSearchSlots), the
+    // selection list and descriptor table of a per-query filtered launch (filter.hip)
+    void  *d_scratch[ 12 + 3 * kLanes ] = {};
+    size_t scratch_bytes[ 12 + 3 * kLanes ] = {};
     hipStream_t lane_stream[ kLanes ] = {};  // created on first use
     char       *lane_host[ kLanes + 1 ] = {};  // page-locked staging of queries and answers: the lanes (one caller each), [kLanes] lantern_gpu_search_batch (under mu)
     size_t      lane_host_bytes[ kLanes + 1 ] = {};
@@ -195,6 +197,7 @@ struct Index
     size_t   filter_cand_cap = 0;       // 0: max(4 expansion, 256), capped by LDS
     double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
     uint64_t c_filter_walk = 0, c_filter_exact = 0;
+    uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches
     uint32_t last_filtered[ 6 ] = {};  // path, grid, expansion, cand_cap, vis_slots, LDS bytes of the last filtered launch (lantern_gpu_last_filtered_launch)
 
     hipStream_t stream = nullptr;
@@ -218,6 +221,8 @@ void       *scratch(Index *ix, int which, size_t bytes);
 bool        pad_row(const Index *ix, const void *vec, int kind_in, uint32_t *dst);
 size_t      input_bytes(const Index *ix, int kind_in);
 bool        kind_accepted(const Index *ix, int kind_in);
+char       *host_stage(Index *ix, int which, size_t need);  // page-locked staging block of a lane ([kLanes]: the index stream's, under mu), grown on demand
+void        pad_rows(const Index *ix, const void *rows, int kind, size_t count, uint32_t *padded);
 uint32_t   *next_ticket(Index *ix, size_t work, int grid, hipStream_t stream);  // a zeroed work ticket of a persistent launch, or NULL
 uint32_t    vis_undo_cap();
 int         search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu);

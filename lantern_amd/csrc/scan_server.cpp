@@ -15,6 +15,22 @@
 //             the same query (usearch_search_ef(streaming = true), scan.c:273-281)
 //   server -> u32 0x5052534C ("LSRP"), u32 status (0 = ok), u32 count, count x u64 labels, count x f32 distances
 //             status != 0: u32 length, message
+//   client -> u32 0x4652534C ("LSRF"), u32 flags, u64 count, count x u64 labels: SET THE CONNECTION'S FILTER to the rows whose label is
+//             in the list (lantern_gpu_filter_from_labels).  flags: bit 0 = LANTERN_GPU_FILTER_SKIP_DELETED, bit 31 = CLEAR (count must
+//             be 0: the connection is unfiltered again).  An empty list without CLEAR is a valid filter that allows nothing.
+//   server -> u32 "LSRP", u32 status 0, u32 0, u64 allowed rows -- or the error frame above (status != 0: u32 length, message)
+// The filter belongs to the CONNECTION, like the continuation state: every later "LSRQ" / "LSRC" of the connection is searched
+// through it, until it is replaced, cleared or the connection closes (the server then releases it).  A filter message that is
+// answered with status 0 ends the connection's current scan (its hand-out history is dropped); one that is answered with an error
+// changes nothing: the previous filter, if any, stays in force.  Limits: a message carries at most kMaxFilterLabels labels -- beyond
+// that the error frame goes out at once and the connection is CLOSED (its payload is not read); the filters resident on the
+// server may take LANTERN_SCAN_FILTER_BYTES (default 1 GiB) of device memory -- a filter that would exceed it is refused with an
+// error frame after its payload has been read, and the connection survives.  A back end without filters
+// (lantern_scan_server_start_fn) answers every filter message with an error frame; the connection survives.  A filter gone stale
+// (the served index grew) makes the connection's searches come back as error frames carrying the library's message until the
+// backend sends its filter again.
+// Filters are built and released on a thread of their own (device allocation and a sort: milliseconds), never on an I/O thread;
+// a large message is read in slices between which the I/O thread serves its other connections.
 // A connection carries one request at a time (a backend runs one scan step at a time) and stays open across requests.
 // The continuation state -- which rows this scan has been handed since its last "LSRQ" -- belongs to the CONNECTION
 // (one backend, one scan at a time), never to the shared index: any number of backends paginate concurrently.  A
@@ -67,7 +83,10 @@
 
 namespace {
 
-constexpr uint32_t REQ_MAGIC = 0x5152534Cu, CONT_MAGIC = 0x4352534Cu, REP_MAGIC = 0x5052534Cu;
+constexpr uint32_t REQ_MAGIC = 0x5152534Cu, CONT_MAGIC = 0x4352534Cu, REP_MAGIC = 0x5052534Cu, FILTER_MAGIC = 0x4652534Cu;
+constexpr uint32_t FILTER_CLEAR = 0x80000000u;            // flags of a filter message: bit 31 (bit 0: LANTERN_GPU_FILTER_SKIP_DELETED)
+constexpr uint64_t kMaxFilterLabels = (uint64_t)1 << 24;  // labels per filter message (128 MiB of payload)
+constexpr size_t   kFilterSlice = (size_t)1 << 20;        // bytes of a filter message one visit of an I/O thread reads
 constexpr uint32_t MAX_K = 4096, MAX_VEC_BYTES = 1u << 20;
 
 bool read_exact(int fd, void *buf, size_t n)
@@ -133,6 +152,10 @@ struct Conn
     bool                 cont = false;
     uint32_t             want = 0, k = 0, ef = 0;  // rows the client asked for; rows the search is asked for (handed out + want)
     std::vector<uint8_t> vec;
+    // its filter (set by the filter thread while the connection is disarmed; read by the dispatcher that has it in a batch)
+    void                *filter = nullptr;
+    uint64_t             filter_bytes = 0;
+    uint32_t             fflags = 0;  // the outstanding filter message: its flags (its labels are in `vec`)
     uint64_t             t_read = 0, t_closed = 0;  // ns: its request was read / its batch closed (lantern_scan_server_timing)
     // this connection's scan: labels handed out since its last fresh request, and how many label-0 rows among them
     std::unordered_set<uint64_t> seen;
@@ -146,6 +169,7 @@ struct Done
     bool                  gone = false;  // the dispatcher answered it itself and the write failed: only the connection's end is left to do
     uint64_t              t_known = 0;  // ns: when the dispatcher learnt the answer
     std::string           error;  // non-empty: an error frame
+    std::vector<uint8_t>  raw;    // non-empty: the reply as it goes out (a filter message's)
     std::vector<uint64_t> labels;
     std::vector<float>    dists;
 };
@@ -168,6 +192,17 @@ struct lantern_scan_server
 {
     lantern_batch_search_fn fn = nullptr;
     void                   *fn_ctx = nullptr;
+    // filters: how the back end makes, frees and searches through them (all NULL: a back end without filters)
+    lantern_scan_filter_make_fn  f_make = nullptr;
+    lantern_scan_filter_free_fn  f_free = nullptr;
+    lantern_batch_search_each_fn f_each = nullptr;
+    struct FilterJob { Conn *c = nullptr; void *release = nullptr; uint64_t release_bytes = 0; };  // a connection's message, or a filter to release
+    std::thread             filter_thread;
+    std::mutex              fmu;
+    std::condition_variable fcv;
+    std::deque<FilterJob>   fjobs;
+    uint64_t                filter_budget = (uint64_t)1 << 30;
+    std::atomic<uint64_t>   n_filters_set{ 0 }, n_filtered{ 0 }, n_each_calls{ 0 }, max_distinct{ 0 }, filter_resident{ 0 };
     usearch_index_t         index = nullptr;  // the default backend: lantern_gpu_search_batch on this index
     usearch_scalar_kind_t   kind = usearch_scalar_f32_k;
     size_t                  vec_bytes = 0, max_batch = 256;
@@ -208,6 +243,28 @@ int default_backend(void *ctx, const void *queries, size_t nq, size_t, size_t k,
     return 0;
 }
 
+void *default_filter_make(void *ctx, const uint64_t *labels, size_t n, uint32_t flags, uint64_t *allowed, uint64_t *bytes, const char **err)
+{
+    lantern_scan_server  *s = (lantern_scan_server *)ctx;
+    usearch_error_t       e = nullptr;
+    lantern_gpu_filter_t *f = lantern_gpu_filter_from_labels(s->index, labels, n, flags, &e);
+    if(!f) { *err = e ? e : "lantern_scan_server: cannot build the filter"; return nullptr; }
+    *allowed = lantern_gpu_filter_count(f, &e);
+    *bytes = lantern_gpu_filter_resident_bytes(f, &e);
+    return f;
+}
+void default_filter_free(void *, void *f) { lantern_gpu_filter_free((lantern_gpu_filter_t *)f); }
+int default_search_each(void *ctx, const void *const *filters, const void *queries, size_t nq, size_t, size_t k, size_t ef, uint64_t *labels,
+                        float *dists, uint32_t *counts, const char **err)
+{
+    lantern_scan_server *s = (lantern_scan_server *)ctx;
+    usearch_error_t      e = nullptr;
+    lantern_gpu_search_batch_filtered_each_lane(s->index, tl_lane, (const lantern_gpu_filter_t *const *)filters, queries, nq, s->kind, k, ef, labels,
+                                                dists, counts, &e);
+    if(e) { *err = e; return 1; }
+    return 0;
+}
+
 bool reply_error(int fd, const std::string &msg)
 {
     uint32_t head[ 3 ] = { REP_MAGIC, 1u, (uint32_t)msg.size() };
@@ -228,6 +285,17 @@ bool arm(IoThread *t, Conn *c, int op)
 void drop(lantern_scan_server *s, IoThread *t, Conn *c)
 {
     const int fd = c->fd;
+    if(c->filter) {  // released by the filter thread: freeing device memory may wait for the device
+        {
+            std::lock_guard<std::mutex> g(s->fmu);
+            lantern_scan_server::FilterJob job;
+            job.release = c->filter;
+            job.release_bytes = c->filter_bytes;
+            s->fjobs.push_back(job);
+        }
+        s->fcv.notify_one();
+        c->filter = nullptr;
+    }
     ::epoll_ctl(t->epfd, EPOLL_CTL_DEL, fd, nullptr);
     t->conns.erase(fd);  // (frees c)
     {
@@ -242,24 +310,58 @@ void drop(lantern_scan_server *s, IoThread *t, Conn *c)
 // Reads what the socket holds of the connection's next request -- never past its end: a valid request is 16 + vec_bytes long, and
 // a connection's following request stays in the socket until the connection is armed again.  1 = a complete, valid request is
 // in c (vec, k, ef, want); 0 = not yet, or an error frame went out and the connection waits for its next request: re-arm;
-// -1 = the connection is over.
+// -1 = the connection is over; 2 = a complete filter message is in c (fflags; vec = its labels).
+// A filter message has a 16-byte head too (magic, flags, u64 count) and may be megabytes long: one visit reads at most kFilterSlice
+// of it, then the connection is re-armed (its socket still readable, it comes up again behind whatever else is ready).
 int read_request(lantern_scan_server *s, Conn *c)
 {
+    size_t visit = 0;
+    bool   is_filter = false;
     for(;;) {
         size_t goal = 16 + s->vec_bytes;
         if(c->in.size() >= 16) {
-            uint32_t nbytes;
-            std::memcpy(&nbytes, c->in.data() + 12, 4);
-            if(nbytes > MAX_VEC_BYTES) { reply_error(c->fd, "lantern_scan_server: vector too large"); return -1; }
-            goal = 16 + (size_t)nbytes;
+            uint32_t magic, nbytes;
+            std::memcpy(&magic, c->in.data(), 4);
+            is_filter = magic == FILTER_MAGIC;
+            if(is_filter) {
+                uint64_t count;
+                std::memcpy(&count, c->in.data() + 8, 8);
+                if(count > kMaxFilterLabels) {
+                    reply_error(c->fd, "lantern_scan_server: a filter message carries at most " + std::to_string(kMaxFilterLabels) + " labels; this one announces " +
+                                           std::to_string(count) + " (the connection is closed)");
+                    return -1;
+                }
+                goal = 16 + (size_t)count * 8;
+            } else {
+                std::memcpy(&nbytes, c->in.data() + 12, 4);
+                if(nbytes > MAX_VEC_BYTES) { reply_error(c->fd, "lantern_scan_server: vector too large"); return -1; }
+                goal = 16 + (size_t)nbytes;
+            }
             if(c->in.size() >= goal) break;
+            if(is_filter && visit >= kFilterSlice) return 0;
         }
-        uint8_t       tmp[ 16384 ];
+        uint8_t       tmp[ 65536 ];
         const ssize_t r = ::recv(c->fd, tmp, std::min(sizeof(tmp), goal - c->in.size()), MSG_DONTWAIT);
-        if(r > 0) c->in.insert(c->in.end(), tmp, tmp + r);
+        if(r > 0) { c->in.insert(c->in.end(), tmp, tmp + r); visit += (size_t)r; }
         else if(r == 0) return -1;  // peer closed
         else if(errno == EAGAIN || errno == EWOULDBLOCK) return 0;
         else if(errno != EINTR) return -1;
+    }
+    if(is_filter) {
+        uint32_t flags;
+        uint64_t count;
+        std::memcpy(&flags, c->in.data() + 4, 4);
+        std::memcpy(&count, c->in.data() + 8, 8);
+        const size_t len = 16 + (size_t)count * 8;
+        c->vec.assign(c->in.begin() + 16, c->in.begin() + (ptrdiff_t)len);
+        c->in.erase(c->in.begin(), c->in.begin() + (ptrdiff_t)len);
+        c->in.shrink_to_fit();
+        if((flags & ~(FILTER_CLEAR | (uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED)) || ((flags & FILTER_CLEAR) && count))
+            return reply_error(c->fd, "lantern_scan_server: bad filter flags (bit 0: skip deleted rows; bit 31: clear, with no labels)") ? 0 : -1;
+        if(!s->f_make)
+            return reply_error(c->fd, "lantern_scan_server: this back end has no filters (lantern_scan_server_start_fn)") ? 0 : -1;
+        c->fflags = flags;
+        return 2;
     }
     uint32_t head[ 4 ];
     std::memcpy(head, c->in.data(), 16);
@@ -317,12 +419,26 @@ void io_loop(lantern_scan_server *s, IoThread *t)
         const int n = ::epoll_wait(t->epfd, events, 256, -1);
         if(n < 0 && errno != EINTR) return;
         size_t queued = 0;
-        for(int i = 0; i < n; ++i) {
-            Conn *c = (Conn *)events[ i ].data.ptr;
-            if(c) {  // a connection with something to read
+        // a connection with something to read (or, behind a filter message's reply, with the head of its next message already here:
+        // the read of a short filter message may have taken up to a request's length)
+        auto serve = [&](Conn *c) {
+            {
                 const int got = read_request(s, c);
                 if(got < 0) drop(s, t, c);
                 else if(got == 0) { if(!arm(t, c, EPOLL_CTL_MOD)) drop(s, t, c); }
+                else if(got == 2) {  // a filter message: to the filter thread; the connection stays disarmed until its reply is written
+                    {
+                        std::lock_guard<std::mutex> g(s->mu);
+                        s->in_flight += 1;  // (accounted for: nobody waits for this connection to join a batch)
+                    }
+                    {
+                        std::lock_guard<std::mutex> g(s->fmu);
+                        lantern_scan_server::FilterJob job;
+                        job.c = c;
+                        s->fjobs.push_back(job);
+                    }
+                    s->fcv.notify_one();
+                }
                 else {
                     s->n_requests += 1;
                     c->t_read = now_ns();
@@ -330,6 +446,12 @@ void io_loop(lantern_scan_server *s, IoThread *t)
                     s->queue.push_back(c);
                     ++queued;
                 }
+            }
+        };
+        for(int i = 0; i < n; ++i) {
+            Conn *c = (Conn *)events[ i ].data.ptr;
+            if(c) {
+                serve(c);
                 continue;
             }
             // the event descriptor: answers to write, connections to adopt, or the end
@@ -348,13 +470,85 @@ void io_loop(lantern_scan_server *s, IoThread *t)
             }
             fresh.clear();
             for(Done &d : done) {
-                const bool sent = !d.gone && (d.error.empty() ? reply_rows(d.c, d.labels.data(), d.dists.data(), d.labels.size()) : reply_error(d.c->fd, d.error));
+                const bool sent = !d.gone && (!d.raw.empty()     ? write_answer(d.c->fd, d.raw.data(), d.raw.size())
+                                              : d.error.empty() ? reply_rows(d.c, d.labels.data(), d.dists.data(), d.labels.size())
+                                                                : reply_error(d.c->fd, d.error));
                 if(d.t_known) s->t_reply_ns += now_ns() - d.t_known;
-                if(!sent || !arm(t, d.c, EPOLL_CTL_MOD)) drop(s, t, d.c);  // answered: the connection may speak again
+                if(!sent) drop(s, t, d.c);
+                else if(!d.c->in.empty()) serve(d.c);
+                else if(!arm(t, d.c, EPOLL_CTL_MOD)) drop(s, t, d.c);  // answered: the connection may speak again
             }
             done.clear();
         }
         if(queued) s->cv.notify_all();  // one wake-up for everything this round read
+    }
+}
+
+// The filter thread: builds the filter of a connection's message (transactionally: the previous filter stays until the new one
+// stands) and releases the filters of connections that closed.  The connection of a message is disarmed and in no batch -- a
+// backend has one request outstanding -- so this thread is its only holder: no batch that holds a filter is being searched while
+// the filter is replaced or released.
+void filter_loop(lantern_scan_server *s)
+{
+    for(;;) {
+        lantern_scan_server::FilterJob job;
+        {
+            std::unique_lock<std::mutex> lk(s->fmu);
+            s->fcv.wait(lk, [&] { return s->stop.load() || !s->fjobs.empty(); });
+            if(s->fjobs.empty()) return;  // (stop: what is queued is still worked off, then lantern_scan_server_stop cleans up)
+            job = s->fjobs.front();
+            s->fjobs.pop_front();
+        }
+        if(job.release) {
+            s->f_free(s->fn_ctx, job.release);
+            s->filter_resident -= job.release_bytes;
+            continue;
+        }
+        Conn *c = job.c;
+        Done  d;
+        d.c = c;
+        void    *made = nullptr;
+        uint64_t allowed = 0, bytes = 0;
+        if(!(c->fflags & FILTER_CLEAR)) {
+            const char *err = nullptr;
+            made = s->f_make(s->fn_ctx, (const uint64_t *)c->vec.data(), c->vec.size() / 8, c->fflags & ~FILTER_CLEAR, &allowed, &bytes, &err);
+            if(!made) d.error = err ? err : "lantern_scan_server: cannot build the filter";
+            else if(s->filter_resident.load() - c->filter_bytes + bytes > s->filter_budget) {
+                s->f_free(s->fn_ctx, made);
+                made = nullptr;
+                d.error = "lantern_scan_server: the filter needs " + std::to_string(bytes) + " bytes; " + std::to_string(s->filter_resident.load()) +
+                          " of the server's budget of " + std::to_string(s->filter_budget) + " are in use (LANTERN_SCAN_FILTER_BYTES)";
+            }
+        }
+        std::vector<uint8_t>().swap(c->vec);
+        if(d.error.empty()) {
+            if(c->filter) {
+                s->f_free(s->fn_ctx, c->filter);
+                s->filter_resident -= c->filter_bytes;
+            }
+            c->filter = made;
+            c->filter_bytes = made ? bytes : 0;
+            s->filter_resident += c->filter_bytes;
+            if(made) s->n_filters_set += 1;
+            c->seen.clear();  // the connection's scan is over
+            c->seen_zero = 0;
+            const uint32_t head[ 3 ] = { REP_MAGIC, 0u, 0u };
+            d.raw.resize(20);
+            std::memcpy(d.raw.data(), head, 12);
+            std::memcpy(d.raw.data() + 12, &allowed, 8);
+        }
+        IoThread *t = s->io[ (size_t)c->io ].get();
+        {
+            std::lock_guard<std::mutex> g(t->mu);
+            t->done.push_back(std::move(d));
+        }
+        const uint64_t one = 1;
+        (void)!::write(t->evfd, &one, 8);
+        {
+            std::lock_guard<std::mutex> g(s->mu);
+            s->in_flight -= 1;
+        }
+        s->cv.notify_all();
     }
 }
 
@@ -418,15 +612,18 @@ void dispatch_loop(lantern_scan_server *s, int lane)
         uint64_t seen = s->max_batch_seen.load();
         while(batch.size() > seen && !s->max_batch_seen.compare_exchange_weak(seen, batch.size())) {}
         // one launch per distinct (k, ef): scans of one workload share them (init_k, the ef GUC)
-        std::map<std::pair<uint32_t, uint32_t>, std::vector<size_t>> groups;
-        for(size_t i = 0; i < batch.size(); ++i) groups[ { batch[ i ]->k, batch[ i ]->ef } ].push_back(i);
+        // ... and within (k, ef) the requests of connections with a filter go out TOGETHER, whatever their filters, in one per-query
+        // call (lantern_gpu_search_batch_filtered_each_lane); the unfiltered ones take the path they always took
+        std::map<std::pair<std::pair<uint32_t, uint32_t>, int>, std::vector<size_t>> groups;
+        for(size_t i = 0; i < batch.size(); ++i) groups[ { { batch[ i ]->k, batch[ i ]->ef }, batch[ i ]->filter ? 1 : 0 } ].push_back(i);
         touched.assign(s->io.size(), 0);
         // A handful of answers the dispatcher writes itself (a disarmed connection has one holder at a time, and this is it):
         // one thread hand-off less on the path of a lone backend.  Larger batches go back to the I/O threads, whose sends
         // run side by side.
         const bool direct = batch.size() <= 8;
         for(auto &kv : groups) {
-            const size_t k = kv.first.first, ef = kv.first.second, nq = kv.second.size();
+            const size_t k = kv.first.first.first, ef = kv.first.first.second, nq = kv.second.size();
+            const bool   filtered = kv.first.second != 0;
             qbuf.resize(nq * s->vec_bytes);
             for(size_t j = 0; j < nq; ++j) std::memcpy(&qbuf[ j * s->vec_bytes ], batch[ kv.second[ j ] ]->vec.data(), s->vec_bytes);
             labels.assign(nq * k, 0);
@@ -478,7 +675,33 @@ void dispatch_loop(lantern_scan_server *s, int lane)
                 s->in_flight -= count;
             };
             const char *err = nullptr;
-            if(s->notify) {
+            if(filtered) {
+                std::vector<const void *> fl(nq);
+                for(size_t j = 0; j < nq; ++j) fl[ j ] = batch[ kv.second[ j ] ]->filter;
+                {
+                    std::vector<const void *> u(fl);
+                    std::sort(u.begin(), u.end());
+                    const uint64_t distinct = (uint64_t)(std::unique(u.begin(), u.end()) - u.begin());
+                    uint64_t       seen_d = s->max_distinct.load();
+                    while(distinct > seen_d && !s->max_distinct.compare_exchange_weak(seen_d, distinct)) {}
+                }
+                s->n_filtered += nq;
+                s->n_each_calls += 1;
+                rc = s->f_each(s->fn_ctx, fl.data(), qbuf.data(), nq, s->vec_bytes, k, ef, labels.data(), dists.data(), counts.data(), &err);
+                if(rc != 0 && nq > 1) {
+                    // one bad filter (stale: the index grew since it was built) refuses the whole call: ask again one by one, so that
+                    // only the connections whose filter is at fault get the error frame
+                    for(size_t j = 0; j < nq; ++j) {
+                        const char *err1 = nullptr;
+                        s->n_each_calls += 1;
+                        rc = s->f_each(s->fn_ctx, &fl[ j ], &qbuf[ j * s->vec_bytes ], 1, s->vec_bytes, k, ef, &labels[ j * k ], &dists[ j * k ], &counts[ j ], &err1);
+                        if(rc != 0) msg = std::string(err1 ? err1 : "lantern_scan_server: the batch search failed");
+                        const uint32_t which = (uint32_t)j;
+                        deliver(&which, 1);
+                    }
+                    rc = 0;
+                }
+            } else if(s->notify) {
                 // the device index: every answer goes back when ITS walk ends, not when the batch's longest one does
                 // (lantern_gpu_search_batch_lane_notify; the callback runs on this thread)
                 struct Ctx { decltype(deliver) *fn; } cx{ &deliver };
@@ -592,6 +815,8 @@ lantern_scan_server *start_common(lantern_scan_server *s, const char *host, int 
         return nullptr;
     }
     for(auto &t : s->io) t->t = std::thread(io_loop, s, t.get());
+    if(const char *fb = std::getenv("LANTERN_SCAN_FILTER_BYTES")) s->filter_budget = std::strtoull(fb, nullptr, 10);
+    if(s->f_make) s->filter_thread = std::thread(filter_loop, s);
     for(int l = 0; l < s->lanes; ++l) s->dispatch_thread[ l ] = std::thread(dispatch_loop, s, l);
     s->accept_thread = std::thread(accept_loop, s);
     return s;
@@ -623,6 +848,9 @@ try {
     s->vec_bytes = ham ? (m.dimensions + 7) / 8 : m.dimensions * 4;
     s->fn = default_backend;
     s->fn_ctx = s;
+    s->f_make = default_filter_make;
+    s->f_free = default_filter_free;
+    s->f_each = default_search_each;
     // dispatchers = lanes of lantern_gpu_search_batch_lane (up to four batches in flight on the device, each in its own slab of
     // visited bitmaps).  Default four; LANTERN_SCAN_LANES = 1 .. 8.  Measured with lantern-scan-load on 100k x 128 (round 4,
     // profiles/r04_scan_load_lanes.jsonl; lanes 1 / 2 / 3 / 4): 16 backends p50 201 / 214 / 193 / 173 us, 64: 301 / 243 / 235 / 227 us,
@@ -667,7 +895,36 @@ try {
 }
 LANTERN_ABI_CATCH(e)
 
+lantern_scan_server_t *lantern_scan_server_start_filtered_fn(lantern_batch_search_fn fn, lantern_scan_filter_make_fn make, lantern_scan_filter_free_fn free_fn,
+                                                             lantern_batch_search_each_fn each, void *ctx, size_t vec_bytes, const char *host, int port,
+                                                             size_t max_batch, unsigned max_wait_us, usearch_error_t *e)
+try {
+    if(e) *e = nullptr;
+    if(!fn || !make || !free_fn || !each || vec_bytes == 0 || vec_bytes > MAX_VEC_BYTES) { if(e) *e = "lantern_gpu: bad scan server arguments"; return nullptr; }
+    lantern_scan_server *s = new lantern_scan_server();
+    s->fn = fn;
+    s->fn_ctx = ctx;
+    s->f_make = make;
+    s->f_free = free_fn;
+    s->f_each = each;
+    s->vec_bytes = vec_bytes;
+    if(const char *ln = std::getenv("LANTERN_SCAN_LANES")) s->lanes = std::min(kMaxLanes, std::max(1, std::atoi(ln)));
+    return start_common(s, host, port, max_batch, max_wait_us, e);
+}
+LANTERN_ABI_CATCH(e)
+
 int lantern_scan_server_port(lantern_scan_server_t *s) { return s ? s->port : -1; }
+
+void lantern_scan_server_filter_stats(lantern_scan_server_t *s, uint64_t *filters_set, uint64_t *filtered_requests, uint64_t *each_calls,
+                                      uint64_t *most_distinct_filters, uint64_t *resident_bytes)
+try {
+    if(filters_set) *filters_set = s ? s->n_filters_set.load() : 0;
+    if(filtered_requests) *filtered_requests = s ? s->n_filtered.load() : 0;
+    if(each_calls) *each_calls = s ? s->n_each_calls.load() : 0;
+    if(most_distinct_filters) *most_distinct_filters = s ? s->max_distinct.load() : 0;
+    if(resident_bytes) *resident_bytes = s ? s->filter_resident.load() : 0;
+}
+LANTERN_ABI_CATCH_VOID(nullptr)
 
 void lantern_scan_server_stats(lantern_scan_server_t *s, uint64_t *requests, uint64_t *batches, uint64_t *launches, uint64_t *largest_batch)
 try {
@@ -706,9 +963,14 @@ try {
         s->stop = true;
     }
     s->cv.notify_all();
+    {
+        std::lock_guard<std::mutex> g(s->fmu);  // (the filter thread checks `stop` under this one)
+    }
+    s->fcv.notify_all();
     const uint64_t one = 1;
     for(auto &t : s->io) (void)!::write(t->evfd, &one, 8);
     if(s->accept_thread.joinable()) s->accept_thread.join();
+    if(s->filter_thread.joinable()) s->filter_thread.join();
     for(auto &t : s->dispatch_thread)
         if(t.joinable()) t.join();
     for(auto &t : s->io)
@@ -719,6 +981,7 @@ try {
     for(auto &t : s->io) {
         for(Done &d : t->done) reply_error(d.c->fd, "lantern_scan_server: stopping");
         for(auto &kv : t->conns) {
+            if(kv.second->filter) s->f_free(s->fn_ctx, kv.second->filter);  // (no batch is left that could hold it)
             ::shutdown(kv.first, SHUT_RDWR);
             ::close(kv.first);
         }
@@ -800,6 +1063,50 @@ try {
     return client_request(c, CONT_MAGIC, query, query_bytes, k, ef, labels, distances, e);
 }
 LANTERN_ABI_CATCH(e)
+
+// the connection's filter: the rows whose label is in labels[0 .. n) (n = 0: a filter that allows nothing); returns the allowed rows
+static size_t client_filter(lantern_scan_client_t *c, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e)
+{
+    if(e) *e = nullptr;
+    if(!c || c->fd < 0) { if(e) *e = "lantern_gpu: the scan client is not connected"; return 0; }
+    if(n && !labels) { if(e) *e = "lantern_gpu: null label array"; return 0; }
+    if(n > kMaxFilterLabels) { if(e) *e = "lantern_gpu: too many labels for one filter message (at most 2^24)"; return 0; }
+    auto fail = [&](const char *msg) {
+        c->err = msg;
+        ::close(c->fd);
+        c->fd = -1;
+        if(e) *e = c->err.c_str();
+        return (size_t)0;
+    };
+    const uint32_t head[ 2 ] = { FILTER_MAGIC, flags };
+    const uint64_t count = n;
+    if(!write_all(c->fd, head, 8) || !write_all(c->fd, &count, 8) || (n && !write_all(c->fd, labels, n * 8))) return fail("lantern_gpu: the scan server went away");
+    uint32_t rep[ 3 ];
+    if(!read_exact(c->fd, rep, sizeof(rep)) || rep[ 0 ] != REP_MAGIC) return fail("lantern_gpu: the scan server went away");
+    if(rep[ 1 ] != 0) {  // an error frame: the connection stays usable unless the server closed it (the label cap)
+        std::string msg(rep[ 2 ] <= 4096 ? rep[ 2 ] : 0, '\0');
+        if(rep[ 2 ] > 4096 || (rep[ 2 ] && !read_exact(c->fd, &msg[ 0 ], rep[ 2 ]))) return fail("lantern_gpu: the scan server went away");
+        c->err = msg;
+        if(e) *e = c->err.c_str();
+        return 0;
+    }
+    uint64_t allowed = 0;
+    if(!read_exact(c->fd, &allowed, 8)) return fail("lantern_gpu: the scan server went away");
+    return (size_t)allowed;
+}
+
+size_t lantern_scan_client_set_filter(lantern_scan_client_t *c, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e)
+try {
+    if(flags & ~(uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED) { if(e) *e = "lantern_gpu: unknown filter flags (only LANTERN_GPU_FILTER_SKIP_DELETED is defined)"; return 0; }
+    return client_filter(c, labels, n, flags, e);
+}
+LANTERN_ABI_CATCH(e)
+
+void lantern_scan_client_clear_filter(lantern_scan_client_t *c, usearch_error_t *e)
+try {
+    (void)client_filter(c, nullptr, 0, FILTER_CLEAR, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
 
 void lantern_scan_client_close(lantern_scan_client_t *c)
 try {

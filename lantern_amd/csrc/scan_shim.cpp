@@ -149,7 +149,7 @@ void lantern_scan_set_filter(lantern_scan_t *s, const lantern_gpu_filter_t *filt
 try {
     if(e) *e = nullptr;
     if(!s) { if(e) *e = "lantern_gpu: null scan"; return; }
-    if(s->client) { if(e) *e = "lantern_gpu: a scan through the scan service cannot be filtered (its wire format carries no filter)"; return; }
+    if(s->client) { if(e) *e = "lantern_gpu: a scan through the scan service cannot be filtered with a filter handle (a handle is local to a process): set the connection's filter with lantern_scan_client_set_filter"; return; }
     if(filter) {
         usearch_error_t err = nullptr;
         (void)lantern_gpu_filter_count(filter, &err);  // a live filter handle

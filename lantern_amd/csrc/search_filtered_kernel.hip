@@ -32,6 +32,12 @@
 namespace lgpu {
 
 __device__ __forceinline__ uint64_t allow_bit(const uint32_t *bits, uint32_t slot) { return (uint64_t)((bits[ slot >> 5 ] >> (slot & 31)) & 1u); }
+// the per-query form: a NULL bitmap is the descriptor's "unfiltered" mark (every slot allowed)
+template <bool EACH> __device__ __forceinline__ uint64_t allow_bit_of(const uint32_t *bits, uint32_t slot)
+{
+    if constexpr(EACH) return bits ? allow_bit(bits, slot) : 1ull;
+    else return allow_bit(bits, slot);
+}
 
 // #{j < n : a[j] < k}, every key of a[] taken
 __device__ __forceinline__ int count_below(const uint64_t *a, int n, uint64_t k)
@@ -69,7 +75,7 @@ size_t filtered_exact_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_
 enum { S_ADMIT0 = S_FRONT, S_ADMIT1, S_ALLOWED0, S_ALLOWED1 };
 
 // The base layer of the filtered walk.  On return s.keys[0..cnt) holds top, ascending; returns cnt.
-template <int METRIC, int G>
+template <int METRIC, int G, bool EACH>
 __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, uint64_t *nx2, const uint32_t *allow, uint32_t *bitmap,
                                      uint32_t bm_words, uint32_t start, int exp, int C, uint32_t &D, uint32_t &E)
 {
@@ -81,7 +87,7 @@ __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, ui
     if(g == 0) {
         float d = group_dist_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, start), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, start));
         if(gl == G - 1) {
-            const uint64_t key = make_key(d, start) | allow_bit(allow, start);
+            const uint64_t key = make_key(d, start) | allow_bit_of<EACH>(allow, start);
             nx[ 0 ] = key;
             s.keys[ 0 ] = key;
             s.scal[ S_CNT ] = (int)(key & 1u);
@@ -146,7 +152,7 @@ __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, ui
             const int      j = i + NG;
             const uint32_t id0 = s.newids[ i ];
             const uint32_t id1 = j < nnew ? s.newids[ j ] : id0;
-            const uint64_t a0 = allow_bit(allow, id0), a1 = allow_bit(allow, id1);
+            const uint64_t a0 = allow_bit_of<EACH>(allow, id0), a1 = allow_bit_of<EACH>(allow, id1);
             float          d0, d1;
             group_dist2_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, id0), row_of_m<METRIC>(v, id1), (int)v.chunks, gl, qn2,
                                      row_norm<METRIC>(v, id0), row_norm<METRIC>(v, id1), d0, d1);
@@ -211,8 +217,10 @@ __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, ui
 
 #define LGPU_FARG(base, field) LGPU_KARG(base, decltype(FilteredArgs::field), offsetof(FilteredArgs, field))
 
-// the answer of one query: top[skip, skip + k) of the list in s.keys, the unused tail label 0 / +inf / EMPTY; counts, D, E; the ticket
-__device__ __forceinline__ void write_answers(WalkLds &s, uint32_t q, int cnt, uint32_t D, uint32_t E)
+// the answer of one query: top[skip, skip + k) of the list in s.keys, the unused tail label 0 / +inf / EMPTY; counts, D, E; the ticket.
+// `pos` is the ticket position the workgroup drew and `q` the query it stands for (the same number unless the launch has a selection
+// list): rows are written by q, the next position is drawn after pos.
+__device__ __forceinline__ void write_answers(WalkLds &s, uint32_t q, uint32_t pos, int cnt, uint32_t D, uint32_t E)
 {
     const int          tid = threadIdx.x, T = blockDim.x;
     const KernargBytes kb = kernarg_opaque();
@@ -246,7 +254,7 @@ __device__ __forceinline__ void write_answers(WalkLds &s, uint32_t q, int cnt, u
         if(out_D) out_D[ q ] = D;
         if(out_E) out_E[ q ] = E;
         if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
-        s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(q + gridDim.x);
+        s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(pos + gridDim.x);
     }
     __syncthreads();
 }
@@ -266,7 +274,18 @@ template <int METRIC, int G> __device__ __forceinline__ void load_query(WalkLds 
     }
 }
 
-template <int METRIC, int G>
+// the query a workgroup serves at ticket position `pos`: pos itself, or -- the per-query form -- the entry of the launch's selection list
+template <bool EACH> __device__ __forceinline__ uint32_t query_at(uint32_t pos)
+{
+    if constexpr(EACH) return (uint32_t)__builtin_amdgcn_readfirstlane((int)LGPU_FARG(kernarg_opaque(), select)[ pos ]);
+    else return pos;
+}
+
+// EACH: the per-query form.  The launch serves the queries of its selection list (FilteredArgs::select), and the filter of a query is
+// its descriptor (FilteredArgs::descs[q]), read from memory anew for every query at the point that needs it: a workgroup serves many
+// queries and carries nothing of one query's filter into the next.  A descriptor with count 0 (and no unfiltered mark) is an empty
+// filter: no walk, the empty answer.
+template <int METRIC, int G, bool EACH>
 __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
 {
     WalkLds   s;
@@ -276,9 +295,10 @@ __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
         carve_filtered(lgpu_smem, s, nx, nx2, LGPU_VIEW_ARG(ka, FilteredArgs, chunks), LGPU_FARG(ka, exp), LGPU_FARG(ka, cand_cap),
                        LGPU_VIEW_ARG(ka, FilteredArgs, M0), LGPU_FARG(ka, vis_slots));
     }
-    for(uint32_t q = blockIdx.x; q < LGPU_FARG(kernarg_opaque(), nq);) {
-        uint32_t D = 0, E = 0;
-        int      cnt = 0;
+    for(uint32_t pos = blockIdx.x; pos < LGPU_FARG(kernarg_opaque(), nq);) {
+        const uint32_t q = query_at<EACH>(pos);
+        uint32_t       D = 0, E = 0;
+        int            cnt = 0;
         {
             const KernargBytes ka = kernarg_opaque();
             View               v;
@@ -288,21 +308,31 @@ __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
             s.undo = bitmap + bm_words;
             s.undo_cap = LGPU_FARG(ka, undo_cap);
             load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
-            if(v.n != 0) {
+            const uint32_t *allow;
+            bool            any = true;
+            if constexpr(EACH) {
+                const FilterDesc *const d = LGPU_FARG(ka, descs) + q;
+                const uint32_t          unfiltered = d->unfiltered;
+                allow = unfiltered ? nullptr : d->bits;
+                any = unfiltered || d->count != 0;
+            } else {
+                allow = LGPU_FARG(ka, allow_bits);
+            }
+            if(v.n != 0 && any) {
                 const uint32_t start = greedy_descent<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
-                cnt = search_level_filtered<METRIC, G>(v, s, nx, nx2, LGPU_FARG(ka, allow_bits), bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
-                                                       (int)LGPU_FARG(ka, cand_cap), D, E);
+                cnt = search_level_filtered<METRIC, G, EACH>(v, s, nx, nx2, allow, bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
+                                                             (int)LGPU_FARG(ka, cand_cap), D, E);
             }
         }
-        write_answers(s, q, cnt, D, E);
-        q = (uint32_t)s.scal[ S_POS ];
+        write_answers(s, q, pos, cnt, D, E);
+        pos = (uint32_t)s.scal[ S_POS ];
         __syncthreads();
     }
 }
 
 // The exact path: rows_per_round allowed rows per round (two per G-lane group, group_dist2_n as the walk's hops), merged into an
 // LDS list of k + skip keys when any of them beats its worst.
-template <int METRIC, int G>
+template <int METRIC, int G, bool EACH>
 __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
 {
     const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
@@ -311,17 +341,27 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
         const KernargBytes ka = kernarg_opaque();
         carve_walk(lgpu_smem, s, LGPU_VIEW_ARG(ka, FilteredArgs, chunks), LGPU_FARG(ka, exp), LGPU_FARG(ka, rows_per_round), 0);
     }
-    for(uint32_t q = blockIdx.x; q < LGPU_FARG(kernarg_opaque(), nq);) {
-        int cnt = 0;
-        uint32_t D = 0;
+    for(uint32_t pos = blockIdx.x; pos < LGPU_FARG(kernarg_opaque(), nq);) {
+        const uint32_t q = query_at<EACH>(pos);
+        int            cnt = 0;
+        uint32_t       D = 0;
         {
             const KernargBytes ka = kernarg_opaque();
             View               v;
             LGPU_LOAD_VIEW(v, ka, FilteredArgs)
             load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
             const float     qn2 = __int_as_float(s.scal[ S_QN2 ]);
-            const uint32_t *slots = LGPU_FARG(ka, allow_slots);
-            const int       count = (int)LGPU_FARG(ka, allow_count), kk = (int)LGPU_FARG(ka, exp), R = 2 * NG;
+            const uint32_t *slots;
+            int             count;
+            if constexpr(EACH) {
+                const FilterDesc *const d = LGPU_FARG(ka, descs) + q;
+                slots = d->slots;
+                count = (int)d->count;
+            } else {
+                slots = LGPU_FARG(ka, allow_slots);
+                count = (int)LGPU_FARG(ka, allow_count);
+            }
+            const int kk = (int)LGPU_FARG(ka, exp), R = 2 * NG;
             for(int base = 0, round = 0; base < count; base += R, ++round) {
                 const int      nr = count - base < R ? count - base : R;
                 const uint64_t worst = cnt == kk ? s.keys[ kk - 1 ] : ~0ull;
@@ -363,34 +403,46 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
             }
             D = (uint32_t)count;
         }
-        write_answers(s, q, cnt, D, 0);
-        q = (uint32_t)s.scal[ S_POS ];
+        write_answers(s, q, pos, cnt, D, 0);
+        pos = (uint32_t)s.scal[ S_POS ];
         __syncthreads();
     }
 }
 
-#define LGPU_LAUNCH_FILTERED(KERNEL, LDS_, MM, GG)                                                   \
-    {                                                                                                \
-        static LdsAttrCache attr_;                                                                   \
-        ensure_dynamic_lds((const void *)KERNEL<MM, GG>, LDS_, attr_);                               \
-        hipLaunchKernelGGL((KERNEL<MM, GG>), dim3(grid), dim3(64 * waves), LDS_, stream, a);         \
+#define LGPU_LAUNCH_FILTERED(KERNEL, EACH_, LDS_, MM, GG)                                                   \
+    {                                                                                                       \
+        static LdsAttrCache attr_;                                                                          \
+        ensure_dynamic_lds((const void *)KERNEL<MM, GG, EACH_>, LDS_, attr_);                               \
+        hipLaunchKernelGGL((KERNEL<MM, GG, EACH_>), dim3(grid), dim3(64 * waves), LDS_, stream, a);         \
     }
 
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.vis_slots);
-#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG)
-    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+    if(a.descs) {
+#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, true, lds, MM, GG)
+        LGPU_DISPATCH(metric, a.view.chunks, CALL);
 #undef CALL
+    } else {
+#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, false, lds, MM, GG)
+        LGPU_DISPATCH(metric, a.view.chunks, CALL);
+#undef CALL
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_exact_lds_bytes(a.view.chunks, a.exp, a.rows_per_round);
-#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG)
-    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+    if(a.descs) {
+#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, true, lds, MM, GG)
+        LGPU_DISPATCH(metric, a.view.chunks, CALL);
 #undef CALL
+    } else {
+#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, false, lds, MM, GG)
+        LGPU_DISPATCH(metric, a.view.chunks, CALL);
+#undef CALL
+    }
     return hipGetLastError();
 }
 

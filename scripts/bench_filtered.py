@@ -10,6 +10,15 @@ Clustered rows (lantern_amd/synth.py), f32 L2sq, M = 16, ef_construction = 128, 
   * the crossover on the random filters (log-log interpolation of walk / exact q/s between the two legs around 1), as
     exact_factor = allowed^2 / (ef * n) -- the constant of the auto path rule.
 The exact path reads allowed x row bytes per query, so it is timed on --nq-exact queries.
+
+    python scripts/bench_filtered.py --each [--nq-each 256]
+
+measures the per-query-filter call instead (lantern_gpu_search_batch_filtered_each_device) and prints ONE JSON line:
+  * distinct_filters: --nq-each queries, each with its OWN random filter, at 10 % (walk path) and at 0.1 % (exact path): one per-query
+    call against the only way the single-filter API answers them -- one one-query call per filter; wall-clock queries/s of both,
+    alternated, every repeat listed;
+  * shared_filter: ONE 10 % filter for --nq queries through the per-query call against search_batch_filtered_device (the same walks;
+    the per-query form pays the descriptor reads and the selection list): queries/s of both, alternated, and their ratio.
 """
 import argparse
 import json
@@ -36,6 +45,62 @@ def cluster_ids(n, dim):
     return out
 
 
+def each_legs(a, ix, rows, dq, bufs, k, ef):
+    """The per-query-filter call against the single-filter API (module docstring)."""
+    lab, dist, slot, cnt, D, E = bufs
+    stride = rows.strides[0]
+
+    def wall(fn, n_q):
+        hip.synchronize()
+        t = time.perf_counter()
+        fn()
+        hip.synchronize()
+        return n_q / (time.perf_counter() - t)
+
+    def each(filters, n_q):
+        filters = capi.GpuIndex._filter_array(filters, n_q)  # (the handle array built once: the call is timed, not the list walk)
+        return lambda: ix.search_batch_filtered_each_device(filters, dq.ptr, stride, n_q, k, ef, 0, lab.ptr, dist.ptr, slot.ptr, cnt.ptr, D.ptr, E.ptr)
+
+    def one_by_one(filters):
+        def fn():
+            for i, f in enumerate(filters):  # one query, one filter, one launch: the rows of query i
+                ix.search_batch_filtered_device(f, dq.ptr + i * stride, stride, 1, k, ef, 0, lab.ptr + i * k * 8, dist.ptr + i * k * 4,
+                                                slot.ptr + i * k * 4, cnt.ptr + i * 4, D.ptr + i * 8, E.ptr + i * 8)
+        return fn
+
+    out = {"distinct_filters": [], "reps": a.reps}
+    ix.set_filter_policy("auto")
+    rng = np.random.default_rng(11)
+    m = a.nq_each
+    for sel in (0.1, 0.001):
+        filters = [ix.filter_from_bitmap(rng.random(a.n) < sel) for _ in range(m)]
+        call = each(filters, m)
+        call()
+        one_by_one(filters[:8])()
+        together, alone = [], []
+        for _ in range(a.reps):  # alternated
+            together.append(wall(call, m))
+            alone.append(wall(one_by_one(filters), m))
+        out["distinct_filters"].append({"selectivity": sel, "queries": m, "filters": m, "regime": ix.last_filtered_each(),
+                                        "per_query_call_qps": together, "one_call_per_filter_qps": alone,
+                                        "speedup_best": max(together) / max(alone)})
+        for f in filters:
+            f.close()
+    f = ix.filter_from_bitmap(rng.random(a.n) < 0.1)
+    nq = a.nq
+    single = lambda: ix.search_batch_filtered_device(f, dq.ptr, stride, nq, k, ef, 0, lab.ptr, dist.ptr, slot.ptr, cnt.ptr, D.ptr, E.ptr)  # noqa: E731
+    shared = each([f] * nq, nq)
+    single()
+    shared()
+    s_qps, e_qps = [], []
+    for _ in range(max(a.reps, 3)):
+        s_qps.append(wall(single, nq))
+        e_qps.append(wall(shared, nq))
+    out["shared_filter"] = {"selectivity": 0.1, "queries": nq, "single_filter_qps": s_qps, "per_query_call_qps": e_qps,
+                            "ratio_best": max(e_qps) / max(s_qps), "single_filter_spread": (max(s_qps) - min(s_qps)) / max(s_qps)}
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=1_000_000)
@@ -43,6 +108,8 @@ def main():
     p.add_argument("--nq", type=int, default=8192)
     p.add_argument("--nq-exact", type=int, default=256)
     p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--each", action="store_true", help="the legs of the per-query-filter call")
+    p.add_argument("--nq-each", type=int, default=256)
     a = p.parse_args()
     M, efc, ef, k = 16, 128, 64, 10
     t0 = time.time()
@@ -81,6 +148,11 @@ def main():
 
     out = {"workload": f"clustered {a.n}x{a.dim} f32 l2sq M={M} efc={efc} ef={ef} k={k}", "queries": nq, "queries_exact": a.nq_exact,
            "build_seconds": build_s}
+    if a.each:
+        out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
+        out.update(each_legs(a, ix, rows, dq, (lab, dist, slot, cnt, D, E), k, ef))
+        print(json.dumps(out))
+        return
     everyone = ix.filter_from_bitmap(np.ones(a.n, dtype=bool))
     ix.set_filter_policy("walk")
     walk_qps, plain_qps = [], []
