@@ -21,7 +21,18 @@ inline void abi_fail(std::nullptr_t, const char *) {}
 constexpr const char *kAbiOom = "lantern_gpu: out of host memory";
 constexpr const char *kAbiTooLarge = "lantern_gpu: requested size exceeds what can be allocated";
 constexpr const char *kAbiException = "lantern_gpu: internal error (C++ exception stopped at the C boundary)";
+constexpr const char *kStrideMismatch = "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)";
+
+struct Index;
+// The index behind a usearch_index_t, with HIP's current device set to the one it lives on (the current device is per host thread:
+// one thread per GPU is how a single process drives a node, lantern_gpu_comm_init_local); NULL with *e set for a null, stale,
+// freed or foreign pointer (index.cpp)
+Index *H(void *h, const char **e);
 }  // namespace lgpu
+
+// every entry point's error slot: cleared on entry, set to a string that outlives the call on failure
+#define CLEAR(e) do { if(e) *(e) = nullptr; } while(0)
+#define FAIL(e, msg) do { if(e) *(e) = (msg); } while(0)
 
 #define LANTERN_ABI_CATCH_(e, RET)                                               \
     catch(const std::bad_alloc &) { lgpu::abi_fail(e, lgpu::kAbiOom); RET; }            \

@@ -207,9 +207,6 @@ bool Comm::allgatherv_host(void *h_buf, const size_t *off, const size_t *cnt)
 // =====================================================================================================
 using namespace lgpu;
 
-#define CLEAR(e) do { if(e) *(e) = nullptr; } while(0)
-#define FAIL(e, msg) do { if(e) *(e) = (msg); } while(0)
-
 static thread_local std::string g_comm_err;
 static const char *keep_err(const std::string &s)
 {

@@ -52,6 +52,7 @@ __global__ void k_filter_mask(const uint64_t *slot_labels, size_t n, int skip_de
     bits[ w ] = word;
 }
 
+static const char *kFilteredBatchFailed = "lantern_gpu: HIP failure during filtered batched search";
 static const char *kFilterFlags = "lantern_gpu: unknown filter flags (only LANTERN_GPU_FILTER_SKIP_DELETED is defined)";
 
 static void filter_release(Filter *f)
@@ -192,24 +193,102 @@ static bool filtered_shape(Index *ix, bool exact, size_t k, size_t skip, size_t 
     return true;
 }
 
+static const char *kNotAFilter = "lantern_gpu: not a filter handle (stale, freed or foreign pointer)";
+
+// Why `f` cannot serve a search of `ix` as it stands now; empty: it can.
+static std::string filter_mismatch(const Index *ix, const Filter *f)
+{
+    if(f->ix != ix)
+        return "lantern_gpu: the filter belongs to another index (built over " + std::to_string(f->n) + " rows; this index holds " + std::to_string(ix->n) + ")";
+    if(f->n != ix->n)
+        return "lantern_gpu: stale filter: built when the index held " + std::to_string(f->n) + " rows, it now holds " + std::to_string(ix->n) +
+               " (build the filter again)";
+    return {};
+}
+// (checked after the filters)
+static bool filtered_index_ok(Index *ix)
+{
+    if(ix->pq_compact) set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
+    return !ix->pq_compact;
+}
+
+// the path of a query under `f`: forced, or the rule of DESIGN.md 4.9 -- a walk under selectivity s evaluates about D / s rows, the
+// exact pass `allowed`
+static bool filter_takes_exact(const Index *ix, const Filter *f, size_t ef_sel)
+{
+    if(ix->filter_path) return ix->filter_path == 2;
+    return (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
+}
+
+// the kernel arguments that depend neither on the filter nor on the path
+static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, size_t skip, uint64_t *d_labels, float *d_dists, uint32_t *d_slots,
+                                  uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E)
+{
+    FilteredArgs a{};
+    a.view = ix->view();
+    a.queries = d_q;
+    a.k = (uint32_t)k;
+    a.skip = (uint32_t)skip;
+    a.labels = ix->d_labels;
+    a.out_labels = d_labels;
+    a.out_dists = d_dists;
+    a.out_slots = d_slots;
+    a.out_counts = d_counts;
+    a.out_D = d_D;
+    a.out_E = d_E;
+    a.totals = ix->d_totals;
+    return a;
+}
+
+// the per-query form's table of one launch: host bytes that go into the scratch of the launch's slot, and where in them the launch's
+// descriptors and selection list lie
+struct EachTable
+{
+    const char *host;
+    size_t      bytes, descs_at, select_at;
+};
+
+// ONE launch of either kernel over a.nq queries, `a` shaped by filtered_shape: the grid, the launch slot (which orders the launch
+// after inserts and holds the walk's visited bitmaps), the per-query table if there is one, the ticket, the launch and its count.
+// Returns the grid; < 0 -> ix->err.
+static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, hipStream_t stream, const EachTable *tbl = nullptr)
+{
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
+    const int grid = search_grid(ix, a.nq, kFilteredWaves, kFilteredWaves * per_cu);
+    const int slot = acquire_search_slot(ix, stream, (size_t)grid);
+    if(slot < 0) return -1;
+    if(tbl) {
+        char *const d_tbl = (char *)scratch(ix, launch_table_scratch(slot), tbl->bytes);
+        if(!d_tbl) return -1;
+        if(hipMemcpyAsync(d_tbl, tbl->host, tbl->bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+            set_err(ix, "lantern_gpu: HIP failure (per-query filter table)");
+            return -1;
+        }
+        a.descs = (const FilterDesc *)(d_tbl + tbl->descs_at);
+        a.select = (const uint32_t *)(d_tbl + tbl->select_at);
+    }
+    a.bitmaps = ix->slot_bitmaps[ slot ];
+    a.bm_words = (uint32_t)ix->slot_words[ slot ];
+    a.undo_cap = vis_undo_cap();
+    a.ticket = next_ticket(ix, a.nq, grid, stream);
+    const hipError_t e = exact ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
+                               : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
+    if(e != hipSuccess) {
+        set_err(ix, std::string("lantern_gpu: HIP error launching the filtered search: ") + hipGetErrorString(e));
+        return -1;
+    }
+    if(!release_search_slot(ix, slot, stream)) return -1;
+    (exact ? ix->c_filter_exact : ix->c_filter_walk) += 1;
+    return grid;
+}
+
 // The caller holds ix->mu and has flushed.  false -> ix->err.
 static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
                                    float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, hipStream_t stream)
 {
-    if(f->ix != ix) {
-        set_err(ix, "lantern_gpu: the filter belongs to another index (built over " + std::to_string(f->n) + " rows; this index holds " +
-                        std::to_string(ix->n) + ")");
-        return false;
-    }
-    if(f->n != ix->n) {
-        set_err(ix, "lantern_gpu: stale filter: built when the index held " + std::to_string(f->n) + " rows, it now holds " + std::to_string(ix->n) +
-                        " (build the filter again)");
-        return false;
-    }
-    if(ix->pq_compact) {
-        set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
-        return false;
-    }
+    const std::string why = filter_mismatch(ix, f);
+    if(!why.empty()) return set_err(ix, why), false;
+    if(!filtered_index_ok(ix)) return false;
     if(nq == 0 || k == 0) return true;
     const size_t ef_sel = ef ? ef : ix->ef;
     const size_t exp = std::max(ef_sel, k + skip);
@@ -223,44 +302,16 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
         if(d_E && hipMemsetAsync(d_E, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
         return true;
     }
-    // the path: forced, or the rule of DESIGN.md 4.9 -- a walk under selectivity s evaluates about D / s rows, the exact pass `allowed`
-    bool exact = ix->filter_path == 2;
-    if(ix->filter_path == 0) exact = (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
-    FilteredArgs a{};
-    a.view = ix->view();
-    a.queries = d_q;
+    const bool   exact = filter_takes_exact(ix, f, ef_sel);
+    FilteredArgs a = filtered_args(ix, d_q, k, skip, d_labels, d_dists, d_slots, d_counts, d_D, d_E);
     a.nq = (uint32_t)nq;
-    a.k = (uint32_t)k;
-    a.skip = (uint32_t)skip;
     a.allow_bits = f->d_bits;
     a.allow_slots = f->d_slots;
     a.allow_count = (uint32_t)f->count;
-    a.labels = ix->d_labels;
-    a.out_labels = d_labels;
-    a.out_dists = d_dists;
-    a.out_slots = d_slots;
-    a.out_counts = d_counts;
-    a.out_D = d_D;
-    a.out_E = d_E;
-    a.totals = ix->d_totals;
     size_t lds = 0;
     if(!filtered_shape(ix, exact, k, skip, exp, a, lds)) return false;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
-    const int grid = search_grid(ix, nq, kFilteredWaves, kFilteredWaves * per_cu);
-    const int slot = acquire_search_slot(ix, stream, (size_t)grid);  // (orders the launch after inserts; the walk's visited bitmaps)
-    if(slot < 0) return false;
-    a.bitmaps = ix->slot_bitmaps[ slot ];
-    a.bm_words = (uint32_t)ix->slot_words[ slot ];
-    a.undo_cap = vis_undo_cap();
-    a.ticket = next_ticket(ix, nq, grid, stream);
-    const hipError_t e = exact ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
-                               : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
-    if(e != hipSuccess) {
-        set_err(ix, std::string("lantern_gpu: HIP error launching the filtered search: ") + hipGetErrorString(e));
-        return false;
-    }
-    if(!release_search_slot(ix, slot, stream)) return false;
-    (exact ? ix->c_filter_exact : ix->c_filter_walk) += 1;
+    const int grid = filtered_launch(ix, exact, a, lds, stream);
+    if(grid < 0) return false;
     const uint32_t shape[ 6 ] = { exact ? 2u : 1u, (uint32_t)grid, a.exp, a.cand_cap, a.vis_slots, (uint32_t)lds };
     std::copy(std::begin(shape), std::end(shape), ix->last_filtered);
     ix->c_search_queries += nq;
@@ -271,34 +322,18 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
 // bytes of the host block filtered_each_locked stages its selection lists and descriptor table in
 static size_t each_table_bytes(size_t nq) { return nq * (sizeof(FilterDesc) + 4) + 16; }
 
-static const char *kNotAFilter = "lantern_gpu: not a filter handle (stale, freed or foreign pointer)";
-
 // Every entry of filters[] is NULL or a live filter of this index at its present size; else ix->err names the first offender.
 static bool each_filters_ok(Index *ix, const Filter *const *filters, size_t nq)
 {
     for(size_t i = 0; i < nq; ++i) {
         const Filter *f = filters[ i ];
         if(!f) continue;
-        if(f->magic != kFilterMagic) {
-            set_err(ix, std::string(kNotAFilter) + " (filters[" + std::to_string(i) + "])");
-            return false;
-        }
-        if(f->ix != ix) {
-            set_err(ix, "lantern_gpu: the filter belongs to another index (built over " + std::to_string(f->n) + " rows; this index holds " +
-                            std::to_string(ix->n) + ") (filters[" + std::to_string(i) + "])");
-            return false;
-        }
-        if(f->n != ix->n) {
-            set_err(ix, "lantern_gpu: stale filter: built when the index held " + std::to_string(f->n) + " rows, it now holds " + std::to_string(ix->n) +
-                            " (build the filter again) (filters[" + std::to_string(i) + "])");
-            return false;
-        }
-    }
-    if(ix->pq_compact) {
-        set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
+        const std::string why = f->magic != kFilterMagic ? std::string(kNotAFilter) : filter_mismatch(ix, f);
+        if(why.empty()) continue;
+        set_err(ix, why + " (filters[" + std::to_string(i) + "])");
         return false;
     }
-    return true;
+    return filtered_index_ok(ix);
 }
 
 // The caller holds ix->mu and has flushed.  The queries split into a walk group and an exact group by the path rule, evaluated per
@@ -321,9 +356,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
         const Filter *f = filters[ i ];
         if(ix->n == 0 || (f && f->count == 0)) { empty.push_back((uint32_t)i); continue; }
         if(!f) { n_unfiltered += 1; walk.push_back((uint32_t)i); continue; }
-        bool ex = ix->filter_path == 2;
-        if(ix->filter_path == 0) ex = (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
-        (ex ? exact : walk).push_back((uint32_t)i);
+        (filter_takes_exact(ix, f, ef_sel) ? exact : walk).push_back((uint32_t)i);
     }
     const uint32_t n_walk = (uint32_t)walk.size(), n_exact = (uint32_t)exact.size(), n_empty = (uint32_t)empty.size();
     // the exact group's queries differ in length by orders of magnitude: longest first, so that the launch's tail is a short one
@@ -336,19 +369,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
     std::sort(distinct.begin(), distinct.end());
     distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
 
-    FilteredArgs base{};
-    base.view = ix->view();
-    base.queries = d_q;
-    base.k = (uint32_t)k;
-    base.skip = (uint32_t)skip;
-    base.labels = ix->d_labels;
-    base.out_labels = d_labels;
-    base.out_dists = d_dists;
-    base.out_slots = d_slots;
-    base.out_counts = d_counts;
-    base.out_D = d_D;
-    base.out_E = d_E;
-    base.totals = ix->d_totals;
+    const FilteredArgs base = filtered_args(ix, d_q, k, skip, d_labels, d_dists, d_slots, d_counts, d_D, d_E);
     FilteredArgs aw = base, ae = base;
     size_t       lds_w = 0, lds_e = 0;
     if(!walk.empty() && !filtered_shape(ix, false, k, skip, exp, aw, lds_w)) return false;
@@ -370,37 +391,12 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
 
     uint32_t launches = 0;
     for(int pass = 0; pass < 2; ++pass) {
-        const bool                   ex = pass == 1;
-        const std::vector<uint32_t> &sel = ex ? exact : walk;
-        if(sel.empty()) continue;
+        const bool ex = pass == 1;
+        if((ex ? exact : walk).empty()) continue;
         FilteredArgs &a = ex ? ae : aw;
-        const size_t  lds = ex ? lds_e : lds_w;
-        a.nq = (uint32_t)sel.size();
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
-        const int grid = search_grid(ix, sel.size(), kFilteredWaves, kFilteredWaves * per_cu);
-        const int slot = acquire_search_slot(ix, stream, (size_t)grid);
-        if(slot < 0) return false;
-        const size_t from = ex ? off_desc : 0, bytes = (ex ? tbl_bytes : off_sel_e) - from;
-        char *const  d_tbl = (char *)scratch(ix, 12 + 2 * Index::kLanes + slot, bytes);
-        if(!d_tbl) return false;
-        if(hipMemcpyAsync(d_tbl, h_tbl + from, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
-            set_err(ix, "lantern_gpu: HIP failure (per-query filter table)");
-            return false;
-        }
-        a.descs = (const FilterDesc *)(d_tbl + (ex ? 0 : off_desc));
-        a.select = (const uint32_t *)(d_tbl + (ex ? nq * sizeof(FilterDesc) : 0));
-        a.bitmaps = ix->slot_bitmaps[ slot ];
-        a.bm_words = (uint32_t)ix->slot_words[ slot ];
-        a.undo_cap = vis_undo_cap();
-        a.ticket = next_ticket(ix, sel.size(), grid, stream);
-        const hipError_t e = ex ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
-                                : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
-        if(e != hipSuccess) {
-            set_err(ix, std::string("lantern_gpu: HIP error launching the filtered search: ") + hipGetErrorString(e));
-            return false;
-        }
-        if(!release_search_slot(ix, slot, stream)) return false;
-        (ex ? ix->c_filter_exact : ix->c_filter_walk) += 1;
+        a.nq = (uint32_t)(ex ? exact : walk).size();
+        const EachTable t = ex ? EachTable{ h_tbl + off_desc, tbl_bytes - off_desc, 0, nq * sizeof(FilterDesc) } : EachTable{ h_tbl, off_sel_e, off_desc, 0 };
+        if(filtered_launch(ix, ex, a, ex ? lds_e : lds_w, stream, &t) < 0) return false;
         launches += 1;
     }
     const uint32_t shape[ 6 ] = { n_walk, n_exact, n_unfiltered, n_empty, (uint32_t)distinct.size(), launches };
@@ -419,15 +415,12 @@ static size_t cursor_search_filtered_locked(Index *ix, const Filter *f, Cursor *
     const size_t row = (size_t)ix->chunks * 16;
     std::vector<uint32_t> padded((size_t)ix->chunks * 4);
     pad_row(ix, query, kind, padded.data());
-    char *dq = (char *)scratch(ix, 5, row);
-    char *dout = (char *)scratch(ix, 6, want * 16 + 16);
+    char *dq = (char *)scratch(ix, kScratchCallIn, row);
+    char *dout = (char *)scratch(ix, kScratchCallOut, want * 16 + 16);
     if(!dq || !dout) return 0;
-    uint64_t *d_lab = (uint64_t *)dout;
-    float    *d_dist = (float *)(dout + want * 8);
-    uint32_t *d_slot = (uint32_t *)(dout + want * 12);
-    uint32_t *d_cnt = (uint32_t *)(dout + want * 16);
     bool ok = hipMemcpyAsync(dq, padded.data(), row, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
-    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, 1, want, ef, 0, d_lab, d_dist, d_slot, d_cnt, nullptr, nullptr, ix->stream);
+    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, 1, want, ef, 0, (uint64_t *)dout, (float *)(dout + want * 8), (uint32_t *)(dout + want * 12),
+                                      (uint32_t *)(dout + want * 16), nullptr, nullptr, ix->stream);
     std::vector<char> h(want * 16 + 4);
     ok = ok && hipMemcpyAsync(h.data(), dout, want * 16 + 4, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
     ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
@@ -435,19 +428,9 @@ static size_t cursor_search_filtered_locked(Index *ix, const Filter *f, Cursor *
         if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during filtered search");
         return 0;
     }
-    const uint64_t *h_lab = (const uint64_t *)h.data();
-    const float    *h_dist = (const float *)(h.data() + want * 8);
-    const uint32_t *h_slot = (const uint32_t *)(h.data() + want * 12);
-    uint32_t        got;
+    uint32_t got;
     std::memcpy(&got, h.data() + want * 16, 4);
-    size_t out = 0;
-    for(uint32_t i = 0; i < got && out < k; ++i) {
-        if(!cur->seen.insert(h_slot[ i ]).second) continue;
-        labels[ out ] = h_lab[ i ];
-        distances[ out ] = h_dist[ i ];
-        ++out;
-    }
-    return out;
+    return take_unseen(cur, (const uint64_t *)h.data(), (const float *)(h.data() + want * 8), (const uint32_t *)(h.data() + want * 12), got, k, labels, distances);
 }
 
 }  // namespace lgpu
@@ -458,16 +441,6 @@ static size_t cursor_search_filtered_locked(Index *ix, const Filter *f, Cursor *
 using namespace lgpu;
 
 // (lantern_gpu_filter_t stays an incomplete type: a handle is a Filter, recognised by its magic word)
-#define CLEAR(e) do { if(e) *(e) = nullptr; } while(0)
-#define FAIL(e, msg) do { if(e) *(e) = (msg); } while(0)
-
-static Index *FH(usearch_index_t h, usearch_error_t *e)
-{
-    if(!h) { FAIL(e, "lantern_gpu: null index handle"); return nullptr; }
-    if(((const Index *)h)->magic != kIndexMagic) { FAIL(e, "lantern_gpu: not an index handle (stale, freed or foreign pointer)"); return nullptr; }
-    (void)hipSetDevice(((Index *)h)->device);
-    return (Index *)h;
-}
 static Filter *FF(const lantern_gpu_filter_t *f, usearch_error_t *e)
 {
     if(!f) { FAIL(e, "lantern_gpu: null filter handle"); return nullptr; }
@@ -482,7 +455,7 @@ static Index *FHS(usearch_index_t h, const lantern_gpu_filter_t *const *filters,
 {
     static thread_local std::string msg;
     if(nq && !filters) { FAIL(e, "lantern_gpu: null filter array"); return nullptr; }
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(ix) return ix;
     for(size_t i = 0; i < nq; ++i) {
         if(!filters[ i ] || ((const Filter *)filters[ i ])->magic == kFilterMagic) continue;
@@ -500,7 +473,7 @@ try {
     CLEAR(e);
     if(flags & ~(uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED) { FAIL(e, kFilterFlags); return nullptr; }
     if(n && !labels) { FAIL(e, "lantern_gpu: null label array"); return nullptr; }
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return nullptr;
     std::lock_guard<std::mutex> g(ix->mu);
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return nullptr; }
@@ -516,7 +489,7 @@ try {
     CLEAR(e);
     if(flags & ~(uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED) { FAIL(e, kFilterFlags); return nullptr; }
     if(n_words && !words) { FAIL(e, "lantern_gpu: null bitmap"); return nullptr; }
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return nullptr;
     std::lock_guard<std::mutex> g(ix->mu);
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return nullptr; }
@@ -562,7 +535,7 @@ try {
     CLEAR(e);
     if(path < 0 || path > 2) { FAIL(e, "lantern_gpu: filter path must be 0 (auto), 1 (walk) or 2 (exact)"); return; }
     if(!(exact_factor >= 0) || std::isinf(exact_factor)) { FAIL(e, "lantern_gpu: exact_factor must be a finite number >= 0"); return; }
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return;
     std::lock_guard<std::mutex> g(ix->mu);
     ix->filter_path = path;
@@ -574,7 +547,7 @@ LANTERN_ABI_CATCH_VOID(e)
 void lantern_gpu_filter_stats(usearch_index_t h, uint64_t *walk_launches, uint64_t *exact_launches, usearch_error_t *e)
 try {
     CLEAR(e);
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return;
     std::lock_guard<std::mutex> g(ix->mu);
     if(walk_launches) *walk_launches = ix->c_filter_walk;
@@ -585,7 +558,7 @@ LANTERN_ABI_CATCH_VOID(e)
 void lantern_gpu_last_filtered_launch(usearch_index_t h, uint32_t out[ 6 ], usearch_error_t *e)
 try {
     CLEAR(e);
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return;
     if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
     std::lock_guard<std::mutex> g(ix->mu);
@@ -600,10 +573,10 @@ try {
     CLEAR(e);
     const Filter *f = FF(filter, e);
     if(!f) return;
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return;
     std::lock_guard<std::mutex> g(ix->mu);
-    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)"); return; }
+    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
     if(!filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts, d_D, d_E, (hipStream_t)stream))
@@ -617,7 +590,7 @@ try {
     CLEAR(e);
     const Filter *f = FF(filter, e);
     if(!f) return;
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return;
     if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
     if(nq == 0 || k == 0) return;
@@ -625,36 +598,20 @@ try {
     std::lock_guard<std::mutex> g(ix->mu);
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
-    const size_t row_words = (size_t)ix->chunks * 4, in_bytes = input_bytes(ix, (int)kind);
-    std::vector<uint32_t> padded(nq * row_words);
-    for(size_t i = 0; i < nq; ++i) pad_row(ix, (const char *)queries + i * in_bytes, (int)kind, padded.data() + i * row_words);
-    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
-    char *dq = (char *)scratch(ix, 5, q_bytes);
-    char *dout = (char *)scratch(ix, 6, out_bytes + 64);
-    if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
-    uint64_t *d_lab = (uint64_t *)dout;
-    float    *d_dist = (float *)(dout + nq * k * 8);
-    uint32_t *d_cnt = (uint32_t *)(dout + nq * k * 12);
-    std::vector<char> h_out(out_bytes);
-    bool ok = hipMemcpyAsync(dq, padded.data(), q_bytes, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
-    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, nq, k, ef, 0, d_lab, d_dist, nullptr, d_cnt, nullptr, nullptr, ix->stream);
-    ok = ok && hipMemcpyAsync(h_out.data(), dout, out_bytes, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
-    if(!ok) {
-        if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during filtered batched search");
-        FAIL(e, ix->err.c_str());
-        return;
-    }
-    std::memcpy(labels, h_out.data(), nq * k * 8);
-    std::memcpy(distances, h_out.data() + nq * k * 8, nq * k * 4);
-    if(counts) std::memcpy(counts, h_out.data() + nq * k * 12, nq * 4);
+    HostBatch b = batch_layout(ix, Index::kLanes, nq, k);
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
+    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
+    bool ok = batch_upload(b);
+    ok = ok && filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                      nullptr, b.stream);
+    if(!batch_finish_locked(ix, b, ok, kFilteredBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
 
 void lantern_gpu_last_filtered_each(usearch_index_t h, uint32_t out[ 6 ], usearch_error_t *e)
 try {
     CLEAR(e);
-    Index *ix = FH(h, e);
+    Index *ix = H(h, e);
     if(!ix) return;
     if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
     std::lock_guard<std::mutex> g(ix->mu);
@@ -671,7 +628,7 @@ try {
     Index *ix = FHS(h, filters, nq, e);
     if(!ix) return;
     std::lock_guard<std::mutex> g(ix->mu);
-    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)"); return; }
+    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
     if(!filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts,
@@ -694,30 +651,13 @@ try {
     ix->err.clear();
     if(!each_filters_ok(ix, (const Filter *const *)filters, nq)) { FAIL(e, ix->err.c_str()); return; }
     if(nq == 0 || k == 0) return;
-    const size_t row_words = (size_t)ix->chunks * 4;
-    std::vector<uint32_t> padded(nq * row_words);
-    pad_rows(ix, queries, (int)kind, nq, padded.data());
-    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
-    char *dq = (char *)scratch(ix, 5, q_bytes);
-    char *dout = (char *)scratch(ix, 6, out_bytes + 64);
-    if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
-    uint64_t *d_lab = (uint64_t *)dout;
-    float    *d_dist = (float *)(dout + nq * k * 8);
-    uint32_t *d_cnt = (uint32_t *)(dout + nq * k * 12);
-    std::vector<char> h_out(out_bytes);
-    bool ok = hipMemcpyAsync(dq, padded.data(), q_bytes, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
-    ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)dq, nq, k, ef, 0, d_lab, d_dist, nullptr, d_cnt, nullptr, nullptr,
-                                    ix->stream, nullptr);
-    ok = ok && hipMemcpyAsync(h_out.data(), dout, out_bytes, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
-    if(!ok) {
-        if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during filtered batched search");
-        FAIL(e, ix->err.c_str());
-        return;
-    }
-    std::memcpy(labels, h_out.data(), nq * k * 8);
-    std::memcpy(distances, h_out.data() + nq * k * 8, nq * k * 4);
-    if(counts) std::memcpy(counts, h_out.data() + nq * k * 12, nq * 4);
+    HostBatch b = batch_layout(ix, Index::kLanes, nq, k, each_table_bytes(nq));
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
+    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
+    bool ok = batch_upload(b);
+    ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr,
+                                    b.counts(b.d_out), nullptr, nullptr, b.stream, b.h_extra());
+    if(!batch_finish_locked(ix, b, ok, kFilteredBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -735,43 +675,26 @@ try {
     if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null buffer"); return; }
     static thread_local std::string msg;  // (a lane's error text belongs to the calling thread: lantern_gpu_search_batch_lane)
     msg.clear();
-    const size_t row_words = (size_t)ix->chunks * 4;
-    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
-    const size_t out_at = (q_bytes + 63) & ~(size_t)63, tbl_at = (out_at + out_bytes + 63) & ~(size_t)63;
-    char        *hs = nullptr;
-    if(nq && k) {
-        hs = host_stage(ix, lane, tbl_at + each_table_bytes(nq));
-        if(!hs) { FAIL(e, "lantern_gpu: cannot allocate the lane's page-locked staging block"); return; }
-        pad_rows(ix, queries, (int)kind, nq, (uint32_t *)hs);
-    }
-    hipStream_t st = nullptr;
-    bool        ok = true;
+    HostBatch b = batch_layout(ix, lane, nq, k, each_table_bytes(nq));
+    if(nq && k && !batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
+    bool ok = true;
     {
         std::lock_guard<std::mutex> g(ix->mu);
         if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
         ix->err.clear();
         if(!each_filters_ok(ix, (const Filter *const *)filters, nq)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
         if(nq == 0 || k == 0) return;
-        if(!ix->lane_stream[ lane ] && hipStreamCreateWithFlags(&ix->lane_stream[ lane ], hipStreamNonBlocking) != hipSuccess) {
-            FAIL(e, "lantern_gpu: cannot create the lane's stream");
-            return;
-        }
-        st = ix->lane_stream[ lane ];
-        char *dq = (char *)scratch(ix, 12 + 2 * lane, q_bytes);
-        char *dout = (char *)scratch(ix, 13 + 2 * lane, out_bytes + 64);
-        if(!dq || !dout) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ok = hipMemcpyAsync(dq, hs, q_bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)dq, nq, k, ef, 0, (uint64_t *)dout, (float *)(dout + nq * k * 8),
-                                        nullptr, (uint32_t *)(dout + nq * k * 12), nullptr, nullptr, st, hs + tbl_at);
-        ok = ok && hipMemcpyAsync(hs + out_at, dout, out_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-        if(!ok) msg = ix->err.empty() ? "lantern_gpu: HIP failure during filtered batched search" : ix->err;
+        if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        ok = batch_upload(b);
+        ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr,
+                                        b.counts(b.d_out), nullptr, nullptr, b.stream, b.h_extra());
+        ok = ok && batch_download(b);
+        if(!ok) msg = ix->err.empty() ? kFilteredBatchFailed : ix->err;
     }
     // (whatever was queued is waited for even after a failure: the filters may be freed once this returns)
-    if(hipStreamSynchronize(st) != hipSuccess && ok) { ok = false; msg = "lantern_gpu: HIP failure during filtered batched search"; }
+    if(hipStreamSynchronize(b.stream) != hipSuccess && ok) { ok = false; msg = kFilteredBatchFailed; }
     if(!ok) { FAIL(e, msg.c_str()); return; }
-    std::memcpy(labels, hs + out_at, nq * k * 8);
-    std::memcpy(distances, hs + out_at + nq * k * 8, nq * k * 4);
-    if(counts) std::memcpy(counts, hs + out_at + nq * k * 12, nq * 4);
+    batch_unpack(b, 0, nq, labels, distances, counts);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -782,7 +705,7 @@ try {
     if(!c) { FAIL(e, "lantern_gpu: null cursor"); return 0; }
     const Filter *f = FF(filter, e);
     if(!f) return 0;
-    Index *ix = FH(c->ix, e);
+    Index *ix = H(c->ix, e);
     if(!ix) return 0;
     if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the query does not match the index"); return 0; }
     if(k == 0) return 0;

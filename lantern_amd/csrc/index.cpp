@@ -562,15 +562,15 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
     }
     // one "item" per (new node, level): the walk result the selection kernel works on
     const size_t items = total_links / ix->M;
-    uint32_t *d_link_off = (uint32_t *)scratch(ix, 0, b * 4 + items * 4 + items * 4);
-    LinkReq  *d_links = (LinkReq *)scratch(ix, 1, total_links * sizeof(LinkReq));
-    uint64_t *d_tops = (uint64_t *)scratch(ix, 7, items * (size_t)ix->efc * 8);
-    LinkReq  *d_reqs = (LinkReq *)scratch(ix, 2, total_links * sizeof(LinkReq));
+    uint32_t *d_link_off = (uint32_t *)scratch(ix, kScratchLinkOff, b * 4 + items * 4 + items * 4);
+    LinkReq  *d_links = (LinkReq *)scratch(ix, kScratchLinks, total_links * sizeof(LinkReq));
+    uint64_t *d_tops = (uint64_t *)scratch(ix, kScratchTops, items * (size_t)ix->efc * 8);
+    LinkReq  *d_reqs = (LinkReq *)scratch(ix, kScratchReqs, total_links * sizeof(LinkReq));
     // groups | ngroups | owner counts
-    char     *d_grp = (char *)scratch(ix, 3, total_links * sizeof(uint2) + 16 + (size_t)W * 4);
-    void     *d_work = scratch(ix, 4, total_links * 8 + 16);
+    char     *d_grp = (char *)scratch(ix, kScratchGroups, total_links * sizeof(uint2) + 16 + (size_t)W * 4);
+    void     *d_work = scratch(ix, kScratchWork, total_links * 8 + 16);
     const size_t temp_bytes = group_temp_bytes(total_links);
-    char     *d_sort = (char *)scratch(ix, 8, total_links * 24 + temp_bytes + 64);
+    char     *d_sort = (char *)scratch(ix, kScratchSort, total_links * 24 + temp_bytes + 64);
     if(!d_link_off || !d_links || !d_tops || !d_reqs || !d_grp || !d_work || !d_sort) return false;
     uint32_t *d_item_node = d_link_off + b, *d_top_count = d_item_node + items;
     uint2    *d_groups = (uint2 *)d_grp;
@@ -735,7 +735,7 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
             total_recs += owner_reqs[ (size_t)r ];
         }
         if(total_recs) {
-            char *d_rec = (char *)scratch(ix, 5, total_recs * rec_bytes);
+            char *d_rec = (char *)scratch(ix, kScratchCallIn, total_recs * rec_bytes);
             if(!d_rec) return false;
             if(cnt[ (size_t)R ]) HIPCHK(ix, hipMemsetAsync(d_rec + off[ (size_t)R ], 0xFF, cnt[ (size_t)R ], ix->stream));
             HIPCHK(ix, launch_pack_lists(ra, (uint32_t *)(d_rec + off[ (size_t)R ]), ix->stream));
@@ -989,7 +989,7 @@ static bool row_shard_candidates(Index *ix, const RowShard &rs, size_t first, si
     Comm        *comm = rs.comm;
     const int    W = comm->world, R = comm->rank;
     const size_t K = rs.K, part = b * K, row = (size_t)ix->chunks * 16;
-    char *d_all = (char *)scratch(ix, 10, (size_t)W * part * 12 + 64);  // [W][b][K] labels | [W][b][K] distances
+    char *d_all = (char *)scratch(ix, kScratchShardParts, (size_t)W * part * 12 + 64);  // [W][b][K] labels | [W][b][K] distances
     if(!d_all) return false;
     uint64_t *g_lab = (uint64_t *)d_all;
     float    *g_dist = (float *)(d_all + (size_t)W * part * 8);
@@ -1512,20 +1512,90 @@ size_t search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, si
         return 0;
     }
     ix->err.clear();
-    const char     *host = ix->h_single + row;
-    const uint64_t *h_lab = (const uint64_t *)host;
-    const float    *h_dist = (const float *)(host + want * 8);
-    const uint32_t *h_slot = (const uint32_t *)(host + want * 12);
-    uint32_t        got;
+    char    *host = ix->h_single + row;
+    uint32_t got;
     std::memcpy(&got, host + want * 16, 4);
+    return take_unseen(cur, (const uint64_t *)host, (const float *)(host + want * 8), (const uint32_t *)(host + want * 12), got, k, labels, distances);
+}
+
+size_t take_unseen(Cursor *cur, const uint64_t *labels, const float *dists, const uint32_t *slots, uint32_t got, size_t k, uint64_t *out_labels,
+                   float *out_dists)
+{
     size_t out = 0;
     for(uint32_t i = 0; i < got && out < k; ++i) {
-        if(!cur->seen.insert(h_slot[ i ]).second) continue;  // returned by an earlier call of this scan
-        labels[ out ] = h_lab[ i ];
-        distances[ out ] = h_dist[ i ];
+        if(!cur->seen.insert(slots[ i ]).second) continue;  // returned by an earlier call of this scan
+        out_labels[ out ] = labels[ i ];
+        out_dists[ out ] = dists[ i ];
         ++out;
     }
     return out;
+}
+
+// ---- one batched search's trip through the host (index.hpp HostBatch) -----------------------------------------------------------
+static size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+HostBatch batch_layout(const Index *ix, int which, size_t nq, size_t k, size_t extra_bytes)
+{
+    HostBatch b;
+    b.which = which;
+    b.nq = nq;
+    b.k = k;
+    b.q_bytes = nq * (size_t)ix->chunks * 16;
+    b.out_at = up64(b.q_bytes);
+    b.out_bytes = nq * k * 12 + nq * 4;
+    b.extra_at = up64(b.out_at + b.out_bytes);
+    b.extra_bytes = extra_bytes;
+    return b;
+}
+
+// (four copies of pageable memory, staged by the runtime, cost ~40 us of a small batch's ~150; the block is device-mapped for
+// lane_notify's kernels; chunks and the scalar kind are fixed at init, so padding needs no lock)
+bool batch_stage(Index *ix, HostBatch &b, const void *queries, int kind)
+{
+    char *&block = ix->lane_host[ b.which ];
+    if(ix->lane_host_bytes[ b.which ] < b.bytes()) {
+        if(block) (void)hipHostFree(block);
+        block = nullptr;
+        ix->lane_host_bytes[ b.which ] = 0;
+        const size_t grow = b.bytes() + b.bytes() / 2;
+        if(hipHostMalloc((void **)&block, grow, hipHostMallocMapped) != hipSuccess) return false;
+        ix->lane_host_bytes[ b.which ] = grow;
+    }
+    b.hs = block;
+    pad_rows(ix, queries, kind, b.nq, (uint32_t *)b.hs);
+    return true;
+}
+
+bool batch_device(Index *ix, HostBatch &b, bool buffers)
+{
+    const bool lane = b.which < Index::kLanes;
+    if(lane && !ix->lane_stream[ b.which ] && hipStreamCreateWithFlags(&ix->lane_stream[ b.which ], hipStreamNonBlocking) != hipSuccess) {
+        set_err(ix, "lantern_gpu: cannot create the lane's stream");
+        return false;
+    }
+    b.stream = lane ? ix->lane_stream[ b.which ] : ix->stream;
+    if(!buffers) return true;
+    b.d_q = (char *)scratch(ix, lane ? lane_query_scratch(b.which) : kScratchCallIn, b.q_bytes);
+    b.d_out = (char *)scratch(ix, lane ? lane_answer_scratch(b.which) : kScratchCallOut, b.out_bytes + 64);
+    return b.d_q && b.d_out;
+}
+
+bool batch_upload(const HostBatch &b) { return hipMemcpyAsync(b.d_q, b.hs, b.q_bytes, hipMemcpyHostToDevice, b.stream) == hipSuccess; }
+bool batch_download(const HostBatch &b) { return hipMemcpyAsync(b.h_out(), b.d_out, b.out_bytes, hipMemcpyDeviceToHost, b.stream) == hipSuccess; }
+
+void batch_unpack(const HostBatch &b, size_t first, size_t count, uint64_t *labels, float *distances, uint32_t *counts)
+{
+    std::memcpy(labels + first * b.k, b.labels(b.h_out()) + first * b.k, count * b.k * 8);
+    std::memcpy(distances + first * b.k, b.dists(b.h_out()) + first * b.k, count * b.k * 4);
+    if(counts) std::memcpy(counts + first, b.counts(b.h_out()) + first, count * 4);
+}
+
+bool batch_finish_locked(Index *ix, const HostBatch &b, bool ok, const char *what, uint64_t *labels, float *distances, uint32_t *counts)
+{
+    ok = ok && batch_download(b) && hipStreamSynchronize(b.stream) == hipSuccess;
+    if(ok) batch_unpack(b, 0, b.nq, labels, distances, counts);
+    else if(ix->err.empty()) set_err(ix, what);
+    return ok;
 }
 
 bool import_graph_locked(Index *ix, size_t size, const void *vectors, const uint64_t *labels, const uint8_t *levels,
@@ -1579,15 +1649,10 @@ bool import_graph_locked(Index *ix, size_t size, const void *vectors, const uint
 // =====================================================================================================
 using namespace lgpu;
 
-#define CLEAR(e) do { if(e) *(e) = nullptr; } while(0)
-#define FAIL(e, msg) do { if(e) *(e) = (msg); } while(0)
-
-static Index *H(usearch_index_t h, usearch_error_t *e)
+Index *lgpu::H(usearch_index_t h, usearch_error_t *e)
 {
     if(!h) { FAIL(e, "lantern_gpu: null index handle"); return nullptr; }
     if(((const Index *)h)->magic != kIndexMagic) { FAIL(e, "lantern_gpu: not an index handle (stale, freed or foreign pointer)"); return nullptr; }
-    // HIP's current device is per host thread: an index lives on the device it was created on, whichever thread calls
-    // (one thread per GPU is how a single process drives a node: lantern_gpu_comm_init_local)
     (void)hipSetDevice(((Index *)h)->device);
     return (Index *)h;
 }
@@ -1910,9 +1975,9 @@ try {
     const size_t row_words = (size_t)ix->chunks * 4;
     std::vector<uint32_t> padded(nq * row_words);
     pad_rows(ix, queries, (int)kind, nq, padded.data());
-    char *dq = (char *)scratch(ix, 5, nq * row_words * 4);
+    char *dq = (char *)scratch(ix, kScratchCallIn, nq * row_words * 4);
     // [W][nq][k] labels | [W][nq][k] distances | merged labels | merged distances | merged counts
-    char *dall = (char *)scratch(ix, 6, (size_t)W * part * 12 + part * 12 + nq * 4 + 64);
+    char *dall = (char *)scratch(ix, kScratchCallOut, (size_t)W * part * 12 + part * 12 + nq * 4 + 64);
     if(!dq || !dall) { FAIL(e, ix->err.c_str()); return; }
     uint64_t *g_lab = (uint64_t *)dall;
     float    *g_dist = (float *)(dall + (size_t)W * part * 8);
@@ -2103,7 +2168,6 @@ void lantern_gpu_cursor_close(lantern_gpu_cursor_t *c) { delete c; }
 // that laid its rows out at any other stride would get wrong answers and a read past the end of its buffer with no error.  The
 // stride is therefore part of the call (`_strided`) and a mismatch is refused; the form without it is accepted only where the
 // stride is unambiguous -- the index stores rows at the vector's own length rounded up to 16 bytes.
-static const char *kStrideMismatch = "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)";
 static const char *kStrideAmbiguous =
     "lantern_gpu: this index stores rows at a stride wider than the vector's own length (lantern_gpu_row_bytes): device-resident "
     "queries must be handed over with their stride, through lantern_gpu_search_batch_device_strided";
@@ -2140,20 +2204,7 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
-// the page-locked staging block `which` (0 .. kLanes - 1: the lanes, kLanes: lantern_gpu_search_batch), grown on demand; nullptr on failure
-extern "C++" char *lgpu::host_stage(Index *ix, int which, size_t need)
-try {
-    if(ix->lane_host_bytes[ which ] < need) {
-        if(ix->lane_host[ which ]) (void)hipHostFree(ix->lane_host[ which ]);
-        ix->lane_host[ which ] = nullptr;
-        ix->lane_host_bytes[ which ] = 0;
-        const size_t grow = need + need / 2;
-        if(hipHostMalloc((void **)&ix->lane_host[ which ], grow, hipHostMallocMapped) != hipSuccess) return nullptr;  // (mapped: lane_notify's kernels write into it)
-        ix->lane_host_bytes[ which ] = grow;
-    }
-    return ix->lane_host[ which ];
-}
-LANTERN_ABI_CATCH(nullptr)
+static const char *kBatchFailed = "lantern_gpu: HIP failure during batched search";
 
 void lantern_gpu_search_batch(usearch_index_t h, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
                               usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
@@ -2165,34 +2216,14 @@ try {
     if(nq == 0 || k == 0) return;
     std::lock_guard<std::mutex> g(ix->mu);
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    const size_t row_words = (size_t)ix->chunks * 4;
-    // queries and answers pass through one page-locked block: one copy up, one down (labels | distances | counts as they lie),
-    // at the link's rate instead of through the runtime's staging of pageable memory
-    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4;
-    char *const  hs = host_stage(ix, Index::kLanes, q_bytes + out_bytes + 64);
-    if(!hs) { FAIL(e, "lantern_gpu: cannot allocate the page-locked staging block"); return; }
-    uint32_t *const padded = (uint32_t *)hs;
-    char *const     h_out = hs + ((q_bytes + 63) & ~(size_t)63);
-    pad_rows(ix, queries, (int)kind, nq, padded);
-    char *dq = (char *)scratch(ix, 5, q_bytes);
-    char *dout = (char *)scratch(ix, 6, out_bytes + 64);
-    if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
-    uint64_t *d_lab = (uint64_t *)dout;
-    float    *d_dist = (float *)(dout + nq * k * 8);
-    uint32_t *d_cnt = (uint32_t *)(dout + nq * k * 12);
-    bool      ok = hipMemcpyAsync(dq, padded, q_bytes, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
-    ok = ok && run_search_device(ix, (const uint4 *)dq, nq, k, ef, 0, d_lab, d_dist, nullptr, d_cnt, nullptr, nullptr, ix->stream,
-                                 ix->search_waves);
-    ok = ok && hipMemcpyAsync(h_out, dout, out_bytes, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
-    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
-    if(!ok) {
-        if(ix->err.empty()) set_err(ix, "lantern_gpu: HIP failure during batched search");
-        FAIL(e, ix->err.c_str());
-        return;
-    }
-    std::memcpy(labels, h_out, nq * k * 8);
-    std::memcpy(distances, h_out + nq * k * 8, nq * k * 4);
-    if(counts) std::memcpy(counts, h_out + nq * k * 12, nq * 4);
+    ix->err.clear();
+    HostBatch b = batch_layout(ix, Index::kLanes, nq, k);
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
+    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
+    bool ok = batch_upload(b);
+    ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr, nullptr,
+                                 b.stream, ix->search_waves);
+    if(!batch_finish_locked(ix, b, ok, kBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2210,18 +2241,9 @@ try {
     if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null buffer"); return; }
-    const size_t row_words = (size_t)ix->chunks * 4;
-    // Queries and answers pass through ONE page-locked block per lane (a lane has one caller at a time): the padded queries go up
-    // in one copy, labels + distances + counts come back in one, both at the link's rate and without the runtime's staging of
-    // pageable memory (four copies of it before: ~40 us of a small batch's ~150).
-    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4, need = q_bytes + out_bytes + 64;
-    char *const hs = host_stage(ix, lane, need);
-    if(!hs) { FAIL(e, "lantern_gpu: cannot allocate the lane's page-locked staging block"); return; }
-    uint32_t *const padded = (uint32_t *)hs;  // (chunks and the scalar kind are fixed at init: no lock needed yet)
-    char *const     h_out = hs + ((q_bytes + 63) & ~(size_t)63);
-    pad_rows(ix, queries, (int)kind, nq, padded);
-    hipStream_t st = nullptr;
-    bool        ok = true;
+    HostBatch b = batch_layout(ix, lane, nq, k);
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
+    bool ok = true;
     // A lane's error text belongs to the calling thread: ix->err is shared by both lanes (and by every other entry point) and
     // may be rewritten or cleared the moment the mutex is dropped, while the caller -- the scan service's dispatcher -- reads
     // the message later and without the lock.
@@ -2230,28 +2252,18 @@ try {
     {
         std::lock_guard<std::mutex> g(ix->mu);
         if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        if(!ix->lane_stream[ lane ] && hipStreamCreateWithFlags(&ix->lane_stream[ lane ], hipStreamNonBlocking) != hipSuccess) {
-            FAIL(e, "lantern_gpu: cannot create the lane's stream");
-            return;
-        }
-        st = ix->lane_stream[ lane ];
-        char *dq = (char *)scratch(ix, 12 + 2 * lane, nq * row_words * 4);
-        char *dout = (char *)scratch(ix, 13 + 2 * lane, nq * k * 12 + nq * 4 + 64);
-        if(!dq || !dout) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        uint64_t *d_lab = (uint64_t *)dout;
-        float    *d_dist = (float *)(dout + nq * k * 8);
-        uint32_t *d_cnt = (uint32_t *)(dout + nq * k * 12);
-        ok = hipMemcpyAsync(dq, padded, q_bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && run_search_device(ix, (const uint4 *)dq, nq, k, ef, 0, d_lab, d_dist, nullptr, d_cnt, nullptr, nullptr, st, ix->search_waves);
-        ok = ok && hipMemcpyAsync(h_out, dout, out_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;  // labels | distances | counts, as they lie
-        if(!ok) msg = ix->err.empty() ? "lantern_gpu: HIP failure during batched search" : ix->err;
+        ix->err.clear();
+        if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        ok = batch_upload(b);
+        ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                     nullptr, b.stream, ix->search_waves);
+        ok = ok && batch_download(b);
+        if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
     }
     // the wait is the long part: outside the mutex, so that the other lane can queue its batch meanwhile
-    if(hipStreamSynchronize(st) != hipSuccess && ok) { ok = false; msg = "lantern_gpu: HIP failure during batched search"; }
+    if(hipStreamSynchronize(b.stream) != hipSuccess && ok) { ok = false; msg = kBatchFailed; }
     if(!ok) { FAIL(e, msg.c_str()); return; }
-    std::memcpy(labels, h_out, nq * k * 8);
-    std::memcpy(distances, h_out + nq * k * 8, nq * k * 4);
-    if(counts) std::memcpy(counts, h_out + nq * k * 12, nq * 4);
+    batch_unpack(b, 0, nq, labels, distances, counts);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2272,46 +2284,37 @@ try {
     if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances || !done) { FAIL(e, "lantern_gpu: null buffer or callback"); return; }
-    const size_t row_words = (size_t)ix->chunks * 4;
-    const size_t q_bytes = nq * row_words * 4, out_bytes = nq * k * 12 + nq * 4, flag_bytes = nq * 4;
-    const size_t out_at = (q_bytes + 63) & ~(size_t)63, flag_at = (out_at + out_bytes + 63) & ~(size_t)63, need = flag_at + flag_bytes + 64;
-    char *const  hs = host_stage(ix, lane, need);
-    if(!hs) { FAIL(e, "lantern_gpu: cannot allocate the lane's page-locked staging block"); return; }
+    HostBatch b = batch_layout(ix, lane, nq, k, nq * 4);  // extra: one flag per query
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
     char *hs_dev = nullptr;  // the same block as the device names it
-    if(hipHostGetDevicePointer((void **)&hs_dev, hs, 0) != hipSuccess || !hs_dev) {
+    if(hipHostGetDevicePointer((void **)&hs_dev, b.hs, 0) != hipSuccess || !hs_dev) {
         (void)hipGetLastError();
         FAIL(e, "lantern_gpu: the lane's staging block is not device-mapped");
         return;
     }
-    uint32_t *const padded = (uint32_t *)hs;
-    char *const     h_out = hs + out_at;
-    uint32_t *const flags = (uint32_t *)(hs + flag_at);
-    pad_rows(ix, queries, (int)kind, nq, padded);
-    std::memset(flags, 0, flag_bytes);
-    hipStream_t st = nullptr;
-    bool        ok = true;
+    uint32_t *const flags = (uint32_t *)b.h_extra();
+    std::memset(flags, 0, b.extra_bytes);
+    bool ok = true;
     static thread_local std::string msg;
     msg.clear();
     {
         std::lock_guard<std::mutex> g(ix->mu);
         if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        if(!ix->lane_stream[ lane ] && hipStreamCreateWithFlags(&ix->lane_stream[ lane ], hipStreamNonBlocking) != hipSuccess) {
-            FAIL(e, "lantern_gpu: cannot create the lane's stream");
-            return;
-        }
-        st = ix->lane_stream[ lane ];
+        ix->err.clear();
         // A service-sized batch's queries are read by the walks straight out of the page-locked block (each workgroup fetches its 3 KB
         // row over the host link once, as a lone usearch_search_ef does): no copy command in front of the kernel -- a DMA command costs
         // tens of microseconds of queueing, as much as a tenth of a walk.  Large batches are copied into HBM first, at the link's rate.
-        const bool  direct_queries = q_bytes <= (size_t)1 << 20;
-        char       *dq = direct_queries ? hs_dev : (char *)scratch(ix, 12 + 2 * lane, nq * row_words * 4);
-        if(!dq) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        char *const d_out = hs_dev + out_at;
-        ok = direct_queries || hipMemcpyAsync(dq, padded, q_bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && run_search_device(ix, (const uint4 *)dq, nq, k, ef, 0, (uint64_t *)d_out, (float *)(d_out + nq * k * 8), nullptr, (uint32_t *)(d_out + nq * k * 12),
-                                     nullptr, nullptr, st, ix->search_waves, nullptr, (uint32_t *)(hs_dev + flag_at));
-        if(!ok) msg = ix->err.empty() ? "lantern_gpu: HIP failure during batched search" : ix->err;
+        const bool direct_queries = b.q_bytes <= (size_t)1 << 20;
+        if(!batch_device(ix, b, false)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        b.d_q = direct_queries ? hs_dev : (char *)scratch(ix, lane_query_scratch(lane), b.q_bytes);
+        if(!b.d_q) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        b.d_out = hs_dev + b.out_at;  // the answers land in the block itself: nothing to copy down
+        ok = direct_queries || batch_upload(b);
+        ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                     nullptr, b.stream, ix->search_waves, nullptr, (uint32_t *)(hs_dev + b.extra_at));
+        if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
     }
+    const hipStream_t st = b.stream;
     if(!ok) { (void)hipStreamSynchronize(st); FAIL(e, msg.c_str()); return; }
     // hand the answers on as their flags come up (outside the mutex: the other lanes queue their batches meanwhile)
     std::vector<uint32_t> pending(nq), ready;
@@ -2350,11 +2353,7 @@ try {
             }
         }
         if(!ready.empty()) {
-            for(uint32_t j : ready) {
-                std::memcpy(labels + (size_t)j * k, h_out + (size_t)j * k * 8, k * 8);
-                std::memcpy(distances + (size_t)j * k, h_out + nq * k * 8 + (size_t)j * k * 4, k * 4);
-                if(counts) std::memcpy(counts + j, h_out + nq * k * 12 + (size_t)j * 4, 4);
-            }
+            for(uint32_t j : ready) batch_unpack(b, j, 1, labels, distances, counts);
             done(done_ctx, ready.data(), ready.size());
             idle = 0;
             quiet_since = now_ns();
@@ -2379,7 +2378,7 @@ try {
         }
     }
     if(hipStreamSynchronize(st) != hipSuccess) ok = false;
-    if(!ok) { msg = "lantern_gpu: HIP failure during batched search"; FAIL(e, msg.c_str()); }
+    if(!ok) { msg = kBatchFailed; FAIL(e, msg.c_str()); }
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2448,7 +2447,7 @@ try {
     for(size_t i = 0; i < n; ++i)
         if(slots[ i ] >= ix->n) { FAIL(e, "lantern_gpu: slot out of range"); return; }
     const size_t row = (size_t)ix->chunks * 16;
-    char        *buf = (char *)scratch(ix, 5, row + n * 8 + 16);
+    char        *buf = (char *)scratch(ix, kScratchCallIn, row + n * 8 + 16);
     if(!buf) { FAIL(e, ix->err.c_str()); return; }
     std::vector<uint32_t> padded((size_t)ix->chunks * 4);
     pad_row(ix, query, (ix->scalar == usearch_scalar_b1_k && !ix->b1_from_f32) ? usearch_scalar_b1_k : usearch_scalar_f32_k, padded.data());
@@ -2741,8 +2740,8 @@ try {
     const size_t in_bytes = input_bytes(ix, qkind);
     std::vector<uint32_t> padded(nq * row_words);
     for(size_t i = 0; i < nq; ++i) pad_row(ix, (const char *)queries + i * in_bytes, qkind, &padded[ i * row_words ]);
-    uint4 *dq = (uint4 *)scratch(ix, 5, nq * row_words * 4);
-    char  *dout = (char *)scratch(ix, 6, nq * k * 8 + 64);
+    uint4 *dq = (uint4 *)scratch(ix, kScratchCallIn, nq * row_words * 4);
+    char  *dout = (char *)scratch(ix, kScratchCallOut, nq * k * 8 + 64);
     if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
     uint32_t *d_slots = (uint32_t *)dout;
     float    *d_dists = (float *)(d_slots + nq * k);

@@ -24,11 +24,38 @@ struct Cursor
     std::unordered_set<uint32_t> seen;
 };
 
+constexpr int kIndexLanes = 8;  // Index::kLanes, Index::kSearchSlots
+
+// ---- the device scratch buffers (Index::d_scratch) by name ---------------------------------------------------------------------
+enum ScratchSlot : int
+{
+    // an insert batch (flush_locked)
+    kScratchLinkOff,
+    kScratchLinks,
+    kScratchReqs,
+    kScratchGroups,
+    kScratchWork,
+    kScratchTops,
+    kScratchSort,
+    kScratchShardParts,  // the sharded build's gathered candidate lists
+    // The input and the output of ONE CALL on the index stream (the host forms of every batched, cursor, exact and partitioned search,
+    // the distance gather, the sharded insert's list records).  Shared safely: every user queues its work under ix->mu and on the
+    // index stream, which runs one call's work after the other's.
+    kScratchCallIn,
+    kScratchCallOut,
+    kScratchLanes,                                     // 2 per lane: queries, answers (lantern_gpu_search_batch_lane*)
+    kScratchTables = kScratchLanes + 2 * kIndexLanes,  // 1 per launch slot: a per-query filtered launch's selection list + descriptors
+    kScratchCount = kScratchTables + kIndexLanes
+};
+inline int lane_query_scratch(int lane) { return kScratchLanes + 2 * lane; }
+inline int lane_answer_scratch(int lane) { return kScratchLanes + 2 * lane + 1; }
+inline int launch_table_scratch(int launch_slot) { return kScratchTables + launch_slot; }
+
 constexpr uint64_t kIndexMagic = 0x4C414E5445524E31ull;  // "LANTERN1": the first word of every live index handle
 
 struct Index
 {
-    uint64_t magic = kIndexMagic;  // checked by every entry point (index.cpp H()): a stale, freed or foreign pointer handed over as a
+    uint64_t magic = kIndexMagic;  // checked by every entry point (abi_guard.hpp H()): a stale, freed or foreign pointer handed over as a
                                    // usearch_index_t is refused with an error string instead of being dereferenced as an index
     // ---- configuration (usearch_init_options_t as Lantern fills it) -------------------------------
     usearch_init_options_t opts{};
@@ -93,12 +120,11 @@ struct Index
     bool      use_tickets = true;   // LANTERN_GPU_TICKETS=0: static striding (tuning / debugging)
     unsigned long long *d_totals = nullptr;  // [0..1] search D,E  [2..4] insert D,E,refine  [5] revlink pairs
 
-    // scratch (grown on demand)
-    static const int kLanes = 8;  // lantern_gpu_search_batch_lane: batches one caller each may keep in flight side by side
-    // [12 ..]: queries / answers of the lanes of lantern_gpu_search_batch_lane; [12 + 2 kLanes ..]: one per launch slot (kSearchSlots), the
-    // selection list and descriptor table of a per-query filtered launch (filter.hip)
-    void  *d_scratch[ 12 + 3 * kLanes ] = {};
-    size_t scratch_bytes[ 12 + 3 * kLanes ] = {};
+    // scratch (grown on demand): device buffers named by ScratchSlot (below the struct)
+    static const int kLanes = kIndexLanes;   // lantern_gpu_search_batch_lane: batches one caller each may keep in flight side by side
+    static const int kSearchSlots = kLanes;  // search launches in flight side by side ("launch slots", below)
+    void  *d_scratch[ kScratchCount ] = {};
+    size_t scratch_bytes[ kScratchCount ] = {};
     hipStream_t lane_stream[ kLanes ] = {};  // created on first use
     char       *lane_host[ kLanes + 1 ] = {};  // page-locked staging of queries and answers: the lanes (one caller each), [kLanes] lantern_gpu_search_batch (under mu)
     size_t      lane_host_bytes[ kLanes + 1 ] = {};
@@ -179,7 +205,7 @@ struct Index
     // have two slabs ("launch slots"): two batches on two streams run side by side (the second fills the machine while the
     // first one's longest walks drain); a third waits for the slot it reuses.  INSERT batches mutate the graph: they wait for
     // every search in flight, and searches on other streams wait for them.
-    static const int kSearchSlots = kLanes;  // one slab of visited bitmaps per search launch in flight (allocated on first use)
+    // one slab of visited bitmaps per search launch in flight (allocated on first use)
     uint32_t   *slot_bitmaps[ kSearchSlots ] = {};  // [0] aliases d_bitmaps (the slab inserts use too)
     size_t      slot_rows[ kSearchSlots ] = {}, slot_words[ kSearchSlots ] = {};
     hipEvent_t  slot_done[ kSearchSlots ] = {};
@@ -208,6 +234,41 @@ struct Index
     View view() const;
 };
 
+// ---- one batched search's trip through the host ---------------------------------------------------------------------------------
+// The block `padded queries | labels | distances | counts [| extra]` as it lies in a page-locked staging block (every region at a
+// multiple of 64 bytes; the answers lie the same way in their device buffer), and the stream and buffers the trip uses.  `which`
+// names them all: a lane (its own stream, staging block and device buffers: one caller at a time), or kLanes -- the index stream,
+// the index's own staging block and the per-call scratch, all three under ix->mu.  One copy up, one down, at the link's rate.
+struct HostBatch
+{
+    size_t      nq = 0, k = 0, q_bytes = 0, out_at = 0, out_bytes = 0, extra_at = 0, extra_bytes = 0;
+    int         which = Index::kLanes;
+    char       *hs = nullptr;                     // the staging block (batch_stage)
+    hipStream_t stream = nullptr;                 // (batch_device)
+    char       *d_q = nullptr, *d_out = nullptr;  // device: the queries, the answers (batch_device)
+
+    size_t    bytes() const { return extra_at + extra_bytes + 64; }
+    char     *h_out() const { return hs + out_at; }
+    char     *h_extra() const { return hs + extra_at; }
+    // the three answer arrays of a block that starts at `out` (host or device)
+    uint64_t *labels(char *out) const { return (uint64_t *)out; }
+    float    *dists(char *out) const { return (float *)(out + nq * k * 8); }
+    uint32_t *counts(char *out) const { return (uint32_t *)(out + nq * k * 12); }
+};
+constexpr const char *kNoStage = "lantern_gpu: cannot allocate the page-locked staging block";  // batch_stage failed: the index's block, a lane's
+constexpr const char *kNoLaneStage = "lantern_gpu: cannot allocate the lane's page-locked staging block";
+HostBatch batch_layout(const Index *ix, int which, size_t nq, size_t k, size_t extra_bytes = 0);
+bool      batch_stage(Index *ix, HostBatch &b, const void *queries, int kind);  // the staging block, the queries padded into it; false: no block (ix->err untouched: lanes stage without ix->mu)
+bool      batch_device(Index *ix, HostBatch &b, bool buffers = true);  // under ix->mu: the stream (a lane's is created on first use), the two device buffers; false -> ix->err
+bool      batch_upload(const HostBatch &b);    // queue staging -> d_q
+bool      batch_download(const HostBatch &b);  // queue d_out -> staging
+void      batch_unpack(const HostBatch &b, size_t first, size_t count, uint64_t *labels, float *distances, uint32_t *counts /* or NULL */);  // staged rows -> the caller's arrays
+// under ix->mu throughout: the answers down, the wait, the caller's arrays; false -> ix->err (`what` if nothing more specific is there)
+bool      batch_finish_locked(Index *ix, const HostBatch &b, bool ok, const char *what, uint64_t *labels, float *distances, uint32_t *counts);
+// the first k of `got` results whose slot `cur` has not handed out before, recorded in cur->seen as they are taken; returns how many
+size_t    take_unseen(Cursor *cur, const uint64_t *labels, const float *dists, const uint32_t *slots, uint32_t got, size_t k, uint64_t *out_labels,
+                      float *out_dists);
+
 // implemented in index.cpp
 const char *set_err(Index *ix, const std::string &msg);
 bool        flush_locked(Index *ix);            // false -> ix->err set
@@ -221,7 +282,6 @@ void       *scratch(Index *ix, int which, size_t bytes);
 bool        pad_row(const Index *ix, const void *vec, int kind_in, uint32_t *dst);
 size_t      input_bytes(const Index *ix, int kind_in);
 bool        kind_accepted(const Index *ix, int kind_in);
-char       *host_stage(Index *ix, int which, size_t need);  // page-locked staging block of a lane ([kLanes]: the index stream's, under mu), grown on demand
 void        pad_rows(const Index *ix, const void *rows, int kind, size_t count, uint32_t *padded);
 uint32_t   *next_ticket(Index *ix, size_t work, int grid, hipStream_t stream);  // a zeroed work ticket of a persistent launch, or NULL
 uint32_t    vis_undo_cap();
