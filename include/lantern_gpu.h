@@ -283,6 +283,37 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_device_strided(usearch_index_t,
                                                                 float *d_distances, uint32_t *d_slots, uint32_t *d_counts,
                                                                 uint64_t *d_dist_evals, uint64_t *d_expansions, void *stream,
                                                                 usearch_error_t *);
+/* PER-QUERY k, ef AND skip.  The entry points above take one k, one ef and one skip for the whole call; the four
+ * below take them per query, params[i] for query i (ef 0 = the index's default; reserved must be 0), and serve the whole batch in at
+ * most THREE launches whatever the parameters: the queries are split by where the walk keeps its candidate list -- expansion
+ * (= max(ef, k + skip)) <= 64, <= 128, beyond -- and each non-empty class is one launch.
+ * CONTRACT: for query i the ids, distance bits, count, D and E are exactly those of the uniform call with (k_i, ef_i, skip_i).
+ * labels / distances (and slots) are nq x k_stride: row i holds query i's k_i answers, its tail label 0, +inf (slot ~0) as a uniform
+ * row's unused tail; k_stride < max k_i is refused.  A query with k_i = 0 takes no walk: count 0, D = E = 0, and it is still handed on
+ * by the notify form.  Every refusal -- a bad parameter, an expansion beyond the 160 KiB LDS budget -- is for the whole call, before
+ * anything is launched or written, and names the first offending position: "... (params[i])".
+ * The host and lane forms take `skip` too (the uniform host forms have none): a service that wants the device to drop the rows a scan
+ * was already handed says so here.  Filtered searches keep a uniform (k, ef, skip): lantern_gpu_search_batch_filtered_each*. */
+typedef struct lantern_gpu_query_params { uint32_t k, ef, skip, reserved; } lantern_gpu_query_params; /* ef 0 = index default; reserved must be 0 */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_params(usearch_index_t, const void *queries, size_t nq, usearch_scalar_kind_t,
+                                                        const lantern_gpu_query_params *params, size_t k_stride, usearch_label_t *labels,
+                                                        float *distances, uint32_t *counts, usearch_error_t *);
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_params_lane(usearch_index_t, int lane, const void *queries, size_t nq, usearch_scalar_kind_t,
+                                                             const lantern_gpu_query_params *params, size_t k_stride, usearch_label_t *labels,
+                                                             float *distances, uint32_t *counts, usearch_error_t *);
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_params_lane_notify(usearch_index_t, int lane, const void *queries, size_t nq,
+                                                                    usearch_scalar_kind_t, const lantern_gpu_query_params *params, size_t k_stride,
+                                                                    usearch_label_t *labels, float *distances, uint32_t *counts,
+                                                                    lantern_gpu_queries_done_fn done, void *done_ctx, usearch_error_t *);
+/* every buffer in device memory except `params`, a HOST array that is read during the call (it may be reused once the call returns) */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_params_device(usearch_index_t, const void *d_queries, size_t query_stride_bytes, size_t nq,
+                                                               const lantern_gpu_query_params *params, size_t k_stride, uint64_t *d_labels,
+                                                               float *d_distances, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_dist_evals,
+                                                               uint64_t *d_expansions, void *stream, usearch_error_t *);
+/* the last per-query-parameter call on this index that passed its checks (diagnostic; tests assert the regime): out[0] launches made
+ * (0 .. 3), [1] [2] [3] queries in the classes expansion <= 64, <= 128, beyond, [4] the largest expansion, [5] 1 if any launch took a
+ * latency-bound (spec) shape.  All zero before the first such call. */
+LANTERN_GPU_EXPORT void lantern_gpu_last_params_launch(usearch_index_t, uint32_t out[6], usearch_error_t *);
 /* ------------------------------------------------------------------------------------------ */
 /* Filtered search: k-NN limited to an allow-set of rows.                       */
 /* PARITY UNPINNED BY THE REFERENCE: the reference's usearch fork is not in the tree; what follows */
@@ -700,8 +731,12 @@ LANTERN_GPU_EXPORT void     lantern_index_server_stop(lantern_index_server_t *);
 /* (scan.c:167-338) calls lantern_scan_client_search where it calls usearch_search_ef today; the   */
 /* server waits at most `max_wait_us` after the first queued query for company (at most            */
 /* `max_batch` queries per launch; less if every connected backend is already accounted for or    */
-/* a dispatcher's share of them is), runs one lantern_gpu_search_batch per distinct (k, ef) and    */
-/* routes the answers back.  No thread per connection: a few epoll I/O threads                    */
+/* a dispatcher's share of them is), searches them and routes the answers back: one call per    */
+/* distinct (k, ef) of the batch.  LANTERN_SCAN_MIXED=1, on a device index: the unfiltered        */
+/* requests of a batch go out in ONE per-query-parameter call whatever their (k, ef)              */
+/* (lantern_gpu_search_batch_params_lane_notify: at most three launches), or -- when they all      */
+/* share one (k, ef) -- in the uniform call.  (Off by default until its A/B is on record:         */
+/* DESIGN.md 4.10.)  No thread per connection: a few epoll I/O threads                    */
 /* (LANTERN_SCAN_IO_THREADS) carry all sockets.  Wire format: lantern_amd/csrc/scan_server.cpp.    */
 /* ------------------------------------------------------------------------------------------ */
 typedef struct lantern_scan_server lantern_scan_server_t;
@@ -739,10 +774,20 @@ LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_filtered_fn(
                                                                                 size_t max_batch, unsigned max_wait_us, usearch_error_t *);
 /* filters set (clears not counted), requests searched through a filter, per-query-filter calls made, the largest number of DISTINCT
  * filters one such call carried, device bytes of the filters resident now */
+/* MIXED BATCHES THROUGH AN INJECTED BACK END (tests of the dispatcher; a host that shards queries over several GPUs): the batch
+ * search with (k, ef, skip) per query -- answer rows k_stride wide, as lantern_gpu_search_batch_params.  The unfiltered requests of a
+ * batch that carry more than one distinct (k, ef) go to it in one call; a batch with one shared (k, ef) goes to the plain function. */
+typedef int (*lantern_batch_search_params_fn)(void *ctx, const void *queries, size_t nq, size_t vec_bytes, const lantern_gpu_query_params *params,
+                                              size_t k_stride, uint64_t *labels, float *distances, uint32_t *counts, const char **err);
+LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_params_fn(lantern_batch_search_fn, lantern_batch_search_params_fn, void *ctx,
+                                                                              size_t vec_bytes, const char *host, int port, size_t max_batch,
+                                                                              unsigned max_wait_us, usearch_error_t *);
 LANTERN_GPU_EXPORT void lantern_scan_server_filter_stats(lantern_scan_server_t *, uint64_t *filters_set, uint64_t *filtered_requests,
                                                          uint64_t *each_calls, uint64_t *most_distinct_filters, uint64_t *resident_bytes);
 LANTERN_GPU_EXPORT int  lantern_scan_server_port(lantern_scan_server_t *);
-/* queries received, batches formed, search launches (one per distinct (k, ef) of a batch), largest batch so far */
+/* queries received, batches formed, back-end calls made (per batch: one per distinct (k, ef) -- or ONE for all its unfiltered requests
+ * where the back end takes mixed batches -- plus one per (k, ef) of its filtered requests; a mixed call is at most three kernel
+ * launches), largest batch so far */
 LANTERN_GPU_EXPORT void lantern_scan_server_stats(lantern_scan_server_t *, uint64_t *requests, uint64_t *batches,
                                                   uint64_t *launches, uint64_t *largest_batch);
 /* batches formed so far by size: bins[b] counts batches of 2^b .. 2^(b+1) - 1 requests (b < 16); returns the bins written */

@@ -114,7 +114,25 @@ EXPORTS = [
     "lantern_gpu_filter_resident_bytes", "lantern_scan_server_start_filtered_fn", "lantern_scan_server_filter_stats", "lantern_scan_client_set_filter",
     "lantern_scan_client_clear_filter",
     "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
+    # per-query k, ef and skip (lantern_gpu.h "PER-QUERY k, ef AND skip")
+    "lantern_gpu_search_batch_params", "lantern_gpu_search_batch_params_lane", "lantern_gpu_search_batch_params_lane_notify",
+    "lantern_gpu_search_batch_params_device", "lantern_gpu_last_params_launch", "lantern_scan_server_start_params_fn",
 ]
+# lantern_gpu_query_params: one row {k, ef, skip, reserved} per query (ef 0 = the index's default; reserved must be 0)
+QUERY_PARAMS = np.dtype([("k", np.uint32), ("ef", np.uint32), ("skip", np.uint32), ("reserved", np.uint32)])
+
+
+def query_params(params) -> np.ndarray:
+    """Rows of (k, ef, skip) -- or (k, ef), or a ready QUERY_PARAMS array -- as the C array of lantern_gpu_query_params."""
+    if isinstance(params, np.ndarray) and params.dtype == QUERY_PARAMS:
+        return np.ascontiguousarray(params)
+    out = np.zeros(len(params), dtype=QUERY_PARAMS)
+    for i, p in enumerate(params):
+        p = tuple(int(x) for x in p)
+        out[i] = (p[0], p[1] if len(p) > 1 else 0, p[2] if len(p) > 2 else 0, 0)
+    return out
+
+
 FILTER_SKIP_DELETED = 1  # LANTERN_GPU_FILTER_SKIP_DELETED
 FILTER_PATHS = {"auto": 0, "walk": 1, "exact": 2}
 
@@ -126,6 +144,9 @@ BATCH_SEARCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_s
 FILTER_MAKE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                              C.POINTER(C.c_char_p))
 FILTER_FREE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p)
+# the mixed-batch back end of lantern_scan_server_start_params_fn: (ctx, queries, nq, vec_bytes, params, k_stride, labels, dists, counts, err)
+BATCH_SEARCH_PARAMS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
 BATCH_SEARCH_EACH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
 
@@ -294,7 +315,13 @@ def lib() -> C.CDLL:
         "lantern_gpu_search_batch_filtered_each_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_search_batch_filtered_each_lane": (None, [vp, i32, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
         "lantern_gpu_last_filtered_each": (None, [vp, vp, err]),
+        "lantern_gpu_search_batch_params": (None, [vp, vp, sz, i32, vp, sz, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_params_lane": (None, [vp, i32, vp, sz, i32, vp, sz, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_params_lane_notify": (None, [vp, i32, vp, sz, i32, vp, sz, vp, vp, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_params_device": (None, [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, err]),
+        "lantern_gpu_last_params_launch": (None, [vp, vp, err]),
         "lantern_gpu_filter_resident_bytes": (sz, [vp, err]),
+        "lantern_scan_server_start_params_fn": (vp, [BATCH_SEARCH_FN, BATCH_SEARCH_PARAMS_FN, vp, sz, C.c_char_p, i32, sz, C.c_uint, err]),
         "lantern_scan_server_start_filtered_fn": (vp, [BATCH_SEARCH_FN, FILTER_MAKE_FN, FILTER_FREE_FN, BATCH_SEARCH_EACH_FN, vp, sz, C.c_char_p, i32, sz,
                                                        C.c_uint, err]),
         "lantern_scan_server_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
@@ -781,6 +808,65 @@ class GpuIndex:
         walk, exact, unfiltered, empty, distinct, launches = (int(x) for x in out)
         return {"walk": walk, "exact": exact, "unfiltered": unfiltered, "empty": empty, "distinct_filters": distinct, "launches": launches}
 
+    def _params_buffers(self, queries, params, k_stride):
+        Q = _rows(queries, self.metric)
+        nq = Q.shape[0]
+        P = query_params(params)
+        if len(P) != nq:
+            raise ValueError("one parameter row per query: got %d for %d queries" % (len(P), nq))
+        if k_stride is None:
+            k_stride = int(P["k"].max()) if nq else 0
+        return (Q, nq, P, k_stride, np.zeros((nq, k_stride), dtype=np.uint64), np.zeros((nq, k_stride), dtype=np.float32),
+                np.zeros(nq, dtype=np.uint32))
+
+    def search_batch_params(self, queries, params, k_stride=None):
+        """search_batch with (k, ef, skip) PER QUERY: params[i] = (k, ef[, skip]) -- one call, at most three launches.  The answers
+        are nq x k_stride (default: the largest k), row i's tail beyond its k_i label 0 / +inf."""
+        Q, nq, P, k_stride, labels, dists, counts = self._params_buffers(queries, params, k_stride)
+        _call("lantern_gpu_search_batch_params", self.h, _ptr(Q), nq, _kind(self.metric), _ptr(P), k_stride, _ptr(labels), _ptr(dists), _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_params_lane(self, lane, queries, params, k_stride=None):
+        """search_batch_params on a lane (one caller per lane; the lanes' launches overlap on the device)."""
+        Q, nq, P, k_stride, labels, dists, counts = self._params_buffers(queries, params, k_stride)
+        _call("lantern_gpu_search_batch_params_lane", self.h, lane, _ptr(Q), nq, _kind(self.metric), _ptr(P), k_stride, _ptr(labels), _ptr(dists),
+              _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_params_lane_notify(self, lane, queries, params, k_stride=None):
+        """lantern_gpu_search_batch_params_lane_notify: the answers, the order the queries were handed on in (one index list per
+        callback) and every row as it stood when its callback ran."""
+        Q, nq, P, k_stride, labels, dists, counts = self._params_buffers(queries, params, k_stride)
+        calls = []
+        snapshots = {}
+
+        def on_done(ctx, which, count):
+            idx = [int(which[i]) for i in range(count)]
+            calls.append(idx)
+            for j in idx:  # the rows are filled in when the callback runs
+                snapshots[j] = (labels[j].copy(), dists[j].copy(), int(counts[j]))
+
+        cb = QUERIES_DONE_FN(on_done)
+        _call("lantern_gpu_search_batch_params_lane_notify", self.h, lane, _ptr(Q), nq, _kind(self.metric), _ptr(P), k_stride, _ptr(labels),
+              _ptr(dists), _ptr(counts), C.cast(cb, C.c_void_p), None)
+        return labels, dists, counts, calls, snapshots
+
+    def search_batch_params_device(self, d_queries, query_stride, nq, params, k_stride, d_labels=None, d_dists=None, d_slots=None, d_counts=None,
+                                   d_D=None, d_E=None, stream=None):
+        """search_batch_device with (k, ef, skip) per query: `params` is a HOST array (read during the call), the rest raw device addresses."""
+        P = query_params(params)
+        if len(P) != nq:
+            raise ValueError("one parameter row per query: got %d for %d queries" % (len(P), nq))
+        _call("lantern_gpu_search_batch_params_device", self.h, _ptr(d_queries), int(query_stride), nq, _ptr(P), k_stride, _ptr(d_labels),
+              _ptr(d_dists), _ptr(d_slots), _ptr(d_counts), _ptr(d_D), _ptr(d_E), _ptr(stream))
+
+    def last_params_launch(self):
+        """The regime of the last per-query-parameter call on this index (lantern_gpu_last_params_launch)."""
+        out = np.zeros(6, dtype=np.uint32)
+        _call("lantern_gpu_last_params_launch", self.h, _ptr(out))
+        launches, c64, c128, beyond, largest, spec = (int(x) for x in out)
+        return {"launches": launches, "classes": (c64, c128, beyond), "largest_expansion": largest, "spec": bool(spec)}
+
     def distance_gather(self, query, slots):
         q = _rows(query, self.metric)[0]
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -1217,11 +1303,13 @@ class Scan:
 class ScanServer:
     """lantern_scan_server_*: one HBM-resident index serving many backends' queries in batched launches."""
 
-    def __init__(self, index=None, host="127.0.0.1", port=0, max_batch=256, max_wait_us=200, batch_fn=None, vec_bytes=0, filter_fns=None):
+    def __init__(self, index=None, host="127.0.0.1", port=0, max_batch=256, max_wait_us=200, batch_fn=None, vec_bytes=0, filter_fns=None,
+                 params_fn=None):
         """index: a GpuIndex (the server runs lantern_gpu_search_batch on it), or batch_fn(queries u8[nq, vec_bytes], k, ef)
         -> (labels u64[nq, k], dists f32[nq, k], counts u32[nq]) for tests / custom back ends.  filter_fns, with batch_fn: a back end
         with filters -- (make(labels u64[n], flags) -> (handle int != 0, allowed, resident_bytes), free(handle),
-        each(filters [nq] of handles, queries, k, ef) -> as batch_fn)."""
+        each(filters [nq] of handles, queries, k, ef) -> as batch_fn).  params_fn, with batch_fn: a back end that takes mixed batches --
+        params_fn(queries, params QUERY_PARAMS[nq], k_stride) -> (labels u64[nq, k_stride], dists f32[nq, k_stride], counts u32[nq])."""
         self._keep = None
         self.index = index
         if batch_fn is not None and filter_fns is not None:
@@ -1270,6 +1358,38 @@ class ScanServer:
 
             self._keep = (BATCH_SEARCH_FN(tramp), FILTER_MAKE_FN(tramp_make), FILTER_FREE_FN(tramp_free), BATCH_SEARCH_EACH_FN(tramp_each))
             self.s = _call("lantern_scan_server_start_filtered_fn", *self._keep, None, vec_bytes, host.encode(), port, max_batch, max_wait_us)
+        elif batch_fn is not None and params_fn is not None:
+            def fail(ex, errp):
+                self._last_error = C.c_char_p(str(ex).encode())
+                errp[0] = self._last_error
+
+            def tramp(ctx, queries, nq, vb, k, ef, labels, dists, counts, errp):
+                try:
+                    q = np.ctypeslib.as_array(C.cast(queries, C.POINTER(C.c_uint8)), shape=(nq, vb))
+                    lab, dst, cnt = batch_fn(q, int(k), int(ef))
+                    np.ctypeslib.as_array(labels, shape=(nq, k))[:] = lab
+                    np.ctypeslib.as_array(dists, shape=(nq, k))[:] = dst
+                    np.ctypeslib.as_array(counts, shape=(nq,))[:] = cnt
+                    return 0
+                except Exception as ex:  # noqa: BLE001
+                    fail(ex, errp)
+                    return 1
+
+            def tramp_params(ctx, queries, nq, vb, params, k_stride, labels, dists, counts, errp):
+                try:
+                    q = np.ctypeslib.as_array(C.cast(queries, C.POINTER(C.c_uint8)), shape=(nq, vb))
+                    P = np.ctypeslib.as_array(C.cast(params, C.POINTER(C.c_uint32)), shape=(nq, 4)).copy().view(QUERY_PARAMS).reshape(nq)
+                    lab, dst, cnt = params_fn(q, P, int(k_stride))
+                    np.ctypeslib.as_array(labels, shape=(nq, k_stride))[:] = lab
+                    np.ctypeslib.as_array(dists, shape=(nq, k_stride))[:] = dst
+                    np.ctypeslib.as_array(counts, shape=(nq,))[:] = cnt
+                    return 0
+                except Exception as ex:  # noqa: BLE001 -- becomes the error frame every query of the call gets
+                    fail(ex, errp)
+                    return 1
+
+            self._keep = (BATCH_SEARCH_FN(tramp), BATCH_SEARCH_PARAMS_FN(tramp_params))
+            self.s = _call("lantern_scan_server_start_params_fn", *self._keep, None, vec_bytes, host.encode(), port, max_batch, max_wait_us)
         elif batch_fn is not None:
             def tramp(ctx, queries, nq, vb, k, ef, labels, dists, counts, errp):
                 try:

@@ -1184,13 +1184,34 @@ bool flush_locked(Index *ix)
 // search
 // ---------------------------------------------------------------------------------------------------
 
+// the table and the query list of a per-query-parameter launch: in the scratch of the launch's slot (one copy in front of the launch; a
+// slot's earlier launch is over before its next one starts), or where the caller's device-mapped block has them
+static bool each_bind(Index *ix, const EachLaunch &each, int slot, hipStream_t stream, SearchArgs &a)
+{
+    const char *d_tbl = each.d_table;
+    if(!d_tbl) {
+        char *const d = (char *)scratch(ix, launch_table_scratch(slot), each.table_bytes);
+        if(!d) return false;
+        if(hipMemcpyAsync(d, each.h_table, each.table_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+            set_err(ix, "lantern_gpu: HIP failure (per-query parameter table)");
+            return false;
+        }
+        d_tbl = d;
+    }
+    a.qparams = (const uint4 *)d_tbl;
+    a.qlist = (const uint32_t *)(d_tbl + each.list_at);
+    a.k_stride = a.k;
+    return true;
+}
+
 bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
                        float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, hipStream_t stream,
-                       int waves, uint32_t *done, uint32_t *done_flags)
+                       int waves, uint32_t *done, uint32_t *done_flags, EachLaunch *each)
 {
-    if(nq == 0 || k == 0) return true;
+    if(nq == 0 || (k == 0 && !each)) return true;
     size_t expansion = ef ? ef : ix->ef;
     if(expansion < k + skip) expansion = k + skip;  // usearch: expansion = max(expansion, wanted)
+    if(each) expansion = each->max_expansion;       // (the per-query form: the largest of the list's own)
     // ---- a compact pq index whose subvectors are whole 16-byte chunks: the f32 walk below over rows DECODED ON THE FLY from the
     // L2-resident centroid tables (device_common.hpp PqdRow) -- the arithmetic, and so every bit of every answer, of the expanded
     // form of the same index.  (LANTERN_GPU_PQ_ADC=1, or subvectors of another width: the table walk of search_adc_kernel.hip.)
@@ -1207,6 +1228,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
         if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
         size_t lds = search_adc_lds_bytes(code_chunks, ix->chunks, (uint32_t)expansion, ix->M0, vis_slots);
         if(lds > 160 * 1024) { set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the ADC search kernel"); return false; }
+        if(each && each->dry) return true;
         int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
         // A table that leaves room for one workgroup per CU anyway (96 subvectors x 256 centroids): every query walks alone on
         // its CU, so it runs the walk that is fastest alone -- walk_spec.hpp's lone-query shape, 3 role + 8 row waves
@@ -1270,6 +1292,10 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
         a.spec = adc_spec ? 2 : 0;
         a.spec_prefetch = adc_spec ? adc_prefetch : 0;
         a.spec_cache = adc_spec ? adc_cache : 0;
+        if(each) {
+            if(!each_bind(ix, *each, slot, stream, a)) return false;
+            each->took_spec = adc_spec;
+        }
         HIPCHK(ix, launch_search_adc(ix->metric + M_ADC, a, aw, grid, stream));
         if(done) ix->slot_pending[ slot ] = false;
         else if(!release_search_slot(ix, slot, stream)) return false;
@@ -1286,7 +1312,8 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
     int spec = 0;
     if(waves <= 0) {
         const char *se = std::getenv("LANTERN_GPU_SPEC");
-        const bool  can = ix->M0 >= 2 && ix->M0 <= 64 && expansion <= 128 && !ix->phase_profile && !lds_list_env();
+        // (the per-query form has no instrumented instantiation: a profiling mode sends it to the classic shape)
+        const bool  can = ix->M0 >= 2 && ix->M0 <= 64 && expansion <= 128 && !ix->phase_profile && !lds_list_env() && !(each && ix->spec_profile);
         if(can) {
             // (measured, 1M x 768 cosine, one 1024-query batch: the four-wave latency-bound shape 796 k QPS, the classic kernel
             // 819 k -- with every walk of the batch resident the row loads saturate HBM for most of the launch and the speculative
@@ -1295,6 +1322,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
             if(se) spec = std::atoi(se);
             else if(nq <= (size_t)ix->num_cus * 2) spec = 2;  // (1M x 768 cosine: 384 queries 528 k vs 389 k, 512: 624 k vs 500 k, 768: 658 k vs 691 k)
             if(spec < 0 || spec > 4) spec = 0;
+            if(each) spec = spec >= 2 ? 2 : 0;  // the per-query form exists for the 3 + 8 wave shape only: spec 1 falls back to the classic shape
 #if !LGPU_EXPERIMENTAL
             if(spec >= 3) spec = 2;  // the variants behind 3 / 4 are not in this library (LANTERN_BUILD_EXPERIMENTAL=1 builds them)
 #else
@@ -1305,7 +1333,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
             // one wave has to issue all ~540 instructions of a hop itself; parity-green in every regime it takes.
             // Anything it does not take falls back to spec 2.
             static const bool solo_auto = std::getenv("LANTERN_GPU_SOLO") && std::atoi(std::getenv("LANTERN_GPU_SOLO")) != 0;
-            if(spec == 2 && !se && solo_auto && nq <= (size_t)ix->num_cus) spec = 4;
+            if(spec == 2 && !se && solo_auto && nq <= (size_t)ix->num_cus && !each) spec = 4;
             if(spec == 4) {
                 const size_t words = ((std::max<size_t>(ix->n, 1) + 31) / 32 + 3) & ~(size_t)3;
                 uint32_t     ne_log2 = 9;
@@ -1389,6 +1417,7 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
         set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel");
         return false;
     }
+    if(each && each->dry) return true;
     const int grid = search_grid(ix, nq, waves, spec >= 2 ? waves : spec == 1 ? 16 : 24);
     ix->last_search_grid = grid;
     const int slot = acquire_search_slot(ix, stream, (size_t)grid);
@@ -1423,8 +1452,8 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
     a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
     a.ticket = next_ticket(ix, nq, grid, stream);
     // (there is no instrumented instantiation of the decoding walk: a compact pq launch ignores phase_profile)
-    const bool prof_walk = ix->phase_profile && !pqd;
-    a.phase_cycles = spec ? (ix->spec_profile ? ix->d_totals + 16 : nullptr) : prof_walk ? ix->d_totals + 8 : nullptr;
+    const bool prof_walk = ix->phase_profile && !pqd && !each;  // (nor of the per-query form)
+    a.phase_cycles = each ? nullptr : spec ? (ix->spec_profile ? ix->d_totals + 16 : nullptr) : prof_walk ? ix->d_totals + 8 : nullptr;
     // the row bitmap only when unique-rows mode asked for it AND it covers every slot the walk can name (a reserve / add since
     // it was sized would otherwise let mark_touched write past it)
     a.touched = (!spec && prof_walk && ix->unique_rows_on && ix->d_touched && ix->touched_words * 32 >= ix->cap) ? ix->d_touched : nullptr;
@@ -1443,10 +1472,99 @@ bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, s
     a.spec = spec;
     a.spec_prefetch = spec_prefetch;
     a.spec_cache = spec_cache;
+    if(each) {
+        if(!each_bind(ix, *each, slot, stream, a)) return false;
+        each->took_spec = spec != 0;
+    }
     HIPCHK(ix, launch_search(pqd ? ix->metric + M_PQD : ix->mcode, a, waves, grid, stream));
     if(done) ix->slot_pending[ slot ] = false;  // the caller waits for the kernel itself: nothing to order later launches against
     else if(!release_search_slot(ix, slot, stream)) return false;
     ix->c_search_queries += nq;
+    return true;
+}
+
+// ---- per-query k, ef and skip (lantern_gpu_search_batch_params*) --------------------------------------------------
+std::string params_check(const lantern_gpu_query_params *params, size_t nq, size_t k_stride)
+{
+    if(nq && !params) return "lantern_gpu: null parameter array";
+    for(size_t i = 0; i < nq; ++i) {
+        const char *why = params[ i ].reserved != 0 ? "lantern_gpu: a query's reserved parameter word must be 0"
+                          : params[ i ].k > k_stride ? "lantern_gpu: k_stride is smaller than a query's k"
+                                                     : nullptr;
+        if(why) return std::string(why) + " (params[" + std::to_string(i) + "])";
+    }
+    return "";
+}
+
+bool search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const lantern_gpu_query_params *params, size_t k_stride,
+                          uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
+                          hipStream_t stream, int waves, uint32_t *done_flags, char *h_block, const char *d_block)
+{
+    const std::string why = params_check(params, nq, k_stride);
+    if(!why.empty()) return set_err(ix, why), false;
+    if(nq == 0) return true;
+    // the table {k, expansion, skip, 0} by batch position (run_search_device's rule: expansion = max(ef or the index's, k + skip)), and
+    // the three classes of the list placement (search_kernel.hip: one key per lane up to 64, two up to 128, the LDS list beyond)
+    std::vector<char> pageable;
+    if(!h_block) { pageable.resize(params_table_bytes(nq)); h_block = pageable.data(); d_block = nullptr; }
+    uint32_t *const tbl = (uint32_t *)h_block;
+    std::vector<uint32_t> cls[ 3 ];
+    uint32_t              top[ 3 ] = { 0, 0, 0 };
+    auto class_of = [](uint32_t exp) { return exp <= 64 ? 0 : exp <= 128 ? 1 : 2; };
+    for(size_t i = 0; i < nq; ++i) {
+        size_t exp = params[ i ].ef ? params[ i ].ef : ix->ef;
+        exp = std::max(exp, (size_t)params[ i ].k + (size_t)params[ i ].skip);
+        exp = std::min<size_t>(exp, (size_t)1 << 20);  // (far past the LDS budget already: refused below, and it fits the table's word)
+        tbl[ 4 * i ] = params[ i ].k;
+        tbl[ 4 * i + 1 ] = (uint32_t)exp;
+        tbl[ 4 * i + 2 ] = params[ i ].skip;
+        tbl[ 4 * i + 3 ] = 0;
+        const int c = class_of((uint32_t)exp);
+        cls[ c ].push_back((uint32_t)i);
+        top[ c ] = std::max(top[ c ], (uint32_t)exp);
+    }
+    // refusals are for the whole call and come before anything is queued: every class's launch is planned once without being made
+    for(int c = 2; c >= 0; --c) {
+        if(cls[ c ].empty()) continue;
+        EachLaunch dry;
+        dry.max_expansion = top[ c ];
+        dry.dry = true;
+        if(run_search_device(ix, d_queries, cls[ c ].size(), k_stride, 0, 0, d_labels, d_dists, d_slots, d_counts, d_D, d_E, stream, waves, nullptr, done_flags, &dry))
+            continue;
+        const std::string refusal = ix->err;
+        for(uint32_t i : cls[ c ]) {  // (batch order: the first position whose own expansion is refused)
+            dry.max_expansion = tbl[ 4 * i + 1 ];
+            if(run_search_device(ix, d_queries, cls[ c ].size(), k_stride, 0, 0, d_labels, d_dists, d_slots, d_counts, d_D, d_E, stream, waves, nullptr, done_flags, &dry))
+                continue;
+            return set_err(ix, refusal + " (params[" + std::to_string(i) + "])"), false;
+        }
+        return set_err(ix, refusal), false;
+    }
+    // within a list: by expansion descending, stable -- the longest walks first, so that the launch's tail is a short one
+    uint32_t *lists = tbl + 4 * nq;
+    size_t    list_at[ 3 ], at = 0;
+    for(int c = 0; c < 3; ++c) {
+        std::stable_sort(cls[ c ].begin(), cls[ c ].end(), [&](uint32_t x, uint32_t y) { return tbl[ 4 * x + 1 ] > tbl[ 4 * y + 1 ]; });
+        list_at[ c ] = (nq * 4 + at) * 4;
+        if(!cls[ c ].empty()) std::memcpy(lists + at, cls[ c ].data(), cls[ c ].size() * 4);
+        at += cls[ c ].size();
+    }
+    uint32_t launches = 0, any_spec = 0;
+    for(int c = 0; c < 3; ++c) {
+        if(cls[ c ].empty()) continue;
+        EachLaunch each;
+        each.h_table = h_block;
+        each.table_bytes = nq * 20;
+        each.d_table = d_block;
+        each.list_at = list_at[ c ];
+        each.max_expansion = top[ c ];
+        if(!run_search_device(ix, d_queries, cls[ c ].size(), k_stride, 0, 0, d_labels, d_dists, d_slots, d_counts, d_D, d_E, stream, waves, nullptr, done_flags, &each))
+            return false;
+        launches += 1;
+        any_spec |= each.took_spec ? 1u : 0u;
+    }
+    const uint32_t shape[ 6 ] = { launches, (uint32_t)cls[ 0 ].size(), (uint32_t)cls[ 1 ].size(), (uint32_t)cls[ 2 ].size(), std::max(top[ 0 ], std::max(top[ 1 ], top[ 2 ])), any_spec };
+    std::copy(std::begin(shape), std::end(shape), ix->last_params);
     return true;
 }
 
@@ -2273,18 +2391,14 @@ LANTERN_ABI_CATCH_VOID(e)
 // their rows are in the caller's arrays by then.  A launch's walks differ in length by 2x and more (140 hops where the mean is
 // 78): a caller that answers each client when ITS walk is over, instead of when the longest one is, halves what a client of a
 // small batch waits (the scan-side service: scan_server.cpp).  Returns when every query has been handed on.
-void lantern_gpu_search_batch_lane_notify(usearch_index_t h, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
-                                          usearch_label_t *labels, float *distances, uint32_t *counts, lantern_gpu_queries_done_fn done, void *done_ctx,
-                                          usearch_error_t *e)
-try {
-    CLEAR(e);
-    Index *ix = H(h, e);
-    if(!ix) return;
-    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
-    if(nq == 0 || k == 0) return;
-    if(!queries || !labels || !distances || !done) { FAIL(e, "lantern_gpu: null buffer or callback"); return; }
-    HostBatch b = batch_layout(ix, lane, nq, k, nq * 4);  // extra: one flag per query
+// (`params`: NULL, or the per-query-parameter form -- lantern_gpu_search_batch_params_lane_notify: k is then the answer rows' width and
+// the block carries the call's table behind the flags, which the kernels read in place)
+static void lane_notify(Index *ix, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
+                        const lantern_gpu_query_params *params, usearch_label_t *labels, float *distances, uint32_t *counts,
+                        lantern_gpu_queries_done_fn done, void *done_ctx, usearch_error_t *e)
+{
+    const size_t flag_bytes = (nq * 4 + 15) & ~(size_t)15;
+    HostBatch b = batch_layout(ix, lane, nq, k, params ? flag_bytes + params_table_bytes(nq) : nq * 4);  // extra: one flag per query
     if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
     char *hs_dev = nullptr;  // the same block as the device names it
     if(hipHostGetDevicePointer((void **)&hs_dev, b.hs, 0) != hipSuccess || !hs_dev) {
@@ -2293,7 +2407,7 @@ try {
         return;
     }
     uint32_t *const flags = (uint32_t *)b.h_extra();
-    std::memset(flags, 0, b.extra_bytes);
+    std::memset(flags, 0, nq * 4);
     bool ok = true;
     static thread_local std::string msg;
     msg.clear();
@@ -2310,8 +2424,13 @@ try {
         if(!b.d_q) { msg = ix->err; FAIL(e, msg.c_str()); return; }
         b.d_out = hs_dev + b.out_at;  // the answers land in the block itself: nothing to copy down
         ok = direct_queries || batch_upload(b);
-        ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                     nullptr, b.stream, ix->search_waves, nullptr, (uint32_t *)(hs_dev + b.extra_at));
+        if(params)
+            ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                            nullptr, b.stream, ix->search_waves, (uint32_t *)(hs_dev + b.extra_at), b.h_extra() + flag_bytes,
+                                            hs_dev + b.extra_at + flag_bytes);
+        else
+            ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                         nullptr, b.stream, ix->search_waves, nullptr, (uint32_t *)(hs_dev + b.extra_at));
         if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
     }
     const hipStream_t st = b.stream;
@@ -2379,6 +2498,128 @@ try {
     }
     if(hipStreamSynchronize(st) != hipSuccess) ok = false;
     if(!ok) { msg = kBatchFailed; FAIL(e, msg.c_str()); }
+}
+
+void lantern_gpu_search_batch_lane_notify(usearch_index_t h, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
+                                          usearch_label_t *labels, float *distances, uint32_t *counts, lantern_gpu_queries_done_fn done, void *done_ctx,
+                                          usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq == 0 || k == 0) return;
+    if(!queries || !labels || !distances || !done) { FAIL(e, "lantern_gpu: null buffer or callback"); return; }
+    lane_notify(ix, lane, queries, nq, kind, k, ef, nullptr, labels, distances, counts, done, done_ctx, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+// ---- per-query k, ef and skip: the entry points (search_params_locked; include/lantern_gpu.h has the contract) ---------------------
+// The checks that need no index come first, so that a bad argument is named whatever the handle is; then the handle.
+static Index *PH(usearch_index_t h, const lantern_gpu_query_params *params, size_t nq, size_t k_stride, usearch_error_t *e)
+{
+    static thread_local std::string msg;
+    msg = params_check(params, nq, k_stride);
+    if(!msg.empty()) { FAIL(e, msg.c_str()); return nullptr; }
+    return H(h, e);
+}
+
+void lantern_gpu_search_batch_params_device(usearch_index_t h, const void *d_queries, size_t query_stride_bytes, size_t nq,
+                                            const lantern_gpu_query_params *params, size_t k_stride, uint64_t *d_labels, float *d_distances,
+                                            uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, void *stream, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = PH(h, params, nq, k_stride, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    if(!search_params_locked(ix, (const uint4 *)d_queries, nq, params, k_stride, d_labels, d_distances, d_slots, d_counts, d_D, d_E, (hipStream_t)stream,
+                             ix->search_waves, nullptr, nullptr, nullptr))
+        FAIL(e, ix->err.c_str());
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_params(usearch_index_t h, const void *queries, size_t nq, usearch_scalar_kind_t kind, const lantern_gpu_query_params *params,
+                                     size_t k_stride, usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(nq && k_stride && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
+    Index *ix = PH(h, params, nq, k_stride, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq == 0) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    HostBatch b = batch_layout(ix, Index::kLanes, nq, k_stride, params_table_bytes(nq));
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
+    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
+    bool ok = batch_upload(b);
+    ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                    nullptr, b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
+    if(!batch_finish_locked(ix, b, ok, kBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_params_lane(usearch_index_t h, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind,
+                                          const lantern_gpu_query_params *params, size_t k_stride, usearch_label_t *labels, float *distances,
+                                          uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    if(nq && k_stride && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null buffer"); return; }
+    Index *ix = PH(h, params, nq, k_stride, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq == 0) return;
+    HostBatch b = batch_layout(ix, lane, nq, k_stride, params_table_bytes(nq));
+    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
+    bool ok = true;
+    static thread_local std::string msg;  // (a lane's error text belongs to the calling thread: lantern_gpu_search_batch_lane)
+    msg.clear();
+    {
+        std::lock_guard<std::mutex> g(ix->mu);
+        if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        ix->err.clear();
+        if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        ok = batch_upload(b);
+        ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
+                                        nullptr, b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
+        ok = ok && batch_download(b);
+        if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
+    }
+    if(hipStreamSynchronize(b.stream) != hipSuccess && ok) { ok = false; msg = kBatchFailed; }
+    if(!ok) { FAIL(e, msg.c_str()); return; }
+    batch_unpack(b, 0, nq, labels, distances, counts);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_params_lane_notify(usearch_index_t h, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind,
+                                                 const lantern_gpu_query_params *params, size_t k_stride, usearch_label_t *labels, float *distances,
+                                                 uint32_t *counts, lantern_gpu_queries_done_fn done, void *done_ctx, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    if(nq && (!done || (k_stride && (!queries || !labels || !distances)))) { FAIL(e, "lantern_gpu: null buffer or callback"); return; }
+    Index *ix = PH(h, params, nq, k_stride, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(nq == 0) return;
+    lane_notify(ix, lane, queries, nq, kind, k_stride, 0, params, labels, distances, counts, done, done_ctx, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_last_params_launch(usearch_index_t h, uint32_t out[ 6 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::copy(std::begin(ix->last_params), std::end(ix->last_params), out);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

@@ -224,6 +224,7 @@ struct Index
     double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
     uint64_t c_filter_walk = 0, c_filter_exact = 0;
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches
+    uint32_t last_params[ 6 ] = {};  // the last per-query-parameter call: launches, queries per list-placement class (3), largest expansion, any spec shape (lantern_gpu_last_params_launch)
     uint32_t last_filtered[ 6 ] = {};  // path, grid, expansion, cand_cap, vis_slots, LDS bytes of the last filtered launch (lantern_gpu_last_filtered_launch)
 
     hipStream_t stream = nullptr;
@@ -288,10 +289,32 @@ uint32_t    vis_undo_cap();
 int         search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu);
 // `done`: NULL, or a device-visible counter the kernel bumps per finished query; the caller then WAITS ON IT (not on the
 // stream) and no completion event is queued behind the launch
+// `each`: NULL, or the launch is ONE CLASS of a per-query-parameter call (search_params_locked): nq = the queries of its list, k =
+// the answer rows' width, ef and skip unused -- every query's own come from the table, the launch is shaped by each->max_expansion.
+struct EachLaunch
+{
+    const char *h_table = nullptr;   // host: the call's table {k, expansion, skip, 0} by batch position, then the classes' query lists
+    size_t      table_bytes = 0;     // ... copied into the scratch of the launch's slot; or
+    const char *d_table = nullptr;   // ... the same block as the device names it (page-locked, device-mapped): read in place, no copy
+    size_t      list_at = 0;         // byte offset of this launch's list in the block
+    uint32_t    max_expansion = 0;   // the largest expansion of the list: sizes the LDS carve, the list placement, the visited set
+    bool        dry = false;         // only the refusals: nothing is acquired, copied or launched
+    bool        took_spec = false;   // out: the launch took a latency-bound shape
+};
 bool        run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, size_t ef, size_t skip,
                               uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D,
                               uint64_t *d_E, hipStream_t stream, int waves, uint32_t *done = nullptr,
-                       uint32_t *done_flags = nullptr);
+                              uint32_t *done_flags = nullptr, EachLaunch *each = nullptr);
+// A batch whose queries bring their own (k, ef, skip) (lantern_gpu_search_batch_params*; the caller holds ix->mu and has flushed): the
+// planning of the whole call -- parameter checks, expansions, the split into at most three launches, the table.  Answer rows are
+// k_stride wide.  `h_block`: NULL, or a page-locked block of params_table_bytes(nq) that stays untouched until the stream work is done;
+// `d_block`: the same block's device address if the kernels are to read it in place.  false -> ix->err, nothing launched or written
+// unless the failure is HIP's.
+std::string params_check(const lantern_gpu_query_params *params, size_t nq, size_t k_stride);  // the checks that need no index: "" or the message
+inline size_t params_table_bytes(size_t nq) { return nq * 20 + 16; }
+bool        search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const lantern_gpu_query_params *params, size_t k_stride,
+                                 uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
+                                 hipStream_t stream, int waves, uint32_t *done_flags, char *h_block, const char *d_block);
 
 // one usearch_search_ef on behalf of `cur` (the caller holds ix->mu); returns the number of results
 size_t      search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, size_t k, size_t ef, bool streaming,

@@ -59,6 +59,10 @@ struct SearchArgs
     uint32_t        trace_cap;
     unsigned long long *screen_totals;  // [2] cumulative row evaluations and how many of them read the f32 row (the int8 screen:
                                         // lantern_gpu_search_screen_stats) of the launches whose view has a screen, or NULL
+    // the per-query-parameter form (k_search<.., EACH = true>, lantern_gpu_search_batch_params*); all three NULL / 0 otherwise
+    const uint32_t *qlist;       // [nq] the launch's queries as positions of the caller's batch; answers land in the row of that position
+    const uint4    *qparams;     // [caller's batch] {k, expansion, skip, 0} by position; `k`, `skip` above are unused, `ef` is the list's largest expansion
+    uint32_t        k_stride;    // width of an answer row
 };                               // launch's queries by phase: pop | list + visited | distances | merge | descent | whole query
 
 // one reverse-link request produced by the insert pass: add `new_slot` to `close`'s list at `level`
@@ -169,6 +173,9 @@ inline void ensure_dynamic_lds(const void *fn, size_t lds, LdsAttrCache &cache)
 // All launchers return hipSuccess or the launch error.  `metric` is a usearch_metric_kind_t value.
 hipError_t launch_search(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);
 hipError_t launch_search_spec(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);  // a.spec != 0 (search_spec_kernel.hip)
+// a.qparams != NULL: the per-query-parameter instantiations (search_each_kernel.hip: the classic shapes; search_each_spec_kernel.hip: a.spec == 2)
+hipError_t launch_search_each(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);
+hipError_t launch_search_each_spec(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);
 size_t     search_spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries, uint32_t twin = 0);
 #if LGPU_EXPERIMENTAL
 // the one-wave walk (experimental/search_solo_kernel.hip, experimental/walk_solo.hpp): a.spec_cache = log2 of the list-cache entries,

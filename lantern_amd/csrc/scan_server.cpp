@@ -196,6 +196,9 @@ struct lantern_scan_server
     lantern_scan_filter_make_fn  f_make = nullptr;
     lantern_scan_filter_free_fn  f_free = nullptr;
     lantern_batch_search_each_fn f_each = nullptr;
+    // mixed batches: the back end's search with (k, ef, skip) per query (NULL: a back end without one -- a batch then goes out as one
+    // call per distinct (k, ef)).  The device index has it under LANTERN_SCAN_MIXED=1.
+    lantern_batch_search_params_fn f_params = nullptr;
     struct FilterJob { Conn *c = nullptr; void *release = nullptr; uint64_t release_bytes = 0; };  // a connection's message, or a filter to release
     std::thread             filter_thread;
     std::mutex              fmu;
@@ -261,6 +264,16 @@ int default_search_each(void *ctx, const void *const *filters, const void *queri
     usearch_error_t      e = nullptr;
     lantern_gpu_search_batch_filtered_each_lane(s->index, tl_lane, (const lantern_gpu_filter_t *const *)filters, queries, nq, s->kind, k, ef, labels,
                                                 dists, counts, &e);
+    if(e) { *err = e; return 1; }
+    return 0;
+}
+
+int default_search_params(void *ctx, const void *queries, size_t nq, size_t, const lantern_gpu_query_params *params, size_t k_stride, uint64_t *labels,
+                          float *dists, uint32_t *counts, const char **err)
+{
+    lantern_scan_server *s = (lantern_scan_server *)ctx;
+    usearch_error_t      e = nullptr;
+    lantern_gpu_search_batch_params_lane(s->index, tl_lane, queries, nq, s->kind, params, k_stride, labels, dists, counts, &e);
     if(e) { *err = e; return 1; }
     return 0;
 }
@@ -614,16 +627,44 @@ void dispatch_loop(lantern_scan_server *s, int lane)
         // one launch per distinct (k, ef): scans of one workload share them (init_k, the ef GUC)
         // ... and within (k, ef) the requests of connections with a filter go out TOGETHER, whatever their filters, in one per-query
         // call (lantern_gpu_search_batch_filtered_each_lane); the unfiltered ones take the path they always took
+        // ... unless the back end takes (k, ef) per query (f_params: the device index, lantern_gpu_search_batch_params_lane*): the
+        // unfiltered requests of a batch then go out in ONE call whatever their (k, ef) -- group kind 2, keyed (0, 0).  A batch whose
+        // unfiltered requests share one (k, ef) anyway makes the uniform call it always made.
         std::map<std::pair<std::pair<uint32_t, uint32_t>, int>, std::vector<size_t>> groups;
-        for(size_t i = 0; i < batch.size(); ++i) groups[ { { batch[ i ]->k, batch[ i ]->ef }, batch[ i ]->filter ? 1 : 0 } ].push_back(i);
+        bool mixed_batch = false;
+        if(s->f_params) {
+            const Conn *first = nullptr;
+            for(const Conn *c : batch) {
+                if(c->filter) continue;
+                if(!first) first = c;
+                else if(c->k != first->k || c->ef != first->ef) { mixed_batch = true; break; }
+            }
+        }
+        for(size_t i = 0; i < batch.size(); ++i) {
+            const Conn *c = batch[ i ];
+            if(mixed_batch && !c->filter) groups[ { { 0u, 0u }, 2 } ].push_back(i);
+            else groups[ { { c->k, c->ef }, c->filter ? 1 : 0 } ].push_back(i);
+        }
         touched.assign(s->io.size(), 0);
         // A handful of answers the dispatcher writes itself (a disarmed connection has one holder at a time, and this is it):
         // one thread hand-off less on the path of a lone backend.  Larger batches go back to the I/O threads, whose sends
         // run side by side.
         const bool direct = batch.size() <= 8;
         for(auto &kv : groups) {
-            const size_t k = kv.first.first.first, ef = kv.first.first.second, nq = kv.second.size();
-            const bool   filtered = kv.first.second != 0;
+            const size_t ef = kv.first.first.second, nq = kv.second.size();
+            const bool   filtered = kv.first.second == 1, mixed = kv.first.second == 2;
+            // the answer rows' width: the group's k, or -- a mixed group -- its largest; k_of(j): what request j of the group asked for
+            std::vector<lantern_gpu_query_params> qp;
+            size_t                                k = kv.first.first.first;
+            if(mixed) {
+                qp.resize(nq);
+                for(size_t j = 0; j < nq; ++j) {
+                    const Conn *c = batch[ kv.second[ j ] ];
+                    qp[ j ] = lantern_gpu_query_params{ c->k, c->ef, 0u, 0u };
+                    k = std::max<size_t>(k, c->k);
+                }
+            }
+            auto k_of = [&](size_t j) -> size_t { return mixed ? qp[ j ].k : k; };
             qbuf.resize(nq * s->vec_bytes);
             for(size_t j = 0; j < nq; ++j) std::memcpy(&qbuf[ j * s->vec_bytes ], batch[ kv.second[ j ] ]->vec.data(), s->vec_bytes);
             labels.assign(nq * k, 0);
@@ -647,7 +688,7 @@ void dispatch_loop(lantern_scan_server *s, int lane)
                     s->t_count += 1;
                     if(direct) {
                         const bool sent = rc != 0 ? reply_error(d.c->fd, msg)
-                                                  : reply_rows(d.c, &labels[ j * k ], &dists[ j * k ], std::min<size_t>(counts[ j ], k));
+                                                  : reply_rows(d.c, &labels[ j * k ], &dists[ j * k ], std::min<size_t>(counts[ j ], k_of(j)));
                         s->t_reply_ns += now_ns() - t_known;
                         if(sent && arm(s->io[ (size_t)d.c->io ].get(), d.c, EPOLL_CTL_MOD)) continue;
                         d.gone = true;  // its I/O thread takes it down
@@ -656,7 +697,7 @@ void dispatch_loop(lantern_scan_server *s, int lane)
                     } else if(rc != 0) {
                         d.error = msg;
                     } else {
-                        const size_t cn = std::min<size_t>(counts[ j ], k);
+                        const size_t cn = std::min<size_t>(counts[ j ], k_of(j));
                         d.labels.assign(labels.begin() + (ptrdiff_t)(j * k), labels.begin() + (ptrdiff_t)(j * k + cn));
                         d.dists.assign(dists.begin() + (ptrdiff_t)(j * k), dists.begin() + (ptrdiff_t)(j * k + cn));
                     }
@@ -701,6 +742,18 @@ void dispatch_loop(lantern_scan_server *s, int lane)
                     }
                     rc = 0;
                 }
+            } else if(mixed && s->notify) {
+                struct Ctx { decltype(deliver) *fn; } cx{ &deliver };
+                usearch_error_t ue = nullptr;
+                lantern_gpu_search_batch_params_lane_notify(s->index, tl_lane, qbuf.data(), nq, s->kind, qp.data(), k, labels.data(), dists.data(), counts.data(),
+                                                            [](void *c, const uint32_t *which, size_t count) {
+                                                                Ctx *x = (Ctx *)c;
+                                                                (*x->fn)(which, count);
+                                                            },
+                                                            &cx, &ue);
+                if(ue) { rc = 1; err = ue; }
+            } else if(mixed) {
+                rc = s->f_params(s->fn_ctx, qbuf.data(), nq, s->vec_bytes, qp.data(), k, labels.data(), dists.data(), counts.data(), &err);
             } else if(s->notify) {
                 // the device index: every answer goes back when ITS walk ends, not when the batch's longest one does
                 // (lantern_gpu_search_batch_lane_notify; the callback runs on this thread)
@@ -851,6 +904,11 @@ try {
     s->f_make = default_filter_make;
     s->f_free = default_filter_free;
     s->f_each = default_search_each;
+    // mixed batches in one call: LANTERN_SCAN_MIXED=1 (=0: one call per distinct (k, ef), as before).  The switch is the A/B lever of
+    // scripts/scan_mixed_ab.py and defaults to OFF until that A/B has been taken (the rule that decides it).
+    constexpr bool kMixedByDefault = false;
+    if(const char *mx = std::getenv("LANTERN_SCAN_MIXED")) { if(std::atoi(mx) != 0) s->f_params = default_search_params; }
+    else if(kMixedByDefault) s->f_params = default_search_params;
     // dispatchers = lanes of lantern_gpu_search_batch_lane (up to four batches in flight on the device, each in its own slab of
     // visited bitmaps).  Default four; LANTERN_SCAN_LANES = 1 .. 8.  Measured with lantern-scan-load on 100k x 128 (round 4,
     // profiles/r04_scan_load_lanes.jsonl; lanes 1 / 2 / 3 / 4): 16 backends p50 201 / 214 / 193 / 173 us, 64: 301 / 243 / 235 / 227 us,
@@ -907,6 +965,21 @@ try {
     s->f_make = make;
     s->f_free = free_fn;
     s->f_each = each;
+    s->vec_bytes = vec_bytes;
+    if(const char *ln = std::getenv("LANTERN_SCAN_LANES")) s->lanes = std::min(kMaxLanes, std::max(1, std::atoi(ln)));
+    return start_common(s, host, port, max_batch, max_wait_us, e);
+}
+LANTERN_ABI_CATCH(e)
+
+lantern_scan_server_t *lantern_scan_server_start_params_fn(lantern_batch_search_fn fn, lantern_batch_search_params_fn params_fn, void *ctx, size_t vec_bytes,
+                                                           const char *host, int port, size_t max_batch, unsigned max_wait_us, usearch_error_t *e)
+try {
+    if(e) *e = nullptr;
+    if(!fn || !params_fn || vec_bytes == 0 || vec_bytes > MAX_VEC_BYTES) { if(e) *e = "lantern_gpu: bad scan server arguments"; return nullptr; }
+    lantern_scan_server *s = new lantern_scan_server();
+    s->fn = fn;
+    s->f_params = params_fn;
+    s->fn_ctx = ctx;
     s->vec_bytes = vec_bytes;
     if(const char *ln = std::getenv("LANTERN_SCAN_LANES")) s->lanes = std::min(kMaxLanes, std::max(1, std::atoi(ln)));
     return start_common(s, host, port, max_batch, max_wait_us, e);

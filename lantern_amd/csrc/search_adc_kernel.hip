@@ -71,7 +71,9 @@ __device__ __forceinline__ void adc_build_table(float *lut, const float *centers
 // a batch walks alone on its CU whatever the batch size: the walk that is fastest alone is the one to run.
 // (SPEC 2 = the lone-query shape.  The two-nodes-per-round form of walk_twin.hpp was measured here too -- 1.98 -> 1.65 M queries/s at
 // 96 subvectors -- and is not instantiated.)
-template <int METRIC, int KPL, int SPEC = 0>
+// EACH: the per-query-parameter form, as k_search's (search_kernel.hpp): the launch's queries come from SearchArgs::qlist, every
+// query's k, expansion and skip from its row of SearchArgs::qparams, answer rows are k_stride wide.
+template <int METRIC, int KPL, int SPEC = 0, bool EACH = false>
 __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(SearchArgs)
 {
     // (arguments are re-read from the kernarg segment where a query needs them, as in k_search -- search_kernel.hpp: kept live
@@ -92,10 +94,20 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
     float *const       lut = (float *)s.q;
     const uint4 *const rawq4 = s.q + lut_chunks;
     const float *const rawq = (const float *)rawq4;
-    for(uint32_t q = blockIdx.x; q < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
+    for(uint32_t pos = blockIdx.x; pos < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
+        uint32_t q = pos, each_k = 0, each_ef = 0, each_skip = 0;
+        if constexpr(EACH) {
+            const KernargBytes ka = kernarg_opaque();
+            const uint32_t     upos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
+            q = ((ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qlist))[ upos ];
+            const ConstWords row = (ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qparams) + (size_t)q * 4;
+            each_k = row[ 0 ];
+            each_ef = row[ 1 ];
+            each_skip = row[ 2 ];
+        }
         uint32_t D = 0, E = 0;
         int      cnt = 0;
-        {
+        if(!EACH || each_k != 0) {  // (a query that wants no rows needs no table)
             const KernargBytes ka = kernarg_opaque();
             const uint32_t     S = LGPU_SEARCH_ARG(ka, adc_S), C = LGPU_SEARCH_ARG(ka, adc_C), subdim = LGPU_SEARCH_ARG(ka, adc_subdim),
                            sub_floats = ((subdim + 3) / 4) * 4, qchunks = LGPU_SEARCH_ARG(ka, adc_qchunks), S16 = LGPU_VIEW_ARG(ka, SearchArgs, chunks) * 16;
@@ -128,8 +140,8 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
             uint32_t      *bitmap = LGPU_SEARCH_ARG(ka, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
             s.undo = bitmap + bm_words;
             s.undo_cap = LGPU_SEARCH_ARG(ka, undo_cap);
-            const int      ef = (int)LGPU_SEARCH_ARG(ka, ef);
-            if(v.n != 0) {
+            const int      ef = EACH ? (int)each_ef : (int)LGPU_SEARCH_ARG(ka, ef);
+            if(v.n != 0 && (!EACH || each_k != 0)) {
                 if constexpr(SPEC != 0) {
                     static_assert(SPEC == 0 || KPL > 0, "the latency-bound walk keeps its list in registers");
                     const uint32_t start = greedy_descent_spec<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
@@ -142,15 +154,16 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
             }
         }
         const KernargBytes kb = kernarg_opaque();
-        const uint32_t     k = LGPU_SEARCH_ARG(kb, k), skip = LGPU_SEARCH_ARG(kb, skip);
+        const uint32_t     k = EACH ? each_k : LGPU_SEARCH_ARG(kb, k), skip = EACH ? each_skip : LGPU_SEARCH_ARG(kb, skip);
+        const uint32_t     kw = EACH ? LGPU_SEARCH_ARG(kb, k_stride) : k;  // the width of an answer row
         const uint64_t    *labels = LGPU_SEARCH_ARG(kb, labels);
         uint64_t          *out_labels = LGPU_SEARCH_ARG(kb, out_labels);
         float             *out_dists = LGPU_SEARCH_ARG(kb, out_dists);
         uint32_t          *out_slots = LGPU_SEARCH_ARG(kb, out_slots);
         int                got = cnt - (int)skip;
         got = got < 0 ? 0 : (got > (int)k ? (int)k : got);
-        for(uint32_t i = tid; i < k; i += T) {
-            const size_t o = (size_t)q * k + i;
+        for(uint32_t i = tid; i < kw; i += T) {
+            const size_t o = (size_t)q * kw + i;
             if((int)i < got) {
                 const uint64_t key = s.keys[ skip + i ];
                 const uint32_t slot = key_slot(key);
@@ -173,7 +186,7 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
             if(out_D) out_D[ q ] = D;
             if(out_E) out_E[ q ] = E;
             if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
-            s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(q + gridDim.x);
+            s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(pos + gridDim.x);
         }
         __syncthreads();
         uint32_t *const done_flags = LGPU_SEARCH_ARG(kb, done_flags);
@@ -182,7 +195,7 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
             if(done) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             if(done_flags) __hip_atomic_store(&done_flags[ q ], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        q = (uint32_t)s.scal[ S_POS ];
+        pos = (uint32_t)s.scal[ S_POS ];
         __syncthreads();
     }
 }
@@ -198,11 +211,16 @@ hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int gri
     const int kpl = a.lds_list ? 0 : a.ef <= 64 ? 1 : a.ef <= 128 ? 2 : 0;
     if(a.spec && (kpl == 0 || waves < 4 || waves > 11 || a.view.M0 > 64 || a.view.M0 < 2)) return hipErrorInvalidValue;
     const size_t lds = search_adc_lds_bytes(a.view.chunks, a.adc_qchunks, a.ef, a.view.M0, a.vis_slots) + (a.spec ? spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache) : 0);
-#define LGPU_ADC1(MM, KK, SS)                                                                                                   \
+#define LGPU_ADC2(MM, KK, SS, EE)                                                                                               \
     {                                                                                                                           \
         static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_search_adc<MM, KK, SS>, lds, attr_);    \
-        hipLaunchKernelGGL((k_search_adc<MM, KK, SS>), dim3(grid), dim3(64 * waves), lds, stream, a);                           \
+        ensure_dynamic_lds((const void *)k_search_adc<MM, KK, SS, EE>, lds, attr_);    \
+        hipLaunchKernelGGL((k_search_adc<MM, KK, SS, EE>), dim3(grid), dim3(64 * waves), lds, stream, a);                       \
+    }
+#define LGPU_ADC1(MM, KK, SS)                                    \
+    {                                                            \
+        if(a.qparams) LGPU_ADC2(MM, KK, SS, true)                \
+        else LGPU_ADC2(MM, KK, SS, false)                        \
     }
 #define LGPU_ADC(MM)                                  \
     {                                                 \
@@ -218,6 +236,7 @@ hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int gri
     else return hipErrorInvalidValue;
 #undef LGPU_ADC
 #undef LGPU_ADC1
+#undef LGPU_ADC2
     return hipGetLastError();
 }
 

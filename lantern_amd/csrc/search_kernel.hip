@@ -17,6 +17,7 @@ size_t search_lds_bytes(uint32_t chunks, uint32_t ef_cap, uint32_t M0, uint32_t 
 
 hipError_t launch_search(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream)
 {
+    if(a.qparams) return launch_search_each(metric, a, waves, grid, stream);  // the per-query-parameter form (search_each_kernel.hip)
     if(a.spec) return launch_search_spec(metric, a, waves, grid, stream);
     const size_t lds = search_lds_bytes(a.view.chunks, a.ef, a.view.M0, a.vis_slots);
     const int    kpl = a.lds_list ? 0 : a.ef <= 64 ? 1 : a.ef <= 128 ? 2 : 0;

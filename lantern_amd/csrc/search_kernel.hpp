@@ -69,13 +69,20 @@ __device__ __forceinline__ KernargBytes kernarg_opaque()
 // SPEC: the latency-bound walk of walk_spec.hpp -- 1: every wave evaluates rows and waves 0..2 carry the roles on top (the
 // small-batch shape, four waves); 2: three dedicated role waves + row waves (the lone-query shape, 3 + 8 waves); 3: the same
 // shape with two nodes per round, the second one speculative (walk_twin.hpp).
-template <int METRIC, int G, bool PROF = false, int ROWS = 2, int KPL = 1, int SPEC = 0>
+// EACH: the per-query-parameter form (search_each_kernel.hip, search_each_spec_kernel.hip).  The launch serves the queries of a list
+// (SearchArgs::qlist: the ticket hands out list positions, the answers land in the row of the query a position names) and every query
+// brings its own k, expansion and skip in a 16-byte row {k, expansion, skip, 0} of SearchArgs::qparams, read through the scalar cache
+// once the workgroup has its query.  The LDS carve is the launch's (SearchArgs::ef = the largest expansion of the list); the walk runs
+// with the query's own expansion, the answer rows are k_stride wide.  k = 0: no walk, the empty answer.
+typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
+template <int METRIC, int G, bool PROF = false, int ROWS = 2, int KPL = 1, int SPEC = 0, bool EACH = false>
 #ifndef LGPU_SEARCH_MIN_BLOCKS_COS
 #define LGPU_SEARCH_MIN_BLOCKS_COS 6
 #endif
 __global__ void __launch_bounds__(SPEC >= 2 ? 704 : 512, SPEC >= 2 ? 3 : (SPEC == 1 || ROWS != 2) ? 4 : (METRIC % 100 == M_COS) ? LGPU_SEARCH_MIN_BLOCKS_COS : 6)  // SPEC 0, ROWS 2: <= 80 VGPRs, six 4-wave workgroups per CU
 k_search(SearchArgs)
 {
+    static_assert(!EACH || (!PROF && (SPEC == 0 || SPEC == 2)), "the per-query form exists for the classic shapes and the 3 + 8 wave shape");
     const int tid = threadIdx.x, T = blockDim.x;
     WalkLds   s;
     SpecLds   sc;
@@ -88,7 +95,17 @@ k_search(SearchArgs)
     }
     // the int8 screen of the f32 l2sq walk over rows of >= 128 chunks (walk.hpp hop_distances_screened); used iff the view has one
     constexpr bool SCREEN = LGPU_SCREEN && METRIC == M_L2SQ && G == 64 && !PROF && SPEC == 0 && KPL > 0;
-    for(uint32_t q = blockIdx.x; q < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
+    for(uint32_t pos = blockIdx.x; pos < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
+        uint32_t q = pos, each_k = 0, each_ef = 0, each_skip = 0;
+        if constexpr(EACH) {  // (pos comes out of LDS: made wave-uniform, the list entry and the parameter row are scalar loads)
+            const KernargBytes ka = kernarg_opaque();
+            const uint32_t     upos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
+            q = ((ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qlist))[ upos ];
+            const ConstWords row = (ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qparams) + (size_t)q * 4;
+            each_k = row[ 0 ];
+            each_ef = row[ 1 ];
+            each_skip = row[ 2 ];
+        }
         uint32_t D = 0, E = 0;
         int      cnt = 0;
         unsigned long long pc[ 8 ] = { 0, 0, 0, 0, 0, 0, 0, 0 }, t_q = 0;
@@ -110,7 +127,7 @@ k_search(SearchArgs)
             s.undo = bitmap + bm_words;
             s.undo_cap = LGPU_SEARCH_ARG(ka, undo_cap);
             const uint4   *queries = LGPU_SEARCH_ARG(ka, queries);
-            const int      ef = (int)LGPU_SEARCH_ARG(ka, ef);
+            const int      ef = EACH ? (int)each_ef : (int)LGPU_SEARCH_ARG(ka, ef);
             for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = queries[ (size_t)q * chunks + i ];
             __syncthreads();
             if(kCachedNorms<METRIC>) {  // ||query||^2 once per query, by the chain Acc<M_COS> would run for every row
@@ -128,7 +145,7 @@ k_search(SearchArgs)
                 s.trace = tr ? tr + (size_t)q * s.trace_cap : nullptr;
                 s.trace_count = tr ? LGPU_SEARCH_ARG(ka, trace_count) + q : nullptr;
             }
-            if(v.n != 0) {
+            if(v.n != 0 && (!EACH || each_k != 0)) {
                 uint32_t start;
                 if constexpr(SPEC != 0) start = greedy_descent_spec<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
                 else start = greedy_descent<METRIC, G, PROF>(v, s, v.entry, v.max_level, 0, D);
@@ -156,15 +173,16 @@ k_search(SearchArgs)
                     if(tid == 0 ? (i != 4 || pc[ 4 ] != 0) : (i == 4 && pc[ 4 ] != 0)) atomicAdd(&phase_cycles[ i ], pc[ i ]);
             }
         }
-        const uint32_t  k = LGPU_SEARCH_ARG(kb, k), skip = LGPU_SEARCH_ARG(kb, skip);
+        const uint32_t  k = EACH ? each_k : LGPU_SEARCH_ARG(kb, k), skip = EACH ? each_skip : LGPU_SEARCH_ARG(kb, skip);
+        const uint32_t  kw = EACH ? LGPU_SEARCH_ARG(kb, k_stride) : k;  // the width of an answer row
         const uint64_t *labels = LGPU_SEARCH_ARG(kb, labels);
         uint64_t       *out_labels = LGPU_SEARCH_ARG(kb, out_labels);
         float          *out_dists = LGPU_SEARCH_ARG(kb, out_dists);
         uint32_t       *out_slots = LGPU_SEARCH_ARG(kb, out_slots);
         int             got = cnt - (int)skip;
         got = got < 0 ? 0 : (got > (int)k ? (int)k : got);
-        for(uint32_t i = tid; i < k; i += T) {
-            const size_t o = (size_t)q * k + i;
+        for(uint32_t i = tid; i < kw; i += T) {
+            const size_t o = (size_t)q * kw + i;
             if((int)i < got) {
                 const uint64_t key = s.keys[ skip + i ];
                 const uint32_t slot = key_slot(key);
@@ -191,7 +209,7 @@ k_search(SearchArgs)
                 if(st) { atomicAdd(&st[ 0 ], (unsigned long long)D); atomicAdd(&st[ 1 ], (unsigned long long)(D - (uint32_t)s.scal[ S_NREJ ])); }
             }
             // next query: a ticket (walks differ in length by 2x; static striding leaves workgroups idle at the end)
-            s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(q + gridDim.x);
+            s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(pos + gridDim.x);
         }
         __syncthreads();
         if(tid == 0) {
@@ -202,7 +220,7 @@ k_search(SearchArgs)
             if(done) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             if(done_flags) __hip_atomic_store(&done_flags[ q ], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        q = (uint32_t)s.scal[ S_POS ];
+        pos = (uint32_t)s.scal[ S_POS ];
         __syncthreads();
     }
 }

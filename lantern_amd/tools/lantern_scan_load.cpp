@@ -11,6 +11,9 @@
 // query and connection thread, on the cores the server shares with it) leaves the picture, and what remains is the service.
 // --port P [--host H] drives a service that is ALREADY running (another process's index: bench.py's headline index) instead of
 // building one here; the service's own statistics are then the other process's to report.
+// --pages P (P > 1; connection threads only): every scan is PAGINATED -- one search followed by P - 1 continuations of the same query
+// (lantern_scan_client_search_next: the next k rows, served as a search for handed-out + k), each counted and timed as a request.
+// Connections drift out of step, so a batch carries requests for k, 2k, .. Pk rows: the mixed-(k, ef) workload of DESIGN.md 4.10.
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <netinet/tcp.h>
@@ -35,7 +38,7 @@ using Clock = std::chrono::steady_clock;
 
 int main(int argc, char **argv)
 {
-    size_t   rows = 100000, dim = 128, m = 16, efc = 128, ef = 64, k = 10, connections = 256, max_batch = 1024, pool = 8192, client_threads = 0;
+    size_t   rows = 100000, dim = 128, m = 16, efc = 128, ef = 64, k = 10, connections = 256, max_batch = 1024, pool = 8192, client_threads = 0, pages = 1;
     unsigned wait_us = 200;
     double   seconds = 5.0, warm = 1.0;
     int      ext_port = 0;
@@ -50,6 +53,7 @@ int main(int argc, char **argv)
         else if(const char *v = val("--k")) k = (size_t)std::atoll(v);
         else if(const char *v = val("--connections")) connections = (size_t)std::atoll(v);
         else if(const char *v = val("--client-threads")) client_threads = (size_t)std::atoll(v);
+        else if(const char *v = val("--pages")) pages = std::max<size_t>(1, (size_t)std::atoll(v));
         else if(const char *v = val("--max-batch")) max_batch = (size_t)std::atoll(v);
         else if(const char *v = val("--max-wait-us")) wait_us = (unsigned)std::atoi(v);
         else if(const char *v = val("--seconds")) seconds = std::atof(v);
@@ -58,10 +62,11 @@ int main(int argc, char **argv)
         else if(const char *v = val("--host")) ext_host = v;
         else {
             std::fprintf(stderr, "usage: %s [--rows N --dim D --m M --ef-construction E --ef E --k K] [--connections C] [--max-batch B] "
-                                 "[--max-wait-us U] [--seconds S] [--warmup-seconds W] [--client-threads T] [--port P [--host H]]\n", argv[ 0 ]);
+                                 "[--max-wait-us U] [--seconds S] [--warmup-seconds W] [--client-threads T] [--pages P] [--port P [--host H]]\n", argv[ 0 ]);
             return 2;
         }
     }
+    if(pages > 1 && client_threads > 0) { std::fprintf(stderr, "--pages needs connection threads (--client-threads 0)\n"); return 2; }
     usearch_error_t err = nullptr;
     usearch_init_options_t o;
     std::memset(&o, 0, sizeof(o));
@@ -190,13 +195,21 @@ int main(int argc, char **argv)
             std::vector<float>           dist(k);
             std::mt19937                 pick((unsigned)c * 7919u + 13u);
             lat[ c ].reserve(1 << 16);
+            size_t       page = (size_t)pick() % pages;  // (connections start on different pages of their first scan's length)
+            const float *q = &queries[ (size_t)(pick() % pool) * dim ];
+            bool         fresh = true;
             while(phase.load(std::memory_order_relaxed) < 2) {
-                const float *q = &queries[ (size_t)(pick() % pool) * dim ];
                 const auto   t0 = Clock::now();
-                const size_t got = lantern_scan_client_search(cl, q, dim * 4, k, 0, lab.data(), dist.data(), &e);
+                const size_t got = fresh ? lantern_scan_client_search(cl, q, dim * 4, k, 0, lab.data(), dist.data(), &e)
+                                         : lantern_scan_client_search_next(cl, q, dim * 4, k, 0, lab.data(), dist.data(), &e);
                 const auto   t1 = Clock::now();
                 if(e || got != k) { failures++; if(e) break; }
                 if(phase.load(std::memory_order_relaxed) == 1) lat[ c ].push_back((uint32_t)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count());
+                fresh = ++page >= pages;
+                if(fresh) {
+                    page = 0;
+                    q = &queries[ (size_t)(pick() % pool) * dim ];
+                }
             }
             lantern_scan_client_close(cl);
         });
@@ -226,11 +239,11 @@ int main(int argc, char **argv)
     double mean = 0;
     for(uint32_t x : all) mean += x;
     mean = all.empty() ? 0 : mean / (double)all.size();
-    std::printf("{\"tool\": \"lantern-scan-load\", \"index\": \"%zux%zu f32 l2sq M=%zu ef_construction=%zu ef=%zu\", \"k\": %zu, \"connections\": %zu, "
+    std::printf("{\"tool\": \"lantern-scan-load\", \"index\": \"%zux%zu f32 l2sq M=%zu ef_construction=%zu ef=%zu\", \"k\": %zu, \"pages\": %zu, \"connections\": %zu, "
                 "\"connected\": %zu, \"client_threads\": %zu, \"max_batch\": %zu, \"max_wait_us\": %u, \"seconds\": %.3f, \"queries\": %zu, \"queries_per_s\": %.1f, "
                 "\"latency_us\": {\"mean\": %.1f, \"p50\": %u, \"p90\": %u, \"p99\": %u, \"max\": %u}, \"failures\": %zu, "
                 "\"service\": {\"requests\": %llu, \"batches\": %llu, \"launches\": %llu, \"mean_batch\": %.1f, \"largest_batch\": %llu, \"batch_size_histogram\": {",
-                rows, dim, m, efc, ef, k, connections, connected.load(), client_threads, max_batch, wait_us, elapsed, all.size(), (double)all.size() / elapsed, mean, pct(0.5), pct(0.9),
+                rows, dim, m, efc, ef, k, pages, connections, connected.load(), client_threads, max_batch, wait_us, elapsed, all.size(), (double)all.size() / elapsed, mean, pct(0.5), pct(0.9),
                 pct(0.99), all.empty() ? 0u : all.back(), failures.load(), (unsigned long long)(r1 - r0), (unsigned long long)(b1 - b0),
                 (unsigned long long)(l1 - l0), b1 > b0 ? (double)(r1 - r0) / (double)(b1 - b0) : 0.0, (unsigned long long)big);
     bool first = true;
