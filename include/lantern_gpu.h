@@ -440,8 +440,25 @@ LANTERN_GPU_EXPORT void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t 
 LANTERN_GPU_EXPORT void lantern_gpu_search_row_trace(usearch_index_t, int on, size_t nq, size_t per_query_cap, uint32_t *trace,
                                                      uint32_t *counts, usearch_error_t *);
 
-/* workgroups of the last search launch = walks resident on the device at a time (the cache model's `walkers`) */
+/* workgroups of the last unfiltered search launch, whatever path it took = walks resident on the device at a time (the cache
+ * model's `walkers`) */
 LANTERN_GPU_EXPORT int lantern_gpu_last_search_grid(usearch_index_t, usearch_error_t *);
+/* The shape the library gives an unfiltered search launch, without a device (a pure function: tests of the shape rules, tuning).
+ * in[31], by the names of the index's fields, the call and the environment switches:
+ *   [0] chunks (16-byte chunks per stored row)  [1] M  [2] M0  [3] mcode (metric, +100 for f16 rows, +200 for i8)  [4] n (rows)
+ *   [5] the index's default ef  [6] num_cus  [7] pq_compact  [8] pqd_inv (!= 0: rows can be decoded on the fly)  [9] pq_S16 (bytes
+ *   per padded code row)  [10] search_vis_slots (-1: automatic)  [11] search_max_wg (0: none)  [12] phase_profile  [13] spec_profile
+ *   [14] nq  [15] k  [16] ef  [17] skip  [18] waves (> 0: explicit; < 0: automatic, the classic fallback takes -waves)
+ *   [19] 1: one class of a per-query-parameter call, shaped by [20] its largest expansion
+ *   [21] LANTERN_GPU_SPEC is set, [22] its value  [23] LANTERN_GPU_ADC_SPEC is set, [24] != 0  [25] LANTERN_GPU_PQ_ADC != 0
+ *   [26] LANTERN_GPU_SPEC_WAVES (0: unset)  [27] LANTERN_GPU_LDS_LIST != 0  [28] LANTERN_GPU_WIDE_ROWS (-1: unset)
+ *   [29] LANTERN_GPU_SOLO != 0  [30] LANTERN_GPU_WAVES_PER_CU (0: unset)
+ * out[12]: [0] path (0 ADC over the code rows, 1 the f32 walk over rows decoded on the fly, 2 classic, 3 spec 1, 4 spec 2, 5 two
+ *   nodes per round, 6 the one-wave walk; 5 and 6 in a LANTERN_BUILD_EXPERIMENTAL library only)  [1] spec (the walk's shape; paths 0
+ *   and 1 take 0 / 2 and any)  [2] expansion  [3] waves per workgroup  [4] grid  [5] vis_slots  [6] LDS bytes per workgroup
+ *   [7] spec_prefetch  [8] spec_cache  [9] wide_rows  [10] a latency-bound shape  [11] lds_list
+ * Returns NULL, or the text the launch is refused with (then only out[2] is meaningful). */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search(const int64_t in[31], uint32_t out[12]);
 
 /* Gathered distances: out[i] = metric(query, row(slots[i])) -- the kernel the graph walk is
  * made of, exposed for tests and profiling.  Host buffers. */

@@ -98,7 +98,7 @@ EXPORTS = [
     "lantern_gpu_comm_init_local", "lantern_gpu_comm_free", "lantern_gpu_comm_rank", "lantern_gpu_comm_world",
     "lantern_gpu_comm_set_timeout", "lantern_gpu_comm_stats", "lantern_gpu_comm_allgatherv_host",
     "lantern_gpu_comm_allgatherv_device", "lantern_gpu_shard_range", "lantern_gpu_add_sharded", "lantern_gpu_add_row_sharded", "lantern_gpu_search_partitioned", "lantern_gpu_search_batch_lane", "lantern_gpu_search_batch_lane_notify", "lantern_gpu_row_bytes",
-    "lantern_gpu_level_for", "lantern_gpu_plan_batch", "lantern_gpu_row_shard_plan",
+    "lantern_gpu_level_for", "lantern_gpu_plan_batch", "lantern_gpu_row_shard_plan", "lantern_gpu_plan_search",
     "lantern_scan_server_start", "lantern_scan_server_start_fn", "lantern_scan_server_port", "lantern_scan_server_stats",
     "lantern_scan_server_batch_histogram", "lantern_scan_server_timing", "lantern_scan_server_stop", "lantern_scan_client_connect", "lantern_scan_client_search", "lantern_scan_client_search_next",
     "lantern_scan_client_close", "lantern_scan_begin_client",
@@ -270,6 +270,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_search_batch_lane_notify": (None, [vp, i32, vp, sz, i32, sz, sz, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_level_for": (i32, [u64, u64, u32]),
         "lantern_gpu_plan_batch": (sz, [sz, i32, vp, sz, sz, sz]),
+        "lantern_gpu_plan_search": (C.c_char_p, [vp, vp]),
         "lantern_gpu_row_shard_plan": (sz, [vp, i32, u64, u32, sz, sz, vp, vp, vp, sz]),
         "lantern_scan_server_start": (vp, [vp, C.c_char_p, i32, sz, C.c_uint, err]),
         "lantern_scan_server_start_fn": (vp, [BATCH_SEARCH_FN, vp, sz, C.c_char_p, i32, sz, C.c_uint, err]),
@@ -1110,6 +1111,23 @@ def level_for(seed: int, slot: int, M: int) -> int:
 def plan_batch(size: int, max_level: int, pending_levels, max_batch: int, min_ratio: int) -> int:
     lv = np.ascontiguousarray(pending_levels, dtype=np.int32)
     return int(lib().lantern_gpu_plan_batch(size, max_level, _ptr(lv), lv.size, max_batch, min_ratio))
+
+
+# lantern_gpu_plan_search's arrays, in order (include/lantern_gpu.h)
+PLAN_SEARCH_IN = ("chunks", "M", "M0", "mcode", "n", "ef_default", "num_cus", "pq_compact", "pqd_inv", "pq_S16", "search_vis_slots", "search_max_wg",
+                  "phase_profile", "spec_profile", "nq", "k", "ef", "skip", "waves", "each", "max_expansion", "env_spec_set", "env_spec",
+                  "env_adc_spec_set", "env_adc_spec", "env_pq_adc", "env_spec_waves", "env_lds_list", "env_wide_rows", "env_solo", "env_waves_per_cu")
+PLAN_SEARCH_OUT = ("path", "spec", "expansion", "waves", "grid", "vis_slots", "lds", "spec_prefetch", "spec_cache", "wide_rows", "took_spec", "lds_list")
+
+
+def plan_search(fields) -> tuple[dict, str | None]:
+    """The shape of the unfiltered search launch for PLAN_SEARCH_IN values (a dict or a sequence; host arithmetic, no device):
+    ({PLAN_SEARCH_OUT name: value}, refusal text or None)."""
+    vals = [fields[n] for n in PLAN_SEARCH_IN] if isinstance(fields, dict) else list(fields)
+    assert len(vals) == len(PLAN_SEARCH_IN)
+    a, out = np.asarray(vals, dtype=np.int64), np.zeros(len(PLAN_SEARCH_OUT), dtype=np.uint32)
+    why = lib().lantern_gpu_plan_search(_ptr(a), _ptr(out))
+    return dict(zip(PLAN_SEARCH_OUT, (int(x) for x in out))), (why.decode() if why else None)
 
 
 def row_shard_plan(shard_sizes, seed: int, M: int, max_batch: int, min_ratio: int):

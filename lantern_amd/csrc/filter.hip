@@ -221,8 +221,7 @@ static bool filter_takes_exact(const Index *ix, const Filter *f, size_t ef_sel)
 }
 
 // the kernel arguments that depend neither on the filter nor on the path
-static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, size_t skip, uint64_t *d_labels, float *d_dists, uint32_t *d_slots,
-                                  uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E)
+static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, size_t skip, const SearchOut &out)
 {
     FilteredArgs a{};
     a.view = ix->view();
@@ -230,12 +229,8 @@ static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, s
     a.k = (uint32_t)k;
     a.skip = (uint32_t)skip;
     a.labels = ix->d_labels;
-    a.out_labels = d_labels;
-    a.out_dists = d_dists;
-    a.out_slots = d_slots;
-    a.out_counts = d_counts;
-    a.out_D = d_D;
-    a.out_E = d_E;
+    a.out_labels = out.labels, a.out_dists = out.dists, a.out_slots = out.slots;
+    a.out_counts = out.counts, a.out_D = out.D, a.out_E = out.E;
     a.totals = ix->d_totals;
     return a;
 }
@@ -283,8 +278,8 @@ static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, h
 }
 
 // The caller holds ix->mu and has flushed.  false -> ix->err.
-static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
-                                   float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, hipStream_t stream)
+static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip, const SearchOut &out,
+                                   hipStream_t stream)
 {
     const std::string why = filter_mismatch(ix, f);
     if(!why.empty()) return set_err(ix, why), false;
@@ -294,16 +289,16 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     const size_t exp = std::max(ef_sel, k + skip);
     if(f->count == 0 || ix->n == 0) {  // nothing allowed: the empty answer, no launch
         std::fill(std::begin(ix->last_filtered), std::end(ix->last_filtered), 0u);
-        if(d_labels && hipMemsetAsync(d_labels, 0, nq * k * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(d_dists && hipMemsetD32Async((hipDeviceptr_t)d_dists, 0x7F800000, nq * k, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(d_slots && hipMemsetAsync(d_slots, 0xFF, nq * k * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(d_counts && hipMemsetAsync(d_counts, 0, nq * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(d_D && hipMemsetAsync(d_D, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(d_E && hipMemsetAsync(d_E, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(out.labels && hipMemsetAsync(out.labels, 0, nq * k * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(out.dists && hipMemsetD32Async((hipDeviceptr_t)out.dists, 0x7F800000, nq * k, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(out.slots && hipMemsetAsync(out.slots, 0xFF, nq * k * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(out.counts && hipMemsetAsync(out.counts, 0, nq * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(out.D && hipMemsetAsync(out.D, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+        if(out.E && hipMemsetAsync(out.E, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
         return true;
     }
     const bool   exact = filter_takes_exact(ix, f, ef_sel);
-    FilteredArgs a = filtered_args(ix, d_q, k, skip, d_labels, d_dists, d_slots, d_counts, d_D, d_E);
+    FilteredArgs a = filtered_args(ix, d_q, k, skip, out);
     a.nq = (uint32_t)nq;
     a.allow_bits = f->d_bits;
     a.allow_slots = f->d_slots;
@@ -343,8 +338,7 @@ static bool each_filters_ok(Index *ix, const Filter *const *filters, size_t nq)
 // `h_tbl`: a page-locked block of each_table_bytes(nq) that stays untouched until the stream work is done, or NULL (pageable
 // staging: the copies then complete before this returns).  false -> ix->err; nothing has been launched unless the failure is HIP's.
 static bool filtered_each_locked(Index *ix, const Filter *const *filters, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip,
-                                 uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
-                                 hipStream_t stream, char *h_tbl)
+                                 const SearchOut &out, hipStream_t stream, char *h_tbl)
 {
     if(!each_filters_ok(ix, filters, nq)) return false;
     if(nq == 0 || k == 0) return true;
@@ -369,7 +363,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
     std::sort(distinct.begin(), distinct.end());
     distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
 
-    const FilteredArgs base = filtered_args(ix, d_q, k, skip, d_labels, d_dists, d_slots, d_counts, d_D, d_E);
+    const FilteredArgs base = filtered_args(ix, d_q, k, skip, out);
     FilteredArgs aw = base, ae = base;
     size_t       lds_w = 0, lds_e = 0;
     if(!walk.empty() && !filtered_shape(ix, false, k, skip, exp, aw, lds_w)) return false;
@@ -419,8 +413,8 @@ static size_t cursor_search_filtered_locked(Index *ix, const Filter *f, Cursor *
     char *dout = (char *)scratch(ix, kScratchCallOut, want * 16 + 16);
     if(!dq || !dout) return 0;
     bool ok = hipMemcpyAsync(dq, padded.data(), row, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
-    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, 1, want, ef, 0, (uint64_t *)dout, (float *)(dout + want * 8), (uint32_t *)(dout + want * 12),
-                                      (uint32_t *)(dout + want * 16), nullptr, nullptr, ix->stream);
+    const SearchOut out{ (uint64_t *)dout, (float *)(dout + want * 8), (uint32_t *)(dout + want * 12), (uint32_t *)(dout + want * 16), nullptr, nullptr };
+    ok = ok && filtered_search_locked(ix, f, (const uint4 *)dq, 1, want, ef, 0, out, ix->stream);
     std::vector<char> h(want * 16 + 4);
     ok = ok && hipMemcpyAsync(h.data(), dout, want * 16 + 4, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
     ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
@@ -579,7 +573,7 @@ try {
     if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
-    if(!filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts, d_D, d_E, (hipStream_t)stream))
+    if(!filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E }, (hipStream_t)stream))
         FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -602,8 +596,7 @@ try {
     if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
     if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
     bool ok = batch_upload(b);
-    ok = ok && filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                      nullptr, b.stream);
+    ok = ok && filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream);
     if(!batch_finish_locked(ix, b, ok, kFilteredBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -631,8 +624,8 @@ try {
     if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
-    if(!filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts,
-                             d_D, d_E, (hipStream_t)stream, nullptr))
+    if(!filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip,
+                             SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E }, (hipStream_t)stream, nullptr))
         FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -655,8 +648,7 @@ try {
     if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
     if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
     bool ok = batch_upload(b);
-    ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr,
-                                    b.counts(b.d_out), nullptr, nullptr, b.stream, b.h_extra());
+    ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra());
     if(!batch_finish_locked(ix, b, ok, kFilteredBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -686,8 +678,7 @@ try {
         if(nq == 0 || k == 0) return;
         if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
         ok = batch_upload(b);
-        ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr,
-                                        b.counts(b.d_out), nullptr, nullptr, b.stream, b.h_extra());
+        ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra());
         ok = ok && batch_download(b);
         if(!ok) msg = ix->err.empty() ? kFilteredBatchFailed : ix->err;
     }

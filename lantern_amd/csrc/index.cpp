@@ -35,13 +35,6 @@ static bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, si
 
 namespace lgpu {
 
-// LANTERN_GPU_LDS_LIST=1: walks keep their candidate list in LDS even when it fits wave 0's registers (walk.hpp search_level vs
-// search_level_reg; identical results -- the switch exists for A/B timing and for the parity test that runs both)
-static int lds_list_env()
-{
-    const char *e = std::getenv("LANTERN_GPU_LDS_LIST");
-    return e && std::atoi(e) != 0;
-}
 static const char *kNoDevice = "lantern_gpu: no HIP device available (this library has no CPU fallback)";
 
 const char *set_err(Index *ix, const std::string &msg)
@@ -453,15 +446,19 @@ bool release_search_slot(Index *ix, int s, hipStream_t stream)
 // Resident workgroups of a walk kernel.  k_search is compiled for six waves per SIMD (<= 80 VGPRs:
 // __launch_bounds__(512, 6)) and its LDS is sized for six workgroups per CU, i.e. 24 waves per CU; k_insert (wider
 // lists, a larger visited set) runs at five.  LANTERN_GPU_WAVES_PER_CU overrides (tuning).
-int search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu)
+int search_grid(int num_cus, int max_wg, int forced, size_t nq, int waves, int waves_per_cu)
 {
-    static const int forced = std::getenv("LANTERN_GPU_WAVES_PER_CU") ? std::atoi(std::getenv("LANTERN_GPU_WAVES_PER_CU")) : 0;
     if(forced > 0) waves_per_cu = forced;
     int per_cu = std::max(1, waves_per_cu / std::max(1, waves));
-    size_t g = (size_t)ix->num_cus * per_cu;
-    if(ix->search_max_wg > 0) g = (size_t)ix->search_max_wg;
+    size_t g = (size_t)num_cus * per_cu;
+    if(max_wg > 0) g = (size_t)max_wg;
     if(g > nq) g = nq;
     return (int)std::max<size_t>(g, 1);
+}
+int search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu)
+{
+    static const int forced = search_env().waves_per_cu;
+    return search_grid(ix->num_cus, ix->search_max_wg, forced, nq, waves, waves_per_cu);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -590,7 +587,7 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
     // A handful of insertions -- ldb_aminsert's one row, the first batches of a build -- walk alone on their CUs: level 0 by the
     // lone-query walk (insert_spec_kernel.hip), up to two insertions per CU one after the other (LANTERN_GPU_INSERT_SPEC=0: off).
     static const bool ins_spec_env = !(std::getenv("LANTERN_GPU_INSERT_SPEC") && std::atoi(std::getenv("LANTERN_GPU_INSERT_SPEC")) == 0);
-    const bool ins_spec = ins_spec_env && !comm && !rs && b_hi - b_lo <= (size_t)ix->num_cus * 2 && insert_spec_supported(ix->mcode, ix->efc, ix->M0) && !lds_list_env();
+    const bool ins_spec = ins_spec_env && !comm && !rs && b_hi - b_lo <= (size_t)ix->num_cus * 2 && insert_spec_supported(ix->mcode, ix->efc, ix->M0) && !search_env().lds_list;
     const int  ins_waves = ins_spec ? 11 : ix->insert_waves;
     const int  grid = ins_spec ? (int)std::max<size_t>(1, std::min<size_t>(b_hi - b_lo, (size_t)ix->num_cus)) : search_grid(ix, b_hi - b_lo, ix->insert_waves, 20);
     if(!ensure_bitmaps(ix, (size_t)grid)) return false;
@@ -609,7 +606,7 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
     ia.bitmaps = ix->d_bitmaps;
     ia.bm_words = (uint32_t)ix->bm_words;
     ia.undo_cap = vis_undo_cap();
-    ia.lds_list = lds_list_env();
+    ia.lds_list = search_env().lds_list;
     ia.only_upper = rs ? 1u : 0u;
     // LDS visited set for the ef_construction-wide walk (spills to the bitmap when 3/4 full); env override for tuning
     // the largest table that still lets FIVE workgroups share a CU (160 KB / 5, minus the walk's lists): 6400 slots at
@@ -1001,8 +998,8 @@ static bool row_shard_candidates(Index *ix, const RowShard &rs, size_t first, si
              hipStreamSynchronize(ix->stream) == hipSuccess;  // `inf` is a local
     } else {
         std::lock_guard<std::mutex> gl(loc->mu);
-        ok = run_search_device(loc, (const uint4 *)((const char *)ix->d_vec + first * row), b, K, rs.ef, 0, g_lab + (size_t)R * part, g_dist + (size_t)R * part,
-                               nullptr, nullptr, nullptr, nullptr, ix->stream, loc->search_waves);
+        ok = run_search_device(loc, (const uint4 *)((const char *)ix->d_vec + first * row), b, K, rs.ef, 0,
+                               SearchOut{ g_lab + (size_t)R * part, g_dist + (size_t)R * part, nullptr, nullptr, nullptr, nullptr }, ix->stream, loc->search_waves);
         if(!ok) set_err(ix, "lantern_gpu: row-sharded build, candidate search: " + loc->err);
     }
     if(ok && W > 1) {
@@ -1184,390 +1181,7 @@ bool flush_locked(Index *ix)
 // search
 // ---------------------------------------------------------------------------------------------------
 
-// the table and the query list of a per-query-parameter launch: in the scratch of the launch's slot (one copy in front of the launch; a
-// slot's earlier launch is over before its next one starts), or where the caller's device-mapped block has them
-static bool each_bind(Index *ix, const EachLaunch &each, int slot, hipStream_t stream, SearchArgs &a)
-{
-    const char *d_tbl = each.d_table;
-    if(!d_tbl) {
-        char *const d = (char *)scratch(ix, launch_table_scratch(slot), each.table_bytes);
-        if(!d) return false;
-        if(hipMemcpyAsync(d, each.h_table, each.table_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
-            set_err(ix, "lantern_gpu: HIP failure (per-query parameter table)");
-            return false;
-        }
-        d_tbl = d;
-    }
-    a.qparams = (const uint4 *)d_tbl;
-    a.qlist = (const uint32_t *)(d_tbl + each.list_at);
-    a.k_stride = a.k;
-    return true;
-}
-
-bool run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, size_t ef, size_t skip, uint64_t *d_labels,
-                       float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, hipStream_t stream,
-                       int waves, uint32_t *done, uint32_t *done_flags, EachLaunch *each)
-{
-    if(nq == 0 || (k == 0 && !each)) return true;
-    size_t expansion = ef ? ef : ix->ef;
-    if(expansion < k + skip) expansion = k + skip;  // usearch: expansion = max(expansion, wanted)
-    if(each) expansion = each->max_expansion;       // (the per-query form: the largest of the list's own)
-    // ---- a compact pq index whose subvectors are whole 16-byte chunks: the f32 walk below over rows DECODED ON THE FLY from the
-    // L2-resident centroid tables (device_common.hpp PqdRow) -- the arithmetic, and so every bit of every answer, of the expanded
-    // form of the same index.  (LANTERN_GPU_PQ_ADC=1, or subvectors of another width: the table walk of search_adc_kernel.hip.)
-    const char *const adc_e = std::getenv("LANTERN_GPU_PQ_ADC");
-    const bool        pq_adc_env = adc_e && std::atoi(adc_e) != 0;
-    const bool pqd = ix->pq_compact && !pq_adc_env && ix->pqd_inv != 0;
-    if(ix->pq_compact && !pqd) {
-        // ---- a compact pq index: ADC over the code rows (search_adc_kernel.hip).  One 8-wave workgroup per query; the per-query
-        // table takes num_subvectors16 x 256 floats of LDS (98 KB at 96 subvectors: one workgroup per CU, three at 32).
-        const uint32_t code_chunks = ix->pq_S16 / 16;
-        uint32_t       vis_slots = 2048;
-        if(ix->search_vis_slots >= 0) vis_slots = (uint32_t)ix->search_vis_slots / 4 * 4;
-        while(vis_slots && search_adc_lds_bytes(code_chunks, ix->chunks, (uint32_t)expansion, ix->M0, vis_slots) > 150 * 1024) vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
-        if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
-        size_t lds = search_adc_lds_bytes(code_chunks, ix->chunks, (uint32_t)expansion, ix->M0, vis_slots);
-        if(lds > 160 * 1024) { set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the ADC search kernel"); return false; }
-        if(each && each->dry) return true;
-        int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
-        // A table that leaves room for one workgroup per CU anyway (96 subvectors x 256 centroids): every query walks alone on
-        // its CU, so it runs the walk that is fastest alone -- walk_spec.hpp's lone-query shape, 3 role + 8 row waves
-        // (LANTERN_GPU_ADC_SPEC=0|1 overrides; an explicit wave count selects the classic kernel as for the f32 walk).
-        bool adc_spec = false;
-        const uint32_t adc_prefetch = ix->M0 % 4 == 0 && ix->M0 <= 32 ? 1u : 0u, adc_cache = adc_prefetch ? 128u : 0u;  // (8-lane groups: four list words per lane)
-        if(waves <= 0 && ix->M0 >= 2 && ix->M0 <= 64 && expansion <= 128 && !lds_list_env()) {
-            const size_t with_spec = lds + search_spec_lds_bytes(ix->M0, adc_prefetch, adc_cache);
-            const char  *se = std::getenv("LANTERN_GPU_ADC_SPEC");
-            adc_spec = with_spec <= 160 * 1024 && (se ? std::atoi(se) != 0 : (per_cu == 1 || nq <= (size_t)ix->num_cus * 2));  // (small batches: as the f32 walk)
-            if(adc_spec) {
-                lds = with_spec;
-                per_cu = 1;
-            }
-        }
-        // (rows of at most 8 chunks: a row wave holds eight 8-lane groups, so FOUR row waves cover a 32-entry list in one pass --
-        // measured, LANTERN_GPU_SPEC_WAVES=7: 1.84 M queries/s against 1.96 M with eight: the shorter row waves matter more)
-        int aw = adc_spec ? 11 : waves > 0 ? std::min(waves, 8) : 8;
-        if(adc_spec) {
-            if(const char *sw = std::getenv("LANTERN_GPU_SPEC_WAVES")) {
-                const int w = std::atoi(sw);
-                if(w >= 4 && w <= 11) aw = w;
-            }
-        }
-        size_t     g = (size_t)ix->num_cus * (size_t)per_cu;
-        if(ix->search_max_wg > 0) g = (size_t)ix->search_max_wg;
-        const int grid = (int)std::max<size_t>(1, std::min(g, nq));
-        const int slot = acquire_search_slot(ix, stream, (size_t)grid);
-        if(slot < 0) return false;
-        SearchArgs a{};
-        a.view = ix->view();
-        a.view.vec = (const uint4 *)ix->d_codes16;
-        a.view.chunks = code_chunks;
-        a.queries = d_queries;
-        a.nq = (uint32_t)nq;
-        a.k = (uint32_t)k;
-        a.ef = (uint32_t)expansion;
-        a.skip = (uint32_t)skip;
-        a.labels = ix->d_labels;
-        a.out_labels = d_labels;
-        a.out_dists = d_dists;
-        a.out_slots = d_slots;
-        a.out_counts = d_counts;
-        a.out_D = d_D;
-        a.out_E = d_E;
-        a.bitmaps = ix->slot_bitmaps[ slot ];
-        a.bm_words = (uint32_t)ix->slot_words[ slot ];
-        a.undo_cap = vis_undo_cap();
-        a.vis_slots = vis_slots;
-        a.totals = ix->d_totals;
-        a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
-        a.ticket = next_ticket(ix, nq, grid, stream);
-        a.done = done;
-        a.done_flags = done_flags;
-        a.lds_list = lds_list_env();
-        a.adc_centers = ix->d_centers;
-        a.adc_S = ix->pq_S;
-        a.adc_C = ix->pq_C;
-        a.adc_subdim = ix->pq_subdim;
-        a.adc_qchunks = ix->chunks;
-        a.spec = adc_spec ? 2 : 0;
-        a.spec_prefetch = adc_spec ? adc_prefetch : 0;
-        a.spec_cache = adc_spec ? adc_cache : 0;
-        if(each) {
-            if(!each_bind(ix, *each, slot, stream, a)) return false;
-            each->took_spec = adc_spec;
-        }
-        HIPCHK(ix, launch_search_adc(ix->metric + M_ADC, a, aw, grid, stream));
-        if(done) ix->slot_pending[ slot ] = false;
-        else if(!release_search_slot(ix, slot, stream)) return false;
-        ix->c_search_queries += nq;
-        return true;
-    }
-    // Launch shape.  Batches that fill the chip: four waves per query, six workgroups per CU -- the walk is HBM-bound and its
-    // serial phases hide behind other walks' row loads.  Batches that cannot (and the lone query): the latency-bound walk of
-    // walk_spec.hpp -- one barrier per hop, speculative row loads, neighbour lists fetched with the rows:
-    //   spec 2: at most one query per CU: three role waves + eight row waves per query (a whole list in one pass);
-    //   spec 1: up to four four-wave workgroups per CU (on request: LANTERN_GPU_SPEC=1).
-    // An explicit wave count (lantern_gpu_set_search_shape; tests, tuning) selects the classic kernel; LANTERN_GPU_SPEC=0|1|2
-    // overrides the automatic choice.
-    int spec = 0;
-    if(waves <= 0) {
-        const char *se = std::getenv("LANTERN_GPU_SPEC");
-        // (the per-query form has no instrumented instantiation: a profiling mode sends it to the classic shape)
-        const bool  can = ix->M0 >= 2 && ix->M0 <= 64 && expansion <= 128 && !ix->phase_profile && !lds_list_env() && !(each && ix->spec_profile);
-        if(can) {
-            // (measured, 1M x 768 cosine, one 1024-query batch: the four-wave latency-bound shape 796 k QPS, the classic kernel
-            // 819 k -- with every walk of the batch resident the row loads saturate HBM for most of the launch and the speculative
-            // rows cost bandwidth; so spec 1 is chosen only on request, spec 2 up to two queries per CU -- one workgroup per CU, the
-            // second query after the first: two workgroups side by side measure the same, 631 vs 627 k at 512 queries)
-            if(se) spec = std::atoi(se);
-            else if(nq <= (size_t)ix->num_cus * 2) spec = 2;  // (1M x 768 cosine: 384 queries 528 k vs 389 k, 512: 624 k vs 500 k, 768: 658 k vs 691 k)
-            if(spec < 0 || spec > 4) spec = 0;
-            if(each) spec = spec >= 2 ? 2 : 0;  // the per-query form exists for the 3 + 8 wave shape only: spec 1 falls back to the classic shape
-#if !LGPU_EXPERIMENTAL
-            if(spec >= 3) spec = 2;  // the variants behind 3 / 4 are not in this library (LANTERN_BUILD_EXPERIMENTAL=1 builds them)
-#else
-            // 4: the ONE-WAVE walk (walk_solo.hpp): no barrier, no hand-over between waves -- f32 l2sq / cos rows of < 64 chunks,
-            // M <= 16, ef <= 64, an index whose visited bitmap fits LDS.  ON REQUEST ONLY (LANTERN_GPU_SPEC=4, or LANTERN_GPU_SOLO=1 for
-            // every launch it applies to): measured in round 5 on the lone 100k x 128 query it is SLOWER than the 3 + 8 wave shape --
-            // 117.7 us against 102.0 us per query on one box (its first form: 152.6 against 106.0), 1.70 against 1.47 us per hop -- because
-            // one wave has to issue all ~540 instructions of a hop itself; parity-green in every regime it takes.
-            // Anything it does not take falls back to spec 2.
-            static const bool solo_auto = std::getenv("LANTERN_GPU_SOLO") && std::atoi(std::getenv("LANTERN_GPU_SOLO")) != 0;
-            if(spec == 2 && !se && solo_auto && nq <= (size_t)ix->num_cus && !each) spec = 4;
-            if(spec == 4) {
-                const size_t words = ((std::max<size_t>(ix->n, 1) + 31) / 32 + 3) & ~(size_t)3;
-                uint32_t     ne_log2 = 9;
-                while(ne_log2 > 5 && search_solo_lds_bytes(ne_log2, (uint32_t)words) > 160 * 1024) --ne_log2;
-                // (the instrumented instantiation -- lantern_gpu_spec_profile -- exists for f32 l2sq rows of exactly 32 chunks)
-                const bool prof_ok = !ix->spec_profile || (ix->mcode == M_L2SQ && ix->chunks == 32);
-                if(pqd || !prof_ok || !search_solo_supported(ix->mcode, ix->chunks, ix->M, ix->M0, (uint32_t)expansion) ||
-                   search_solo_lds_bytes(ne_log2, (uint32_t)words) > 160 * 1024)
-                    spec = 2;
-                else {
-                    const size_t lds = search_solo_lds_bytes(ne_log2, (uint32_t)words);
-                    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-                    size_t       gmax = (size_t)ix->num_cus * per_cu;
-                    if(ix->search_max_wg > 0) gmax = (size_t)ix->search_max_wg;
-                    const int grid = (int)std::max<size_t>(1, std::min(gmax, nq));
-                    const int slot = acquire_search_slot(ix, stream, (size_t)grid);
-                    if(slot < 0) return false;
-                    SearchArgs a{};
-                    a.view = ix->view();
-                    a.queries = d_queries;
-                    a.nq = (uint32_t)nq;
-                    a.k = (uint32_t)k;
-                    a.ef = (uint32_t)expansion;
-                    a.skip = (uint32_t)skip;
-                    a.labels = ix->d_labels;
-                    a.out_labels = d_labels;
-                    a.out_dists = d_dists;
-                    a.out_slots = d_slots;
-                    a.out_counts = d_counts;
-                    a.out_D = d_D;
-                    a.out_E = d_E;
-                    a.vis_slots = (uint32_t)words;   // the LDS bitmap (nothing of the slot's HBM slab is touched)
-                    a.spec_cache = ne_log2;
-                    a.totals = ix->d_totals;
-                    a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
-                    a.ticket = next_ticket(ix, nq, grid, stream);
-                    a.done = done;
-                    a.done_flags = done_flags;
-                    a.spec = 4;
-                    a.phase_cycles = ix->spec_profile ? ix->d_totals + 16 : nullptr;
-                    HIPCHK(ix, launch_search_solo(ix->mcode, a, grid, stream));
-                    ix->c_solo_launches += 1;
-                    if(done) ix->slot_pending[ slot ] = false;
-                    else if(!release_search_slot(ix, slot, stream)) return false;
-                    ix->c_search_queries += nq;
-                    return true;
-                }
-            }
-            // (3: two nodes per round, the second speculative -- walk_twin.hpp; on request only: measured slower)
-            if(spec == 3 && !(expansion <= 64 && (ix->mcode == M_L2SQ || ix->mcode == M_COS) && (group_lanes_for(ix->chunks) == 64 || (ix->mcode == M_L2SQ && group_lanes_for(ix->chunks) == 16))))
-                spec = 2;
-#endif
-        }
-        // (measured, classic kernel, 1M x 768 cosine, 1024 queries: 4 waves 693 k QPS, 6 waves 525 k, 8 waves 594 k -- more waves
-        // only make its serial phases costlier; so four waves per query whatever the batch size)
-        waves = spec >= 2 ? 11 : spec == 1 ? 4 : waves < 0 ? -waves : 4;  // (a negative count: the caller's classic fallback)
-        if(spec) {  // tuning: LANTERN_GPU_SPEC_WAVES = waves per query of the latency-bound shapes (spec 1: 2..8; spec 2: 4..11)
-            if(const char *sw = std::getenv("LANTERN_GPU_SPEC_WAVES")) {
-                const int w = std::atoi(sw);
-                if(w >= (spec >= 2 ? 4 : 2) && w <= (spec >= 2 ? 11 : 8)) waves = w;
-            }
-        }
-    }
-    // list prefetch of the latency-bound walk: every lane of a row's group fetches LW words of the row's own list
-    const int      G_ = group_lanes_for(ix->chunks), LW_ = G_ >= 32 ? 1 : G_ == 16 ? 2 : 4;
-    const uint32_t spec_prefetch = spec && ix->M0 % (uint32_t)LW_ == 0 && ix->M0 <= (uint32_t)(G_ * LW_) ? 1u : 0u;
-    const uint32_t spec_cache = !spec_prefetch ? 0u : spec >= 2 ? 128u : 64u;
-    const size_t   spec_lds = spec ? search_spec_lds_bytes(ix->M0, spec_prefetch, spec_cache, spec == 3) : 0;
-    // LDS visited set: sized for ~3x the planner's estimate of visited nodes per query (hnsw.c:89-132 puts it at
-    // about 2 M ef S with S ~ 3), capped so that SIX workgroups fit on a CU (more walks in flight beat a roomier
-    // set: 1.106 -> 1.17 M QPS at 1M x 768) -- four for the four-wave latency-bound shape, one for the lone-query shape;
-    // it spills to the bitmap beyond
-    const size_t lds_budget = spec >= 2 ? 96 * 1024 : spec == 1 ? 39 * 1024 : 26 * 1024;
-    uint32_t vis_slots = 1024;
-    while(vis_slots < 8192 && vis_slots / 4 * 3 < expansion * ix->M0 * 2) vis_slots <<= 1;
-    if(ix->search_vis_slots >= 0) vis_slots = (uint32_t)ix->search_vis_slots / 4 * 4;
-    while(vis_slots && search_lds_bytes(ix->chunks, (uint32_t)expansion, ix->M0, vis_slots) + spec_lds > lds_budget)
-        vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
-    if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
-    if(search_lds_bytes(ix->chunks, (uint32_t)expansion, ix->M0, vis_slots) + spec_lds > 160 * 1024) {
-        set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel");
-        return false;
-    }
-    if(each && each->dry) return true;
-    const int grid = search_grid(ix, nq, waves, spec >= 2 ? waves : spec == 1 ? 16 : 24);
-    ix->last_search_grid = grid;
-    const int slot = acquire_search_slot(ix, stream, (size_t)grid);
-    if(slot < 0) return false;
-    SearchArgs a{};
-    a.view = ix->view();
-    if(pqd) {
-        a.view.vec = (const uint4 *)ix->d_codes16;
-        a.view.pq_centers = (const uint4 *)ix->d_centers;
-        a.view.pq_cps = ix->pq_subdim / 4;
-        a.view.pq_C = ix->pq_C;
-        a.view.pq_inv = ix->pqd_inv;
-        a.view.pq_row_bytes = ix->pq_S16;
-    }
-    a.queries = d_queries;
-    a.nq = (uint32_t)nq;
-    a.k = (uint32_t)k;
-    a.ef = (uint32_t)expansion;
-    a.skip = (uint32_t)skip;
-    a.labels = ix->d_labels;
-    a.out_labels = d_labels;
-    a.out_dists = d_dists;
-    a.out_slots = d_slots;
-    a.out_counts = d_counts;
-    a.out_D = d_D;
-    a.out_E = d_E;
-    a.bitmaps = ix->slot_bitmaps[ slot ];
-    a.bm_words = (uint32_t)ix->slot_words[ slot ];
-    a.undo_cap = vis_undo_cap();
-    a.vis_slots = vis_slots;
-    a.totals = ix->d_totals;
-    a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
-    a.ticket = next_ticket(ix, nq, grid, stream);
-    // (there is no instrumented instantiation of the decoding walk: a compact pq launch ignores phase_profile)
-    const bool prof_walk = ix->phase_profile && !pqd && !each;  // (nor of the per-query form)
-    a.phase_cycles = each ? nullptr : spec ? (ix->spec_profile ? ix->d_totals + 16 : nullptr) : prof_walk ? ix->d_totals + 8 : nullptr;
-    // the row bitmap only when unique-rows mode asked for it AND it covers every slot the walk can name (a reserve / add since
-    // it was sized would otherwise let mark_touched write past it)
-    a.touched = (!spec && prof_walk && ix->unique_rows_on && ix->d_touched && ix->touched_words * 32 >= ix->cap) ? ix->d_touched : nullptr;
-    if(!spec && prof_walk && ix->trace_on && ix->d_trace && nq <= ix->trace_nq) {  // (lantern_gpu_search_row_trace: the launch's own counts start at zero)
-        HIPCHK(ix, hipMemsetAsync(ix->d_trace_count, 0, nq * 4, stream));
-        a.trace = ix->d_trace;
-        a.trace_count = ix->d_trace_count;
-        a.trace_cap = (uint32_t)ix->trace_cap;
-    }
-    a.done = done;
-    a.done_flags = done_flags;
-    a.lds_list = lds_list_env();
-    // small batch (at most four 4-wave workgroups per CU would be resident anyway): four rows in flight per group
-    static const int wide_env = std::getenv("LANTERN_GPU_WIDE_ROWS") ? std::atoi(std::getenv("LANTERN_GPU_WIDE_ROWS")) : -1;
-    a.wide_rows = spec ? 0 : wide_env >= 0 ? wide_env : (nq * (size_t)waves <= (size_t)ix->num_cus * 16 && nq >= 64);
-    a.spec = spec;
-    a.spec_prefetch = spec_prefetch;
-    a.spec_cache = spec_cache;
-    if(each) {
-        if(!each_bind(ix, *each, slot, stream, a)) return false;
-        each->took_spec = spec != 0;
-    }
-    HIPCHK(ix, launch_search(pqd ? ix->metric + M_PQD : ix->mcode, a, waves, grid, stream));
-    if(done) ix->slot_pending[ slot ] = false;  // the caller waits for the kernel itself: nothing to order later launches against
-    else if(!release_search_slot(ix, slot, stream)) return false;
-    ix->c_search_queries += nq;
-    return true;
-}
-
-// ---- per-query k, ef and skip (lantern_gpu_search_batch_params*) --------------------------------------------------
-std::string params_check(const lantern_gpu_query_params *params, size_t nq, size_t k_stride)
-{
-    if(nq && !params) return "lantern_gpu: null parameter array";
-    for(size_t i = 0; i < nq; ++i) {
-        const char *why = params[ i ].reserved != 0 ? "lantern_gpu: a query's reserved parameter word must be 0"
-                          : params[ i ].k > k_stride ? "lantern_gpu: k_stride is smaller than a query's k"
-                                                     : nullptr;
-        if(why) return std::string(why) + " (params[" + std::to_string(i) + "])";
-    }
-    return "";
-}
-
-bool search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const lantern_gpu_query_params *params, size_t k_stride,
-                          uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
-                          hipStream_t stream, int waves, uint32_t *done_flags, char *h_block, const char *d_block)
-{
-    const std::string why = params_check(params, nq, k_stride);
-    if(!why.empty()) return set_err(ix, why), false;
-    if(nq == 0) return true;
-    // the table {k, expansion, skip, 0} by batch position (run_search_device's rule: expansion = max(ef or the index's, k + skip)), and
-    // the three classes of the list placement (search_kernel.hip: one key per lane up to 64, two up to 128, the LDS list beyond)
-    std::vector<char> pageable;
-    if(!h_block) { pageable.resize(params_table_bytes(nq)); h_block = pageable.data(); d_block = nullptr; }
-    uint32_t *const tbl = (uint32_t *)h_block;
-    std::vector<uint32_t> cls[ 3 ];
-    uint32_t              top[ 3 ] = { 0, 0, 0 };
-    auto class_of = [](uint32_t exp) { return exp <= 64 ? 0 : exp <= 128 ? 1 : 2; };
-    for(size_t i = 0; i < nq; ++i) {
-        size_t exp = params[ i ].ef ? params[ i ].ef : ix->ef;
-        exp = std::max(exp, (size_t)params[ i ].k + (size_t)params[ i ].skip);
-        exp = std::min<size_t>(exp, (size_t)1 << 20);  // (far past the LDS budget already: refused below, and it fits the table's word)
-        tbl[ 4 * i ] = params[ i ].k;
-        tbl[ 4 * i + 1 ] = (uint32_t)exp;
-        tbl[ 4 * i + 2 ] = params[ i ].skip;
-        tbl[ 4 * i + 3 ] = 0;
-        const int c = class_of((uint32_t)exp);
-        cls[ c ].push_back((uint32_t)i);
-        top[ c ] = std::max(top[ c ], (uint32_t)exp);
-    }
-    // refusals are for the whole call and come before anything is queued: every class's launch is planned once without being made
-    for(int c = 2; c >= 0; --c) {
-        if(cls[ c ].empty()) continue;
-        EachLaunch dry;
-        dry.max_expansion = top[ c ];
-        dry.dry = true;
-        if(run_search_device(ix, d_queries, cls[ c ].size(), k_stride, 0, 0, d_labels, d_dists, d_slots, d_counts, d_D, d_E, stream, waves, nullptr, done_flags, &dry))
-            continue;
-        const std::string refusal = ix->err;
-        for(uint32_t i : cls[ c ]) {  // (batch order: the first position whose own expansion is refused)
-            dry.max_expansion = tbl[ 4 * i + 1 ];
-            if(run_search_device(ix, d_queries, cls[ c ].size(), k_stride, 0, 0, d_labels, d_dists, d_slots, d_counts, d_D, d_E, stream, waves, nullptr, done_flags, &dry))
-                continue;
-            return set_err(ix, refusal + " (params[" + std::to_string(i) + "])"), false;
-        }
-        return set_err(ix, refusal), false;
-    }
-    // within a list: by expansion descending, stable -- the longest walks first, so that the launch's tail is a short one
-    uint32_t *lists = tbl + 4 * nq;
-    size_t    list_at[ 3 ], at = 0;
-    for(int c = 0; c < 3; ++c) {
-        std::stable_sort(cls[ c ].begin(), cls[ c ].end(), [&](uint32_t x, uint32_t y) { return tbl[ 4 * x + 1 ] > tbl[ 4 * y + 1 ]; });
-        list_at[ c ] = (nq * 4 + at) * 4;
-        if(!cls[ c ].empty()) std::memcpy(lists + at, cls[ c ].data(), cls[ c ].size() * 4);
-        at += cls[ c ].size();
-    }
-    uint32_t launches = 0, any_spec = 0;
-    for(int c = 0; c < 3; ++c) {
-        if(cls[ c ].empty()) continue;
-        EachLaunch each;
-        each.h_table = h_block;
-        each.table_bytes = nq * 20;
-        each.d_table = d_block;
-        each.list_at = list_at[ c ];
-        each.max_expansion = top[ c ];
-        if(!run_search_device(ix, d_queries, cls[ c ].size(), k_stride, 0, 0, d_labels, d_dists, d_slots, d_counts, d_D, d_E, stream, waves, nullptr, done_flags, &each))
-            return false;
-        launches += 1;
-        any_spec |= each.took_spec ? 1u : 0u;
-    }
-    const uint32_t shape[ 6 ] = { launches, (uint32_t)cls[ 0 ].size(), (uint32_t)cls[ 1 ].size(), (uint32_t)cls[ 2 ].size(), std::max(top[ 0 ], std::max(top[ 1 ], top[ 2 ])), any_spec };
-    std::copy(std::begin(shape), std::end(shape), ix->last_params);
-    return true;
-}
-
+// (the launch itself -- plan_search, run_search_device, search_params_locked: search_plan.cpp)
 // One usearch_search_ef (scan.c:220-228, :273-281) on behalf of one scan.  The query row and the answer live in ONE
 // pinned, device-mapped block: the kernel reads the row over the host link and writes labels | distances | slots |
 // count straight back, so the call is one launch + one stream synchronisation (no H2D / D2H copy commands, whose
@@ -1597,10 +1211,7 @@ size_t search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, si
     }
     char *dev = ix->h_single_dev;
     pad_row(ix, query, kind, (uint32_t *)ix->h_single);
-    uint64_t *d_lab = (uint64_t *)(dev + row);
-    float    *d_dist = (float *)(dev + row + want * 8);
-    uint32_t *d_slot = (uint32_t *)(dev + row + want * 12);
-    uint32_t *d_cnt = (uint32_t *)(dev + row + want * 16);
+    const SearchOut out{ (uint64_t *)(dev + row), (float *)(dev + row + want * 8), (uint32_t *)(dev + row + want * 12), (uint32_t *)(dev + row + want * 16), nullptr, nullptr };
     // completion: the kernel bumps a counter in this block after its answers (system-scope release); the host spins on it.
     // No event, no stream synchronisation: of a ~200 us call those cost ~5 us.  The stream is consulted only as a watchdog
     // (a kernel that died leaves the counter at 0 and the stream idle or in error).
@@ -1609,8 +1220,7 @@ size_t search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, si
     *h_done = 0;
     // one query: the lone-query shape (three role waves + eight row waves: walk_spec.hpp); an explicit wave count
     // (lantern_gpu_set_search_shape) or a list beyond its limits selects the classic eight-wave workgroup
-    bool ok = run_search_device(ix, (const uint4 *)dev, 1, want, ef, 0, d_lab, d_dist, d_slot, d_cnt, nullptr, nullptr, ix->stream,
-                                ix->search_waves > 0 ? 8 : -8, (uint32_t *)(dev + flag_off));
+    bool ok = run_search_device(ix, (const uint4 *)dev, 1, want, ef, 0, out, ix->stream, ix->search_waves > 0 ? 8 : -8, (uint32_t *)(dev + flag_off));
     if(ok) {
         for(unsigned spins = 0; *h_done == 0; ++spins) {
             cpu_relax();
@@ -1703,9 +1313,10 @@ bool batch_download(const HostBatch &b) { return hipMemcpyAsync(b.h_out(), b.d_o
 
 void batch_unpack(const HostBatch &b, size_t first, size_t count, uint64_t *labels, float *distances, uint32_t *counts)
 {
-    std::memcpy(labels + first * b.k, b.labels(b.h_out()) + first * b.k, count * b.k * 8);
-    std::memcpy(distances + first * b.k, b.dists(b.h_out()) + first * b.k, count * b.k * 4);
-    if(counts) std::memcpy(counts + first, b.counts(b.h_out()) + first, count * 4);
+    const SearchOut h = b.out(b.h_out());
+    std::memcpy(labels + first * b.k, h.labels + first * b.k, count * b.k * 8);
+    std::memcpy(distances + first * b.k, h.dists + first * b.k, count * b.k * 4);
+    if(counts) std::memcpy(counts + first, h.counts + first, count * 4);
 }
 
 bool batch_finish_locked(Index *ix, const HostBatch &b, bool ok, const char *what, uint64_t *labels, float *distances, uint32_t *counts)
@@ -2109,8 +1720,8 @@ try {
         ok = ok && hipMemcpyAsync(g_dist + (size_t)R * part, inf.data(), part * 4, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
         ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;  // `inf` is a local
     } else {
-        ok = ok && run_search_device(ix, (const uint4 *)dq, nq, k, ef, 0, g_lab + (size_t)R * part, g_dist + (size_t)R * part, nullptr, nullptr,
-                                     nullptr, nullptr, ix->stream, ix->search_waves);
+        ok = ok && run_search_device(ix, (const uint4 *)dq, nq, k, ef, 0, SearchOut{ g_lab + (size_t)R * part, g_dist + (size_t)R * part, nullptr, nullptr, nullptr, nullptr },
+                                     ix->stream, ix->search_waves);
     }
     if(ok && W > 1) {
         std::vector<size_t> off(W), cnt(W);
@@ -2300,7 +1911,7 @@ try {
     std::lock_guard<std::mutex> g(ix->mu);
     if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    if(!run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts, d_D, d_E,
+    if(!run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E },
                           (hipStream_t)stream, ix->search_waves))
         FAIL(e, ix->err.c_str());
 }
@@ -2316,7 +1927,7 @@ try {
     std::lock_guard<std::mutex> g(ix->mu);
     if(ix->chunks != ix->natural_chunks) { FAIL(e, kStrideAmbiguous); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    if(!run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, d_labels, d_distances, d_slots, d_counts, d_D, d_E,
+    if(!run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E },
                           (hipStream_t)stream, ix->search_waves))
         FAIL(e, ix->err.c_str());
 }
@@ -2339,8 +1950,7 @@ try {
     if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
     if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
     bool ok = batch_upload(b);
-    ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr, nullptr,
-                                 b.stream, ix->search_waves);
+    ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves);
     if(!batch_finish_locked(ix, b, ok, kBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -2373,8 +1983,7 @@ try {
         ix->err.clear();
         if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
         ok = batch_upload(b);
-        ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                     nullptr, b.stream, ix->search_waves);
+        ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves);
         ok = ok && batch_download(b);
         if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
     }
@@ -2425,12 +2034,11 @@ static void lane_notify(Index *ix, int lane, const void *queries, size_t nq, use
         b.d_out = hs_dev + b.out_at;  // the answers land in the block itself: nothing to copy down
         ok = direct_queries || batch_upload(b);
         if(params)
-            ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                            nullptr, b.stream, ix->search_waves, (uint32_t *)(hs_dev + b.extra_at), b.h_extra() + flag_bytes,
-                                            hs_dev + b.extra_at + flag_bytes);
+            ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k, b.out(b.d_out), b.stream, ix->search_waves,
+                                            (uint32_t *)(hs_dev + b.extra_at), b.h_extra() + flag_bytes, hs_dev + b.extra_at + flag_bytes);
         else
-            ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                         nullptr, b.stream, ix->search_waves, nullptr, (uint32_t *)(hs_dev + b.extra_at));
+            ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves, nullptr,
+                                         (uint32_t *)(hs_dev + b.extra_at));
         if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
     }
     const hipStream_t st = b.stream;
@@ -2536,8 +2144,8 @@ try {
     if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
-    if(!search_params_locked(ix, (const uint4 *)d_queries, nq, params, k_stride, d_labels, d_distances, d_slots, d_counts, d_D, d_E, (hipStream_t)stream,
-                             ix->search_waves, nullptr, nullptr, nullptr))
+    if(!search_params_locked(ix, (const uint4 *)d_queries, nq, params, k_stride, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E },
+                             (hipStream_t)stream, ix->search_waves, nullptr, nullptr, nullptr))
         FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -2558,8 +2166,7 @@ try {
     if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
     if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
     bool ok = batch_upload(b);
-    ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                    nullptr, b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
+    ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.out(b.d_out), b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
     if(!batch_finish_locked(ix, b, ok, kBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -2586,8 +2193,7 @@ try {
         ix->err.clear();
         if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
         ok = batch_upload(b);
-        ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.labels(b.d_out), b.dists(b.d_out), nullptr, b.counts(b.d_out), nullptr,
-                                        nullptr, b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
+        ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.out(b.d_out), b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
         ok = ok && batch_download(b);
         if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
     }

@@ -155,7 +155,7 @@ struct Index
     size_t                  trace_nq = 0, trace_cap = 0;
     bool                    trace_on = false;
     float                   last_gather_ms = 0.f;   // kernel time of the last lantern_gpu_distance_gather launch (HIP events on the index stream)
-    int                     last_search_grid = 0;   // workgroups of the last bandwidth-bound search launch (lantern_gpu_last_search_grid)
+    int                     last_search_grid = 0;   // workgroups of the last unfiltered search launch, whatever its path (lantern_gpu_last_search_grid)
     std::deque<ProfBatch>   prof_pending;
     std::vector<hipEvent_t> prof_free;
     lantern_gpu_build_profile prof{};
@@ -235,6 +235,9 @@ struct Index
     View view() const;
 };
 
+// the six answer arrays of a search, device addresses; every one may be NULL
+struct SearchOut { uint64_t *labels; float *dists; uint32_t *slots, *counts; uint64_t *D, *E; };
+
 // ---- one batched search's trip through the host ---------------------------------------------------------------------------------
 // The block `padded queries | labels | distances | counts [| extra]` as it lies in a page-locked staging block (every region at a
 // multiple of 64 bytes; the answers lie the same way in their device buffer), and the stream and buffers the trip uses.  `which`
@@ -251,10 +254,8 @@ struct HostBatch
     size_t    bytes() const { return extra_at + extra_bytes + 64; }
     char     *h_out() const { return hs + out_at; }
     char     *h_extra() const { return hs + extra_at; }
-    // the three answer arrays of a block that starts at `out` (host or device)
-    uint64_t *labels(char *out) const { return (uint64_t *)out; }
-    float    *dists(char *out) const { return (float *)(out + nq * k * 8); }
-    uint32_t *counts(char *out) const { return (uint32_t *)(out + nq * k * 12); }
+    // the three answer arrays of a block that starts at `block` (host or device)
+    SearchOut out(char *block) const { return { (uint64_t *)block, (float *)(block + nq * k * 8), nullptr, (uint32_t *)(block + nq * k * 12), nullptr, nullptr }; }
 };
 constexpr const char *kNoStage = "lantern_gpu: cannot allocate the page-locked staging block";  // batch_stage failed: the index's block, a lane's
 constexpr const char *kNoLaneStage = "lantern_gpu: cannot allocate the lane's page-locked staging block";
@@ -287,24 +288,58 @@ void        pad_rows(const Index *ix, const void *rows, int kind, size_t count, 
 uint32_t   *next_ticket(Index *ix, size_t work, int grid, hipStream_t stream);  // a zeroed work ticket of a persistent launch, or NULL
 uint32_t    vis_undo_cap();
 int         search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu);
-// `done`: NULL, or a device-visible counter the kernel bumps per finished query; the caller then WAITS ON IT (not on the
-// stream) and no completion event is queued behind the launch
-// `each`: NULL, or the launch is ONE CLASS of a per-query-parameter call (search_params_locked): nq = the queries of its list, k =
-// the answer rows' width, ef and skip unused -- every query's own come from the table, the launch is shaped by each->max_expansion.
+int         search_grid(int num_cus, int max_wg, int forced_waves_per_cu, size_t nq, int waves, int waves_per_cu);  // the same, pure
+// ---- the unfiltered search launch: a pure plan (plan_search), then one launch of it (search_plan.cpp) ---------------------------------
+// the environment switches of the launch shape, as values (search_env reads them: LANTERN_GPU_SPEC, _ADC_SPEC, _PQ_ADC, _SPEC_WAVES and
+// _LDS_LIST on every call -- in-process tests set them between calls --, _WIDE_ROWS, _SOLO and _WAVES_PER_CU once per process)
+struct SearchEnv
+{
+    bool spec_set = false, adc_spec_set = false;                          // LANTERN_GPU_SPEC / _ADC_SPEC are present
+    int  spec = 0, spec_waves = 0, wide_rows = -1, waves_per_cu = 0;      // their values; 0, -1, 0: absent
+    bool adc_spec = false, pq_adc = false, lds_list = false, solo = false;  // != 0
+};
+SearchEnv search_env();
+// what the shape rules read: the index's fields by their Index names, the call, the environment.  `each`: the launch is ONE CLASS of a
+// per-query-parameter call (search_params_locked): nq = the queries of its list, k = the answer rows' width, ef and skip unused -- every
+// query's own come from the table, the launch is shaped by max_expansion, the largest expansion of the list.
+struct SearchPlanIn
+{
+    uint32_t  chunks = 0, M = 0, M0 = 0, ef_default = 0, pqd_inv = 0, pq_S16 = 0;                            // the index
+    int       mcode = 0, num_cus = 0, search_vis_slots = -1, search_max_wg = 0;
+    bool      pq_compact = false, phase_profile = false, spec_profile = false;
+    size_t    n = 0, nq = 0, k = 0, ef = 0, skip = 0;                                                         // (n: the index's rows) the call
+    int       waves = 0;  // > 0: explicit (the classic kernel); < 0: automatic, the classic fallback takes -waves
+    bool      each = false;
+    uint32_t  max_expansion = 0;
+    SearchEnv env;
+};
+// path: the rows and the launcher -- ADC over the code rows of a compact pq index (spec 0 or 2), the f32 walk over rows decoded on the fly
+// (any spec), or the plain walk by its shape: classic (spec 0), spec 1, spec 2, and in LGPU_EXPERIMENTAL builds twin (3) and solo (4)
+enum SearchPath : uint32_t { kSearchAdc, kSearchPqd, kSearchClassic, kSearchSpec1, kSearchSpec2, kSearchTwin, kSearchSolo };
+struct SearchPlan
+{
+    SearchPath  path = kSearchClassic;
+    int         spec = 0, waves = 0, grid = 0, wide_rows = 0, lds_list = 0;  // spec, wide_rows, lds_list: SearchArgs'
+    uint32_t    expansion = 0, vis_slots = 0, spec_prefetch = 0, spec_cache = 0;  // (solo: words of the LDS bitmap, -, log2 of the list cache)
+    size_t      lds = 0;             // dynamic LDS of a workgroup
+    bool        took_spec = false;   // a latency-bound shape
+    const char *refusal = nullptr;   // NULL: accepted; else the error text, and only `expansion` above is meaningful
+};
+SearchPlan   plan_search(const SearchPlanIn &in);  // pure: no HIP runtime call, no Index, no getenv, no allocation
+SearchPlanIn search_plan_in(const Index *ix, size_t nq, size_t k, size_t ef, size_t skip, int waves);  // the index's fields, the call, search_env()
+// the table of a per-query-parameter launch (search_params_locked)
 struct EachLaunch
 {
     const char *h_table = nullptr;   // host: the call's table {k, expansion, skip, 0} by batch position, then the classes' query lists
     size_t      table_bytes = 0;     // ... copied into the scratch of the launch's slot; or
     const char *d_table = nullptr;   // ... the same block as the device names it (page-locked, device-mapped): read in place, no copy
     size_t      list_at = 0;         // byte offset of this launch's list in the block
-    uint32_t    max_expansion = 0;   // the largest expansion of the list: sizes the LDS carve, the list placement, the visited set
-    bool        dry = false;         // only the refusals: nothing is acquired, copied or launched
-    bool        took_spec = false;   // out: the launch took a latency-bound shape
 };
-bool        run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, size_t ef, size_t skip,
-                              uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D,
-                              uint64_t *d_E, hipStream_t stream, int waves, uint32_t *done = nullptr,
-                              uint32_t *done_flags = nullptr, EachLaunch *each = nullptr);
+// plan + refuse (ix->err, nothing acquired) + launch.
+// `done`: NULL, or a device-visible counter the kernel bumps per finished query; the caller then WAITS ON IT (not on the
+// stream) and no completion event is queued behind the launch
+bool        run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size_t k, size_t ef, size_t skip, const SearchOut &out,
+                              hipStream_t stream, int waves, uint32_t *done = nullptr, uint32_t *done_flags = nullptr);
 // A batch whose queries bring their own (k, ef, skip) (lantern_gpu_search_batch_params*; the caller holds ix->mu and has flushed): the
 // planning of the whole call -- parameter checks, expansions, the split into at most three launches, the table.  Answer rows are
 // k_stride wide.  `h_block`: NULL, or a page-locked block of params_table_bytes(nq) that stays untouched until the stream work is done;
@@ -313,8 +348,7 @@ bool        run_search_device(Index *ix, const uint4 *d_queries, size_t nq, size
 std::string params_check(const lantern_gpu_query_params *params, size_t nq, size_t k_stride);  // the checks that need no index: "" or the message
 inline size_t params_table_bytes(size_t nq) { return nq * 20 + 16; }
 bool        search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const lantern_gpu_query_params *params, size_t k_stride,
-                                 uint64_t *d_labels, float *d_dists, uint32_t *d_slots, uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E,
-                                 hipStream_t stream, int waves, uint32_t *done_flags, char *h_block, const char *d_block);
+                                 const SearchOut &out, hipStream_t stream, int waves, uint32_t *done_flags, char *h_block, const char *d_block);
 
 // one usearch_search_ef on behalf of `cur` (the caller holds ix->mu); returns the number of results
 size_t      search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, size_t k, size_t ef, bool streaming,
