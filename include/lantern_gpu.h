@@ -332,8 +332,20 @@ LANTERN_GPU_EXPORT void lantern_gpu_last_params_launch(usearch_index_t, uint32_t
  *  3. EXACT path: every allowed slot evaluated, the (distance, slot)-smallest [skip, skip + k) returned; D = allowed count, E = 0;
  *  4. distances are the walk's per-pair reduction, bit for bit (usearch_distance): a row has the same bits on either path and in
  *     the unfiltered search.
- * With an all-allowed filter and C >= expansion the walk path returns exactly the ids, distance bits, D and E of the unfiltered
- * search.  Deleted rows carry label 0 (hnsw.h:40); the reference skips them only after a search has returned them (scan.c:296-300)
+ *  5. SEEDED WALK (lantern_gpu_set_filter_seeds > 0; off by default): the walk path of a query whose filter has count >= 1 allowed
+ *     rows, S' = min(seeds, count), replaces "Start: ..." of 2 by
+ *       seeding: for j = 0 .. S'-1 in order, x = the ((j * count) / S')-th allowed slot in ascending order (64-bit product, integer
+ *         division); if x is unvisited, mark it visited, evaluate it (D += 1) and admit it by the rule of 2 (if |top| < expansion
+ *         or x < worst(top): push x to next and insert it into top);
+ *       allowed-only stage: the loop of 2 to its stop, except that only ALLOWED neighbours are considered -- a disallowed neighbour
+ *         is neither marked, counted nor evaluated;
+ *       hand-over: next := the keys of top (what the stage left in next lies beyond the radius and could never be popped); if the
+ *         start node is unvisited, mark it visited, evaluate it (D += 1) and admit it (into top only if it is allowed);
+ *     and then runs the loop of 2, unchanged, to its stop.  The exact path ignores the setting; seeds = 0 is the walk of 2 exactly;
+ *     every row keeps the walk's distance bits and the order (distance, slot).
+ * With an all-allowed filter, C >= expansion and seeds = 0 the walk path returns exactly the ids, distance bits, D and E of the
+ * unfiltered search.  With seeds > 0 an all-allowed FILTER is no longer the unfiltered search (its walk starts from the seeds); a
+ * NULL entry of the per-query form has no slot list, runs the walk of 2 and still is, bit for bit.  Deleted rows carry label 0 (hnsw.h:40); the reference skips them only after a search has returned them (scan.c:296-300)
  * and gives up streaming after 1000 rows (scan.c:249-252), so a selective predicate applied after the index scan returns fewer
  * than LIMIT rows -- a filter makes the walk itself look for allowed rows.
  * A filter is refused (an error naming both sizes) on another index, or once the index has grown: it is never extended. */
@@ -355,6 +367,15 @@ LANTERN_GPU_EXPORT void   lantern_gpu_filter_free(lantern_gpu_filter_t *);
  * across a scan's pages.  Default exact_factor: 5.6, the measured crossover of the two paths (clustered 1M x 768 f32, ef = 64:
  * DESIGN.md 4.9).  An empty filter returns 0 results without a launch. */
 LANTERN_GPU_EXPORT void lantern_gpu_set_filter_policy(usearch_index_t, int path, size_t cand_cap, double exact_factor, usearch_error_t *);
+/* The seeded walk (5 above): the walk path of every later filtered search on this index -- single filter, per query, cursor, scan,
+ * scan-side service -- starts from min(seeds, allowed) allowed rows.  0 = off (the default).  More than 4096 is refused.  For a
+ * filter correlated with the data (the rows of one cluster, queries from all) the unseeded walk exhausts `next` among disallowed rows
+ * before it meets an allowed one; a random filter pays the seeds' evaluations. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_seeds(usearch_index_t, size_t seeds, usearch_error_t *);
+/* diagnostic: out[0] the setting, [1] S' of the last single-filter walk launch (0 after an exact or empty one; per-query calls leave
+ * it alone), [2] queries of the last filtered call that ran seeded, [3] walk-path queries of that call that did not (seeds = 0, or
+ * NULL entries) */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_seeds(usearch_index_t, uint32_t out[4], usearch_error_t *);
 /* launches of the two filtered kernels since the index was created */
 LANTERN_GPU_EXPORT void lantern_gpu_filter_stats(usearch_index_t, uint64_t *walk_launches, uint64_t *exact_launches, usearch_error_t *);
 /* the shape of the last filtered launch on this index (diagnostic; tests assert the regime a launch ran in):

@@ -114,6 +114,7 @@ EXPORTS = [
     "lantern_gpu_filter_resident_bytes", "lantern_scan_server_start_filtered_fn", "lantern_scan_server_filter_stats", "lantern_scan_client_set_filter",
     "lantern_scan_client_clear_filter",
     "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
+    "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds",
     # per-query k, ef and skip (lantern_gpu.h "PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_params", "lantern_gpu_search_batch_params_lane", "lantern_gpu_search_batch_params_lane_notify",
     "lantern_gpu_search_batch_params_device", "lantern_gpu_last_params_launch", "lantern_scan_server_start_params_fn",
@@ -316,6 +317,8 @@ def lib() -> C.CDLL:
         "lantern_gpu_search_batch_filtered_each_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_search_batch_filtered_each_lane": (None, [vp, i32, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
         "lantern_gpu_last_filtered_each": (None, [vp, vp, err]),
+        "lantern_gpu_set_filter_seeds": (None, [vp, sz, err]),
+        "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
         "lantern_gpu_search_batch_params": (None, [vp, vp, sz, i32, vp, sz, vp, vp, vp, err]),
         "lantern_gpu_search_batch_params_lane": (None, [vp, i32, vp, sz, i32, vp, sz, vp, vp, vp, err]),
         "lantern_gpu_search_batch_params_lane_notify": (None, [vp, i32, vp, sz, i32, vp, sz, vp, vp, vp, vp, vp, err]),
@@ -732,6 +735,17 @@ class GpuIndex:
     def set_filter_policy(self, path="auto", cand_cap=0, exact_factor=5.6):
         """path: "auto" | "walk" | "exact" (or 0 / 1 / 2)."""
         _call("lantern_gpu_set_filter_policy", self.h, FILTER_PATHS.get(path, path), cand_cap, float(exact_factor))
+
+    def set_filter_seeds(self, n):
+        """The walk path of later filtered searches starts from min(n, allowed) allowed rows (0 = off; at most 4096)."""
+        _call("lantern_gpu_set_filter_seeds", self.h, int(n))
+
+    def last_filtered_seeds(self):
+        """lantern_gpu_last_filtered_seeds: the setting, S' of the last single-filter walk launch, seeded / unseeded walk queries of the last call."""
+        out = np.zeros(4, dtype=np.uint32)
+        _call("lantern_gpu_last_filtered_seeds", self.h, _ptr(out))
+        setting, s1, seeded, unseeded = (int(x) for x in out)
+        return {"seeds": setting, "single_seeds": s1, "seeded": seeded, "unseeded": unseeded}
 
     def filter_stats(self):
         w, e = C.c_uint64(), C.c_uint64()

@@ -155,6 +155,7 @@ static Filter *filter_from_bitmap_locked(Index *ix, const uint32_t *words, size_
 constexpr size_t kFilteredLds = 160 * 1024;  // a workgroup's LDS
 constexpr size_t kFilteredLdsTarget = 64 * 1024;  // what the visited set may grow the walk's LDS to (two workgroups per CU)
 constexpr int    kFilteredWaves = 4;
+constexpr size_t kFilterSeedsMax = 4096;  // lantern_gpu_set_filter_seeds refuses more
 
 // The part of a filtered launch's shape that depends on (k, ef, skip, index) only -- not on the filter: exp, cand_cap, vis_slots /
 // rows_per_round and the LDS bytes.  false -> ix->err.
@@ -287,6 +288,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     if(nq == 0 || k == 0) return true;
     const size_t ef_sel = ef ? ef : ix->ef;
     const size_t exp = std::max(ef_sel, k + skip);
+    std::fill(std::begin(ix->last_seeds), std::end(ix->last_seeds), 0u);
     if(f->count == 0 || ix->n == 0) {  // nothing allowed: the empty answer, no launch
         std::fill(std::begin(ix->last_filtered), std::end(ix->last_filtered), 0u);
         if(out.labels && hipMemsetAsync(out.labels, 0, nq * k * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
@@ -305,7 +307,26 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     a.allow_count = (uint32_t)f->count;
     size_t lds = 0;
     if(!filtered_shape(ix, exact, k, skip, exp, a, lds)) return false;
-    const int grid = filtered_launch(ix, exact, a, lds, stream);
+    int grid;
+    if(!exact && ix->filter_seeds) {
+        // the seeded walk exists in the per-query form only: every query's descriptor is this filter, the selection list the identity
+        const size_t      off_desc = (nq * 4 + 7) & ~(size_t)7;
+        std::vector<char> tbl(off_desc + nq * sizeof(FilterDesc));
+        uint32_t *const   sel = (uint32_t *)tbl.data();
+        FilterDesc *const hd = (FilterDesc *)(tbl.data() + off_desc);
+        for(size_t i = 0; i < nq; ++i) {
+            sel[ i ] = (uint32_t)i;
+            hd[ i ] = FilterDesc{ f->d_bits, f->d_slots, (uint32_t)f->count, 0u };
+        }
+        a.seeds = (uint32_t)ix->filter_seeds;
+        const EachTable t{ tbl.data(), tbl.size(), off_desc, 0 };
+        grid = filtered_launch(ix, false, a, lds, stream, &t);  // (pageable staging: the copy completes before this returns)
+        ix->last_seeds[ 1 ] = (uint32_t)std::min(ix->filter_seeds, f->count);
+        ix->last_seeds[ 2 ] = (uint32_t)nq;
+    } else {
+        grid = filtered_launch(ix, exact, a, lds, stream);
+        if(!exact) ix->last_seeds[ 3 ] = (uint32_t)nq;
+    }
     if(grid < 0) return false;
     const uint32_t shape[ 6 ] = { exact ? 2u : 1u, (uint32_t)grid, a.exp, a.cand_cap, a.vis_slots, (uint32_t)lds };
     std::copy(std::begin(shape), std::end(shape), ix->last_filtered);
@@ -365,6 +386,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
 
     const FilteredArgs base = filtered_args(ix, d_q, k, skip, out);
     FilteredArgs aw = base, ae = base;
+    aw.seeds = (uint32_t)ix->filter_seeds;  // (an unfiltered entry has no slot list: it runs the unseeded walk in the same launch)
     size_t       lds_w = 0, lds_e = 0;
     if(!walk.empty() && !filtered_shape(ix, false, k, skip, exp, aw, lds_w)) return false;
     if(!exact.empty() && !filtered_shape(ix, true, k, skip, exp, ae, lds_e)) return false;
@@ -395,6 +417,9 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
     }
     const uint32_t shape[ 6 ] = { n_walk, n_exact, n_unfiltered, n_empty, (uint32_t)distinct.size(), launches };
     std::copy(std::begin(shape), std::end(shape), ix->last_each);
+    const uint32_t n_seeded = ix->filter_seeds ? n_walk - n_unfiltered : 0u;
+    ix->last_seeds[ 2 ] = n_seeded;
+    ix->last_seeds[ 3 ] = n_walk - n_seeded;
     ix->c_search_queries += nq;
     return true;
 }
@@ -535,6 +560,29 @@ try {
     ix->filter_path = path;
     ix->filter_cand_cap = cand_cap;
     ix->filter_exact_factor = exact_factor;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_set_filter_seeds(usearch_index_t h, size_t seeds, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(seeds > kFilterSeedsMax) { FAIL(e, "lantern_gpu: filter seeds must be at most 4096 (0 = off)"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->filter_seeds = seeds;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_last_filtered_seeds(usearch_index_t h, uint32_t out[ 4 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    out[ 0 ] = (uint32_t)ix->filter_seeds;
+    std::copy(ix->last_seeds + 1, ix->last_seeds + 4, out + 1);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

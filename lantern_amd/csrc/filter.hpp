@@ -31,7 +31,7 @@ struct Filter
 struct FilterDesc
 {
     const uint32_t *bits;        // the filter's bitmap (unused when `unfiltered`)
-    const uint32_t *slots;       // [count] the allowed slots, ascending (exact only)
+    const uint32_t *slots;       // [count] the allowed slots, ascending (the exact path's work list; the seeded walk's seeds)
     uint32_t        count;       // allowed slots; 0 without `unfiltered`: an empty filter, the empty answer
     uint32_t        unfiltered;  // != 0: every slot is allowed and there is no bitmap (a NULL entry of the caller's filter array)
 };
@@ -66,6 +66,9 @@ struct FilteredArgs
     // query a position selects, and that query's filter is descs[query]
     const FilterDesc *descs;     // [queries of the call]
     const uint32_t   *select;    // [nq] ticket position -> query
+    // the seeded walk (per-query form only): > 0 = a query whose descriptor has count >= 1 starts from min(seeds, count) allowed rows
+    // taken at even strides from the descriptor's slot list (search_filtered_kernel.hip "SEEDED"); 0 = off
+    uint32_t          seeds;
 };
 
 size_t     filtered_walk_lds_bytes(uint32_t chunks, uint32_t exp, uint32_t cand_cap, uint32_t M0, uint32_t vis_slots);

@@ -14,6 +14,20 @@
 //    radius: they never enter top (it keeps its exp smallest allowed keys either way), and in next they can neither be popped
 //    (next's minimum is >= worst(top) once only they remain: the walk stops) nor push out an entry that could be (an entry evicted
 //    by one of them is larger still).  So the hop's batch gives the keys, D and E of the one-at-a-time definition.
+//    The same holds for a ROUND of the seeded stage below (at most M0 seeds, or the start node alone): its rows are admitted
+//    against worst(top) at the start of the round, and what that admits beyond the one-at-a-time radius is >= the final radius.
+//    SEEDED (an index's lantern_gpu_set_filter_seeds > 0; per-query form only, a single filter goes through a descriptor table):
+//    for a query whose filter has count >= 1 allowed rows, S' = min(seeds, count), the start node is NOT evaluated first.  Instead
+//      seeding:      rounds of at most M0 slots x = allow_slots[(j * count) / S'], j = 0 .. S'-1 in order, through the hop's visited
+//                    filter, distance phase and rank-merges (no pop: E is not touched; D += 1 per seed);
+//      allowed-only: the hop loop, a disallowed neighbour presented to the visited filter as EMPTY (not marked, counted or
+//                    evaluated), to the loop's own stop;
+//      hand-over:    next := the keys of top (what the stage left in next lies beyond the radius and could never be popped), then
+//                    the start node as a one-slot round through the same visited test (evaluated and counted only if unvisited);
+//      today's loop, unchanged, to its stop.
+//    The phase is wave-uniform and every thread derives it from what the whole workgroup reads (the round counter, the stop mark
+//    in the hop's scalar slot); it, S' and the descriptor are per query and read anew for every ticket.  A NULL (unfiltered) entry
+//    has no slot list: S' = 0, today's walk.
 //    ALL-ALLOWED PROPERTY: with every slot allowed and C >= exp the walk returns exactly the ids, distance bits, D and E of the
 //    unfiltered k_search.  Every entry of next that is smaller than worst(top) is in top (both lists received it, top drops only
 //    entries larger than its worst); so an entry evicted from a full next has at least exp smaller entries in top and would never
@@ -74,63 +88,95 @@ size_t filtered_exact_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_
 // a barrier must not see the next hop's reset)
 enum { S_ADMIT0 = S_FRONT, S_ADMIT1, S_ALLOWED0, S_ALLOWED1 };
 
+// the phases of a seeded walk (wave-uniform); a walk that is not seeded is in PH_FINAL from its first hop
+enum { PH_FINAL = 0, PH_SEED, PH_ALLOWED, PH_START };
+
 // The base layer of the filtered walk.  On return s.keys[0..cnt) holds top, ascending; returns cnt.
-template <int METRIC, int G, bool EACH>
+// SEEDED: seed_slots[0, seed_count) is the filter's ascending slot list and S = S' (0: this query is not seeded).
+template <int METRIC, int G, bool EACH, bool SEEDED = false>
 __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, uint64_t *nx2, const uint32_t *allow, uint32_t *bitmap,
-                                     uint32_t bm_words, uint32_t start, int exp, int C, uint32_t &D, uint32_t &E)
+                                     uint32_t bm_words, uint32_t start, int exp, int C, uint32_t &D, uint32_t &E,
+                                     const uint32_t *seed_slots = nullptr, uint32_t seed_count = 0, uint32_t S = 0)
 {
     const int  tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
     const int  lane = tid & 63;
     const bool wave0 = __builtin_amdgcn_readfirstlane(tid) < 64;
     for(uint32_t i = tid; i < s.vis_slots; i += T) s.vis[ i ] = EMPTY;
     const float qn2 = __int_as_float(s.scal[ S_QN2 ]);
-    if(g == 0) {
-        float d = group_dist_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, start), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, start));
-        if(gl == G - 1) {
-            const uint64_t key = make_key(d, start) | allow_bit_of<EACH>(allow, start);
-            nx[ 0 ] = key;
-            s.keys[ 0 ] = key;
-            s.scal[ S_CNT ] = (int)(key & 1u);
-        }
-    }
-    D += 1;
-    __syncthreads();
-    int tcnt = s.scal[ S_CNT ];  // |top|
-    int head = 0, ncnt = 1;      // next = nx[head, ncnt)
+    int      phase = PH_FINAL;
+    uint32_t seed_base = 0;  // the first seed of the next round
+    if constexpr(SEEDED) phase = S ? PH_SEED : PH_FINAL;
+    int      tcnt = 0;            // |top|
+    int      head = 0, ncnt = 0;  // next = nx[head, ncnt)
     uint32_t viscnt = 0;
     bool     spilled = false;
     VisUndo  undo;
-    if(tid == 0) {
-        (void)visit_test_and_set(s, bitmap, start, false);
-        viscnt = s.vis_slots ? 1u : 0u;
+    if(!SEEDED || phase == PH_FINAL) {
+        if(g == 0) {
+            float d = group_dist_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, start), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, start));
+            if(gl == G - 1) {
+                const uint64_t key = make_key(d, start) | allow_bit_of<EACH>(allow, start);
+                nx[ 0 ] = key;
+                s.keys[ 0 ] = key;
+                s.scal[ S_CNT ] = (int)(key & 1u);
+            }
+        }
+        D += 1;
+        __syncthreads();
+        tcnt = s.scal[ S_CNT ];
+        ncnt = 1;
+        if(tid == 0) {
+            (void)visit_test_and_set(s, bitmap, start, false);
+            viscnt = s.vis_slots ? 1u : 0u;
+        }
+        viscnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)viscnt);
+        if(wave0 && !s.vis_slots) undo_record(s, undo, lane == 0, start, 1ull, lane);
     }
-    viscnt = (uint32_t)__builtin_amdgcn_readfirstlane((int)viscnt);
-    if(wave0 && !s.vis_slots) undo_record(s, undo, lane == 0, start, 1ull, lane);
-    __syncthreads();  // (S_CNT is read by every wave before wave 0 may reuse the scalars)
+    __syncthreads();  // (S_CNT is read by every wave before wave 0 may reuse the scalars; a seeded walk: the visited set is EMPTY)
     for(int hop = 0;; ++hop) {
         int *const nnew_slot = &s.scal[ (hop & 1) ? S_NNEW1 : S_NNEW0 ];
         int *const admit_slot = &s.scal[ (hop & 1) ? S_ADMIT1 : S_ADMIT0 ];
         int *const allowed_slot = &s.scal[ (hop & 1) ? S_ALLOWED1 : S_ALLOWED0 ];
         // ---- (1) wave 0: stop test, pop, neighbour list, visited filter
         if(wave0) {
-            bool     stop = head >= ncnt;
-            uint64_t c = 0;
-            if(!stop) {
+            const bool hopping = !SEEDED || phase == PH_FINAL || phase == PH_ALLOWED;  // a round of seeds, or the start node, pops nothing
+            bool       stop = hopping && head >= ncnt;
+            uint64_t   c = 0;
+            if(hopping && !stop) {
                 c = nx[ head ];
                 stop = tcnt == exp && s.keys[ exp - 1 ] < c;
             }
             if(stop) {
                 if(lane == 0) *nnew_slot = -1;
             } else {
-                E += 1;
+                if(hopping) E += 1;
                 const uint32_t node = key_slot(c);
                 if(s.vis_slots && !spilled && viscnt + v.M0 > s.vis_slots / 4 * 3) spilled = true;
                 uint32_t        cap;
-                const uint32_t *list = neighbors_of(v, node, 0, cap);
-                int             nb_new = 0;
+                const uint32_t *list;
+                if constexpr(SEEDED) {
+                    if(phase == PH_SEED) { list = seed_slots; cap = S - seed_base < v.M0 ? S - seed_base : v.M0; }
+                    else if(phase == PH_START) { list = seed_slots; cap = 1; }
+                    else list = neighbors_of(v, node, 0, cap);
+                } else {
+                    list = neighbors_of(v, node, 0, cap);
+                }
+                int nb_new = 0;
                 for(uint32_t off = 0; off < cap; off += 64) {
-                    const uint32_t           i = off + (uint32_t)lane;
-                    const uint32_t           nb = i < cap ? list[ i ] : EMPTY;
+                    const uint32_t i = off + (uint32_t)lane;
+                    uint32_t       nb = EMPTY;
+                    if constexpr(SEEDED) {
+                        if(i < cap) {
+                            if(phase == PH_SEED) nb = list[ (uint32_t)(((uint64_t)(seed_base + i) * seed_count) / S) ];
+                            else if(phase == PH_START) nb = start;
+                            else {
+                                nb = list[ i ];
+                                if(phase == PH_ALLOWED && nb != EMPTY && !allow_bit_of<EACH>(allow, nb)) nb = EMPTY;
+                            }
+                        }
+                    } else {
+                        nb = i < cap ? list[ i ] : EMPTY;
+                    }
                     const bool               isnew = hop_is_new(s, bitmap, nb, spilled);
                     const unsigned long long m = __ballot(isnew);
                     if(isnew) s.newids[ nb_new + __popcll(m & ((1ull << lane) - 1ull)) ] = nb;
@@ -143,8 +189,29 @@ __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, ui
         }
         __syncthreads();
         const int nnew = *nnew_slot;
-        if(nnew < 0) break;
-        head += 1;  // the pop
+        if constexpr(SEEDED) {
+            if(nnew < 0) {
+                if(phase != PH_ALLOWED) break;
+                // hand-over: next := the keys of top; then the start node, as a round of one slot
+                for(int t = tid; t < tcnt; t += T) nx[ t ] = s.keys[ t ];
+                head = 0;
+                ncnt = tcnt;
+                phase = PH_START;
+                __syncthreads();
+                continue;
+            }
+            if(phase == PH_SEED) {
+                seed_base += v.M0;
+                if(seed_base >= S) phase = PH_ALLOWED;
+            } else if(phase == PH_START) {
+                phase = PH_FINAL;
+            } else {
+                head += 1;  // the pop
+            }
+        } else {
+            if(nnew < 0) break;
+            head += 1;  // the pop
+        }
         if(nnew == 0) continue;
         // ---- (2) distances: one G-lane group per row, two rows in flight per group (walk.hpp hop_distances), the allow bit in the key
         const uint64_t worst = tcnt == exp ? s.keys[ exp - 1 ] : ~0ull;
@@ -285,9 +352,11 @@ template <bool EACH> __device__ __forceinline__ uint32_t query_at(uint32_t pos)
 // its descriptor (FilteredArgs::descs[q]), read from memory anew for every query at the point that needs it: a workgroup serves many
 // queries and carries nothing of one query's filter into the next.  A descriptor with count 0 (and no unfiltered mark) is an empty
 // filter: no walk, the empty answer.
-template <int METRIC, int G, bool EACH>
+// SEEDED (with EACH only): the seeded walk of the header, S' = min(FilteredArgs::seeds, the descriptor's count), 0 for an unfiltered entry.
+template <int METRIC, int G, bool EACH, bool SEEDED = false>
 __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
 {
+    static_assert(EACH || !SEEDED, "the seeded walk is instantiated in the per-query form only");
     WalkLds   s;
     uint64_t *nx, *nx2;
     {
@@ -310,18 +379,29 @@ __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
             load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
             const uint32_t *allow;
             bool            any = true;
+            const uint32_t *seed_slots = nullptr;
+            uint32_t        seed_count = 0, S = 0;
             if constexpr(EACH) {
                 const FilterDesc *const d = LGPU_FARG(ka, descs) + q;
                 const uint32_t          unfiltered = d->unfiltered;
                 allow = unfiltered ? nullptr : d->bits;
                 any = unfiltered || d->count != 0;
+                if constexpr(SEEDED) {
+                    if(!unfiltered) {
+                        const uint32_t seeds = LGPU_FARG(ka, seeds);
+                        seed_slots = d->slots;
+                        seed_count = d->count;
+                        S = seeds < seed_count ? seeds : seed_count;
+                    }
+                    S = (uint32_t)__builtin_amdgcn_readfirstlane((int)S);
+                }
             } else {
                 allow = LGPU_FARG(ka, allow_bits);
             }
             if(v.n != 0 && any) {
                 const uint32_t start = greedy_descent<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
-                cnt = search_level_filtered<METRIC, G, EACH>(v, s, nx, nx2, allow, bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
-                                                             (int)LGPU_FARG(ka, cand_cap), D, E);
+                cnt = search_level_filtered<METRIC, G, EACH, SEEDED>(v, s, nx, nx2, allow, bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
+                                                                     (int)LGPU_FARG(ka, cand_cap), D, E, seed_slots, seed_count, S);
             }
         }
         write_answers(s, q, pos, cnt, D, E);
@@ -419,7 +499,17 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.vis_slots);
-    if(a.descs) {
+    if(a.seeds) {
+        if(!a.descs) return hipErrorInvalidValue;  // the seeded walk exists in the per-query form only (filter.hip builds the table)
+#define CALL(MM, GG)                                                                                        \
+    {                                                                                                       \
+        static LdsAttrCache attr_;                                                                          \
+        ensure_dynamic_lds((const void *)k_search_filtered<MM, GG, true, true>, lds, attr_);                \
+        hipLaunchKernelGGL((k_search_filtered<MM, GG, true, true>), dim3(grid), dim3(64 * waves), lds, stream, a); \
+    }
+        LGPU_DISPATCH(metric, a.view.chunks, CALL);
+#undef CALL
+    } else if(a.descs) {
 #define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, true, lds, MM, GG)
         LGPU_DISPATCH(metric, a.view.chunks, CALL);
 #undef CALL

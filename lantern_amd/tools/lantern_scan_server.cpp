@@ -2,7 +2,8 @@
 // index file (what `usearch_save` / the external indexing server produce, lantern_hnsw/src/hnsw/build.c:583) into HBM and
 // serves the k-NN queries of many PostgreSQL backends in coalesced launches (lantern_amd/csrc/scan_server.cpp).
 //   --index FILE --metric l2sq|cos|hamming --dim D --m M [--ef 64] [--ef-construction 128] [--quant-bits 32|16|8]
-//   [--host 127.0.0.1] [--port 8997] [--max-batch 256] [--max-wait-us 150]
+//   [--host 127.0.0.1] [--port 8997] [--max-batch 256] [--max-wait-us 150] [--filter-seeds 0]
+// `--filter-seeds N`: filtered walks start from N allowed rows (lantern_gpu_set_filter_seeds; 0 = off, at most 4096).
 // `--dim` is the number of f32 scalars, or of BITS for hamming -- the reloption `dim` as Lantern passes it (scan.c:84-88).
 #include <unistd.h>
 
@@ -20,7 +21,7 @@ int main(int argc, char **argv)
     (void)::setenv("GPU_MAX_HW_QUEUES", "16", 0);
     std::string host = "127.0.0.1", index_path, metric = "l2sq";
     int         port = 8997, quant_bits = 32;
-    size_t      dim = 0, m = 16, ef = 64, efc = 128, max_batch = 256;
+    size_t      dim = 0, m = 16, ef = 64, efc = 128, max_batch = 256, filter_seeds = 0;
     unsigned    max_wait_us = 150;
     for(int i = 1; i < argc; ++i) {
         auto val = [&](const char *name) -> const char * {
@@ -38,10 +39,11 @@ int main(int argc, char **argv)
         else if(const char *v = val("--quant-bits")) quant_bits = std::atoi(v);
         else if(const char *v = val("--max-batch")) max_batch = (size_t)std::atoll(v);
         else if(const char *v = val("--max-wait-us")) max_wait_us = (unsigned)std::atoi(v);
+        else if(const char *v = val("--filter-seeds")) filter_seeds = (size_t)std::atoll(v);
         else {
             std::fprintf(stderr,
                          "usage: %s --index FILE --metric l2sq|cos|hamming --dim D --m M [--ef 64] [--ef-construction 128]\n"
-                         "          [--quant-bits 32|16|8] [--host H] [--port P] [--max-batch N] [--max-wait-us U]\n",
+                         "          [--quant-bits 32|16|8] [--host H] [--port P] [--max-batch N] [--max-wait-us U] [--filter-seeds S]\n",
                          argv[ 0 ]);
             return 2;
         }
@@ -73,6 +75,11 @@ int main(int argc, char **argv)
         return 1;
     }
     usearch_load(index, index_path.c_str(), &err);
+    if(err) {
+        std::fprintf(stderr, "%s\n", err);
+        return 1;
+    }
+    lantern_gpu_set_filter_seeds(index, filter_seeds, &err);
     if(err) {
         std::fprintf(stderr, "%s\n", err);
         return 1;

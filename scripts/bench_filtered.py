@@ -19,6 +19,13 @@ measures the per-query-filter call instead (lantern_gpu_search_batch_filtered_ea
     alternated, every repeat listed;
   * shared_filter: ONE 10 % filter for --nq queries through the per-query call against search_batch_filtered_device (the same walks;
     the per-query form pays the descriptor reads and the selection list): queries/s of both, alternated, and their ratio.
+
+    python scripts/bench_filtered.py --seeds 0,64,256
+
+measures the seeded walk (lantern_gpu_set_filter_seeds) and prints ONE JSON line: per filter -- the random and
+cluster-correlated ones above, and the rows of one whole cluster (1/16), of half a cluster and of four clusters -- and per seeds value,
+the walk forced: q/s (the seeds values alternated within every repeat, every repeat listed), mean D, and recall@10 against the exact
+path on the first --nq-exact queries.
 """
 import argparse
 import json
@@ -101,6 +108,52 @@ def each_legs(a, ix, rows, dq, bufs, k, ef):
     return out
 
 
+def seeds_legs(a, ix, cluster, filtered, timed_once, slot, D, k):
+    """The seeded walk per filter and seeds value (module docstring)."""
+    values = [int(x) for x in a.seeds.split(",")]
+    rng = np.random.default_rng(7)
+    member = cluster == 0
+    sets = []
+    for kind in ("random", "cluster"):  # the filters of the standing set, drawn as main() draws them
+        for sel in (0.5, 0.1, 0.01, 0.001):
+            if kind == "random":
+                allowed = rng.random(a.n) < sel
+            else:
+                pool = np.flatnonzero(member) if sel * a.n <= member.sum() else np.arange(a.n)
+                allowed = np.zeros(a.n, dtype=bool)
+                allowed[rng.choice(pool, size=min(pool.size, max(1, int(sel * a.n))), replace=False)] = True
+            sets.append((kind, sel, allowed))
+    half = member & (np.random.default_rng(8).random(a.n) < 0.5)
+    sets += [("one_cluster", 1 / 16, member), ("half_cluster", 1 / 32, half), ("four_clusters", 1 / 4, cluster < 4)]
+    legs = []
+    for kind, sel, allowed in sets:
+        f = ix.filter_from_bitmap(allowed)
+        ix.set_filter_seeds(0)
+        ix.set_filter_policy("exact")
+        filtered(f)(a.nq_exact)
+        hip.synchronize()
+        truth = [set(t for t in row.tolist() if t != capi.EMPTY) for row in slot.download((a.nq_exact, k), np.uint32)]
+        ix.set_filter_policy("walk")
+        leg = {"filter": kind, "selectivity": sel, "allowed": int(f.count), "seeds": {}}
+        for v in values:
+            ix.set_filter_seeds(v)
+            filtered(f)(a.nq)  # warm, and the answers
+            hip.synchronize()
+            got = slot.download((a.nq, k), np.uint32)[: a.nq_exact]
+            rec = float(np.mean([len(set(got[i].tolist()) & truth[i]) / max(1, len(truth[i])) for i in range(a.nq_exact)]))
+            leg["seeds"][str(v)] = {"walk_qps": [], "walk_mean_D": float(D.download(a.nq, np.uint64).mean()), "walk_recall_at_10": rec,
+                                    "regime": ix.last_filtered_seeds()}
+        for _ in range(a.reps):  # alternated
+            for v in values:
+                ix.set_filter_seeds(v)
+                leg["seeds"][str(v)]["walk_qps"].append(timed_once(filtered(f), a.nq))
+        legs.append(leg)
+        f.close()
+    ix.set_filter_seeds(0)
+    ix.set_filter_policy("auto")
+    return {"seeds_values": values, "reps": a.reps, "filters": legs}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=1_000_000)
@@ -110,6 +163,7 @@ def main():
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--each", action="store_true", help="the legs of the per-query-filter call")
     p.add_argument("--nq-each", type=int, default=256)
+    p.add_argument("--seeds", default="", help="comma-separated seeds values: the legs of the seeded walk")
     a = p.parse_args()
     M, efc, ef, k = 16, 128, 64, 10
     t0 = time.time()
@@ -151,6 +205,19 @@ def main():
     if a.each:
         out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
         out.update(each_legs(a, ix, rows, dq, (lab, dist, slot, cnt, D, E), k, ef))
+        print(json.dumps(out))
+        return
+    if a.seeds:
+        def timed_once(fn, n_q):
+            s, e = hip.Event(), hip.Event()
+            s.record()
+            fn(n_q)
+            e.record()
+            hip.synchronize()
+            return n_q / (s.elapsed_ms(e) / 1e3)
+
+        out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
+        out.update(seeds_legs(a, ix, cluster, filtered, timed_once, slot, D, k))
         print(json.dumps(out))
         return
     everyone = ix.filter_from_bitmap(np.ones(a.n, dtype=bool))
