@@ -7,7 +7,8 @@ contraction launches it always did."""
 import numpy as np
 import pytest
 
-from tests.exact_knn_bound import mfma_error_cos, mfma_error_l2, gamma, padded_dims
+from tests.exact_knn_bound import certify, mfma_error_cos, mfma_error_l2, gamma, padded_dims
+from tests.value_range import STRICT, exact64, pair_rounding, within_rounding
 from tests.test_gpu_quantized_indexes import quantize_reference
 
 pytestmark = pytest.mark.gpu
@@ -91,36 +92,13 @@ def fam_scaled_by(fam, s):
 FAMILIES = {"gauss": fam_gauss, "offset10": fam_offset(10, 0.01), "offset100": fam_offset(100, 0.1), "dupgroups": fam_dupgroups,
             "repeated": fam_repeated, "lattice": fam_lattice, "scaled": fam_scaled, "bits": fam_bits,
             # i8 storage keeps trunc(100 x) in [-100, 100]: rows whose integers fill that range, and a common offset of 90 +- 2
-            "i8gauss": fam_scaled_by(fam_gauss, 0.3), "i8offset": fam_offset(0.9, 0.02)}
+            "i8gauss": fam_scaled_by(fam_gauss, 0.3), "i8offset": fam_offset(0.9, 0.02),
+            # the edges of the f32 range (tests/value_range.py): norms^2 of 2^-85 and 2^117, denormal squares, sums that overflow
+            "tiny": fam_scaled_by(fam_gauss, 2.0 ** -45), "huge": fam_scaled_by(fam_gauss, 2.0 ** 55), "denorm": fam_scaled_by(fam_gauss, 1e-20),
+            "edge": STRICT["l2_edge"][2]}
 
 
-# ---- float64 distances over the stored values, and the referee's own check ----------------------------------------------------
-def exact64(metric, rows, queries):
-    """[nq][n] float64 distances (l2sq: the norm expansion in float64 -- far inside the f32 bounds checked with it)"""
-    if metric == "hamming":
-        return np.stack([np.unpackbits(np.bitwise_xor(q[None, :], rows).view(np.uint8), axis=1).sum(1) for q in queries]).astype(np.float64)
-    R, Q = rows.astype(np.float64), queries.astype(np.float64)
-    dot = Q @ R.T
-    qn, rn = (Q * Q).sum(1), (R * R).sum(1)
-    if metric == "l2sq":
-        return np.maximum(qn[:, None] + rn[None, :] - 2.0 * dot, 0.0)
-    den = np.sqrt(qn)[:, None] * np.sqrt(rn)[None, :]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        out = 1.0 - dot / den
-    out[(qn[:, None] == 0) & (rn[None, :] == 0)] = 0.0
-    out[(qn[:, None] == 0) ^ (rn[None, :] == 0)] = 1.0
-    return out
-
-
-def pair_rounding(metric, delta, dims):
-    """how far the pair kernel's exact-order distance may be from the real one"""
-    if metric == "hamming":
-        return np.zeros_like(delta)
-    if metric == "cos":
-        return np.full_like(delta, gamma(2 * dims + 16) + 2.0 ** -100)
-    return gamma(dims + 8) * np.abs(delta) + 4.0 * (dims + 8) * 2.0 ** -126
-
-
+# ---- the referee's own check against float64 (exact64, pair_rounding: tests/value_range.py) -----------------------------------------
 def referee(oracle, cores, metric, storage, rows, queries, k):
     """oracle.bruteforce in the storage's sum mode over the stored values; checked against float64: the referee's k-th distance is
     within the pair kernel's rounding of the float64 k-th distance (order statistics move no more than the values do)"""
@@ -138,9 +116,9 @@ def referee(oracle, cores, metric, storage, rows, queries, k):
     for q0 in range(0, sq.shape[0], 128):
         d64 = exact64(metric, sr, sq[q0:q0 + 128])
         kth = np.partition(d64, kk - 1, axis=1)[:, kk - 1]
-        tol = pair_rounding(metric, kth, dims)
-        got = dists[q0:q0 + 128, kk - 1].astype(np.float64)
-        assert np.all(np.abs(got - kth) <= tol), ("referee off float64", q0, np.max(np.abs(got - kth) - tol))
+        got = dists[q0:q0 + 128, kk - 1].astype(np.float64)  # (a k-th distance above FLT_MAX is +inf: within_rounding)
+        with np.errstate(invalid="ignore"):
+            assert np.all(within_rounding(metric, got, kth, dims)), ("referee off float64", q0, np.max(np.abs(got - kth) - pair_rounding(metric, kth, dims)))
     return ids, dists, sr
 
 
@@ -163,7 +141,30 @@ def run_case(capi, oracle, cores, monkeypatch, family, metric, n, d, nq, k, stor
     bad = np.nonzero(np.any(slots != ids, axis=1) | np.any(got.view(np.uint32) != dists.view(np.uint32), axis=1))[0]
     assert bad.size == 0, (f"{bad.size} of {nq} queries differ from the brute force", bad[:8].tolist(), slots[bad[0]][:12].tolist(), ids[bad[0]][:12].tolist())
     ix.close()
-    return {key: after[key] - before[key] for key in after}
+    st = {key: after[key] - before[key] for key in after}
+    st["range_refused"] = range_refusals(metric, stored, queries if storage == "f32" else None, k, dists[:, -1], padded_dims(d)) if metric != "hamming" else 0
+    return st
+
+
+def range_refusals(metric, rows, queries, k, dk, dims):
+    """how many of the call's queries k_certify's RANGE rules refuse whatever the contraction found (tests/exact_knn_bound.py certify with
+    tau = +inf).  Read off index.cpp exact_knn_device_impl / bruteforce.hip k_certify: one cosine ROW norm^2 outside [2^-60, 2^60] raises
+    flag[nq] and the host clears every query's certificate -- all of the call's queries; a QUERY norm out of range, |q|^2 >= 2^120 and the
+    l2sq rule (2 qa + sqrt(dup))^2 >= 2^120 are tested per query and refuse that query alone -- and only where the survivor list is full:
+    with fewer than kk = k + 16 rows every row is a survivor and k_certify passes the query before it looks at a norm (certify's tau =
+    None).  Norms in float64 here, in f32 on the device: a query within 2^-10 of a threshold is not counted."""
+    if queries is None:
+        return 0
+    with np.errstate(over="ignore"):
+        rn = (rows.astype(np.float64) ** 2).sum(1)
+        qn = (queries.astype(np.float64) ** 2).sum(1)
+    if metric == "cos" and np.any((rn != 0) & ((rn < 2.0 ** -61) | (rn > 2.0 ** 61))):
+        return len(qn)
+    if rows.shape[0] < k + 16:
+        return 0
+    slack = 1.0 + 2.0 ** -10
+    return sum(1 for q2, d in zip(qn, dk.astype(np.float64))
+               if not any(certify(metric, np.inf, dd, qq, dims) for qq in (q2 / slack, q2 * slack) for dd in (d / slack, d * slack)))
 
 
 # (family, metric, n, d, nq, k): a list over the edges, not the product -- n: 1, fewer than k, the fused path's start (kSeedCols =
@@ -192,7 +193,16 @@ CASES = [
     ("scaled", "cos", 20000, 3, 16, 100),
     ("bits", "hamming", 4097, 4, 128, 10),
     ("bits", "hamming", 65537, 25, 16, 240),
+    # the edges of the f32 range; RANGE_ALL: the cases in which the certificate's range rules refuse every query of the call
+    ("tiny", "cos", 4097, 33, 64, 10),       # row norms^2 ~ 2^-85 < 2^-60: flag[nq], every query falls back
+    ("huge", "cos", 4097, 128, 64, 10),      # row norms^2 ~ 2^117 > 2^60: the same
+    ("huge", "l2sq", 4097, 128, 64, 10),     # (2 qa + sqrt(dup))^2 >= 2^120, a per-query rule that every query of this set meets
+    ("tiny", "l2sq", 4097, 33, 129, 10),
+    ("denorm", "l2sq", 4097, 128, 16, 10),   # every distance below the bound's absolute term 4 (d + 8) 2^-126
+    ("edge", "l2sq", 4000, 31, 16, 10),      # |q|^2 >= 1e36 chi^2_31 > 2^120, +inf distances: contraction keys inf and inf - inf
+    ("huge", "l2sq", 65537, 33, 16, 100),
 ]
+RANGE_ALL = {("tiny", "cos", 4097), ("huge", "cos", 4097), ("huge", "l2sq", 4097), ("edge", "l2sq", 4000)}
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "unfused"])
@@ -200,6 +210,9 @@ CASES = [
 def test_exact_search_is_the_brute_force(capi, oracle, cores, monkeypatch, family, metric, n, d, nq, k, fused):
     st = run_case(capi, oracle, cores, monkeypatch, family, metric, n, d, nq, k, fused=fused)
     assert st["queries"] == nq and st["certified"] + st["fallback"] == nq
+    assert st["fallback"] >= st["range_refused"], st  # (the range rules refuse whatever the contraction found)
+    if (family, metric, n) in RANGE_ALL:
+        assert st["range_refused"] == nq and st["fallback"] == nq, st
 
 
 QUANT_CASES = [("f16", "gauss", "l2sq", 20000, 128, 64, 10), ("f16", "offset10", "l2sq", 20000, 128, 64, 10), ("f16", "gauss", "cos", 4097, 33, 129, 100),
