@@ -465,27 +465,43 @@ __device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nne
 template <int G, int ROWS>
 __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s, int nnew, uint64_t worst)
 {
-    constexpr int GS = G / 4 >= 8 ? G / 4 : 8;  // lanes per screen row (a quarter of the bytes of the f32 row)
+    // Eight lanes per screen row, each lane's chunks requested in blocks of NB before the first of a block is consumed: a 768-d row
+    // is 48 chunks = six uint4 per lane = two blocks, and a workgroup of 256 lanes takes a hop of up to 32 new rows in one round of
+    // groups -- two memory round trips per hop (16-lane groups with two chunks in flight, then a third, over two rounds took four).
+    // Rows of up to 125 chunks (d = 2000) take more blocks, the last one partial; a chunk beyond the row is neither requested nor
+    // consumed.  Only exec-mask arithmetic stands between the loads of a block in the instruction stream, and (s, r) is requested
+    // ahead of them, in the same block.  NB = 3 is what the register budget holds: the whole 768-d row in one block (NB = 6, 24
+    // VGPRs of row data) spills 13 VGPRs where this spills the parent's 4.  Eight-lane groups also halve the bank
+    // conflict of the query reads below (a lane's chunks are 64 B of query apart: eight addresses per ds_read_b128 service group, not 16).
+    constexpr int GS = 8, NB = 3;
+    static_assert(G % GS == 0, "a screen group lies within one wave");
     const int       tid = threadIdx.x, T = blockDim.x, gs = tid / GS, gsl = tid % GS, NGS = T / GS;
     uint32_t *const surv = (uint32_t *)s.sorted;
-    const uint4    *screen = ((const uint4 *const *)&s.scal[ S_SCREEN ])[ 0 ];
-    const float2   *screen_meta = ((const float2 *const *)&s.scal[ S_SCREEN ])[ 1 ];
-    const uint32_t  chunks = v.chunks, sch = screen_chunks_for(chunks);
-    const float     rd = key_dist(worst);
-    const float     ome = 1.f - fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
+    // (the two tables are read through global-memory pointers: a pointer fetched from LDS is generic to the compiler, and flat loads
+    // count against the LDS reads' counter as well, so every wait for a query chunk would wait for the row block too)
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef float    f32x2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(1))) u32x4 *ScreenRow;
+    typedef const __attribute__((address_space(1))) f32x2 *ScreenMeta;
+    auto uniform = [](uint64_t x) {  // a value every lane holds, moved to scalar registers (the hop loop has no VGPR to spare)
+        return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x) |
+               (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32;
+    };
+    const ScreenRow  screen = (ScreenRow)uniform(((const uint64_t *)&s.scal[ S_SCREEN ])[ 0 ]);
+    const ScreenMeta screen_meta = (ScreenMeta)uniform(((const uint64_t *)&s.scal[ S_SCREEN ])[ 1 ]);
+    const uint32_t   chunks = v.chunks, sch = screen_chunks_for(chunks);
     for(int j = gs; j < nnew; j += NGS) {
         const uint32_t id = s.newids[ j ];
-        const uint4   *row = screen + (size_t)id * sch;
-        const float2   meta = screen_meta[ id ];
+        const ScreenRow row = screen + (size_t)id * sch;
+        const f32x2     meta = screen_meta[ id ];
         float          acc = 0.f;
-        constexpr int  B = 2;  // the loads of two steps in flight together
-        for(uint32_t base = (uint32_t)gsl; base < sch; base += B * GS) {
-            uint4 y[ B ];
+        for(uint32_t base = (uint32_t)gsl; base < sch; base += NB * GS) {
+            u32x4 y[ NB ];
 #pragma unroll
-            for(int c = 0; c < B; ++c)
+            for(int c = 0; c < NB; ++c)
                 if(base + c * GS < sch) y[ c ] = row[ base + c * GS ];
 #pragma unroll
-            for(int c = 0; c < B; ++c)
+            for(int c = 0; c < NB; ++c)
                 if(base + c * GS < sch) {
                     const uint32_t w[ 4 ] = { y[ c ].x, y[ c ].y, y[ c ].z, y[ c ].w };
 #pragma unroll
@@ -503,7 +519,8 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
         }
         acc = group_sum<GS>(acc);
         if(gsl == GS - 1) {
-            bool reject = false;
+            const float rd = key_dist(worst), ome = 1.f - fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
+            bool        reject = false;
             if(__builtin_isfinite(acc)) {
                 const float a = __builtin_sqrtf(acc) * ome - meta.y;
                 const float lb = a > 0.f ? a * a : 0.f;
