@@ -487,8 +487,9 @@ LANTERN_GPU_EXPORT void lantern_gpu_distance_gather(usearch_index_t, const void 
                                                     size_t n, float *out, usearch_error_t *);
 /* kernel time (ms, HIP events on the index stream) of the last lantern_gpu_distance_gather launch of this index */
 LANTERN_GPU_EXPORT float lantern_gpu_last_gather_ms(usearch_index_t, usearch_error_t *);
-/* The int8 screen of the f32 l2sq walk: row evaluations of the searches that ran with it (logical, cumulative)
- * and how many of them read the f32 row (exact); the rest were rejected on the screen row.  Both 0 when the index has no screen. */
+/* The int8 screen of the f32 l2sq and cosine walks: row evaluations of the searches that ran with it (logical,
+ * cumulative) and how many of them read the f32 row (exact); the rest were rejected on the screen row.  Both 0 when the index has
+ * no screen (another metric or storage, rows of fewer than 128 chunks, LANTERN_GPU_SCREEN=0). */
 LANTERN_GPU_EXPORT void lantern_gpu_search_screen_stats(usearch_index_t, uint64_t *logical, uint64_t *exact, usearch_error_t *);
 /* Dense na x nb distance matrix between two host matrices (f32 rows of `dims` scalars, or u32
  * words for hamming with dims = bits).  `exact_order` != 0 uses the per-pair reduction order of

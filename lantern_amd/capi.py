@@ -568,7 +568,8 @@ class GpuIndex:
         return float(_call("lantern_gpu_last_gather_ms", self.h))
 
     def screen_stats(self):
-        """lantern_gpu_search_screen_stats: (row evaluations of the screened searches, how many of them read the f32 row)"""
+        """lantern_gpu_search_screen_stats: (row evaluations of the screened searches, how many of them read the f32 row); f32 l2sq
+        and cosine indexes over rows of >= 128 chunks have a screen, every other index reports (0, 0)"""
         logical, exact = C.c_uint64(0), C.c_uint64(0)
         _call("lantern_gpu_search_screen_stats", self.h, C.byref(logical), C.byref(exact))
         return int(logical.value), int(exact.value)

@@ -29,7 +29,7 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 #ifndef LGPU_ROW_BLOCK1
 #define LGPU_ROW_BLOCK1 4
 #endif
-// the int8 screen of f32 l2sq rows (walk.hpp hop_distances_screened, kernels.hip k_fill_screen): 0 = never built
+// the int8 screen of f32 l2sq and cosine rows (walk.hpp hop_distances_screened, kernels.hip k_fill_screen): 0 = never built
 #ifndef LGPU_SCREEN
 #define LGPU_SCREEN 1
 #endif
@@ -596,18 +596,24 @@ struct View
     uint32_t        pq_C;         // centroids per subvector
     uint32_t        pq_inv;       // ceil(2^16 / pq_cps): chunk / pq_cps == (chunk * pq_inv) >> 16 for chunk < 2^11 (host-checked)
     uint32_t        pq_row_bytes; // bytes of one code row (num_subvectors padded to 16)
-    // the int8 SCREEN copy of an f32 l2sq index (rows of >= 128 chunks; walk.hpp hop_distances_screened); NULL when off
+    // the int8 SCREEN copy of an f32 l2sq or cosine index (rows of >= 128 chunks; walk.hpp hop_distances_screened); NULL when off
     const uint4    *screen;        // [cap][screen_chunks] 16 int8 values per chunk, zero padded
-    const float2   *screen_meta;   // [cap] (s, r): the row's screen values are s * q (f32 multiply), r >= ||row - screen row||
+    const float2   *screen_meta;   // [cap] l2sq (s, r): the row's screen values are s * q (f32 multiply), r >= ||row - screen row||
+                                   //       cosine (s / norm2[slot], rho): rho >= ||row - screen row|| / ||row||
     uint32_t        screen_chunks; // ceil(chunks / 4)
 };
 
-// ---- the int8 screen of an f32 l2sq row ------------------------------------------------------------------------------
+// ---- the int8 screen of an f32 l2sq or cosine row -------------------------------------------------------------------
 // Screen value b (0..3) of word w of a screen row with scale s: the f32 product s * q.  k_fill_screen measures r against
 // exactly these values, and the walk's screen distance reads them the same way.
 __host__ __device__ __forceinline__ float screen_val(float s, uint32_t w, int b) { return s * (float)(int)(int8_t)(uint8_t)(w >> (8 * b)); }
-// the screen is built for f32 l2sq rows that the walk reads with 64 lanes (>= 128 chunks: d >= 509)
+// the screen is built for f32 rows that the walk reads with 64 lanes (>= 128 chunks: d >= 509)
 __host__ __device__ inline bool screen_rows_for(uint32_t chunks) { return chunks >= 128; }
+// The cosine screen rejects only where BOTH rooted norms lie in this range.  Inside it no square of the norm chains and no product
+// of the ab chain leaves the normal range by more than 2^-19 of the result (squares >= 2^-96 against terms flushed below 2^-126,
+// at most 2016 of them), and ra rb, ab and <x, c> are finite; outside it the device's distance may be 0, 1, +-inf, NaN or carry a
+// norm that lost its small components, and the bound says nothing.
+__host__ __device__ inline bool screen_cos_norm_ok(float r) { return r >= 0x1p-48f && r <= 0x1p48f; }  // (false for NaN and 0)
 __host__ __device__ inline uint32_t screen_chunks_for(uint32_t chunks) { return (chunks + 3) / 4; }
 
 __device__ __forceinline__ const uint4 *row_of(const View &v, uint32_t slot) { return v.vec + (size_t)slot * v.chunks; }

@@ -153,7 +153,8 @@ bool rows_stored(Index *ix, size_t first, size_t count)
 {
     if(count == 0) return true;
     if(ix->d_norm2) HIPCHK(ix, launch_fill_norms(ix->mcode, ix->view(), (uint32_t)first, (uint32_t)count, ix->d_norm2, ix->stream));
-    if(ix->d_screen) HIPCHK(ix, launch_fill_screen(ix->view(), (uint32_t)first, (uint32_t)count, ix->d_screen, ix->d_screen_meta, ix->stream));
+    if(ix->d_screen)  // (a cosine index: its metadata reads the norms queued above)
+        HIPCHK(ix, launch_fill_screen(ix->view(), (uint32_t)first, (uint32_t)count, ix->d_screen, ix->d_screen_meta, ix->mcode == M_COS ? ix->d_norm2 : nullptr, ix->stream));
     return true;
 }
 
@@ -1494,10 +1495,11 @@ try {
             return nullptr;
         }
     }
-    // the int8 screen of the f32 l2sq walk: LGPU_SCREEN builds it in, LANTERN_GPU_SCREEN=0 leaves it out at run time
+    // the int8 screen of the f32 l2sq and cosine walks: LGPU_SCREEN builds it in, LANTERN_GPU_SCREEN=0 leaves it out
+    // at run time
     {
         const char *se = std::getenv("LANTERN_GPU_SCREEN");
-        ix->screen = LGPU_SCREEN && ix->mcode == M_L2SQ && !ix->pq && screen_rows_for(ix->chunks) && !(se && std::atoi(se) == 0);
+        ix->screen = LGPU_SCREEN && (ix->mcode == M_L2SQ || ix->mcode == M_COS) && !ix->pq && screen_rows_for(ix->chunks) && !(se && std::atoi(se) == 0);
     }
     return ix;
 }

@@ -101,11 +101,11 @@ struct Index
     // ---- HBM ---------------------------------------------------------------------------------------
     uint4    *d_vec = nullptr;
     float    *d_norm2 = nullptr;  // ||row||^2 per stored row, cosine metrics only (device_common.hpp "cached row norms")
-    // the int8 SCREEN copy of every row (f32 l2sq rows of >= 128 chunks; walk.hpp hop_distances_screened): derived data, filled
+    // the int8 SCREEN copy of every row (f32 l2sq or cosine rows of >= 128 chunks; walk.hpp hop_distances_screened): derived data, filled
     // wherever rows enter d_vec (rows_stored), never serialised.  screen = false (LANTERN_GPU_SCREEN=0, or another kind): not allocated
     bool      screen = false;
     uint4    *d_screen = nullptr;       // [cap][screen_chunks_for(chunks)]
-    float2   *d_screen_meta = nullptr;  // [cap] (s, r)
+    float2   *d_screen_meta = nullptr;  // [cap] (s, r); a cosine index: (s / norm, rho)
     uint64_t *d_labels = nullptr;
     uint8_t  *d_levels = nullptr;
     uint32_t *d_nbr0 = nullptr;

@@ -9,7 +9,7 @@
 //                   (all-pairs table, rows in registers, chain form), k_revlink_staged (rows staged whole in LDS),
 //                   k_revlink (rows read from L2: lists longer than 32 entries, rows beyond 2048 f32 dims).
 //   k_fill_norms    sqrt(||row||^2) of newly stored rows for the cosine metrics (device_common.hpp).
-//   k_fill_screen   the int8 screen copy of newly stored f32 l2sq rows (walk.hpp hop_distances_screened).
+//   k_fill_screen   the int8 screen copy of newly stored f32 l2sq / cosine rows (walk.hpp hop_distances_screened).
 //   k_apply_own_links / k_pack_lists / k_apply_lists
 //                   scatter kernels either side of the all-gathers of the work-sharded build (comm.cpp).
 //   k_gather        metric(query, row[slots[i]]) -- the distance kernel on its own (tests, profiling).
@@ -898,11 +898,16 @@ __global__ void __launch_bounds__(256) k_fill_norms(View v, uint32_t first, uint
     }
 }
 
-// k_fill_screen: the int8 SCREEN copy of the f32 l2sq rows [first, first + count) -- once, when the rows enter the index (walk.hpp
+// k_fill_screen: the int8 SCREEN copy of the f32 rows [first, first + count) -- once, when the rows enter the index (walk.hpp
 // hop_distances_screened).  One wave per row: s = max |y_i| / 127 (f32), q_i = rint(y_i / s) clamped to [-127, 127], and
 // r = ||y - y'|| over exactly the f32 values the walk reconstructs (screen_val), summed in double and rounded UP into f32.  A row
 // with a non-finite value, or whose s is 0, subnormal or not finite, gets q = 0 and r = +inf: the walk then never rejects it.
-__global__ void __launch_bounds__(256) k_fill_screen(View v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta)
+// COS (cosine indexes; norm2 = View::norm2, filled before this kernel on the same stream): the same codes, and the metadata
+// (s / rb, rho): rb = norm2[slot] is the rooted norm the exact evaluation divides by, rho = ||y - y'|| / ||y|| with both norms in
+// double, rounded UP into f32.  Folding s / rb costs one more f32 rounding (inside the bound's e: walk.hpp) and saves a rejected
+// row the gather of its norm.  rho = +inf also where rb is outside screen_cos_norm_ok (zero rows among them).
+template <bool COS>
+__global__ void __launch_bounds__(256) k_fill_screen(View v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, const float *norm2)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
@@ -926,9 +931,14 @@ __global__ void __launch_bounds__(256) k_fill_screen(View v, uint32_t first, uin
             bad |= __shfl_xor(bad, off);
         }
         float      sc = mx / 127.f;
-        const bool ok = !bad && __builtin_isfinite(sc) && sc >= 0x1p-126f;
+        bool       ok = !bad && __builtin_isfinite(sc) && sc >= 0x1p-126f;
+        float      rb = 0.f;
+        if constexpr(COS) {
+            rb = norm2[ slot ];
+            ok = ok && screen_cos_norm_ok(rb);
+        }
         if(!ok) sc = 0.f;
-        double r2 = 0.0;
+        double r2 = 0.0, y2 = 0.0;
         for(uint32_t c = lane; c < sch; c += 64) {
             uint32_t w[ 4 ] = { 0u, 0u, 0u, 0u };
 #pragma unroll
@@ -944,20 +954,25 @@ __global__ void __launch_bounds__(256) k_fill_screen(View v, uint32_t first, uin
                     w[ k ] |= ((uint32_t)q & 255u) << (8 * b);
                     const double dd = (double)f[ b ] - (double)screen_val(sc, w[ k ], b);  // exact: two f32 values of like magnitude, or y' = 0
                     r2 = r2 + dd * dd;
+                    if constexpr(COS) y2 = y2 + (double)f[ b ] * (double)f[ b ];
                 }
             }
             screen[ (size_t)slot * sch + c ] = make_uint4(w[ 0 ], w[ 1 ], w[ 2 ], w[ 3 ]);
         }
-        for(int off = 32; off > 0; off >>= 1) r2 = r2 + __shfl_xor(r2, off);
+        for(int off = 32; off > 0; off >>= 1) {
+            r2 = r2 + __shfl_xor(r2, off);
+            if constexpr(COS) y2 = y2 + __shfl_xor(y2, off);
+        }
         if(lane == 0) {
             float r = __builtin_inff();
             if(ok) {
-                const double rr = sqrt(r2 * (1.0 + 0x1p-40));  // (the margin covers the rounding of the double sum and sqrt)
+                // (the margin covers the rounding of the double sums, the quotient and sqrt; y2 > 0: rb is in range)
+                const double rr = COS ? sqrt(r2 / y2 * (1.0 + 0x1p-40)) : sqrt(r2 * (1.0 + 0x1p-40));
                 r = (float)rr;
                 if((double)r < rr) r = nextafterf(r, __builtin_inff());
                 if(!__builtin_isfinite(r)) r = __builtin_inff();
             }
-            meta[ slot ] = make_float2(sc, r);
+            meta[ slot ] = make_float2(COS && ok ? sc / rb : sc, r);
         }
     }
 }
@@ -1144,12 +1159,14 @@ hipError_t launch_fill_norms(int metric, const View &v, uint32_t first, uint32_t
     return hipGetLastError();
 }
 
-hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, hipStream_t stream)
+hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, const float *norm2, hipStream_t stream)
 {
     if(count == 0) return hipSuccess;
     uint32_t blocks = (count + 3) / 4;  // four rows (waves) per block
     if(blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(k_fill_screen, dim3(blocks), dim3(256), 0, stream, v, first, count, screen, meta);
+    // norm2 (the cached rooted norms of a cosine index, already queued for these rows): the cosine metadata; NULL: the l2sq metadata
+    if(norm2) hipLaunchKernelGGL(k_fill_screen<true>, dim3(blocks), dim3(256), 0, stream, v, first, count, screen, meta, norm2);
+    else hipLaunchKernelGGL(k_fill_screen<false>, dim3(blocks), dim3(256), 0, stream, v, first, count, screen, meta, norm2);
     return hipGetLastError();
 }
 

@@ -224,8 +224,9 @@ hipError_t launch_store_quantised(const float *src, uint32_t dims, uint32_t coun
 
 // ||row||^2 of rows [first, first + count) into norm2 (cosine metrics only; no-op otherwise)
 hipError_t launch_fill_norms(int metric, const View &v, uint32_t first, uint32_t count, float *norm2, hipStream_t stream);
-// the int8 screen rows and (s, r) of the f32 rows [first, first + count) (walk.hpp hop_distances_screened)
-hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, hipStream_t stream);
+// the int8 screen rows and (s, r) of the f32 rows [first, first + count) (walk.hpp hop_distances_screened); norm2 != NULL (a cosine
+// index: the rows' cached rooted norms, filled before this on the same stream): (s / norm, rho) instead
+hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, const float *norm2, hipStream_t stream);
 // out[i] = metric(query, row(slots[i]))
 hipError_t launch_gather(int metric, const View &v, const uint4 *query, const uint32_t *slots, uint32_t n, float *out,
                          hipStream_t stream);

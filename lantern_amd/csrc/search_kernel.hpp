@@ -93,8 +93,9 @@ k_search(SearchArgs)
         if constexpr(SPEC != 0) carve_spec(end, sc, LGPU_VIEW_ARG(ka, SearchArgs, M0), LGPU_SEARCH_ARG(ka, spec_prefetch), LGPU_SEARCH_ARG(ka, spec_cache), SPEC == 3 ? 1u : 0u);
         else (void)end;
     }
-    // the int8 screen of the f32 l2sq walk over rows of >= 128 chunks (walk.hpp hop_distances_screened); used iff the view has one
-    constexpr bool SCREEN = LGPU_SCREEN && METRIC == M_L2SQ && G == 64 && !PROF && SPEC == 0 && KPL > 0;
+    // the int8 screen of the f32 l2sq and cosine walks over rows of >= 128 chunks (walk.hpp hop_distances_screened); used iff the view
+    // has one
+    constexpr bool SCREEN = LGPU_SCREEN && (METRIC == M_L2SQ || METRIC == M_COS) && G == 64 && !PROF && SPEC == 0 && KPL > 0;
     for(uint32_t pos = blockIdx.x; pos < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
         uint32_t q = pos, each_k = 0, each_ef = 0, each_skip = 0;
         if constexpr(EACH) {  // (pos comes out of LDS: made wave-uniform, the list entry and the parameter row are scalar loads)

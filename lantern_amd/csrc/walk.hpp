@@ -450,9 +450,10 @@ __device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nne
 }
 
 // ---- the int8 screen -------------------------------------------------------------------------------------
-// The distance phase of a hop of an f32 l2sq walk whose list is full (radius = the key `worst`): most new rows land outside
-// the radius and are read only to be thrown away.  So first every new row's distance is BOUNDED from below on its int8 screen
-// copy y' = s * q (a quarter of the bytes; View::screen), and only the rows the bound cannot reject pay for the f32 row.
+// The distance phase of a hop of an f32 l2sq or cosine walk whose list is full (radius = the key `worst`): most new rows land
+// outside the radius and are read only to be thrown away.  So first every new row's distance is BOUNDED from below on its int8
+// screen copy y' = s * q (a quarter of the bytes; View::screen), and only the rows the bound cannot reject pay for the f32 row.
+// l2sq:
 //   d' = sum (x_i - y'_i)^2 in f32 (any order: every term is >= 0, so the relative error is at most (terms + tree) ulps),
 //   r  >= ||y - y'|| (k_fill_screen: in double, rounded up; +inf for rows with non-finite values or a zero / subnormal scale),
 //   ||x - y|| >= ||x - y'|| - r  (triangle inequality), so  LB = max(0, sqrt(d') (1 - e) - r)^2 <= ||x - y||^2,
@@ -462,9 +463,30 @@ __device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nne
 // radius only shrinks it never can.  Its key becomes ~0 (above every radius: the visit wave's choice and the list wave's merge
 // skip it, as they would skip the exact key).  Survivors get the exact evaluation of hop_distances, same chain, same tree, same
 // bits (the caller runs it over the survivors, s.sorted[0..ns), ns returned).
-template <int G, int ROWS>
-__device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s, int nnew, uint64_t worst)
+// cosine (the device's distance is d = fl(1 - fl(ab / fl(ra rb))): ab the 64-lane chain of <x, y>, ra = qn2 and rb = norm2[slot] the
+// rooted norms; X = ||x||, Y = ||y||, P = X Y exact, u = 2^-24, m = ceil(chunks / 64) 4 + 6 the length of a 64-lane chain and tree):
+//   <x, y> <= <x, y'> + X ||y - y'||  (Cauchy-Schwarz), so  sigma = <x, y> / P <= <x, q> s / P + rho,  rho >= ||y - y'|| / Y
+//   (k_fill_screen<true>: both norms in double, rounded up; +inf for rows with non-finite values, a zero / subnormal scale, or rb
+//   outside screen_cos_norm_ok -- the zero rows among them).  Where ra and rb are inside screen_cos_norm_ok:
+//   (a) the device's similarity.  ab = <x, y> + alpha P with |alpha| <= m u (every partial sum of products is at most P in
+//       magnitude); ra = X (1 + a), rb = Y (1 + b) with |a|, |b| <= (m / 2 + 1) u + 2^-20 (the chain of squares has positive terms;
+//       the last term is what squares flushed below the normal range can take); fl(ra rb) and the divide round once each.  With
+//       |sigma| <= 1:  |fl(ab / fl(ra rb)) - sigma| <= (2 m + 4) u + 2^-19 =: e1, and the final subtraction is monotone and rounds
+//       by at most 2 u:  d >= 1 - sigma - e1 - 2 u.
+//   (b) the screen's similarity.  acc = <x, q> + beta X ||q|| with |beta| <= n u, n = 16 ceil(chunks / 32) + 3 (the eight-lane chain
+//       and tree below; the terms have BOTH signs, so unlike l2sq's "any order" holds only because the error of any order is bounded
+//       by n u sum |x_i q_i| <= n u X ||q|| -- an absolute error on the similarity scale, not a relative one), and s ||q|| = ||y'||
+//       <= 2 Y.  The folded constant t = fl(s / rb) = (s / Y)(1 + tau), |tau| <= |b| + u, and fl(fl(acc t) / ra) adds 2 u + |a|
+//       relative to a value of magnitude at most 2:  |sim8 - <x, q> s / P| <= 2 n u + 2 (|a| + |b| + 3 u) =: e2.
+//   (c) the test's own f32 steps ((sim8 + rho) + e, 1 - that, - e: values of magnitude <= 4) round by at most 16 u together.
+//   At 128 <= chunks <= 500 (n <= 259, m <= 38): e1 + 2 u + e2 + 16 u <= 114 u + 668 u + 16 u < 8192 u = 2^-11 = 2 e, so with
+//   u_ = sim8 + rho + e:  1 - u_ - e <= 1 - sigma - e1 - 2 u <= d.  The (2 chunks + 64) 2^-24 arm of e keeps the inequality for longer
+//   rows (both e1 and e2 grow by less than chunks u each).  A row is rejected iff 1 - u_ - e > dist(worst), strictly; a NaN anywhere
+//   fails the test, and so does rho = +inf.  Nothing in (a) - (c) depends on the scale of x or of y inside the range.
+template <int METRIC, int G, int ROWS>
+__device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s, int nnew, uint64_t worst, float qn2)
 {
+    static_assert(METRIC == M_L2SQ || METRIC == M_COS, "the screen serves the f32 l2sq and cosine walks");
     // Eight lanes per screen row, each lane's chunks requested in blocks of NB before the first of a block is consumed: a 768-d row
     // is 48 chunks = six uint4 per lane = two blocks, and a workgroup of 256 lanes takes a hop of up to 32 new rows in one round of
     // groups -- two memory round trips per hop (16-lane groups with two chunks in flight, then a third, over two rounds took four).
@@ -511,20 +533,37 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
                         const float    xs[ 4 ] = { __uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w) };
 #pragma unroll
                         for(int b = 0; b < 4; ++b) {
-                            const float t = xs[ b ] - screen_val(meta.x, w[ k ], b);
-                            acc = __builtin_fmaf(t, t, acc);
+                            if constexpr(METRIC == M_COS) {
+                                // <x, q>: one convert and one fma per value, the scale applied once behind the group sum.  Terms of
+                                // both signs: any order is within n u X ||q|| of the exact sum -- (b) above -- which is all e needs.
+                                acc = __builtin_fmaf(xs[ b ], (float)(int)(int8_t)(uint8_t)(w[ k ] >> (8 * b)), acc);
+                            } else {
+                                const float t = xs[ b ] - screen_val(meta.x, w[ k ], b);
+                                acc = __builtin_fmaf(t, t, acc);
+                            }
                         }
                     }
                 }
         }
         acc = group_sum<GS>(acc);
         if(gsl == GS - 1) {
-            const float rd = key_dist(worst), ome = 1.f - fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
-            bool        reject = false;
-            if(__builtin_isfinite(acc)) {
-                const float a = __builtin_sqrtf(acc) * ome - meta.y;
-                const float lb = a > 0.f ? a * a : 0.f;
-                reject = lb > 0x1p-100f && lb * ome > rd;  // (lb > 2^-100: far above what underflow can take from either sum)
+            bool reject = false;
+            if constexpr(METRIC == M_COS) {
+                // meta = (s / rb, rho); qn2 = ra.  The steps of (b) and (c), in this order (tests/test_screen_bound_cos.py restates
+                // them); a query whose norm is 0 or outside the range rejects nothing, a row's range is in rho.
+                const float rd = key_dist(worst), e = fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
+                if(screen_cos_norm_ok(qn2)) {
+                    const float sim8 = (acc * meta.x) / qn2;
+                    const float ub = (sim8 + meta.y) + e;
+                    reject = (1.f - ub) - e > rd;
+                }
+            } else {
+                const float rd = key_dist(worst), ome = 1.f - fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
+                if(__builtin_isfinite(acc)) {
+                    const float a = __builtin_sqrtf(acc) * ome - meta.y;
+                    const float lb = a > 0.f ? a * a : 0.f;
+                    reject = lb > 0x1p-100f && lb * ome > rd;  // (lb > 2^-100: far above what underflow can take from either sum)
+                }
             }
             if(reject) s.newkeys[ j ] = ~0ull;
             else surv[ atomicAdd(&s.scal[ S_NSURV ], 1) ] = (uint32_t)j;
@@ -705,14 +744,14 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l)  // l uniform
             tl = t_;                                                  \
         }                                                             \
     }
-// SCREEN (k_search over f32 l2sq rows of >= 128 chunks, never the instrumented walk): level 0 of a split walk whose screen pointer
+// SCREEN (k_search over f32 l2sq or cosine rows of >= 128 chunks, never the instrumented walk): level 0 of a split walk whose screen pointer
 // (s.scal[S_SCREEN]) is set runs the hops whose list is full through hop_distances_screened, counting the rows it rejected in
 // s.scal[S_NREJ].
 template <int METRIC, int G, int KPL, bool PROF = false, int ROWS = 2, bool SCREEN = false>
 __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uint32_t bm_words, uint32_t start, int level, int ef,
                                 uint32_t &D, uint32_t &E, unsigned long long *prof = nullptr)
 {
-    static_assert(!SCREEN || (METRIC == M_L2SQ && !PROF), "the screen serves the f32 l2sq walk");
+    static_assert(!SCREEN || ((METRIC == M_L2SQ || METRIC == M_COS) && !PROF), "the screen serves the f32 l2sq and cosine walks");
 
     const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G;
     const int lane = tid & 63;
@@ -933,7 +972,7 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
         if constexpr(SCREEN) {  // one copy of the exact phase: over the screen's survivors, or over all rows
             const uint64_t radius = screen_on ? worst_pub[ par ^ 1 ] : ~0ull;
             int            ne = nnew;
-            if(radius != ~0ull) ne = hop_distances_screened<G, ROWS>(v, s, nnew, radius);
+            if(radius != ~0ull) ne = hop_distances_screened<METRIC, G, ROWS>(v, s, nnew, radius, qn2);
             hop_distances<METRIC, G, ROWS, false, true>(v, s, ne, qn2, ~0ull, nullptr, radius != ~0ull ? (const uint32_t *)s.sorted : nullptr);
         } else {
             hop_distances<METRIC, G, ROWS, false>(v, s, nnew, qn2, ~0ull, nullptr);
