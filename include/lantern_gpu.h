@@ -491,6 +491,19 @@ LANTERN_GPU_EXPORT float lantern_gpu_last_gather_ms(usearch_index_t, usearch_err
  * cumulative) and how many of them read the f32 row (exact); the rest were rejected on the screen row.  Both 0 when the index has
  * no screen (another metric or storage, rows of fewer than 128 chunks, LANTERN_GPU_SCREEN=0). */
 LANTERN_GPU_EXPORT void lantern_gpu_search_screen_stats(usearch_index_t, uint64_t *logical, uint64_t *exact, usearch_error_t *);
+/* Diagnostics (tests): what the device STORED as the int8 screen of slots [first, first + count), copied out behind the index stream
+ * after buffered single adds are flushed.  rows[count][row_bytes] int8 (16 per screen chunk, zero padded); meta[count][2] f32: l2sq
+ * (s, r), cosine (s / norm, rho); norms[count] f32: a cosine index's cached rooted norms, the ones the fill divided by (an l2sq index
+ * writes nothing there).  Any output pointer may be NULL.  Returns row_bytes = ceil(chunks / 4) * 16, or 0 for an index without a
+ * screen (see lantern_gpu_search_screen_stats), which is not an error: nothing is written then.  A range that does not lie within
+ * the index's size is refused. */
+LANTERN_GPU_EXPORT size_t lantern_gpu_export_screen(usearch_index_t, size_t first, size_t count, int8_t *rows, float *meta, float *norms,
+                                                    usearch_error_t *);
+/* Diagnostics (tests): the screened hop's own decision (walk.hpp hop_distances_screened, called as the walk calls it) for one query,
+ * n <= 64 slots (repeats allowed) and the radius `radius`, by one workgroup of `workgroup` = 256 or 512 threads:
+ * rejected[i] = 1 where the screen rejects slots[i], else 0.  An index without a screen is refused. */
+LANTERN_GPU_EXPORT void lantern_gpu_screen_probe(usearch_index_t, const void *query, const uint32_t *slots, size_t n, float radius,
+                                                 int workgroup, uint8_t *rejected, usearch_error_t *);
 /* Dense na x nb distance matrix between two host matrices (f32 rows of `dims` scalars, or u32
  * words for hamming with dims = bits).  `exact_order` != 0 uses the per-pair reduction order of
  * the graph walk (bit-identical to usearch_distance); 0 uses the fp32-MFMA contraction. */

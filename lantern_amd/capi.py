@@ -118,6 +118,8 @@ EXPORTS = [
     # per-query k, ef and skip (lantern_gpu.h "PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_params", "lantern_gpu_search_batch_params_lane", "lantern_gpu_search_batch_params_lane_notify",
     "lantern_gpu_search_batch_params_device", "lantern_gpu_last_params_launch", "lantern_scan_server_start_params_fn",
+    # diagnostics of the int8 screen (lantern_gpu.h lantern_gpu_export_screen)
+    "lantern_gpu_export_screen", "lantern_gpu_screen_probe",
 ]
 # lantern_gpu_query_params: one row {k, ef, skip, reserved} per query (ef 0 = the index's default; reserved must be 0)
 QUERY_PARAMS = np.dtype([("k", np.uint32), ("ef", np.uint32), ("skip", np.uint32), ("reserved", np.uint32)])
@@ -221,6 +223,8 @@ def lib() -> C.CDLL:
         "lantern_gpu_last_search_grid": (i32, [vp, err]),
         "lantern_gpu_last_gather_ms": (f32, [vp, err]),
         "lantern_gpu_search_screen_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), err]),
+        "lantern_gpu_export_screen": (sz, [vp, sz, sz, vp, vp, vp, err]),
+        "lantern_gpu_screen_probe": (None, [vp, vp, vp, sz, f32, i32, vp, err]),
         "lantern_gpu_save_stream": (None, [vp, vp, vp, err]),
         "lantern_gpu_pq_compact": (None, [vp, err]),
         "lantern_gpu_pq_expand": (None, [vp, err]),
@@ -573,6 +577,28 @@ class GpuIndex:
         logical, exact = C.c_uint64(0), C.c_uint64(0)
         _call("lantern_gpu_search_screen_stats", self.h, C.byref(logical), C.byref(exact))
         return int(logical.value), int(exact.value)
+
+    def export_screen(self, first=0, count=None):
+        """lantern_gpu_export_screen: the stored int8 screen of slots [first, first + count) (count None: to the end) as
+        {"codes": int8 [count][row_bytes], "meta": f32 [count][2], "norms": f32 [count] (cosine) or None, "row_bytes"}; an index
+        without a screen gives row_bytes 0, empty codes and meta None"""
+        if count is None:
+            count = len(self) - first
+        row_bytes = int(_call("lantern_gpu_export_screen", self.h, first, count, None, None, None))
+        if row_bytes == 0:
+            return {"codes": np.zeros((count, 0), np.int8), "meta": None, "norms": None, "row_bytes": 0}
+        codes, meta = np.zeros((count, row_bytes), np.int8), np.zeros((count, 2), np.float32)
+        norms = np.zeros(count, np.float32) if self.metric == METRIC_COS else None
+        _call("lantern_gpu_export_screen", self.h, first, count, _ptr(codes), _ptr(meta), _ptr(norms))
+        return {"codes": codes, "meta": meta, "norms": norms, "row_bytes": row_bytes}
+
+    def screen_probe(self, query, slots, radius, workgroup=256):
+        """lantern_gpu_screen_probe: bool per slot (at most 64, repeats allowed) -- the screened hop rejects it at `radius`"""
+        q = _rows(query, self.metric)[0]
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        out = np.zeros(s.size, dtype=np.uint8)
+        _call("lantern_gpu_screen_probe", self.h, _ptr(q), _ptr(s), s.size, float(radius), int(workgroup), _ptr(out))
+        return out.astype(bool)
 
     def last_search_grid(self) -> int:
         return int(_call("lantern_gpu_last_search_grid", self.h))

@@ -2893,6 +2893,63 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
+// diagnostics: the stored int8 screen of slots [first, first + count) as the device holds it (tests/test_gpu_screen_rows.py)
+size_t lantern_gpu_export_screen(usearch_index_t h, size_t first, size_t count, int8_t *rows, float *meta, float *norms, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(count > SIZE_MAX - first) { FAIL(e, "lantern_gpu: slot range out of the index"); return 0; }
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return 0; }
+    if(first + count > ix->n) { FAIL(e, "lantern_gpu: slot range out of the index"); return 0; }
+    if(!ix->d_screen || !ix->d_screen_meta) return 0;  // no screen: nothing stored, nothing to export
+    const size_t srow = (size_t)screen_chunks_for(ix->chunks) * 16;
+    bool         ok = true;
+    if(count) {
+        if(rows) ok = ok && hipMemcpyAsync(rows, (const char *)ix->d_screen + first * srow, count * srow, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+        if(meta) ok = ok && hipMemcpyAsync(meta, ix->d_screen_meta + first, count * 8, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+        if(norms && ix->mcode == M_COS && ix->d_norm2)
+            ok = ok && hipMemcpyAsync(norms, ix->d_norm2 + first, count * 4, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+        ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
+    }
+    if(!ok) { FAIL(e, "lantern_gpu: HIP failure exporting the screen"); return 0; }
+    return srow;
+}
+LANTERN_ABI_CATCH(e)
+
+// diagnostics: one screened hop's verdicts, by the walk's own device function (screen_probe_kernel.hip)
+void lantern_gpu_screen_probe(usearch_index_t h, const void *query, const uint32_t *slots, size_t n, float radius, int workgroup,
+                              uint8_t *rejected, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(n > 64) { FAIL(e, "lantern_gpu: screen_probe takes at most 64 slots"); return; }
+    if(workgroup != 256 && workgroup != 512) { FAIL(e, "lantern_gpu: screen_probe workgroup must be 256 or 512"); return; }
+    if(!query || (n && (!slots || !rejected))) { FAIL(e, "lantern_gpu: null buffer"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    if(!ix->d_screen || !ix->d_screen_meta) { FAIL(e, "lantern_gpu: the index has no int8 screen"); return; }
+    if(n == 0) return;
+    for(size_t i = 0; i < n; ++i)
+        if(slots[ i ] >= ix->n) { FAIL(e, "lantern_gpu: slot out of range"); return; }
+    const size_t row = (size_t)ix->chunks * 16;
+    char        *buf = (char *)scratch(ix, kScratchCallIn, row + n * 4 + 64);
+    if(!buf) { FAIL(e, ix->err.c_str()); return; }
+    std::vector<uint32_t> padded((size_t)ix->chunks * 4);
+    pad_row(ix, query, usearch_scalar_f32_k, padded.data());
+    uint32_t *d_slots = (uint32_t *)(buf + row);
+    uint8_t  *d_out = (uint8_t *)(buf + row + n * 4);
+    bool      ok = hipMemcpyAsync(buf, padded.data(), row, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d_slots, slots, n * 4, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
+    ok = ok && launch_screen_probe(ix->mcode, ix->view(), (const uint4 *)buf, d_slots, (uint32_t)n, radius, workgroup, d_out, ix->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(rejected, d_out, n, hipMemcpyDeviceToHost, ix->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;
+    if(!ok) FAIL(e, "lantern_gpu: HIP failure in screen_probe");
+}
+LANTERN_ABI_CATCH_VOID(e)
+
 float lantern_gpu_last_gather_ms(usearch_index_t h, usearch_error_t *e)
 try {
     CLEAR(e);

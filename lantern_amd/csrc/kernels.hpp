@@ -227,6 +227,10 @@ hipError_t launch_fill_norms(int metric, const View &v, uint32_t first, uint32_t
 // the int8 screen rows and (s, r) of the f32 rows [first, first + count) (walk.hpp hop_distances_screened); norm2 != NULL (a cosine
 // index: the rows' cached rooted norms, filled before this on the same stream): (s / norm, rho) instead
 hipError_t launch_fill_screen(const View &v, uint32_t first, uint32_t count, uint4 *screen, float2 *meta, const float *norm2, hipStream_t stream);
+// diagnostics (screen_probe_kernel.hip): out[i] = 1 where hop_distances_screened rejects slots[i] (n <= 64) for `query` at `radius`,
+// run by one workgroup of `threads` (256 or 512); the view must have a screen
+hipError_t launch_screen_probe(int metric, const View &v, const uint4 *query, const uint32_t *slots, uint32_t n, float radius, int threads,
+                               uint8_t *out, hipStream_t stream);
 // out[i] = metric(query, row(slots[i]))
 hipError_t launch_gather(int metric, const View &v, const uint4 *query, const uint32_t *slots, uint32_t n, float *out,
                          hipStream_t stream);
