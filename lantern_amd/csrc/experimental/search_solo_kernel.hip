@@ -10,18 +10,18 @@ __global__ void __launch_bounds__(64, 1) k_search_solo(SearchArgs a)
 {
     const int lane = (int)(threadIdx.x & 63);
     SoloLds   s;
-    carve_solo(lgpu_smem, s, a.spec_cache, a.vis_slots);
+    carve_solo(lgpu_smem, s, a.spec_cache, a.frame.vis_slots);
     for(uint32_t i = (uint32_t)lane; i < (1u << a.spec_cache); i += 64) {
         s.tags[ i ] = EMPTY;
         s.stamps[ i ] = 0u;
     }
     uint32_t hop_ctr = 0;
-    for(uint32_t q = blockIdx.x; q < a.nq;) {
+    for(uint32_t q = blockIdx.x; q < a.frame.nq;) {
         uint32_t D = 0, E = 0;
         int      cnt = 0;
         if(a.view.n != 0) {
             SoloWalk<METRIC, G, CPL, RAGGED> w(a.view, s);
-            w.load_query(a.queries + (size_t)q * a.view.chunks);
+            w.load_query(a.frame.queries + (size_t)q * a.view.chunks);
             float          d0;
             const uint32_t start = w.descend(D, d0);
             cnt = w.template level0<PROF>(start, d0, (int)a.ef, D, E, hop_ctr, PROF ? a.phase_cycles : nullptr);
@@ -34,22 +34,22 @@ __global__ void __launch_bounds__(64, 1) k_search_solo(SearchArgs a)
             if((int)i < got) {
                 const uint64_t key = s.keys[ a.skip + i ];
                 const uint32_t slot = key_slot(key);
-                if(a.out_labels) a.out_labels[ o ] = a.labels[ slot ];
-                if(a.out_dists) a.out_dists[ o ] = key_dist(key);
-                if(a.out_slots) a.out_slots[ o ] = slot;
+                if(a.frame.out_labels) a.frame.out_labels[ o ] = a.frame.labels[ slot ];
+                if(a.frame.out_dists) a.frame.out_dists[ o ] = key_dist(key);
+                if(a.frame.out_slots) a.frame.out_slots[ o ] = slot;
             } else {
-                if(a.out_labels) a.out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
-                if(a.out_dists) a.out_dists[ o ] = __builtin_inff();
-                if(a.out_slots) a.out_slots[ o ] = EMPTY;
+                if(a.frame.out_labels) a.frame.out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
+                if(a.frame.out_dists) a.frame.out_dists[ o ] = __builtin_inff();
+                if(a.frame.out_slots) a.frame.out_slots[ o ] = EMPTY;
             }
         }
         uint32_t next = q + gridDim.x;
         if(lane == 0) {
-            if(a.out_counts) a.out_counts[ q ] = (uint32_t)got;
-            if(a.out_D) a.out_D[ q ] = D;
-            if(a.out_E) a.out_E[ q ] = E;
-            if(a.totals) { atomicAdd(&a.totals[ 0 ], (unsigned long long)D); atomicAdd(&a.totals[ 1 ], (unsigned long long)E); }
-            if(a.ticket) next = gridDim.x + atomicAdd(a.ticket, 1u);
+            if(a.frame.out_counts) a.frame.out_counts[ q ] = (uint32_t)got;
+            if(a.frame.out_D) a.frame.out_D[ q ] = D;
+            if(a.frame.out_E) a.frame.out_E[ q ] = E;
+            if(a.frame.totals) { atomicAdd(&a.frame.totals[ 0 ], (unsigned long long)D); atomicAdd(&a.frame.totals[ 1 ], (unsigned long long)E); }
+            if(a.frame.ticket) next = gridDim.x + atomicAdd(a.frame.ticket, 1u);
         }
         next = (uint32_t)__builtin_amdgcn_readfirstlane((int)next);
         if(a.done || a.done_flags) {
@@ -93,12 +93,12 @@ bool search_solo_supported(int metric, uint32_t chunks, uint32_t M, uint32_t M0,
         default: LGPU_LAUNCH_SOLO(MM, GG, 4) break;                                               \
     }
 
-// a.spec_cache = log2 of the list-cache entries, a.vis_slots = words of the LDS visited bitmap (a multiple of 4, >= ceil(n / 32))
+// a.spec_cache = log2 of the list-cache entries, a.frame.vis_slots = words of the LDS visited bitmap (a multiple of 4, >= ceil(n / 32))
 hipError_t launch_search_solo(int metric, const SearchArgs &a, int grid, hipStream_t stream)
 {
     if(!search_solo_supported(metric, a.view.chunks, a.view.M, a.view.M0, a.ef)) return hipErrorInvalidValue;
-    const size_t lds = search_solo_lds_bytes(a.spec_cache, a.vis_slots);
-    if(lds > 160 * 1024 || (size_t)a.vis_slots * 32 < a.view.n) return hipErrorInvalidValue;
+    const size_t lds = search_solo_lds_bytes(a.spec_cache, a.frame.vis_slots);
+    if(lds > 160 * 1024 || (size_t)a.frame.vis_slots * 32 < a.view.n) return hipErrorInvalidValue;
     const int  G_ = group_lanes_for(a.view.chunks), cpl = ((int)a.view.chunks + G_ - 1) / G_;
     const bool ragged = (int)a.view.chunks % G_ != 0;
     if(a.phase_cycles) {  // the diagnostic instantiation (lantern_gpu_spec_profile): f32 l2sq, 32-chunk rows (128-d)

@@ -188,7 +188,7 @@ static bool filtered_shape(Index *ix, bool exact, size_t k, size_t skip, size_t 
         while(vis_slots && filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots) > kFilteredLdsTarget)
             vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
         if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
-        a.vis_slots = vis_slots;
+        a.frame.vis_slots = vis_slots;
         lds = filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots);
     }
     return true;
@@ -226,13 +226,13 @@ static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, s
 {
     FilteredArgs a{};
     a.view = ix->view();
-    a.queries = d_q;
+    a.frame.queries = d_q;
     a.k = (uint32_t)k;
     a.skip = (uint32_t)skip;
-    a.labels = ix->d_labels;
-    a.out_labels = out.labels, a.out_dists = out.dists, a.out_slots = out.slots;
-    a.out_counts = out.counts, a.out_D = out.D, a.out_E = out.E;
-    a.totals = ix->d_totals;
+    a.frame.labels = ix->d_labels;
+    a.frame.out_labels = out.labels, a.frame.out_dists = out.dists, a.frame.out_slots = out.slots;
+    a.frame.out_counts = out.counts, a.frame.out_D = out.D, a.frame.out_E = out.E;
+    a.frame.totals = ix->d_totals;
     return a;
 }
 
@@ -244,13 +244,13 @@ struct EachTable
     size_t      bytes, descs_at, select_at;
 };
 
-// ONE launch of either kernel over a.nq queries, `a` shaped by filtered_shape: the grid, the launch slot (which orders the launch
+// ONE launch of either kernel over a.frame.nq queries, `a` shaped by filtered_shape: the grid, the launch slot (which orders the launch
 // after inserts and holds the walk's visited bitmaps), the per-query table if there is one, the ticket, the launch and its count.
 // Returns the grid; < 0 -> ix->err.
 static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, hipStream_t stream, const EachTable *tbl = nullptr)
 {
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
-    const int grid = search_grid(ix, a.nq, kFilteredWaves, kFilteredWaves * per_cu);
+    const int grid = search_grid(ix, a.frame.nq, kFilteredWaves, kFilteredWaves * per_cu);
     const int slot = acquire_search_slot(ix, stream, (size_t)grid);
     if(slot < 0) return -1;
     if(tbl) {
@@ -261,12 +261,12 @@ static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, h
             return -1;
         }
         a.descs = (const FilterDesc *)(d_tbl + tbl->descs_at);
-        a.select = (const uint32_t *)(d_tbl + tbl->select_at);
+        a.frame.qlist = (const uint32_t *)(d_tbl + tbl->select_at);
     }
-    a.bitmaps = ix->slot_bitmaps[ slot ];
-    a.bm_words = (uint32_t)ix->slot_words[ slot ];
-    a.undo_cap = vis_undo_cap();
-    a.ticket = next_ticket(ix, a.nq, grid, stream);
+    a.frame.bitmaps = ix->slot_bitmaps[ slot ];
+    a.frame.bm_words = (uint32_t)ix->slot_words[ slot ];
+    a.frame.undo_cap = vis_undo_cap();
+    a.frame.ticket = next_ticket(ix, a.frame.nq, grid, stream);
     const hipError_t e = exact ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
                                : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
     if(e != hipSuccess) {
@@ -301,7 +301,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     }
     const bool   exact = filter_takes_exact(ix, f, ef_sel);
     FilteredArgs a = filtered_args(ix, d_q, k, skip, out);
-    a.nq = (uint32_t)nq;
+    a.frame.nq = (uint32_t)nq;
     a.allow_bits = f->d_bits;
     a.allow_slots = f->d_slots;
     a.allow_count = (uint32_t)f->count;
@@ -328,7 +328,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
         if(!exact) ix->last_seeds[ 3 ] = (uint32_t)nq;
     }
     if(grid < 0) return false;
-    const uint32_t shape[ 6 ] = { exact ? 2u : 1u, (uint32_t)grid, a.exp, a.cand_cap, a.vis_slots, (uint32_t)lds };
+    const uint32_t shape[ 6 ] = { exact ? 2u : 1u, (uint32_t)grid, a.exp, a.cand_cap, a.frame.vis_slots, (uint32_t)lds };
     std::copy(std::begin(shape), std::end(shape), ix->last_filtered);
     ix->c_search_queries += nq;
     return true;
@@ -410,7 +410,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
         const bool ex = pass == 1;
         if((ex ? exact : walk).empty()) continue;
         FilteredArgs &a = ex ? ae : aw;
-        a.nq = (uint32_t)(ex ? exact : walk).size();
+        a.frame.nq = (uint32_t)(ex ? exact : walk).size();
         const EachTable t = ex ? EachTable{ h_tbl + off_desc, tbl_bytes - off_desc, 0, nq * sizeof(FilterDesc) } : EachTable{ h_tbl, off_sel_e, off_desc, 0 };
         if(filtered_launch(ix, ex, a, ex ? lds_e : lds_w, stream, &t) < 0) return false;
         launches += 1;

@@ -37,35 +37,21 @@ struct FilterDesc
 };
 
 // kernel arguments of both filtered kernels.  Fields are re-read from the kernarg segment at the points of a query that need them
-// (search_kernel.hpp "kernarg re-read").
+// (query_frame.hpp "kernarg re-read").
 struct FilteredArgs
 {
     View            view;
-    const uint4    *queries;     // [nq][chunks], zero padded
-    uint32_t        nq, k, skip;
+    FrameArgs       frame;       // (kernels.hpp; bitmaps, bm_words, undo_cap and vis_slots: walk only)
+    uint32_t        k, skip;
     uint32_t        exp;         // expansion = max(ef, k + skip): the capacity of `top` (walk) / k + skip (exact)
     uint32_t        cand_cap;    // C: the capacity of `next` (walk only; >= exp)
     const uint32_t *allow_bits;  // [words] the filter's bitmap
     const uint32_t *allow_slots; // [allow_count] the allowed slots, ascending (exact only)
     uint32_t        allow_count;
     uint32_t        rows_per_round;  // exact only: rows evaluated per round (2 per G-lane group)
-    const uint64_t *labels;      // [n]
-    uint64_t       *out_labels;  // [nq][k] or NULL
-    float          *out_dists;   // [nq][k] or NULL
-    uint32_t       *out_slots;   // [nq][k] or NULL
-    uint32_t       *out_counts;  // [nq] or NULL
-    uint64_t       *out_D;       // [nq] or NULL
-    uint64_t       *out_E;       // [nq] or NULL
-    uint32_t       *bitmaps;     // walk only: the launch slot's visited bitmaps + undo logs (SearchArgs::bitmaps)
-    uint32_t        bm_words;
-    uint32_t        undo_cap;
-    uint32_t        vis_slots;
-    unsigned long long *totals;  // [2] cumulative D, E or NULL
-    uint32_t       *ticket;      // zeroed before the launch, or NULL (static striding)
-    // the per-query form (descs != NULL; allow_* unused): `nq` counts the entries of `select`, every output row is indexed by the
-    // query a position selects, and that query's filter is descs[query]
+    // the per-query form (descs != NULL; allow_* unused): `frame.nq` counts the entries of the selection list `frame.qlist`, every
+    // output row is indexed by the query a position selects, and that query's filter is descs[query]
     const FilterDesc *descs;     // [queries of the call]
-    const uint32_t   *select;    // [nq] ticket position -> query
     // the seeded walk (per-query form only): > 0 = a query whose descriptor has count >= 1 starts from min(seeds, count) allowed rows
     // taken at even strides from the descriptor's slot list (search_filtered_kernel.hip "SEEDED"); 0 = off
     uint32_t          seeds;

@@ -17,11 +17,12 @@
 
 namespace lgpu {
 
-struct SearchArgs
+// What a persistent search workgroup does AROUND one query reads these fields (query_frame.hpp: pick, stage, bind, answer rows,
+// close).  SearchArgs and FilteredArgs (filter.hpp) each embed one as `frame`, so that the frame is written once.
+struct FrameArgs
 {
-    View            view;
     const uint4    *queries;   // [nq][chunks], zero padded
-    uint32_t        nq, k, ef, skip;
+    uint32_t        nq;
     const uint64_t *labels;    // [n]
     uint64_t       *out_labels;  // [nq][k] or NULL
     float          *out_dists;   // [nq][k] or NULL
@@ -36,6 +37,15 @@ struct SearchArgs
     unsigned long long *totals;  // [2] cumulative D, E (atomicAdd) or NULL
     uint32_t       *ticket;      // zeroed before the launch: queries beyond the first gridDim.x are handed out dynamically
                                  // (NULL = static striding); results do not depend on who runs a query
+    // the launches that serve a LIST of queries (k_search<.., EACH = true>; the per-query form of the filtered kernels); NULL otherwise
+    const uint32_t *qlist;       // [nq] ticket position -> query of the caller's batch; answers land in the row of that query
+};
+
+struct SearchArgs
+{
+    View            view;
+    FrameArgs       frame;
+    uint32_t        k, ef, skip;
     int             lds_list;    // keep the candidate list in LDS even when it fits wave 0's registers (LANTERN_GPU_LDS_LIST=1: the
                                  // round-1 walk, kept for A/B parity runs and for ef > 128)
     int             wide_rows;   // small batch: the four-rows-in-flight instantiation (k_search<.., ROWS = 4>)
@@ -49,7 +59,7 @@ struct SearchArgs
     uint32_t        adc_qchunks;    // 16-byte chunks of a (raw f32) query row
     unsigned long long *phase_cycles;  // diagnostics (lantern_gpu_search_phase_profile): [8] shader-clock cycles summed over the
     uint32_t       *done;        // NULL, or a counter in host-visible memory: +1 (system scope) per finished query, after its answers
-    uint32_t       *done_flags;  // NULL, or [nq] words in host-visible memory: done_flags[q] = 1 (system scope, release) once query q's answers
+    uint32_t       *done_flags;  // NULL, or [nq] words in host-visible memory: query q's word = 1 (system scope, release) once its answers
                                  // are written -- a host that keeps the answers in device-mapped memory hands each one on as ITS walk ends
                                  // instead of when the launch's longest walk does (lantern_gpu_search_batch_lane_notify)
     uint32_t       *touched;     // diagnostics (lantern_gpu_search_unique_rows; the instrumented instantiations only): [ceil(n / 32)] one
@@ -59,8 +69,7 @@ struct SearchArgs
     uint32_t        trace_cap;
     unsigned long long *screen_totals;  // [2] cumulative row evaluations and how many of them read the f32 row (the int8 screen:
                                         // lantern_gpu_search_screen_stats) of the launches whose view has a screen, or NULL
-    // the per-query-parameter form (k_search<.., EACH = true>, lantern_gpu_search_batch_params*); all three NULL / 0 otherwise
-    const uint32_t *qlist;       // [nq] the launch's queries as positions of the caller's batch; answers land in the row of that position
+    // the per-query-parameter form (k_search<.., EACH = true>, lantern_gpu_search_batch_params*; with frame.qlist); NULL / 0 otherwise
     const uint4    *qparams;     // [caller's batch] {k, expansion, skip, 0} by position; `k`, `skip` above are unused, `ef` is the list's largest expansion
     uint32_t        k_stride;    // width of an answer row
 };                               // launch's queries by phase: pop | list + visited | distances | merge | descent | whole query

@@ -1,10 +1,9 @@
 // screen_probe_kernel.hip -- diagnostics: the int8 screen's reject decision, made by walk.hpp's own
 // hop_distances_screened and exported (lantern_gpu_screen_probe).  One workgroup plays one hop of a walk whose list is full: it stages
-// the query as k_search does (the cached norm of a cosine query included), takes the caller's slots as the hop's new neighbours and the
+// the query with the search kernels' own piece (query_frame.hpp frame_stage: the cached norm of a cosine query included), takes the caller's slots as the hop's new neighbours and the
 // caller's radius as the key `worst`, and reports which keys the screen set to ~0.  Nothing here decides anything: the tests compare
 // the verdicts with tests/test_screen_bound*.py on the host.
-#include "kernels.hpp"
-#include "walk.hpp"
+#include "query_frame.hpp"
 
 namespace lgpu {
 
@@ -25,19 +24,11 @@ __global__ void __launch_bounds__(512) k_screen_probe(View v, const uint4 *query
         s.scal[ S_NSURV ] = 0;
         s.scal[ S_QN2 ] = 0;
     }
-    for(uint32_t i = tid; i < v.chunks; i += T) s.q[ i ] = query[ i ];
     for(uint32_t i = tid; i < n; i += T) {
         s.newids[ i ] = slots[ i ];
         s.newkeys[ i ] = 0;  // a survivor's key is left alone by the screen
     }
-    __syncthreads();
-    if(kCachedNorms<METRIC>) {  // (k_search: ||query|| once per query, by the chain every row's norm took)
-        if(tid < G) {
-            const float qn = group_norm<METRIC, G>(s.q, (int)v.chunks, tid);
-            if(tid == G - 1) s.scal[ S_QN2 ] = __float_as_int(qn);
-        }
-        __syncthreads();
-    }
+    frame_stage<METRIC, G>(tid, T, s, query, 0, v.chunks);  // (its barriers cover the writes above)
     const float qn2 = __int_as_float(s.scal[ S_QN2 ]);
     (void)hop_distances_screened<METRIC, G, 2>(v, s, (int)n, make_key(radius, 0u), qn2);  // (ends in a barrier)
     for(uint32_t i = tid; i < n; i += T) out[ i ] = s.newkeys[ i ] == ~0ull ? 1 : 0;

@@ -71,13 +71,15 @@ __device__ __forceinline__ void adc_build_table(float *lut, const float *centers
 // a batch walks alone on its CU whatever the batch size: the walk that is fastest alone is the one to run.
 // (SPEC 2 = the lone-query shape.  The two-nodes-per-round form of walk_twin.hpp was measured here too -- 1.98 -> 1.65 M queries/s at
 // 96 subvectors -- and is not instantiated.)
-// EACH: the per-query-parameter form, as k_search's (search_kernel.hpp): the launch's queries come from SearchArgs::qlist, every
+// EACH: the per-query-parameter form, as k_search's (search_kernel.hpp): the launch's queries come from FrameArgs::qlist, every
 // query's k, expansion and skip from its row of SearchArgs::qparams, answer rows are k_stride wide.
+// The frame around the walk -- pick, bind, answer rows, close -- is query_frame.hpp's; the staging is this kernel's own (the raw
+// query row, the table, and |query| by the chain of the query's own width).
 template <int METRIC, int KPL, int SPEC = 0, bool EACH = false>
 __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(SearchArgs)
 {
-    // (arguments are re-read from the kernarg segment where a query needs them, as in k_search -- search_kernel.hpp: kept live
-    // across the persistent loop they cost the hop loop ~120 scalar-register spill reloads)
+    // (arguments are re-read from the kernarg segment where a query needs them -- query_frame.hpp: kept live across the
+    // persistent loop they cost the hop loop ~120 scalar-register spill reloads)
     constexpr int G = 8;  // rows are at most 8 chunks (128 codes)
     const int     tid = threadIdx.x, T = blockDim.x;
     WalkLds       s;
@@ -87,31 +89,28 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
         const KernargBytes ka = kernarg_opaque();
         lut_chunks = LGPU_VIEW_ARG(ka, SearchArgs, chunks) * 16 * ADC_LUT_STRIDE / 4;
         unsigned char *end = carve_walk(lgpu_smem, s, lut_chunks + LGPU_SEARCH_ARG(ka, adc_qchunks), LGPU_SEARCH_ARG(ka, ef), LGPU_VIEW_ARG(ka, SearchArgs, M0),
-                                        LGPU_SEARCH_ARG(ka, vis_slots));  // s.q = the table, then the raw query row
+                                        LGPU_FRAME_ARG(ka, SearchArgs, vis_slots));  // s.q = the table, then the raw query row
         if constexpr(SPEC != 0) carve_spec(end, sc, LGPU_VIEW_ARG(ka, SearchArgs, M0), LGPU_SEARCH_ARG(ka, spec_prefetch), LGPU_SEARCH_ARG(ka, spec_cache));
         else (void)end;
     }
     float *const       lut = (float *)s.q;
     const uint4 *const rawq4 = s.q + lut_chunks;
     const float *const rawq = (const float *)rawq4;
-    for(uint32_t pos = blockIdx.x; pos < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
-        uint32_t q = pos, each_k = 0, each_ef = 0, each_skip = 0;
+    for(uint32_t pos = blockIdx.x; pos < LGPU_FRAME_ARG(kernarg_opaque(), SearchArgs, nq);) {
+        uint32_t    q = pos;
+        QueryParams each{};
         if constexpr(EACH) {
             const KernargBytes ka = kernarg_opaque();
-            const uint32_t     upos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
-            q = ((ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qlist))[ upos ];
-            const ConstWords row = (ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qparams) + (size_t)q * 4;
-            each_k = row[ 0 ];
-            each_ef = row[ 1 ];
-            each_skip = row[ 2 ];
+            q = frame_query<SearchArgs, true>(ka, pos);
+            each = query_params(ka, q);
         }
         uint32_t D = 0, E = 0;
         int      cnt = 0;
-        if(!EACH || each_k != 0) {  // (a query that wants no rows needs no table)
+        if(!EACH || each.k != 0) {  // (a query that wants no rows needs no table)
             const KernargBytes ka = kernarg_opaque();
             const uint32_t     S = LGPU_SEARCH_ARG(ka, adc_S), C = LGPU_SEARCH_ARG(ka, adc_C), subdim = LGPU_SEARCH_ARG(ka, adc_subdim),
                            sub_floats = ((subdim + 3) / 4) * 4, qchunks = LGPU_SEARCH_ARG(ka, adc_qchunks), S16 = LGPU_VIEW_ARG(ka, SearchArgs, chunks) * 16;
-            const uint4 *queries = LGPU_SEARCH_ARG(ka, queries);
+            const uint4 *queries = LGPU_FRAME_ARG(ka, SearchArgs, queries);
             for(uint32_t i = tid; i < qchunks; i += T) ((uint4 *)rawq4)[ i ] = queries[ (size_t)q * qchunks + i ];
             __syncthreads();
             // entry 0 of the padding rows is +0.0
@@ -136,12 +135,10 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
             const KernargBytes ka = kernarg_opaque();
             View               v;
             LGPU_LOAD_VIEW(v, ka, SearchArgs)
-            const uint32_t bm_words = LGPU_SEARCH_ARG(ka, bm_words);
-            uint32_t      *bitmap = LGPU_SEARCH_ARG(ka, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
-            s.undo = bitmap + bm_words;
-            s.undo_cap = LGPU_SEARCH_ARG(ka, undo_cap);
-            const int      ef = EACH ? (int)each_ef : (int)LGPU_SEARCH_ARG(ka, ef);
-            if(v.n != 0 && (!EACH || each_k != 0)) {
+            uint32_t        bm_words;
+            uint32_t *const bitmap = frame_bind<SearchArgs>(ka, s, bm_words);
+            const int       ef = EACH ? (int)each.ef : (int)LGPU_SEARCH_ARG(ka, ef);
+            if(v.n != 0 && (!EACH || each.k != 0)) {
                 if constexpr(SPEC != 0) {
                     static_assert(SPEC == 0 || KPL > 0, "the latency-bound walk keeps its list in registers");
                     const uint32_t start = greedy_descent_spec<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
@@ -154,49 +151,10 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
             }
         }
         const KernargBytes kb = kernarg_opaque();
-        const uint32_t     k = EACH ? each_k : LGPU_SEARCH_ARG(kb, k), skip = EACH ? each_skip : LGPU_SEARCH_ARG(kb, skip);
+        const uint32_t     k = EACH ? each.k : LGPU_SEARCH_ARG(kb, k), skip = EACH ? each.skip : LGPU_SEARCH_ARG(kb, skip);
         const uint32_t     kw = EACH ? LGPU_SEARCH_ARG(kb, k_stride) : k;  // the width of an answer row
-        const uint64_t    *labels = LGPU_SEARCH_ARG(kb, labels);
-        uint64_t          *out_labels = LGPU_SEARCH_ARG(kb, out_labels);
-        float             *out_dists = LGPU_SEARCH_ARG(kb, out_dists);
-        uint32_t          *out_slots = LGPU_SEARCH_ARG(kb, out_slots);
-        int                got = cnt - (int)skip;
-        got = got < 0 ? 0 : (got > (int)k ? (int)k : got);
-        for(uint32_t i = tid; i < kw; i += T) {
-            const size_t o = (size_t)q * kw + i;
-            if((int)i < got) {
-                const uint64_t key = s.keys[ skip + i ];
-                const uint32_t slot = key_slot(key);
-                if(out_labels) out_labels[ o ] = labels[ slot ];
-                if(out_dists) out_dists[ o ] = key_dist(key);
-                if(out_slots) out_slots[ o ] = slot;
-            } else {
-                if(out_labels) out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
-                if(out_dists) out_dists[ o ] = __builtin_inff();
-                if(out_slots) out_slots[ o ] = EMPTY;
-            }
-        }
-        uint32_t *const done = LGPU_SEARCH_ARG(kb, done);
-        if(tid == 0) {
-            uint32_t *const           out_counts = LGPU_SEARCH_ARG(kb, out_counts);
-            uint64_t *const           out_D = LGPU_SEARCH_ARG(kb, out_D), *const out_E = LGPU_SEARCH_ARG(kb, out_E);
-            unsigned long long *const totals = LGPU_SEARCH_ARG(kb, totals);
-            uint32_t *const           ticket = LGPU_SEARCH_ARG(kb, ticket);
-            if(out_counts) out_counts[ q ] = (uint32_t)got;
-            if(out_D) out_D[ q ] = D;
-            if(out_E) out_E[ q ] = E;
-            if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
-            s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(pos + gridDim.x);
-        }
-        __syncthreads();
-        uint32_t *const done_flags = LGPU_SEARCH_ARG(kb, done_flags);
-        if(tid == 0 && (done || done_flags)) {
-            __threadfence_system();
-            if(done) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            if(done_flags) __hip_atomic_store(&done_flags[ q ], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        pos = (uint32_t)s.scal[ S_POS ];
-        __syncthreads();
+        const int          got = frame_answer_rows<SearchArgs>(tid, T, kb, s, q, cnt, k, skip, kw);
+        pos = frame_close<SearchArgs>(tid, kb, s, q, pos, got, D, E);
     }
 }
 
@@ -210,7 +168,7 @@ hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int gri
     if(a.view.chunks == 0 || a.view.chunks > 8 || a.adc_C == 0 || a.adc_C > (uint32_t)ADC_LUT_STRIDE) return hipErrorInvalidValue;
     const int kpl = a.lds_list ? 0 : a.ef <= 64 ? 1 : a.ef <= 128 ? 2 : 0;
     if(a.spec && (kpl == 0 || waves < 4 || waves > 11 || a.view.M0 > 64 || a.view.M0 < 2)) return hipErrorInvalidValue;
-    const size_t lds = search_adc_lds_bytes(a.view.chunks, a.adc_qchunks, a.ef, a.view.M0, a.vis_slots) + (a.spec ? spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache) : 0);
+    const size_t lds = search_adc_lds_bytes(a.view.chunks, a.adc_qchunks, a.ef, a.view.M0, a.frame.vis_slots) + (a.spec ? spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache) : 0);
 #define LGPU_ADC2(MM, KK, SS, EE)                                                                                               \
     {                                                                                                                           \
         static LdsAttrCache attr_;        \

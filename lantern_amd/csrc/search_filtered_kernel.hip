@@ -1,5 +1,6 @@
 // search_filtered_kernel.hip -- filtered k-NN search over an allow-set of slots (filter.hpp).  Two kernels, one workgroup per query,
-// persistent over the batch (work handed out by ticket), kernel arguments re-read from the kernarg segment (search_kernel.hpp):
+// persistent over the batch (work handed out by ticket); the frame around a query's walk is query_frame.hpp's (kernel arguments
+// re-read from the kernarg segment, the query picked, staged, answered and closed there):
 //
 //  * k_search_filtered: the base-layer walk with TWO lists in LDS, both ordered by the walk's total order (distance, slot):
 //      top  -- at most `exp` keys, ALLOWED slots only (the answer is top[skip, skip + k));
@@ -284,71 +285,7 @@ __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, ui
 
 #define LGPU_FARG(base, field) LGPU_KARG(base, decltype(FilteredArgs::field), offsetof(FilteredArgs, field))
 
-// the answer of one query: top[skip, skip + k) of the list in s.keys, the unused tail label 0 / +inf / EMPTY; counts, D, E; the ticket.
-// `pos` is the ticket position the workgroup drew and `q` the query it stands for (the same number unless the launch has a selection
-// list): rows are written by q, the next position is drawn after pos.
-__device__ __forceinline__ void write_answers(WalkLds &s, uint32_t q, uint32_t pos, int cnt, uint32_t D, uint32_t E)
-{
-    const int          tid = threadIdx.x, T = blockDim.x;
-    const KernargBytes kb = kernarg_opaque();
-    const uint32_t     k = LGPU_FARG(kb, k), skip = LGPU_FARG(kb, skip);
-    const uint64_t    *labels = LGPU_FARG(kb, labels);
-    uint64_t          *out_labels = LGPU_FARG(kb, out_labels);
-    float             *out_dists = LGPU_FARG(kb, out_dists);
-    uint32_t          *out_slots = LGPU_FARG(kb, out_slots);
-    int                got = cnt - (int)skip;
-    got = got < 0 ? 0 : (got > (int)k ? (int)k : got);
-    for(uint32_t i = tid; i < k; i += T) {
-        const size_t o = (size_t)q * k + i;
-        if((int)i < got) {
-            const uint64_t key = s.keys[ skip + i ];
-            const uint32_t slot = key_slot(key);
-            if(out_labels) out_labels[ o ] = labels[ slot ];
-            if(out_dists) out_dists[ o ] = key_dist(key);
-            if(out_slots) out_slots[ o ] = slot;
-        } else {
-            if(out_labels) out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
-            if(out_dists) out_dists[ o ] = __builtin_inff();
-            if(out_slots) out_slots[ o ] = EMPTY;
-        }
-    }
-    if(tid == 0) {
-        uint32_t *const           out_counts = LGPU_FARG(kb, out_counts);
-        uint64_t *const           out_D = LGPU_FARG(kb, out_D), *const out_E = LGPU_FARG(kb, out_E);
-        unsigned long long *const totals = LGPU_FARG(kb, totals);
-        uint32_t *const           ticket = LGPU_FARG(kb, ticket);
-        if(out_counts) out_counts[ q ] = (uint32_t)got;
-        if(out_D) out_D[ q ] = D;
-        if(out_E) out_E[ q ] = E;
-        if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
-        s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(pos + gridDim.x);
-    }
-    __syncthreads();
-}
-
-// the query row into LDS, and ||query||^2 for the cosine metrics (as k_search)
-template <int METRIC, int G> __device__ __forceinline__ void load_query(WalkLds &s, const uint4 *queries, uint32_t q, uint32_t chunks)
-{
-    const int tid = threadIdx.x, T = blockDim.x;
-    for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = queries[ (size_t)q * chunks + i ];
-    __syncthreads();
-    if(kCachedNorms<METRIC>) {
-        if(tid < G) {
-            const float qn = group_norm<METRIC, G>(s.q, (int)chunks, tid);
-            if(tid == G - 1) s.scal[ S_QN2 ] = __float_as_int(qn);
-        }
-        __syncthreads();
-    }
-}
-
-// the query a workgroup serves at ticket position `pos`: pos itself, or -- the per-query form -- the entry of the launch's selection list
-template <bool EACH> __device__ __forceinline__ uint32_t query_at(uint32_t pos)
-{
-    if constexpr(EACH) return (uint32_t)__builtin_amdgcn_readfirstlane((int)LGPU_FARG(kernarg_opaque(), select)[ pos ]);
-    else return pos;
-}
-
-// EACH: the per-query form.  The launch serves the queries of its selection list (FilteredArgs::select), and the filter of a query is
+// EACH: the per-query form.  The launch serves the queries of its selection list (FrameArgs::qlist), and the filter of a query is
 // its descriptor (FilteredArgs::descs[q]), read from memory anew for every query at the point that needs it: a workgroup serves many
 // queries and carries nothing of one query's filter into the next.  A descriptor with count 0 (and no unfiltered mark) is an empty
 // filter: no walk, the empty answer.
@@ -357,26 +294,25 @@ template <int METRIC, int G, bool EACH, bool SEEDED = false>
 __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
 {
     static_assert(EACH || !SEEDED, "the seeded walk is instantiated in the per-query form only");
+    const int tid = threadIdx.x, T = blockDim.x;
     WalkLds   s;
     uint64_t *nx, *nx2;
     {
         const KernargBytes ka = kernarg_opaque();
         carve_filtered(lgpu_smem, s, nx, nx2, LGPU_VIEW_ARG(ka, FilteredArgs, chunks), LGPU_FARG(ka, exp), LGPU_FARG(ka, cand_cap),
-                       LGPU_VIEW_ARG(ka, FilteredArgs, M0), LGPU_FARG(ka, vis_slots));
+                       LGPU_VIEW_ARG(ka, FilteredArgs, M0), LGPU_FRAME_ARG(ka, FilteredArgs, vis_slots));
     }
-    for(uint32_t pos = blockIdx.x; pos < LGPU_FARG(kernarg_opaque(), nq);) {
-        const uint32_t q = query_at<EACH>(pos);
+    for(uint32_t pos = blockIdx.x; pos < LGPU_FRAME_ARG(kernarg_opaque(), FilteredArgs, nq);) {
+        const uint32_t q = frame_query<FilteredArgs, EACH>(kernarg_opaque(), pos);
         uint32_t       D = 0, E = 0;
         int            cnt = 0;
         {
             const KernargBytes ka = kernarg_opaque();
             View               v;
             LGPU_LOAD_VIEW(v, ka, FilteredArgs)
-            const uint32_t bm_words = LGPU_FARG(ka, bm_words);
-            uint32_t      *bitmap = LGPU_FARG(ka, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
-            s.undo = bitmap + bm_words;
-            s.undo_cap = LGPU_FARG(ka, undo_cap);
-            load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
+            uint32_t        bm_words;
+            uint32_t *const bitmap = frame_bind<FilteredArgs>(ka, s, bm_words);
+            frame_stage<METRIC, G>(tid, T, s, LGPU_FRAME_ARG(ka, FilteredArgs, queries), q, v.chunks);
             const uint32_t *allow;
             bool            any = true;
             const uint32_t *seed_slots = nullptr;
@@ -404,9 +340,10 @@ __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
                                                                      (int)LGPU_FARG(ka, cand_cap), D, E, seed_slots, seed_count, S);
             }
         }
-        write_answers(s, q, pos, cnt, D, E);
-        pos = (uint32_t)s.scal[ S_POS ];
-        __syncthreads();
+        const KernargBytes kb = kernarg_opaque();
+        const uint32_t     k = LGPU_FARG(kb, k);
+        const int          got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, k, LGPU_FARG(kb, skip), k);
+        pos = frame_close<FilteredArgs>(tid, kb, s, q, pos, got, D, E);
     }
 }
 
@@ -421,15 +358,15 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
         const KernargBytes ka = kernarg_opaque();
         carve_walk(lgpu_smem, s, LGPU_VIEW_ARG(ka, FilteredArgs, chunks), LGPU_FARG(ka, exp), LGPU_FARG(ka, rows_per_round), 0);
     }
-    for(uint32_t pos = blockIdx.x; pos < LGPU_FARG(kernarg_opaque(), nq);) {
-        const uint32_t q = query_at<EACH>(pos);
+    for(uint32_t pos = blockIdx.x; pos < LGPU_FRAME_ARG(kernarg_opaque(), FilteredArgs, nq);) {
+        const uint32_t q = frame_query<FilteredArgs, EACH>(kernarg_opaque(), pos);
         int            cnt = 0;
         uint32_t       D = 0;
         {
             const KernargBytes ka = kernarg_opaque();
             View               v;
             LGPU_LOAD_VIEW(v, ka, FilteredArgs)
-            load_query<METRIC, G>(s, LGPU_FARG(ka, queries), q, v.chunks);
+            frame_stage<METRIC, G>(tid, T, s, LGPU_FRAME_ARG(ka, FilteredArgs, queries), q, v.chunks);
             const float     qn2 = __int_as_float(s.scal[ S_QN2 ]);
             const uint32_t *slots;
             int             count;
@@ -483,56 +420,46 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
             }
             D = (uint32_t)count;
         }
-        write_answers(s, q, pos, cnt, D, 0);
-        pos = (uint32_t)s.scal[ S_POS ];
-        __syncthreads();
+        const KernargBytes kb = kernarg_opaque();
+        const uint32_t     k = LGPU_FARG(kb, k);
+        const int          got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, k, LGPU_FARG(kb, skip), k);
+        pos = frame_close<FilteredArgs>(tid, kb, s, q, pos, got, D, 0);
     }
 }
 
-#define LGPU_LAUNCH_FILTERED(KERNEL, EACH_, LDS_, MM, GG)                                                   \
-    {                                                                                                       \
-        static LdsAttrCache attr_;                                                                          \
-        ensure_dynamic_lds((const void *)KERNEL<MM, GG, EACH_>, LDS_, attr_);                               \
-        hipLaunchKernelGGL((KERNEL<MM, GG, EACH_>), dim3(grid), dim3(64 * waves), LDS_, stream, a);         \
+// one instantiation KERNEL<MM, GG, ...>: opt it in to its dynamic LDS size, then launch
+#define LGPU_LAUNCH_FILTERED(KERNEL, LDS_, MM, GG, ...)                                                              \
+    {                                                                                                                \
+        static LdsAttrCache attr_;                                                                                   \
+        ensure_dynamic_lds((const void *)KERNEL<MM, GG, __VA_ARGS__>, LDS_, attr_);                                  \
+        hipLaunchKernelGGL((KERNEL<MM, GG, __VA_ARGS__>), dim3(grid), dim3(64 * waves), LDS_, stream, a);            \
     }
 
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
-    const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.vis_slots);
-    if(a.seeds) {
-        if(!a.descs) return hipErrorInvalidValue;  // the seeded walk exists in the per-query form only (filter.hip builds the table)
-#define CALL(MM, GG)                                                                                        \
-    {                                                                                                       \
-        static LdsAttrCache attr_;                                                                          \
-        ensure_dynamic_lds((const void *)k_search_filtered<MM, GG, true, true>, lds, attr_);                \
-        hipLaunchKernelGGL((k_search_filtered<MM, GG, true, true>), dim3(grid), dim3(64 * waves), lds, stream, a); \
+    const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.frame.vis_slots);
+    if(a.seeds && !a.descs) return hipErrorInvalidValue;  // the seeded walk exists in the per-query form only (filter.hip builds the table)
+#define CALL(MM, GG)                                                                   \
+    {                                                                                  \
+        if(a.seeds) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true, true)   \
+        else if(a.descs) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true)    \
+        else LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, false)               \
     }
-        LGPU_DISPATCH(metric, a.view.chunks, CALL);
+    LGPU_DISPATCH(metric, a.view.chunks, CALL);
 #undef CALL
-    } else if(a.descs) {
-#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, true, lds, MM, GG)
-        LGPU_DISPATCH(metric, a.view.chunks, CALL);
-#undef CALL
-    } else {
-#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_filtered, false, lds, MM, GG)
-        LGPU_DISPATCH(metric, a.view.chunks, CALL);
-#undef CALL
-    }
     return hipGetLastError();
 }
 
 hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_exact_lds_bytes(a.view.chunks, a.exp, a.rows_per_round);
-    if(a.descs) {
-#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, true, lds, MM, GG)
-        LGPU_DISPATCH(metric, a.view.chunks, CALL);
-#undef CALL
-    } else {
-#define CALL(MM, GG) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, false, lds, MM, GG)
-        LGPU_DISPATCH(metric, a.view.chunks, CALL);
-#undef CALL
+#define CALL(MM, GG)                                                                   \
+    {                                                                                  \
+        if(a.descs) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG, true)    \
+        else LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG, false)          \
     }
+    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+#undef CALL
     return hipGetLastError();
 }
 

@@ -20,6 +20,7 @@
 #include "experimental/walk_twin.hpp"
 #endif
 #include "dispatch.hpp"
+#include "query_frame.hpp"
 
 namespace lgpu {
 
@@ -27,18 +28,7 @@ namespace lgpu {
 // ROWS = 4 is the SMALL-BATCH shape: when the batch cannot fill six workgroups per CU anyway (<= four 4-wave workgroups per
 // CU), every workgroup keeps four rows per group in flight instead of two and may use 128 VGPRs (four waves per SIMD): a
 // CU's fetch rate is set by the bytes it has in flight, and at 1024 queries x 768-d the two-row shape left it at ~60 %.
-// Kernel arguments are RE-READ from the kernarg segment at the two points of a query that need them (before the walk: the
-// view, the query pointer, ef; after it: the output pointers) through a pointer the compiler cannot see through.  Left to
-// itself it loads all ~45 argument dwords once and keeps them live across the persistent loop -- over the hop loop, which
-// already needs ~60 scalars -- and pays with ~60 scalar-register spill reloads per hop; a dozen scalar loads per QUERY are free.
-typedef const __attribute__((address_space(4))) unsigned char *KernargBytes;
-__device__ __forceinline__ KernargBytes kernarg_opaque()
-{
-    KernargBytes p = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return p;
-}
-#define LGPU_KARG(base, T, ...) (*(const __attribute__((address_space(4))) T *)((base) + (__VA_ARGS__)))
+// (Kernel arguments are re-read from the kernarg segment at the points of a query that need them: query_frame.hpp says why.)
 #define LGPU_SEARCH_ARG(base, field) LGPU_KARG(base, decltype(SearchArgs::field), offsetof(SearchArgs, field))
 #define LGPU_VIEW_ARG(base, STRUCT, field) LGPU_KARG(base, decltype(View::field), offsetof(STRUCT, view) + offsetof(View, field))
 #define LGPU_LOAD_VIEW(v, base, STRUCT)             \
@@ -66,15 +56,22 @@ __device__ __forceinline__ KernargBytes kernarg_opaque()
         v.pq_row_bytes = LGPU_VIEW_ARG(base, STRUCT, pq_row_bytes); \
     }
 
+// a query's row of SearchArgs::qparams (wave-uniform: q came through the scalar cache, and so does the row)
+struct QueryParams { uint32_t k, ef, skip; };
+__device__ __forceinline__ QueryParams query_params(KernargBytes ka, uint32_t q)
+{
+    const ConstWords row = (ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qparams) + (size_t)q * 4;
+    return QueryParams{ row[ 0 ], row[ 1 ], row[ 2 ] };
+}
+
 // SPEC: the latency-bound walk of walk_spec.hpp -- 1: every wave evaluates rows and waves 0..2 carry the roles on top (the
 // small-batch shape, four waves); 2: three dedicated role waves + row waves (the lone-query shape, 3 + 8 waves); 3: the same
 // shape with two nodes per round, the second one speculative (walk_twin.hpp).
 // EACH: the per-query-parameter form (search_each_kernel.hip, search_each_spec_kernel.hip).  The launch serves the queries of a list
-// (SearchArgs::qlist: the ticket hands out list positions, the answers land in the row of the query a position names) and every query
+// (FrameArgs::qlist: the ticket hands out list positions, the answers land in the row of the query a position names) and every query
 // brings its own k, expansion and skip in a 16-byte row {k, expansion, skip, 0} of SearchArgs::qparams, read through the scalar cache
 // once the workgroup has its query.  The LDS carve is the launch's (SearchArgs::ef = the largest expansion of the list); the walk runs
 // with the query's own expansion, the answer rows are k_stride wide.  k = 0: no walk, the empty answer.
-typedef const __attribute__((address_space(4))) uint32_t *ConstWords;
 template <int METRIC, int G, bool PROF = false, int ROWS = 2, int KPL = 1, int SPEC = 0, bool EACH = false>
 #ifndef LGPU_SEARCH_MIN_BLOCKS_COS
 #define LGPU_SEARCH_MIN_BLOCKS_COS 6
@@ -89,23 +86,20 @@ k_search(SearchArgs)
     {
         const KernargBytes ka = kernarg_opaque();
         unsigned char     *end = carve_walk(lgpu_smem, s, LGPU_VIEW_ARG(ka, SearchArgs, chunks), LGPU_SEARCH_ARG(ka, ef), LGPU_VIEW_ARG(ka, SearchArgs, M0),
-                                            LGPU_SEARCH_ARG(ka, vis_slots));
+                                            LGPU_FRAME_ARG(ka, SearchArgs, vis_slots));
         if constexpr(SPEC != 0) carve_spec(end, sc, LGPU_VIEW_ARG(ka, SearchArgs, M0), LGPU_SEARCH_ARG(ka, spec_prefetch), LGPU_SEARCH_ARG(ka, spec_cache), SPEC == 3 ? 1u : 0u);
         else (void)end;
     }
     // the int8 screen of the f32 l2sq and cosine walks over rows of >= 128 chunks (walk.hpp hop_distances_screened); used iff the view
     // has one
     constexpr bool SCREEN = LGPU_SCREEN && (METRIC == M_L2SQ || METRIC == M_COS) && G == 64 && !PROF && SPEC == 0 && KPL > 0;
-    for(uint32_t pos = blockIdx.x; pos < LGPU_SEARCH_ARG(kernarg_opaque(), nq);) {
-        uint32_t q = pos, each_k = 0, each_ef = 0, each_skip = 0;
-        if constexpr(EACH) {  // (pos comes out of LDS: made wave-uniform, the list entry and the parameter row are scalar loads)
+    for(uint32_t pos = blockIdx.x; pos < LGPU_FRAME_ARG(kernarg_opaque(), SearchArgs, nq);) {
+        uint32_t    q = pos;
+        QueryParams each{};
+        if constexpr(EACH) {
             const KernargBytes ka = kernarg_opaque();
-            const uint32_t     upos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
-            q = ((ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qlist))[ upos ];
-            const ConstWords row = (ConstWords)(uintptr_t)LGPU_SEARCH_ARG(ka, qparams) + (size_t)q * 4;
-            each_k = row[ 0 ];
-            each_ef = row[ 1 ];
-            each_skip = row[ 2 ];
+            q = frame_query<SearchArgs, true>(ka, pos);
+            each = query_params(ka, q);
         }
         uint32_t D = 0, E = 0;
         int      cnt = 0;
@@ -123,21 +117,10 @@ k_search(SearchArgs)
                     s.scal[ S_NREJ ] = 0;
                 }
             }
-            const uint32_t chunks = v.chunks, bm_words = LGPU_SEARCH_ARG(ka, bm_words);
-            uint32_t      *bitmap = LGPU_SEARCH_ARG(ka, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
-            s.undo = bitmap + bm_words;
-            s.undo_cap = LGPU_SEARCH_ARG(ka, undo_cap);
-            const uint4   *queries = LGPU_SEARCH_ARG(ka, queries);
-            const int      ef = EACH ? (int)each_ef : (int)LGPU_SEARCH_ARG(ka, ef);
-            for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = queries[ (size_t)q * chunks + i ];
-            __syncthreads();
-            if(kCachedNorms<METRIC>) {  // ||query||^2 once per query, by the chain Acc<M_COS> would run for every row
-                if(tid < G) {
-                    const float qn = group_norm<METRIC, G>(s.q, (int)chunks, tid);
-                    if(tid == G - 1) s.scal[ S_QN2 ] = __float_as_int(qn);
-                }
-                __syncthreads();
-            }
+            uint32_t        bm_words;
+            uint32_t *const bitmap = frame_bind<SearchArgs>(ka, s, bm_words);
+            const int       ef = EACH ? (int)each.ef : (int)LGPU_SEARCH_ARG(ka, ef);
+            frame_stage<METRIC, G>(tid, T, s, LGPU_FRAME_ARG(ka, SearchArgs, queries), q, v.chunks);
             if constexpr(PROF) {
                 t_q = (unsigned long long)clock64();
                 s.touched = LGPU_SEARCH_ARG(ka, touched);
@@ -146,7 +129,7 @@ k_search(SearchArgs)
                 s.trace = tr ? tr + (size_t)q * s.trace_cap : nullptr;
                 s.trace_count = tr ? LGPU_SEARCH_ARG(ka, trace_count) + q : nullptr;
             }
-            if(v.n != 0 && (!EACH || each_k != 0)) {
+            if(v.n != 0 && (!EACH || each.k != 0)) {
                 uint32_t start;
                 if constexpr(SPEC != 0) start = greedy_descent_spec<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
                 else start = greedy_descent<METRIC, G, PROF>(v, s, v.entry, v.max_level, 0, D);
@@ -174,64 +157,11 @@ k_search(SearchArgs)
                     if(tid == 0 ? (i != 4 || pc[ 4 ] != 0) : (i == 4 && pc[ 4 ] != 0)) atomicAdd(&phase_cycles[ i ], pc[ i ]);
             }
         }
-        const uint32_t  k = EACH ? each_k : LGPU_SEARCH_ARG(kb, k), skip = EACH ? each_skip : LGPU_SEARCH_ARG(kb, skip);
-        const uint32_t  kw = EACH ? LGPU_SEARCH_ARG(kb, k_stride) : k;  // the width of an answer row
-        const uint64_t *labels = LGPU_SEARCH_ARG(kb, labels);
-        uint64_t       *out_labels = LGPU_SEARCH_ARG(kb, out_labels);
-        float          *out_dists = LGPU_SEARCH_ARG(kb, out_dists);
-        uint32_t       *out_slots = LGPU_SEARCH_ARG(kb, out_slots);
-        int             got = cnt - (int)skip;
-        got = got < 0 ? 0 : (got > (int)k ? (int)k : got);
-        for(uint32_t i = tid; i < kw; i += T) {
-            const size_t o = (size_t)q * kw + i;
-            if((int)i < got) {
-                const uint64_t key = s.keys[ skip + i ];
-                const uint32_t slot = key_slot(key);
-                if(out_labels) out_labels[ o ] = labels[ slot ];
-                if(out_dists) out_dists[ o ] = key_dist(key);
-                if(out_slots) out_slots[ o ] = slot;
-            } else {
-                if(out_labels) out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
-                if(out_dists) out_dists[ o ] = __builtin_inff();
-                if(out_slots) out_slots[ o ] = EMPTY;
-            }
-        }
-        if(tid == 0) {
-            uint32_t *const           out_counts = LGPU_SEARCH_ARG(kb, out_counts);
-            uint64_t *const           out_D = LGPU_SEARCH_ARG(kb, out_D), *const out_E = LGPU_SEARCH_ARG(kb, out_E);
-            unsigned long long *const totals = LGPU_SEARCH_ARG(kb, totals);
-            uint32_t *const           ticket = LGPU_SEARCH_ARG(kb, ticket);
-            if(out_counts) out_counts[ q ] = (uint32_t)got;
-            if(out_D) out_D[ q ] = D;
-            if(out_E) out_E[ q ] = E;
-            if(totals) { atomicAdd(&totals[ 0 ], (unsigned long long)D); atomicAdd(&totals[ 1 ], (unsigned long long)E); }
-            if constexpr(SCREEN) {
-                unsigned long long *const st = LGPU_SEARCH_ARG(kb, screen_totals);
-                if(st) { atomicAdd(&st[ 0 ], (unsigned long long)D); atomicAdd(&st[ 1 ], (unsigned long long)(D - (uint32_t)s.scal[ S_NREJ ])); }
-            }
-            // next query: a ticket (walks differ in length by 2x; static striding leaves workgroups idle at the end)
-            s.scal[ S_POS ] = ticket ? (int)(gridDim.x + atomicAdd(ticket, 1u)) : (int)(pos + gridDim.x);
-        }
-        __syncthreads();
-        if(tid == 0) {
-            // a host that waits on this counter instead of on the stream (the lone-query path: index.cpp search_one_locked)
-            // sees this query's answers first: they were written before the barrier above, and the fence orders them
-            uint32_t *const done = LGPU_SEARCH_ARG(kb, done), *const done_flags = LGPU_SEARCH_ARG(kb, done_flags);
-            if(done || done_flags) __threadfence_system();
-            if(done) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            if(done_flags) __hip_atomic_store(&done_flags[ q ], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-        pos = (uint32_t)s.scal[ S_POS ];
-        __syncthreads();
+        const uint32_t k = EACH ? each.k : LGPU_SEARCH_ARG(kb, k), skip = EACH ? each.skip : LGPU_SEARCH_ARG(kb, skip);
+        const uint32_t kw = EACH ? LGPU_SEARCH_ARG(kb, k_stride) : k;  // the width of an answer row
+        const int      got = frame_answer_rows<SearchArgs>(tid, T, kb, s, q, cnt, k, skip, kw);
+        pos = frame_close<SearchArgs, SCREEN>(tid, kb, s, q, pos, got, D, E);
     }
 }
-
-// one instantiation: opt the kernel in to its dynamic LDS size, then launch
-#define LGPU_LAUNCH_SEARCH(...)                                                                                        \
-    {                                                                                                                  \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_search<__VA_ARGS__>, lds, attr_);    \
-        hipLaunchKernelGGL((k_search<__VA_ARGS__>), dim3(grid), dim3(64 * waves), lds, stream, a);                     \
-    }
 
 }  // namespace lgpu

@@ -192,17 +192,17 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     if(slot < 0) return false;
     SearchArgs a{};
     a.view = ix->view();
-    a.queries = d_queries;
-    a.nq = (uint32_t)nq, a.k = (uint32_t)k, a.ef = p.expansion, a.skip = (uint32_t)skip;
-    a.labels = ix->d_labels;
-    a.out_labels = out.labels, a.out_dists = out.dists, a.out_slots = out.slots;
-    a.out_counts = out.counts, a.out_D = out.D, a.out_E = out.E;
+    a.frame.queries = d_queries;
+    a.frame.nq = (uint32_t)nq, a.k = (uint32_t)k, a.ef = p.expansion, a.skip = (uint32_t)skip;
+    a.frame.labels = ix->d_labels;
+    a.frame.out_labels = out.labels, a.frame.out_dists = out.dists, a.frame.out_slots = out.slots;
+    a.frame.out_counts = out.counts, a.frame.out_D = out.D, a.frame.out_E = out.E;
     // (the one-wave walk keeps its bitmap in LDS: nothing of the slot's HBM slab is touched)
-    if(!solo) a.bitmaps = ix->slot_bitmaps[ slot ], a.bm_words = (uint32_t)ix->slot_words[ slot ], a.undo_cap = vis_undo_cap();
-    a.vis_slots = p.vis_slots;
-    a.totals = ix->d_totals;
+    if(!solo) a.frame.bitmaps = ix->slot_bitmaps[ slot ], a.frame.bm_words = (uint32_t)ix->slot_words[ slot ], a.frame.undo_cap = vis_undo_cap();
+    a.frame.vis_slots = p.vis_slots;
+    a.frame.totals = ix->d_totals;
     a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
-    a.ticket = next_ticket(ix, nq, p.grid, stream);
+    a.frame.ticket = next_ticket(ix, nq, p.grid, stream);
     a.done = done, a.done_flags = done_flags;
     a.lds_list = p.lds_list, a.wide_rows = p.wide_rows;
     a.spec = p.spec, a.spec_prefetch = p.spec_prefetch, a.spec_cache = p.spec_cache;
@@ -241,7 +241,7 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
             d_tbl = d;
         }
         a.qparams = (const uint4 *)d_tbl;
-        a.qlist = (const uint32_t *)(d_tbl + each->list_at);
+        a.frame.qlist = (const uint32_t *)(d_tbl + each->list_at);
         a.k_stride = a.k;
     }
     if(e == hipSuccess) {
