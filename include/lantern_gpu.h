@@ -480,6 +480,10 @@ LANTERN_GPU_EXPORT int lantern_gpu_last_search_grid(usearch_index_t, usearch_err
  *   [7] spec_prefetch  [8] spec_cache  [9] wide_rows  [10] a latency-bound shape  [11] lds_list
  * Returns NULL, or the text the launch is refused with (then only out[2] is meaningful). */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search(const int64_t in[31], uint32_t out[12]);
+/* ... of an index that has ([31] != 0) or has not an int8 screen (f32 l2sq / cosine rows of >= 128 chunks; lantern_gpu_plan_search
+ * plans the index without one): in[32], out[13].  out[12]: the bytes of the query's int8 planes in the workgroup's LDS, != 0 iff the
+ * launch screens; they are part of out[6] and come out of out[5]. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search_screen(const int64_t in[32], uint32_t out[13]);
 
 /* Gathered distances: out[i] = metric(query, row(slots[i])) -- the kernel the graph walk is
  * made of, exposed for tests and profiling.  Host buffers. */

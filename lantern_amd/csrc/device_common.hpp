@@ -615,6 +615,13 @@ __host__ __device__ inline bool screen_rows_for(uint32_t chunks) { return chunks
 // norm that lost its small components, and the bound says nothing.
 __host__ __device__ inline bool screen_cos_norm_ok(float r) { return r >= 0x1p-48f && r <= 0x1p48f; }  // (false for NaN and 0)
 __host__ __device__ inline uint32_t screen_chunks_for(uint32_t chunks) { return (chunks + 3) / 4; }
+// The screened launches test a row against a 16-bit copy of the query, X = 256 h + l in two int8 planes (walk.hpp screen_stage_query):
+// per workgroup four f32 scalars, then per screen chunk 16 B of h and 16 B of l.  The block lies behind the visited set and is carved
+// ONLY in the launches that screen (search_plan.cpp plan_search takes it out of vis_slots; k_screen_probe).
+__host__ __device__ inline uint32_t screen_query_lds_bytes(uint32_t chunks) { return 16 + screen_chunks_for(chunks) * 32; }
+// The integer l2sq test multiplies the two scales: it is made only where the query's scale sx and the row's scale s lie in this range,
+// so that sx s, sx^2, s^2 and their products with the integer sums (< 2^34) stay normal and finite (false for NaN and 0).
+__host__ __device__ inline bool screen_l2_scale_ok(float s) { return s >= 0x1p-40f && s <= 0x1p40f; }
 
 __device__ __forceinline__ const uint4 *row_of(const View &v, uint32_t slot) { return v.vec + (size_t)slot * v.chunks; }
 

@@ -309,6 +309,7 @@ struct SearchPlanIn
     uint32_t  chunks = 0, M = 0, M0 = 0, ef_default = 0, pqd_inv = 0, pq_S16 = 0;                            // the index
     int       mcode = 0, num_cus = 0, search_vis_slots = -1, search_max_wg = 0;
     bool      pq_compact = false, phase_profile = false, spec_profile = false;
+    bool      screen = false;  // the index has an int8 screen (d_screen)
     size_t    n = 0, nq = 0, k = 0, ef = 0, skip = 0;                                                         // (n: the index's rows) the call
     int       waves = 0;  // > 0: explicit (the classic kernel); < 0: automatic, the classic fallback takes -waves
     bool      each = false;
@@ -324,6 +325,7 @@ struct SearchPlan
     int         spec = 0, waves = 0, grid = 0, wide_rows = 0, lds_list = 0;  // spec, wide_rows, lds_list: SearchArgs'
     uint32_t    expansion = 0, vis_slots = 0, spec_prefetch = 0, spec_cache = 0;  // (solo: words of the LDS bitmap, -, log2 of the list cache)
     size_t      lds = 0;             // dynamic LDS of a workgroup
+    uint32_t    screen_lds = 0;      // ... of which the query's int8 planes (screen_query_lds_bytes): != 0 iff the launch screens
     bool        took_spec = false;   // a latency-bound shape
     const char *refusal = nullptr;   // NULL: accepted; else the error text, and only `expansion` above is meaningful
 };

@@ -1,6 +1,7 @@
 // screen_probe_kernel.hip -- diagnostics: the int8 screen's reject decision, made by walk.hpp's own
 // hop_distances_screened and exported (lantern_gpu_screen_probe).  One workgroup plays one hop of a walk whose list is full: it stages
-// the query with the search kernels' own piece (query_frame.hpp frame_stage: the cached norm of a cosine query included), takes the caller's slots as the hop's new neighbours and the
+// the query with the search kernels' own pieces (query_frame.hpp frame_stage: the cached norm of a cosine query included; walk.hpp
+// screen_stage_query: its int8 planes), takes the caller's slots as the hop's new neighbours and the
 // caller's radius as the key `worst`, and reports which keys the screen set to ~0.  Nothing here decides anything: the tests compare
 // the verdicts with tests/test_screen_bound*.py on the host.
 #include "query_frame.hpp"
@@ -30,6 +31,7 @@ __global__ void __launch_bounds__(512) k_screen_probe(View v, const uint4 *query
     }
     frame_stage<METRIC, G>(tid, T, s, query, 0, v.chunks);  // (its barriers cover the writes above)
     const float qn2 = __int_as_float(s.scal[ S_QN2 ]);
+    screen_stage_query<METRIC>(tid, s, v.chunks, qn2);  // the planes block: behind the (empty) visited set
     (void)hop_distances_screened<METRIC, G, 2>(v, s, (int)n, make_key(radius, 0u), qn2);  // (ends in a barrier)
     for(uint32_t i = tid; i < n; i += T) out[ i ] = s.newkeys[ i ] == ~0ull ? 1 : 0;
 }
@@ -39,7 +41,7 @@ hipError_t launch_screen_probe(int metric, const View &v, const uint4 *query, co
 {
     if(n == 0) return hipSuccess;
     if(n > kProbeSlots || (threads != 256 && threads != 512) || !v.screen || !v.screen_meta || !screen_rows_for(v.chunks)) return hipErrorInvalidValue;
-    const size_t lds = walk_lds_bytes(v.chunks, kProbeSlots, kProbeSlots);
+    const size_t lds = walk_lds_bytes(v.chunks, kProbeSlots, kProbeSlots) + screen_query_lds_bytes(v.chunks);
     if(metric == M_L2SQ) hipLaunchKernelGGL(k_screen_probe<M_L2SQ>, dim3(1), dim3(threads), lds, stream, v, query, slots, n, radius, out);
     else if(metric == M_COS) hipLaunchKernelGGL(k_screen_probe<M_COS>, dim3(1), dim3(threads), lds, stream, v, query, slots, n, radius, out);
     else return hipErrorInvalidValue;

@@ -121,6 +121,9 @@ k_search(SearchArgs)
             uint32_t *const bitmap = frame_bind<SearchArgs>(ka, s, bm_words);
             const int       ef = EACH ? (int)each.ef : (int)LGPU_SEARCH_ARG(ka, ef);
             frame_stage<METRIC, G>(tid, T, s, LGPU_FRAME_ARG(ka, SearchArgs, queries), q, v.chunks);
+            if constexpr(SCREEN) {  // the query's int8 planes, where the launch carved their block: iff its view has a screen (search_plan.cpp)
+                if(LGPU_VIEW_ARG(ka, SearchArgs, screen)) screen_stage_query<METRIC>(tid, s, v.chunks, __int_as_float(s.scal[ S_QN2 ]));
+            }
             if constexpr(PROF) {
                 t_q = (unsigned long long)clock64();
                 s.touched = LGPU_SEARCH_ARG(ka, touched);

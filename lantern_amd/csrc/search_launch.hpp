@@ -28,7 +28,8 @@ namespace lgpu {
 template <bool EACH> static hipError_t launch_search_classic(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream)
 {
     if(EACH && a.phase_cycles) return hipErrorInvalidValue;
-    const size_t lds = search_lds_bytes(a.view.chunks, a.ef, a.view.M0, a.frame.vis_slots);
+    // (a view with a screen: the launch screens -- search_plan.cpp passes the screen only where it planned the planes' block)
+    const size_t lds = search_lds_bytes(a.view.chunks, a.ef, a.view.M0, a.frame.vis_slots) + (a.view.screen ? screen_query_lds_bytes(a.view.chunks) : 0);
     const int    kpl = a.lds_list ? 0 : a.ef <= 64 ? 1 : a.ef <= 128 ? 2 : 0;
     const int    G_ = group_lanes_for(a.view.chunks);
     if(a.wide_rows && !a.phase_cycles && G_ == 64) {  // the small-batch shape (rows of >= 128 chunks)

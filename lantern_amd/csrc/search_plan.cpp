@@ -33,6 +33,7 @@ SearchPlanIn search_plan_in(const Index *ix, size_t nq, size_t k, size_t ef, siz
     in.pq_compact = ix->pq_compact; in.pqd_inv = ix->pqd_inv; in.pq_S16 = ix->pq_S16;
     in.search_vis_slots = ix->search_vis_slots; in.search_max_wg = ix->search_max_wg;
     in.phase_profile = ix->phase_profile; in.spec_profile = ix->spec_profile;
+    in.screen = ix->d_screen && ix->d_screen_meta;
     in.nq = nq; in.k = k; in.ef = ef; in.skip = skip; in.waves = waves;
     in.env = search_env();
     return in;
@@ -162,13 +163,21 @@ SearchPlan plan_search(const SearchPlanIn &in)
     // set: 1.106 -> 1.17 M QPS at 1M x 768) -- four for the four-wave latency-bound shape, one for the lone-query shape;
     // it spills to the bitmap beyond
     const size_t lds_budget = spec >= 2 ? 96 * 1024 : spec == 1 ? 39 * 1024 : 26 * 1024;
+    // The launches that screen (search_kernel.hpp SCREEN: the classic shape of an index with an int8 screen, its list in registers,
+    // never the instrumented walk) also hold the query's int8 planes (walk.hpp screen_stage_query): a block of their own behind the
+    // visited set, paid for out of vis_slots -- 1.5 KB at 768-d, where 4 864 slots remain of 5 376 and three quarters of them still hold
+    // a walk's ~2 150 visits.  Every other launch carves, and plans, what it did before.
+    const bool   screened = in.screen && spec == 0 && !pqd && screen_rows_for(in.chunks) && (in.mcode == M_L2SQ || in.mcode == M_COS) &&
+                          !(in.phase_profile && !in.each) && !env.lds_list && expansion <= 128;
+    const size_t screen_lds = screened ? screen_query_lds_bytes(in.chunks) : 0;
     uint32_t vis_slots = 1024;
     while(vis_slots < 8192 && vis_slots / 4 * 3 < expansion * in.M0 * 2) vis_slots <<= 1;
     if(in.search_vis_slots >= 0) vis_slots = (uint32_t)in.search_vis_slots / 4 * 4;
-    while(vis_slots && search_lds_bytes(in.chunks, (uint32_t)expansion, in.M0, vis_slots) + spec_lds > lds_budget)
+    while(vis_slots && search_lds_bytes(in.chunks, (uint32_t)expansion, in.M0, vis_slots) + spec_lds + screen_lds > lds_budget)
         vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
     if(vis_slots && vis_slots < 4 * in.M0) vis_slots = 0;
-    p.lds = search_lds_bytes(in.chunks, (uint32_t)expansion, in.M0, vis_slots) + spec_lds;
+    p.lds = search_lds_bytes(in.chunks, (uint32_t)expansion, in.M0, vis_slots) + spec_lds + screen_lds;
+    p.screen_lds = (uint32_t)screen_lds;
     if(p.lds > 160 * 1024) { p.refusal = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel"; return p; }
     p.path = pqd ? kSearchPqd : spec == 0 ? kSearchClassic : spec == 1 ? kSearchSpec1 : spec == 2 ? kSearchSpec2 : kSearchTwin;
     p.spec = spec, p.took_spec = spec != 0;
@@ -207,6 +216,7 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     a.lds_list = p.lds_list, a.wide_rows = p.wide_rows;
     a.spec = p.spec, a.spec_prefetch = p.spec_prefetch, a.spec_cache = p.spec_cache;
     hipError_t e = hipSuccess;
+    if(!p.screen_lds) a.view.screen = nullptr, a.view.screen_meta = nullptr, a.view.screen_chunks = 0;  // no planes' block: the launch does not screen
     if(adc || pqd) a.view.vec = (const uint4 *)ix->d_codes16;
     if(adc) {
         a.view.chunks = ix->pq_S16 / 16;
@@ -343,10 +353,11 @@ bool search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const la
 }  // namespace lgpu
 
 // the plan without a device (include/lantern_gpu.h has the field order)
-extern "C" const char *lantern_gpu_plan_search(const int64_t in[ 31 ], uint32_t out[ 12 ])
+static const char *plan_search_flat(const int64_t *in, bool screen, uint32_t *out, uint32_t *screen_lds)
 {
     if(!in || !out) return "lantern_gpu: null array";
     lgpu::SearchPlanIn s;
+    s.screen = screen;
     s.chunks = (uint32_t)in[ 0 ]; s.M = (uint32_t)in[ 1 ]; s.M0 = (uint32_t)in[ 2 ]; s.mcode = (int)in[ 3 ]; s.n = (size_t)in[ 4 ];
     s.ef_default = (uint32_t)in[ 5 ]; s.num_cus = (int)in[ 6 ]; s.pq_compact = in[ 7 ] != 0; s.pqd_inv = (uint32_t)in[ 8 ]; s.pq_S16 = (uint32_t)in[ 9 ];
     s.search_vis_slots = (int)in[ 10 ]; s.search_max_wg = (int)in[ 11 ]; s.phase_profile = in[ 12 ] != 0; s.spec_profile = in[ 13 ] != 0;
@@ -359,5 +370,13 @@ extern "C" const char *lantern_gpu_plan_search(const int64_t in[ 31 ], uint32_t 
     const uint32_t flat[ 12 ] = { (uint32_t)p.path, (uint32_t)p.spec, p.expansion, (uint32_t)p.waves, (uint32_t)p.grid, p.vis_slots, (uint32_t)p.lds,
                                   p.spec_prefetch, p.spec_cache, (uint32_t)p.wide_rows, p.took_spec ? 1u : 0u, (uint32_t)p.lds_list };
     std::copy(std::begin(flat), std::end(flat), out);
+    if(screen_lds) *screen_lds = p.screen_lds;
     return p.refusal;
+}
+extern "C" const char *lantern_gpu_plan_search(const int64_t in[ 31 ], uint32_t out[ 12 ]) { return plan_search_flat(in, false, out, nullptr); }
+// ... of an index that has (in[31] != 0) or has not an int8 screen; out[12]: the bytes of the query's int8 planes in the launch's LDS
+extern "C" const char *lantern_gpu_plan_search_screen(const int64_t in[ 32 ], uint32_t out[ 13 ])
+{
+    if(!in || !out) return "lantern_gpu: null array";
+    return plan_search_flat(in, in[ 31 ] != 0, out, out + 12);
 }

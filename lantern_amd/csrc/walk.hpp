@@ -452,37 +452,123 @@ __device__ __forceinline__ void hop_distances(const View &v, WalkLds &s, int nne
 // ---- the int8 screen -------------------------------------------------------------------------------------
 // The distance phase of a hop of an f32 l2sq or cosine walk whose list is full (radius = the key `worst`): most new rows land
 // outside the radius and are read only to be thrown away.  So first every new row's distance is BOUNDED from below on its int8
-// screen copy y' = s * q (a quarter of the bytes; View::screen), and only the rows the bound cannot reject pay for the f32 row.
-// l2sq:
-//   d' = sum (x_i - y'_i)^2 in f32 (any order: every term is >= 0, so the relative error is at most (terms + tree) ulps),
-//   r  >= ||y - y'|| (k_fill_screen: in double, rounded up; +inf for rows with non-finite values or a zero / subnormal scale),
-//   ||x - y|| >= ||x - y'|| - r  (triangle inequality), so  LB = max(0, sqrt(d') (1 - e) - r)^2 <= ||x - y||^2,
-// and the device's f32 distance d of the row is within (1 - e) of its exact value, e = max(2^-12, (2 chunks + 64) 2^-24) being
-// far above the rounding of either sum.  A row is rejected iff LB (1 - e) > dist(worst) -- strictly, and a NaN anywhere fails the
-// test -- so a rejected row's d is strictly above the radius: its exact key could not have entered the list, and since the
-// radius only shrinks it never can.  Its key becomes ~0 (above every radius: the visit wave's choice and the list wave's merge
-// skip it, as they would skip the exact key).  Survivors get the exact evaluation of hop_distances, same chain, same tree, same
-// bits (the caller runs it over the survivors, s.sorted[0..ns), ns returned).
+// screen copy y' = s * c (a quarter of the bytes; View::screen), and only the rows the bound cannot reject pay for the f32 row.
+// The bound is formed in INTEGERS against a 16-bit copy of the query: u = 2^-24, e = max(2^-12, (2 chunks + 64) u).
+//
+// The query's copy (screen_stage_query, once per query, wave 0; tests/test_screen_bound_int.py restates every step):
+//   sx = max |x_i| / 32639,  q_i = fl(x_i / sx),  X_i = rint(q_i) in [-32639, 32639] (|q_i| <= 32639 (1 + 2 u): nothing to clip),
+//   X = 256 h + l with h = (X + 128) >> 8 in [-127, 127], l = X - 256 h in [-128, 127]: both int8 (32639 = 127 * 256 + 127); x' = sx X (exact reals).
+//   delta >= ||x - x'||:  |x_i / sx - X_i| <= |q_i - X_i| + |q_i| u < rho_i + 2^-9 with rho_i = |q_i - X_i| exact in f32 (the fraction of
+//   an f32 below 2^16), so delta = fl(sx sqrt(S)) (1 + 2^-10), S = sum (rho_i + 2^-9)^2 in f32 (positive terms: within 64 u of the exact
+//   sum; a quotient flushed below the normal range moves rho_i by 2^-150, inside the slack 2^-9 - 32640 u).  Scale-free: no term
+//   underflows whatever sx is.  sum X^2 = 65536 sum h^2 + 512 sum h l + sum l^2 reaches 2^41 at d = 2000: the three sums are int32
+//   (<= 2000 * 128^2 < 2^25), combined in double, exact.  ||x'||^2 = sx^2 sum X^2 =: P.
+//   A query with a non-finite value, max |x| = 0 or a scale outside the range (l2sq: screen_l2_scale_ok(sx); cosine: sx normal) publishes
+//   zero planes and delta = +inf: it rejects nothing, as a cosine query whose norm is outside screen_cos_norm_ok.
+// The row's sums (eight lanes per row): Ih = <h, c>, Il = <l, c> and, l2sq, C2 = <c, c> by v_dot4_i32_i8, three per screen word.  A lane
+//   sees at most 256 values (d = 2000): each of its sums is <= 256 * 128 * 127 < 2^22; an eight-lane sum is <= 2000 * 128 * 127 < 2^25: int32
+//   holds them and no order of summation matters.  I = 256 Ih + Il = <X, c> reaches 2000 * 32639 * 127 = 8.3e9 and does NOT fit int32:
+//   it is formed in double (exact) and rounded to f32 once, fI = I (1 + u).
+// l2sq (r >= ||y - y~||, k_fill_screen: in double, rounded up, against the F32 products y~_i = fl(s c_i); +inf for rows with non-finite
+//   values or a zero / subnormal scale):  ||x - y|| >= ||x' - y~|| - delta - r  (triangle inequality, twice), and with y' = s c exact,
+//   Q = ||y'||^2 = s^2 C2, A = ||x' - y'||:   A^2 = P - 2 sx s I + Q   exactly.
+//   eta.  ||y~ - y'|| <= u ||y'||, so ||x' - y~||^2 >= A^2 - 2 A u ||y'|| >= A^2 - u (2 P + 3 Q)  (2 a b <= a^2 + b^2, A^2 <= 2 (P + Q)).
+//   The f32 value d' = fl(fl(P~ - R~) + Q~): P~ = fl(fl(sx sx) fl(sum X^2)) errs by 3 u P, R~ = fl(fl(2 fl(sx s)) fI) by 3 u |R| <= 3 u
+//   (P + Q) (|R| = 2 sx s |I| <= 2 sqrt(P Q)), Q~ = fl(fl(s s) fl(C2)) by 3 u Q, the two additions by u (2 P + Q) and 2 u (P + Q) --
+//   to first order, all scales inside screen_l2_scale_ok, so nothing under- or overflows: |d' - A^2| <= (10 P + 9 Q) 1.01 u.  Together
+//   ||x' - y~||^2 >= d' - 13.2 u (P + Q) >= d' - eta,  eta = 16 u fl(P~ + Q~).  (The expansion cancels where x ~ y: there d' - eta < 0
+//   and the row is kept.)  For a row near or beyond the radius d' is of the order of P + Q: eta takes about 1e-6 of it, no rejections.
+//   LB = max(0, sqrt(max(0, d' - eta)) (1 - e) - r - delta)^2 <= ||x - y||^2: the subtraction, the root, the product and the two
+//   subtractions round by 5 u, far inside (1 - e); and the device's f32 distance d of the row is within (1 - e) of its exact value, e
+//   being far above the rounding of its sum.  A row is rejected iff LB (1 - e) > dist(worst) -- strictly, and a NaN anywhere fails the
+//   test -- so a rejected row's d is strictly above the radius: its exact key could not have entered the list, and since the
+//   radius only shrinks it never can.  Its key becomes ~0 (above every radius: the visit wave's choice and the list wave's merge
+//   skip it, as they would skip the exact key).  Survivors get the exact evaluation of hop_distances, same chain, same tree, same
+//   bits (the caller runs it over the survivors, s.sorted[0..ns), ns returned).
 // cosine (the device's distance is d = fl(1 - fl(ab / fl(ra rb))): ab the 64-lane chain of <x, y>, ra = qn2 and rb = norm2[slot] the
-// rooted norms; X = ||x||, Y = ||y||, P = X Y exact, u = 2^-24, m = ceil(chunks / 64) 4 + 6 the length of a 64-lane chain and tree):
-//   <x, y> <= <x, y'> + X ||y - y'||  (Cauchy-Schwarz), so  sigma = <x, y> / P <= <x, q> s / P + rho,  rho >= ||y - y'|| / Y
-//   (k_fill_screen<true>: both norms in double, rounded up; +inf for rows with non-finite values, a zero / subnormal scale, or rb
-//   outside screen_cos_norm_ok -- the zero rows among them).  Where ra and rb are inside screen_cos_norm_ok:
-//   (a) the device's similarity.  ab = <x, y> + alpha P with |alpha| <= m u (every partial sum of products is at most P in
+// rooted norms; X = ||x||, Y = ||y||, u = 2^-24, m = ceil(chunks / 64) 4 + 6 the length of a 64-lane chain and tree):
+//   <x, y> = <x', y~> + <x', y - y~> + <x - x', y> <= <x', y~> + (X + delta) ||y - y~|| + delta Y  (Cauchy-Schwarz), so
+//   sigma = <x, y> / (X Y) <= <x', y~> / (X Y) + rho (1 + dq) + dq,   rho >= ||y - y~|| / Y,  dq >= delta / X
+//   (rho: k_fill_screen<true>, both norms in double, rounded up; +inf for rows with non-finite values, a zero / subnormal scale, or rb
+//   outside screen_cos_norm_ok -- the zero rows among them; dq = fl(delta / ra) (1 + 2^-10), ra = X (1 + a) below).  Where ra and rb are
+//   inside screen_cos_norm_ok:
+//   (a) the device's similarity.  ab = <x, y> + alpha X Y with |alpha| <= m u (every partial sum of products is at most X Y in
 //       magnitude); ra = X (1 + a), rb = Y (1 + b) with |a|, |b| <= (m / 2 + 1) u + 2^-20 (the chain of squares has positive terms;
 //       the last term is what squares flushed below the normal range can take); fl(ra rb) and the divide round once each.  With
 //       |sigma| <= 1:  |fl(ab / fl(ra rb)) - sigma| <= (2 m + 4) u + 2^-19 =: e1, and the final subtraction is monotone and rounds
 //       by at most 2 u:  d >= 1 - sigma - e1 - 2 u.
-//   (b) the screen's similarity.  acc = <x, q> + beta X ||q|| with |beta| <= n u, n = 16 ceil(chunks / 32) + 3 (the eight-lane chain
-//       and tree below; the terms have BOTH signs, so unlike l2sq's "any order" holds only because the error of any order is bounded
-//       by n u sum |x_i q_i| <= n u X ||q|| -- an absolute error on the similarity scale, not a relative one), and s ||q|| = ||y'||
-//       <= 2 Y.  The folded constant t = fl(s / rb) = (s / Y)(1 + tau), |tau| <= |b| + u, and fl(fl(acc t) / ra) adds 2 u + |a|
-//       relative to a value of magnitude at most 2:  |sim8 - <x, q> s / P| <= 2 n u + 2 (|a| + |b| + 3 u) =: e2.
-//   (c) the test's own f32 steps ((sim8 + rho) + e, 1 - that, - e: values of magnitude <= 4) round by at most 16 u together.
-//   At 128 <= chunks <= 500 (n <= 259, m <= 38): e1 + 2 u + e2 + 16 u <= 114 u + 668 u + 16 u < 8192 u = 2^-11 = 2 e, so with
-//   u_ = sim8 + rho + e:  1 - u_ - e <= 1 - sigma - e1 - 2 u <= d.  The (2 chunks + 64) 2^-24 arm of e keeps the inequality for longer
-//   rows (both e1 and e2 grow by less than chunks u each).  A row is rejected iff 1 - u_ - e > dist(worst), strictly; a NaN anywhere
-//   fails the test, and so does rho = +inf.  Nothing in (a) - (c) depends on the scale of x or of y inside the range.
+//   (b) the screen's similarity.  <x', y'> = sx s I exactly, and <x', y~ - y'> <= (X + delta) u ||y'|| with ||y'|| <= 2 Y: 3 u on the
+//       similarity scale.  sim8 = fl(fl(fl(fI sx) t) / ra) with the folded constant t = fl(s / rb) = (s / Y)(1 + tau), |tau| <= |b| + u:
+//       four roundings and |a|, |tau| relative to a value of magnitude at most 2 (1 + dq) (no step leaves the normal range: sx |I| >=
+//       2^-126 unless I = 0):  |sim8 - sx s I / (X Y)| <= 9 u + 2.1 (|a| + |b| + u) =: e2.
+//   (c) the test's own f32 steps (1 + dq, rho times that, (sim8 + it) + dq, + e, 1 - that, - e: values of magnitude <= 4 wherever a row
+//       can be rejected) round by at most 24 u together.
+//   At 128 <= chunks <= 500 (m <= 38): e1 + 2 u + 3 u + e2 + 24 u < 600 u < 8192 u = 2^-11 = 2 e, so with u_ = sim8 + rho (1 + dq) + dq
+//   + e:  1 - u_ - e <= 1 - sigma - e1 - 2 u <= d.  The (2 chunks + 64) 2^-24 arm of e keeps the inequality for longer rows (both e1 and
+//   e2 grow by less than chunks u each).  A row is rejected iff 1 - u_ - e > dist(worst), strictly; a NaN anywhere fails the test, and
+//   so do rho = +inf and dq = +inf.  Nothing in (a) - (c) depends on the scale of x or of y inside the range.
+
+// The block of the query's planes: behind the visited set, in the launches that carve it (device_common.hpp screen_query_lds_bytes)
+__device__ __forceinline__ uint32_t *screen_query_block(const WalkLds &s) { return s.vis + s.vis_slots; }
+
+// Stage the 16-bit copy of the query in s.q (frame_stage has run) into the workgroup's planes block: wave 0, then a barrier.
+// Scalars: [0] sx, [1] delta (cosine: dq), [2] ||x'||^2 (l2sq).  qn2: the query's rooted norm (cosine).
+template <int METRIC> __device__ __forceinline__ void screen_stage_query(const int tid, const WalkLds &s, uint32_t chunks, float qn2)
+{
+    uint32_t *const blk = screen_query_block(s);
+    if(__builtin_amdgcn_readfirstlane(tid) < 64) {
+        const uint32_t lane = (uint32_t)tid, sch = screen_chunks_for(chunks);
+        uint32_t       mb = 0;  // max |x_i| as bits: a NaN or an infinity is above every finite value
+        for(uint32_t i = lane; i < chunks; i += 64) {
+            const uint4 x = s.q[ i ];
+            mb = max(max(mb, x.x & 0x7FFFFFFFu), max(max(x.y & 0x7FFFFFFFu, x.z & 0x7FFFFFFFu), x.w & 0x7FFFFFFFu));
+        }
+        for(int off = 32; off > 0; off >>= 1) mb = max(mb, (uint32_t)__shfl_xor((int)mb, off));
+        const float sx = __uint_as_float(mb) / 32639.f;
+        const bool  ok = mb < 0x7F800000u && mb != 0u && (METRIC == M_COS ? (sx >= 0x1p-126f && sx <= 0x1p100f) : screen_l2_scale_ok(sx));
+        float    S = 0.f;
+        uint32_t hh = 0, hl = 0, ll = 0;
+        for(uint32_t i = lane; i < 4 * sch; i += 64) {  // query chunk i: word i % 4 of both planes of screen chunk i / 4 (beyond the row: zeros)
+            const uint4 x = i < chunks ? s.q[ i ] : make_uint4(0u, 0u, 0u, 0u);
+            const float xs[ 4 ] = { __uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w) };
+            uint32_t    hw = 0, lw = 0;
+#pragma unroll
+            for(int b = 0; b < 4; ++b) {
+                const float q = ok ? xs[ b ] / sx : 0.f;
+                const float Xf = fminf(fmaxf(__builtin_rintf(q), -32639.f), 32639.f);
+                const float rho = __builtin_fabsf(q - Xf) + 0x1p-9f;
+                S = __builtin_fmaf(rho, rho, S);
+                const int X = (int)Xf, h = (X + 128) >> 8, l = X - 256 * h;
+                hw |= ((uint32_t)h & 0xFFu) << (8 * b);
+                lw |= ((uint32_t)l & 0xFFu) << (8 * b);
+            }
+            hh = (uint32_t)dot4_i8(hw, hw, (int)hh);
+            hl = (uint32_t)dot4_i8(hw, lw, (int)hl);
+            ll = (uint32_t)dot4_i8(lw, lw, (int)ll);
+            blk[ 4 + 8 * (i / 4) + i % 4 ] = hw;
+            blk[ 8 + 8 * (i / 4) + i % 4 ] = lw;
+        }
+        S = group_sum<64>(S);
+        hh = group_sum<64>(hh), hl = group_sum<64>(hl), ll = group_sum<64>(ll);
+        if(lane == 63) {
+            float delta = __builtin_inff(), nx2 = 0.f;
+            if(ok) {
+                delta = (sx * __builtin_sqrtf(S)) * (1.f + 0x1p-10f);
+                if constexpr(METRIC == M_COS) delta = (delta / qn2) * (1.f + 0x1p-10f);  // dq (qn2 outside the range: the test is not made)
+                nx2 = (sx * sx) * (float)(65536.0 * (double)(int)hh + 512.0 * (double)(int)hl + (double)(int)ll);
+            }
+            blk[ 0 ] = __float_as_uint(ok ? sx : 0.f);
+            blk[ 1 ] = __float_as_uint(delta);
+            blk[ 2 ] = __float_as_uint(nx2);
+            blk[ 3 ] = 0u;
+        }
+    }
+    __syncthreads();
+}
+
+#ifndef LGPU_SCREEN_NB
+#define LGPU_SCREEN_NB 3
+#endif
 template <int METRIC, int G, int ROWS>
 __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s, int nnew, uint64_t worst, float qn2)
 {
@@ -492,10 +578,10 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
     // groups -- two memory round trips per hop (16-lane groups with two chunks in flight, then a third, over two rounds took four).
     // Rows of up to 125 chunks (d = 2000) take more blocks, the last one partial; a chunk beyond the row is neither requested nor
     // consumed.  Only exec-mask arithmetic stands between the loads of a block in the instruction stream, and (s, r) is requested
-    // ahead of them, in the same block.  NB = 3 is what the register budget holds: the whole 768-d row in one block (NB = 6, 24
-    // VGPRs of row data) spills 13 VGPRs where this spills the parent's 4.  Eight-lane groups also halve the bank
-    // conflict of the query reads below (a lane's chunks are 64 B of query apart: eight addresses per ds_read_b128 service group, not 16).
-    constexpr int GS = 8, NB = 3;
+    // ahead of them, in the same block.  NB = 3: the whole 768-d row in one block (NB = 6) spills more (DESIGN.md 4.3 has both builds' figures).
+    // A screen chunk meets 32 B of the query's planes, 16 B of h then 16 B of l: the eight lanes of a ds_read_b128 service group read
+    // addresses 32 B apart (eight bank sets: no conflict), the groups of a wave read the same addresses (broadcast).
+    constexpr int GS = 8, NB = LGPU_SCREEN_NB;
     static_assert(G % GS == 0, "a screen group lies within one wave");
     const int       tid = threadIdx.x, T = blockDim.x, gs = tid / GS, gsl = tid % GS, NGS = T / GS;
     uint32_t *const surv = (uint32_t *)s.sorted;
@@ -512,11 +598,13 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
     const ScreenRow  screen = (ScreenRow)uniform(((const uint64_t *)&s.scal[ S_SCREEN ])[ 0 ]);
     const ScreenMeta screen_meta = (ScreenMeta)uniform(((const uint64_t *)&s.scal[ S_SCREEN ])[ 1 ]);
     const uint32_t   chunks = v.chunks, sch = screen_chunks_for(chunks);
+    const uint32_t *const blk = screen_query_block(s);
+    const uint4 *const    planes = (const uint4 *)(blk + 4);  // [sch][2]: h, l
     for(int j = gs; j < nnew; j += NGS) {
         const uint32_t id = s.newids[ j ];
         const ScreenRow row = screen + (size_t)id * sch;
         const f32x2     meta = screen_meta[ id ];
-        float          acc = 0.f;
+        int            ih = 0, il = 0, c2 = 0;
         for(uint32_t base = (uint32_t)gsl; base < sch; base += NB * GS) {
             u32x4 y[ NB ];
 #pragma unroll
@@ -525,44 +613,45 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
 #pragma unroll
             for(int c = 0; c < NB; ++c)
                 if(base + c * GS < sch) {
+                    const uint4    hq = planes[ 2 * (base + c * GS) ], lq = planes[ 2 * (base + c * GS) + 1 ];
                     const uint32_t w[ 4 ] = { y[ c ].x, y[ c ].y, y[ c ].z, y[ c ].w };
+                    const uint32_t hs[ 4 ] = { hq.x, hq.y, hq.z, hq.w }, ls[ 4 ] = { lq.x, lq.y, lq.z, lq.w };
 #pragma unroll
-                    for(int k = 0; k < 4; ++k) {  // screen word k covers query chunk 4 (base + c GS) + k (beyond the row: zeros)
-                        const uint32_t qc = 4 * (base + c * GS) + (uint32_t)k;
-                        const uint4    x = qc < chunks ? s.q[ qc ] : make_uint4(0u, 0u, 0u, 0u);
-                        const float    xs[ 4 ] = { __uint_as_float(x.x), __uint_as_float(x.y), __uint_as_float(x.z), __uint_as_float(x.w) };
-#pragma unroll
-                        for(int b = 0; b < 4; ++b) {
-                            if constexpr(METRIC == M_COS) {
-                                // <x, q>: one convert and one fma per value, the scale applied once behind the group sum.  Terms of
-                                // both signs: any order is within n u X ||q|| of the exact sum -- (b) above -- which is all e needs.
-                                acc = __builtin_fmaf(xs[ b ], (float)(int)(int8_t)(uint8_t)(w[ k ] >> (8 * b)), acc);
-                            } else {
-                                const float t = xs[ b ] - screen_val(meta.x, w[ k ], b);
-                                acc = __builtin_fmaf(t, t, acc);
-                            }
-                        }
+                    for(int k = 0; k < 4; ++k) {  // (words beyond the row are zero in the screen row and in the planes)
+                        ih = dot4_i8(hs[ k ], w[ k ], ih);
+                        il = dot4_i8(ls[ k ], w[ k ], il);
+                        if constexpr(METRIC == M_L2SQ) c2 = dot4_i8(w[ k ], w[ k ], c2);
                     }
                 }
         }
-        acc = group_sum<GS>(acc);
+        ih = (int)group_sum<GS>((uint32_t)ih);
+        il = (int)group_sum<GS>((uint32_t)il);
+        if constexpr(METRIC == M_L2SQ) c2 = (int)group_sum<GS>((uint32_t)c2);
         if(gsl == GS - 1) {
-            bool reject = false;
+            bool        reject = false;
+            const float sx = __uint_as_float(blk[ 0 ]), delta = __uint_as_float(blk[ 1 ]);
+            const float fI = (float)(256.0 * (double)ih + (double)il);  // <X, c>: beyond int32 at d = 2000; exact in double, one rounding
+            const float rd = key_dist(worst), e = fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
             if constexpr(METRIC == M_COS) {
-                // meta = (s / rb, rho); qn2 = ra.  The steps of (b) and (c), in this order (tests/test_screen_bound_cos.py restates
-                // them); a query whose norm is 0 or outside the range rejects nothing, a row's range is in rho.
-                const float rd = key_dist(worst), e = fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
+                // meta = (s / rb, rho); qn2 = ra; delta = dq.  The steps of (b) and (c), in this order (tests/test_screen_bound_int.py
+                // restates them); a query whose norm is 0 or outside the range rejects nothing, a row's range is in rho.
                 if(screen_cos_norm_ok(qn2)) {
-                    const float sim8 = (acc * meta.x) / qn2;
-                    const float ub = (sim8 + meta.y) + e;
+                    const float sim8 = ((fI * sx) * meta.x) / qn2;
+                    const float ub = ((sim8 + meta.y * (1.f + delta)) + delta) + e;
                     reject = (1.f - ub) - e > rd;
                 }
             } else {
-                const float rd = key_dist(worst), ome = 1.f - fmaxf(0x1p-12f, (float)(2 * chunks + 64) * 0x1p-24f);
-                if(__builtin_isfinite(acc)) {
-                    const float a = __builtin_sqrtf(acc) * ome - meta.y;
-                    const float lb = a > 0.f ? a * a : 0.f;
-                    reject = lb > 0x1p-100f && lb * ome > rd;  // (lb > 2^-100: far above what underflow can take from either sum)
+                // meta = (s, r).  d' and eta as derived above, in this order
+                const float ome = 1.f - e;
+                if(screen_l2_scale_ok(meta.x)) {
+                    const float nx2 = __uint_as_float(blk[ 2 ]);
+                    const float R = (2.f * (sx * meta.x)) * fI, Q = (meta.x * meta.x) * (float)c2;
+                    const float m = ((nx2 - R) + Q) - 0x1p-20f * (nx2 + Q);
+                    if(__builtin_isfinite(m)) {
+                        const float a = (__builtin_sqrtf(fmaxf(m, 0.f)) * ome - meta.y) - delta;
+                        const float lb = a > 0.f ? a * a : 0.f;
+                        reject = lb > 0x1p-100f && lb * ome > rd;  // (lb > 2^-100: as in the float form; nothing here underflows)
+                    }
                 }
             }
             if(reject) s.newkeys[ j ] = ~0ull;
