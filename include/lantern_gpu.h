@@ -495,6 +495,25 @@ LANTERN_GPU_EXPORT float lantern_gpu_last_gather_ms(usearch_index_t, usearch_err
  * cumulative) and how many of them read the f32 row (exact); the rest were rejected on the screen row.  Both 0 when the index has
  * no screen (another metric or storage, rows of fewer than 128 chunks, LANTERN_GPU_SCREEN=0). */
 LANTERN_GPU_EXPORT void lantern_gpu_search_screen_stats(usearch_index_t, uint64_t *logical, uint64_t *exact, usearch_error_t *);
+/* The int8 screen in the INSERTION walk: builds and batched inserts of an index that has a screen table test the
+ * level-0 candidates of k_insert on the int8 row copy first, with the searches' exact bound -- the graph is edge for edge the one built
+ * without it.  mode: 0 = off, 1 = on; any other value is refused.  On an index without a screen table mode 1 is accepted and has no
+ * effect.  A launch is screened iff the mode is on, the index has the table, ef_construction <= 128, LANTERN_GPU_LDS_LIST is off, the
+ * batch does not take the lone-insertion walk (more than 2 x CUs rows), it is not the row-sharded build, and the walk has two waves or
+ * more.  The initial mode is LANTERN_GPU_INSERT_SCREEN (0 | 1) where set, on otherwise. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_insert_screen(usearch_index_t, int mode, usearch_error_t *);
+/* ... counted since init, after buffered adds are flushed: out[0] screened k_insert launches, out[1] unscreened k_insert launches (the
+ * lone-insertion walk is neither), out[2] rows put to the screen test, out[3] rows it rejected (their f32 rows were not read). */
+LANTERN_GPU_EXPORT void lantern_gpu_insert_screen_stats(usearch_index_t, uint64_t out[4], usearch_error_t *);
+/* The shape of a batch's k_insert launch, host arithmetic only (no device, no index, no environment).
+ * in[13]: [0] metric code (1 cos, 3 l2sq, 8 hamming, +100 f16 rows, +200 i8 rows)  [1] 16-byte chunks per row  [2] M0
+ *   [3] ef_construction  [4] rows the launch walks  [5] CUs  [6] waves per workgroup  [7] the index has a screen table
+ *   [8] mode (lantern_gpu_set_insert_screen)  [9] LANTERN_GPU_LDS_LIST != 0  [10] row-sharded build (upper levels only)
+ *   [11] the lone-insertion walk may be taken (one index, LANTERN_GPU_INSERT_SPEC != 0)  [12] LANTERN_GPU_INSERT_VIS_SLOTS, or -1
+ * out[7]: [0] screened  [1] vis_slots  [2] LDS bytes per workgroup  [3] of which the query's int8 planes (!= 0 iff screened; they come
+ *   out of [1])  [4] the lone-insertion walk  [5] spec_prefetch  [6] spec_cache
+ * Returns NULL, or the text the launch is refused with. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_insert(const int64_t in[13], uint32_t out[7]);
 /* Diagnostics (tests): what the device STORED as the int8 screen of slots [first, first + count), copied out behind the index stream
  * after buffered single adds are flushed.  rows[count][row_bytes] int8 (16 per screen chunk, zero padded); meta[count][2] f32: l2sq
  * (s, r), cosine (s / norm, rho); norms[count] f32: a cosine index's cached rooted norms, the ones the fill divided by (an l2sq index

@@ -88,6 +88,7 @@ EXPORTS = [
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
     "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_distance_gather",
     "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
+    "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
     "lantern_gpu_export_codes",
     "lantern_gpu_counters_get", "lantern_gpu_set_profiling", "lantern_gpu_build_profile_get", "lantern_gpu_search_phase_profile", "lantern_scan_begin", "lantern_scan_rescan", "lantern_scan_gettuple", "lantern_scan_trace", "lantern_scan_end",
@@ -223,6 +224,8 @@ def lib() -> C.CDLL:
         "lantern_gpu_last_search_grid": (i32, [vp, err]),
         "lantern_gpu_last_gather_ms": (f32, [vp, err]),
         "lantern_gpu_search_screen_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), err]),
+        "lantern_gpu_set_insert_screen": (None, [vp, C.c_int, err]),
+        "lantern_gpu_insert_screen_stats": (None, [vp, vp, err]),
         "lantern_gpu_export_screen": (sz, [vp, sz, sz, vp, vp, vp, err]),
         "lantern_gpu_screen_probe": (None, [vp, vp, vp, sz, f32, i32, vp, err]),
         "lantern_gpu_save_stream": (None, [vp, vp, vp, err]),
@@ -277,6 +280,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_plan_batch": (sz, [sz, i32, vp, sz, sz, sz]),
         "lantern_gpu_plan_search": (C.c_char_p, [vp, vp]),
         "lantern_gpu_plan_search_screen": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_plan_insert": (C.c_char_p, [vp, vp]),
         "lantern_gpu_row_shard_plan": (sz, [vp, i32, u64, u32, sz, sz, vp, vp, vp, sz]),
         "lantern_scan_server_start": (vp, [vp, C.c_char_p, i32, sz, C.c_uint, err]),
         "lantern_scan_server_start_fn": (vp, [BATCH_SEARCH_FN, vp, sz, C.c_char_p, i32, sz, C.c_uint, err]),
@@ -578,6 +582,18 @@ class GpuIndex:
         logical, exact = C.c_uint64(0), C.c_uint64(0)
         _call("lantern_gpu_search_screen_stats", self.h, C.byref(logical), C.byref(exact))
         return int(logical.value), int(exact.value)
+
+    def set_insert_screen(self, mode):
+        """lantern_gpu_set_insert_screen: 0 = the insertion walk reads every candidate's f32 row, 1 = it tests level-0 candidates on
+        the int8 row copy first where the launch qualifies (same graph); no effect on an index without a screen table"""
+        _call("lantern_gpu_set_insert_screen", self.h, int(mode))
+
+    def insert_screen_stats(self):
+        """lantern_gpu_insert_screen_stats: (screened k_insert launches, unscreened k_insert launches, rows put to the screen test,
+        rows it rejected), counted since init"""
+        out = np.zeros(4, dtype=np.uint64)
+        _call("lantern_gpu_insert_screen_stats", self.h, _ptr(out))
+        return tuple(int(x) for x in out)
 
     def export_screen(self, first=0, count=None):
         """lantern_gpu_export_screen: the stored int8 screen of slots [first, first + count) (count None: to the end) as
@@ -1178,6 +1194,21 @@ def plan_search(fields) -> tuple[dict, str | None]:
         a, out = np.asarray(vals, dtype=np.int64), np.zeros(len(names), dtype=np.uint32)
         why = lib().lantern_gpu_plan_search(_ptr(a), _ptr(out))
     return dict(zip(names, (int(x) for x in out))), (why.decode() if why else None)
+
+
+# lantern_gpu_plan_insert's arrays, in order (include/lantern_gpu.h)
+PLAN_INSERT_IN = ("mcode", "chunks", "M0", "efc", "rows", "num_cus", "waves", "screen_table", "mode", "lds_list", "only_upper", "lone_ok", "vis_slots_env")
+PLAN_INSERT_OUT = ("screened", "vis_slots", "lds", "screen_lds", "lone", "spec_prefetch", "spec_cache")
+
+
+def plan_insert(fields) -> tuple[dict, str | None]:
+    """The shape of a batch's k_insert launch for PLAN_INSERT_IN values (a dict or a sequence; host arithmetic, no device):
+    ({PLAN_INSERT_OUT name: value}, refusal text or None)."""
+    vals = [fields[n] for n in PLAN_INSERT_IN] if isinstance(fields, dict) else list(fields)
+    assert len(vals) == len(PLAN_INSERT_IN)
+    a, out = np.asarray(vals, dtype=np.int64), np.zeros(len(PLAN_INSERT_OUT), dtype=np.uint32)
+    why = lib().lantern_gpu_plan_insert(_ptr(a), _ptr(out))
+    return dict(zip(PLAN_INSERT_OUT, (int(x) for x in out))), (why.decode() if why else None)
 
 
 def row_shard_plan(shard_sizes, seed: int, M: int, max_batch: int, min_ratio: int):

@@ -545,6 +545,42 @@ struct RowShard
 };
 static bool row_shard_candidates(Index *ix, const RowShard &rs, size_t first, size_t b, const uint32_t *d_link_off, uint64_t *d_tops, uint32_t *d_top_count);
 
+// The initial mode of Index::insert_screen where LANTERN_GPU_INSERT_SCREEN does not say.  On: the same-box A/B of DESIGN.md 4.4
+// (profiles/insert_screen_build_ab.json) -- Gaussian 1M x 768 builds at 894 k vectors/s against 580 k, clustered at the same speed.
+static const bool kInsertScreenByDefault = true;
+
+// The shape of a batch's k_insert launch (run_batch below; lantern_gpu_plan_insert shows it without a device).
+// Lone walk: a handful of insertions -- ldb_aminsert's one row, the first batches of a build -- walk alone on their CUs: level 0 by the
+// lone-query walk (insert_spec_kernel.hip), up to two insertions per CU one after the other.
+// Screened: level 0 tests its candidates on the int8 row copy first (insert_kernel.hip k_insert<.., SCREEN = true>) iff the index's mode
+// is on, it has the table, the rows are f32 l2sq / cosine of >= 128 chunks, the list lives in registers (efc <= 128, no LDS list), the
+// walk is split over two or more waves, has a level 0 and is not the lone walk.  The query's int8 planes then come out of vis_slots.
+InsertPlan plan_insert(const InsertPlanIn &in)
+{
+    InsertPlan p;
+    p.lone = in.lone_ok && in.rows <= (size_t)in.num_cus * 2 && insert_spec_supported(in.mcode, in.efc, in.M0) && !in.lds_list;
+    p.screened = in.mode == 1 && in.screen_table && (in.mcode == M_L2SQ || in.mcode == M_COS) && screen_rows_for(in.chunks) && in.efc <= 128 &&
+                 !in.lds_list && !p.lone && !in.only_upper && in.waves >= 2;
+    p.screen_lds = p.screened ? screen_query_lds_bytes(in.chunks) : 0;
+    // LDS visited set for the ef_construction-wide walk (spills to the bitmap when 3/4 full); env override for tuning
+    // the largest table that still lets FIVE workgroups share a CU (160 KB / 5, minus the walk's lists): 6400 slots at
+    // 768-d / efc 128, enough for the ~3700 nodes such a walk visits at the 3/4 load limit
+    uint32_t ivis = 8192;
+    if(in.vis_slots_env >= 0) ivis = (uint32_t)in.vis_slots_env / 4 * 4;
+    const int G_ = group_lanes_for(in.chunks), LW_ = G_ >= 32 ? 1 : G_ == 16 ? 2 : 4;  // list words a lane of a row's group fetches
+    p.spec_prefetch = p.lone && in.M0 % (uint32_t)LW_ == 0 && in.M0 <= (uint32_t)(G_ * LW_) ? 1u : 0u;
+    p.spec_cache = p.spec_prefetch ? 128u : 0u;
+    auto ins_lds = [&](uint32_t vis) {
+        return (p.lone ? insert_spec_lds_bytes(in.chunks, in.efc, in.M0, vis, p.spec_prefetch, p.spec_cache) : insert_lds_bytes(in.chunks, in.efc, in.M0, vis)) + p.screen_lds;
+    };
+    while(ivis && ins_lds(ivis) > (p.lone ? 96u : 31u) * 1024) ivis = ivis > 256 ? ivis - 256 : 0;  // (one workgroup per CU in the lone-walk shape)
+    if(ivis && ivis < 4 * in.M0) ivis = 0;
+    p.vis_slots = ivis;
+    p.lds = ins_lds(ivis);
+    if(p.lds > 160 * 1024) p.refusal = "lantern_gpu: ef_construction/dimensions exceed the 160 KiB LDS budget";
+    return p;
+}
+
 static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowShard *rs = nullptr)
 {
     const size_t first = ix->n;
@@ -585,10 +621,22 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
     prof_mark(ix, 0);
     HIPCHK(ix, launch_batch_layout(ix->d_levels + first, (uint32_t)b, ix->M, d_link_off, d_item_node, ix->stream));
 
-    // A handful of insertions -- ldb_aminsert's one row, the first batches of a build -- walk alone on their CUs: level 0 by the
-    // lone-query walk (insert_spec_kernel.hip), up to two insertions per CU one after the other (LANTERN_GPU_INSERT_SPEC=0: off).
+    // the launch's shape: plan_insert (above).  LANTERN_GPU_INSERT_SPEC=0: no lone-insertion walk; LANTERN_GPU_INSERT_VIS_SLOTS: the LDS
+    // visited set's size, for tuning
     static const bool ins_spec_env = !(std::getenv("LANTERN_GPU_INSERT_SPEC") && std::atoi(std::getenv("LANTERN_GPU_INSERT_SPEC")) == 0);
-    const bool ins_spec = ins_spec_env && !comm && !rs && b_hi - b_lo <= (size_t)ix->num_cus * 2 && insert_spec_supported(ix->mcode, ix->efc, ix->M0) && !search_env().lds_list;
+    InsertPlanIn pin;
+    pin.mcode = ix->mcode, pin.num_cus = ix->num_cus, pin.waves = ix->insert_waves;
+    pin.chunks = ix->chunks, pin.M0 = ix->M0, pin.efc = ix->efc;
+    pin.rows = b_hi - b_lo;
+    pin.screen_table = ix->d_screen && ix->d_screen_meta;
+    pin.mode = ix->insert_screen;
+    pin.lds_list = search_env().lds_list;
+    pin.only_upper = rs != nullptr;
+    pin.lone_ok = ins_spec_env && !comm && !rs;
+    if(const char *vs = std::getenv("LANTERN_GPU_INSERT_VIS_SLOTS")) pin.vis_slots_env = std::max(0, std::atoi(vs));
+    const InsertPlan ip = plan_insert(pin);
+    if(ip.refusal) { set_err(ix, ip.refusal); return false; }
+    const bool ins_spec = ip.lone;
     const int  ins_waves = ins_spec ? 11 : ix->insert_waves;
     const int  grid = ins_spec ? (int)std::max<size_t>(1, std::min<size_t>(b_hi - b_lo, (size_t)ix->num_cus)) : search_grid(ix, b_hi - b_lo, ix->insert_waves, 20);
     if(!ensure_bitmaps(ix, (size_t)grid)) return false;
@@ -597,6 +645,7 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
 
     InsertArgs ia;
     ia.view = ix->view();  // size/entry/max_level as they were BEFORE the batch
+    if(!ip.screened) ia.view.screen = nullptr, ia.view.screen_meta = nullptr, ia.view.screen_chunks = 0;  // no planes' block: the launch does not screen
     ia.first_slot = (uint32_t)first;
     ia.b_begin = (uint32_t)b_lo;
     ia.count = (uint32_t)b_hi;
@@ -607,27 +656,18 @@ static bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowS
     ia.bitmaps = ix->d_bitmaps;
     ia.bm_words = (uint32_t)ix->bm_words;
     ia.undo_cap = vis_undo_cap();
-    ia.lds_list = search_env().lds_list;
+    ia.lds_list = pin.lds_list;
     ia.only_upper = rs ? 1u : 0u;
-    // LDS visited set for the ef_construction-wide walk (spills to the bitmap when 3/4 full); env override for tuning
-    // the largest table that still lets FIVE workgroups share a CU (160 KB / 5, minus the walk's lists): 6400 slots at
-    // 768-d / efc 128, enough for the ~3700 nodes such a walk visits at the 3/4 load limit
-    uint32_t ivis = 8192;
-    if(const char *vs = std::getenv("LANTERN_GPU_INSERT_VIS_SLOTS")) ivis = (uint32_t)std::atoi(vs) / 4 * 4;
-    const int      G_ = group_lanes_for(ix->chunks), LW_ = G_ >= 32 ? 1 : G_ == 16 ? 2 : 4;  // list words a lane of a row's group fetches
-    ia.spec_prefetch = ins_spec && ix->M0 % (uint32_t)LW_ == 0 && ix->M0 <= (uint32_t)(G_ * LW_) ? 1u : 0u;
-    ia.spec_cache = ia.spec_prefetch ? 128u : 0u;
-    auto ins_lds = [&](uint32_t vis) {
-        return ins_spec ? insert_spec_lds_bytes(ix->chunks, ix->efc, ix->M0, vis, ia.spec_prefetch, ia.spec_cache) : insert_lds_bytes(ix->chunks, ix->efc, ix->M0, vis);
-    };
-    while(ivis && ins_lds(ivis) > (ins_spec ? 96u : 31u) * 1024) ivis = ivis > 256 ? ivis - 256 : 0;  // (one workgroup per CU in the lone-walk shape)
-    if(ivis && ivis < 4 * ix->M0) ivis = 0;
-    ia.vis_slots = ivis;
-    ia.totals = ix->d_totals + 2;
+    ia.spec_prefetch = ip.spec_prefetch;
+    ia.spec_cache = ip.spec_cache;
+    ia.vis_slots = ip.vis_slots;
+    ia.totals = ix->d_totals + 2;  // (a screened launch: and [kInsertScreenTotals..+1] from there)
     ia.ticket = next_ticket(ix, b_hi - b_lo, grid, ix->stream);
-    if(ins_lds(ivis) > 160 * 1024) { set_err(ix, "lantern_gpu: ef_construction/dimensions exceed the 160 KiB LDS budget"); return false; }
     if(ins_spec) HIPCHK(ix, launch_insert_spec(ix->mcode, ia, ins_waves, grid, ix->stream));
-    else HIPCHK(ix, launch_insert(ix->mcode, ia, ix->insert_waves, grid, ix->stream));
+    else {
+        HIPCHK(ix, launch_insert(ix->mcode, ia, ix->insert_waves, grid, ix->stream));
+        (ip.screened ? ix->insert_launches_screened : ix->insert_launches_plain) += 1;
+    }
     if(rs && !row_shard_candidates(ix, *rs, first, b, d_link_off, d_tops, d_top_count)) return false;  // level 0: from the shards' graphs
     prof_mark(ix, 1);
 
@@ -1500,6 +1540,8 @@ try {
     {
         const char *se = std::getenv("LANTERN_GPU_SCREEN");
         ix->screen = LGPU_SCREEN && (ix->mcode == M_L2SQ || ix->mcode == M_COS) && !ix->pq && screen_rows_for(ix->chunks) && !(se && std::atoi(se) == 0);
+        const char *ie = std::getenv("LANTERN_GPU_INSERT_SCREEN");  // ... in the insertion walk: the initial mode (lantern_gpu_set_insert_screen)
+        ix->insert_screen = ie ? (std::atoi(ie) != 0 ? 1 : 0) : (kInsertScreenByDefault ? 1 : 0);
     }
     return ix;
 }
@@ -2892,6 +2934,49 @@ try {
     if(exact) *exact = t[ 1 ];
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_set_insert_screen(usearch_index_t h, int mode, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(mode != 0 && mode != 1) { FAIL(e, "lantern_gpu: insert screen mode must be 0 (off) or 1 (on)"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->insert_screen = mode;  // (an index without a screen table: no launch qualifies, plan_insert)
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_insert_screen_stats(usearch_index_t h, uint64_t out[ 4 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(!out) { FAIL(e, "lantern_gpu: null array"); return; }
+    out[ 0 ] = out[ 1 ] = out[ 2 ] = out[ 3 ] = 0;
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    unsigned long long t[ 2 ] = {};
+    if(hipDeviceSynchronize() != hipSuccess || hipMemcpy(t, ix->d_totals + 2 + kInsertScreenTotals, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) {
+        FAIL(e, "lantern_gpu: HIP failure reading the screen counters");
+        return;
+    }
+    out[ 0 ] = ix->insert_launches_screened, out[ 1 ] = ix->insert_launches_plain, out[ 2 ] = t[ 0 ], out[ 3 ] = t[ 1 ];
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+// the k_insert plan without a device (include/lantern_gpu.h has the field order)
+const char *lantern_gpu_plan_insert(const int64_t in[ 13 ], uint32_t out[ 7 ])
+{
+    if(!in || !out) return "lantern_gpu: null array";
+    lgpu::InsertPlanIn s;
+    s.mcode = (int)in[ 0 ]; s.chunks = (uint32_t)in[ 1 ]; s.M0 = (uint32_t)in[ 2 ]; s.efc = (uint32_t)in[ 3 ]; s.rows = (size_t)in[ 4 ];
+    s.num_cus = (int)in[ 5 ]; s.waves = (int)in[ 6 ]; s.screen_table = in[ 7 ] != 0; s.mode = (int)in[ 8 ]; s.lds_list = in[ 9 ] != 0;
+    s.only_upper = in[ 10 ] != 0; s.lone_ok = in[ 11 ] != 0; s.vis_slots_env = (int)in[ 12 ];
+    const lgpu::InsertPlan p = lgpu::plan_insert(s);
+    const uint32_t flat[ 7 ] = { p.screened ? 1u : 0u, p.vis_slots, (uint32_t)p.lds, p.screen_lds, p.lone ? 1u : 0u, p.spec_prefetch, p.spec_cache };
+    std::copy(std::begin(flat), std::end(flat), out);
+    return p.refusal;
+}
 
 // diagnostics: the stored int8 screen of slots [first, first + count) as the device holds it (tests/test_gpu_screen_rows.py)
 size_t lantern_gpu_export_screen(usearch_index_t h, size_t first, size_t count, int8_t *rows, float *meta, float *norms, usearch_error_t *e)

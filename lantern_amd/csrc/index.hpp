@@ -118,7 +118,11 @@ struct Index
     uint32_t *d_tickets = nullptr;  // ring of work tickets, one per launch in flight (kernels.hpp SearchArgs::ticket)
     uint32_t  ticket_next = 0;
     bool      use_tickets = true;   // LANTERN_GPU_TICKETS=0: static striding (tuning / debugging)
-    unsigned long long *d_totals = nullptr;  // [0..1] search D,E  [2..4] insert D,E,refine  [5] revlink pairs
+    unsigned long long *d_totals = nullptr;  // [0..1] search D,E  [2..4] insert D,E,refine  [5] revlink pairs  [8..47] profiles  [48..49] the
+                                             // searches' screen  [50..51] k_insert's screen: rows tested, rows rejected
+    // the int8 screen in the insertion walk (plan_insert below; lantern_gpu_set_insert_screen): 0 off, 1 on where the launch qualifies
+    int      insert_screen = 0;
+    uint64_t insert_launches_screened = 0, insert_launches_plain = 0;  // k_insert launches since init (lantern_gpu_insert_screen_stats)
 
     // scratch (grown on demand): device buffers named by ScratchSlot (below the struct)
     static const int kLanes = kIndexLanes;   // lantern_gpu_search_batch_lane: batches one caller each may keep in flight side by side
@@ -331,6 +335,28 @@ struct SearchPlan
 };
 SearchPlan   plan_search(const SearchPlanIn &in);  // pure: no HIP runtime call, no Index, no getenv, no allocation
 SearchPlanIn search_plan_in(const Index *ix, size_t nq, size_t k, size_t ef, size_t skip, int waves);  // the index's fields, the call, search_env()
+// ---- the k_insert launch of a batch (index.cpp run_batch): a pure plan, shown without a device by lantern_gpu_plan_insert -----------
+struct InsertPlanIn
+{
+    int      mcode = 0, num_cus = 0, waves = 0;
+    uint32_t chunks = 0, M0 = 0, efc = 0;
+    size_t   rows = 0;             // the batch members this launch walks
+    bool     screen_table = false; // the index has an int8 screen (d_screen)
+    int      mode = 0;             // Index::insert_screen
+    bool     lds_list = false;     // LANTERN_GPU_LDS_LIST
+    bool     only_upper = false;   // the row-sharded build: no level-0 walk
+    bool     lone_ok = false;      // a handful of rows may take the lone-insertion walk (one index, LANTERN_GPU_INSERT_SPEC != 0)
+    int      vis_slots_env = -1;   // LANTERN_GPU_INSERT_VIS_SLOTS, or -1
+};
+struct InsertPlan
+{
+    bool        screened = false;  // k_insert<.., SCREEN = true>: the planes' block is part of lds and came out of vis_slots
+    bool        lone = false;      // the lone-insertion walk (insert_spec_kernel.hip), never screened
+    uint32_t    vis_slots = 0, screen_lds = 0, spec_prefetch = 0, spec_cache = 0;
+    size_t      lds = 0;           // dynamic LDS of a workgroup
+    const char *refusal = nullptr;
+};
+InsertPlan plan_insert(const InsertPlanIn &in);  // pure: no HIP runtime call, no Index, no getenv, no allocation
 // the table of a per-query-parameter launch (search_params_locked)
 struct EachLaunch
 {

@@ -19,15 +19,23 @@ namespace lgpu {
 // k_insert: the WALK half of an insertion.  Per new vector: descent to its level, then per level an
 // ef_construction-wide search_level whose sorted result (<= efc keys) goes to HBM for k_connect.  The start of
 // the next lower level is connect_new_node_'s first pick: the closest result under (distance, tie_mix).
-template <int METRIC, int G, int KPL = 2>  // KPL: as k_search (keys per lane of wave 0's register list; 0 = LDS list)
+// SCREEN (f32 l2sq / cosine rows of >= 128 chunks, the register list: launch_insert below): level 0 tests its candidates on the int8
+// row copy first, as k_search does (walk.hpp hop_distances_screened); the launch has the planes' block behind its visited set.
+template <int METRIC, int G, int KPL = 2, bool SCREEN = false>  // KPL: as k_search (keys per lane of wave 0's register list; 0 = LDS list)
 #ifndef LGPU_INSERT_MIN_BLOCKS
 #define LGPU_INSERT_MIN_BLOCKS 6  // (measured: 5 and 4 -- 81 / 90 registers, no spills -- build at the same speed; DESIGN_HISTORY.md H.2 item 1)
 #endif
 // [r6] the cosine walks are compiled for the FIVE workgroups per CU that k_insert's LDS lets run anyway (<= 96 VGPRs): with the blocked row
 // loads they spill at 80 (48 bytes of scratch, reloads inside a hop) -- same-box A/B at 1M x 768: walk 742 -> 691 ms, 949 -> 993 k vectors/s;
 // the other metrics measure the same or slower at five (profiles/r06_row_block_ab.jsonl, second table)
-__global__ void __launch_bounds__(512, (METRIC % 100 == M_COS) ? 5 : LGPU_INSERT_MIN_BLOCKS) k_insert(InsertArgs a)
+// The screened walks are compiled for five whatever the metric: k_insert's LDS (31 KB: index.cpp plan_insert) lets five workgroups share a
+// CU anyway, and at six the l2sq form spills 21 / 24 VGPRs (80 / 92 bytes of scratch) against 3 / 8 (16 / 36 bytes) at five
+#ifndef LGPU_INSERT_SCREEN_MIN_BLOCKS
+#define LGPU_INSERT_SCREEN_MIN_BLOCKS 5
+#endif
+__global__ void __launch_bounds__(512, SCREEN ? LGPU_INSERT_SCREEN_MIN_BLOCKS : (METRIC % 100 == M_COS) ? 5 : LGPU_INSERT_MIN_BLOCKS) k_insert(InsertArgs a)
 {
+    static_assert(!SCREEN || ((METRIC == M_L2SQ || METRIC == M_COS) && G == 64 && KPL > 0), "the screen serves the f32 l2sq and cosine walks over rows of >= 128 chunks, list in registers");
     const int tid = threadIdx.x, T = blockDim.x;
     WalkLds   s;
     carve_walk(lgpu_smem, s, a.view.chunks, a.efc, a.view.M0, a.vis_slots);
@@ -44,14 +52,25 @@ __global__ void __launch_bounds__(512, (METRIC % 100 == M_COS) ? 5 : LGPU_INSERT
             for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = own[ i ];
             for(uint32_t i = tid; i <= (uint32_t)target; i += T) a.top_count[ item0 + i ] = 0;  // levels above max_level stay empty
             if(tid == 0) s.scal[ S_QN2 ] = __float_as_int(row_norm<METRIC>(a.view, me));     // the "query" is a stored row
+            if constexpr(SCREEN) {  // (walk.hpp S_SCREEN: the screen's tables, and this vector's counts, live in LDS)
+                if(tid == 0) {
+                    uint64_t *const sp = (uint64_t *)&s.scal[ S_SCREEN ];
+                    sp[ 0 ] = (uint64_t)a.view.screen;
+                    sp[ 1 ] = (uint64_t)a.view.screen_meta;
+                    s.scal[ S_NREJ ] = 0;
+                    s.scal[ S_NTEST ] = 0;
+                }
+            }
         }
         __syncthreads();
+        if constexpr(SCREEN) screen_stage_query<METRIC>(tid, s, chunks, __int_as_float(s.scal[ S_QN2 ]));  // (ends in a barrier)
         uint32_t D = 0, E = 0;
         const int lowest = a.only_upper ? 1 : 0;  // (block-uniform: a node of level 0 has nothing to walk then)
         uint32_t cur = target >= lowest ? greedy_descent<METRIC, G>(a.view, s, a.view.entry, a.view.max_level, target, D) : 0u;
         for(int level = target < a.view.max_level ? target : a.view.max_level; level >= lowest; --level) {
             int cnt;
-            if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
+            if constexpr(SCREEN) cnt = search_level_reg<METRIC, G, KPL, false, 2, true, true>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
+            else if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
             else cnt = search_level<METRIC, G>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
             uint64_t *top = a.tops + (size_t)(item0 + (uint32_t)level) * a.efc;
             for(int i = tid; i < cnt; i += T) top[ i ] = s.keys[ i ] & ~1ull;  // drop the "expanded" bit
@@ -75,6 +94,10 @@ __global__ void __launch_bounds__(512, (METRIC % 100 == M_COS) ? 5 : LGPU_INSERT
             if(a.totals) {
                 atomicAdd(&a.totals[ 0 ], (unsigned long long)D);
                 atomicAdd(&a.totals[ 1 ], (unsigned long long)E);
+                if constexpr(SCREEN) {
+                    atomicAdd(&a.totals[ kInsertScreenTotals ], (unsigned long long)(uint32_t)s.scal[ S_NTEST ]);
+                    atomicAdd(&a.totals[ kInsertScreenTotals + 1 ], (unsigned long long)(uint32_t)s.scal[ S_NREJ ]);
+                }
             }
             s.scal[ S_POS ] = a.ticket ? (int)(a.b_begin + gridDim.x + atomicAdd(a.ticket, 1u)) : (int)(b + gridDim.x);
         }
@@ -88,7 +111,9 @@ size_t insert_lds_bytes(uint32_t chunks, uint32_t efc, uint32_t M0, uint32_t vis
 
 hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, hipStream_t stream)
 {
-    const size_t lds = insert_lds_bytes(a.view.chunks, a.efc, a.view.M0, a.vis_slots);
+    // (a view with a screen: the launch screens -- index.cpp passes the screen only where plan_insert planned the planes' block)
+    const bool   screened = a.view.screen != nullptr;
+    const size_t lds = insert_lds_bytes(a.view.chunks, a.efc, a.view.M0, a.vis_slots) + (screened ? screen_query_lds_bytes(a.view.chunks) : 0);
     const int    kpl = a.lds_list ? 0 : a.efc <= 64 ? 1 : a.efc <= 128 ? 2 : 0;
 #define LGPU_LAUNCH_INSERT(...)                                                                                        \
     {                                                                                                                  \
@@ -101,6 +126,15 @@ hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, h
         if(kpl == 1) LGPU_LAUNCH_INSERT(MM, GG, 1) \
         else if(kpl == 2) LGPU_LAUNCH_INSERT(MM, GG, 2) \
         else LGPU_LAUNCH_INSERT(MM, GG, 0)         \
+    }
+    if(screened) {  // the four screened instantiations: f32 l2sq / cosine, 64 lanes per row, the register list, a split walk
+        if(kpl == 0 || group_lanes_for(a.view.chunks) != 64 || waves < 2 || !a.view.screen_meta || a.only_upper) return hipErrorInvalidValue;
+        if(metric == M_L2SQ && kpl == 1) LGPU_LAUNCH_INSERT(M_L2SQ, 64, 1, true)
+        else if(metric == M_L2SQ) LGPU_LAUNCH_INSERT(M_L2SQ, 64, 2, true)
+        else if(metric == M_COS && kpl == 1) LGPU_LAUNCH_INSERT(M_COS, 64, 1, true)
+        else if(metric == M_COS) LGPU_LAUNCH_INSERT(M_COS, 64, 2, true)
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
     }
     LGPU_DISPATCH(metric, a.view.chunks, CALL);
 #undef CALL

@@ -97,12 +97,16 @@ struct InsertArgs
     uint32_t        bm_words;
     uint32_t        undo_cap;
     uint32_t        vis_slots;   // LDS visited-set slots (0 = HBM bitmap only)
-    unsigned long long *totals;  // [2] cumulative D, E
+    unsigned long long *totals;  // [2] cumulative D, E (and, screened launches, [kInsertScreenTotals..+1] below)
     uint32_t       *ticket;      // as SearchArgs::ticket, over the batch members
     int             lds_list;    // as SearchArgs::lds_list
     uint32_t        spec_prefetch, spec_cache;  // the latency-bound form (insert_spec_kernel.hip): as SearchArgs'
     uint32_t        only_upper = 0;  // k_insert only: 1 = walk levels >= 1 only (the row-sharded build takes a node's level-0 candidates from the shards)
 };
+// k_insert's screened launches (view.screen set) add the rows they put to the int8 screen test, and the rows it rejected, to two words
+// of the block InsertArgs::totals points into: totals[kInsertScreenTotals], [+ 1] = Index::d_totals[50..51]
+// (lantern_gpu_insert_screen_stats).  An offset rather than a field: the argument block of the unscreened kernels stays as it was.
+constexpr int kInsertScreenTotals = 48;
 
 // neighbour selection of the new nodes: one item per (new node, level)
 struct ConnectArgs

@@ -32,7 +32,8 @@ enum { S_POS = 0, S_NNEW, S_CNT, S_ANY, S_BAD, S_CUR, S_CURD, S_CHANGED, S_VISCN
        // search_level_reg's int8 screen, in slots that walk leaves alone: the screened hop's survivor count, the walk's rejected rows,
        // and (set by k_search before the walk) two u64: View::screen and View::screen_meta -- in LDS rather than in scalar registers,
        // which the hop loop has none of to spare
-       S_NSURV = S_ANY0, S_NREJ = S_ANY1, S_SCREEN = S_MASK };
+       S_NSURV = S_ANY0, S_NREJ = S_ANY1, S_SCREEN = S_MASK,
+       S_NTEST = 15 };  // TALLY (k_insert's screened walks): the rows the walk put to the screen test
 // S_QN2: ||query||^2 as float bits (cosine metrics; set by the kernel before a walk: device_common.hpp "cached row norms")
 
 struct WalkLds
@@ -569,7 +570,7 @@ template <int METRIC> __device__ __forceinline__ void screen_stage_query(const i
 #ifndef LGPU_SCREEN_NB
 #define LGPU_SCREEN_NB 3
 #endif
-template <int METRIC, int G, int ROWS>
+template <int METRIC, int G, int ROWS, bool TALLY = false>
 __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s, int nnew, uint64_t worst, float qn2)
 {
     static_assert(METRIC == M_L2SQ || METRIC == M_COS, "the screen serves the f32 l2sq and cosine walks");
@@ -660,7 +661,10 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
     }
     __syncthreads();
     const int ns = s.scal[ S_NSURV ];
-    if(tid == 0) s.scal[ S_NREJ ] += nnew - ns;
+    if(tid == 0) {
+        s.scal[ S_NREJ ] += nnew - ns;
+        if constexpr(TALLY) s.scal[ S_NTEST ] += nnew;
+    }
     return ns;
 }
 
@@ -835,8 +839,8 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l)  // l uniform
     }
 // SCREEN (k_search over f32 l2sq or cosine rows of >= 128 chunks, never the instrumented walk): level 0 of a split walk whose screen pointer
 // (s.scal[S_SCREEN]) is set runs the hops whose list is full through hop_distances_screened, counting the rows it rejected in
-// s.scal[S_NREJ].
-template <int METRIC, int G, int KPL, bool PROF = false, int ROWS = 2, bool SCREEN = false>
+// s.scal[S_NREJ] -- and, TALLY, the rows it tested in s.scal[S_NTEST] (k_insert: insert_kernel.hip).
+template <int METRIC, int G, int KPL, bool PROF = false, int ROWS = 2, bool SCREEN = false, bool TALLY = false>
 __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uint32_t bm_words, uint32_t start, int level, int ef,
                                 uint32_t &D, uint32_t &E, unsigned long long *prof = nullptr)
 {
@@ -1061,7 +1065,7 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
         if constexpr(SCREEN) {  // one copy of the exact phase: over the screen's survivors, or over all rows
             const uint64_t radius = screen_on ? worst_pub[ par ^ 1 ] : ~0ull;
             int            ne = nnew;
-            if(radius != ~0ull) ne = hop_distances_screened<METRIC, G, ROWS>(v, s, nnew, radius, qn2);
+            if(radius != ~0ull) ne = hop_distances_screened<METRIC, G, ROWS, TALLY>(v, s, nnew, radius, qn2);
             hop_distances<METRIC, G, ROWS, false, true>(v, s, ne, qn2, ~0ull, nullptr, radius != ~0ull ? (const uint32_t *)s.sorted : nullptr);
         } else {
             hop_distances<METRIC, G, ROWS, false>(v, s, nnew, qn2, ~0ull, nullptr);
