@@ -484,6 +484,10 @@ LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search(const int64_t in[31], uin
  * plans the index without one): in[32], out[13].  out[12]: the bytes of the query's int8 planes in the workgroup's LDS, != 0 iff the
  * launch screens; they are part of out[6] and come out of out[5]. */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search_screen(const int64_t in[32], uint32_t out[13]);
+/* ... with the switch of the screened launches' list prefetch: in[33], [32] = LANTERN_GPU_SCREEN_LIST_PREFETCH (-1: unset, 0, 1; read
+ * on every call); out[14], [13] != 0: the visit wave requests the front's level-0 list one hop ahead.  Only a launch that screens
+ * (out[12] != 0) ever does; every other launch is planned as by lantern_gpu_plan_search. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search_screen_prefetch(const int64_t in[33], uint32_t out[14]);
 
 /* Gathered distances: out[i] = metric(query, row(slots[i])) -- the kernel the graph walk is
  * made of, exposed for tests and profiling.  Host buffers. */

@@ -99,7 +99,7 @@ EXPORTS = [
     "lantern_gpu_comm_init_local", "lantern_gpu_comm_free", "lantern_gpu_comm_rank", "lantern_gpu_comm_world",
     "lantern_gpu_comm_set_timeout", "lantern_gpu_comm_stats", "lantern_gpu_comm_allgatherv_host",
     "lantern_gpu_comm_allgatherv_device", "lantern_gpu_shard_range", "lantern_gpu_add_sharded", "lantern_gpu_add_row_sharded", "lantern_gpu_search_partitioned", "lantern_gpu_search_batch_lane", "lantern_gpu_search_batch_lane_notify", "lantern_gpu_row_bytes",
-    "lantern_gpu_level_for", "lantern_gpu_plan_batch", "lantern_gpu_row_shard_plan", "lantern_gpu_plan_search", "lantern_gpu_plan_search_screen",
+    "lantern_gpu_level_for", "lantern_gpu_plan_batch", "lantern_gpu_row_shard_plan", "lantern_gpu_plan_search", "lantern_gpu_plan_search_screen", "lantern_gpu_plan_search_screen_prefetch",
     "lantern_scan_server_start", "lantern_scan_server_start_fn", "lantern_scan_server_port", "lantern_scan_server_stats",
     "lantern_scan_server_batch_histogram", "lantern_scan_server_timing", "lantern_scan_server_stop", "lantern_scan_client_connect", "lantern_scan_client_search", "lantern_scan_client_search_next",
     "lantern_scan_client_close", "lantern_scan_begin_client",
@@ -280,6 +280,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_plan_batch": (sz, [sz, i32, vp, sz, sz, sz]),
         "lantern_gpu_plan_search": (C.c_char_p, [vp, vp]),
         "lantern_gpu_plan_search_screen": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_plan_search_screen_prefetch": (C.c_char_p, [vp, vp]),
         "lantern_gpu_plan_insert": (C.c_char_p, [vp, vp]),
         "lantern_gpu_row_shard_plan": (sz, [vp, i32, u64, u32, sz, sz, vp, vp, vp, sz]),
         "lantern_scan_server_start": (vp, [vp, C.c_char_p, i32, sz, C.c_uint, err]),
@@ -1182,10 +1183,16 @@ def plan_search(fields) -> tuple[dict, str | None]:
     """The shape of the unfiltered search launch for PLAN_SEARCH_IN values (a dict or a sequence; host arithmetic, no device):
     ({PLAN_SEARCH_OUT name: value}, refusal text or None).  A dict may say "screen": 1 -- the index has an int8 screen
     (lantern_gpu_plan_search_screen); the answer then has "screen_lds" too, the bytes of the query's int8 planes (0: the launch does
-    not screen)."""
+    not screen).  With "screen_list_prefetch" as well (LANTERN_GPU_SCREEN_LIST_PREFETCH: -1 unset, 0, 1; lantern_gpu_plan_search_screen_prefetch)
+    it also has "list_prefetch": the launch requests the front's neighbour list one hop ahead."""
     vals = [fields[n] for n in PLAN_SEARCH_IN] if isinstance(fields, dict) else list(fields)
     assert len(vals) == len(PLAN_SEARCH_IN)
-    if isinstance(fields, dict) and "screen" in fields:
+    if isinstance(fields, dict) and "screen_list_prefetch" in fields:
+        names = PLAN_SEARCH_OUT + ("screen_lds", "list_prefetch")
+        a = np.asarray(vals + [fields.get("screen", 0), fields["screen_list_prefetch"]], dtype=np.int64)
+        out = np.zeros(len(names), dtype=np.uint32)
+        why = lib().lantern_gpu_plan_search_screen_prefetch(_ptr(a), _ptr(out))
+    elif isinstance(fields, dict) and "screen" in fields:
         names = PLAN_SEARCH_OUT + ("screen_lds",)
         a, out = np.asarray(vals + [fields["screen"]], dtype=np.int64), np.zeros(len(names), dtype=np.uint32)
         why = lib().lantern_gpu_plan_search_screen(_ptr(a), _ptr(out))

@@ -26,6 +26,13 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 #ifndef LGPU_LIST_PREFETCH  // speculative fetch of the front's neighbour list (walk.hpp search_level_reg): 0 off, 1 rows of < 128 chunks, 2 all
 #define LGPU_LIST_PREFETCH 1
 #endif
+// ... and in the launches that screen (SCREEN instantiations of search_level_reg, any row width): 0 = not compiled in, 1 = compiled in and off
+// unless LANTERN_GPU_SCREEN_LIST_PREFETCH=1 asks, 2 = compiled in and on unless LANTERN_GPU_SCREEN_LIST_PREFETCH=0 asks (search_plan.cpp:
+// SearchArgs::list_prefetch carries the launch's choice).  The unscreened launches and the insertion walks never read it.
+// Measured on the screened hop and not adopted (profiles/screen_block6_ab.jsonl): compiled in, off.
+#ifndef LGPU_SCREEN_LIST_PREFETCH
+#define LGPU_SCREEN_LIST_PREFETCH 1
+#endif
 #ifndef LGPU_ROW_BLOCK1
 #define LGPU_ROW_BLOCK1 4
 #endif

@@ -72,6 +72,7 @@ struct SearchArgs
     // the per-query-parameter form (k_search<.., EACH = true>, lantern_gpu_search_batch_params*; with frame.qlist); NULL / 0 otherwise
     const uint4    *qparams;     // [caller's batch] {k, expansion, skip, 0} by position; `k`, `skip` above are unused, `ef` is the list's largest expansion
     uint32_t        k_stride;    // width of an answer row
+    uint32_t        list_prefetch;  // the launches that screen: request the front's neighbour list one hop ahead (walk.hpp search_level_reg; LGPU_SCREEN_LIST_PREFETCH)
 };                               // launch's queries by phase: pop | list + visited | distances | merge | descent | whole query
 
 // one reverse-link request produced by the insert pass: add `new_slot` to `close`'s list at `level`

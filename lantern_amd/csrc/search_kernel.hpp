@@ -147,7 +147,7 @@ k_search(SearchArgs)
                 if constexpr(SPEC != 0)
                     cnt = search_level_spec<METRIC, G, KPL, ROWS, (G == 64 && SPEC == 2 ? 3 : 2), SPEC == 2, PROF>(v, s, sc, bitmap, bm_words, start, ef, D, E,
                                                                                                                      PROF ? LGPU_SEARCH_ARG(ka, phase_cycles) : nullptr);
-                else if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL, PROF, ROWS, SCREEN>(v, s, bitmap, bm_words, start, 0, ef, D, E, pc);
+                else if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL, PROF, ROWS, SCREEN>(v, s, bitmap, bm_words, start, 0, ef, D, E, pc, SCREEN ? LGPU_SEARCH_ARG(ka, list_prefetch) : 0u);
                 else cnt = search_level<METRIC, G, PROF, ROWS>(v, s, bitmap, bm_words, start, 0, ef, D, E, pc);
             }
         }

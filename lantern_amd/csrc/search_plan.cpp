@@ -18,6 +18,7 @@ SearchEnv search_env()
     // LANTERN_GPU_LDS_LIST=1: walks keep their candidate list in LDS even when it fits wave 0's registers (walk.hpp search_level vs
     // search_level_reg; identical results -- the switch exists for A/B timing and for the parity test that runs both)
     if(const char *ll = std::getenv("LANTERN_GPU_LDS_LIST")) e.lds_list = std::atoi(ll) != 0;
+    if(const char *lp = std::getenv("LANTERN_GPU_SCREEN_LIST_PREFETCH")) e.screen_list_prefetch = std::atoi(lp) != 0;
     static const int  wide_env = std::getenv("LANTERN_GPU_WIDE_ROWS") ? std::atoi(std::getenv("LANTERN_GPU_WIDE_ROWS")) : -1;
     static const bool solo_auto = std::getenv("LANTERN_GPU_SOLO") && std::atoi(std::getenv("LANTERN_GPU_SOLO")) != 0;
     static const int  forced = std::getenv("LANTERN_GPU_WAVES_PER_CU") ? std::atoi(std::getenv("LANTERN_GPU_WAVES_PER_CU")) : 0;
@@ -178,6 +179,10 @@ SearchPlan plan_search(const SearchPlanIn &in)
     if(vis_slots && vis_slots < 4 * in.M0) vis_slots = 0;
     p.lds = search_lds_bytes(in.chunks, (uint32_t)expansion, in.M0, vis_slots) + spec_lds + screen_lds;
     p.screen_lds = (uint32_t)screen_lds;
+    // the front's list one hop ahead (walk.hpp search_level_reg): in the launches that screen, where the list fetch is a quarter of a hop's
+    // dependent round trips; lists of at most 64 entries (one per lane of the visit wave)
+    p.list_prefetch = screened && LGPU_SCREEN_LIST_PREFETCH != 0 && in.M0 <= 64 &&
+                      (env.screen_list_prefetch >= 0 ? env.screen_list_prefetch != 0 : LGPU_SCREEN_LIST_PREFETCH >= 2);
     if(p.lds > 160 * 1024) { p.refusal = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel"; return p; }
     p.path = pqd ? kSearchPqd : spec == 0 ? kSearchClassic : spec == 1 ? kSearchSpec1 : spec == 2 ? kSearchSpec2 : kSearchTwin;
     p.spec = spec, p.took_spec = spec != 0;
@@ -215,6 +220,7 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     a.done = done, a.done_flags = done_flags;
     a.lds_list = p.lds_list, a.wide_rows = p.wide_rows;
     a.spec = p.spec, a.spec_prefetch = p.spec_prefetch, a.spec_cache = p.spec_cache;
+    a.list_prefetch = p.list_prefetch;
     hipError_t e = hipSuccess;
     if(!p.screen_lds) a.view.screen = nullptr, a.view.screen_meta = nullptr, a.view.screen_chunks = 0;  // no planes' block: the launch does not screen
     if(adc || pqd) a.view.vec = (const uint4 *)ix->d_codes16;
@@ -353,7 +359,7 @@ bool search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const la
 }  // namespace lgpu
 
 // the plan without a device (include/lantern_gpu.h has the field order)
-static const char *plan_search_flat(const int64_t *in, bool screen, uint32_t *out, uint32_t *screen_lds)
+static const char *plan_search_flat(const int64_t *in, bool screen, uint32_t *out, uint32_t *screen_lds, int screen_list_prefetch = -1, uint32_t *list_prefetch = nullptr)
 {
     if(!in || !out) return "lantern_gpu: null array";
     lgpu::SearchPlanIn s;
@@ -366,11 +372,13 @@ static const char *plan_search_flat(const int64_t *in, bool screen, uint32_t *ou
     s.env.spec_set = in[ 21 ] != 0; s.env.spec = (int)in[ 22 ]; s.env.adc_spec_set = in[ 23 ] != 0; s.env.adc_spec = in[ 24 ] != 0;
     s.env.pq_adc = in[ 25 ] != 0; s.env.spec_waves = (int)in[ 26 ]; s.env.lds_list = in[ 27 ] != 0; s.env.wide_rows = (int)in[ 28 ];
     s.env.solo = in[ 29 ] != 0; s.env.waves_per_cu = (int)in[ 30 ];
+    s.env.screen_list_prefetch = screen_list_prefetch;
     const lgpu::SearchPlan p = lgpu::plan_search(s);
     const uint32_t flat[ 12 ] = { (uint32_t)p.path, (uint32_t)p.spec, p.expansion, (uint32_t)p.waves, (uint32_t)p.grid, p.vis_slots, (uint32_t)p.lds,
                                   p.spec_prefetch, p.spec_cache, (uint32_t)p.wide_rows, p.took_spec ? 1u : 0u, (uint32_t)p.lds_list };
     std::copy(std::begin(flat), std::end(flat), out);
     if(screen_lds) *screen_lds = p.screen_lds;
+    if(list_prefetch) *list_prefetch = p.list_prefetch;
     return p.refusal;
 }
 extern "C" const char *lantern_gpu_plan_search(const int64_t in[ 31 ], uint32_t out[ 12 ]) { return plan_search_flat(in, false, out, nullptr); }
@@ -379,4 +387,11 @@ extern "C" const char *lantern_gpu_plan_search_screen(const int64_t in[ 32 ], ui
 {
     if(!in || !out) return "lantern_gpu: null array";
     return plan_search_flat(in, in[ 31 ] != 0, out, out + 12);
+}
+// ... with in[32] = LANTERN_GPU_SCREEN_LIST_PREFETCH (-1: unset, 0, 1); out[13]: the launch requests the front's neighbour list one hop ahead
+// (only ever != 0 where out[12] != 0)
+extern "C" const char *lantern_gpu_plan_search_screen_prefetch(const int64_t in[ 33 ], uint32_t out[ 14 ])
+{
+    if(!in || !out) return "lantern_gpu: null array";
+    return plan_search_flat(in, in[ 31 ] != 0, out, out + 12, in[ 32 ] < 0 ? -1 : in[ 32 ] != 0, out + 13);
 }

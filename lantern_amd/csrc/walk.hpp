@@ -174,12 +174,17 @@ __device__ __forceinline__ void undo_record(const WalkLds &s, VisUndo &u, bool m
         u.over = true;
     }
 }
-// at the end of a walk, by the visit wave: the bitmap goes back to all-zero
+// at the end of a walk, by the visit wave: the bitmap goes back to all-zero.  FRESH_ZERO (the screened search walks, which have no VGPR
+// to spare): the zeros of the rare whole-bitmap clear are made where they are stored -- left to itself the compiler keeps a zero uint4
+// live through the whole kernel for this one loop and spills it around every row block.
+template <bool FRESH_ZERO = false>
 __device__ __forceinline__ void undo_apply(const WalkLds &s, uint32_t *bitmap, uint32_t bm_words, const VisUndo &u, int lane)
 {
     if(u.over) {
         uint4 *b4 = (uint4 *)bitmap;
-        for(uint32_t i = (uint32_t)lane; i < bm_words / 4; i += 64) b4[ i ] = make_uint4(0, 0, 0, 0);
+        uint32_t z = 0;
+        if constexpr(FRESH_ZERO) asm volatile("" : "+v"(z));
+        for(uint32_t i = (uint32_t)lane; i < bm_words / 4; i += 64) b4[ i ] = make_uint4(z, z, z, z);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // the clears reach L2 before the next walk's atomics on these words
     } else if(u.cnt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the log's own stores have left
@@ -567,7 +572,7 @@ template <int METRIC> __device__ __forceinline__ void screen_stage_query(const i
     __syncthreads();
 }
 
-#ifndef LGPU_SCREEN_NB
+#ifndef LGPU_SCREEN_NB  // uint4 of a screen row a lane requests before it consumes the first: 3 = half a 768-d row, 6 = the whole row (the insertion walks: always 3)
 #define LGPU_SCREEN_NB 3
 #endif
 template <int METRIC, int G, int ROWS, bool TALLY = false>
@@ -575,16 +580,23 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
 {
     static_assert(METRIC == M_L2SQ || METRIC == M_COS, "the screen serves the f32 l2sq and cosine walks");
     // Eight lanes per screen row, each lane's chunks requested in blocks of NB before the first of a block is consumed: a 768-d row
-    // is 48 chunks = six uint4 per lane = two blocks, and a workgroup of 256 lanes takes a hop of up to 32 new rows in one round of
-    // groups -- two memory round trips per hop (16-lane groups with two chunks in flight, then a third, over two rounds took four).
-    // Rows of up to 125 chunks (d = 2000) take more blocks, the last one partial; a chunk beyond the row is neither requested nor
-    // consumed.  Only exec-mask arithmetic stands between the loads of a block in the instruction stream, and (s, r) is requested
-    // ahead of them, in the same block.  NB = 3: the whole 768-d row in one block (NB = 6) spills more (DESIGN.md 4.3 has both builds' figures).
+    // is 48 chunks = six uint4 per lane = two blocks (NB = 3), and a workgroup of 256 lanes takes a hop of up to 32 new rows in one round
+    // of groups -- two memory round trips per hop (16-lane groups with two chunks in flight, then a third, over two rounds took four).
+    // Rows of up to 125 chunks (d = 2000) take ceil(sch / (8 NB)) blocks, the last one partial; a chunk beyond the row is neither
+    // requested nor consumed.  Only exec-mask arithmetic stands between the loads of a block in the instruction stream, and (s, r) is
+    // requested ahead of them, in the same block.  The sums are integers: the order of consumption is free.  NB = 6, the whole 768-d row
+    // in ONE block, builds with no more spills than NB = 3 did before and was measured: not faster (DESIGN.md 4.3,
+    // profiles/screen_block6_ab.jsonl), so NB stays 3.  The insertion walks (TALLY) take 3 whatever the switch says.
     // A screen chunk meets 32 B of the query's planes, 16 B of h then 16 B of l: the eight lanes of a ds_read_b128 service group read
     // addresses 32 B apart (eight bank sets: no conflict), the groups of a wave read the same addresses (broadcast).
-    constexpr int GS = 8, NB = LGPU_SCREEN_NB;
+    constexpr int GS = 8, NB = TALLY ? 3 : LGPU_SCREEN_NB;
     static_assert(G % GS == 0, "a screen group lies within one wave");
-    const int       tid = threadIdx.x, T = blockDim.x, gs = tid / GS, gsl = tid % GS, NGS = T / GS;
+    const int       tid = threadIdx.x, T = blockDim.x, gs = tid / GS, NGS = T / GS;
+    int             gsl = tid % GS;
+    // (the search walks: the lane's offset into a row is formed HERE.  Left to itself the compiler forms it once per kernel, spills it,
+    // and reloads it in front of the row block -- and the wait for a scratch reload is a wait for every load in flight, the list
+    // fetched ahead among them)
+    if constexpr(!TALLY) asm volatile("" : "+v"(gsl));
     uint32_t *const surv = (uint32_t *)s.sorted;
     // (the two tables are read through global-memory pointers: a pointer fetched from LDS is generic to the compiler, and flat loads
     // count against the LDS reads' counter as well, so every wait for a query chunk would wait for the row block too)
@@ -842,7 +854,7 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l)  // l uniform
 // s.scal[S_NREJ] -- and, TALLY, the rows it tested in s.scal[S_NTEST] (k_insert: insert_kernel.hip).
 template <int METRIC, int G, int KPL, bool PROF = false, int ROWS = 2, bool SCREEN = false, bool TALLY = false>
 __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uint32_t bm_words, uint32_t start, int level, int ef,
-                                uint32_t &D, uint32_t &E, unsigned long long *prof = nullptr)
+                                uint32_t &D, uint32_t &E, unsigned long long *prof = nullptr, uint32_t screen_list_prefetch = 0)
 {
     static_assert(!SCREEN || ((METRIC == M_L2SQ || METRIC == M_COS) && !PROF), "the screen serves the f32 l2sq and cosine walks");
 
@@ -868,8 +880,12 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
     // (one 128-byte line at M = 16) right before the distance phase and finds it in a register one hop later; a wrong guess costs the
     // line.  Level 0 only (an upper list's address needs a load of its own), lists of at most 64 entries, never in the instrumented
     // walk (its trace is the logical access sequence).  LGPU_LIST_PREFETCH: 0 off, 1 rows of fewer than 128 chunks (G < 64), 2 all.
+    // On 3 KiB rows the fetch bought nothing while a hop was five long row round trips; a SCREENED hop is three or four short ones (list,
+    // screen block(s), survivors' rows), the list a third or a quarter of the chain: there the launch says whether to fetch ahead
+    // (screen_list_prefetch = SearchArgs::list_prefetch; LGPU_SCREEN_LIST_PREFETCH != 0 compiles it in; never the insertion walks, TALLY).
     constexpr bool PF = !PROF && (LGPU_LIST_PREFETCH >= 2 || (LGPU_LIST_PREFETCH == 1 && G < 64));
-    const bool     pf_on = PF && split && level == 0 && v.M0 <= 64;
+    constexpr bool PFS = !PF && SCREEN && !TALLY && LGPU_SCREEN_LIST_PREFETCH != 0;
+    const bool     pf_on = (PF || (PFS && screen_on && screen_list_prefetch != 0)) && split && level == 0 && v.M0 <= 64;
     uint32_t       pf_node = EMPTY, pf_nb = EMPTY;
     unsigned long long tl = 0;
     if constexpr(PROF) tl = (unsigned long long)clock64();
@@ -1074,7 +1090,7 @@ __device__ int search_level_reg(const View &v, WalkLds &s, uint32_t *bitmap, uin
         __syncthreads();
         LGPU_MARK(2)
     }
-    if(visit_wave) undo_apply(s, bitmap, bm_words, undo, lane);  // the workgroup's HBM bitmap goes back to all-zero
+    if(visit_wave) undo_apply<SCREEN && !TALLY>(s, bitmap, bm_words, undo, lane);  // the workgroup's HBM bitmap goes back to all-zero
     // the result goes where the callers read it: s.keys, ascending
     if(list_wave) {
 #pragma unroll

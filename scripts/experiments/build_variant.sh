@@ -11,6 +11,7 @@ for f in lantern_amd/csrc/*.hip; do
   /opt/rocm/bin/hipcc $FLAGS $DEFS -c "$f" -o "$VAR/$b.o" &
 done
 wait
-HOST=$(ls $OBJ/*.o | grep -v -E "/(search_kernel|search_spec_kernel|search_adc_kernel|insert_kernel|insert_spec_kernel|kernels|bruteforce|grouping)\.o$")
+# (the host objects: every object of the tree's library that is not one of the kernel units recompiled above)
+HOST=$(for o in $OBJ/*.o; do [ -f "lantern_amd/csrc/$(basename "$o" .o).hip" ] || echo "$o"; done)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "gpurun_ab_$NAME.so" $VAR/*.o $HOST -lpthread -ldl
 ls -la "gpurun_ab_$NAME.so"
