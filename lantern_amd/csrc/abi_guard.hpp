@@ -22,6 +22,7 @@ constexpr const char *kAbiOom = "lantern_gpu: out of host memory";
 constexpr const char *kAbiTooLarge = "lantern_gpu: requested size exceeds what can be allocated";
 constexpr const char *kAbiException = "lantern_gpu: internal error (C++ exception stopped at the C boundary)";
 constexpr const char *kStrideMismatch = "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)";
+constexpr const char *kKindMismatch = "lantern_gpu: scalar kind of the queries does not match the index";
 
 struct Index;
 // The index behind a usearch_index_t, with HIP's current device set to the one it lives on (the current device is per host thread:

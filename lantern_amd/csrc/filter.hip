@@ -12,6 +12,7 @@
 
 #include "abi_guard.hpp"
 #include "filter.hpp"
+#include "host_trip.hpp"
 #include "index.hpp"
 
 namespace lgpu {
@@ -617,12 +618,9 @@ try {
     if(!f) return;
     Index *ix = H(h, e);
     if(!ix) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    if(!filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E }, (hipStream_t)stream))
-        FAIL(e, ix->err.c_str());
+    const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
+    device_trip(ix, stride_is(query_stride_bytes),
+                [ & ] { return filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream); }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -634,18 +632,12 @@ try {
     if(!f) return;
     Index *ix = H(h, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    HostBatch b = batch_layout(ix, Index::kLanes, nq, k);
-    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
-    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
-    bool ok = batch_upload(b);
-    ok = ok && filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream);
-    if(!batch_finish_locked(ix, b, ok, kFilteredBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
+    host_trip_sync(ix, nq, k, 0, queries, (int)kind, kFilteredBatchFailed, nullptr,
+                   [ = ](const HostBatch &b) { return filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream); }, labels,
+                   distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -668,15 +660,24 @@ try {
     CLEAR(e);
     Index *ix = FHS(h, filters, nq, e);
     if(!ix) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    if(!filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip,
-                             SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E }, (hipStream_t)stream, nullptr))
-        FAIL(e, ix->err.c_str());
+    const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
+    device_trip(ix, stride_is(query_stride_bytes), [ & ] {
+        return filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream, nullptr);
+    }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+// the filter check and the launch of the per-query host forms, of either host trip (the tables go into the staging block's extra area)
+static auto each_validate(const lantern_gpu_filter_t *const *filters, size_t nq)
+{
+    return [ = ](Index *ix) { return each_filters_ok(ix, (const Filter *const *)filters, nq); };
+}
+static auto each_launch(Index *ix, const lantern_gpu_filter_t *const *filters, size_t nq, size_t k, size_t ef)
+{
+    return [ = ](const HostBatch &b) {
+        return filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra());
+    };
+}
 
 void lantern_gpu_search_batch_filtered_each(usearch_index_t h, const lantern_gpu_filter_t *const *filters, const void *queries, size_t nq,
                                             usearch_scalar_kind_t kind, size_t k, size_t ef, usearch_label_t *labels, float *distances,
@@ -685,55 +686,26 @@ try {
     CLEAR(e);
     Index *ix = FHS(h, filters, nq, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    if(!each_filters_ok(ix, (const Filter *const *)filters, nq)) { FAIL(e, ix->err.c_str()); return; }
-    if(nq == 0 || k == 0) return;
-    HostBatch b = batch_layout(ix, Index::kLanes, nq, k, each_table_bytes(nq));
-    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
-    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
-    bool ok = batch_upload(b);
-    ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra());
-    if(!batch_finish_locked(ix, b, ok, kFilteredBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
+    host_trip_sync(ix, nq, k, each_table_bytes(nq), queries, (int)kind, kFilteredBatchFailed, each_validate(filters, nq), each_launch(ix, filters, nq, k, ef),
+                   labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
-// lantern_gpu_search_batch_lane with a filter per query: the lane's stream and page-locked block (queries | answers | the selection
-// lists and descriptor table), the index mutex held only while the copies and the launches are queued, the wait outside it.
+// lantern_gpu_search_batch_lane with a filter per query: the lane trip, the selection lists and descriptor table in the block's extra area
 void lantern_gpu_search_batch_filtered_each_lane(usearch_index_t h, int lane, const lantern_gpu_filter_t *const *filters, const void *queries,
                                                  size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef, usearch_label_t *labels,
                                                  float *distances, uint32_t *counts, usearch_error_t *e)
 try {
     CLEAR(e);
-    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    if(!lane_ok(lane, e)) return;
     Index *ix = FHS(h, filters, nq, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null buffer"); return; }
-    static thread_local std::string msg;  // (a lane's error text belongs to the calling thread: lantern_gpu_search_batch_lane)
-    msg.clear();
-    HostBatch b = batch_layout(ix, lane, nq, k, each_table_bytes(nq));
-    if(nq && k && !batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
-    bool ok = true;
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ix->err.clear();
-        if(!each_filters_ok(ix, (const Filter *const *)filters, nq)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        if(nq == 0 || k == 0) return;
-        if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ok = batch_upload(b);
-        ok = ok && filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra());
-        ok = ok && batch_download(b);
-        if(!ok) msg = ix->err.empty() ? kFilteredBatchFailed : ix->err;
-    }
-    // (whatever was queued is waited for even after a failure: the filters may be freed once this returns)
-    if(hipStreamSynchronize(b.stream) != hipSuccess && ok) { ok = false; msg = kFilteredBatchFailed; }
-    if(!ok) { FAIL(e, msg.c_str()); return; }
-    batch_unpack(b, 0, nq, labels, distances, counts);
+    host_trip_lane(ix, lane, nq, k, each_table_bytes(nq), queries, (int)kind, kFilteredBatchFailed, each_validate(filters, nq),
+                   each_launch(ix, filters, nq, k, ef), labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

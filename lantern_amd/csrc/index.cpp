@@ -6,6 +6,7 @@
 // buffer of not-yet-inserted vectors.
 #include "index.hpp"
 #include "abi_guard.hpp"
+#include "host_trip.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -1738,7 +1739,7 @@ try {
     if(!ix) return;
     Comm *comm = (Comm *)comm_;
     if(!comm) { FAIL(e, "lantern_gpu: null communicator"); return; }
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null buffer"); return; }
     std::lock_guard<std::mutex> g(ix->mu);
@@ -1941,10 +1942,6 @@ void lantern_gpu_cursor_close(lantern_gpu_cursor_t *c) { delete c; }
 // that laid its rows out at any other stride would get wrong answers and a read past the end of its buffer with no error.  The
 // stride is therefore part of the call (`_strided`) and a mismatch is refused; the form without it is accepted only where the
 // stride is unambiguous -- the index stores rows at the vector's own length rounded up to 16 bytes.
-static const char *kStrideAmbiguous =
-    "lantern_gpu: this index stores rows at a stride wider than the vector's own length (lantern_gpu_row_bytes): device-resident "
-    "queries must be handed over with their stride, through lantern_gpu_search_batch_device_strided";
-
 void lantern_gpu_search_batch_device_strided(usearch_index_t h, const void *d_queries, size_t query_stride_bytes, size_t nq, size_t k, size_t ef,
                                              size_t skip, uint64_t *d_labels, float *d_distances, uint32_t *d_slots, uint32_t *d_counts,
                                              uint64_t *d_D, uint64_t *d_E, void *stream, usearch_error_t *e)
@@ -1952,12 +1949,9 @@ try {
     CLEAR(e);
     Index *ix = H(h, e);
     if(!ix) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    if(!run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E },
-                          (hipStream_t)stream, ix->search_waves))
-        FAIL(e, ix->err.c_str());
+    const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
+    device_trip(ix, stride_is(query_stride_bytes),
+                [ & ] { return run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream, ix->search_waves); }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -1968,16 +1962,23 @@ try {
     CLEAR(e);
     Index *ix = H(h, e);
     if(!ix) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(ix->chunks != ix->natural_chunks) { FAIL(e, kStrideAmbiguous); return; }
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    if(!run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E },
-                          (hipStream_t)stream, ix->search_waves))
-        FAIL(e, ix->err.c_str());
+    const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
+    static const char *const ambiguous =
+        "lantern_gpu: this index stores rows at a stride wider than the vector's own length (lantern_gpu_row_bytes): device-resident "
+        "queries must be handed over with their stride, through lantern_gpu_search_batch_device_strided";
+    device_trip(ix, [](const Index *x) { return x->chunks == x->natural_chunks ? nullptr : ambiguous; },
+                [ & ] { return run_search_device(ix, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream, ix->search_waves); }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
+// ---- the host forms: the refusals and the handles here, the trip in host_trip.hpp ---------------------------------------------------
 static const char *kBatchFailed = "lantern_gpu: HIP failure during batched search";
+
+// the launch of the plain forms, of either host trip
+static auto plain_launch(Index *ix, size_t nq, size_t k, size_t ef)
+{
+    return [ = ](const HostBatch &b) { return run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves); };
+}
 
 void lantern_gpu_search_batch(usearch_index_t h, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
                               usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
@@ -1985,56 +1986,25 @@ try {
     CLEAR(e);
     Index *ix = H(h, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0 || k == 0) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    HostBatch b = batch_layout(ix, Index::kLanes, nq, k);
-    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
-    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
-    bool ok = batch_upload(b);
-    ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves);
-    if(!batch_finish_locked(ix, b, ok, kBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
+    if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
+    host_trip_sync(ix, nq, k, 0, queries, (int)kind, kBatchFailed, nullptr, plain_launch(ix, nq, k, ef), labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
-// The same as lantern_gpu_search_batch for a caller that keeps SEVERAL batches in flight (the scan-side service: up to eight
-// dispatchers, each executing a batch while another collects the next): each lane has its own stream and staging buffers, the index mutex is
-// held only while the lane's copies and its launch are queued, and the wait for the answers happens outside it -- so the two
-// lanes' launches overlap on the device (each in its own visited-bitmap slab: acquire_search_slot).
+// The same for a caller that keeps several batches in flight: the lane trip (host_trip.hpp).
 void lantern_gpu_search_batch_lane(usearch_index_t h, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
                                    usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
 try {
     CLEAR(e);
     Index *ix = H(h, e);
     if(!ix) return;
-    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!lane_ok(lane, e)) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null buffer"); return; }
-    HostBatch b = batch_layout(ix, lane, nq, k);
-    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
-    bool ok = true;
-    // A lane's error text belongs to the calling thread: ix->err is shared by both lanes (and by every other entry point) and
-    // may be rewritten or cleared the moment the mutex is dropped, while the caller -- the scan service's dispatcher -- reads
-    // the message later and without the lock.
-    static thread_local std::string msg;
-    msg.clear();
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ix->err.clear();
-        if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ok = batch_upload(b);
-        ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves);
-        ok = ok && batch_download(b);
-        if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
-    }
-    // the wait is the long part: outside the mutex, so that the other lane can queue its batch meanwhile
-    if(hipStreamSynchronize(b.stream) != hipSuccess && ok) { ok = false; msg = kBatchFailed; }
-    if(!ok) { FAIL(e, msg.c_str()); return; }
-    batch_unpack(b, 0, nq, labels, distances, counts);
+    host_trip_lane(ix, lane, nq, k, 0, queries, (int)kind, kBatchFailed, nullptr, plain_launch(ix, nq, k, ef), labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2062,19 +2032,17 @@ static void lane_notify(Index *ix, int lane, const void *queries, size_t nq, use
     uint32_t *const flags = (uint32_t *)b.h_extra();
     std::memset(flags, 0, nq * 4);
     bool ok = true;
-    static thread_local std::string msg;
-    msg.clear();
     {
         std::lock_guard<std::mutex> g(ix->mu);
-        if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        if(!flush_locked(ix)) { lane_fail(e, ix->err); return; }
         ix->err.clear();
         // A service-sized batch's queries are read by the walks straight out of the page-locked block (each workgroup fetches its 3 KB
         // row over the host link once, as a lone usearch_search_ef does): no copy command in front of the kernel -- a DMA command costs
         // tens of microseconds of queueing, as much as a tenth of a walk.  Large batches are copied into HBM first, at the link's rate.
         const bool direct_queries = b.q_bytes <= (size_t)1 << 20;
-        if(!batch_device(ix, b, false)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        if(!batch_device(ix, b, false)) { lane_fail(e, ix->err); return; }
         b.d_q = direct_queries ? hs_dev : (char *)scratch(ix, lane_query_scratch(lane), b.q_bytes);
-        if(!b.d_q) { msg = ix->err; FAIL(e, msg.c_str()); return; }
+        if(!b.d_q) { lane_fail(e, ix->err); return; }
         b.d_out = hs_dev + b.out_at;  // the answers land in the block itself: nothing to copy down
         ok = direct_queries || batch_upload(b);
         if(params)
@@ -2083,10 +2051,10 @@ static void lane_notify(Index *ix, int lane, const void *queries, size_t nq, use
         else
             ok = ok && run_search_device(ix, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, ix->search_waves, nullptr,
                                          (uint32_t *)(hs_dev + b.extra_at));
-        if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
+        if(!ok) lane_fail(e, ix->err.empty() ? kBatchFailed : ix->err);
     }
     const hipStream_t st = b.stream;
-    if(!ok) { (void)hipStreamSynchronize(st); FAIL(e, msg.c_str()); return; }
+    if(!ok) { (void)hipStreamSynchronize(st); return; }
     // hand the answers on as their flags come up (outside the mutex: the other lanes queue their batches meanwhile)
     std::vector<uint32_t> pending(nq), ready;
     for(size_t i = 0; i < nq; ++i) pending[ i ] = (uint32_t)i;
@@ -2149,7 +2117,7 @@ static void lane_notify(Index *ix, int lane, const void *queries, size_t nq, use
         }
     }
     if(hipStreamSynchronize(st) != hipSuccess) ok = false;
-    if(!ok) { msg = kBatchFailed; FAIL(e, msg.c_str()); }
+    if(!ok) FAIL(e, kBatchFailed);
 }
 
 void lantern_gpu_search_batch_lane_notify(usearch_index_t h, int lane, const void *queries, size_t nq, usearch_scalar_kind_t kind, size_t k, size_t ef,
@@ -2159,8 +2127,8 @@ try {
     CLEAR(e);
     Index *ix = H(h, e);
     if(!ix) return;
-    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!lane_ok(lane, e)) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances || !done) { FAIL(e, "lantern_gpu: null buffer or callback"); return; }
     lane_notify(ix, lane, queries, nq, kind, k, ef, nullptr, labels, distances, counts, done, done_ctx, e);
@@ -2184,15 +2152,20 @@ try {
     CLEAR(e);
     Index *ix = PH(h, params, nq, k_stride, e);
     if(!ix) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(query_stride_bytes != (size_t)ix->chunks * 16) { FAIL(e, kStrideMismatch); return; }
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    if(!search_params_locked(ix, (const uint4 *)d_queries, nq, params, k_stride, SearchOut{ d_labels, d_distances, d_slots, d_counts, d_D, d_E },
-                             (hipStream_t)stream, ix->search_waves, nullptr, nullptr, nullptr))
-        FAIL(e, ix->err.c_str());
+    const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
+    device_trip(ix, stride_is(query_stride_bytes), [ & ] {
+        return search_params_locked(ix, (const uint4 *)d_queries, nq, params, k_stride, out, (hipStream_t)stream, ix->search_waves, nullptr, nullptr, nullptr);
+    }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+// the launch of the params forms, of either host trip: the call's table is built in the staging block's extra area
+static auto params_launch(Index *ix, size_t nq, const lantern_gpu_query_params *params, size_t k_stride)
+{
+    return [ = ](const HostBatch &b) {
+        return search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.out(b.d_out), b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
+    };
+}
 
 void lantern_gpu_search_batch_params(usearch_index_t h, const void *queries, size_t nq, usearch_scalar_kind_t kind, const lantern_gpu_query_params *params,
                                      size_t k_stride, usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
@@ -2201,17 +2174,10 @@ try {
     if(nq && k_stride && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
     Index *ix = PH(h, params, nq, k_stride, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0) return;
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    ix->err.clear();
-    HostBatch b = batch_layout(ix, Index::kLanes, nq, k_stride, params_table_bytes(nq));
-    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoStage); return; }
-    if(!batch_device(ix, b)) { FAIL(e, ix->err.c_str()); return; }
-    bool ok = batch_upload(b);
-    ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.out(b.d_out), b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
-    if(!batch_finish_locked(ix, b, ok, kBatchFailed, labels, distances, counts)) FAIL(e, ix->err.c_str());
+    host_trip_sync(ix, nq, k_stride, params_table_bytes(nq), queries, (int)kind, kBatchFailed, nullptr, params_launch(ix, nq, params, k_stride), labels,
+                   distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2220,30 +2186,14 @@ void lantern_gpu_search_batch_params_lane(usearch_index_t h, int lane, const voi
                                           uint32_t *counts, usearch_error_t *e)
 try {
     CLEAR(e);
-    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    if(!lane_ok(lane, e)) return;
     if(nq && k_stride && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null buffer"); return; }
     Index *ix = PH(h, params, nq, k_stride, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0) return;
-    HostBatch b = batch_layout(ix, lane, nq, k_stride, params_table_bytes(nq));
-    if(!batch_stage(ix, b, queries, (int)kind)) { FAIL(e, kNoLaneStage); return; }
-    bool ok = true;
-    static thread_local std::string msg;  // (a lane's error text belongs to the calling thread: lantern_gpu_search_batch_lane)
-    msg.clear();
-    {
-        std::lock_guard<std::mutex> g(ix->mu);
-        if(!flush_locked(ix)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ix->err.clear();
-        if(!batch_device(ix, b)) { msg = ix->err; FAIL(e, msg.c_str()); return; }
-        ok = batch_upload(b);
-        ok = ok && search_params_locked(ix, (const uint4 *)b.d_q, nq, params, k_stride, b.out(b.d_out), b.stream, ix->search_waves, nullptr, b.h_extra(), nullptr);
-        ok = ok && batch_download(b);
-        if(!ok) msg = ix->err.empty() ? kBatchFailed : ix->err;
-    }
-    if(hipStreamSynchronize(b.stream) != hipSuccess && ok) { ok = false; msg = kBatchFailed; }
-    if(!ok) { FAIL(e, msg.c_str()); return; }
-    batch_unpack(b, 0, nq, labels, distances, counts);
+    host_trip_lane(ix, lane, nq, k_stride, params_table_bytes(nq), queries, (int)kind, kBatchFailed, nullptr, params_launch(ix, nq, params, k_stride),
+                   labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2252,11 +2202,11 @@ void lantern_gpu_search_batch_params_lane_notify(usearch_index_t h, int lane, co
                                                  uint32_t *counts, lantern_gpu_queries_done_fn done, void *done_ctx, usearch_error_t *e)
 try {
     CLEAR(e);
-    if(lane < 0 || lane >= Index::kLanes) { FAIL(e, "lantern_gpu: lane must be in [0, 8)"); return; }
+    if(!lane_ok(lane, e)) return;
     if(nq && (!done || (k_stride && (!queries || !labels || !distances)))) { FAIL(e, "lantern_gpu: null buffer or callback"); return; }
     Index *ix = PH(h, params, nq, k_stride, e);
     if(!ix) return;
-    if(!kind_accepted(ix, (int)kind)) { FAIL(e, "lantern_gpu: scalar kind of the queries does not match the index"); return; }
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq == 0) return;
     lane_notify(ix, lane, queries, nq, kind, k_stride, 0, params, labels, distances, counts, done, done_ctx, e);
 }

@@ -249,6 +249,13 @@ struct SearchOut { uint64_t *labels; float *dists; uint32_t *slots, *counts; uin
 // multiple of 64 bytes; the answers lie the same way in their device buffer), and the stream and buffers the trip uses.  `which`
 // names them all: a lane (its own stream, staging block and device buffers: one caller at a time), or kLanes -- the index stream,
 // the index's own staging block and the per-call scratch, all three under ix->mu.  One copy up, one down, at the link's rate.
+// The pieces below are put together in three places only (host_trip.hpp: the locking rule of each is stated there, once), and every
+// lantern_gpu_search_batch* entry point is its refusals, its handles and one call with its launch as a callable:
+//   host_trip_sync   the index's own block and stream, everything under ix->mu, ended by batch_finish_locked
+//   host_trip_lane   staged without ix->mu; device buffers, upload, launch and download queued under it; the wait and the unpacking
+//                    outside it; the error text in the calling thread's own string
+//   device_trip      the caller's device memory and stream: lock, stride rule, flush, launch
+// (lane_notify, index.cpp, keeps a body of its own: device-mapped block, no download, polling.)
 struct HostBatch
 {
     size_t      nq = 0, k = 0, q_bytes = 0, out_at = 0, out_bytes = 0, extra_at = 0, extra_bytes = 0;
