@@ -1035,7 +1035,9 @@ def test_row_widths_around_every_load_block_boundary(capi, oracle, metric, chunk
 
 @pytest.mark.parametrize("kind", ["f16", "i8"])
 @pytest.mark.parametrize("metric", ["l2sq", "cos"])
-@pytest.mark.parametrize("chunks", [15, 16, 17, 47, 48, 49, 95, 96, 97, 125])  # (Lantern caps d at 2000: an i8 row has at most 125 chunks)
+# (Lantern caps d at 2000: an i8 row has at most 125 chunks.  The cap of 125 is i8's alone: an f16 row of 2000 dimensions has 250, and f16
+# rows above 125 chunks -- d = 1017 .. 2000 run the 64-lane instantiations -- are covered by tests/test_gpu_f16_wide_rows.py)
+@pytest.mark.parametrize("chunks", [15, 16, 17, 47, 48, 49, 95, 96, 97, 125])
 def test_quantised_row_widths_around_the_load_block_boundaries(capi, oracle, kind, metric, chunks):
     per_chunk = 8 if kind == "f16" else 16
     rng = np.random.default_rng(chunks + per_chunk)
