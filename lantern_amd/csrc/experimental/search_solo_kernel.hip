@@ -74,12 +74,7 @@ bool search_solo_supported(int metric, uint32_t chunks, uint32_t M, uint32_t M0,
     return (metric == M_L2SQ || metric == M_COS) && chunks >= 1 && chunks < 64 && M0 <= 32 && M0 == 2 * M && M % 4 == 0 && M >= 4 && ef <= 64 && ef >= 1;
 }
 
-#define LGPU_LAUNCH_SOLO_R(MM, GG, CC, RR)                                                            \
-    {                                                                                                 \
-        static LdsAttrCache attr_;                                                                    \
-        ensure_dynamic_lds((const void *)k_search_solo<MM, GG, CC, RR>, lds, attr_);                  \
-        hipLaunchKernelGGL((k_search_solo<MM, GG, CC, RR>), dim3(grid), dim3(64), lds, stream, a);    \
-    }
+#define LGPU_LAUNCH_SOLO_R(MM, GG, CC, RR) LGPU_LAUNCH_LDS((k_search_solo<MM, GG, CC, RR>), grid, 64, lds, stream, a)
 #define LGPU_LAUNCH_SOLO(MM, GG, CC)                                                              \
     {                                                                                             \
         if(ragged) LGPU_LAUNCH_SOLO_R(MM, GG, CC, true)                                           \
@@ -103,9 +98,7 @@ hipError_t launch_search_solo(int metric, const SearchArgs &a, int grid, hipStre
     const bool ragged = (int)a.view.chunks % G_ != 0;
     if(a.phase_cycles) {  // the diagnostic instantiation (lantern_gpu_spec_profile): f32 l2sq, 32-chunk rows (128-d)
         if(metric != M_L2SQ || G_ != 16 || cpl != 2 || ragged) return hipErrorInvalidValue;
-        static LdsAttrCache attr_;
-        ensure_dynamic_lds((const void *)k_search_solo<M_L2SQ, 16, 2, false, true>, lds, attr_);
-        hipLaunchKernelGGL((k_search_solo<M_L2SQ, 16, 2, false, true>), dim3(grid), dim3(64), lds, stream, a);
+        LGPU_LAUNCH_LDS((k_search_solo<M_L2SQ, 16, 2, false, true>), grid, 64, lds, stream, a)
         return hipGetLastError();
     }
     if(metric == M_L2SQ) {

@@ -233,7 +233,7 @@ static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, s
     a.frame.labels = ix->d_labels;
     a.frame.out_labels = out.labels, a.frame.out_dists = out.dists, a.frame.out_slots = out.slots;
     a.frame.out_counts = out.counts, a.frame.out_D = out.D, a.frame.out_E = out.E;
-    a.frame.totals = ix->d_totals;
+    a.frame.totals = ix->d_totals + kTotSearch;
     return a;
 }
 

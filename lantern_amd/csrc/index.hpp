@@ -118,9 +118,8 @@ struct Index
     uint32_t *d_tickets = nullptr;  // ring of work tickets, one per launch in flight (kernels.hpp SearchArgs::ticket)
     uint32_t  ticket_next = 0;
     bool      use_tickets = true;   // LANTERN_GPU_TICKETS=0: static striding (tuning / debugging)
-    unsigned long long *d_totals = nullptr;  // [0..1] search D,E  [2..4] insert D,E,refine  [5] revlink pairs  [8..47] profiles  [48..49] the
-                                             // searches' screen  [50..51] k_insert's screen: rows tested, rows rejected
-    // the int8 screen in the insertion walk (plan_insert below; lantern_gpu_set_insert_screen): 0 off, 1 on where the launch qualifies
+    unsigned long long *d_totals = nullptr;  // [kTotalsWords] cumulative device counters: the slots are TotalsSlot (kernels.hpp)
+    // the int8 screen in the insertion walk (plan_insert below, insert_batch.cpp; lantern_gpu_set_insert_screen): 0 off, 1 on where the launch qualifies
     int      insert_screen = 0;
     uint64_t insert_launches_screened = 0, insert_launches_plain = 0;  // k_insert launches since init (lantern_gpu_insert_screen_stats)
 
@@ -286,6 +285,15 @@ size_t    take_unseen(Cursor *cur, const uint64_t *labels, const float *dists, c
 
 // implemented in index.cpp
 const char *set_err(Index *ix, const std::string &msg);
+// `expr` failed: ix->err names it, the enclosing function returns false
+#define HIPCHK(ix, expr)                                                                  \
+    do {                                                                                  \
+        hipError_t e_ = (expr);                                                           \
+        if(e_ != hipSuccess) {                                                            \
+            set_err(ix, std::string("lantern_gpu: HIP error in " #expr ": ") + hipGetErrorString(e_)); \
+            return false;                                                                 \
+        }                                                                                 \
+    } while(0)
 bool        flush_locked(Index *ix);            // false -> ix->err set
 bool        ensure_bitmaps(Index *ix, size_t slots);
 bool        pq_encode_rows(Index *ix, size_t first, size_t count);  // raw f32 rows [first, first+count) in d_vec -> codes + decodings
@@ -344,7 +352,7 @@ struct SearchPlan
 };
 SearchPlan   plan_search(const SearchPlanIn &in);  // pure: no HIP runtime call, no Index, no getenv, no allocation
 SearchPlanIn search_plan_in(const Index *ix, size_t nq, size_t k, size_t ef, size_t skip, int waves);  // the index's fields, the call, search_env()
-// ---- the k_insert launch of a batch (index.cpp run_batch): a pure plan, shown without a device by lantern_gpu_plan_insert -----------
+// ---- the k_insert launch of a batch (insert_batch.cpp run_batch): a pure plan, shown without a device by lantern_gpu_plan_insert -----------
 struct InsertPlanIn
 {
     int      mcode = 0, num_cus = 0, waves = 0;
@@ -366,6 +374,29 @@ struct InsertPlan
     const char *refusal = nullptr;
 };
 InsertPlan plan_insert(const InsertPlanIn &in);  // pure: no HIP runtime call, no Index, no getenv, no allocation
+extern const bool kInsertScreenByDefault;  // the initial mode of Index::insert_screen where LANTERN_GPU_INSERT_SCREEN does not say
+// the environment switches of a batch, as values (insert_env, insert_batch.cpp, says which is read once per process and which on every batch)
+struct InsertEnv
+{
+    bool spec = true;            // LANTERN_GPU_INSERT_SPEC != 0: a handful of rows may take the lone-insertion walk
+    bool group_all = false;      // LANTERN_GPU_GROUP_ALL != 0
+    int  vis_slots = -1;         // LANTERN_GPU_INSERT_VIS_SLOTS (>= 0), or -1: absent
+    bool reprune_state = true;   // LANTERN_GPU_REPRUNE_STATE != 0
+    bool debug_groups = false;   // LANTERN_GPU_DEBUG_GROUPS is present
+};
+InsertEnv insert_env();
+struct Comm;
+// Row-sharded build (index.cpp add_row_sharded_locked): where a batch's level-0 candidates come from
+struct RowShard
+{
+    Index *loc;   // this rank's graph over ITS rows (labels = global slot + 1)
+    Comm  *comm;
+    size_t K;     // candidates a shard answers with per row
+    size_t ef;    // ... found with this expansion (>= K)
+};
+// one batch of b new nodes at slots [ix->n, ix->n + b) with levels lv, rows and metadata already in HBM (insert_batch.cpp); false -> ix->err
+bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowShard *rs = nullptr);
+bool sync_stream(Index *ix, Comm *comm);  // wait for the index stream (a sharded build: with the collective's deadline); false -> ix->err
 // the table of a per-query-parameter launch (search_params_locked)
 struct EachLaunch
 {

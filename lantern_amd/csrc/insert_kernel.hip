@@ -11,14 +11,15 @@
 #endif
 #include "kernels.hpp"
 #include "walk.hpp"
+#include "insert_frame.hpp"
 #include "dispatch.hpp"
 
 namespace lgpu {
 
 // ---------------------------------------------------------------------------------------------------
 // k_insert: the WALK half of an insertion.  Per new vector: descent to its level, then per level an
-// ef_construction-wide search_level whose sorted result (<= efc keys) goes to HBM for k_connect.  The start of
-// the next lower level is connect_new_node_'s first pick: the closest result under (distance, tie_mix).
+// ef_construction-wide search_level whose sorted result (<= efc keys) goes to HBM for k_connect.  What surrounds
+// the walk -- staging, publishing a level, the next level's start, the totals, the next member -- is insert_frame.hpp.
 // SCREEN (f32 l2sq / cosine rows of >= 128 chunks, the register list: launch_insert below): level 0 tests its candidates on the int8
 // row copy first, as k_search does (walk.hpp hop_distances_screened); the launch has the planes' block behind its visited set.
 template <int METRIC, int G, int KPL = 2, bool SCREEN = false>  // KPL: as k_search (keys per lane of wave 0's register list; 0 = LDS list)
@@ -28,7 +29,7 @@ template <int METRIC, int G, int KPL = 2, bool SCREEN = false>  // KPL: as k_sea
 // [r6] the cosine walks are compiled for the FIVE workgroups per CU that k_insert's LDS lets run anyway (<= 96 VGPRs): with the blocked row
 // loads they spill at 80 (48 bytes of scratch, reloads inside a hop) -- same-box A/B at 1M x 768: walk 742 -> 691 ms, 949 -> 993 k vectors/s;
 // the other metrics measure the same or slower at five (profiles/r06_row_block_ab.jsonl, second table)
-// The screened walks are compiled for five whatever the metric: k_insert's LDS (31 KB: index.cpp plan_insert) lets five workgroups share a
+// The screened walks are compiled for five whatever the metric: k_insert's LDS (31 KB: insert_batch.cpp plan_insert) lets five workgroups share a
 // CU anyway, and at six the l2sq form spills 21 / 24 VGPRs (80 / 92 bytes of scratch) against 3 / 8 (16 / 36 bytes) at five
 #ifndef LGPU_INSERT_SCREEN_MIN_BLOCKS
 #define LGPU_INSERT_SCREEN_MIN_BLOCKS 5
@@ -39,29 +40,13 @@ __global__ void __launch_bounds__(512, SCREEN ? LGPU_INSERT_SCREEN_MIN_BLOCKS : 
     const int tid = threadIdx.x, T = blockDim.x;
     WalkLds   s;
     carve_walk(lgpu_smem, s, a.view.chunks, a.efc, a.view.M0, a.vis_slots);
-    uint32_t *bitmap = a.bitmaps + (size_t)blockIdx.x * (a.bm_words + kVisUndoWords);
-    s.undo = bitmap + a.bm_words;
-    s.undo_cap = a.undo_cap;
+    uint32_t *bitmap = insert_bind(a, s);
     const uint32_t chunks = a.view.chunks, M = a.view.M;
     for(uint32_t b = a.b_begin + blockIdx.x; b < a.count;) {
         const uint32_t me = a.first_slot + b;
         const int      target = a.view.levels[ me ];
         const uint32_t item0 = a.link_off[ b ] / M;  // one item per (node, level)
-        {
-            const uint4 *own = row_of(a.view, me);
-            for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = own[ i ];
-            for(uint32_t i = tid; i <= (uint32_t)target; i += T) a.top_count[ item0 + i ] = 0;  // levels above max_level stay empty
-            if(tid == 0) s.scal[ S_QN2 ] = __float_as_int(row_norm<METRIC>(a.view, me));     // the "query" is a stored row
-            if constexpr(SCREEN) {  // (walk.hpp S_SCREEN: the screen's tables, and this vector's counts, live in LDS)
-                if(tid == 0) {
-                    uint64_t *const sp = (uint64_t *)&s.scal[ S_SCREEN ];
-                    sp[ 0 ] = (uint64_t)a.view.screen;
-                    sp[ 1 ] = (uint64_t)a.view.screen_meta;
-                    s.scal[ S_NREJ ] = 0;
-                    s.scal[ S_NTEST ] = 0;
-                }
-            }
-        }
+        insert_stage<METRIC, SCREEN>(tid, T, a, s, me, item0, target, chunks);
         __syncthreads();
         if constexpr(SCREEN) screen_stage_query<METRIC>(tid, s, chunks, __int_as_float(s.scal[ S_QN2 ]));  // (ends in a barrier)
         uint32_t D = 0, E = 0;
@@ -72,38 +57,9 @@ __global__ void __launch_bounds__(512, SCREEN ? LGPU_INSERT_SCREEN_MIN_BLOCKS : 
             if constexpr(SCREEN) cnt = search_level_reg<METRIC, G, KPL, false, 2, true, true>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
             else if constexpr(KPL > 0) cnt = search_level_reg<METRIC, G, KPL>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
             else cnt = search_level<METRIC, G>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
-            uint64_t *top = a.tops + (size_t)(item0 + (uint32_t)level) * a.efc;
-            for(int i = tid; i < cnt; i += T) top[ i ] = s.keys[ i ] & ~1ull;  // drop the "expanded" bit
-            if(tid == 0) {
-                a.top_count[ item0 + (uint32_t)level ] = (uint32_t)cnt;
-                // sel[0] of the heuristic = minimum by (distance, tie_mix(slot, me)): only an exact tie at the
-                // smallest distance can differ from keys[0]
-                const uint32_t d0 = (uint32_t)(s.keys[ 0 ] >> 32);
-                uint32_t       best = key_slot(s.keys[ 0 ]);
-                for(int i = 1; i < cnt && (uint32_t)(s.keys[ i ] >> 32) == d0; ++i) {
-                    const uint32_t id = key_slot(s.keys[ i ]);
-                    if(tie_mix(id, me) < tie_mix(best, me)) best = id;
-                }
-                s.scal[ S_CUR ] = (int)best;
-            }
-            __syncthreads();
-            cur = (uint32_t)s.scal[ S_CUR ];
-            __syncthreads();
+            cur = insert_publish_level(tid, T, a, s, me, item0 + (uint32_t)level, cnt);
         }
-        if(tid == 0) {
-            if(a.totals) {
-                atomicAdd(&a.totals[ 0 ], (unsigned long long)D);
-                atomicAdd(&a.totals[ 1 ], (unsigned long long)E);
-                if constexpr(SCREEN) {
-                    atomicAdd(&a.totals[ kInsertScreenTotals ], (unsigned long long)(uint32_t)s.scal[ S_NTEST ]);
-                    atomicAdd(&a.totals[ kInsertScreenTotals + 1 ], (unsigned long long)(uint32_t)s.scal[ S_NREJ ]);
-                }
-            }
-            s.scal[ S_POS ] = a.ticket ? (int)(a.b_begin + gridDim.x + atomicAdd(a.ticket, 1u)) : (int)(b + gridDim.x);
-        }
-        __syncthreads();
-        b = (uint32_t)s.scal[ S_POS ];
-        __syncthreads();
+        b = insert_close<SCREEN>(tid, a, s, b, D, E);
     }
 }
 
@@ -111,16 +67,11 @@ size_t insert_lds_bytes(uint32_t chunks, uint32_t efc, uint32_t M0, uint32_t vis
 
 hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, hipStream_t stream)
 {
-    // (a view with a screen: the launch screens -- index.cpp passes the screen only where plan_insert planned the planes' block)
+    // (a view with a screen: the launch screens -- insert_batch.cpp passes the screen only where plan_insert planned the planes' block)
     const bool   screened = a.view.screen != nullptr;
     const size_t lds = insert_lds_bytes(a.view.chunks, a.efc, a.view.M0, a.vis_slots) + (screened ? screen_query_lds_bytes(a.view.chunks) : 0);
     const int    kpl = a.lds_list ? 0 : a.efc <= 64 ? 1 : a.efc <= 128 ? 2 : 0;
-#define LGPU_LAUNCH_INSERT(...)                                                                                        \
-    {                                                                                                                  \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_insert<__VA_ARGS__>, lds, attr_);    \
-        hipLaunchKernelGGL((k_insert<__VA_ARGS__>), dim3(grid), dim3(64 * waves), lds, stream, a);                     \
-    }
+#define LGPU_LAUNCH_INSERT(...) LGPU_LAUNCH_LDS((k_insert<__VA_ARGS__>), grid, 64 * waves, lds, stream, a)
 #define CALL(MM, GG)                               \
     {                                              \
         if(kpl == 1) LGPU_LAUNCH_INSERT(MM, GG, 1) \

@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "walk.hpp"
 #include "walk_spec.hpp"
+#include "insert_frame.hpp"
 
 namespace lgpu {
 
@@ -25,20 +26,13 @@ __global__ void __launch_bounds__(704, 1) k_insert_spec(InsertArgs a)
         unsigned char *end = carve_walk(lgpu_smem, s, a.view.chunks, a.efc, a.view.M0, a.vis_slots);
         carve_spec(end, sc, a.view.M0, a.spec_prefetch, a.spec_cache);
     }
-    uint32_t      *bitmap = a.bitmaps + (size_t)blockIdx.x * (a.bm_words + kVisUndoWords);
-    s.undo = bitmap + a.bm_words;
-    s.undo_cap = a.undo_cap;
+    uint32_t      *bitmap = insert_bind(a, s);
     const uint32_t chunks = a.view.chunks, M = a.view.M;
     for(uint32_t b = a.b_begin + blockIdx.x; b < a.count;) {
         const uint32_t me = a.first_slot + b;
         const int      target = a.view.levels[ me ];
         const uint32_t item0 = a.link_off[ b ] / M;  // one item per (node, level)
-        {
-            const uint4 *own = row_of(a.view, me);
-            for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = own[ i ];
-            for(uint32_t i = tid; i <= (uint32_t)target; i += T) a.top_count[ item0 + i ] = 0;  // levels above max_level stay empty
-            if(tid == 0) s.scal[ S_QN2 ] = __float_as_int(row_norm<METRIC>(a.view, me));     // the "query" is a stored row
-        }
+        insert_stage<METRIC>(tid, T, a, s, me, item0, target, chunks);
         __syncthreads();
         uint32_t D = 0, E = 0;
         uint32_t cur = greedy_descent_spec<METRIC, G>(a.view, s, a.view.entry, a.view.max_level, target, D);
@@ -46,34 +40,9 @@ __global__ void __launch_bounds__(704, 1) k_insert_spec(InsertArgs a)
             int cnt;
             if(level == 0) cnt = search_level_spec<METRIC, G, KPL, ROWS, U, true, false>(a.view, s, sc, bitmap, a.bm_words, cur, (int)a.efc, D, E, nullptr);
             else cnt = search_level_reg<METRIC, G, KPL>(a.view, s, bitmap, a.bm_words, cur, level, (int)a.efc, D, E);
-            uint64_t *top = a.tops + (size_t)(item0 + (uint32_t)level) * a.efc;
-            for(int i = tid; i < cnt; i += T) top[ i ] = s.keys[ i ] & ~1ull;  // drop the "expanded" bit
-            if(tid == 0) {
-                a.top_count[ item0 + (uint32_t)level ] = (uint32_t)cnt;
-                // sel[0] of the heuristic = minimum by (distance, tie_mix(slot, me)): only an exact tie at the smallest distance
-                // can differ from keys[0]
-                const uint32_t d0 = (uint32_t)(s.keys[ 0 ] >> 32);
-                uint32_t       best = key_slot(s.keys[ 0 ]);
-                for(int i = 1; i < cnt && (uint32_t)(s.keys[ i ] >> 32) == d0; ++i) {
-                    const uint32_t id = key_slot(s.keys[ i ]);
-                    if(tie_mix(id, me) < tie_mix(best, me)) best = id;
-                }
-                s.scal[ S_CUR ] = (int)best;
-            }
-            __syncthreads();
-            cur = (uint32_t)s.scal[ S_CUR ];
-            __syncthreads();
+            cur = insert_publish_level(tid, T, a, s, me, item0 + (uint32_t)level, cnt);
         }
-        if(tid == 0) {
-            if(a.totals) {
-                atomicAdd(&a.totals[ 0 ], (unsigned long long)D);
-                atomicAdd(&a.totals[ 1 ], (unsigned long long)E);
-            }
-            s.scal[ S_POS ] = a.ticket ? (int)(a.b_begin + gridDim.x + atomicAdd(a.ticket, 1u)) : (int)(b + gridDim.x);
-        }
-        __syncthreads();
-        b = (uint32_t)s.scal[ S_POS ];
-        __syncthreads();
+        b = insert_close(tid, a, s, b, D, E);
     }
 }
 
@@ -90,12 +59,7 @@ hipError_t launch_insert_spec(int metric, const InsertArgs &a, int waves, int gr
     const size_t lds = insert_spec_lds_bytes(a.view.chunks, a.efc, a.view.M0, a.vis_slots, a.spec_prefetch, a.spec_cache);
     const int    kpl = a.efc <= 64 ? 1 : 2;
     const int    G_ = group_lanes_for(a.view.chunks);
-#define LGPU_INS1(MM, GG, KK)                                                                                                   \
-    {                                                                                                                           \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_insert_spec<MM, GG, KK>, lds, attr_);    \
-        hipLaunchKernelGGL((k_insert_spec<MM, GG, KK>), dim3(grid), dim3(64 * waves), lds, stream, a);                          \
-    }
+#define LGPU_INS1(MM, GG, KK) LGPU_LAUNCH_LDS((k_insert_spec<MM, GG, KK>), grid, 64 * waves, lds, stream, a)
 #define LGPU_INS(MM)                                                                  \
     switch(G_) {                                                                      \
         case 64: if(kpl == 1) LGPU_INS1(MM, 64, 1) else LGPU_INS1(MM, 64, 2) break;   \

@@ -1075,12 +1075,7 @@ hipError_t launch_revlink(int metric, const RevlinkArgs &a, void *work, uint32_t
         // (a work item is a group whose list overflowed: never more than there are groups -- a lone insertion has at most 2M of them,
         // and a grid of hundreds of idle 512-thread workgroups costs more to dispatch than its re-prunes take)
         const int    grid = (int)std::min<uint32_t>((uint32_t)(num_cus * (cpl3 ? 2 : 1)), a.max_groups);
-#define PAIRS_ONE(MM, CC)                                                                                                               \
-    {                                                                                                                                   \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_revlink_pairs<MM, CC>, lds, attr_);    \
-        hipLaunchKernelGGL((k_revlink_pairs<MM, CC>), dim3(grid), dim3(512), lds, stream, a, (const RevWork *)work, work_count);        \
-    }
+#define PAIRS_ONE(MM, CC) LGPU_LAUNCH_LDS((k_revlink_pairs<MM, CC>), grid, 512, lds, stream, a, (const RevWork *)work, work_count)
 #define PAIRS(MM)                                                                                                                       \
     {                                                                                                                                   \
         if(cpl == 3) PAIRS_ONE(MM, 3) else if(cpl == 4) PAIRS_ONE(MM, 4) else if(cpl == 6) PAIRS_ONE(MM, 6) else PAIRS_ONE(MM, 8)       \
@@ -1103,12 +1098,7 @@ hipError_t launch_revlink(int metric, const RevlinkArgs &a, void *work, uint32_t
         hipError_t e = work_count_is_zero ? hipSuccess : hipMemsetAsync(work_count, 0, 4, stream);
         if(e != hipSuccess) return e;
         hipLaunchKernelGGL(k_revlink_append, dim3(append_grid), dim3(256), 0, stream, a, (RevWork *)work, work_count);
-#define CALL(MM, GG)                                                                                                    \
-    {                                                                                                                   \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_revlink_staged<MM, GG>, staged, attr_);    \
-        hipLaunchKernelGGL((k_revlink_staged<MM, GG>), dim3(std::min<uint32_t>((uint32_t)(num_cus * staged_per_cu), a.max_groups)), dim3(512), staged, stream, a, (const RevWork *)work, work_count); \
-    }
+#define CALL(MM, GG) LGPU_LAUNCH_LDS((k_revlink_staged<MM, GG>), std::min<uint32_t>((uint32_t)(num_cus * staged_per_cu), a.max_groups), 512, staged, stream, a, (const RevWork *)work, work_count)
         LGPU_DISPATCH(metric, a.view.chunks, CALL);
 #undef CALL
         return hipGetLastError();

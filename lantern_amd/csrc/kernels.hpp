@@ -104,10 +104,30 @@ struct InsertArgs
     uint32_t        spec_prefetch, spec_cache;  // the latency-bound form (insert_spec_kernel.hip): as SearchArgs'
     uint32_t        only_upper = 0;  // k_insert only: 1 = walk levels >= 1 only (the row-sharded build takes a node's level-0 candidates from the shards)
 };
-// k_insert's screened launches (view.screen set) add the rows they put to the int8 screen test, and the rows it rejected, to two words
-// of the block InsertArgs::totals points into: totals[kInsertScreenTotals], [+ 1] = Index::d_totals[50..51]
-// (lantern_gpu_insert_screen_stats).  An offset rather than a field: the argument block of the unscreened kernels stays as it was.
-constexpr int kInsertScreenTotals = 48;
+// The slots of Index::d_totals, the block of cumulative device counters (atomicAdd; one allocation, zeroed at init).  A kernel gets a
+// pointer AT its range: SearchArgs / FilteredArgs frame.totals -> kTotSearch, InsertArgs::totals -> kTotInsert, ConnectArgs::totals
+// -> kTotConnect, RevlinkArgs::totals -> kTotRevlink, SearchArgs::phase_cycles -> one of the profiles, ::screen_totals -> kTotSearchScreen.
+enum TotalsSlot : int
+{
+    kTotSearch = 0,         // [2] the searches' D, E
+    kTotInsert = 2,         // [2] the insert walk's D, E
+    kTotConnect = 4,        // [1] k_connect's pair evaluations
+    kTotRevlink = 5,        // [2] the reverse links' pair evaluations, re-prunes
+    kTotPhaseProfile = 8,   // [kTotPhaseProfileWords] lantern_gpu_search_phase_profile
+    kTotSpecProfile = 16,   // [kTotSpecProfileWords] lantern_gpu_spec_profile
+    kTotSearchScreen = 48,  // [2] the searches' screen: row evaluations, of which read the f32 row
+    kTotInsertScreen = 50,  // [2] k_insert's screen: rows tested, rows rejected
+    kTotalsWords = 64       // the block's size
+};
+constexpr int kTotPhaseProfileWords = 8, kTotSpecProfileWords = 32;
+static_assert(kTotSearch + 2 <= kTotInsert && kTotInsert + 2 <= kTotConnect && kTotConnect + 1 <= kTotRevlink && kTotRevlink + 2 <= kTotPhaseProfile &&
+                  kTotPhaseProfile + kTotPhaseProfileWords <= kTotSpecProfile && kTotSpecProfile + kTotSpecProfileWords <= kTotSearchScreen &&
+                  kTotSearchScreen + 2 <= kTotInsertScreen && kTotInsertScreen + 2 <= kTotalsWords,
+              "the ranges of Index::d_totals are disjoint and inside the block");
+// k_insert's screened launches (view.screen set) add the rows they put to the int8 screen test, and the rows it rejected, to
+// kTotInsertScreen, reached from InsertArgs::totals: totals[kInsertScreenTotals], [+ 1] (lantern_gpu_insert_screen_stats).
+// An offset rather than a field: the argument block of the unscreened kernels stays as it was.
+constexpr int kInsertScreenTotals = kTotInsertScreen - kTotInsert;
 
 // neighbour selection of the new nodes: one item per (new node, level)
 struct ConnectArgs
@@ -183,6 +203,15 @@ inline void ensure_dynamic_lds(const void *fn, size_t lds, LdsAttrCache &cache)
     size_t seen = cache.set[ dev ].load(std::memory_order_relaxed);
     while(seen < lds && !cache.set[ dev ].compare_exchange_weak(seen, lds, std::memory_order_release)) {}
 }
+
+// One instantiation KERNEL (in parentheses: its template arguments hold commas): its LdsAttrCache, the opt-in to `lds_` bytes of dynamic
+// LDS, the launch with the arguments that follow.  A block, so that `if(..) LGPU_LAUNCH_LDS(..) else ..` reads as written.
+#define LGPU_LAUNCH_LDS(KERNEL, grid_, block_, lds_, stream_, ...)                                  \
+    {                                                                                               \
+        static LdsAttrCache attr_;                                                                  \
+        ensure_dynamic_lds((const void *)KERNEL, lds_, attr_);                                      \
+        hipLaunchKernelGGL(KERNEL, dim3(grid_), dim3(block_), lds_, stream_, __VA_ARGS__);          \
+    }
 
 // All launchers return hipSuccess or the launch error.  `metric` is a usearch_metric_kind_t value.
 hipError_t launch_search(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);

@@ -68,7 +68,7 @@ template <int METRIC, int G> __device__ __forceinline__ void frame_stage(const i
 template <class ARGS> __device__ __forceinline__ uint32_t *frame_bind(KernargBytes ka, WalkLds &s, uint32_t &bm_words)
 {
     bm_words = LGPU_FRAME_ARG(ka, ARGS, bm_words);
-    uint32_t *bitmap = LGPU_FRAME_ARG(ka, ARGS, bitmaps) + (size_t)blockIdx.x * (bm_words + kVisUndoWords);
+    uint32_t *bitmap = vis_slab(LGPU_FRAME_ARG(ka, ARGS, bitmaps), bm_words);
     s.undo = bitmap + bm_words;
     s.undo_cap = LGPU_FRAME_ARG(ka, ARGS, undo_cap);
     return bitmap;

@@ -169,12 +169,7 @@ hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int gri
     const int kpl = a.lds_list ? 0 : a.ef <= 64 ? 1 : a.ef <= 128 ? 2 : 0;
     if(a.spec && (kpl == 0 || waves < 4 || waves > 11 || a.view.M0 > 64 || a.view.M0 < 2)) return hipErrorInvalidValue;
     const size_t lds = search_adc_lds_bytes(a.view.chunks, a.adc_qchunks, a.ef, a.view.M0, a.frame.vis_slots) + (a.spec ? spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache) : 0);
-#define LGPU_ADC2(MM, KK, SS, EE)                                                                                               \
-    {                                                                                                                           \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_search_adc<MM, KK, SS, EE>, lds, attr_);    \
-        hipLaunchKernelGGL((k_search_adc<MM, KK, SS, EE>), dim3(grid), dim3(64 * waves), lds, stream, a);                       \
-    }
+#define LGPU_ADC2(MM, KK, SS, EE) LGPU_LAUNCH_LDS((k_search_adc<MM, KK, SS, EE>), grid, 64 * waves, lds, stream, a)
 #define LGPU_ADC1(MM, KK, SS)                                    \
     {                                                            \
         if(a.qparams) LGPU_ADC2(MM, KK, SS, true)                \

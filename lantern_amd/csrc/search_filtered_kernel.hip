@@ -428,12 +428,7 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
 }
 
 // one instantiation KERNEL<MM, GG, ...>: opt it in to its dynamic LDS size, then launch
-#define LGPU_LAUNCH_FILTERED(KERNEL, LDS_, MM, GG, ...)                                                              \
-    {                                                                                                                \
-        static LdsAttrCache attr_;                                                                                   \
-        ensure_dynamic_lds((const void *)KERNEL<MM, GG, __VA_ARGS__>, LDS_, attr_);                                  \
-        hipLaunchKernelGGL((KERNEL<MM, GG, __VA_ARGS__>), dim3(grid), dim3(64 * waves), LDS_, stream, a);            \
-    }
+#define LGPU_LAUNCH_FILTERED(KERNEL, LDS_, MM, GG, ...) LGPU_LAUNCH_LDS((KERNEL<MM, GG, __VA_ARGS__>), grid, 64 * waves, LDS_, stream, a)
 
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {

@@ -9,12 +9,7 @@
 namespace lgpu {
 
 // one instantiation: opt the kernel in to its dynamic LDS size, then launch
-#define LGPU_LAUNCH_SEARCH(...)                                                                                        \
-    {                                                                                                                  \
-        static LdsAttrCache attr_;        \
-        ensure_dynamic_lds((const void *)k_search<__VA_ARGS__>, lds, attr_);    \
-        hipLaunchKernelGGL((k_search<__VA_ARGS__>), dim3(grid), dim3(64 * waves), lds, stream, a);                     \
-    }
+#define LGPU_LAUNCH_SEARCH(...) LGPU_LAUNCH_LDS((k_search<__VA_ARGS__>), grid, 64 * waves, lds, stream, a)
 // ... for the list placement of this launch (walk.hpp search_level_reg): one key per lane of wave 0 up to ef = 64, two up to
 // 128, the LDS list beyond (or when LANTERN_GPU_LDS_LIST asks for it)
 #define LGPU_LAUNCH_SEARCH_KPL(MM, GG, PP, RR)                           \

@@ -214,8 +214,8 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     // (the one-wave walk keeps its bitmap in LDS: nothing of the slot's HBM slab is touched)
     if(!solo) a.frame.bitmaps = ix->slot_bitmaps[ slot ], a.frame.bm_words = (uint32_t)ix->slot_words[ slot ], a.frame.undo_cap = vis_undo_cap();
     a.frame.vis_slots = p.vis_slots;
-    a.frame.totals = ix->d_totals;
-    a.screen_totals = ix->d_screen ? ix->d_totals + 48 : nullptr;  // [48..49] lantern_gpu_search_screen_stats
+    a.frame.totals = ix->d_totals + kTotSearch;
+    a.screen_totals = ix->d_screen ? ix->d_totals + kTotSearchScreen : nullptr;  // lantern_gpu_search_screen_stats
     a.frame.ticket = next_ticket(ix, nq, p.grid, stream);
     a.done = done, a.done_flags = done_flags;
     a.lds_list = p.lds_list, a.wide_rows = p.wide_rows;
@@ -238,7 +238,7 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
         }
         // (there is no instrumented instantiation of the decoding walk: a compact pq launch ignores phase_profile)
         const bool prof_walk = ix->phase_profile && !pqd && !each;  // (nor of the per-query form)
-        a.phase_cycles = each ? nullptr : p.spec ? (ix->spec_profile ? ix->d_totals + 16 : nullptr) : prof_walk ? ix->d_totals + 8 : nullptr;
+        a.phase_cycles = each ? nullptr : p.spec ? (ix->spec_profile ? ix->d_totals + kTotSpecProfile : nullptr) : prof_walk ? ix->d_totals + kTotPhaseProfile : nullptr;
         // the row bitmap only when unique-rows mode asked for it AND it covers every slot the walk can name (a reserve / add since
         // it was sized would otherwise let mark_touched write past it)
         a.touched = (!p.spec && prof_walk && ix->unique_rows_on && ix->d_touched && ix->touched_words * 32 >= ix->cap) ? ix->d_touched : nullptr;

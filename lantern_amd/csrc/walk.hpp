@@ -61,6 +61,9 @@ struct WalkLds
 };
 constexpr uint32_t TRACE_LIST0 = 0x80000000u, TRACE_LISTU = 0xC0000000u;
 
+// a workgroup's slab of a launch's `bitmaps`: its visited bitmap (bm_words words) with its undo log (kVisUndoWords) behind it
+__device__ __forceinline__ uint32_t *vis_slab(uint32_t *bitmaps, uint32_t bm_words) { return bitmaps + (size_t)blockIdx.x * (bm_words + kVisUndoWords); }
+
 template <bool PROF> __device__ __forceinline__ void trace_append(const WalkLds &s, uint32_t entry)
 {
     if constexpr(PROF) {

@@ -3,7 +3,7 @@
 rows x dim f32, M, ef_construction, bench.py's batch plan -- with mode 0 and mode 1, alternated inside every repetition, on the
 Gaussian and the clustered set (l2sq) and on the clustered set under cosine.  Per build: vectors/s, the build profile (walk_ms is
 the figure the screen can move), the rejected share of the rows put to the screen test, and the graph checksum, which must not
-depend on the mode.  One JSON document; the verdict applies the rule that sets kInsertScreenByDefault (csrc/index.cpp):
+depend on the mode.  One JSON document; the verdict applies the rule that sets kInsertScreenByDefault (csrc/insert_batch.cpp):
 
     on  iff  on both l2sq sets median(mode 1) >= median(mode 0) - spread(mode 0)
         and  on at least one of them median(mode 1) > median(mode 0) + spread(mode 0),     spread = max - min of the mode-0 runs

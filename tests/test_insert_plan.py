@@ -1,4 +1,4 @@
-"""The shape of a batch's k_insert launch, without a device: lantern_gpu_plan_insert (csrc/index.cpp plan_insert) says which launches
+"""The shape of a batch's k_insert launch, without a device: lantern_gpu_plan_insert (csrc/insert_batch.cpp plan_insert) says which launches
 test their level-0 candidates on the int8 row copy, and what the query's int8 planes cost the LDS visited set.  The unscreened
 answers are held to the arithmetic run_batch did before the plan existed, restated below; the screened ones to the 31 KB budget.
 lantern_gpu_set_insert_screen's argument checks need no device either."""

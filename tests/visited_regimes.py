@@ -44,7 +44,7 @@ SHAPES = {
 }
 PQ_SHAPE = ("l2sq", 3000, 128, 32, 256, 8, 48)  # metric, n, d, S, C, M, efc: built on the device (a pq index cannot be imported)
 # The insertion walks: metric, n, d, M, efc, rows of the first part, insert screen.  k_insert takes batches of MORE than 2 x CUs rows
-# (index.cpp plan_insert: smaller ones go to the lone-insertion walk, whose grid set_search_shape does not cap), and under plan (512, 16)
+# (insert_batch.cpp plan_insert: smaller ones go to the lone-insertion walk, whose grid set_search_shape does not cap), and under plan (512, 16)
 # no batch of these builds has more than n / 16 rows.  So the first part is built under (512, 16) and the rest is added under (1024, 1):
 # one batch of min(rows so far, 1024, rows left) > 512 rows, all of whose walks run on the first part's graph -- by k_insert, W workgroups.
 INSERT_FIRST_PLAN, INSERT_PLAN, INSERT_W = (512, 16), (1024, 1), 3
