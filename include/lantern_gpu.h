@@ -293,7 +293,7 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_device_strided(usearch_index_t,
  * by the notify form.  Every refusal -- a bad parameter, an expansion beyond the 160 KiB LDS budget -- is for the whole call, before
  * anything is launched or written, and names the first offending position: "... (params[i])".
  * The host and lane forms take `skip` too (the uniform host forms have none): a service that wants the device to drop the rows a scan
- * was already handed says so here.  Filtered searches keep a uniform (k, ef, skip): lantern_gpu_search_batch_filtered_each*. */
+ * was already handed says so here.  Filtered searches take them per query through lantern_gpu_search_batch_filtered_each_params*. */
 typedef struct lantern_gpu_query_params { uint32_t k, ef, skip, reserved; } lantern_gpu_query_params; /* ef 0 = index default; reserved must be 0 */
 LANTERN_GPU_EXPORT void lantern_gpu_search_batch_params(usearch_index_t, const void *queries, size_t nq, usearch_scalar_kind_t,
                                                         const lantern_gpu_query_params *params, size_t k_stride, usearch_label_t *labels,
@@ -428,6 +428,74 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each_lane(usearch_inde
  * path (the unfiltered ones included), [1] on the exact path, [2] unfiltered (NULL) entries, [3] empty filters, [4] distinct filter
  * handles in the array, [5] kernel launches made (0 .. 2).  All zero before the first such call. */
 LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each(usearch_index_t, uint32_t out[6], usearch_error_t *);
+/* PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip: query i through filters[i] with params[i] = (k_i, ef_i,
+ * skip_i) -- ef 0 = the index's default, reserved must be 0; `params` is a HOST array in all three forms, read during the call.
+ * CONTRACT: for query i the ids, distance bits, count, D and E are exactly those of the single-filter call with filters[i] and
+ * (k_i, ef_i, skip_i), with no tolerance.  filters[i] == NULL: the unfiltered search's answer for those parameters (the all-allowed
+ * property above).  An empty filter: count 0, D = E = 0.  k_i == 0: no walk, count 0, D = E = 0, and the row is still written.
+ * Answer rows are k_stride wide; the tail of row i beyond k_i is label 0 / +inf / EMPTY slot.
+ * Per query, by the arithmetic of the uniform call: the path rule from that query's filter count and ef_i (or the index's default);
+ * the walk's expansion max(ef_i, k_i + skip_i); the exact pass keeps k_i + skip_i keys; the candidate cap C_i is the policy's
+ * cand_cap raised to the expansion, or max(4 expansion_i, 256), capped by the LDS left beside that query's own expansion.
+ * lantern_gpu_set_filter_policy and lantern_gpu_set_filter_seeds apply as to lantern_gpu_search_batch_filtered_each.
+ * LAUNCHES: at most two -- one walk launch over its list (expansion descending, stable) and one exact launch over its list (allowed
+ * count descending, stable).  Queries without a path -- an empty filter, k_i == 0, an empty index -- ride in the exact launch (in the
+ * walk launch when no query takes the exact path), where they touch no row; a call of such queries ALONE makes no launch: its rows
+ * are written by memsets.  Each launch is carved once: the walk's from its largest expansion and its largest C_i, the exact one's from
+ * its largest k_i + skip_i; vis_slots, the rows per round and the grid follow from that carve by the uniform call's rules.  The size
+ * of the visited set changes no answer, D or E.
+ * REFUSALS are for the whole call, before anything is queued or written, in this order:
+ *  1. the handles, as lantern_gpu_search_batch_filtered_each: a null filter array, the index handle (an entry of filters[] that is no
+ *     filter handle at all is named then, too);
+ *  2. the parameter array, with lantern_gpu_search_batch_params' texts: NULL, reserved != 0, k_stride below a k_i -- each but the
+ *     first with " (params[i])", i the first offender;
+ *  (the scalar kind and NULL buffers of the host forms, the lane number before everything, the row stride of the device form)
+ *  3. the filters: not a live handle / another index / stale, with " (filters[i])";
+ *  4. a compact pq index, with the single-filter calls' text;
+ *  5. a query whose own shape exceeds the 160 KiB LDS budget, in batch order: the uniform call's text plus " (params[i])";
+ *  6. "... the largest expansion and the largest candidate cap of the batch do not fit together: split the batch": every query fits
+ *     alone, the walk launch's joint carve does not.  This needs the automatic cap (an explicit cand_cap gives the query of the largest
+ *     expansion the largest C as well, and that query fits): with B(e) = 16 chunks + 2 ceil16(8 e) + 2 ceil16(8 M0) + ceil16(4 M0) +
+ *     scalars + 16 bytes of walk LDS beside `next`, a query's C is min(max(4 e, 256), floor((163840 - B(e)) / 16)), and the call is
+ *     refused iff B(e_max) + 16 C_max > 163840.  A query's own cap starts to bind at 80 e > 163840 - B(0): e > 2000 on 768-d f32
+ *     rows with M = 16, 2032 at 128-d; below that, C_max = 4 e_max belongs to the largest expansion itself and the call fits.  So it
+ *     takes a query of e > ~2000 whose room, floor((163840 - B(e)) / 16), is smaller than another query's C: a scan that has paged
+ *     to 4900 rows leaves 5100 (768-d) and is refused beside any query of expansion 1276 or more; two long scans of different lengths
+ *     (3300 and 3010) refuse each other.  A caller who meets it splits the batch.
+ * Lifetime of the filters as for lantern_gpu_search_batch_filtered_each.  There is no notify form. */
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each_params(usearch_index_t, const lantern_gpu_filter_t *const *filters,
+                                                                      const void *queries, size_t nq, usearch_scalar_kind_t,
+                                                                      const lantern_gpu_query_params *params, size_t k_stride,
+                                                                      usearch_label_t *labels, float *distances, uint32_t *counts,
+                                                                      usearch_error_t *);
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each_params_lane(usearch_index_t, int lane, const lantern_gpu_filter_t *const *filters,
+                                                                           const void *queries, size_t nq, usearch_scalar_kind_t,
+                                                                           const lantern_gpu_query_params *params, size_t k_stride,
+                                                                           usearch_label_t *labels, float *distances, uint32_t *counts,
+                                                                           usearch_error_t *);
+LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_each_params_device(usearch_index_t, const lantern_gpu_filter_t *const *filters,
+                                                                             const void *d_queries, size_t query_stride_bytes, size_t nq,
+                                                                             const lantern_gpu_query_params *params, size_t k_stride,
+                                                                             uint64_t *d_labels, float *d_distances, uint32_t *d_slots,
+                                                                             uint32_t *d_counts, uint64_t *d_dist_evals, uint64_t *d_expansions,
+                                                                             void *stream, usearch_error_t *);
+/* These calls update lantern_gpu_last_filtered_each (its fields mean the same; [3] counts every query without a path, k_i == 0
+ * included) and fill this: out[0] the largest walk expansion, [1] the largest C_i, [2] the largest k_i + skip_i on the exact path,
+ * [3] queries with k_i == 0.  All zero before the first such call. */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each_params(usearch_index_t, uint32_t out[4], usearch_error_t *);
+/* The plan of such a call, without a device, an index or the environment (a pure function; the entry points plan through it).
+ * in[8]: [0] chunks (16-byte chunks per stored row)  [1] M0  [2] n (rows)  [3] the index's default ef  [4] forced path (0 auto, 1 walk,
+ *   2 exact)  [5] cand_cap (0: automatic)  [6] exact_factor, the BIT PATTERN of the double  [7] seeds (changes no shape).
+ * counts[i]: the allowed count of query i's filter, -1 for a NULL entry.
+ * per_query[i]: [0] path (0 none, 1 walk, 2 exact)  [1] expansion (exact: k + skip; 0 without a path)  [2] C (walk only)  [3] position
+ *   in its launch's list (a query without a path: in the list it rides in; 0 when nothing is launched).
+ * launch[0] the walk's, launch[1] the exact one's: [0] queries of its list, riders included (0: no such launch)  [1] largest expansion
+ *   (exact: largest k + skip)  [2] largest C  [3] vis_slots (walk) / rows per round (exact)  [4] LDS bytes per workgroup
+ *   [5] workgroups per CU.
+ * Returns NULL, or the text the call is refused with (refusals 5 and 6 above). */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_params(const int64_t in[8], const int64_t counts[],
+                                                                const lantern_gpu_query_params params[], size_t nq, uint32_t per_query[][4],
+                                                                uint32_t launch[2][6]);
 /* kernel shape of the search launch: waves per query (1..8; 0 = automatic: 4 when the batch fills the chip, up to 8 for
  * smaller batches) and resident workgroups (0 = auto) */
 LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_per_query, int max_workgroups,
@@ -861,12 +929,25 @@ typedef int (*lantern_batch_search_params_fn)(void *ctx, const void *queries, si
 LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_params_fn(lantern_batch_search_fn, lantern_batch_search_params_fn, void *ctx,
                                                                               size_t vec_bytes, const char *host, int port, size_t max_batch,
                                                                               unsigned max_wait_us, usearch_error_t *);
+/* ... and for the FILTERED requests: the batch search with a filter and (k, ef, skip) per query, answer rows k_stride wide, as
+ * lantern_gpu_search_batch_filtered_each_params.  The filtered requests of a batch that carry more than one distinct (k, ef) go to it
+ * in ONE call; with one shared (k, ef) they take the each-function; a back end started without it keeps them grouped by (k, ef).  A call
+ * it refuses is repeated one request at a time, so that only the offender sees the error.  The device index has it under
+ * LANTERN_SCAN_MIXED=1 (off by default). */
+typedef int (*lantern_batch_search_each_params_fn)(void *ctx, const void *const *filters, const void *queries, size_t nq, size_t vec_bytes,
+                                                   const lantern_gpu_query_params *params, size_t k_stride, uint64_t *labels, float *distances,
+                                                   uint32_t *counts, const char **err);
+LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_filtered_params_fn(lantern_batch_search_fn, lantern_scan_filter_make_fn,
+                                                                                       lantern_scan_filter_free_fn, lantern_batch_search_each_fn,
+                                                                                       lantern_batch_search_each_params_fn, void *ctx, size_t vec_bytes,
+                                                                                       const char *host, int port, size_t max_batch,
+                                                                                       unsigned max_wait_us, usearch_error_t *);
 LANTERN_GPU_EXPORT void lantern_scan_server_filter_stats(lantern_scan_server_t *, uint64_t *filters_set, uint64_t *filtered_requests,
                                                          uint64_t *each_calls, uint64_t *most_distinct_filters, uint64_t *resident_bytes);
 LANTERN_GPU_EXPORT int  lantern_scan_server_port(lantern_scan_server_t *);
 /* queries received, batches formed, back-end calls made (per batch: one per distinct (k, ef) -- or ONE for all its unfiltered requests
- * where the back end takes mixed batches -- plus one per (k, ef) of its filtered requests; a mixed call is at most three kernel
- * launches), largest batch so far */
+ * where the back end takes mixed batches -- plus one per (k, ef) of its filtered requests -- or ONE for all of them where the back end takes
+ * a filter and (k, ef) per query; a mixed call is at most three kernel launches, a mixed filtered call at most two), largest batch so far */
 LANTERN_GPU_EXPORT void lantern_scan_server_stats(lantern_scan_server_t *, uint64_t *requests, uint64_t *batches,
                                                   uint64_t *launches, uint64_t *largest_batch);
 /* batches formed so far by size: bins[b] counts batches of 2^b .. 2^(b+1) - 1 requests (b < 16); returns the bins written */

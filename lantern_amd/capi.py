@@ -116,6 +116,10 @@ EXPORTS = [
     "lantern_scan_client_clear_filter",
     "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
     "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds",
+    # ... with per-query k, ef and skip as well (lantern_gpu.h "PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip")
+    "lantern_gpu_search_batch_filtered_each_params", "lantern_gpu_search_batch_filtered_each_params_lane",
+    "lantern_gpu_search_batch_filtered_each_params_device", "lantern_gpu_last_filtered_each_params", "lantern_gpu_plan_filtered_params",
+    "lantern_scan_server_start_filtered_params_fn",
     # per-query k, ef and skip (lantern_gpu.h "PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_params", "lantern_gpu_search_batch_params_lane", "lantern_gpu_search_batch_params_lane_notify",
     "lantern_gpu_search_batch_params_device", "lantern_gpu_last_params_launch", "lantern_scan_server_start_params_fn",
@@ -153,6 +157,9 @@ BATCH_SEARCH_PARAMS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t
                                      C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
 BATCH_SEARCH_EACH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
+# ... with (k, ef, skip) per query as well: (ctx, filters, queries, nq, vec_bytes, params, k_stride, labels, dists, counts, err)
+BATCH_SEARCH_EACH_PARAMS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_char_p))
 
 # int fn(void *ctx, void *host_buf, const size_t *offsets, const size_t *counts, int world, int rank)
 QUERIES_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t)  # lantern_gpu_queries_done_fn
@@ -327,6 +334,11 @@ def lib() -> C.CDLL:
         "lantern_gpu_search_batch_filtered_each_device": (None, [vp, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_search_batch_filtered_each_lane": (None, [vp, i32, vp, vp, sz, i32, sz, sz, vp, vp, vp, err]),
         "lantern_gpu_last_filtered_each": (None, [vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_each_params": (None, [vp, vp, vp, sz, i32, vp, sz, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_each_params_lane": (None, [vp, i32, vp, vp, sz, i32, vp, sz, vp, vp, vp, err]),
+        "lantern_gpu_search_batch_filtered_each_params_device": (None, [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, err]),
+        "lantern_gpu_last_filtered_each_params": (None, [vp, vp, err]),
+        "lantern_gpu_plan_filtered_params": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_set_filter_seeds": (None, [vp, sz, err]),
         "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
         "lantern_gpu_search_batch_params": (None, [vp, vp, sz, i32, vp, sz, vp, vp, vp, err]),
@@ -338,6 +350,8 @@ def lib() -> C.CDLL:
         "lantern_scan_server_start_params_fn": (vp, [BATCH_SEARCH_FN, BATCH_SEARCH_PARAMS_FN, vp, sz, C.c_char_p, i32, sz, C.c_uint, err]),
         "lantern_scan_server_start_filtered_fn": (vp, [BATCH_SEARCH_FN, FILTER_MAKE_FN, FILTER_FREE_FN, BATCH_SEARCH_EACH_FN, vp, sz, C.c_char_p, i32, sz,
                                                        C.c_uint, err]),
+        "lantern_scan_server_start_filtered_params_fn": (vp, [BATCH_SEARCH_FN, FILTER_MAKE_FN, FILTER_FREE_FN, BATCH_SEARCH_EACH_FN, BATCH_SEARCH_EACH_PARAMS_FN,
+                                                              vp, sz, C.c_char_p, i32, sz, C.c_uint, err]),
         "lantern_scan_server_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "lantern_scan_client_set_filter": (sz, [vp, vp, sz, u32, err]),
         "lantern_scan_client_clear_filter": (None, [vp, err]),
@@ -868,6 +882,40 @@ class GpuIndex:
         walk, exact, unfiltered, empty, distinct, launches = (int(x) for x in out)
         return {"walk": walk, "exact": exact, "unfiltered": unfiltered, "empty": empty, "distinct_filters": distinct, "launches": launches}
 
+    def search_batch_filtered_each_params(self, filters, queries, params, k_stride=None):
+        """Query i through filters[i] (a Filter or None) with params[i] = (k, ef[, skip]) -- one call, at most two launches.  The answers
+        are nq x k_stride (default: the largest k), row i's tail beyond its k_i label 0 / +inf."""
+        Q, nq, P, k_stride, labels, dists, counts = self._params_buffers(queries, params, k_stride)
+        F = self._filter_array(filters, nq)
+        _call("lantern_gpu_search_batch_filtered_each_params", self.h, _ptr(F), _ptr(Q), nq, _kind(self.metric), _ptr(P), k_stride, _ptr(labels),
+              _ptr(dists), _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_filtered_each_params_lane(self, lane, filters, queries, params, k_stride=None):
+        """search_batch_filtered_each_params on a lane (one caller per lane; the lanes' launches overlap on the device)."""
+        Q, nq, P, k_stride, labels, dists, counts = self._params_buffers(queries, params, k_stride)
+        F = self._filter_array(filters, nq)
+        _call("lantern_gpu_search_batch_filtered_each_params_lane", self.h, lane, _ptr(F), _ptr(Q), nq, _kind(self.metric), _ptr(P), k_stride,
+              _ptr(labels), _ptr(dists), _ptr(counts))
+        return labels, dists, counts
+
+    def search_batch_filtered_each_params_device(self, filters, d_queries, query_stride, nq, params, k_stride, d_labels=None, d_dists=None,
+                                                 d_slots=None, d_counts=None, d_D=None, d_E=None, stream=None):
+        """search_batch_filtered_each_device with (k, ef, skip) per query: `filters` and `params` are HOST arrays, the rest raw device addresses."""
+        P = query_params(params)
+        if len(P) != nq:
+            raise ValueError("one parameter row per query: got %d for %d queries" % (len(P), nq))
+        F = self._filter_array(filters, nq)
+        _call("lantern_gpu_search_batch_filtered_each_params_device", self.h, _ptr(F), _ptr(d_queries), int(query_stride), nq, _ptr(P), k_stride,
+              _ptr(d_labels), _ptr(d_dists), _ptr(d_slots), _ptr(d_counts), _ptr(d_D), _ptr(d_E), _ptr(stream))
+
+    def last_filtered_each_params(self):
+        """What the last per-query filtered call with per-query parameters carved its launches for (lantern_gpu_last_filtered_each_params)."""
+        out = np.zeros(4, dtype=np.uint32)
+        _call("lantern_gpu_last_filtered_each_params", self.h, _ptr(out))
+        exp, cap, kk, k0 = (int(x) for x in out)
+        return {"largest_expansion": exp, "largest_cand_cap": cap, "largest_exact_keys": kk, "k_zero": k0}
+
     def _params_buffers(self, queries, params, k_stride):
         Q = _rows(queries, self.metric)
         nq = Q.shape[0]
@@ -1203,6 +1251,30 @@ def plan_search(fields) -> tuple[dict, str | None]:
     return dict(zip(names, (int(x) for x in out))), (why.decode() if why else None)
 
 
+# lantern_gpu_plan_filtered_params' arrays, in order (include/lantern_gpu.h)
+PLAN_FILTERED_IN = ("chunks", "M0", "n", "ef_default", "path", "cand_cap", "exact_factor", "seeds")
+PLAN_FILTERED_QUERY = ("path", "expansion", "cand_cap", "position")
+PLAN_FILTERED_LAUNCH = ("queries", "expansion", "cand_cap", "vis_slots_or_rows", "lds", "per_cu")
+
+
+def plan_filtered_params(fields, counts, params):
+    """The plan of a per-query filtered call with per-query parameters (host arithmetic, no device): `fields` a dict of
+    PLAN_FILTERED_IN ("exact_factor" a float; "path" 0 auto, 1 walk, 2 exact), counts[i] the allowed count of query i's filter
+    (-1: a NULL entry), params rows of (k, ef[, skip]).  Returns ([per-query dict], {"walk": launch dict, "exact": launch dict},
+    refusal text or None)."""
+    vals = [int(np.float64(fields[n]).view(np.int64)) if n == "exact_factor" else int(fields[n]) for n in PLAN_FILTERED_IN]
+    a = np.asarray(vals, dtype=np.int64)
+    cnt = np.ascontiguousarray(counts, dtype=np.int64)
+    P = query_params(params)
+    assert len(P) == len(cnt)
+    per = np.zeros((max(len(P), 1), 4), dtype=np.uint32)
+    launch = np.zeros((2, 6), dtype=np.uint32)
+    why = lib().lantern_gpu_plan_filtered_params(_ptr(a), _ptr(cnt), _ptr(P), len(P), _ptr(per), _ptr(launch))
+    queries = [dict(zip(PLAN_FILTERED_QUERY, (int(x) for x in per[i]))) for i in range(len(P))]
+    launches = {name: dict(zip(PLAN_FILTERED_LAUNCH, (int(x) for x in launch[l]))) for l, name in enumerate(("walk", "exact"))}
+    return queries, launches, (why.decode() if why else None)
+
+
 # lantern_gpu_plan_insert's arrays, in order (include/lantern_gpu.h)
 PLAN_INSERT_IN = ("mcode", "chunks", "M0", "efc", "rows", "num_cus", "waves", "screen_table", "mode", "lds_list", "only_upper", "lone_ok", "vis_slots_env")
 PLAN_INSERT_OUT = ("screened", "vis_slots", "lds", "screen_lds", "lone", "spec_prefetch", "spec_cache")
@@ -1414,12 +1486,14 @@ class ScanServer:
         """index: a GpuIndex (the server runs lantern_gpu_search_batch on it), or batch_fn(queries u8[nq, vec_bytes], k, ef)
         -> (labels u64[nq, k], dists f32[nq, k], counts u32[nq]) for tests / custom back ends.  filter_fns, with batch_fn: a back end
         with filters -- (make(labels u64[n], flags) -> (handle int != 0, allowed, resident_bytes), free(handle),
-        each(filters [nq] of handles, queries, k, ef) -> as batch_fn).  params_fn, with batch_fn: a back end that takes mixed batches --
+        each(filters [nq] of handles, queries, k, ef) -> as batch_fn[, each_params(filters, queries, params QUERY_PARAMS[nq], k_stride)
+        -> rows k_stride wide: the filtered requests of a batch with several (k, ef) then arrive in one call]).  params_fn, with batch_fn: a back end that takes mixed batches --
         params_fn(queries, params QUERY_PARAMS[nq], k_stride) -> (labels u64[nq, k_stride], dists f32[nq, k_stride], counts u32[nq])."""
         self._keep = None
         self.index = index
         if batch_fn is not None and filter_fns is not None:
-            make_fn, free_fn, each_fn = filter_fns
+            make_fn, free_fn, each_fn = filter_fns[:3]
+            each_params_fn = filter_fns[3] if len(filter_fns) > 3 else None
 
             def fail(ex, errp):
                 self._last_error = C.c_char_p(str(ex).encode())
@@ -1462,8 +1536,25 @@ class ScanServer:
                     fail(ex, errp)
                     return 1
 
+            def tramp_each_params(ctx, filters, queries, nq, vb, params, k_stride, labels, dists, counts, errp):
+                try:
+                    q = np.ctypeslib.as_array(C.cast(queries, C.POINTER(C.c_uint8)), shape=(nq, vb))
+                    P = np.ctypeslib.as_array(C.cast(params, C.POINTER(C.c_uint32)), shape=(nq, 4)).copy().view(QUERY_PARAMS).reshape(nq)
+                    lab, dst, cnt = each_params_fn([int(filters[i] or 0) for i in range(nq)], q, P, int(k_stride))
+                    np.ctypeslib.as_array(labels, shape=(nq, k_stride))[:] = lab
+                    np.ctypeslib.as_array(dists, shape=(nq, k_stride))[:] = dst
+                    np.ctypeslib.as_array(counts, shape=(nq,))[:] = cnt
+                    return 0
+                except Exception as ex:  # noqa: BLE001 -- the service then asks again one request at a time
+                    fail(ex, errp)
+                    return 1
+
             self._keep = (BATCH_SEARCH_FN(tramp), FILTER_MAKE_FN(tramp_make), FILTER_FREE_FN(tramp_free), BATCH_SEARCH_EACH_FN(tramp_each))
-            self.s = _call("lantern_scan_server_start_filtered_fn", *self._keep, None, vec_bytes, host.encode(), port, max_batch, max_wait_us)
+            if each_params_fn is not None:
+                self._keep += (BATCH_SEARCH_EACH_PARAMS_FN(tramp_each_params),)
+                self.s = _call("lantern_scan_server_start_filtered_params_fn", *self._keep, None, vec_bytes, host.encode(), port, max_batch, max_wait_us)
+            else:
+                self.s = _call("lantern_scan_server_start_filtered_fn", *self._keep, None, vec_bytes, host.encode(), port, max_batch, max_wait_us)
         elif batch_fn is not None and params_fn is not None:
             def fail(ex, errp):
                 self._last_error = C.c_char_p(str(ex).encode())

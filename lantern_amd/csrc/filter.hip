@@ -158,40 +158,80 @@ constexpr size_t kFilteredLdsTarget = 64 * 1024;  // what the visited set may gr
 constexpr int    kFilteredWaves = 4;
 constexpr size_t kFilterSeedsMax = 4096;  // lantern_gpu_set_filter_seeds refuses more
 
-// The part of a filtered launch's shape that depends on (k, ef, skip, index) only -- not on the filter: exp, cand_cap, vis_slots /
-// rows_per_round and the LDS bytes.  false -> ix->err.
+// What the shape and the path of a filtered launch are computed from: the index's fields and its filter policy, nothing else -- so
+// that the plan is a pure function (lantern_gpu_plan_filtered_params) of what the launch really reads.
+struct FilterPlanIn
+{
+    uint32_t chunks, M0;
+    size_t   n, ef_default;
+    int      path;  // lantern_gpu_set_filter_policy
+    size_t   cand_cap;
+    double   exact_factor;
+    size_t   seeds;  // lantern_gpu_set_filter_seeds (changes no shape: a round of seeds is at most M0 rows, a hop's)
+};
+static FilterPlanIn filter_plan_in(const Index *ix)
+{
+    return FilterPlanIn{ ix->chunks, ix->M0, ix->n, ix->ef, ix->filter_path, ix->filter_cand_cap, ix->filter_exact_factor, ix->filter_seeds };
+}
+
+// exp, cand_cap, vis_slots / rows_per_round and the LDS bytes of one launch
+struct FilteredShape
+{
+    uint32_t exp = 0, cand_cap = 0, vis_slots = 0, rows_per_round = 0;
+    size_t   lds = 0;
+};
+static const char *kWalkOverBudget = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the filtered search kernel";
+static const char *kExactOverBudget = "lantern_gpu: k + skip exceed the 160 KiB LDS budget of the exact filtered search kernel";
+static const char *kJointOverBudget =
+    "lantern_gpu: the queries fit the 160 KiB LDS budget of the filtered search kernel one by one, but the largest expansion and the largest "
+    "candidate cap of the batch do not fit together: split the batch";
+
+// the exact launch's carve for a list of kk keys
+static void exact_carve(const FilterPlanIn &p, size_t kk, FilteredShape &s)
+{
+    s.exp = (uint32_t)kk;
+    s.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / group_lanes_for(p.chunks));
+    s.lds = filtered_exact_lds_bytes(p.chunks, s.exp, s.rows_per_round);
+}
+// the walk launch's carve for `exp` keys of top and `cap` of next: the visited set takes what is left of the LDS target
+static void walk_carve(const FilterPlanIn &p, size_t exp, size_t cap, FilteredShape &s)
+{
+    s.exp = (uint32_t)exp;
+    s.cand_cap = (uint32_t)cap;
+    uint32_t vis_slots = 2048;
+    while(vis_slots && filtered_walk_lds_bytes(p.chunks, s.exp, s.cand_cap, p.M0, vis_slots) > kFilteredLdsTarget)
+        vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
+    if(vis_slots && vis_slots < 4 * p.M0) vis_slots = 0;
+    s.vis_slots = vis_slots;
+    s.lds = filtered_walk_lds_bytes(p.chunks, s.exp, s.cand_cap, p.M0, vis_slots);
+}
+// The part of a filtered launch's shape that depends on (k, ef, skip, index) only -- not on the filter.  NULL, or the refusal.
+static const char *filtered_shape_of(const FilterPlanIn &p, bool exact, size_t k, size_t skip, size_t exp, FilteredShape &s)
+{
+    if(exact) {
+        exact_carve(p, k + skip, s);
+        if(s.lds > kFilteredLds) return kExactOverBudget;
+    } else {
+        const size_t base = filtered_walk_lds_bytes(p.chunks, (uint32_t)exp, 0, p.M0, 0);
+        if(base + exp * 16 > kFilteredLds) return kWalkOverBudget;
+        size_t cap = p.cand_cap ? std::max(p.cand_cap, exp) : std::max<size_t>(4 * exp, 256);
+        cap = std::min(cap, (kFilteredLds - base) / 16);
+        if(p.cand_cap && cap < std::max(p.cand_cap, exp)) return "lantern_gpu: the candidate cap exceeds the 160 KiB LDS budget of the filtered search kernel";
+        walk_carve(p, exp, cap, s);
+    }
+    return nullptr;
+}
+static void shape_into(const FilteredShape &s, FilteredArgs &a, size_t &lds)
+{
+    a.exp = s.exp, a.cand_cap = s.cand_cap, a.rows_per_round = s.rows_per_round, a.frame.vis_slots = s.vis_slots;
+    lds = s.lds;
+}
+// ... into the launch's arguments.  false -> ix->err.
 static bool filtered_shape(Index *ix, bool exact, size_t k, size_t skip, size_t exp, FilteredArgs &a, size_t &lds)
 {
-    const int G = group_lanes_for(ix->chunks);
-    if(exact) {
-        a.exp = (uint32_t)(k + skip);
-        a.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / G);
-        lds = filtered_exact_lds_bytes(ix->chunks, a.exp, a.rows_per_round);
-        if(lds > kFilteredLds) {
-            set_err(ix, "lantern_gpu: k + skip exceed the 160 KiB LDS budget of the exact filtered search kernel");
-            return false;
-        }
-    } else {
-        a.exp = (uint32_t)exp;
-        const size_t base = filtered_walk_lds_bytes(ix->chunks, a.exp, 0, ix->M0, 0);
-        if(base + exp * 16 > kFilteredLds) {
-            set_err(ix, "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the filtered search kernel");
-            return false;
-        }
-        size_t cap = ix->filter_cand_cap ? std::max(ix->filter_cand_cap, exp) : std::max<size_t>(4 * exp, 256);
-        cap = std::min(cap, (kFilteredLds - base) / 16);
-        if(ix->filter_cand_cap && cap < std::max(ix->filter_cand_cap, exp)) {
-            set_err(ix, "lantern_gpu: the candidate cap exceeds the 160 KiB LDS budget of the filtered search kernel");
-            return false;
-        }
-        a.cand_cap = (uint32_t)cap;
-        uint32_t vis_slots = 2048;
-        while(vis_slots && filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots) > kFilteredLdsTarget)
-            vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
-        if(vis_slots && vis_slots < 4 * ix->M0) vis_slots = 0;
-        a.frame.vis_slots = vis_slots;
-        lds = filtered_walk_lds_bytes(ix->chunks, a.exp, a.cand_cap, ix->M0, vis_slots);
-    }
+    FilteredShape s;
+    if(const char *why = filtered_shape_of(filter_plan_in(ix), exact, k, skip, exp, s)) return set_err(ix, why), false;
+    shape_into(s, a, lds);
     return true;
 }
 
@@ -216,11 +256,12 @@ static bool filtered_index_ok(Index *ix)
 
 // the path of a query under `f`: forced, or the rule of DESIGN.md 4.9 -- a walk under selectivity s evaluates about D / s rows, the
 // exact pass `allowed`
-static bool filter_takes_exact(const Index *ix, const Filter *f, size_t ef_sel)
+static bool count_takes_exact(const FilterPlanIn &p, size_t count, size_t ef_sel)
 {
-    if(ix->filter_path) return ix->filter_path == 2;
-    return (double)f->count * (double)f->count <= ix->filter_exact_factor * (double)ef_sel * (double)ix->n;
+    if(p.path) return p.path == 2;
+    return (double)count * (double)count <= p.exact_factor * (double)ef_sel * (double)p.n;
 }
+static bool filter_takes_exact(const Index *ix, const Filter *f, size_t ef_sel) { return count_takes_exact(filter_plan_in(ix), f->count, ef_sel); }
 
 // the kernel arguments that depend neither on the filter nor on the path
 static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, size_t skip, const SearchOut &out)
@@ -239,18 +280,35 @@ static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, s
 
 // the per-query form's table of one launch: host bytes that go into the scratch of the launch's slot, and where in them the launch's
 // descriptors and selection list lie
+constexpr size_t kNoTable = ~(size_t)0;
 struct EachTable
 {
     const char *host;
     size_t      bytes, descs_at, select_at;
+    size_t      params_at = kNoTable;  // the per-query-parameter form: where the launch's rows {k, expansion, skip, C} lie
 };
+
+// workgroups of a filtered launch that a CU holds
+static int filtered_per_cu(size_t lds) { return (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1))); }
+
+// the empty answer in every row of a call, kw wide, with no launch
+static bool empty_answers(Index *ix, const SearchOut &out, size_t nq, size_t kw, hipStream_t stream)
+{
+    if(out.labels && kw && hipMemsetAsync(out.labels, 0, nq * kw * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+    if(out.dists && kw && hipMemsetD32Async((hipDeviceptr_t)out.dists, 0x7F800000, nq * kw, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+    if(out.slots && kw && hipMemsetAsync(out.slots, 0xFF, nq * kw * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+    if(out.counts && hipMemsetAsync(out.counts, 0, nq * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+    if(out.D && hipMemsetAsync(out.D, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+    if(out.E && hipMemsetAsync(out.E, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
+    return true;
+}
 
 // ONE launch of either kernel over a.frame.nq queries, `a` shaped by filtered_shape: the grid, the launch slot (which orders the launch
 // after inserts and holds the walk's visited bitmaps), the per-query table if there is one, the ticket, the launch and its count.
 // Returns the grid; < 0 -> ix->err.
 static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, hipStream_t stream, const EachTable *tbl = nullptr)
 {
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(4, kFilteredLds / std::max<size_t>(lds, 1)));
+    const int per_cu = filtered_per_cu(lds);
     const int grid = search_grid(ix, a.frame.nq, kFilteredWaves, kFilteredWaves * per_cu);
     const int slot = acquire_search_slot(ix, stream, (size_t)grid);
     if(slot < 0) return -1;
@@ -263,6 +321,7 @@ static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, h
         }
         a.descs = (const FilterDesc *)(d_tbl + tbl->descs_at);
         a.frame.qlist = (const uint32_t *)(d_tbl + tbl->select_at);
+        if(tbl->params_at != kNoTable) a.qparams = (const uint4 *)(d_tbl + tbl->params_at);
     }
     a.frame.bitmaps = ix->slot_bitmaps[ slot ];
     a.frame.bm_words = (uint32_t)ix->slot_words[ slot ];
@@ -292,13 +351,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     std::fill(std::begin(ix->last_seeds), std::end(ix->last_seeds), 0u);
     if(f->count == 0 || ix->n == 0) {  // nothing allowed: the empty answer, no launch
         std::fill(std::begin(ix->last_filtered), std::end(ix->last_filtered), 0u);
-        if(out.labels && hipMemsetAsync(out.labels, 0, nq * k * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(out.dists && hipMemsetD32Async((hipDeviceptr_t)out.dists, 0x7F800000, nq * k, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(out.slots && hipMemsetAsync(out.slots, 0xFF, nq * k * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(out.counts && hipMemsetAsync(out.counts, 0, nq * 4, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(out.D && hipMemsetAsync(out.D, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        if(out.E && hipMemsetAsync(out.E, 0, nq * 8, stream) != hipSuccess) return set_err(ix, "lantern_gpu: HIP failure (memset)"), false;
-        return true;
+        return empty_answers(ix, out, nq, k, stream);
     }
     const bool   exact = filter_takes_exact(ix, f, ef_sel);
     FilteredArgs a = filtered_args(ix, d_q, k, skip, out);
@@ -337,7 +390,8 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
 
 // ---- the per-query form: filters[i] is query i's filter ------------------------------------------------------------------------
 // bytes of the host block filtered_each_locked stages its selection lists and descriptor table in
-static size_t each_table_bytes(size_t nq) { return nq * (sizeof(FilterDesc) + 4) + 16; }
+// (`params`: with the per-query-parameter form's rows)
+static size_t each_table_bytes(size_t nq, bool params = false) { return nq * (sizeof(FilterDesc) + 4) + 16 + (params ? nq * 16 + 16 : 0); }
 
 // Every entry of filters[] is NULL or a live filter of this index at its present size; else ix->err names the first offender.
 static bool each_filters_ok(Index *ix, const Filter *const *filters, size_t nq)
@@ -351,6 +405,59 @@ static bool each_filters_ok(Index *ix, const Filter *const *filters, size_t nq)
         return false;
     }
     return filtered_index_ok(ix);
+}
+
+// the queries of a per-query call by what becomes of them (lantern_gpu_last_filtered_each [0..4))
+struct EachCounts { uint32_t walk, exact, unfiltered, empty; };
+
+// The launches of a per-query call whose queries are split already: `walk` and `exact` are the two selection lists (what rides in a
+// launch without a path behind the queries of its list), aw / ae the launches' shaped arguments.  `rows`: NULL, or the call's
+// parameter table [nq][4] (the per-query-parameter form).  `h_tbl`: a page-locked block of each_table_bytes(nq, rows) or NULL, as
+// filtered_each_locked's.  false -> ix->err.
+static bool each_launches(Index *ix, const Filter *const *filters, size_t nq, const std::vector<uint32_t> &walk, const std::vector<uint32_t> &exact,
+                          FilteredArgs &aw, size_t lds_w, FilteredArgs &ae, size_t lds_e, const uint32_t *rows, const EachCounts &c, hipStream_t stream,
+                          char *h_tbl)
+{
+    std::vector<const Filter *> distinct;
+    for(size_t i = 0; i < nq; ++i)
+        if(filters[ i ]) distinct.push_back(filters[ i ]);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+
+    // the host block: walk selection list | parameter rows (by query; the per-query-parameter form) | descriptor table (by query) |
+    // exact selection list -- each launch copies its list and the tables in one piece into the scratch of its own launch slot
+    const size_t off_par = rows ? ((size_t)walk.size() * 4 + 15) & ~(size_t)15 : ((size_t)walk.size() * 4 + 7) & ~(size_t)7;
+    const size_t off_desc = off_par + (rows ? nq * 16 : 0), off_sel_e = off_desc + nq * sizeof(FilterDesc);
+    const size_t tbl_bytes = off_sel_e + exact.size() * 4;
+    std::vector<char> pageable;
+    if(!h_tbl) { pageable.resize(tbl_bytes); h_tbl = pageable.data(); }
+    if(!walk.empty()) std::memcpy(h_tbl, walk.data(), walk.size() * 4);
+    if(rows) std::memcpy(h_tbl + off_par, rows, nq * 16);
+    if(!exact.empty()) std::memcpy(h_tbl + off_sel_e, exact.data(), exact.size() * 4);
+    FilterDesc *const hd = (FilterDesc *)(h_tbl + off_desc);
+    for(size_t i = 0; i < nq; ++i) {
+        const Filter *f = filters[ i ];
+        hd[ i ] = f ? FilterDesc{ f->d_bits, f->d_slots, (uint32_t)f->count, 0u } : FilterDesc{ nullptr, nullptr, 0u, ix->n ? 1u : 0u };
+    }
+
+    uint32_t launches = 0;
+    for(int pass = 0; pass < 2; ++pass) {
+        const bool ex = pass == 1;
+        if((ex ? exact : walk).empty()) continue;
+        FilteredArgs &a = ex ? ae : aw;
+        a.frame.nq = (uint32_t)(ex ? exact : walk).size();
+        const EachTable t = ex ? EachTable{ h_tbl + off_par, tbl_bytes - off_par, off_desc - off_par, off_sel_e - off_par, rows ? 0 : kNoTable }
+                               : EachTable{ h_tbl, off_sel_e, off_desc, 0, rows ? off_par : kNoTable };
+        if(filtered_launch(ix, ex, a, ex ? lds_e : lds_w, stream, &t) < 0) return false;
+        launches += 1;
+    }
+    const uint32_t shape[ 6 ] = { c.walk, c.exact, c.unfiltered, c.empty, (uint32_t)distinct.size(), launches };
+    std::copy(std::begin(shape), std::end(shape), ix->last_each);
+    const uint32_t n_seeded = ix->filter_seeds ? c.walk - c.unfiltered : 0u;
+    ix->last_seeds[ 2 ] = n_seeded;
+    ix->last_seeds[ 3 ] = c.walk - n_seeded;
+    ix->c_search_queries += nq;
+    return true;
 }
 
 // The caller holds ix->mu and has flushed.  The queries split into a walk group and an exact group by the path rule, evaluated per
@@ -379,11 +486,6 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
     std::stable_sort(exact.begin(), exact.end(), [&](uint32_t x, uint32_t y) { return filters[ x ]->count > filters[ y ]->count; });
     std::vector<uint32_t> &host = (exact.empty() && !walk.empty()) ? walk : exact;
     host.insert(host.end(), empty.begin(), empty.end());
-    std::vector<const Filter *> distinct;
-    for(size_t i = 0; i < nq; ++i)
-        if(filters[ i ]) distinct.push_back(filters[ i ]);
-    std::sort(distinct.begin(), distinct.end());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
 
     const FilteredArgs base = filtered_args(ix, d_q, k, skip, out);
     FilteredArgs aw = base, ae = base;
@@ -392,37 +494,99 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
     if(!walk.empty() && !filtered_shape(ix, false, k, skip, exp, aw, lds_w)) return false;
     if(!exact.empty() && !filtered_shape(ix, true, k, skip, exp, ae, lds_e)) return false;
 
-    // the host block: walk selection list | descriptor table (by query) | exact selection list -- each launch copies its list and
-    // the table in one piece into the scratch of its own launch slot
-    const size_t off_desc = ((size_t)walk.size() * 4 + 7) & ~(size_t)7, off_sel_e = off_desc + nq * sizeof(FilterDesc);
-    const size_t tbl_bytes = off_sel_e + exact.size() * 4;
-    std::vector<char> pageable;
-    if(!h_tbl) { pageable.resize(tbl_bytes); h_tbl = pageable.data(); }
-    if(!walk.empty()) std::memcpy(h_tbl, walk.data(), walk.size() * 4);
-    if(!exact.empty()) std::memcpy(h_tbl + off_sel_e, exact.data(), exact.size() * 4);
-    FilterDesc *const hd = (FilterDesc *)(h_tbl + off_desc);
-    for(size_t i = 0; i < nq; ++i) {
-        const Filter *f = filters[ i ];
-        hd[ i ] = f ? FilterDesc{ f->d_bits, f->d_slots, (uint32_t)f->count, 0u } : FilterDesc{ nullptr, nullptr, 0u, ix->n ? 1u : 0u };
-    }
+    const EachCounts c{ n_walk, n_exact, n_unfiltered, n_empty };
+    return each_launches(ix, filters, nq, walk, exact, aw, lds_w, ae, lds_e, nullptr, c, stream, h_tbl);
+}
 
-    uint32_t launches = 0;
-    for(int pass = 0; pass < 2; ++pass) {
-        const bool ex = pass == 1;
-        if((ex ? exact : walk).empty()) continue;
-        FilteredArgs &a = ex ? ae : aw;
-        a.frame.nq = (uint32_t)(ex ? exact : walk).size();
-        const EachTable t = ex ? EachTable{ h_tbl + off_desc, tbl_bytes - off_desc, 0, nq * sizeof(FilterDesc) } : EachTable{ h_tbl, off_sel_e, off_desc, 0 };
-        if(filtered_launch(ix, ex, a, ex ? lds_e : lds_w, stream, &t) < 0) return false;
-        launches += 1;
+// ---- per-query filters AND per-query (k, ef, skip): lantern_gpu_search_batch_filtered_each_params* -------------------------------
+// The plan of such a call: every query's path, expansion and C by the uniform call's own rules, the two selection lists, the
+// parameter table and the two launches' carves.  A pure function of FilterPlanIn, the filters' counts and the parameters.
+struct EachParamsPlan
+{
+    std::vector<uint32_t> walk, exact;  // the selection lists, in launch order, the riders (no path: an empty filter, k == 0, an empty
+                                        // index) behind the queries of the list they ride in
+    std::vector<uint32_t> rows;         // [nq][4] {k, expansion (exact: k + skip), skip, C}
+    std::vector<uint8_t>  path;         // [nq] 0 none, 1 walk, 2 exact
+    EachCounts            counts{};     // (`empty`: every rider)
+    uint32_t              n_k0 = 0;     // queries with k == 0
+    FilteredShape         sw, se;       // the launches' carves: the largest expansion with the largest C; the largest k + skip
+};
+
+// "" or the refusal.  counts[i]: the allowed count of query i's filter, -1 for a NULL entry.
+static std::string plan_filtered_params(const FilterPlanIn &p, const int64_t *counts, const lantern_gpu_query_params *params, size_t nq, EachParamsPlan &out)
+{
+    out = EachParamsPlan{};
+    out.rows.assign(nq * 4, 0u);
+    out.path.assign(nq, 0);
+    std::vector<uint32_t> riders;
+    size_t                max_exp = 0, max_cap = 0, max_kk = 0;
+    for(size_t i = 0; i < nq; ++i) {
+        const size_t k = params[ i ].k, skip = params[ i ].skip;
+        uint32_t *const row = &out.rows[ 4 * i ];
+        row[ 0 ] = (uint32_t)k, row[ 2 ] = (uint32_t)skip;
+        out.n_k0 += k == 0;
+        if(k == 0 || p.n == 0 || counts[ i ] == 0) { riders.push_back((uint32_t)i); continue; }
+        const size_t ef_sel = params[ i ].ef ? params[ i ].ef : p.ef_default;
+        const bool   exact = counts[ i ] >= 0 && count_takes_exact(p, (size_t)counts[ i ], ef_sel);
+        // (far past the LDS budget already: refused below, and it fits the table's word)
+        const size_t  exp = std::min<size_t>(std::max(ef_sel, k + skip), (size_t)1 << 20), kk = std::min<size_t>(k + skip, (size_t)1 << 20);
+        FilteredShape s;
+        if(const char *why = filtered_shape_of(p, exact, kk, 0, exp, s)) return std::string(why) + " (params[" + std::to_string(i) + "])";
+        row[ 1 ] = s.exp, row[ 3 ] = s.cand_cap;
+        out.path[ i ] = exact ? 2 : 1;
+        (exact ? out.exact : out.walk).push_back((uint32_t)i);
+        if(exact) max_kk = std::max<size_t>(max_kk, s.exp);
+        else max_exp = std::max<size_t>(max_exp, s.exp), max_cap = std::max<size_t>(max_cap, s.cand_cap), out.counts.unfiltered += counts[ i ] < 0;
     }
-    const uint32_t shape[ 6 ] = { n_walk, n_exact, n_unfiltered, n_empty, (uint32_t)distinct.size(), launches };
-    std::copy(std::begin(shape), std::end(shape), ix->last_each);
-    const uint32_t n_seeded = ix->filter_seeds ? n_walk - n_unfiltered : 0u;
-    ix->last_seeds[ 2 ] = n_seeded;
-    ix->last_seeds[ 3 ] = n_walk - n_seeded;
-    ix->c_search_queries += nq;
+    out.counts.walk = (uint32_t)out.walk.size(), out.counts.exact = (uint32_t)out.exact.size(), out.counts.empty = (uint32_t)riders.size();
+    // one carve per launch.  The exact list's is the carve of its largest k + skip, which fits because that query does; the walk's
+    // joins the largest expansion with the largest C, which two different queries may have brought
+    if(!out.walk.empty()) {
+        if(filtered_walk_lds_bytes(p.chunks, (uint32_t)max_exp, (uint32_t)max_cap, p.M0, 0) > kFilteredLds) return kJointOverBudget;
+        walk_carve(p, max_exp, max_cap, out.sw);
+    }
+    if(!out.exact.empty()) exact_carve(p, max_kk, out.se);
+    // the walk list by expansion descending, the exact list by allowed count descending (both stable): the longest first, so that a
+    // launch's tail is a short one
+    std::stable_sort(out.walk.begin(), out.walk.end(), [&](uint32_t x, uint32_t y) { return out.rows[ 4 * x + 1 ] > out.rows[ 4 * y + 1 ]; });
+    std::stable_sort(out.exact.begin(), out.exact.end(), [&](uint32_t x, uint32_t y) { return counts[ x ] > counts[ y ]; });
+    std::vector<uint32_t> &host = (out.exact.empty() && !out.walk.empty()) ? out.walk : out.exact;
+    if(!out.walk.empty() || !out.exact.empty()) host.insert(host.end(), riders.begin(), riders.end());
+    return "";
+}
+
+// The caller holds ix->mu and has flushed: the filters checked, the call planned.  false -> ix->err; nothing is queued.
+static bool each_params_plan_locked(Index *ix, const Filter *const *filters, const lantern_gpu_query_params *params, size_t nq, EachParamsPlan &plan)
+{
+    if(!each_filters_ok(ix, filters, nq)) return false;
+    std::vector<int64_t> counts(nq);
+    for(size_t i = 0; i < nq; ++i) counts[ i ] = filters[ i ] ? (int64_t)filters[ i ]->count : -1;
+    const std::string why = plan_filtered_params(filter_plan_in(ix), counts.data(), params, nq, plan);
+    if(!why.empty()) return set_err(ix, why), false;
     return true;
+}
+
+// The caller holds ix->mu, has flushed and has planned the call under this hold of the mutex.  `h_tbl` as filtered_each_locked's, of
+// each_table_bytes(nq, true).
+static bool filtered_each_params_locked(Index *ix, const EachParamsPlan &plan, const Filter *const *filters, const uint4 *d_q, size_t nq, size_t k_stride,
+                                        const SearchOut &out, hipStream_t stream, char *h_tbl)
+{
+    if(nq == 0) return true;
+    const uint32_t shape[ 4 ] = { plan.sw.exp, plan.sw.cand_cap, plan.se.exp, plan.n_k0 };
+    std::copy(std::begin(shape), std::end(shape), ix->last_each_params);
+    if(plan.walk.empty() && plan.exact.empty()) {  // riders only: the empty answers, no launch
+        const uint32_t none[ 6 ] = { 0, 0, 0, plan.counts.empty, 0, 0 };
+        std::copy(std::begin(none), std::end(none), ix->last_each);
+        ix->last_seeds[ 2 ] = ix->last_seeds[ 3 ] = 0;
+        return empty_answers(ix, out, nq, k_stride, stream);
+    }
+    const FilteredArgs base = filtered_args(ix, d_q, k_stride, 0, out);  // (k: the width of an answer row)
+    FilteredArgs aw = base, ae = base;
+    aw.seeds = (uint32_t)ix->filter_seeds;
+    size_t lds_w = 0, lds_e = 0;
+    shape_into(plan.sw, aw, lds_w);
+    shape_into(plan.se, ae, lds_e);
+    return each_launches(ix, filters, nq, plan.walk, plan.exact, aw, lds_w, ae, lds_e, plan.rows.data(), plan.counts, stream, h_tbl);
 }
 
 // one query through `cur` (streaming: never a row twice): the first k allowed rows not handed out before
@@ -708,6 +872,125 @@ try {
                    each_launch(ix, filters, nq, k, ef), labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+// ---- per-query filters with per-query (k, ef, skip): the entry points (include/lantern_gpu.h has the contract and the order of the refusals)
+void lantern_gpu_last_filtered_each_params(usearch_index_t h, uint32_t out[ 4 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::copy(std::begin(ix->last_each_params), std::end(ix->last_each_params), out);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+// refusals 1 and 2: the handles, as FHS; then the parameter array
+static Index *FPH(usearch_index_t h, const lantern_gpu_filter_t *const *filters, const lantern_gpu_query_params *params, size_t nq, size_t k_stride,
+                  usearch_error_t *e)
+{
+    static thread_local std::string msg;
+    Index *ix = FHS(h, filters, nq, e);
+    if(!ix) return nullptr;
+    msg = params_check(params, nq, k_stride);
+    if(msg.empty()) return ix;
+    FAIL(e, msg.c_str());
+    return nullptr;
+}
+
+// refusals 3 to 6 of the host forms, of either host trip: the filters, then the plan, which the launch of the same trip reads
+struct EachParamsValidate
+{
+    static constexpr bool              zero_width_rows = true;  // (host_trip.hpp: k_stride == 0 is a batch of k_i == 0, whose counts are written)
+    const lantern_gpu_filter_t *const *filters;
+    const lantern_gpu_query_params    *params;
+    size_t                             nq;
+    EachParamsPlan                    *plan;
+    bool operator()(Index *ix) const { return each_params_plan_locked(ix, (const Filter *const *)filters, params, nq, *plan); }
+};
+static auto each_params_launch(Index *ix, const EachParamsPlan *plan, const lantern_gpu_filter_t *const *filters, size_t nq, size_t k_stride)
+{
+    return [ = ](const HostBatch &b) {
+        return filtered_each_params_locked(ix, *plan, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k_stride, b.out(b.d_out), b.stream, b.h_extra());
+    };
+}
+
+void lantern_gpu_search_batch_filtered_each_params_device(usearch_index_t h, const lantern_gpu_filter_t *const *filters, const void *d_queries,
+                                                          size_t query_stride_bytes, size_t nq, const lantern_gpu_query_params *params,
+                                                          size_t k_stride, uint64_t *d_labels, float *d_distances, uint32_t *d_slots,
+                                                          uint32_t *d_counts, uint64_t *d_D, uint64_t *d_E, void *stream, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FPH(h, filters, params, nq, k_stride, e);
+    if(!ix) return;
+    const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
+    device_trip(ix, stride_is(query_stride_bytes), [ & ] {
+        EachParamsPlan plan;
+        return each_params_plan_locked(ix, (const Filter *const *)filters, params, nq, plan) &&
+               filtered_each_params_locked(ix, plan, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k_stride, out, (hipStream_t)stream, nullptr);
+    }, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_filtered_each_params(usearch_index_t h, const lantern_gpu_filter_t *const *filters, const void *queries, size_t nq,
+                                                   usearch_scalar_kind_t kind, const lantern_gpu_query_params *params, size_t k_stride,
+                                                   usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = FPH(h, filters, params, nq, k_stride, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
+    if(nq && (!queries || (k_stride && (!labels || !distances)))) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
+    EachParamsPlan plan;
+    host_trip_sync(ix, nq, k_stride, each_table_bytes(nq, true), queries, (int)kind, kFilteredBatchFailed, EachParamsValidate{ filters, params, nq, &plan },
+                   each_params_launch(ix, &plan, filters, nq, k_stride), labels, distances, counts, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_search_batch_filtered_each_params_lane(usearch_index_t h, int lane, const lantern_gpu_filter_t *const *filters, const void *queries,
+                                                        size_t nq, usearch_scalar_kind_t kind, const lantern_gpu_query_params *params, size_t k_stride,
+                                                        usearch_label_t *labels, float *distances, uint32_t *counts, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(!lane_ok(lane, e)) return;
+    Index *ix = FPH(h, filters, params, nq, k_stride, e);
+    if(!ix) return;
+    if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
+    if(nq && (!queries || (k_stride && (!labels || !distances)))) { FAIL(e, "lantern_gpu: null buffer"); return; }
+    EachParamsPlan plan;
+    host_trip_lane(ix, lane, nq, k_stride, each_table_bytes(nq, true), queries, (int)kind, kFilteredBatchFailed,
+                   EachParamsValidate{ filters, params, nq, &plan }, each_params_launch(ix, &plan, filters, nq, k_stride), labels, distances, counts, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+// the plan without a device (include/lantern_gpu.h has the field order)
+const char *lantern_gpu_plan_filtered_params(const int64_t in[ 8 ], const int64_t counts[], const lantern_gpu_query_params params[], size_t nq,
+                                             uint32_t per_query[][ 4 ], uint32_t launch[ 2 ][ 6 ])
+try {
+    static thread_local std::string msg;
+    if(!in || !launch || (nq && (!counts || !params || !per_query))) return "lantern_gpu: null array";
+    double factor;
+    std::memcpy(&factor, &in[ 6 ], 8);
+    const FilterPlanIn p{ (uint32_t)in[ 0 ], (uint32_t)in[ 1 ], (size_t)in[ 2 ], (size_t)in[ 3 ], (int)in[ 4 ], (size_t)in[ 5 ], factor, (size_t)in[ 7 ] };
+    EachParamsPlan plan;
+    msg = plan_filtered_params(p, counts, params, nq, plan);
+    if(!msg.empty()) return msg.c_str();
+    for(size_t i = 0; i < nq; ++i) {
+        per_query[ i ][ 0 ] = plan.path[ i ], per_query[ i ][ 1 ] = plan.rows[ 4 * i + 1 ], per_query[ i ][ 2 ] = plan.rows[ 4 * i + 3 ], per_query[ i ][ 3 ] = 0;
+    }
+    for(int l = 0; l < 2; ++l) {
+        const std::vector<uint32_t> &list = l ? plan.exact : plan.walk;
+        const FilteredShape         &s = l ? plan.se : plan.sw;
+        for(size_t at = 0; at < list.size(); ++at) per_query[ list[ at ] ][ 3 ] = (uint32_t)at;
+        const uint32_t row[ 6 ] = { (uint32_t)list.size(), s.exp, s.cand_cap, l ? s.rows_per_round : s.vis_slots, (uint32_t)s.lds,
+                                    list.empty() ? 0u : (uint32_t)filtered_per_cu(s.lds) };
+        std::copy(std::begin(row), std::end(row), launch[ l ]);
+    }
+    return nullptr;
+}
+catch(...) {
+    return "lantern_gpu: out of memory planning a filtered search";
+}
 
 size_t lantern_gpu_cursor_search_filtered(lantern_gpu_cursor_t *c, const lantern_gpu_filter_t *filter, const void *query, usearch_scalar_kind_t kind,
                                           size_t k, size_t ef, bool streaming, usearch_label_t *labels, float *distances, usearch_error_t *e)

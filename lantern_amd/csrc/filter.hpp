@@ -55,6 +55,9 @@ struct FilteredArgs
     // the seeded walk (per-query form only): > 0 = a query whose descriptor has count >= 1 starts from min(seeds, count) allowed rows
     // taken at even strides from the descriptor's slot list (search_filtered_kernel.hip "SEEDED"); 0 = off
     uint32_t          seeds;
+    // the per-query-parameter form (with descs; k_search_filtered / k_search_exact_allowed <.., PARAMS = true>); NULL otherwise
+    const uint4      *qparams;   // [queries of the call] {k, expansion (exact: k + skip), skip, C} by query; `k` above is then the width of an
+                                 // answer row, `skip` unused, `exp` and `cand_cap` the launch's largest: the LDS carve
 };
 
 size_t     filtered_walk_lds_bytes(uint32_t chunks, uint32_t exp, uint32_t cand_cap, uint32_t M0, uint32_t vis_slots);

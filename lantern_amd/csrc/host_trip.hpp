@@ -8,7 +8,8 @@
 // `validate` is nullptr or a `bool(Index *)` (false -> ix->err) that runs under the mutex, after the flush and before anything is
 // allocated: the per-query filtered forms' check that every filter is the index's.  Those forms alone reach a trip with an empty
 // batch (nq == 0 or k == 0): its filters are checked all the same, then the trip returns silently.  (A params form's k == 0 is the
-// width of its answer rows, not an empty batch: it is launched.)
+// width of its answer rows, not an empty batch: it is launched -- a `validate` of such a form says so with a member
+// `static constexpr bool zero_width_rows = true`.)
 #pragma once
 #include <mutex>
 #include <string>
@@ -18,6 +19,11 @@
 #include "index.hpp"
 
 namespace lgpu {
+
+template <class V, class = void> struct ZeroWidthRows : std::false_type {};
+template <class V> struct ZeroWidthRows<V, std::void_t<decltype(V::zero_width_rows)>> : std::true_type {};
+// a validating form's empty batch
+template <class V> inline bool trip_is_empty(size_t nq, size_t k) { return nq == 0 || (k == 0 && !ZeroWidthRows<V>::value); }
 
 // sync: the index's own page-locked block and stream, everything under ix->mu.
 template <class Validate, class Launch>
@@ -29,7 +35,7 @@ void host_trip_sync(Index *ix, size_t nq, size_t k, size_t extra_bytes, const vo
     ix->err.clear();
     if constexpr(!std::is_null_pointer<Validate>::value) {
         if(!validate(ix)) { FAIL(e, ix->err.c_str()); return; }
-        if(nq == 0 || k == 0) return;
+        if(trip_is_empty<Validate>(nq, k)) return;
     }
     HostBatch b = batch_layout(ix, Index::kLanes, nq, k, extra_bytes);
     if(!batch_stage(ix, b, queries, kind)) { FAIL(e, kNoStage); return; }
@@ -65,7 +71,7 @@ void host_trip_lane(Index *ix, int lane, size_t nq, size_t k, size_t extra_bytes
                     Validate validate, Launch launch, uint64_t *labels, float *distances, uint32_t *counts, const char **e)
 {
     constexpr bool validates = !std::is_null_pointer<Validate>::value;
-    const bool     empty = validates && (nq == 0 || k == 0);
+    const bool     empty = validates && trip_is_empty<Validate>(nq, k);
     HostBatch      b = batch_layout(ix, lane, nq, k, extra_bytes);
     if(!empty && !batch_stage(ix, b, queries, kind)) { FAIL(e, kNoLaneStage); return; }
     bool ok;

@@ -229,6 +229,7 @@ struct Index
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches
+    uint32_t last_each_params[ 4 ] = {};  // the last per-query filtered call with per-query parameters: largest walk expansion, largest C, largest k + skip on the exact path, queries with k == 0 (lantern_gpu_last_filtered_each_params)
     uint32_t last_params[ 6 ] = {};  // the last per-query-parameter call: launches, queries per list-placement class (3), largest expansion, any spec shape (lantern_gpu_last_params_launch)
     uint32_t last_filtered[ 6 ] = {};  // path, grid, expansion, cand_cap, vis_slots, LDS bytes of the last filtered launch (lantern_gpu_last_filtered_launch)
 

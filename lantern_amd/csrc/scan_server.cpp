@@ -199,6 +199,8 @@ struct lantern_scan_server
     // mixed batches: the back end's search with (k, ef, skip) per query (NULL: a back end without one -- a batch then goes out as one
     // call per distinct (k, ef)).  The device index has it under LANTERN_SCAN_MIXED=1.
     lantern_batch_search_params_fn f_params = nullptr;
+    // ... and the same for the filtered requests: a filter and (k, ef, skip) per query (NULL: they stay grouped by (k, ef))
+    lantern_batch_search_each_params_fn f_each_params = nullptr;
     struct FilterJob { Conn *c = nullptr; void *release = nullptr; uint64_t release_bytes = 0; };  // a connection's message, or a filter to release
     std::thread             filter_thread;
     std::mutex              fmu;
@@ -274,6 +276,17 @@ int default_search_params(void *ctx, const void *queries, size_t nq, size_t, con
     lantern_scan_server *s = (lantern_scan_server *)ctx;
     usearch_error_t      e = nullptr;
     lantern_gpu_search_batch_params_lane(s->index, tl_lane, queries, nq, s->kind, params, k_stride, labels, dists, counts, &e);
+    if(e) { *err = e; return 1; }
+    return 0;
+}
+
+int default_search_each_params(void *ctx, const void *const *filters, const void *queries, size_t nq, size_t, const lantern_gpu_query_params *params,
+                               size_t k_stride, uint64_t *labels, float *dists, uint32_t *counts, const char **err)
+{
+    lantern_scan_server *s = (lantern_scan_server *)ctx;
+    usearch_error_t      e = nullptr;
+    lantern_gpu_search_batch_filtered_each_params_lane(s->index, tl_lane, (const lantern_gpu_filter_t *const *)filters, queries, nq, s->kind, params, k_stride,
+                                                       labels, dists, counts, &e);
     if(e) { *err = e; return 1; }
     return 0;
 }
@@ -630,8 +643,19 @@ void dispatch_loop(lantern_scan_server *s, int lane)
         // ... unless the back end takes (k, ef) per query (f_params: the device index, lantern_gpu_search_batch_params_lane*): the
         // unfiltered requests of a batch then go out in ONE call whatever their (k, ef) -- group kind 2, keyed (0, 0).  A batch whose
         // unfiltered requests share one (k, ef) anyway makes the uniform call it always made.
+        // ... and the same for the FILTERED requests where the back end takes a filter and (k, ef) per query (f_each_params: the device
+        // index, lantern_gpu_search_batch_filtered_each_params_lane): with more than one distinct (k, ef) among them they go out in ONE
+        // call -- group kind 3, keyed (0, 0); with one shared (k, ef) they make the per-query-filter call they always made.
         std::map<std::pair<std::pair<uint32_t, uint32_t>, int>, std::vector<size_t>> groups;
-        bool mixed_batch = false;
+        bool mixed_batch = false, mixed_filtered = false;
+        if(s->f_each_params) {
+            const Conn *first = nullptr;
+            for(const Conn *c : batch) {
+                if(!c->filter) continue;
+                if(!first) first = c;
+                else if(c->k != first->k || c->ef != first->ef) { mixed_filtered = true; break; }
+            }
+        }
         if(s->f_params) {
             const Conn *first = nullptr;
             for(const Conn *c : batch) {
@@ -643,6 +667,7 @@ void dispatch_loop(lantern_scan_server *s, int lane)
         for(size_t i = 0; i < batch.size(); ++i) {
             const Conn *c = batch[ i ];
             if(mixed_batch && !c->filter) groups[ { { 0u, 0u }, 2 } ].push_back(i);
+            else if(mixed_filtered && c->filter) groups[ { { 0u, 0u }, 3 } ].push_back(i);
             else groups[ { { c->k, c->ef }, c->filter ? 1 : 0 } ].push_back(i);
         }
         touched.assign(s->io.size(), 0);
@@ -652,7 +677,7 @@ void dispatch_loop(lantern_scan_server *s, int lane)
         const bool direct = batch.size() <= 8;
         for(auto &kv : groups) {
             const size_t ef = kv.first.first.second, nq = kv.second.size();
-            const bool   filtered = kv.first.second == 1, mixed = kv.first.second == 2;
+            const bool   filtered = kv.first.second == 1 || kv.first.second == 3, mixed = kv.first.second >= 2;
             // the answer rows' width: the group's k, or -- a mixed group -- its largest; k_of(j): what request j of the group asked for
             std::vector<lantern_gpu_query_params> qp;
             size_t                                k = kv.first.first.first;
@@ -728,14 +753,21 @@ void dispatch_loop(lantern_scan_server *s, int lane)
                 }
                 s->n_filtered += nq;
                 s->n_each_calls += 1;
-                rc = s->f_each(s->fn_ctx, fl.data(), qbuf.data(), nq, s->vec_bytes, k, ef, labels.data(), dists.data(), counts.data(), &err);
+                // (a mixed group: the filter and the parameters of request j, the rows k wide)
+                auto each = [&](size_t j, size_t count, const char **why) {
+                    return mixed ? s->f_each_params(s->fn_ctx, &fl[ j ], &qbuf[ j * s->vec_bytes ], count, s->vec_bytes, &qp[ j ], k, &labels[ j * k ], &dists[ j * k ],
+                                                    &counts[ j ], why)
+                                 : s->f_each(s->fn_ctx, &fl[ j ], &qbuf[ j * s->vec_bytes ], count, s->vec_bytes, k, ef, &labels[ j * k ], &dists[ j * k ],
+                                             &counts[ j ], why);
+                };
+                rc = each(0, nq, &err);
                 if(rc != 0 && nq > 1) {
-                    // one bad filter (stale: the index grew since it was built) refuses the whole call: ask again one by one, so that
-                    // only the connections whose filter is at fault get the error frame
+                    // one bad filter (stale: the index grew since it was built) or one request's parameters refuse the whole call: ask
+                    // again one by one, so that only the connections at fault get the error frame
                     for(size_t j = 0; j < nq; ++j) {
                         const char *err1 = nullptr;
                         s->n_each_calls += 1;
-                        rc = s->f_each(s->fn_ctx, &fl[ j ], &qbuf[ j * s->vec_bytes ], 1, s->vec_bytes, k, ef, &labels[ j * k ], &dists[ j * k ], &counts[ j ], &err1);
+                        rc = each(j, 1, &err1);
                         if(rc != 0) msg = std::string(err1 ? err1 : "lantern_scan_server: the batch search failed");
                         const uint32_t which = (uint32_t)j;
                         deliver(&which, 1);
@@ -909,6 +941,7 @@ try {
     constexpr bool kMixedByDefault = false;
     if(const char *mx = std::getenv("LANTERN_SCAN_MIXED")) { if(std::atoi(mx) != 0) s->f_params = default_search_params; }
     else if(kMixedByDefault) s->f_params = default_search_params;
+    if(s->f_params) s->f_each_params = default_search_each_params;  // (the same switch: the filtered requests of a batch in one call, too)
     // dispatchers = lanes of lantern_gpu_search_batch_lane (up to four batches in flight on the device, each in its own slab of
     // visited bitmaps).  Default four; LANTERN_SCAN_LANES = 1 .. 8.  Measured with lantern-scan-load on 100k x 128 (round 4,
     // profiles/r04_scan_load_lanes.jsonl; lanes 1 / 2 / 3 / 4): 16 backends p50 201 / 214 / 193 / 173 us, 64: 301 / 243 / 235 / 227 us,
@@ -965,6 +998,29 @@ try {
     s->f_make = make;
     s->f_free = free_fn;
     s->f_each = each;
+    s->vec_bytes = vec_bytes;
+    if(const char *ln = std::getenv("LANTERN_SCAN_LANES")) s->lanes = std::min(kMaxLanes, std::max(1, std::atoi(ln)));
+    return start_common(s, host, port, max_batch, max_wait_us, e);
+}
+LANTERN_ABI_CATCH(e)
+
+lantern_scan_server_t *lantern_scan_server_start_filtered_params_fn(lantern_batch_search_fn fn, lantern_scan_filter_make_fn make, lantern_scan_filter_free_fn free_fn,
+                                                                    lantern_batch_search_each_fn each, lantern_batch_search_each_params_fn each_params, void *ctx,
+                                                                    size_t vec_bytes, const char *host, int port, size_t max_batch, unsigned max_wait_us,
+                                                                    usearch_error_t *e)
+try {
+    if(e) *e = nullptr;
+    if(!fn || !make || !free_fn || !each || !each_params || vec_bytes == 0 || vec_bytes > MAX_VEC_BYTES) {
+        if(e) *e = "lantern_gpu: bad scan server arguments";
+        return nullptr;
+    }
+    lantern_scan_server *s = new lantern_scan_server();
+    s->fn = fn;
+    s->fn_ctx = ctx;
+    s->f_make = make;
+    s->f_free = free_fn;
+    s->f_each = each;
+    s->f_each_params = each_params;
     s->vec_bytes = vec_bytes;
     if(const char *ln = std::getenv("LANTERN_SCAN_LANES")) s->lanes = std::min(kMaxLanes, std::max(1, std::atoi(ln)));
     return start_common(s, host, port, max_batch, max_wait_us, e);

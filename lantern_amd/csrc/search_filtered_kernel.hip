@@ -285,15 +285,29 @@ __device__ int search_level_filtered(const View &v, WalkLds &s, uint64_t *nx, ui
 
 #define LGPU_FARG(base, field) LGPU_KARG(base, decltype(FilteredArgs::field), offsetof(FilteredArgs, field))
 
+// a query's row {k, expansion (exact: k + skip), skip, C} of FilteredArgs::qparams (wave-uniform: q came through the scalar cache, and
+// so does the row -- as query_params of search_kernel.hpp)
+struct FilteredQueryParams { uint32_t k, exp, skip, cand_cap; };
+__device__ __forceinline__ FilteredQueryParams filtered_query_params(KernargBytes ka, uint32_t q)
+{
+    const ConstWords row = (ConstWords)(uintptr_t)LGPU_FARG(ka, qparams) + (size_t)q * 4;
+    return FilteredQueryParams{ row[ 0 ], row[ 1 ], row[ 2 ], row[ 3 ] };
+}
+
 // EACH: the per-query form.  The launch serves the queries of its selection list (FrameArgs::qlist), and the filter of a query is
 // its descriptor (FilteredArgs::descs[q]), read from memory anew for every query at the point that needs it: a workgroup serves many
 // queries and carries nothing of one query's filter into the next.  A descriptor with count 0 (and no unfiltered mark) is an empty
 // filter: no walk, the empty answer.
 // SEEDED (with EACH only): the seeded walk of the header, S' = min(FilteredArgs::seeds, the descriptor's count), 0 for an unfiltered entry.
-template <int METRIC, int G, bool EACH, bool SEEDED = false>
+// PARAMS (with EACH only): the per-query-parameter form.  A query brings its own k, expansion, skip and C in its row of
+// FilteredArgs::qparams, read anew for every ticket at the point that needs it, as the descriptor is: nothing of one query's
+// parameters is carried into the next.  The LDS carve stays the launch's (FilteredArgs::exp and cand_cap: the largest of its list), the
+// walk runs with the query's own expansion and C, the answer rows are FilteredArgs::k wide.  k = 0: no walk, the empty answer.
+template <int METRIC, int G, bool EACH, bool SEEDED = false, bool PARAMS = false>
 __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
 {
     static_assert(EACH || !SEEDED, "the seeded walk is instantiated in the per-query form only");
+    static_assert(EACH || !PARAMS, "the per-query-parameter form is instantiated in the per-query form only");
     const int tid = threadIdx.x, T = blockDim.x;
     WalkLds   s;
     uint64_t *nx, *nx2;
@@ -334,24 +348,39 @@ __global__ void __launch_bounds__(512) k_search_filtered(FilteredArgs)
             } else {
                 allow = LGPU_FARG(ka, allow_bits);
             }
+            if constexpr(PARAMS) any = any && filtered_query_params(ka, q).k != 0;
             if(v.n != 0 && any) {
                 const uint32_t start = greedy_descent<METRIC, G>(v, s, v.entry, v.max_level, 0, D);
-                cnt = search_level_filtered<METRIC, G, EACH, SEEDED>(v, s, nx, nx2, allow, bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
-                                                                     (int)LGPU_FARG(ka, cand_cap), D, E, seed_slots, seed_count, S);
+                if constexpr(PARAMS) {
+                    const FilteredQueryParams p = filtered_query_params(ka, q);
+                    cnt = search_level_filtered<METRIC, G, EACH, SEEDED>(v, s, nx, nx2, allow, bitmap, bm_words, start, (int)p.exp, (int)p.cand_cap, D, E,
+                                                                         seed_slots, seed_count, S);
+                } else {
+                    cnt = search_level_filtered<METRIC, G, EACH, SEEDED>(v, s, nx, nx2, allow, bitmap, bm_words, start, (int)LGPU_FARG(ka, exp),
+                                                                         (int)LGPU_FARG(ka, cand_cap), D, E, seed_slots, seed_count, S);
+                }
             }
         }
         const KernargBytes kb = kernarg_opaque();
-        const uint32_t     k = LGPU_FARG(kb, k);
-        const int          got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, k, LGPU_FARG(kb, skip), k);
+        int                got;
+        if constexpr(PARAMS) {  // (FilteredArgs::k: the width of an answer row)
+            const FilteredQueryParams p = filtered_query_params(kb, q);
+            got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, p.k, p.skip, LGPU_FARG(kb, k));
+        } else {
+            const uint32_t k = LGPU_FARG(kb, k);
+            got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, k, LGPU_FARG(kb, skip), k);
+        }
         pos = frame_close<FilteredArgs>(tid, kb, s, q, pos, got, D, E);
     }
 }
 
 // The exact path: rows_per_round allowed rows per round (two per G-lane group, group_dist2_n as the walk's hops), merged into an
 // LDS list of k + skip keys when any of them beats its worst.
-template <int METRIC, int G, bool EACH>
+// PARAMS (with EACH only): as k_search_filtered's -- the list is carved for the launch's largest k + skip, a query keeps its own.
+template <int METRIC, int G, bool EACH, bool PARAMS = false>
 __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
 {
+    static_assert(EACH || !PARAMS, "the per-query-parameter form is instantiated in the per-query form only");
     const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
     WalkLds   s;
     {
@@ -378,7 +407,14 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
                 slots = LGPU_FARG(ka, allow_slots);
                 count = (int)LGPU_FARG(ka, allow_count);
             }
-            const int kk = (int)LGPU_FARG(ka, exp), R = 2 * NG;
+            int kk = 0;
+            if constexpr(PARAMS) {
+                const FilteredQueryParams p = filtered_query_params(ka, q);
+                kk = (int)p.exp;
+                if(p.k == 0) count = 0;  // no pass: D = 0
+            }
+            if constexpr(!PARAMS) kk = (int)LGPU_FARG(ka, exp);
+            const int R = 2 * NG;
             for(int base = 0, round = 0; base < count; base += R, ++round) {
                 const int      nr = count - base < R ? count - base : R;
                 const uint64_t worst = cnt == kk ? s.keys[ kk - 1 ] : ~0ull;
@@ -421,8 +457,14 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
             D = (uint32_t)count;
         }
         const KernargBytes kb = kernarg_opaque();
-        const uint32_t     k = LGPU_FARG(kb, k);
-        const int          got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, k, LGPU_FARG(kb, skip), k);
+        int                got;
+        if constexpr(PARAMS) {  // (FilteredArgs::k: the width of an answer row)
+            const FilteredQueryParams p = filtered_query_params(kb, q);
+            got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, p.k, p.skip, LGPU_FARG(kb, k));
+        } else {
+            const uint32_t k = LGPU_FARG(kb, k);
+            got = frame_answer_rows<FilteredArgs>(tid, T, kb, s, q, cnt, k, LGPU_FARG(kb, skip), k);
+        }
         pos = frame_close<FilteredArgs>(tid, kb, s, q, pos, got, D, 0);
     }
 }
@@ -433,10 +475,12 @@ __global__ void __launch_bounds__(512) k_search_exact_allowed(FilteredArgs)
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.frame.vis_slots);
-    if(a.seeds && !a.descs) return hipErrorInvalidValue;  // the seeded walk exists in the per-query form only (filter.hip builds the table)
+    if((a.seeds || a.qparams) && !a.descs) return hipErrorInvalidValue;  // the seeded walk and the per-query parameters exist in the per-query form only (filter.hip builds the table)
 #define CALL(MM, GG)                                                                   \
     {                                                                                  \
-        if(a.seeds) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true, true)   \
+        if(a.qparams && a.seeds) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true, true, true) \
+        else if(a.qparams) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true, false, true) \
+        else if(a.seeds) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true, true) \
         else if(a.descs) LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, true)    \
         else LGPU_LAUNCH_FILTERED(k_search_filtered, lds, MM, GG, false)               \
     }
@@ -448,9 +492,11 @@ hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, 
 hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_exact_lds_bytes(a.view.chunks, a.exp, a.rows_per_round);
+    if(a.qparams && !a.descs) return hipErrorInvalidValue;
 #define CALL(MM, GG)                                                                   \
     {                                                                                  \
-        if(a.descs) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG, true)    \
+        if(a.qparams) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG, true, true) \
+        else if(a.descs) LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG, true)    \
         else LGPU_LAUNCH_FILTERED(k_search_exact_allowed, lds, MM, GG, false)          \
     }
     LGPU_DISPATCH(metric, a.view.chunks, CALL);

@@ -20,6 +20,13 @@ measures the per-query-filter call instead (lantern_gpu_search_batch_filtered_ea
   * shared_filter: ONE 10 % filter for --nq queries through the per-query call against search_batch_filtered_device (the same walks;
     the per-query form pays the descriptor reads and the selection list): queries/s of both, alternated, and their ratio.
 
+    python scripts/bench_filtered.py --each-params [--nq-each 256]
+
+measures the per-query-filter call with per-query (k, ef) (lantern_gpu_search_batch_filtered_each_params_device) and prints
+ONE JSON line: --nq-each queries, each with its OWN random filter, four distinct (k, ef) among them, at 10 % (walk path) and at 0.1 %
+(exact path): ONE call against the only way the uniform per-query-filter API answers the batch -- one
+lantern_gpu_search_batch_filtered_each_device call per distinct (k, ef); wall-clock queries/s of both, alternated, every repeat listed.
+
     python scripts/bench_filtered.py --seeds 0,64,256
 
 measures the seeded walk (lantern_gpu_set_filter_seeds) and prints ONE JSON line: per filter -- the random and
@@ -108,6 +115,61 @@ def each_legs(a, ix, rows, dq, bufs, k, ef):
     return out
 
 
+EACH_PARAMS_ROWS = [(10, 64), (20, 64), (10, 128), (40, 200)]  # the four (k, ef) of --each-params: query i takes row i % 4
+
+
+def each_params_legs(a, ix, rows, k_stride):
+    """One per-query-filter call with per-query (k, ef) against one uniform per-query-filter call per distinct (k, ef) (module docstring)."""
+    stride, m = rows.strides[0], a.nq_each
+    classes = [[i for i in range(m) if i % 4 == c] for c in range(4)]
+    params = capi.query_params([EACH_PARAMS_ROWS[i % 4] + (0,) for i in range(m)])
+    dq = hip.Buffer.from_numpy(np.ascontiguousarray(rows[:m]))
+    dq_c = [hip.Buffer.from_numpy(np.ascontiguousarray(rows[:m][idx])) for idx in classes]  # (each class's queries side by side)
+    lab, dist, slot = hip.Buffer(m * k_stride * 8), hip.Buffer(m * k_stride * 4), hip.Buffer(m * k_stride * 4)
+    cnt, D, E = hip.Buffer(m * 4), hip.Buffer(m * 8), hip.Buffer(m * 8)
+
+    def wall(fn):
+        hip.synchronize()
+        t = time.perf_counter()
+        fn()
+        hip.synchronize()
+        return m / (time.perf_counter() - t)
+
+    out = {"each_params": [], "reps": a.reps, "rows": EACH_PARAMS_ROWS}
+    ix.set_filter_policy("auto")
+    rng = np.random.default_rng(11)
+    for sel in (0.1, 0.001):
+        filters = [ix.filter_from_bitmap(rng.random(a.n) < sel) for _ in range(m)]
+        F = capi.GpuIndex._filter_array(filters, m)
+        F_c = [capi.GpuIndex._filter_array([filters[i] for i in idx], len(idx)) for idx in classes]
+
+        def one_call():
+            ix.search_batch_filtered_each_params_device(F, dq.ptr, stride, m, params, k_stride, lab.ptr, dist.ptr, slot.ptr, cnt.ptr, D.ptr, E.ptr)
+
+        def four_calls():
+            at = q0 = 0
+            for c, idx in enumerate(classes):  # class c's answers behind those of the classes before it
+                k, ef = EACH_PARAMS_ROWS[c]
+                ix.search_batch_filtered_each_device(F_c[c], dq_c[c].ptr, stride, len(idx), k, ef, 0, lab.ptr + at * 8, dist.ptr + at * 4,
+                                                     slot.ptr + at * 4, cnt.ptr + q0 * 4, D.ptr + q0 * 8, E.ptr + q0 * 8)
+                at += len(idx) * k
+                q0 += len(idx)
+
+        one_call()
+        regime, carve = ix.last_filtered_each(), ix.last_filtered_each_params()
+        mean_D = float(D.download(m, np.uint64).mean())
+        four_calls()
+        together, apart = [], []
+        for _ in range(a.reps):  # alternated
+            together.append(wall(one_call))
+            apart.append(wall(four_calls))
+        out["each_params"].append({"selectivity": sel, "queries": m, "filters": m, "regime": regime, "carve": carve, "mean_D": mean_D,
+                                   "one_call_qps": together, "one_call_per_k_ef_qps": apart, "ratio_best": max(together) / max(apart)})
+        for f in filters:
+            f.close()
+    return out
+
+
 def seeds_legs(a, ix, cluster, filtered, timed_once, slot, D, k):
     """The seeded walk per filter and seeds value (module docstring)."""
     values = [int(x) for x in a.seeds.split(",")]
@@ -162,6 +224,7 @@ def main():
     p.add_argument("--nq-exact", type=int, default=256)
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--each", action="store_true", help="the legs of the per-query-filter call")
+    p.add_argument("--each-params", action="store_true", help="the legs of the per-query-filter call with per-query (k, ef)")
     p.add_argument("--nq-each", type=int, default=256)
     p.add_argument("--seeds", default="", help="comma-separated seeds values: the legs of the seeded walk")
     a = p.parse_args()
@@ -202,6 +265,11 @@ def main():
 
     out = {"workload": f"clustered {a.n}x{a.dim} f32 l2sq M={M} efc={efc} ef={ef} k={k}", "queries": nq, "queries_exact": a.nq_exact,
            "build_seconds": build_s}
+    if a.each_params:
+        out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
+        out.update(each_params_legs(a, ix, rows, max(r[0] for r in EACH_PARAMS_ROWS)))
+        print(json.dumps(out))
+        return
     if a.each:
         out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
         out.update(each_legs(a, ix, rows, dq, (lab, dist, slot, cnt, D, E), k, ef))
