@@ -376,6 +376,29 @@ LANTERN_GPU_EXPORT void lantern_gpu_set_filter_seeds(usearch_index_t, size_t see
  * it alone), [2] queries of the last filtered call that ran seeded, [3] walk-path queries of that call that did not (seeds = 0, or
  * NULL entries) */
 LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_seeds(usearch_index_t, uint32_t out[4], usearch_error_t *);
+/* COMPACT PQ INDEXES (DESIGN.md 4.9 "Compact pq indexes").  A compact pq index (lantern_gpu_pq_compact) keeps only its code bytes in
+ * HBM.  on = 0, THE DEFAULT: every filtered search on it is refused -- "filtered search does not run on a compact pq index: expand it
+ * first (lantern_gpu_pq_expand)" -- as before this switch existed.  on = 1: every filtered entry point -- single filter, per query,
+ * per-query (k, ef, skip), seeded walk, cursor, scan, scan-side service -- serves it, by the row routine the unfiltered search of that
+ * index takes:
+ *  - rows DECODED ON THE FLY (subvectors of whole 16-byte chunks, LANTERN_GPU_PQ_ADC unset or 0): the expanded index's arithmetic.
+ *    With the same filter and policy every answer is the expanded index's: ids, distance bits, counts, D, E, and the launch shape
+ *    lantern_gpu_last_filtered_launch reports;
+ *  - ADC over the code rows (every other compact index): a row's distance is the unfiltered compact search's, bit for bit, on the walk
+ *    and the exact path.  The per-query table (16 KiB per 16-byte chunk of a code row: 32 KiB at 32 subvectors, 128 KiB at 128 -- and
+ *    at 96, whose rows sit at the 128-byte stride) lies in the launch's LDS in front of the raw query row, the walk's lists and the
+ *    visited set, within the same 160 KiB: expansions and k + skip that no
+ *    longer fit beside it are refused with the texts of the calls above, the visited set takes what is left (at most 2048 slots;
+ *    below 4 M0 the HBM bitmap alone: its size changes no answer, D or E), and one workgroup runs per CU where two do not fit.
+ *    The table is built anew for every query, and for none that evaluates no row (an empty filter, k_i == 0).
+ * The path rule and its default exact_factor are unchanged: the f32 rows' 5.6, which also fits decoded rows; ADC's measured crossover is
+ * far higher, and a caller who serves an ADC index may raise exact_factor through lantern_gpu_set_filter_policy.
+ * on other than 0 or 1 is refused.  On an index that is not compact the setting changes nothing.  Default off until the path has
+ * been measured on a device, as lantern_gpu_set_filter_seeds. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_compact(usearch_index_t, int on, usearch_error_t *);
+/* diagnostic: 0 the switch is off; else what a filtered search on the index as it stands now runs on: 1 stored rows (the index is
+ * not compact), 2 rows decoded on the fly, 3 ADC */
+LANTERN_GPU_EXPORT int lantern_gpu_filter_compact(usearch_index_t, usearch_error_t *);
 /* launches of the two filtered kernels since the index was created */
 LANTERN_GPU_EXPORT void lantern_gpu_filter_stats(usearch_index_t, uint64_t *walk_launches, uint64_t *exact_launches, usearch_error_t *);
 /* the shape of the last filtered launch on this index (diagnostic; tests assert the regime a launch ran in):
@@ -405,7 +428,7 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered_device(usearch_index_t
  * alone is one exact launch.  k, ef and skip -- hence expansion, C and the LDS carve -- are the call's, uniform over its queries.
  * An entry that is not a live filter handle, belongs to another index or is stale refuses the WHOLE call before anything is
  * launched or written: the single-filter message plus " (filters[i])", i the first offending position.  Compact pq indexes are
- * refused as by the single-filter calls.
+ * refused or served as by the single-filter calls (lantern_gpu_set_filter_compact).
  * Lifetime: a filter may be freed by its owner as soon as the call that used it has returned (the host and lane forms), or the
  * work queued on `stream` has completed (the device form).  The filters[] array itself is read only during the call.
  * lantern_gpu_filter_stats counts the launches; lantern_gpu_last_filtered_launch is not updated by these calls. */
@@ -451,7 +474,7 @@ LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each(usearch_index_t, uint32_t
  *     first with " (params[i])", i the first offender;
  *  (the scalar kind and NULL buffers of the host forms, the lane number before everything, the row stride of the device form)
  *  3. the filters: not a live handle / another index / stale, with " (filters[i])";
- *  4. a compact pq index, with the single-filter calls' text;
+ *  4. a compact pq index, with the single-filter calls' text, unless lantern_gpu_set_filter_compact serves it;
  *  5. a query whose own shape exceeds the 160 KiB LDS budget, in batch order: the uniform call's text plus " (params[i])";
  *  6. "... the largest expansion and the largest candidate cap of the batch do not fit together: split the batch": every query fits
  *     alone, the walk launch's joint carve does not.  This needs the automatic cap (an explicit cand_cap gives the query of the largest
@@ -496,6 +519,16 @@ LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each_params(usearch_index_t, u
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_params(const int64_t in[8], const int64_t counts[],
                                                                 const lantern_gpu_query_params params[], size_t nq, uint32_t per_query[][4],
                                                                 uint32_t launch[2][6]);
+/* The same plan for a compact pq index served under lantern_gpu_set_filter_compact -- what the entry points plan such a call through;
+ * pure as the one above.  in[9]: in[0..8) as above, [0] the chunks of a DECODED row (= of a raw f32 query row); [8] the 16-byte chunks
+ * of a code row where the index is served by ADC (1..8: num_subvectors padded to 16, / 16), 0 where its rows are decoded on the fly.
+ * With in[8] == 0 every field is lantern_gpu_plan_filtered_params' on the same in[0..8): the expanded index's shape.  With ADC the
+ * carve is: table (in[8] x 16384 bytes) | raw query row | the lists | the visited set; 8 lanes per row; vis_slots what fits in the
+ * workgroup's 160 KiB, at most 2048, 0 below 4 M0.  per_query as above.  launch[l]: [0..6) as above, [6] the table's bytes (0: no
+ * table, or no such launch).  Returns NULL or the refusal, with the texts and " (params[i])" rules of refusals 5 and 6. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_compact(const int64_t in[9], const int64_t counts[],
+                                                                 const lantern_gpu_query_params params[], size_t nq, uint32_t per_query[][4],
+                                                                 uint32_t launch[2][7]);
 /* kernel shape of the search launch: waves per query (1..8; 0 = automatic: 4 when the batch fills the chip, up to 8 for
  * smaller batches) and resident workgroups (0 = auto) */
 LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_per_query, int max_workgroups,

@@ -115,7 +115,7 @@ EXPORTS = [
     "lantern_gpu_filter_resident_bytes", "lantern_scan_server_start_filtered_fn", "lantern_scan_server_filter_stats", "lantern_scan_client_set_filter",
     "lantern_scan_client_clear_filter",
     "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
-    "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds",
+    "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds", "lantern_gpu_set_filter_compact", "lantern_gpu_filter_compact", "lantern_gpu_plan_filtered_compact",
     # ... with per-query k, ef and skip as well (lantern_gpu.h "PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_filtered_each_params", "lantern_gpu_search_batch_filtered_each_params_lane",
     "lantern_gpu_search_batch_filtered_each_params_device", "lantern_gpu_last_filtered_each_params", "lantern_gpu_plan_filtered_params",
@@ -340,6 +340,9 @@ def lib() -> C.CDLL:
         "lantern_gpu_last_filtered_each_params": (None, [vp, vp, err]),
         "lantern_gpu_plan_filtered_params": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_set_filter_seeds": (None, [vp, sz, err]),
+        "lantern_gpu_set_filter_compact": (None, [vp, C.c_int, err]),
+        "lantern_gpu_filter_compact": (C.c_int, [vp, err]),
+        "lantern_gpu_plan_filtered_compact": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
         "lantern_gpu_search_batch_params": (None, [vp, vp, sz, i32, vp, sz, vp, vp, vp, err]),
         "lantern_gpu_search_batch_params_lane": (None, [vp, i32, vp, sz, i32, vp, sz, vp, vp, vp, err]),
@@ -798,6 +801,14 @@ class GpuIndex:
     def set_filter_seeds(self, n):
         """The walk path of later filtered searches starts from min(n, allowed) allowed rows (0 = off; at most 4096)."""
         _call("lantern_gpu_set_filter_seeds", self.h, int(n))
+
+    def set_filter_compact(self, on):
+        """Filtered searches serve this index in its compact pq form too (1), or refuse it (0, the default)."""
+        _call("lantern_gpu_set_filter_compact", self.h, int(on))
+
+    def filter_compact(self):
+        """lantern_gpu_filter_compact: None (the switch is off), or what a filtered search runs on now: "stored", "decode" or "adc"."""
+        return {0: None, 1: "stored", 2: "decode", 3: "adc"}[int(_call("lantern_gpu_filter_compact", self.h))]
 
     def last_filtered_seeds(self):
         """lantern_gpu_last_filtered_seeds: the setting, S' of the last single-filter walk launch, seeded / unseeded walk queries of the last call."""
@@ -1272,6 +1283,27 @@ def plan_filtered_params(fields, counts, params):
     why = lib().lantern_gpu_plan_filtered_params(_ptr(a), _ptr(cnt), _ptr(P), len(P), _ptr(per), _ptr(launch))
     queries = [dict(zip(PLAN_FILTERED_QUERY, (int(x) for x in per[i]))) for i in range(len(P))]
     launches = {name: dict(zip(PLAN_FILTERED_LAUNCH, (int(x) for x in launch[l]))) for l, name in enumerate(("walk", "exact"))}
+    return queries, launches, (why.decode() if why else None)
+
+
+# lantern_gpu_plan_filtered_compact's arrays: the decoded row's chunks in "chunks", the code row's in "code_chunks" (0: decode on the fly)
+PLAN_FILTERED_COMPACT_IN = PLAN_FILTERED_IN + ("code_chunks",)
+PLAN_FILTERED_COMPACT_LAUNCH = PLAN_FILTERED_LAUNCH + ("table_bytes",)
+
+
+def plan_filtered_compact(fields, counts, params):
+    """plan_filtered_params for a compact pq index served under set_filter_compact (host arithmetic, no device): `fields` a dict of
+    PLAN_FILTERED_COMPACT_IN; the launch dicts carry "table_bytes" too."""
+    vals = [int(np.float64(fields[n]).view(np.int64)) if n == "exact_factor" else int(fields[n]) for n in PLAN_FILTERED_COMPACT_IN]
+    a = np.asarray(vals, dtype=np.int64)
+    cnt = np.ascontiguousarray(counts, dtype=np.int64)
+    P = query_params(params)
+    assert len(P) == len(cnt)
+    per = np.zeros((max(len(P), 1), 4), dtype=np.uint32)
+    launch = np.zeros((2, 7), dtype=np.uint32)
+    why = lib().lantern_gpu_plan_filtered_compact(_ptr(a), _ptr(cnt), _ptr(P), len(P), _ptr(per), _ptr(launch))
+    queries = [dict(zip(PLAN_FILTERED_QUERY, (int(x) for x in per[i]))) for i in range(len(P))]
+    launches = {name: dict(zip(PLAN_FILTERED_COMPACT_LAUNCH, (int(x) for x in launch[l]))) for l, name in enumerate(("walk", "exact"))}
     return queries, launches, (why.decode() if why else None)
 
 

@@ -168,11 +168,24 @@ struct FilterPlanIn
     size_t   cand_cap;
     double   exact_factor;
     size_t   seeds;  // lantern_gpu_set_filter_seeds (changes no shape: a round of seeds is at most M0 rows, a hop's)
+    // a compact pq index served by ADC (search_filtered_pq_kernel.hip): 16-byte chunks of a code row, 1..8; `chunks` is then the raw query
+    // row's.  0: rows of `chunks` chunks, stored -- or decoded on the fly, whose shape is the expanded index's
+    uint32_t adc_code_chunks = 0;
 };
+// a compact pq index's row routine, by plan_search's own condition (search_plan.cpp): decoded on the fly, else ADC
+static bool compact_adc(const Index *ix) { return ix->pq_compact && (search_env().pq_adc || ix->pqd_inv == 0); }
 static FilterPlanIn filter_plan_in(const Index *ix)
 {
-    return FilterPlanIn{ ix->chunks, ix->M0, ix->n, ix->ef, ix->filter_path, ix->filter_cand_cap, ix->filter_exact_factor, ix->filter_seeds };
+    FilterPlanIn p{ ix->chunks, ix->M0, ix->n, ix->ef, ix->filter_path, ix->filter_cand_cap, ix->filter_exact_factor, ix->filter_seeds };
+    if(compact_adc(ix)) p.adc_code_chunks = ix->pq_S16 / 16;
+    return p;
 }
+// What lies in front of the lists in a launch's LDS, in chunks: the query row -- ADC: the table first (code_chunks x 16 KiB:
+// RowAcc<M_*_ADC> reads it from the first LDS bytes), the raw query row behind it
+static uint32_t plan_lds_chunks(const FilterPlanIn &p) { return p.adc_code_chunks ? filtered_adc_lds_chunks(p.adc_code_chunks, p.chunks) : p.chunks; }
+static size_t   plan_table_bytes(const FilterPlanIn &p) { return (size_t)filtered_adc_lds_chunks(p.adc_code_chunks, 0) * 16; }
+// lanes per row: a code row has at most 8 chunks
+static int plan_lanes(const FilterPlanIn &p) { return p.adc_code_chunks ? 8 : group_lanes_for(p.chunks); }
 
 // exp, cand_cap, vis_slots / rows_per_round and the LDS bytes of one launch
 struct FilteredShape
@@ -190,20 +203,23 @@ static const char *kJointOverBudget =
 static void exact_carve(const FilterPlanIn &p, size_t kk, FilteredShape &s)
 {
     s.exp = (uint32_t)kk;
-    s.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / group_lanes_for(p.chunks));
-    s.lds = filtered_exact_lds_bytes(p.chunks, s.exp, s.rows_per_round);
+    s.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / plan_lanes(p));
+    s.lds = filtered_exact_lds_bytes(plan_lds_chunks(p), s.exp, s.rows_per_round);
 }
-// the walk launch's carve for `exp` keys of top and `cap` of next: the visited set takes what is left of the LDS target
+// the walk launch's carve for `exp` keys of top and `cap` of next: the visited set takes what is left of the LDS target -- beside an
+// ADC table, which alone may exceed that target, what is left of the workgroup's LDS (at most 2048 slots either way)
 static void walk_carve(const FilterPlanIn &p, size_t exp, size_t cap, FilteredShape &s)
 {
     s.exp = (uint32_t)exp;
     s.cand_cap = (uint32_t)cap;
+    const uint32_t chunks = plan_lds_chunks(p);
+    const size_t   target = p.adc_code_chunks ? kFilteredLds : kFilteredLdsTarget;
     uint32_t vis_slots = 2048;
-    while(vis_slots && filtered_walk_lds_bytes(p.chunks, s.exp, s.cand_cap, p.M0, vis_slots) > kFilteredLdsTarget)
+    while(vis_slots && filtered_walk_lds_bytes(chunks, s.exp, s.cand_cap, p.M0, vis_slots) > target)
         vis_slots = vis_slots > 256 ? vis_slots - 256 : 0;
     if(vis_slots && vis_slots < 4 * p.M0) vis_slots = 0;
     s.vis_slots = vis_slots;
-    s.lds = filtered_walk_lds_bytes(p.chunks, s.exp, s.cand_cap, p.M0, vis_slots);
+    s.lds = filtered_walk_lds_bytes(chunks, s.exp, s.cand_cap, p.M0, vis_slots);
 }
 // The part of a filtered launch's shape that depends on (k, ef, skip, index) only -- not on the filter.  NULL, or the refusal.
 static const char *filtered_shape_of(const FilterPlanIn &p, bool exact, size_t k, size_t skip, size_t exp, FilteredShape &s)
@@ -212,7 +228,7 @@ static const char *filtered_shape_of(const FilterPlanIn &p, bool exact, size_t k
         exact_carve(p, k + skip, s);
         if(s.lds > kFilteredLds) return kExactOverBudget;
     } else {
-        const size_t base = filtered_walk_lds_bytes(p.chunks, (uint32_t)exp, 0, p.M0, 0);
+        const size_t base = filtered_walk_lds_bytes(plan_lds_chunks(p), (uint32_t)exp, 0, p.M0, 0);
         if(base + exp * 16 > kFilteredLds) return kWalkOverBudget;
         size_t cap = p.cand_cap ? std::max(p.cand_cap, exp) : std::max<size_t>(4 * exp, 256);
         cap = std::min(cap, (kFilteredLds - base) / 16);
@@ -247,11 +263,12 @@ static std::string filter_mismatch(const Index *ix, const Filter *f)
                " (build the filter again)";
     return {};
 }
-// (checked after the filters)
+// (checked after the filters)  A compact pq index is served once lantern_gpu_set_filter_compact has said so.
 static bool filtered_index_ok(Index *ix)
 {
-    if(ix->pq_compact) set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
-    return !ix->pq_compact;
+    const bool refused = ix->pq_compact && !ix->filter_compact;
+    if(refused) set_err(ix, "lantern_gpu: filtered search does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)");
+    return !refused;
 }
 
 // the path of a query under `f`: forced, or the rule of DESIGN.md 4.9 -- a walk under selectivity s evaluates about D / s rows, the
@@ -275,6 +292,20 @@ static FilteredArgs filtered_args(const Index *ix, const uint4 *d_q, size_t k, s
     a.frame.out_labels = out.labels, a.frame.out_dists = out.dists, a.frame.out_slots = out.slots;
     a.frame.out_counts = out.counts, a.frame.out_D = out.D, a.frame.out_E = out.E;
     a.frame.totals = ix->d_totals + kTotSearch;
+    if(ix->pq_compact) {  // the code rows, with what their row routine reads (as search_plan.cpp search_launch fills SearchArgs)
+        a.view.vec = (const uint4 *)ix->d_codes16;
+        if(compact_adc(ix)) {
+            a.view.chunks = ix->pq_S16 / 16;
+            a.adc_centers = ix->d_centers;
+            a.adc_S = ix->pq_S, a.adc_C = ix->pq_C, a.adc_subdim = ix->pq_subdim, a.adc_qchunks = ix->chunks;
+        } else {
+            a.view.pq_centers = (const uint4 *)ix->d_centers;
+            a.view.pq_cps = ix->pq_subdim / 4;
+            a.view.pq_C = ix->pq_C;
+            a.view.pq_inv = ix->pqd_inv;
+            a.view.pq_row_bytes = ix->pq_S16;
+        }
+    }
     return a;
 }
 
@@ -327,8 +358,13 @@ static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, h
     a.frame.bm_words = (uint32_t)ix->slot_words[ slot ];
     a.frame.undo_cap = vis_undo_cap();
     a.frame.ticket = next_ticket(ix, a.frame.nq, grid, stream);
-    const hipError_t e = exact ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream)
-                               : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
+    hipError_t e;
+    if(ix->pq_compact) {
+        const int metric = ix->metric + (a.adc_centers ? M_ADC : M_PQD);
+        e = exact ? launch_search_exact_allowed_pq(metric, a, kFilteredWaves, grid, stream) : launch_search_filtered_pq(metric, a, kFilteredWaves, grid, stream);
+    } else {
+        e = exact ? launch_search_exact_allowed(ix->mcode, a, kFilteredWaves, grid, stream) : launch_search_filtered(ix->mcode, a, kFilteredWaves, grid, stream);
+    }
     if(e != hipSuccess) {
         set_err(ix, std::string("lantern_gpu: HIP error launching the filtered search: ") + hipGetErrorString(e));
         return -1;
@@ -542,7 +578,7 @@ static std::string plan_filtered_params(const FilterPlanIn &p, const int64_t *co
     // one carve per launch.  The exact list's is the carve of its largest k + skip, which fits because that query does; the walk's
     // joins the largest expansion with the largest C, which two different queries may have brought
     if(!out.walk.empty()) {
-        if(filtered_walk_lds_bytes(p.chunks, (uint32_t)max_exp, (uint32_t)max_cap, p.M0, 0) > kFilteredLds) return kJointOverBudget;
+        if(filtered_walk_lds_bytes(plan_lds_chunks(p), (uint32_t)max_exp, (uint32_t)max_cap, p.M0, 0) > kFilteredLds) return kJointOverBudget;
         walk_carve(p, max_exp, max_cap, out.sw);
     }
     if(!out.exact.empty()) exact_carve(p, max_kk, out.se);
@@ -738,6 +774,28 @@ try {
     ix->filter_seeds = seeds;
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_set_filter_compact(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) { FAIL(e, "lantern_gpu: filter_compact must be 0 (compact pq indexes refused) or 1 (served)"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->filter_compact = on != 0;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_filter_compact(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!ix->filter_compact) return 0;
+    return !ix->pq_compact ? 1 : compact_adc(ix) ? 3 : 2;
+}
+LANTERN_ABI_CATCH(e)
 
 void lantern_gpu_last_filtered_seeds(usearch_index_t h, uint32_t out[ 4 ], usearch_error_t *e)
 try {
@@ -963,15 +1021,11 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
-// the plan without a device (include/lantern_gpu.h has the field order)
-const char *lantern_gpu_plan_filtered_params(const int64_t in[ 8 ], const int64_t counts[], const lantern_gpu_query_params params[], size_t nq,
-                                             uint32_t per_query[][ 4 ], uint32_t launch[ 2 ][ 6 ])
-try {
+// the plan without a device (include/lantern_gpu.h has the field order): `cols` words of a launch's row are written
+static const char *plan_flat(const FilterPlanIn &p, const int64_t counts[], const lantern_gpu_query_params params[], size_t nq, uint32_t per_query[][ 4 ],
+                             uint32_t *launch, int cols)
+{
     static thread_local std::string msg;
-    if(!in || !launch || (nq && (!counts || !params || !per_query))) return "lantern_gpu: null array";
-    double factor;
-    std::memcpy(&factor, &in[ 6 ], 8);
-    const FilterPlanIn p{ (uint32_t)in[ 0 ], (uint32_t)in[ 1 ], (size_t)in[ 2 ], (size_t)in[ 3 ], (int)in[ 4 ], (size_t)in[ 5 ], factor, (size_t)in[ 7 ] };
     EachParamsPlan plan;
     msg = plan_filtered_params(p, counts, params, nq, plan);
     if(!msg.empty()) return msg.c_str();
@@ -982,11 +1036,37 @@ try {
         const std::vector<uint32_t> &list = l ? plan.exact : plan.walk;
         const FilteredShape         &s = l ? plan.se : plan.sw;
         for(size_t at = 0; at < list.size(); ++at) per_query[ list[ at ] ][ 3 ] = (uint32_t)at;
-        const uint32_t row[ 6 ] = { (uint32_t)list.size(), s.exp, s.cand_cap, l ? s.rows_per_round : s.vis_slots, (uint32_t)s.lds,
-                                    list.empty() ? 0u : (uint32_t)filtered_per_cu(s.lds) };
-        std::copy(std::begin(row), std::end(row), launch[ l ]);
+        const uint32_t row[ 7 ] = { (uint32_t)list.size(), s.exp, s.cand_cap, l ? s.rows_per_round : s.vis_slots, (uint32_t)s.lds,
+                                    list.empty() ? 0u : (uint32_t)filtered_per_cu(s.lds), list.empty() ? 0u : (uint32_t)plan_table_bytes(p) };
+        std::copy(row, row + cols, launch + l * cols);
     }
     return nullptr;
+}
+static FilterPlanIn plan_in_flat(const int64_t in[ 8 ])
+{
+    double factor;
+    std::memcpy(&factor, &in[ 6 ], 8);
+    return FilterPlanIn{ (uint32_t)in[ 0 ], (uint32_t)in[ 1 ], (size_t)in[ 2 ], (size_t)in[ 3 ], (int)in[ 4 ], (size_t)in[ 5 ], factor, (size_t)in[ 7 ] };
+}
+
+const char *lantern_gpu_plan_filtered_params(const int64_t in[ 8 ], const int64_t counts[], const lantern_gpu_query_params params[], size_t nq,
+                                             uint32_t per_query[][ 4 ], uint32_t launch[ 2 ][ 6 ])
+try {
+    if(!in || !launch || (nq && (!counts || !params || !per_query))) return "lantern_gpu: null array";
+    return plan_flat(plan_in_flat(in), counts, params, nq, per_query, &launch[ 0 ][ 0 ], 6);
+}
+catch(...) {
+    return "lantern_gpu: out of memory planning a filtered search";
+}
+
+const char *lantern_gpu_plan_filtered_compact(const int64_t in[ 9 ], const int64_t counts[], const lantern_gpu_query_params params[], size_t nq,
+                                              uint32_t per_query[][ 4 ], uint32_t launch[ 2 ][ 7 ])
+try {
+    if(!in || !launch || (nq && (!counts || !params || !per_query))) return "lantern_gpu: null array";
+    if(in[ 8 ] < 0 || in[ 8 ] > 8) return "lantern_gpu: a code row has 1 to 8 chunks (0: rows decoded on the fly)";
+    FilterPlanIn p = plan_in_flat(in);
+    p.adc_code_chunks = (uint32_t)in[ 8 ];
+    return plan_flat(p, counts, params, nq, per_query, &launch[ 0 ][ 0 ], 7);
 }
 catch(...) {
     return "lantern_gpu: out of memory planning a filtered search";

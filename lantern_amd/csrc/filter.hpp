@@ -58,11 +58,22 @@ struct FilteredArgs
     // the per-query-parameter form (with descs; k_search_filtered / k_search_exact_allowed <.., PARAMS = true>); NULL otherwise
     const uint4      *qparams;   // [queries of the call] {k, expansion (exact: k + skip), skip, C} by query; `k` above is then the width of an
                                  // answer row, `skip` unused, `exp` and `cand_cap` the launch's largest: the LDS carve
+    // ADC over the code rows of a compact pq index (search_filtered_pq_kernel.hip, M_*_ADC; view.vec = the code rows, view.chunks = 16-byte
+    // chunks per code row): SearchArgs' fields of the same names
+    const float      *adc_centers;  // [S][C][sub_floats] per-subvector centroid tables, rows zero padded to whole chunks
+    uint32_t          adc_S, adc_C, adc_subdim;
+    uint32_t          adc_qchunks;  // 16-byte chunks of a (raw f32) query row
 };
 
 size_t     filtered_walk_lds_bytes(uint32_t chunks, uint32_t exp, uint32_t cand_cap, uint32_t M0, uint32_t vis_slots);
 size_t     filtered_exact_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_round);
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
 hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
+// the same two kernels over a compact pq index (search_filtered_pq_kernel.hip): metric = M_*_PQD (view.chunks: of the DECODED row, the
+// view's pq_* fields set) or M_*_ADC (view.chunks: of the code row, 1..8; adc_* set, adc_C <= 256).  The *_lds_bytes above take the
+// chunks in front of the lists: the decoded row's, or filtered_adc_lds_chunks'.
+hipError_t launch_search_filtered_pq(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
+hipError_t launch_search_exact_allowed_pq(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
+uint32_t   filtered_adc_lds_chunks(uint32_t code_chunks, uint32_t qchunks);  // the ADC table's chunks (code_chunks x 16 KiB) + the raw query row's
 
 }  // namespace lgpu

@@ -226,6 +226,7 @@ struct Index
     size_t   filter_cand_cap = 0;       // 0: max(4 expansion, 256), capped by LDS
     double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
     uint64_t c_filter_walk = 0, c_filter_exact = 0;
+    bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches

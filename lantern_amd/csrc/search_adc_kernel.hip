@@ -13,58 +13,10 @@
 // to define (the fork's is not in the tree): the oracle restates exactly this (oracle/hnsw.c lo_set_pq_view), device and
 // oracle agree bit for bit, and both agree with the decoded-row distances to 1e-5 relative.  PARITY UNPINNED BY THE REFERENCE.
 // Memory: 10M x 768 at 96 subvectors = 0.96 GB of rows instead of 30.7 GB.
+#include "adc_stage.hpp"
 #include "search_kernel.hpp"
 
 namespace lgpu {
-
-// The per-query table: one thread per (subvector, centroid) entry, one fma chain each.  B entries per thread at a time, their
-// centroid loads issued together: the table of centroids comes from L2 (786 KB per query at 96 x 256 x 8), and one chain per
-// thread at a time left the loads' latency bare -- 35 round trips per query, a third of a query's time at ef = 64.
-template <int METRIC, int B>
-__device__ __forceinline__ void adc_build_table(float *lut, const float *centers, const float *rawq, uint32_t S, uint32_t C, uint32_t subdim, uint32_t sub_floats,
-                                                uint32_t tid, uint32_t T)
-{
-    for(uint32_t e0 = tid; e0 < S * C; e0 += B * T) {
-        const float *cent[ B ], *qs[ B ];
-        float        acc[ B ];
-        bool         on[ B ];
-#pragma unroll
-        for(int u = 0; u < B; ++u) {
-            const uint32_t e = e0 + (uint32_t)u * T;
-            on[ u ] = e < S * C;
-            const uint32_t ee = on[ u ] ? e : 0u, sv = ee / C, c = ee % C;
-            cent[ u ] = centers + ((size_t)sv * C + c) * sub_floats;
-            qs[ u ] = rawq + (size_t)sv * subdim;
-            acc[ u ] = 0.f;
-        }
-        for(uint32_t j4 = 0; j4 < sub_floats; j4 += 4) {
-            float4 cv[ B ];
-#pragma unroll
-            for(int u = 0; u < B; ++u) cv[ u ] = *(const float4 *)(cent[ u ] + j4);  // (rows of the centroid table are padded to whole float4s)
-#pragma unroll
-            for(int u = 0; u < B; ++u) {
-                const float cj[ 4 ] = { cv[ u ].x, cv[ u ].y, cv[ u ].z, cv[ u ].w };
-#pragma unroll
-                for(int jj = 0; jj < 4; ++jj) {
-                    if(j4 + (uint32_t)jj < subdim) {
-                        const float qv = qs[ u ][ j4 + (uint32_t)jj ];
-                        if constexpr(METRIC == M_L2SQ_ADC) {
-                            const float t = qv - cj[ jj ];
-                            acc[ u ] = __builtin_fmaf(t, t, acc[ u ]);
-                        } else {
-                            acc[ u ] = __builtin_fmaf(qv, cj[ jj ], acc[ u ]);
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for(int u = 0; u < B; ++u) {
-            const uint32_t e = e0 + (uint32_t)u * T;
-            if(on[ u ]) lut[ (size_t)(e / C) * ADC_LUT_STRIDE + e % C ] = acc[ u ];
-        }
-    }
-}
 
 // SPEC: the latency-bound walk of walk_spec.hpp in its lone-query shape (three role waves + eight row waves, one barrier per hop,
 // neighbour lists fetched with the rows).  A table of 96 x 256 entries leaves room for ONE workgroup per CU, so every query of
@@ -73,8 +25,8 @@ __device__ __forceinline__ void adc_build_table(float *lut, const float *centers
 // 96 subvectors -- and is not instantiated.)
 // EACH: the per-query-parameter form, as k_search's (search_kernel.hpp): the launch's queries come from FrameArgs::qlist, every
 // query's k, expansion and skip from its row of SearchArgs::qparams, answer rows are k_stride wide.
-// The frame around the walk -- pick, bind, answer rows, close -- is query_frame.hpp's; the staging is this kernel's own (the raw
-// query row, the table, and |query| by the chain of the query's own width).
+// The frame around the walk -- pick, bind, answer rows, close -- is query_frame.hpp's; the staging is adc_stage.hpp's (the raw
+// query row, the table, and |query| by the chain of the query's own width), shared with the filtered kernels over ADC rows.
 template <int METRIC, int KPL, int SPEC = 0, bool EACH = false>
 __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(SearchArgs)
 {
@@ -95,7 +47,6 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
     }
     float *const       lut = (float *)s.q;
     const uint4 *const rawq4 = s.q + lut_chunks;
-    const float *const rawq = (const float *)rawq4;
     for(uint32_t pos = blockIdx.x; pos < LGPU_FRAME_ARG(kernarg_opaque(), SearchArgs, nq);) {
         uint32_t    q = pos;
         QueryParams each{};
@@ -109,27 +60,8 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
         if(!EACH || each.k != 0) {  // (a query that wants no rows needs no table)
             const KernargBytes ka = kernarg_opaque();
             const uint32_t     S = LGPU_SEARCH_ARG(ka, adc_S), C = LGPU_SEARCH_ARG(ka, adc_C), subdim = LGPU_SEARCH_ARG(ka, adc_subdim),
-                           sub_floats = ((subdim + 3) / 4) * 4, qchunks = LGPU_SEARCH_ARG(ka, adc_qchunks), S16 = LGPU_VIEW_ARG(ka, SearchArgs, chunks) * 16;
-            const uint4 *queries = LGPU_FRAME_ARG(ka, SearchArgs, queries);
-            for(uint32_t i = tid; i < qchunks; i += T) ((uint4 *)rawq4)[ i ] = queries[ (size_t)q * qchunks + i ];
-            __syncthreads();
-            // entry 0 of the padding rows is +0.0
-            adc_build_table<METRIC, 4>(lut, LGPU_SEARCH_ARG(ka, adc_centers), rawq, S, C, subdim, sub_floats, (uint32_t)tid, (uint32_t)T);  // (8 and 16 at a time: no faster)
-            for(uint32_t sv = S + tid; sv < S16; sv += T) lut[ (size_t)sv * ADC_LUT_STRIDE ] = 0.f;
-            if constexpr(METRIC == M_COS_ADC) {  // |query|: the chain and tree the f32 cosine kernels use for a row of this many chunks
-                const int Gq = group_lanes_for(qchunks);
-                if(tid < Gq) {
-                    float qn;
-                    switch(Gq) {
-                        case 64: qn = group_norm<M_COS, 64>(rawq4, (int)qchunks, tid); break;
-                        case 32: qn = group_norm<M_COS, 32>(rawq4, (int)qchunks, tid); break;
-                        case 16: qn = group_norm<M_COS, 16>(rawq4, (int)qchunks, tid); break;
-                        default: qn = group_norm<M_COS, 8>(rawq4, (int)qchunks, tid); break;
-                    }
-                    if(tid == Gq - 1) s.scal[ S_QN2 ] = __float_as_int(qn);
-                }
-            }
-            __syncthreads();
+                           qchunks = LGPU_SEARCH_ARG(ka, adc_qchunks), S16 = LGPU_VIEW_ARG(ka, SearchArgs, chunks) * 16;
+            adc_stage<METRIC>(tid, T, s, lut, (uint4 *)rawq4, LGPU_FRAME_ARG(ka, SearchArgs, queries), q, LGPU_SEARCH_ARG(ka, adc_centers), S, C, subdim, qchunks, S16);
         }
         {
             const KernargBytes ka = kernarg_opaque();

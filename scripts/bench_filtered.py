@@ -33,6 +33,14 @@ measures the seeded walk (lantern_gpu_set_filter_seeds) and print
 cluster-correlated ones above, and the rows of one whole cluster (1/16), of half a cluster and of four clusters -- and per seeds value,
 the walk forced: q/s (the seeds values alternated within every repeat, every repeat listed), mean D, and recall@10 against the exact
 path on the first --nq-exact queries.
+
+    python scripts/bench_filtered.py --compact [--pq-subvectors 96] [--pq-centroids 256]
+
+measures filtered search on a COMPACT pq index (lantern_gpu_set_filter_compact; DESIGN.md 4.9 "Compact pq indexes") and prints ONE JSON
+line: the same pq index twice, expanded and compact; per filter (all rows, random 50 / 10 / 1 / 0.1 %) and per row routine -- "expanded"
+(the decodings in HBM), "decode" (rows decoded on the fly) and "adc" (LANTERN_GPU_PQ_ADC=1) -- q/s of the forced walk and of the forced
+exact path (the routines alternated within every repeat, every repeat listed), mean D of the walk, recall@10 of the walk against the
+same routine's exact path, and per routine the interpolated walk / exact crossover as exact_factor = allowed^2 / (ef * n).
 """
 import argparse
 import json
@@ -216,6 +224,82 @@ def seeds_legs(a, ix, cluster, filtered, timed_once, slot, D, k):
     return {"seeds_values": values, "reps": a.reps, "filters": legs}
 
 
+def compact_legs(a, base, queries, M, efc, ef, k):
+    """Filtered search on the expanded and on the compact form of one pq index (module docstring)."""
+    S, C = a.pq_subvectors, a.pq_centroids
+    sub = a.dim // S
+    crng = np.random.default_rng(5)
+    cb = np.zeros((C, a.dim), dtype=np.float32)
+    for sv in range(S):
+        cb[:, sv * sub:(sv + 1) * sub] = base[crng.choice(a.n, size=C, replace=False), sv * sub:(sv + 1) * sub]
+    index = {}
+    t0 = time.time()
+    for form in ("expanded", "compact"):
+        ix = capi.GpuIndex("l2sq", a.dim, M=M, ef_construction=efc, ef=ef, seed=42, pq_codebook=cb, num_subvectors=S)
+        ix.reserve(a.n)
+        ix.add_many(np.arange(a.n, dtype=np.uint64) + 1, base)
+        ix.flush()
+        index[form] = ix
+    assert index["expanded"].checksum() == index["compact"].checksum()
+    index["compact"].pq_compact()
+    index["compact"].set_filter_compact(1)
+    build_s = time.time() - t0
+    routines = {"expanded": (index["expanded"], "0"), "decode": (index["compact"], "0"), "adc": (index["compact"], "1")}
+    rows = index["expanded"].device_query_rows(queries)
+    stride, nq = rows.strides[0], a.nq
+    dq = hip.Buffer.from_numpy(rows)
+    lab, dist, slot = hip.Buffer(nq * k * 8), hip.Buffer(nq * k * 4), hip.Buffer(nq * k * 4)
+    cnt, D, E = hip.Buffer(nq * 4), hip.Buffer(nq * 8), hip.Buffer(nq * 8)
+
+    def run(name, f, path, n_q):
+        ix, env = routines[name]
+        os.environ["LANTERN_GPU_PQ_ADC"] = env
+        ix.set_filter_policy(path)
+        s, e = hip.Event(), hip.Event()
+        s.record()
+        ix.search_batch_filtered_device(f, dq.ptr, stride, n_q, k, ef, 0, lab.ptr, dist.ptr, slot.ptr, cnt.ptr, D.ptr, E.ptr)
+        e.record()
+        hip.synchronize()
+        return n_q / (s.elapsed_ms(e) / 1e3)
+
+    rng = np.random.default_rng(7)
+    legs = []
+    for sel in (1.0, 0.5, 0.1, 0.01, 0.001):
+        allowed = np.ones(a.n, dtype=bool) if sel == 1.0 else rng.random(a.n) < sel
+        filt = {"expanded": index["expanded"].filter_from_bitmap(allowed), "compact": index["compact"].filter_from_bitmap(allowed)}
+        leg = {"selectivity": sel, "allowed": int(allowed.sum()), "routines": {}}
+        for name in routines:
+            f = filt["expanded" if name == "expanded" else "compact"]
+            run(name, f, "exact", a.nq_exact)  # warm, and the truth of this routine
+            truth = [set(t for t in row.tolist() if t != capi.EMPTY) for row in slot.download((a.nq_exact, k), np.uint32)]
+            run(name, f, "walk", nq)
+            got = slot.download((nq, k), np.uint32)[: a.nq_exact]
+            rec = float(np.mean([len(set(got[i].tolist()) & truth[i]) / max(1, len(truth[i])) for i in range(a.nq_exact)]))
+            leg["routines"][name] = {"walk_qps": [], "exact_qps": [], "walk_mean_D": float(D.download(nq, np.uint64).mean()), "walk_recall_at_10": rec,
+                                     "launch": routines[name][0].last_filtered_launch()}
+        for _ in range(a.reps):  # alternated
+            for name in routines:
+                f = filt["expanded" if name == "expanded" else "compact"]
+                leg["routines"][name]["walk_qps"].append(run(name, f, "walk", nq))
+                leg["routines"][name]["exact_qps"].append(run(name, f, "exact", a.nq_exact))
+        legs.append(leg)
+        for f in filt.values():
+            f.close()
+    os.environ.pop("LANTERN_GPU_PQ_ADC", None)
+    # per routine the crossover: log(walk / exact q/s, best of the repeats) interpolated linearly in log(allowed) between the two legs around zero
+    cross = {}
+    for name in routines:
+        pts = sorted((np.log(l["allowed"]), np.log(max(l["routines"][name]["walk_qps"]) / max(l["routines"][name]["exact_qps"]))) for l in legs)
+        at = None
+        for (x0, y0), (x1, y1) in zip(pts, pts[1:]):
+            if y0 <= 0 < y1:
+                at = float(np.exp(x0 + (x1 - x0) * (-y0) / (y1 - y0)))
+        cross[name] = {"allowed": at, "exact_factor": at ** 2 / (ef * a.n) if at else None}
+    return {"workload": f"clustered {a.n}x{a.dim} pq {S} subvectors x {C} centroids, l2sq M={M} efc={efc} ef={ef} k={k}", "queries": nq,
+            "queries_exact": a.nq_exact, "build_seconds_both": build_s, "reps": a.reps, "memory_rows_bytes": {n_: index[n_].memory_usage()[0] for n_ in index},
+            "filters": legs, "crossover": cross}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=1_000_000)
@@ -227,12 +311,20 @@ def main():
     p.add_argument("--each-params", action="store_true", help="the legs of the per-query-filter call with per-query (k, ef)")
     p.add_argument("--nq-each", type=int, default=256)
     p.add_argument("--seeds", default="", help="comma-separated seeds values: the legs of the seeded walk")
+    p.add_argument("--compact", action="store_true", help="the legs of filtered search on a compact pq index against its expanded form")
+    p.add_argument("--pq-subvectors", type=int, default=96)
+    p.add_argument("--pq-centroids", type=int, default=256)
     a = p.parse_args()
     M, efc, ef, k = 16, 128, 64, 10
     t0 = time.time()
     base = synth.base_rows("clustered", a.n, a.dim)
     cluster = cluster_ids(a.n, a.dim)
     queries = synth.query_maker("clustered", a.dim)(np.random.default_rng(12345), a.nq)
+    if a.compact:
+        out = {"command": "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])}
+        out.update(compact_legs(a, base, queries, M, efc, ef, k))
+        print(json.dumps(out))
+        return
     ix = capi.GpuIndex("l2sq", a.dim, M=M, ef_construction=efc, ef=ef, seed=42)
     ix.reserve(a.n)
     ix.add_many(np.arange(a.n, dtype=np.uint64) + 1, base)
