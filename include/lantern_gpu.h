@@ -314,6 +314,13 @@ LANTERN_GPU_EXPORT void lantern_gpu_search_batch_params_device(usearch_index_t, 
  * (0 .. 3), [1] [2] [3] queries in the classes expansion <= 64, <= 128, beyond, [4] the largest expansion, [5] 1 if any launch took a
  * latency-bound (spec) shape.  All zero before the first such call. */
 LANTERN_GPU_EXPORT void lantern_gpu_last_params_launch(usearch_index_t, uint32_t out[6], usearch_error_t *);
+/* Diagnostics (tests): the kernel instantiations of the unfiltered search launches THIS THREAD made since the last call, oldest first,
+ * at most cap rows of 10 words (and at most the last four launches: a per-query-parameter call makes at most three):
+ * [0] kernel (1 k_search, 2 k_search_adc)  [1] METRIC  [2] G  [3] PROF  [4] ROWS  [5] KPL  [6] SPEC  [7] EACH -- the template arguments
+ * as the launch macro passed them (k_search_adc: G = 8, PROF = ROWS = 0, which are no parameters of it)  [8] the launch screens (its
+ * view carries the int8 screen)  [9] queries of the launch.
+ * Returns the number of launches since the last call (it may exceed cap, and four) and resets it.  No device is needed. */
+LANTERN_GPU_EXPORT size_t lantern_gpu_last_search_cells(uint32_t *cells, size_t cap);
 /* ------------------------------------------------------------------------------------------ */
 /* Filtered search: k-NN limited to an allow-set of rows.                       */
 /* PARITY UNPINNED BY THE REFERENCE: the reference's usearch fork is not in the tree; what follows */

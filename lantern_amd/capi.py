@@ -123,6 +123,8 @@ EXPORTS = [
     # per-query k, ef and skip (lantern_gpu.h "PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_params", "lantern_gpu_search_batch_params_lane", "lantern_gpu_search_batch_params_lane_notify",
     "lantern_gpu_search_batch_params_device", "lantern_gpu_last_params_launch", "lantern_scan_server_start_params_fn",
+    # which kernel instantiation an unfiltered search launch took (diagnostics)
+    "lantern_gpu_last_search_cells",
     # diagnostics of the int8 screen (lantern_gpu.h lantern_gpu_export_screen)
     "lantern_gpu_export_screen", "lantern_gpu_screen_probe",
 ]
@@ -349,6 +351,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_search_batch_params_lane_notify": (None, [vp, i32, vp, sz, i32, vp, sz, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_search_batch_params_device": (None, [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp, err]),
         "lantern_gpu_last_params_launch": (None, [vp, vp, err]),
+        "lantern_gpu_last_search_cells": (sz, [vp, sz]),
         "lantern_gpu_filter_resident_bytes": (sz, [vp, err]),
         "lantern_scan_server_start_params_fn": (vp, [BATCH_SEARCH_FN, BATCH_SEARCH_PARAMS_FN, vp, sz, C.c_char_p, i32, sz, C.c_uint, err]),
         "lantern_scan_server_start_filtered_fn": (vp, [BATCH_SEARCH_FN, FILTER_MAKE_FN, FILTER_FREE_FN, BATCH_SEARCH_EACH_FN, vp, sz, C.c_char_p, i32, sz,
@@ -1229,6 +1232,18 @@ def level_for(seed: int, slot: int, M: int) -> int:
 def plan_batch(size: int, max_level: int, pending_levels, max_batch: int, min_ratio: int) -> int:
     lv = np.ascontiguousarray(pending_levels, dtype=np.int32)
     return int(lib().lantern_gpu_plan_batch(size, max_level, _ptr(lv), lv.size, max_batch, min_ratio))
+
+
+# a row of lantern_gpu_last_search_cells, in order (include/lantern_gpu.h)
+SEARCH_CELL = ("kernel", "metric", "G", "prof", "rows", "kpl", "spec", "each", "screens", "queries")
+
+
+def last_search_cells(cap: int = 4) -> tuple[int, list[tuple[int, ...]]]:
+    """The kernel instantiations of the unfiltered search launches this thread made since the last call
+    (lantern_gpu_last_search_cells): (launches made, [SEARCH_CELL rows of the last min(launches, cap, 4), oldest first])."""
+    out = np.zeros((max(cap, 1), len(SEARCH_CELL)), dtype=np.uint32)
+    made = int(lib().lantern_gpu_last_search_cells(_ptr(out), cap))
+    return made, [tuple(int(x) for x in row) for row in out[:min(made, cap, 4)]]
 
 
 # lantern_gpu_plan_search's arrays, in order (include/lantern_gpu.h)

@@ -213,6 +213,11 @@ inline void ensure_dynamic_lds(const void *fn, size_t lds, LdsAttrCache &cache)
         hipLaunchKernelGGL(KERNEL, dim3(grid_), dim3(block_), lds_, stream_, __VA_ARGS__);          \
     }
 
+// Diagnostics (lantern_gpu_last_search_cells; search_plan.cpp): the launch macros of k_search (1) and k_search_adc (2) note the template
+// arguments of the instantiation they launch in a thread-local ring, with whether the launch screens and its query count.  Host only:
+// a few thread-local stores per launch.
+void note_search_cell(int kernel, int metric, int G, int prof, int rows, int kpl, int spec, int each, const SearchArgs &a);
+
 // All launchers return hipSuccess or the launch error.  `metric` is a usearch_metric_kind_t value.
 hipError_t launch_search(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);
 hipError_t launch_search_spec(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);  // a.spec != 0 (search_spec_kernel.hip)

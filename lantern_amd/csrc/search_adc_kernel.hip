@@ -90,6 +90,13 @@ __global__ void __launch_bounds__(SPEC ? 704 : 512, SPEC ? 1 : 2) k_search_adc(S
     }
 }
 
+// the record of an instantiation (lantern_gpu_last_search_cells): k_search_adc's own parameter list with its defaults; rows are walked by
+// 8-lane groups, PROF and ROWS are no parameters of this kernel
+template <int METRIC, int KPL, int SPEC = 0, bool EACH = false> static inline void note_search_adc(const SearchArgs &a)
+{
+    note_search_cell(2, METRIC, 8, 0, 0, KPL, SPEC, EACH, a);
+}
+
 size_t search_adc_lds_bytes(uint32_t code_chunks, uint32_t qchunks, uint32_t ef_cap, uint32_t M0, uint32_t vis_slots)
 {
     return walk_lds_bytes(code_chunks * 16 * ADC_LUT_STRIDE / 4 + qchunks, ef_cap, M0, vis_slots);
@@ -101,7 +108,11 @@ hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int gri
     const int kpl = a.lds_list ? 0 : a.ef <= 64 ? 1 : a.ef <= 128 ? 2 : 0;
     if(a.spec && (kpl == 0 || waves < 4 || waves > 11 || a.view.M0 > 64 || a.view.M0 < 2)) return hipErrorInvalidValue;
     const size_t lds = search_adc_lds_bytes(a.view.chunks, a.adc_qchunks, a.ef, a.view.M0, a.frame.vis_slots) + (a.spec ? spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache) : 0);
-#define LGPU_ADC2(MM, KK, SS, EE) LGPU_LAUNCH_LDS((k_search_adc<MM, KK, SS, EE>), grid, 64 * waves, lds, stream, a)
+#define LGPU_ADC2(...)                                                                             \
+    {                                                                                              \
+        note_search_adc<__VA_ARGS__>(a);                                                           \
+        LGPU_LAUNCH_LDS((k_search_adc<__VA_ARGS__>), grid, 64 * waves, lds, stream, a)             \
+    }
 #define LGPU_ADC1(MM, KK, SS)                                    \
     {                                                            \
         if(a.qparams) LGPU_ADC2(MM, KK, SS, true)                \

@@ -8,8 +8,18 @@
 
 namespace lgpu {
 
-// one instantiation: opt the kernel in to its dynamic LDS size, then launch
-#define LGPU_LAUNCH_SEARCH(...) LGPU_LAUNCH_LDS((k_search<__VA_ARGS__>), grid, 64 * waves, lds, stream, a)
+// the record of an instantiation (lantern_gpu_last_search_cells): k_search's own parameter list with its defaults, so that the launch
+// macro hands the recorder and the kernel the same arguments
+template <int METRIC, int G, bool PROF = false, int ROWS = 2, int KPL = 1, int SPEC = 0, bool EACH = false> static inline void note_search(const SearchArgs &a)
+{
+    note_search_cell(1, METRIC, G, PROF, ROWS, KPL, SPEC, EACH, a);
+}
+// one instantiation: note it, opt the kernel in to its dynamic LDS size, then launch
+#define LGPU_LAUNCH_SEARCH(...)                                                                \
+    {                                                                                          \
+        note_search<__VA_ARGS__>(a);                                                           \
+        LGPU_LAUNCH_LDS((k_search<__VA_ARGS__>), grid, 64 * waves, lds, stream, a)             \
+    }
 // ... for the list placement of this launch (walk.hpp search_level_reg): one key per lane of wave 0 up to ef = 64, two up to
 // 128, the LDS list beyond (or when LANTERN_GPU_LDS_LIST asks for it)
 #define LGPU_LAUNCH_SEARCH_KPL(MM, GG, PP, RR)                           \

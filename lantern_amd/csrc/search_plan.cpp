@@ -356,7 +356,32 @@ bool search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, const la
     return true;
 }
 
+// ---- which instantiation a launch took (lantern_gpu_last_search_cells) -------------------------------------------------------------
+// A ring of the calling thread's last four unfiltered search launches (a per-query-parameter call makes at most three) and their count
+// since the ring was last read.
+static const size_t             kCellRing = 4, kCellWords = 10;
+static thread_local uint32_t    cell_ring[ kCellRing ][ kCellWords ];
+static thread_local size_t      cell_count = 0;
+
+void note_search_cell(int kernel, int metric, int G, int prof, int rows, int kpl, int spec, int each, const SearchArgs &a)
+{
+    const uint32_t row[ kCellWords ] = { (uint32_t)kernel, (uint32_t)metric, (uint32_t)G, (uint32_t)prof, (uint32_t)rows, (uint32_t)kpl, (uint32_t)spec,
+                                         (uint32_t)each, a.view.screen ? 1u : 0u, a.frame.nq };
+    std::copy(std::begin(row), std::end(row), cell_ring[ cell_count++ % kCellRing ]);
+}
+
+static size_t take_search_cells(uint32_t *cells, size_t cap)
+{
+    const size_t made = cell_count, kept = std::min(made, kCellRing);
+    for(size_t i = 0; cells && i < std::min(kept, cap); ++i)  // oldest first
+        std::copy(cell_ring[ (made - kept + i) % kCellRing ], cell_ring[ (made - kept + i) % kCellRing ] + kCellWords, cells + i * kCellWords);
+    cell_count = 0;
+    return made;
+}
+
 }  // namespace lgpu
+
+extern "C" size_t lantern_gpu_last_search_cells(uint32_t *cells, size_t cap) { return lgpu::take_search_cells(cells, cap); }
 
 // the plan without a device (include/lantern_gpu.h has the field order)
 static const char *plan_search_flat(const int64_t *in, bool screen, uint32_t *out, uint32_t *screen_lds, int screen_list_prefetch = -1, uint32_t *list_prefetch = nullptr)
