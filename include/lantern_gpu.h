@@ -581,10 +581,10 @@ LANTERN_GPU_EXPORT int lantern_gpu_last_search_grid(usearch_index_t, usearch_err
  *   [19] 1: one class of a per-query-parameter call, shaped by [20] its largest expansion
  *   [21] LANTERN_GPU_SPEC is set, [22] its value  [23] LANTERN_GPU_ADC_SPEC is set, [24] != 0  [25] LANTERN_GPU_PQ_ADC != 0
  *   [26] LANTERN_GPU_SPEC_WAVES (0: unset)  [27] LANTERN_GPU_LDS_LIST != 0  [28] LANTERN_GPU_WIDE_ROWS (-1: unset)
- *   [29] LANTERN_GPU_SOLO != 0  [30] LANTERN_GPU_WAVES_PER_CU (0: unset)
- * out[12]: [0] path (0 ADC over the code rows, 1 the f32 walk over rows decoded on the fly, 2 classic, 3 spec 1, 4 spec 2, 5 two
- *   nodes per round, 6 the one-wave walk; 5 and 6 in a LANTERN_BUILD_EXPERIMENTAL library only)  [1] spec (the walk's shape; paths 0
- *   and 1 take 0 / 2 and any)  [2] expansion  [3] waves per workgroup  [4] grid  [5] vis_slots  [6] LDS bytes per workgroup
+ *   [29] reserved and ignored (the switch of a walk since removed; the slots after it keep their places)
+ *   [30] LANTERN_GPU_WAVES_PER_CU (0: unset)
+ * out[12]: [0] path (0 ADC over the code rows, 1 the f32 walk over rows decoded on the fly, 2 classic, 3 spec 1, 4 spec 2)
+ *   [1] spec (the walk's shape; paths 0 and 1 take 0 / 2 and any)  [2] expansion  [3] waves per workgroup  [4] grid  [5] vis_slots  [6] LDS bytes per workgroup
  *   [7] spec_prefetch  [8] spec_cache  [9] wide_rows  [10] a latency-bound shape  [11] lds_list
  * Returns NULL, or the text the launch is refused with (then only out[2] is meaningful). */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_search(const int64_t in[31], uint32_t out[12]);
@@ -708,9 +708,6 @@ typedef struct lantern_gpu_counters
      * (k_revlink_pairs), where sequential usearch stops at the first blocker -- they are >= the CPU path's counts and are the
      * right numerators for the device's rooflines, not for a CPU comparison. */
     uint64_t add_walk_evals, add_select_evals, add_revlink_evals, add_reprunes;
-    /* search launches that took the one-wave walk (csrc/walk_solo.hpp): what a lone usearch_search_ef call (scan.c:220-228) runs
-     * on an index it applies to -- tests assert the kernel that was meant is the kernel that ran */
-    uint64_t search_solo_launches;
 } lantern_gpu_counters;
 LANTERN_GPU_EXPORT lantern_gpu_counters lantern_gpu_counters_get(usearch_index_t, usearch_error_t *);
 

@@ -20,24 +20,11 @@ LIB = os.path.join(OUT_DIR, "liblantern_gpu.so")
 
 SOURCES = ["search_kernel.hip", "search_spec_kernel.hip", "search_adc_kernel.hip", "search_filtered_kernel.hip", "search_filtered_pq_kernel.hip", "search_each_kernel.hip", "search_each_spec_kernel.hip", "filter.hip", "insert_kernel.hip", "insert_spec_kernel.hip", "kernels.hip", "screen_probe_kernel.hip", "bruteforce.hip", "grouping.hip", "index.cpp", "insert_batch.cpp", "search_plan.cpp", "comm.cpp", "usearch_file.cpp", "scan_shim.cpp", "index_server.cpp", "scan_server.cpp", "mirror_cache.cpp", "node_tape.cpp"]
 # every header under csrc/ is a dependency of every object (globbed, so a new header cannot be forgotten)
-HEADERS = (sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + sorted("experimental/" + h for h in os.listdir(os.path.join(CSRC, "experimental")) if h.endswith(".hpp"))
-           + ["../../include/lantern_gpu.h"])
+HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + ["../../include/lantern_gpu.h"]
 # -ffp-contract=off: every fma in the kernels is explicit, so the reduction tree is exactly the
 # one the oracle models.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-x", "hip"]
-
-
-# LANTERN_BUILD_EXPERIMENTAL=1: also build the walk variants that lost their A/B (csrc/experimental/: the two-nodes-per-round walk
-# and the one-wave walk, LANTERN_GPU_SPEC=3 / 4).  The default library -- what bench.py, the driver's tests and a deployment run --
-# does not contain them.  Objects of the two builds live in separate directories; the library on disk is whichever was built last,
-# and lantern_gpu_version() says which ("... +experimental").
-EXPERIMENTAL = os.environ.get("LANTERN_BUILD_EXPERIMENTAL", "0") not in ("", "0")
-EXPERIMENTAL_SOURCES = ["experimental/search_solo_kernel.hip"]
-if EXPERIMENTAL:
-    SOURCES = SOURCES + EXPERIMENTAL_SOURCES
-    FLAGS = FLAGS + ["-DLGPU_EXPERIMENTAL=1"]
-    OBJ_DIR = os.path.join(OUT_DIR, "obj_experimental")
 
 
 def _hipcc() -> str:
@@ -72,16 +59,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         objs = list(ex.map(compile_one, srcs))
-    marker = os.path.join(OUT_DIR, ".built_experimental")  # which of the two builds the library on disk is
-    if force or _stale(LIB, objs) or os.path.exists(marker) != EXPERIMENTAL:
+    if force or _stale(LIB, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-lpthread", "-ldl"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-        if EXPERIMENTAL:
-            open(marker, "w").close()
-        elif os.path.exists(marker):
-            os.remove(marker)
     # the cache model of bench.py's roofline.frac_dram_model (tools/cache_model.c: plain C, host only)
     cm_src, cm_lib = os.path.join(HERE, "tools", "cache_model.c"), os.path.join(OUT_DIR, "libcache_model.so")
     if os.path.exists(cm_src) and (force or _stale(cm_lib, [cm_src])):

@@ -70,7 +70,7 @@ class GraphInfo(C.Structure):
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("search_dist_evals", "search_expansions", "search_queries", "add_dist_evals",
                                           "add_expansions", "add_vectors", "add_batches", "add_walk_evals", "add_select_evals",
-                                          "add_revlink_evals", "add_reprunes", "search_solo_launches")]
+                                          "add_revlink_evals", "add_reprunes")]
 
 
 class BuildProfile(C.Structure):
@@ -436,11 +436,6 @@ def assign_to_clusters(dataset, centers, metric, subvector_start=0, subvector_di
 
 def version() -> str:
     return lib().lantern_gpu_version().decode()
-
-
-def experimental_build() -> bool:
-    """True when the loaded library contains the walk variants of csrc/experimental/ (LANTERN_BUILD_EXPERIMENTAL=1 at build time)."""
-    return "+experimental" in version()
 
 
 def dense_profile(on: bool):
@@ -1249,7 +1244,7 @@ def last_search_cells(cap: int = 4) -> tuple[int, list[tuple[int, ...]]]:
 # lantern_gpu_plan_search's arrays, in order (include/lantern_gpu.h)
 PLAN_SEARCH_IN = ("chunks", "M", "M0", "mcode", "n", "ef_default", "num_cus", "pq_compact", "pqd_inv", "pq_S16", "search_vis_slots", "search_max_wg",
                   "phase_profile", "spec_profile", "nq", "k", "ef", "skip", "waves", "each", "max_expansion", "env_spec_set", "env_spec",
-                  "env_adc_spec_set", "env_adc_spec", "env_pq_adc", "env_spec_waves", "env_lds_list", "env_wide_rows", "env_solo", "env_waves_per_cu")
+                  "env_adc_spec_set", "env_adc_spec", "env_pq_adc", "env_spec_waves", "env_lds_list", "env_wide_rows", "reserved_29", "env_waves_per_cu")
 PLAN_SEARCH_OUT = ("path", "spec", "expansion", "waves", "grid", "vis_slots", "lds", "spec_prefetch", "spec_cache", "wide_rows", "took_spec", "lds_list")
 
 

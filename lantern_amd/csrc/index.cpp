@@ -1069,7 +1069,7 @@ Index *lgpu::H(usearch_index_t h, usearch_error_t *e)
 
 extern "C" {
 
-const char *lantern_gpu_version(void) { return LGPU_EXPERIMENTAL ? "lantern_gpu 0.1 (gfx950) +experimental" : "lantern_gpu 0.1 (gfx950)"; }
+const char *lantern_gpu_version(void) { return "lantern_gpu 0.1 (gfx950)"; }
 
 int lantern_gpu_device_count(void)
 try {
@@ -2380,7 +2380,6 @@ try {
     c.add_select_evals = t[ kTotConnect ];
     c.add_revlink_evals = t[ kTotRevlink ];
     c.add_reprunes = t[ kTotRevlink + 1 ];
-    c.search_solo_launches = ix->c_solo_launches;
     return c;
 }
 LANTERN_ABI_CATCH(e)

@@ -219,7 +219,7 @@ struct Index
     bool        insert_pending = false;
 
     // ---- counters ----------------------------------------------------------------------------------
-    uint64_t c_search_queries = 0, c_add_vectors = 0, c_add_batches = 0, c_solo_launches = 0;
+    uint64_t c_search_queries = 0, c_add_vectors = 0, c_add_batches = 0;
 
     // ---- filtered search (filter.hip): the path policy (lantern_gpu_set_filter_policy) and which path each launch took
     int      filter_path = 0;           // 0 auto, 1 walk, 2 exact
@@ -314,12 +314,12 @@ int         search_grid(const Index *ix, size_t nq, int waves, int waves_per_cu)
 int         search_grid(int num_cus, int max_wg, int forced_waves_per_cu, size_t nq, int waves, int waves_per_cu);  // the same, pure
 // ---- the unfiltered search launch: a pure plan (plan_search), then one launch of it (search_plan.cpp) ---------------------------------
 // the environment switches of the launch shape, as values (search_env reads them: LANTERN_GPU_SPEC, _ADC_SPEC, _PQ_ADC, _SPEC_WAVES and
-// _LDS_LIST on every call -- in-process tests set them between calls --, _WIDE_ROWS, _SOLO and _WAVES_PER_CU once per process)
+// _LDS_LIST on every call -- in-process tests set them between calls --, _WIDE_ROWS and _WAVES_PER_CU once per process)
 struct SearchEnv
 {
     bool spec_set = false, adc_spec_set = false;                          // LANTERN_GPU_SPEC / _ADC_SPEC are present
     int  spec = 0, spec_waves = 0, wide_rows = -1, waves_per_cu = 0;      // their values; 0, -1, 0: absent
-    bool adc_spec = false, pq_adc = false, lds_list = false, solo = false;  // != 0
+    bool adc_spec = false, pq_adc = false, lds_list = false;  // != 0
     int  screen_list_prefetch = -1;                                       // LANTERN_GPU_SCREEN_LIST_PREFETCH (read on every call): 0 / 1, -1: absent
 };
 SearchEnv search_env();
@@ -339,13 +339,13 @@ struct SearchPlanIn
     SearchEnv env;
 };
 // path: the rows and the launcher -- ADC over the code rows of a compact pq index (spec 0 or 2), the f32 walk over rows decoded on the fly
-// (any spec), or the plain walk by its shape: classic (spec 0), spec 1, spec 2, and in LGPU_EXPERIMENTAL builds twin (3) and solo (4)
-enum SearchPath : uint32_t { kSearchAdc, kSearchPqd, kSearchClassic, kSearchSpec1, kSearchSpec2, kSearchTwin, kSearchSolo };
+// (any spec), or the plain walk by its shape: classic (spec 0), spec 1, spec 2
+enum SearchPath : uint32_t { kSearchAdc, kSearchPqd, kSearchClassic, kSearchSpec1, kSearchSpec2 };
 struct SearchPlan
 {
     SearchPath  path = kSearchClassic;
     int         spec = 0, waves = 0, grid = 0, wide_rows = 0, lds_list = 0;  // spec, wide_rows, lds_list: SearchArgs'
-    uint32_t    expansion = 0, vis_slots = 0, spec_prefetch = 0, spec_cache = 0;  // (solo: words of the LDS bitmap, -, log2 of the list cache)
+    uint32_t    expansion = 0, vis_slots = 0, spec_prefetch = 0, spec_cache = 0;
     size_t      lds = 0;             // dynamic LDS of a workgroup
     uint32_t    screen_lds = 0;      // ... of which the query's int8 planes (screen_query_lds_bytes): != 0 iff the launch screens
     uint32_t    list_prefetch = 0;   // SearchArgs::list_prefetch: only ever set in a launch that screens

@@ -7,14 +7,6 @@
 #include "device_common.hpp"
 #include <atomic>
 
-// LANTERN_BUILD_EXPERIMENTAL=1 (lantern_amd/build.py -> -DLGPU_EXPERIMENTAL=1) adds the walk variants that lost their A/B to the
-// library: two nodes per round (experimental/walk_twin.hpp, LANTERN_GPU_SPEC=3) and the one-wave walk (experimental/walk_solo.hpp +
-// experimental/search_solo_kernel.hip, LANTERN_GPU_SPEC=4 / LANTERN_GPU_SOLO=1).  The default library does not contain them: the
-// switches then select the default latency-bound walk.  lantern_gpu_version() names the build.
-#ifndef LGPU_EXPERIMENTAL
-#define LGPU_EXPERIMENTAL 0
-#endif
-
 namespace lgpu {
 
 // What a persistent search workgroup does AROUND one query reads these fields (query_frame.hpp: pick, stage, bind, answer rows,
@@ -49,8 +41,8 @@ struct SearchArgs
     int             lds_list;    // keep the candidate list in LDS even when it fits wave 0's registers (LANTERN_GPU_LDS_LIST=1: the
                                  // round-1 walk, kept for A/B parity runs and for ef > 128)
     int             wide_rows;   // small batch: the four-rows-in-flight instantiation (k_search<.., ROWS = 4>)
-    int             spec;        // latency-bound launches (walk_spec.hpp): 1 = four-wave shape, 2 = dedicated role waves (3 + 8 waves), 3 = the same with two
-                                 // nodes per round, the second speculative (walk_twin.hpp); 0 = off
+    int             spec;        // latency-bound launches (walk_spec.hpp): 1 = four-wave shape, 2 = dedicated role waves (3 + 8 waves);
+                                 // 0 = off
     uint32_t        spec_prefetch;  // fetch every evaluated row's own level-0 list with the row (M0 % 4 == 0, M0 / 4 <= lanes per row)
     uint32_t        spec_cache;     // entries of the LDS list cache (power of two; 0 = none)
     // ADC over PQ codes (search_adc_kernel.hip; view.vec = the code rows, view.chunks = 16-byte chunks per code row)
@@ -224,14 +216,7 @@ hipError_t launch_search_spec(int metric, const SearchArgs &a, int waves, int gr
 // a.qparams != NULL: the per-query-parameter instantiations (search_each_kernel.hip: the classic shapes; search_each_spec_kernel.hip: a.spec == 2)
 hipError_t launch_search_each(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);
 hipError_t launch_search_each_spec(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);
-size_t     search_spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries, uint32_t twin = 0);
-#if LGPU_EXPERIMENTAL
-// the one-wave walk (experimental/search_solo_kernel.hip, experimental/walk_solo.hpp): a.spec_cache = log2 of the list-cache entries,
-// a.vis_slots = words of the LDS bitmap
-bool       search_solo_supported(int metric, uint32_t chunks, uint32_t M, uint32_t M0, uint32_t ef);
-size_t     search_solo_lds_bytes(uint32_t ne_log2, uint32_t bm_words);
-hipError_t launch_search_solo(int metric, const SearchArgs &a, int grid, hipStream_t stream);
-#endif
+size_t     search_spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries);
 hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);  // metric = M_L2SQ_ADC / M_COS_ADC
 size_t     search_adc_lds_bytes(uint32_t code_chunks, uint32_t qchunks, uint32_t ef_cap, uint32_t M0, uint32_t vis_slots);
 hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, hipStream_t stream);

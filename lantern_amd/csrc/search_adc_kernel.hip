@@ -21,7 +21,7 @@ namespace lgpu {
 // SPEC: the latency-bound walk of walk_spec.hpp in its lone-query shape (three role waves + eight row waves, one barrier per hop,
 // neighbour lists fetched with the rows).  A table of 96 x 256 entries leaves room for ONE workgroup per CU, so every query of
 // a batch walks alone on its CU whatever the batch size: the walk that is fastest alone is the one to run.
-// (SPEC 2 = the lone-query shape.  The two-nodes-per-round form of walk_twin.hpp was measured here too -- 1.98 -> 1.65 M queries/s at
+// (SPEC 2 = the lone-query shape.  A two-nodes-per-round form of the walk was measured here too -- 1.98 -> 1.65 M queries/s at
 // 96 subvectors -- and is not instantiated.)
 // EACH: the per-query-parameter form, as k_search's (search_kernel.hpp): the launch's queries come from FrameArgs::qlist, every
 // query's k, expansion and skip from its row of SearchArgs::qparams, answer rows are k_stride wide.

@@ -1,7 +1,7 @@
 // search_each_spec_kernel.hip -- k_search in its per-query-parameter form (search_kernel.hpp, EACH) for the latency-bound shape a
 // per-query call can take: three role waves + eight row waves (spec 2), which is what service-sized batches run (search_launch.hpp,
-// the same launcher body).  The four-wave shape (spec 1, on request only) and the experimental walks have no per-query form:
-// index.cpp falls back to the classic shape.
+// the same launcher body).  The four-wave shape (spec 1, on request only) has no per-query form:
+// search_plan.cpp falls back to the classic shape.
 #include "search_launch.hpp"
 
 namespace lgpu {

@@ -10,15 +10,6 @@
 #include "kernels.hpp"
 #include "walk.hpp"
 #include "walk_spec.hpp"
-// LGPU_EXPERIMENTAL (build.py, LANTERN_BUILD_EXPERIMENTAL=1): the walk variants that lost their A/B -- two nodes per round
-// (experimental/walk_twin.hpp, SPEC 3) and the one-wave walk (experimental/walk_solo.hpp) -- are kept with their records and
-// parity tests but are NOT in the default library.
-#ifndef LGPU_EXPERIMENTAL
-#define LGPU_EXPERIMENTAL 0
-#endif
-#if LGPU_EXPERIMENTAL
-#include "experimental/walk_twin.hpp"
-#endif
 #include "dispatch.hpp"
 #include "query_frame.hpp"
 
@@ -65,8 +56,7 @@ __device__ __forceinline__ QueryParams query_params(KernargBytes ka, uint32_t q)
 }
 
 // SPEC: the latency-bound walk of walk_spec.hpp -- 1: every wave evaluates rows and waves 0..2 carry the roles on top (the
-// small-batch shape, four waves); 2: three dedicated role waves + row waves (the lone-query shape, 3 + 8 waves); 3: the same
-// shape with two nodes per round, the second one speculative (walk_twin.hpp).
+// small-batch shape, four waves); 2: three dedicated role waves + row waves (the lone-query shape, 3 + 8 waves).
 // EACH: the per-query-parameter form (search_each_kernel.hip, search_each_spec_kernel.hip).  The launch serves the queries of a list
 // (FrameArgs::qlist: the ticket hands out list positions, the answers land in the row of the query a position names) and every query
 // brings its own k, expansion and skip in a 16-byte row {k, expansion, skip, 0} of SearchArgs::qparams, read through the scalar cache
@@ -87,7 +77,7 @@ k_search(SearchArgs)
         const KernargBytes ka = kernarg_opaque();
         unsigned char     *end = carve_walk(lgpu_smem, s, LGPU_VIEW_ARG(ka, SearchArgs, chunks), LGPU_SEARCH_ARG(ka, ef), LGPU_VIEW_ARG(ka, SearchArgs, M0),
                                             LGPU_FRAME_ARG(ka, SearchArgs, vis_slots));
-        if constexpr(SPEC != 0) carve_spec(end, sc, LGPU_VIEW_ARG(ka, SearchArgs, M0), LGPU_SEARCH_ARG(ka, spec_prefetch), LGPU_SEARCH_ARG(ka, spec_cache), SPEC == 3 ? 1u : 0u);
+        if constexpr(SPEC != 0) carve_spec(end, sc, LGPU_VIEW_ARG(ka, SearchArgs, M0), LGPU_SEARCH_ARG(ka, spec_prefetch), LGPU_SEARCH_ARG(ka, spec_cache));
         else (void)end;
     }
     // the int8 screen of the f32 l2sq and cosine walks over rows of >= 128 chunks (walk.hpp hop_distances_screened); used iff the view
@@ -138,12 +128,6 @@ k_search(SearchArgs)
                 else start = greedy_descent<METRIC, G, PROF>(v, s, v.entry, v.max_level, 0, D);
                 if constexpr(PROF) pc[ 6 ] = (unsigned long long)clock64() - t_q;
                 // KPL keys per lane of wave 0 hold the candidate list (ef <= 64 KPL); KPL = 0: the list lives in LDS
-#if LGPU_EXPERIMENTAL
-                if constexpr(SPEC == 3)
-                    cnt = search_level_twin<METRIC, G, KPL, ROWS, (G == 64 ? 3 : 2), PROF>(v, s, sc, bitmap, bm_words, start, ef, D, E,
-                                                                                           PROF ? LGPU_SEARCH_ARG(ka, phase_cycles) : nullptr);
-                else
-#endif
                 if constexpr(SPEC != 0)
                     cnt = search_level_spec<METRIC, G, KPL, ROWS, (G == 64 && SPEC == 2 ? 3 : 2), SPEC == 2, PROF>(v, s, sc, bitmap, bm_words, start, ef, D, E,
                                                                                                                      PROF ? LGPU_SEARCH_ARG(ka, phase_cycles) : nullptr);

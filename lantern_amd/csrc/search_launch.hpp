@@ -1,8 +1,7 @@
 // search_launch.hpp -- the two launcher bodies of k_search (search_kernel.hpp), each a template on EACH (the per-query-parameter
 // form): the bandwidth-bound shapes and the latency-bound ones.  A body is instantiated where it is called: search_kernel.hip and
 // search_spec_kernel.hip take EACH = false, search_each_kernel.hip and search_each_spec_kernel.hip EACH = true, so the kernels stay
-// spread over four translation units that compile side by side.  The instrumented (PROF) and experimental instantiations exist for
-// EACH = false only.
+// spread over four translation units that compile side by side.  The instrumented (PROF) instantiations exist for EACH = false only.
 #pragma once
 #include "search_kernel.hpp"
 
@@ -86,16 +85,12 @@ template <bool EACH> static hipError_t launch_search_latency(int metric, const S
 {
     if(EACH && (a.phase_cycles || a.spec != 2)) return hipErrorInvalidValue;
     if(a.ef > 128 || a.view.M0 > 64 || a.view.M0 < 2 || waves < 2 || (a.spec >= 2 && waves < 4)) return hipErrorInvalidValue;
-    const size_t lds = search_lds_bytes(a.view.chunks, a.ef, a.view.M0, a.frame.vis_slots) + spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache, a.spec == 3);
+    const size_t lds = search_lds_bytes(a.view.chunks, a.ef, a.view.M0, a.frame.vis_slots) + spec_lds_bytes(a.view.M0, a.spec_prefetch, a.spec_cache);
     const int    kpl = a.ef <= 64 ? 1 : 2;
     if constexpr(!EACH) {
         if(a.phase_cycles) {  // diagnostic instantiations (lantern_gpu_spec_profile): f32 l2sq / cos rows of 32..63 and of >= 128 chunks, ef <= 64
             const int G_ = group_lanes_for(a.view.chunks);
-#if LGPU_EXPERIMENTAL
-#define LGPU_PROF_SPEC(MM, GG, RR) { if(a.spec == 3) LGPU_LAUNCH_SEARCH(MM, GG, true, RR, 1, 3) else if(a.spec == 2) LGPU_LAUNCH_SEARCH(MM, GG, true, RR, 1, 2) else LGPU_LAUNCH_SEARCH(MM, GG, true, RR, 1, 1) }
-#else
 #define LGPU_PROF_SPEC(MM, GG, RR) { if(a.spec == 2) LGPU_LAUNCH_SEARCH(MM, GG, true, RR, 1, 2) else LGPU_LAUNCH_SEARCH(MM, GG, true, RR, 1, 1) }
-#endif
             if(kpl == 1 && metric == M_L2SQ && G_ == 16) LGPU_PROF_SPEC(M_L2SQ, 16, 1)
             else if(kpl == 1 && metric == M_L2SQ && G_ == 64) LGPU_PROF_SPEC(M_L2SQ, 64, 4)
             else if(kpl == 1 && metric == M_COS && G_ == 64) LGPU_PROF_SPEC(M_COS, 64, 4)
@@ -103,25 +98,8 @@ template <bool EACH> static hipError_t launch_search_latency(int metric, const S
             else return hipErrorInvalidValue;
             return hipGetLastError();
         }
-#if LGPU_EXPERIMENTAL
-        if(a.spec == 3) {
-            // Two nodes per round, the second one speculative (walk_twin.hpp).  Measured and NOT adopted: parity-green,
-            // 51 rounds instead of 69 hops for the lone 100k x 128 query, but a round costs 1.9 hops -- the walk is bound by the
-            // dependent instructions of its bookkeeping, not by the memory round trip the speculation hides.  Kept for the f32
-            // metrics at the two common row shapes behind LANTERN_GPU_SPEC=3, with its parity tests.
-            const int G_ = group_lanes_for(a.view.chunks);
-            if(kpl != 1) return hipErrorInvalidValue;
-            if(metric == M_L2SQ && G_ == 16) LGPU_LAUNCH_SEARCH(M_L2SQ, 16, false, 1, 1, 3)
-            else if(metric == M_L2SQ && G_ == 64) LGPU_LAUNCH_SEARCH(M_L2SQ, 64, false, 4, 1, 3)
-            else if(metric == M_COS && G_ == 64) LGPU_LAUNCH_SEARCH(M_COS, 64, false, 4, 1, 3)
-            else return hipErrorInvalidValue;
-            return hipGetLastError();
-        }
-#endif
     }
-#if !LGPU_EXPERIMENTAL
-    if(a.spec >= 3) return hipErrorInvalidValue;  // (index.cpp never asks: without the experimental unit LANTERN_GPU_SPEC=3 / 4 mean 2)
-#endif
+    if(a.spec >= 3) return hipErrorInvalidValue;  // (search_plan.cpp never asks: LANTERN_GPU_SPEC=3 / 4 mean 2)
     if(mcode_is_pqd(metric)) PQD_G(metric, a.view.chunks, LGPU_LAUNCH_SPEC);
     else LGPU_DISPATCH(metric, a.view.chunks, LGPU_LAUNCH_SPEC);
     return hipGetLastError();

@@ -20,9 +20,8 @@ SearchEnv search_env()
     if(const char *ll = std::getenv("LANTERN_GPU_LDS_LIST")) e.lds_list = std::atoi(ll) != 0;
     if(const char *lp = std::getenv("LANTERN_GPU_SCREEN_LIST_PREFETCH")) e.screen_list_prefetch = std::atoi(lp) != 0;
     static const int  wide_env = std::getenv("LANTERN_GPU_WIDE_ROWS") ? std::atoi(std::getenv("LANTERN_GPU_WIDE_ROWS")) : -1;
-    static const bool solo_auto = std::getenv("LANTERN_GPU_SOLO") && std::atoi(std::getenv("LANTERN_GPU_SOLO")) != 0;
     static const int  forced = std::getenv("LANTERN_GPU_WAVES_PER_CU") ? std::atoi(std::getenv("LANTERN_GPU_WAVES_PER_CU")) : 0;
-    e.wide_rows = wide_env, e.solo = solo_auto, e.waves_per_cu = forced;
+    e.wide_rows = wide_env, e.waves_per_cu = forced;
     return e;
 }
 
@@ -112,41 +111,7 @@ SearchPlan plan_search(const SearchPlanIn &in)
             else if(nq <= (size_t)in.num_cus * 2) spec = 2;  // (1M x 768 cosine: 384 queries 528 k vs 389 k, 512: 624 k vs 500 k, 768: 658 k vs 691 k)
             if(spec < 0 || spec > 4) spec = 0;
             if(in.each) spec = spec >= 2 ? 2 : 0;  // the per-query form exists for the 3 + 8 wave shape only: spec 1 falls back to the classic shape
-#if !LGPU_EXPERIMENTAL
-            if(spec >= 3) spec = 2;  // the variants behind 3 / 4 are not in this library (LANTERN_BUILD_EXPERIMENTAL=1 builds them)
-#else
-            // 4: the ONE-WAVE walk (walk_solo.hpp): no barrier, no hand-over between waves -- f32 l2sq / cos rows of < 64 chunks,
-            // M <= 16, ef <= 64, an index whose visited bitmap fits LDS.  ON REQUEST ONLY (LANTERN_GPU_SPEC=4, or LANTERN_GPU_SOLO=1 for
-            // every launch it applies to): measured in round 5 on the lone 100k x 128 query it is SLOWER than the 3 + 8 wave shape --
-            // 117.7 us against 102.0 us per query on one box (its first form: 152.6 against 106.0), 1.70 against 1.47 us per hop -- because
-            // one wave has to issue all ~540 instructions of a hop itself; parity-green in every regime it takes.
-            // Anything it does not take falls back to spec 2.
-            if(spec == 2 && !env.spec_set && env.solo && nq <= (size_t)in.num_cus && !in.each) spec = 4;
-            if(spec == 4) {
-                const size_t words = ((std::max<size_t>(in.n, 1) + 31) / 32 + 3) & ~(size_t)3;
-                uint32_t     ne_log2 = 9;
-                while(ne_log2 > 5 && search_solo_lds_bytes(ne_log2, (uint32_t)words) > 160 * 1024) --ne_log2;
-                // (the instrumented instantiation -- lantern_gpu_spec_profile -- exists for f32 l2sq rows of exactly 32 chunks)
-                const bool prof_ok = !in.spec_profile || (in.mcode == M_L2SQ && in.chunks == 32);
-                if(pqd || !prof_ok || !search_solo_supported(in.mcode, in.chunks, in.M, in.M0, (uint32_t)expansion) ||
-                   search_solo_lds_bytes(ne_log2, (uint32_t)words) > 160 * 1024)
-                    spec = 2;
-                else {
-                    const size_t lds = search_solo_lds_bytes(ne_log2, (uint32_t)words);
-                    const size_t per_cu = std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-                    size_t       gmax = (size_t)in.num_cus * per_cu;
-                    if(in.search_max_wg > 0) gmax = (size_t)in.search_max_wg;
-                    p.path = kSearchSolo, p.spec = 4, p.took_spec = true;
-                    p.waves = 1, p.grid = (int)std::max<size_t>(1, std::min(gmax, nq));
-                    p.vis_slots = (uint32_t)words, p.lds = lds;  // the LDS bitmap (nothing of the slot's HBM slab is touched)
-                    p.spec_cache = ne_log2, p.lds_list = 0;
-                    return p;
-                }
-            }
-            // (3: two nodes per round, the second speculative -- walk_twin.hpp; on request only: measured slower)
-            if(spec == 3 && !(expansion <= 64 && (in.mcode == M_L2SQ || in.mcode == M_COS) && (group_lanes_for(in.chunks) == 64 || (in.mcode == M_L2SQ && group_lanes_for(in.chunks) == 16))))
-                spec = 2;
-#endif
+            if(spec >= 3) spec = 2;  // (3 and 4 named walks since removed: they mean the default latency-bound walk)
         }
         // (measured, classic kernel, 1M x 768 cosine, 1024 queries: 4 waves 693 k QPS, 6 waves 525 k, 8 waves 594 k -- more waves
         // only make its serial phases costlier; so four waves per query whatever the batch size)
@@ -158,7 +123,7 @@ SearchPlan plan_search(const SearchPlanIn &in)
     const int      G_ = group_lanes_for(in.chunks), LW_ = G_ >= 32 ? 1 : G_ == 16 ? 2 : 4;
     const uint32_t spec_prefetch = spec && in.M0 % (uint32_t)LW_ == 0 && in.M0 <= (uint32_t)(G_ * LW_) ? 1u : 0u;
     const uint32_t spec_cache = !spec_prefetch ? 0u : spec >= 2 ? 128u : 64u;
-    const size_t   spec_lds = spec ? search_spec_lds_bytes(in.M0, spec_prefetch, spec_cache, spec == 3) : 0;
+    const size_t   spec_lds = spec ? search_spec_lds_bytes(in.M0, spec_prefetch, spec_cache) : 0;
     // LDS visited set: sized for ~3x the planner's estimate of visited nodes per query (hnsw.c:89-132 puts it at
     // about 2 M ef S with S ~ 3), capped so that SIX workgroups fit on a CU (more walks in flight beat a roomier
     // set: 1.106 -> 1.17 M QPS at 1M x 768) -- four for the four-wave latency-bound shape, one for the lone-query shape;
@@ -184,7 +149,7 @@ SearchPlan plan_search(const SearchPlanIn &in)
     p.list_prefetch = screened && LGPU_SCREEN_LIST_PREFETCH != 0 && in.M0 <= 64 &&
                       (env.screen_list_prefetch >= 0 ? env.screen_list_prefetch != 0 : LGPU_SCREEN_LIST_PREFETCH >= 2);
     if(p.lds > 160 * 1024) { p.refusal = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel"; return p; }
-    p.path = pqd ? kSearchPqd : spec == 0 ? kSearchClassic : spec == 1 ? kSearchSpec1 : spec == 2 ? kSearchSpec2 : kSearchTwin;
+    p.path = pqd ? kSearchPqd : spec == 0 ? kSearchClassic : spec == 1 ? kSearchSpec1 : kSearchSpec2;
     p.spec = spec, p.took_spec = spec != 0;
     p.waves = waves, p.grid = search_grid(in.num_cus, in.search_max_wg, env.waves_per_cu, nq, waves, spec >= 2 ? waves : spec == 1 ? 16 : 24);
     p.vis_slots = vis_slots, p.spec_prefetch = spec_prefetch, p.spec_cache = spec_cache;
@@ -200,7 +165,7 @@ SearchPlan plan_search(const SearchPlanIn &in)
 static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries, size_t nq, size_t k, size_t skip, const SearchOut &out,
                           hipStream_t stream, uint32_t *done, uint32_t *done_flags, const EachLaunch *each)
 {
-    const bool adc = p.path == kSearchAdc, pqd = p.path == kSearchPqd, solo = p.path == kSearchSolo;
+    const bool adc = p.path == kSearchAdc, pqd = p.path == kSearchPqd;
     ix->last_search_grid = p.grid;
     const int slot = acquire_search_slot(ix, stream, (size_t)p.grid);
     if(slot < 0) return false;
@@ -211,8 +176,7 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     a.frame.labels = ix->d_labels;
     a.frame.out_labels = out.labels, a.frame.out_dists = out.dists, a.frame.out_slots = out.slots;
     a.frame.out_counts = out.counts, a.frame.out_D = out.D, a.frame.out_E = out.E;
-    // (the one-wave walk keeps its bitmap in LDS: nothing of the slot's HBM slab is touched)
-    if(!solo) a.frame.bitmaps = ix->slot_bitmaps[ slot ], a.frame.bm_words = (uint32_t)ix->slot_words[ slot ], a.frame.undo_cap = vis_undo_cap();
+    a.frame.bitmaps = ix->slot_bitmaps[ slot ], a.frame.bm_words = (uint32_t)ix->slot_words[ slot ], a.frame.undo_cap = vis_undo_cap();
     a.frame.vis_slots = p.vis_slots;
     a.frame.totals = ix->d_totals + kTotSearch;
     a.screen_totals = ix->d_screen ? ix->d_totals + kTotSearchScreen : nullptr;  // lantern_gpu_search_screen_stats
@@ -262,13 +226,9 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     }
     if(e == hipSuccess) {
         if(adc) e = launch_search_adc(ix->metric + M_ADC, a, p.waves, p.grid, stream);
-#if LGPU_EXPERIMENTAL
-        else if(solo) e = launch_search_solo(ix->mcode, a, p.grid, stream);
-#endif
         else e = launch_search(pqd ? ix->metric + M_PQD : ix->mcode, a, p.waves, p.grid, stream);
     }
     if(e != hipSuccess) return set_err(ix, std::string("lantern_gpu: HIP error launching the search: ") + hipGetErrorString(e)), false;
-    if(solo) ix->c_solo_launches += 1;
     if(done) ix->slot_pending[ slot ] = false;  // the caller waits for the kernel itself: nothing to order later launches against
     else if(!release_search_slot(ix, slot, stream)) return false;
     ix->c_search_queries += nq;
@@ -396,7 +356,7 @@ static const char *plan_search_flat(const int64_t *in, bool screen, uint32_t *ou
     s.each = in[ 19 ] != 0; s.max_expansion = (uint32_t)in[ 20 ];
     s.env.spec_set = in[ 21 ] != 0; s.env.spec = (int)in[ 22 ]; s.env.adc_spec_set = in[ 23 ] != 0; s.env.adc_spec = in[ 24 ] != 0;
     s.env.pq_adc = in[ 25 ] != 0; s.env.spec_waves = (int)in[ 26 ]; s.env.lds_list = in[ 27 ] != 0; s.env.wide_rows = (int)in[ 28 ];
-    s.env.solo = in[ 29 ] != 0; s.env.waves_per_cu = (int)in[ 30 ];
+    s.env.waves_per_cu = (int)in[ 30 ];  // (in[ 29 ]: reserved, ignored)
     s.env.screen_list_prefetch = screen_list_prefetch;
     const lgpu::SearchPlan p = lgpu::plan_search(s);
     const uint32_t flat[ 12 ] = { (uint32_t)p.path, (uint32_t)p.spec, p.expansion, (uint32_t)p.waves, (uint32_t)p.grid, p.vis_slots, (uint32_t)p.lds,

@@ -5,7 +5,7 @@
 
 namespace lgpu {
 
-size_t search_spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries, uint32_t twin) { return spec_lds_bytes(M0, prefetch, cache_entries, twin); }
+size_t search_spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries) { return spec_lds_bytes(M0, prefetch, cache_entries); }
 
 hipError_t launch_search_spec(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream)
 {

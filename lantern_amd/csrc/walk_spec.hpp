@@ -34,17 +34,11 @@ struct SpecLds
     uint32_t *ctag;    // [cache_entries] slot whose list the entry holds (EMPTY: none)
     uint32_t *clist;   // [cache_entries][M0]
     uint32_t  cache_entries;  // power of two, or 0
-    // the two-nodes-per-round walk (walk_twin.hpp) on top: the same for the SPECULATIVE node of a round
-    uint32_t *stage2;  // [2][M0][M0]
-    uint64_t *keys2;   // [2][M0] its neighbours' keys, by round parity
-    uint64_t *tw;      // [2][8] by round parity: the list's first three unexpanded keys | its radius | the two "new" masks
 };
-constexpr int TW_F0 = 0, TW_W = 3, TW_MASK1 = 4, TW_MASK2 = 5, TW_STRIDE = 8;
-__device__ __forceinline__ unsigned char *carve_spec(unsigned char *p, SpecLds &c, uint32_t M0, uint32_t prefetch, uint32_t cache_entries, uint32_t twin = 0)
+__device__ __forceinline__ unsigned char *carve_spec(unsigned char *p, SpecLds &c, uint32_t M0, uint32_t prefetch, uint32_t cache_entries)
 {
-    c.stage = c.stage2 = nullptr;
+    c.stage = nullptr;
     c.ctag = c.clist = nullptr;
-    c.keys2 = c.tw = nullptr;
     c.cache_entries = 0;
     if(prefetch) {
         c.stage = (uint32_t *)p;   p += (size_t)2 * M0 * M0 * 4;
@@ -52,17 +46,11 @@ __device__ __forceinline__ unsigned char *carve_spec(unsigned char *p, SpecLds &
         c.clist = (uint32_t *)p;   p += (size_t)cache_entries * M0 * 4;
         c.ctag = (uint32_t *)p;    p += (((size_t)cache_entries * 4) + 15) & ~(size_t)15;
     }
-    if(twin) {
-        if(prefetch) { c.stage2 = (uint32_t *)p; p += (size_t)2 * M0 * M0 * 4; }
-        c.keys2 = (uint64_t *)p;   p += (((size_t)2 * M0 * 8) + 15) & ~(size_t)15;
-        c.tw = (uint64_t *)p;      p += (size_t)2 * TW_STRIDE * 8;
-    }
     return p;
 }
-__host__ inline size_t spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries, uint32_t twin = 0)
+__host__ inline size_t spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_entries)
 {
-    return (prefetch ? (size_t)2 * M0 * M0 * 4 + (size_t)cache_entries * M0 * 4 + ((((size_t)cache_entries * 4) + 15) & ~(size_t)15) : 0) +
-           (twin ? (prefetch ? (size_t)2 * M0 * M0 * 4 : 0) + ((((size_t)2 * M0 * 8) + 15) & ~(size_t)15) + (size_t)2 * TW_STRIDE * 8 : 0);
+    return prefetch ? (size_t)2 * M0 * M0 * 4 + (size_t)cache_entries * M0 * 4 + ((((size_t)cache_entries * 4) + 15) & ~(size_t)15) : 0;
 }
 
 __device__ __forceinline__ uint64_t uniform64(uint64_t x)  // a value every lane read from the same address, as scalar registers

@@ -200,7 +200,7 @@ def plan_fields(r, num_cus):
          "env_spec_set": int("LANTERN_GPU_SPEC" in env), "env_spec": int(env.get("LANTERN_GPU_SPEC", 0)),
          "env_adc_spec_set": int("LANTERN_GPU_ADC_SPEC" in env), "env_adc_spec": int(env.get("LANTERN_GPU_ADC_SPEC", 0)),
          "env_pq_adc": int(env.get("LANTERN_GPU_PQ_ADC", 0)), "env_spec_waves": 0, "env_lds_list": int(env.get("LANTERN_GPU_LDS_LIST", 0)),
-         "env_wide_rows": -1, "env_solo": 0, "env_waves_per_cu": 0}
+         "env_wide_rows": -1, "reserved_29": 0, "env_waves_per_cu": 0}
     if has_screen(r) is not None:
         f["screen"] = int(has_screen(r))
     return f

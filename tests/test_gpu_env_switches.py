@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # tests/test_scan_server.py and tests/test_gpu_fake_rccl.py), diagnostics, and LANTERN_GPU_PQ_ADC (a different summation order by
 # definition: its own parity test, test_compact_pq_index_searches_by_adc_over_the_code_bytes).
 SWITCHES = [{"LANTERN_GPU_SPEC": "0"}, {"LANTERN_GPU_SPEC": "1"}, {"LANTERN_GPU_SPEC": "2"}, {"LANTERN_GPU_SPEC": "3"}, {"LANTERN_GPU_SPEC": "4"},
-            {"LANTERN_GPU_SOLO": "1"}, {"LANTERN_GPU_SPEC_WAVES": "6"}, {"LANTERN_GPU_LDS_LIST": "1"}, {"LANTERN_GPU_WIDE_ROWS": "0"}, {"LANTERN_GPU_WIDE_ROWS": "1"},
+            {"LANTERN_GPU_SPEC_WAVES": "6"}, {"LANTERN_GPU_LDS_LIST": "1"}, {"LANTERN_GPU_WIDE_ROWS": "0"}, {"LANTERN_GPU_WIDE_ROWS": "1"},
             {"LANTERN_GPU_VIS_SLOTS": "0"}, {"LANTERN_GPU_VIS_SLOTS": "256"}, {"LANTERN_GPU_INSERT_VIS_SLOTS": "0"}, {"LANTERN_GPU_INSERT_VIS_SLOTS": "256"},
             {"LANTERN_GPU_WAVES_PER_CU": "8"},
             {"LANTERN_GPU_TICKETS": "0"}, {"LANTERN_GPU_INSERT_SPEC": "0"}, {"LANTERN_GPU_REPRUNE_STATE": "0"}, {"LANTERN_GPU_REGS_CPL4": "1"},

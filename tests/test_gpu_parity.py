@@ -7,7 +7,6 @@ identical top-k id lists, identical distance-evaluation and expansion counts on 
 import numpy as np
 import pytest
 
-from tests.conftest import needs_experimental
 from tests.scan_driver import scan as oracle_scan
 
 pytestmark = pytest.mark.gpu
@@ -777,8 +776,7 @@ def test_candidate_list_in_registers_or_lds_gives_the_oracle_walk(capi, oracle, 
 # ------------------------------------------------------------------------------------------------
 # the latency-bound walk (walk_spec.hpp): one barrier per hop, speculative row loads behind which the visited filter, the list
 # merge and the list-cache fill run, neighbour lists fetched with the rows.  LANTERN_GPU_SPEC=1: the four-wave batch shape,
-# =2: the lone-query shape (three role waves + eight row waves), =3: the same shape with two nodes per round, the second one
-# speculative (walk_twin.hpp).  Every lanes-per-row regime (8 / 16 / 32 / 64), list widths
+# =2: the lone-query shape (three role waves + eight row waves).  Every lanes-per-row regime (8 / 16 / 32 / 64), list widths
 # with and without the list prefetch (M0 = 10 has no 16-byte pieces at 8 lanes per row), M0 = 64 (two passes per hop), both
 # register-list widths (ef <= 64, <= 128), every storage kind -- against the oracle on the same graph: ids, distance bits, D, E.
 # ------------------------------------------------------------------------------------------------
@@ -787,7 +785,7 @@ SPEC_SHAPES = [("l2sq", 3000, 128, 16, 64, "f32"), ("cos", 2500, 768, 16, 64, "f
                ("l2sq", 1500, 768, 8, 64, "f16"), ("cos", 1500, 256, 16, 48, "i8"), ("l2sq", 700, 2000, 4, 20, "f32"), ("l2sq", 800, 600, 32, 64, "f32")]
 
 
-@pytest.mark.parametrize("spec", ["1", "2", pytest.param("3", marks=needs_experimental)])
+@pytest.mark.parametrize("spec", ["1", "2"])
 @pytest.mark.parametrize("metric,n,d,M,ef,quant", SPEC_SHAPES)
 def test_latency_bound_walk_is_the_oracle_walk(capi, oracle, metric, n, d, M, ef, quant, spec, monkeypatch):
     from lantern_amd import hip
@@ -830,54 +828,6 @@ def test_latency_bound_walk_is_the_oracle_walk(capi, oracle, metric, n, d, M, ef
     assert np.array_equal(lab.download((nq, k), np.uint64), o_lab) and np.array_equal(D.download(nq, np.uint64), o_D)
 
 
-# the ONE-WAVE walk (walk_solo.hpp, LANTERN_GPU_SPEC=4; on request only -- measured slower than the 3 + 8 wave shape): f32 l2sq / cos rows of
-# fewer than 64 chunks, M <= 16 (a multiple of 4), ef <= 64.  8 and 16 lanes per row, one to four chunks per lane, rows that end inside
-# a lane's last chunk and rows that do not, full and short neighbour lists, exact duplicates -- ids, distance bits, D, E of the oracle.
-SOLO_SHAPES = [("l2sq", 3000, 128, 16, 64), ("cos", 2500, 128, 16, 64), ("l2sq", 2000, 40, 16, 50), ("cos", 2000, 24, 8, 33), ("l2sq", 1500, 252, 16, 64),
-               ("l2sq", 1500, 192, 4, 20), ("cos", 1800, 100, 12, 40), ("l2sq", 1200, 32, 16, 64), ("l2sq", 1000, 4, 16, 10), ("cos", 1500, 200, 16, 64)]
-
-
-@needs_experimental
-@pytest.mark.parametrize("metric,n,d,M,ef", SOLO_SHAPES)
-def test_one_wave_walk_is_the_oracle_walk(capi, oracle, metric, n, d, M, ef, monkeypatch):
-    from lantern_amd import hip
-
-    rng = np.random.default_rng(n + d + M)
-    base = rand_rows(rng, n, d, metric)
-    nq = 300
-    queries = rand_rows(rng, nq, d, metric)
-    base[n // 2: n // 2 + 100] = base[:100]  # exact duplicates: equal distances, the slot decides
-    gpu = capi.GpuIndex(metric, d, M=M, ef_construction=48, ef=ef, seed=9)
-    gpu.set_add_batch(256, 8)
-    gpu.add_many(np.arange(n, dtype=np.uint64) + 1, base)
-    g = gpu.export_graph()
-    ora = oracle.OracleIndex.from_graph(metric, base, g, M, 48, ef, 9, oracle.SUM_WAVE64)
-    k = min(10, ef)
-    o_lab, o_dist, o_slot, o_D, o_E = ora.search_batch(queries, k, ef, 4)
-    monkeypatch.setenv("LANTERN_GPU_SPEC", "4")
-    dq = hip.Buffer.from_numpy(hip.padded_rows(queries, False))
-    lab, dist, D, E = hip.Buffer(nq * k * 8), hip.Buffer(nq * k * 4), hip.Buffer(nq * 8), hip.Buffer(nq * 8)
-    gpu.set_search_shape(0)  # the automatic shape: LANTERN_GPU_SPEC decides
-    before = gpu.counters()["search_solo_launches"]
-    for rows in (nq, 7, 1):  # more queries than workgroups can be resident (tickets), a handful, one
-        gpu.search_batch_device(dq.ptr, rows, k, 0, 0, lab.ptr, dist.ptr, None, None, D.ptr, E.ptr)
-        hip.synchronize()
-        assert np.array_equal(lab.download((nq, k), np.uint64)[:rows], o_lab[:rows])
-        assert np.array_equal(dist.download((nq, k), np.float32)[:rows], o_dist[:rows])
-        assert np.array_equal(D.download(nq, np.uint64)[:rows], o_D[:rows]), "distance-evaluation counts differ"
-        assert np.array_equal(E.download(nq, np.uint64)[:rows], o_E[:rows]), "expansion counts differ"
-    assert gpu.counters()["search_solo_launches"] == before + 3, "the one-wave kernel did not run"
-    # usearch_search_ef, one query per call: the host waits on the kernel's own completion counter
-    for i in range(20):
-        l1, d1 = gpu.search(queries[i], k)
-        assert np.array_equal(l1, o_lab[i]) and np.array_equal(d1, o_dist[i]), i
-    assert gpu.counters()["search_solo_launches"] == before + 23
-    # ... and without the request a lone query keeps the 3 + 8 wave shape (the faster one: DESIGN.md 4.3c)
-    monkeypatch.delenv("LANTERN_GPU_SPEC")
-    l1, d1 = gpu.search(queries[0], k)
-    assert np.array_equal(l1, o_lab[0]) and gpu.counters()["search_solo_launches"] == before + 23
-
-
 def test_lone_query_and_small_batches_take_the_latency_bound_walk_by_default(capi, oracle):
     """usearch_search_ef (one query per call) and batches around the switch points of the automatic shapes (the lone-query shape up
     to two queries per CU -- the second after the first on the same workgroup --, the classic four-wave walk beyond) -- same answers
@@ -903,7 +853,7 @@ def test_lone_query_and_small_batches_take_the_latency_bound_walk_by_default(cap
     assert len(set(got)) == 30
 
 
-@pytest.mark.parametrize("d", [64, 160])  # 8 lanes per row; 16 lanes per row (where LANTERN_GPU_SPEC=3 has a walk of its own)
+@pytest.mark.parametrize("d", [64, 160])  # 8 lanes per row; 16 lanes per row
 def test_latency_bound_walk_with_a_spilling_visited_set(capi, oracle, monkeypatch, d):
     rng = np.random.default_rng(11)
     base, queries = rng.standard_normal((4000, d), dtype=np.float32), rng.standard_normal((64, d), dtype=np.float32)
@@ -913,7 +863,7 @@ def test_latency_bound_walk_with_a_spilling_visited_set(capi, oracle, monkeypatc
     assert o_D.max() > 300
     for vis_slots in ("256", "0"):  # 256: spills to the HBM bitmap after ~190 visits; 0: the bitmap only
         monkeypatch.setenv("LANTERN_GPU_VIS_SLOTS", vis_slots)
-        for spec in ("1", "2", "3"):  # ("3" is "2" in a library without csrc/experimental/)
+        for spec in ("1", "2", "3"):  # (LANTERN_GPU_SPEC=3 means 2)
             monkeypatch.setenv("LANTERN_GPU_SPEC", spec)
             gpu = capi.GpuIndex("l2sq", d, M=16, ef_construction=64, ef=128, seed=9)
             gpu.import_graph(base, ora.export_graph())

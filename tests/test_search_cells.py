@@ -56,11 +56,8 @@ def test_the_library_holds_exactly_the_cells_of_the_ledger(capi):
     assert len(want) == 542 + 15
     missing, extra = sorted(want - got), sorted(got - want)
     assert not missing, f"{len(missing)} cells of the ledger are not in the library, first {missing[:5]}"
-    if capi.experimental_build():  # (csrc/experimental/: the two-nodes-per-round walk adds its SPEC = 3 instantiations, and nothing else)
-        assert all(c[0] == sc.K_SEARCH and c[6] == 3 for c in extra), [c for c in extra if c[6] != 3][:5]
-    else:
-        assert not extra, f"{len(extra)} instantiations in the library have no row in the ledger, first {extra[:5]}"
-        assert len([c for c in got if c[0] == sc.K_SEARCH]) == 537 and len([c for c in got if c[0] == sc.K_SEARCH_ADC]) == 20
+    assert not extra, f"{len(extra)} instantiations in the library have no row in the ledger, first {extra[:5]}"
+    assert len([c for c in got if c[0] == sc.K_SEARCH]) == 537 and len([c for c in got if c[0] == sc.K_SEARCH_ADC]) == 20
 
 
 def test_every_cell_has_recipes_that_land_on_it():

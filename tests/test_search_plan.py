@@ -1,8 +1,7 @@
 """The shape of the unfiltered search launch, without a device: lantern_gpu_plan_search (csrc/search_plan.cpp plan_search) against
 tests/golden/search_plan_cases.json -- rows recorded from a sweep in which every launch the planned code made was compared, kernel
 argument by kernel argument, with what the code before the plan existed launched for the same index, call and environment.  A row is
-{"in": the 31 input fields, "out": the 12 output fields, "refusal": the text or null, "experimental": 1 if the row was recorded from a
-LANTERN_BUILD_EXPERIMENTAL library and means something only there (paths 5 and 6), "tag": what the row is there for}."""
+{"in": the 31 input fields, "out": the 12 output fields, "refusal": the text or null, "tag": what the row is there for}."""
 import json
 import os
 
@@ -11,7 +10,7 @@ import pytest
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "search_plan_cases.json")
 REFUSAL_WALK = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel"
 REFUSAL_ADC = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the ADC search kernel"
-PATHS = {"adc": 0, "pqd": 1, "classic": 2, "spec1": 3, "spec2": 4, "twin": 5, "solo": 6}
+PATHS = {"adc": 0, "pqd": 1, "classic": 2, "spec1": 3, "spec2": 4}
 
 
 @pytest.fixture(scope="module")
@@ -37,13 +36,8 @@ def test_the_committed_rows_cover_every_path_and_refusal():
 
 
 def test_plan_search_reproduces_the_committed_rows(capi):
-    experimental = capi.experimental_build()
     checked = 0
     for r in rows():
-        if r["experimental"] and not experimental:
-            continue  # the row's path is not in this library
-        if not r["experimental"] and experimental and (r["in"][21] and r["in"][22] >= 3 or r["in"][29]):
-            continue  # LANTERN_GPU_SPEC=3|4 / LANTERN_GPU_SOLO mean spec 2 in the default library only
         out, why = capi.plan_search(r["in"])
         assert why == r["refusal"], r
         if why is None:
@@ -51,7 +45,7 @@ def test_plan_search_reproduces_the_committed_rows(capi):
         else:
             assert out["expansion"] == r["out"][2], r
         checked += 1
-    assert checked >= 40
+    assert checked == len(rows()) == 88
 
 
 def test_the_refusal_texts(capi):
