@@ -550,7 +550,8 @@ LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_
 LANTERN_GPU_EXPORT void lantern_gpu_exact_search(usearch_index_t, const void *queries, size_t nq, size_t k,
                                                  uint32_t *slots, float *distances, usearch_error_t *);
 
-/* Diagnostic for the measurement harness: HIP events around every launch of the fp32-MFMA contraction (k_dense_f32) inside
+/* Diagnostic for the measurement harness: HIP events around every launch of the MFMA contraction (k_dense_f32; k_dense_native on
+ * f16 / i8 indexes) inside
  * lantern_gpu_exact_search / _assign_to_clusters / _distance_matrix.  on != 0 starts recording; on == 0 stops and writes up to
  * `cap` records -- ms[i], rows[i] x cols[i] (queries x base rows of the launch), fused[i] (1: the launch with the fused top-k
  * epilogue) -- and returns how many launches were recorded.  Process-wide; any pointer may be NULL. */
@@ -559,6 +560,18 @@ LANTERN_GPU_EXPORT size_t lantern_gpu_dense_profile(int on, float *ms, uint32_t 
  * answered, how many of them the MFMA pre-selection's certificate passed, and how many took the exact-order fallback
  * (queries = certified + fallback).  Any pointer may be NULL. */
 LANTERN_GPU_EXPORT void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t *certified, uint64_t *fallback);
+/* Process-wide cumulative launches of the MFMA contraction by the type of its operands: launches[0] f32 rows (k_dense_f32; a
+ * quantised index on the dequantised path counts here), [1] f16 rows, [2] i8 rows as stored (k_dense_native).  Counted inside
+ * lantern_gpu_exact_search / _assign_to_clusters / PQ encoding and lantern_gpu_distance_matrix(exact_order = 0). */
+LANTERN_GPU_EXPORT void lantern_gpu_dense_kind_stats(uint64_t launches[3]);
+/* Which contraction an exact k-NN call runs -- host arithmetic only; the call itself takes its decisions from this function.
+ * in:  [0] the index's internal metric code (metric, + 100 for f16 storage, + 200 for i8), [1] 16-byte chunks per stored row,
+ *      [2] base rows, [3] the value of LANTERN_GPU_DENSE_NATIVE (-1: unset).
+ * out: [0] operand kind 0 / 1 / 2 (f32, f16, i8); [1] bytes of the f32 copy of one chunk of base rows the call allocates (0
+ *      when the rows are contracted as stored); [2] the `dims` handed to the certificate (0: the pre-selection ranks on the
+ *      exact-order distance itself and is certified by construction: popcount metrics, native i8); [3] K steps (128 bytes per
+ *      row each) per output tile (0: no MFMA contraction).  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_dense(const int64_t in[4], uint32_t out[4]);
 
 /* Diagnostic for the measurement harness: the memory objects every query of a launch asks for, in order (rows evaluated, adjacency
  * lists read) -- the input of the cache model behind bench.py's roofline.frac_dram_model (lantern_amd/tools/cache_model.c).
@@ -640,8 +653,10 @@ LANTERN_GPU_EXPORT size_t lantern_gpu_export_screen(usearch_index_t, size_t firs
 LANTERN_GPU_EXPORT void lantern_gpu_screen_probe(usearch_index_t, const void *query, const uint32_t *slots, size_t n, float radius,
                                                  int workgroup, uint8_t *rejected, usearch_error_t *);
 /* Dense na x nb distance matrix between two host matrices (f32 rows of `dims` scalars, or u32
- * words for hamming with dims = bits).  `exact_order` != 0 uses the per-pair reduction order of
- * the graph walk (bit-identical to usearch_distance); 0 uses the fp32-MFMA contraction. */
+ * words for hamming with dims = bits; under cos / l2sq also usearch_scalar_f16_k -- rows of `dims` IEEE halves -- and
+ * usearch_scalar_i8_k -- rows of `dims` int8 --, i.e. the values an index of that storage holds).  `exact_order` != 0 uses the
+ * per-pair reduction order of the graph walk (bit-identical to usearch_distance); 0 uses the MFMA contraction of the operand
+ * type: fp32 for f32 rows, f16 / i8 for rows of those kinds (i8: the same bits as exact_order != 0). */
 LANTERN_GPU_EXPORT void lantern_gpu_distance_matrix(const void *a, size_t na, const void *b, size_t nb,
                                                     usearch_scalar_kind_t, size_t dims, usearch_metric_kind_t,
                                                     int exact_order, float *out, usearch_error_t *);

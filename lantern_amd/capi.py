@@ -86,7 +86,7 @@ EXPORTS = [
     "lantern_gpu_version", "lantern_gpu_device_count",
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
-    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_distance_gather",
+    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_distance_gather",
     "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
@@ -226,6 +226,8 @@ def lib() -> C.CDLL:
         "lantern_gpu_exact_search": (None, [vp, vp, sz, sz, vp, vp, err]),
         "lantern_gpu_dense_profile": (sz, [i32, vp, vp, vp, vp, sz]),
         "lantern_gpu_exact_knn_stats": (None, [C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "lantern_gpu_dense_kind_stats": (None, [vp]),
+        "lantern_gpu_plan_dense": (C.c_char_p, [vp, vp]),
         "lantern_gpu_distance_gather": (None, [vp, vp, vp, sz, vp, err]),
         "lantern_gpu_spec_profile": (None, [vp, i32, vp, err]),
         "lantern_gpu_search_unique_rows": (None, [vp, i32, C.POINTER(u64), err]),
@@ -393,30 +395,37 @@ def device_count() -> int:
     return int(lib().lantern_gpu_device_count())
 
 
-def _rows(x, metric):
-    dt = np.uint32 if metric == METRIC_HAMMING else np.float32
+# rows of a stored kind for distance / distance_matrix: kind -> (numpy dtype, usearch_scalar_kind_t)
+ROW_KINDS = {"f16": (np.float16, SCALAR_F16), "i8": (np.int8, SCALAR_I8)}
+
+
+def _rows(x, metric, kind=None):
+    dt = ROW_KINDS[kind][0] if kind is not None else np.uint32 if metric == METRIC_HAMMING else np.float32
     a = np.ascontiguousarray(x, dtype=dt)
     return a.reshape(1, -1) if a.ndim == 1 else a
 
 
-def _kind(metric):
+def _kind(metric, kind=None):
+    if kind is not None:
+        return ROW_KINDS[kind][1]
     return SCALAR_B1 if metric == METRIC_HAMMING else SCALAR_F32
 
 
-def distance(a, b, metric) -> float:
-    """usearch_distance: one pair, on the device."""
+def distance(a, b, metric, kind=None) -> float:
+    """usearch_distance: one pair, on the device.  kind "f16" / "i8": rows of np.float16 / np.int8 (the stored values)."""
     m = METRICS.get(metric, metric)
-    A, B = _rows(a, m)[0], _rows(b, m)[0]
-    dims = A.size * 32 if m == METRIC_HAMMING else A.size
-    return float(_call("usearch_distance", _ptr(A), _ptr(B), _kind(m), dims, m))
+    A, B = _rows(a, m, kind)[0], _rows(b, m, kind)[0]
+    dims = A.size * 32 if m == METRIC_HAMMING and kind is None else A.size
+    return float(_call("usearch_distance", _ptr(A), _ptr(B), _kind(m, kind), dims, m))
 
 
-def distance_matrix(a, b, metric, exact_order=True):
+def distance_matrix(a, b, metric, exact_order=True, kind=None):
+    """lantern_gpu_distance_matrix.  kind None: f32 rows (u32 words for hamming); "f16" / "i8": rows of np.float16 / np.int8."""
     m = METRICS.get(metric, metric)
-    A, B = _rows(a, m), _rows(b, m)
-    dims = A.shape[1] * 32 if m == METRIC_HAMMING else A.shape[1]
+    A, B = _rows(a, m, kind), _rows(b, m, kind)
+    dims = A.shape[1] * 32 if m == METRIC_HAMMING and kind is None else A.shape[1]
     out = np.empty((A.shape[0], B.shape[0]), dtype=np.float32)
-    _call("lantern_gpu_distance_matrix", _ptr(A), A.shape[0], _ptr(B), B.shape[0], _kind(m), dims, m,
+    _call("lantern_gpu_distance_matrix", _ptr(A), A.shape[0], _ptr(B), B.shape[0], _kind(m, kind), dims, m,
           1 if exact_order else 0, _ptr(out))
     return out
 
@@ -439,7 +448,7 @@ def version() -> str:
 
 
 def dense_profile(on: bool):
-    """on=True: record HIP events around every fp32-MFMA contraction launch of the exact k-NN.  on=False: stop and return the records
+    """on=True: record HIP events around every MFMA contraction launch of the exact k-NN (fp32, or f16 / i8 on quantised indexes).  on=False: stop and return the records
     as a list of dicts {ms, rows, cols, fused} (lantern_gpu_dense_profile)."""
     if on:
         lib().lantern_gpu_dense_profile(1, None, None, None, None, 0)
@@ -455,6 +464,23 @@ def exact_knn_stats():
     q, c, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
     lib().lantern_gpu_exact_knn_stats(C.byref(q), C.byref(c), C.byref(f))
     return {"queries": int(q.value), "certified": int(c.value), "fallback": int(f.value)}
+
+
+def dense_kind_stats():
+    """lantern_gpu_dense_kind_stats: process-wide MFMA contraction launches by operand kind, [f32, f16, i8] (cumulative)."""
+    out = np.zeros(3, np.uint64)
+    lib().lantern_gpu_dense_kind_stats(_ptr(out))
+    return [int(v) for v in out]
+
+
+def plan_dense(mcode, chunks, rows, native=-1):
+    """lantern_gpu_plan_dense: {kind, copy_bytes, dims, k_steps} of an exact k-NN over `rows` stored rows of `chunks` 16-byte
+    chunks under the internal metric code `mcode`; native = the value of LANTERN_GPU_DENSE_NATIVE (-1: unset)."""
+    pin, out = np.array([mcode, chunks, rows, native], np.int64), np.zeros(4, np.uint32)
+    why = lib().lantern_gpu_plan_dense(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    return {"kind": int(out[0]), "copy_bytes": int(out[1]), "dims": int(out[2]), "k_steps": int(out[3])}
 
 
 def l2sq_dist(a, b) -> float:

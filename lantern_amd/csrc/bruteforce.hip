@@ -5,7 +5,8 @@
 //   k_row_norms    ||x||^2 per row (one G-lane group per row, same reduction as the walk)
 //   k_dense_f32    D[q][c] = metric(Q[q], B[c]) for a 128 x 128 tile per workgroup on fp32 MFMA
 //                  (v_mfma_f32_32x32x2_f32: f32 in, f32 accumulate -- bf16/fp16 would lose the 1e-5
-//                  tolerance).  l2sq = |q|^2 + |b|^2 - 2 q.b ; cos = 1 - q.b / (|q||b|) with the
+//                  tolerance ON F32 ROWS; rows that are stored as f16 or i8 lose nothing on the MFMAs of their
+//                  own type, and take them: dense_native.hip).  l2sq = |q|^2 + |b|^2 - 2 q.b ; cos = 1 - q.b / (|q||b|) with the
 //                  reference's zero-norm rules.  This is the only place MFMA is used: it is the one
 //                  true dense contraction on the path.
 //   k_dense_ham    the same tile shape for hamming (popcount of XOR; integer, VALU)
@@ -16,6 +17,7 @@
 //                  refuses are recomputed in exact order: k_gather_rows, k_pairs + k_select, k_emit_topk)
 #include "kernels.hpp"
 #include "walk.hpp"
+#include "dense_tile.hpp"
 
 namespace lgpu {
 
@@ -43,23 +45,7 @@ __global__ void __launch_bounds__(256) k_row_norms(const uint4 *rows, uint32_t n
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 128 x 128 output tile per 256-thread workgroup; 4 waves as 2 x 2, each wave 2 x 2 MFMA tiles of 32 x 32 (64 accumulator
-// registers per lane); K staged through LDS 32 floats at a time.
-constexpr int BM = 128, BN = 128, BK = 32;
-
-// FUSED: the tile does not write its distances; an output that can still enter its query's running top-kk -- ordered distance
-// <= the kk-th best so far, read once per tile -- is appended to that query's candidate list (cand[q][CAP], cnt[q]), which
-// k_select folds into `best` after the launch.  Once a few thousand columns have been seen that is a handful of appends per
-// query and launch instead of a 268 MB matrix written here and read back there.
-struct DenseTopk
-{
-    const uint64_t *best;  // [nq][kk] running top-kk keys (ordered distance << 32 | column), ascending
-    uint32_t        kk;
-    uint64_t       *cand;  // [nq][cap]
-    uint32_t       *cnt;   // [nq] appended so far (may exceed cap: k_select reports the overflow)
-    uint32_t        cap;
-    uint32_t        c_base;  // column id of this launch's first base row
-};
+// (the 128 x 128 tile, BK = 32 floats per K step, DenseTopk and DENSE_WGS_PER_CU: dense_tile.hpp, shared with dense_native.hip)
 
 // Persistent workgroups over a stream of K steps.  A launch starts DENSE_WGS_PER_CU workgroups per CU; each walks its own list
 // of tiles, and the K steps of all its tiles form ONE software pipeline over two LDS buffers: while step s (buffer P) is on the
@@ -82,8 +68,6 @@ struct DenseTopk
 // take consecutive tiles of it, so the tiles_m workgroups sharing a B tile run on ONE XCD at about the same time and its L2
 // serves all but the first read.  Loads are branch-free: the descriptor of a tile starts at its first row and ends with its
 // last one that exists, so rows past the end land as zeros, and so does a k past the end (offset pushed out of range).
-constexpr int DENSE_WGS_PER_CU = 2;  // 67 KB of LDS each
-
 template <int METRIC, bool FUSED = false>
 __global__ void __launch_bounds__(256, 2) k_dense_f32(const float *Q, uint32_t nq, const float *B, uint32_t nb, uint32_t stride /* floats per row */,
                                                    const float *qn, const float *bn, float *out, uint32_t ldo, DenseTopk tk)
@@ -792,8 +776,8 @@ hipError_t launch_row_norms(const uint4 *rows, uint32_t n, uint32_t chunks, floa
     return hipGetLastError();
 }
 
-// persistent grid of k_dense_f32: DENSE_WGS_PER_CU workgroups per CU of the current device (fewer if there are fewer tiles)
-static uint32_t dense_grid(uint32_t tiles)
+// persistent grid of k_dense_f32 / k_dense_native: DENSE_WGS_PER_CU workgroups per CU of the current device (fewer if there are fewer tiles)
+uint32_t dense_grid(uint32_t tiles)
 {
     static int cus[ 64 ];  // per device ordinal; filled once (racing fillers write the same value)
     int        dev = 0;

@@ -1864,6 +1864,10 @@ LANTERN_ABI_CATCH_VOID(e)
 
 // ---- distances ------------------------------------------------------------------------------------
 
+namespace {
+std::atomic<uint64_t> g_dense_kind[ 3 ];  // MFMA contraction launches of the process by operand kind: f32, f16, i8 (lantern_gpu_dense_kind_stats)
+}
+
 static bool metric_ok(usearch_metric_kind_t m) { return m == usearch_metric_cos_k || m == usearch_metric_l2sq_k || m == usearch_metric_hamming_k; }
 
 void lantern_gpu_distance_matrix(const void *a, size_t na, const void *b, size_t nb, usearch_scalar_kind_t kind, size_t dims,
@@ -1872,12 +1876,15 @@ try {
     CLEAR(e);
     if(!metric_ok(metric)) { FAIL(e, "lantern_gpu: unsupported metric kind (expected cos, l2sq or hamming)"); return; }
     const bool ham = metric == usearch_metric_hamming_k;
-    if(ham != (kind == usearch_scalar_b1_k) || (!ham && kind != usearch_scalar_f32_k)) { FAIL(e, "lantern_gpu: scalar kind does not fit the metric"); return; }
+    // f16 / i8: rows of IEEE halves / int8 as an index of that storage holds them, under cos / l2sq (upstream usearch_distance takes them)
+    const bool h16 = kind == usearch_scalar_f16_k, s8 = kind == usearch_scalar_i8_k;
+    if(ham != (kind == usearch_scalar_b1_k) || (!ham && kind != usearch_scalar_f32_k && !h16 && !s8)) { FAIL(e, "lantern_gpu: scalar kind does not fit the metric"); return; }
     if(!a || !b || !out || dims == 0) { FAIL(e, "lantern_gpu: bad arguments"); return; }
     if(lantern_gpu_device_count() <= 0) { FAIL(e, kNoDevice); return; }
     if(na == 0 || nb == 0) return;
-    const size_t words = ham ? (dims + 31) / 32 : dims, in_bytes = ham ? (dims + 7) / 8 : dims * 4;
-    const size_t chunks = (words + 3) / 4, row = chunks * 16;
+    const size_t in_bytes = ham ? (dims + 7) / 8 : h16 ? dims * 2 : s8 ? dims : dims * 4;
+    const size_t chunks = (in_bytes + 15) / 16, row = chunks * 16;
+    const int    mcode = (int)metric + (h16 ? M_F16 : s8 ? M_I8 : 0), dkind = h16 ? 1 : s8 ? 2 : 0;
     std::vector<char> ha(na * row, 0), hb(nb * row, 0);
     for(size_t i = 0; i < na; ++i) std::memcpy(&ha[ i * row ], (const char *)a + i * in_bytes, in_bytes);
     for(size_t i = 0; i < nb; ++i) std::memcpy(&hb[ i * row ], (const char *)b + i * in_bytes, in_bytes);
@@ -1887,13 +1894,21 @@ try {
     ok = ok && hipMemcpy(da, ha.data(), na * row, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(db, hb.data(), nb * row, hipMemcpyHostToDevice) == hipSuccess;
     if(exact_order) {
-        ok = ok && launch_pairs((int)metric, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks,
+        ok = ok && launch_pairs(mcode, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks,
                                 (float *)dout, nullptr) == hipSuccess;
+    } else if(dkind) {  // the dense contraction on the stored operand type (dense_native.hip)
+        uint32_t *an = (uint32_t *)dn, *bnn = an + na;
+        ok = ok && launch_row_norms_native(dkind, (int)metric, (const uint4 *)da, (uint32_t)na, (uint32_t)chunks, an, nullptr) == hipSuccess;
+        ok = ok && launch_row_norms_native(dkind, (int)metric, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, bnn, nullptr) == hipSuccess;
+        ok = ok && launch_dense_native(dkind, (int)metric, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, an, bnn,
+                                       (float *)dout, (uint32_t)nb, nullptr) == hipSuccess;
+        ++g_dense_kind[ dkind ];
     } else {  // the dense contraction: fp32 MFMA for l2sq / cos
         float *an = (float *)dn, *bnn = an + na;
         if(!ham) {
             ok = ok && launch_row_norms((const uint4 *)da, (uint32_t)na, (uint32_t)chunks, an, nullptr) == hipSuccess;
             ok = ok && launch_row_norms((const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, bnn, nullptr) == hipSuccess;
+            ++g_dense_kind[ 0 ];
         }
         ok = ok && launch_dense((int)metric, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, an, bnn,
                                 (float *)dout, (uint32_t)nb, nullptr) == hipSuccess;
@@ -2033,6 +2048,36 @@ struct KnnBlock  // pooled if small, allocated for the call otherwise; released 
 };
 }  // namespace
 
+// ---- which contraction an exact k-NN runs: host arithmetic, shared by exact_knn_device_impl and the tests ---------------------
+// Rows stored as f16 / i8 are contracted as they are stored (dense_native.hip) unless LANTERN_GPU_DENSE_NATIVE says otherwise;
+// kDenseNativeDefault is what an unset switch means (set by the measurement rule recorded there).
+static const int      kDenseNativeDefault = 1;
+static const size_t   kDenseChunkRows = 65536;  // base rows per contraction launch
+const char *lantern_gpu_plan_dense(const int64_t in[ 4 ], uint32_t out[ 4 ])
+{
+    if(!in || !out) return "lantern_gpu: null plan array";
+    if(in[ 0 ] < 0 || in[ 0 ] > 0x7FFFFFFF || in[ 1 ] <= 0 || in[ 1 ] > (int64_t)1 << 20 || in[ 2 ] < 0) return "lantern_gpu: bad plan input";
+    const int      mcode = (int)in[ 0 ], base = mcode_base(mcode);
+    const uint32_t chunks = (uint32_t)in[ 1 ];
+    const bool     f16 = mcode_is_f16(mcode), i8 = mcode_is_i8(mcode), bits = base == M_HAMMING || base == M_COS_B1;
+    const bool     native = (f16 || i8) && !bits && (in[ 3 ] < 0 ? kDenseNativeDefault : (int)in[ 3 ]) != 0;
+    const uint32_t fchunks = native ? chunks : i8 ? chunks * 4 : f16 ? chunks * 2 : chunks;
+    const uint64_t copy = (f16 || i8) && !native ? (uint64_t)std::min<int64_t>(in[ 2 ], (int64_t)kDenseChunkRows) * fchunks * 16 : 0;
+    if(copy > 0xFFFFFFFFull) return "lantern_gpu: the f32 copy of a chunk of rows does not fit the plan";
+    out[ 0 ] = !native ? 0u : f16 ? 1u : 2u;
+    out[ 1 ] = (uint32_t)copy;
+    // the certificate's dims: f32 scalars contracted; native f16 -- twice the halves contracted; 0 -- keys are exact
+    out[ 2 ] = bits || (native && i8) ? 0u : native ? chunks * 16 : fchunks * 4;
+    out[ 3 ] = bits ? 0u : (fchunks * 4 + 31) / 32;
+    return nullptr;
+}
+
+void lantern_gpu_dense_kind_stats(uint64_t launches[ 3 ])
+{
+    if(!launches) return;
+    for(int i = 0; i < 3; ++i) launches[ i ] = g_dense_kind[ i ].load();
+}
+
 // certified: one flag per query (1: the certificate of DESIGN.md 4.5 holds -- the result is the exact answer; 0: the caller
 // recomputes the query in exact order, exact_knn_fallback)
 static bool exact_knn_device_impl(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k,
@@ -2050,14 +2095,24 @@ try {
     // column chunk.  [r3] 65536 columns x 1024 queries are 4096 tiles = 5.33 rounds of the 768 workgroups the contraction keeps
     // resident (three per CU): the last round runs a third full.  98304 columns (6144 tiles = 8 rounds) were tried: l2sq 14.9 -> 14.5 ms
     // per 1024 x 1M x 768 call, but cosine 15.4 -> 20.1 ms (the fused call repeated itself unfused), so the chunk stays.
-    const size_t   QT = 1024, CH = std::min<size_t>(nb, 65536);
+    const size_t   QT = 1024, CH = std::min<size_t>(nb, kDenseChunkRows);
+    // which contraction, what it allocates and what the certificate is told: lantern_gpu_plan_dense, read per call
+    const char    *env_native = std::getenv("LANTERN_GPU_DENSE_NATIVE");
+    const int64_t  plan_in[ 4 ] = { mcode, chunks, (int64_t)nb, env_native ? std::atoi(env_native) : -1 };
+    uint32_t       plan[ 4 ] = { 0, 0, 0, 0 };
+    if(lantern_gpu_plan_dense(plan_in, plan) != nullptr) return false;
+    const int      kind = (int)plan[ 0 ];  // 0: the f32 contraction (on a copy, for quantised rows), 1 / 2: f16 / i8 rows as they are stored
     const bool     i8 = mcode_is_i8(mcode);
-    const bool     f16 = mcode_is_f16(mcode) || i8;  // "quantised storage": the contraction runs on an f32 copy
+    const bool     f16 = (mcode_is_f16(mcode) || i8) && !kind;  // quantised storage on the dequantised path: the contraction runs on an f32 copy
     const int      base_metric = mcode_base(mcode);
     const bool bits = base_metric == M_HAMMING || base_metric == M_COS_B1;  // popcount metrics: no MFMA contraction, no row norms
+    const bool exact_keys = plan[ 2 ] == 0;  // the pre-selection ranks on the exact-order distance itself (popcounts, native i8): nothing to certify
     if(bits || nb <= kSeedCols) fused = false;
-    const uint32_t fchunks = i8 ? chunks * 4 : f16 ? chunks * 2 : chunks;  // chunks of the f32 view fed to the contraction
+    const uint32_t fchunks = kind ? chunks : i8 ? chunks * 4 : f16 ? chunks * 2 : chunks;  // chunks of the rows fed to the contraction
     auto dequant = [&](const uint4 *src, size_t nchunks, uint4 *dst) { return i8 ? launch_dequant_i8(src, nchunks, dst, st) : launch_dequant_f16(src, nchunks, dst, st); };
+    auto norms = [&](const uint4 *rows, size_t n, float *out) {
+        return kind ? launch_row_norms_native(kind, base_metric, rows, (uint32_t)n, fchunks, (uint32_t *)out, st) : launch_row_norms(rows, (uint32_t)n, fchunks, out, st);
+    };
     char  *aux = nullptr;
     float *dd = nullptr;
     uint4 *fq = nullptr, *fb = nullptr;  // f32 copies of f16 rows (queries; one chunk of base rows)
@@ -2074,7 +2129,7 @@ try {
     }
     uint32_t *ccnt = cand ? (uint32_t *)((char *)cand + nqt_max * kCandCap * 8) : nullptr, *cover = ccnt ? ccnt + nqt_max : nullptr;
     if(ok && f16)
-        ok = hipMalloc((void **)&fq, nq * (size_t)fchunks * 16) == hipSuccess && hipMalloc((void **)&fb, CH * (size_t)fchunks * 16) == hipSuccess &&
+        ok = hipMalloc((void **)&fq, nq * (size_t)fchunks * 16) == hipSuccess && hipMalloc((void **)&fb, std::max<size_t>(plan[ 1 ], 16)) == hipSuccess &&
              dequant(d_q, nq * (size_t)chunks, fq) == hipSuccess;
     if(ok) {
         float    *qn = (float *)aux, *bn = qn + nq;
@@ -2082,8 +2137,8 @@ try {
         const uint4 *qv = f16 ? fq : d_q;
         const uint32_t ldd = (uint32_t)(fused ? kSeedCols : CH);
         ok = ok && hipMemsetAsync(best, 0xFF, nq * kk * 8, st) == hipSuccess;
-        if(!bits) ok = ok && launch_row_norms(qv, (uint32_t)nq, fchunks, qn, st) == hipSuccess;
-        if(!bits && !f16) ok = ok && launch_row_norms(d_base, (uint32_t)nb, fchunks, bn, st) == hipSuccess;
+        if(!bits) ok = ok && norms(qv, nq, qn) == hipSuccess;
+        if(!bits && !f16) ok = ok && norms(d_base, nb, bn) == hipSuccess;
         for(size_t c0 = 0; ok && c0 < nb; c0 += CH) {
             const size_t nc = std::min(CH, nb - c0);
             const uint4 *bv = d_base + c0 * chunks;
@@ -2099,15 +2154,26 @@ try {
                 if(plain) {
                     {
                         DenseTimer t(st, (uint32_t)nqt, (uint32_t)plain, false);
-                        ok = ok && launch_dense(base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv, (uint32_t)plain, fchunks, qn + q0, bn + c0, dd, ldd, st) == hipSuccess;
+                        if(kind)
+                            ok = ok && launch_dense_native(kind, base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv, (uint32_t)plain, fchunks, (const uint32_t *)(qn + q0),
+                                                           (const uint32_t *)(bn + c0), dd, ldd, st) == hipSuccess;
+                        else
+                            ok = ok && launch_dense(base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv, (uint32_t)plain, fchunks, qn + q0, bn + c0, dd, ldd, st) == hipSuccess;
+                        if(!bits) ++g_dense_kind[ kind ];
                     }
                     ok = ok && launch_select(dd, ldd, (uint32_t)nqt, (uint32_t)plain, (uint32_t)c0, best + q0 * kk, kk, st) == hipSuccess;
                 }
                 if(plain < nc) {
                     {
                         DenseTimer t(st, (uint32_t)nqt, (uint32_t)(nc - plain), true);
-                        ok = ok && launch_dense_topk(base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv + plain * fchunks, (uint32_t)(nc - plain), fchunks, qn + q0,
-                                                     bn + c0 + plain, best + q0 * kk, kk, cand, ccnt, (uint32_t)kCandCap, (uint32_t)(c0 + plain), st) == hipSuccess;
+                        if(kind)
+                            ok = ok && launch_dense_native_topk(kind, base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv + plain * fchunks, (uint32_t)(nc - plain), fchunks,
+                                                                (const uint32_t *)(qn + q0), (const uint32_t *)(bn + c0 + plain), best + q0 * kk, kk, cand, ccnt,
+                                                                (uint32_t)kCandCap, (uint32_t)(c0 + plain), st) == hipSuccess;
+                        else
+                            ok = ok && launch_dense_topk(base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv + plain * fchunks, (uint32_t)(nc - plain), fchunks, qn + q0,
+                                                         bn + c0 + plain, best + q0 * kk, kk, cand, ccnt, (uint32_t)kCandCap, (uint32_t)(c0 + plain), st) == hipSuccess;
+                        ++g_dense_kind[ kind ];
                     }
                     ok = ok && launch_select_candidates((uint32_t)nqt, best + q0 * kk, kk, cand, ccnt, (uint32_t)kCandCap, cover, st) == hipSuccess;
                 }
@@ -2117,11 +2183,11 @@ try {
         // the certificate: 4 bytes per query to the host, behind the synchronisation the call makes anyway.  The popcount metrics
         // rank on the exact-order distance itself (the same integer arithmetic): their pre-selection is exact by construction.
         uint32_t *flag = (uint32_t *)(best + nq * kk);
-        certified.assign(nq + 1, bits ? 1u : 0u);
+        certified.assign(nq + 1, exact_keys ? 1u : 0u);
         certified[ nq ] = 0;
-        if(!bits) {
+        if(!exact_keys) {
             ok = ok && hipMemsetAsync(flag + nq, 0, 4, st) == hipSuccess;
-            ok = ok && launch_certify(base_metric, best, kk, d_dists, (uint32_t)k, qn, (uint32_t)nq, bn, (uint32_t)nb, fchunks * 4, flag, st) == hipSuccess;
+            ok = ok && launch_certify(base_metric, best, kk, d_dists, (uint32_t)k, qn, (uint32_t)nq, bn, (uint32_t)nb, plan[ 2 ], flag, st) == hipSuccess;
             ok = ok && hipMemcpyAsync(certified.data(), flag, (nq + 1) * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
         }
         uint32_t over = 0;

@@ -280,6 +280,15 @@ hipError_t launch_dense(int metric, const uint4 *Q, uint32_t nq, const uint4 *B,
 hipError_t launch_dense_topk(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const float *qn,
                              const float *bn, const uint64_t *best, uint32_t kk, uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t c_base,
                              hipStream_t stream);
+// the same contraction on rows STORED as f16 (kind 1) or i8 (kind 2), on the MFMAs of that operand type (dense_native.hip).
+// Norms as 32-bit words: f16 -- the f32 |x|^2; i8 -- the exact int32 sum of squares (l2sq) or the bits of its IEEE root (cos).
+// The i8 outputs are the pair kernel's distances bit for bit.
+hipError_t launch_row_norms_native(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, uint32_t *out, hipStream_t stream);
+hipError_t launch_dense_native(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
+                               const uint32_t *bn, float *out, uint32_t ldo, hipStream_t stream);
+hipError_t launch_dense_native_topk(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
+                                    const uint32_t *bn, const uint64_t *best, uint32_t kk, uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t c_base,
+                                    hipStream_t stream);
 hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, const uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t *overflow,
                                     hipStream_t stream);
 hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t ncols, uint32_t c_base, uint64_t *best, uint32_t kk,
