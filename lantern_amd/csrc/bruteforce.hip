@@ -387,36 +387,37 @@ __global__ void __launch_bounds__(256, 2) k_dense_f32(const float *Q, uint32_t n
 #undef LGPU_FENCE
 }
 
-// hamming (COSB1: the cosine of the {0, 1} vectors, device_common.hpp M_COS_B1): 16 queries in LDS per workgroup, one base row per thread
-template <bool COSB1>
+// hamming (COSB1: the cosine of the {0, 1} vectors, device_common.hpp M_COS_B1): QB queries in LDS per workgroup, one base row per thread.
+// QB is launch_dense's: 16 while 16 rows fit 64 KB of LDS (rows of up to 1024 words), halved per doubling of the width beyond
+template <bool COSB1, int QB = 16>
 __global__ void __launch_bounds__(256) k_dense_ham(const uint32_t *Q, uint32_t nq, const uint32_t *B, uint32_t nb, uint32_t stride /* words */,
                                                    float *out, uint32_t ldo)
 {
-    extern __shared__ uint32_t qs[];  // [16][stride]
-    const uint32_t q0 = blockIdx.y * 16;
-    for(uint32_t i = threadIdx.x; i < 16 * stride; i += blockDim.x) {
+    extern __shared__ uint32_t qs[];  // [QB][stride]
+    const uint32_t q0 = blockIdx.y * QB;
+    for(uint32_t i = threadIdx.x; i < QB * stride; i += blockDim.x) {
         const uint32_t q = q0 + i / stride;
         qs[ i ] = q < nq ? Q[ (size_t)q * stride + i % stride ] : 0u;
     }
     __syncthreads();
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if(c >= nb) return;
-    uint32_t acc[ 16 ], qpop[ 16 ], bpop = 0;
+    uint32_t acc[ QB ], qpop[ QB ], bpop = 0;
 #pragma unroll
-    for(int j = 0; j < 16; ++j) acc[ j ] = qpop[ j ] = 0;
+    for(int j = 0; j < QB; ++j) acc[ j ] = qpop[ j ] = 0;
     const uint32_t *row = B + (size_t)c * stride;
     for(uint32_t w = 0; w < stride; ++w) {
         const uint32_t x = row[ w ];
         if(COSB1) bpop += __popc(x);
 #pragma unroll
-        for(int j = 0; j < 16; ++j) {
+        for(int j = 0; j < QB; ++j) {
             const uint32_t qw = qs[ j * stride + w ];
             acc[ j ] += COSB1 ? __popc(x & qw) : __popc(x ^ qw);
             if(COSB1) qpop[ j ] += __popc(qw);
         }
     }
 #pragma unroll
-    for(int j = 0; j < 16; ++j)
+    for(int j = 0; j < QB; ++j)
         if(q0 + j < nq) {
             float d = (float)acc[ j ];
             if(COSB1) {
@@ -796,11 +797,24 @@ hipError_t launch_dense(int metric, const uint4 *Q, uint32_t nq, const uint4 *B,
     if(nq == 0 || nb == 0) return hipSuccess;
     const uint32_t stride = chunks * 4;
     if(metric == M_HAMMING || metric == M_COS_B1) {
-        dim3 grid((nb + 255) / 256, (nq + 15) / 16);
-        if(metric == M_HAMMING)
-            hipLaunchKernelGGL(k_dense_ham<false>, grid, dim3(256), 16 * stride * 4, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, stride, out, ldo);
-        else
-            hipLaunchKernelGGL(k_dense_ham<true>, grid, dim3(256), 16 * stride * 4, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, stride, out, ldo);
+        // the query block stays within the 64 KB of dynamic LDS a launch may ask for without an opt-in: 16 queries of up to 1024 words,
+        // then 8, 4, 2, 1; a row that does not fit alone (more than 16384 words) is refused before anything is launched
+        constexpr uint32_t kHamLds = 64 * 1024;
+        if((uint64_t)stride * 4 > kHamLds) return hipErrorInvalidValue;
+#define LGPU_DENSE_HAM(QB)                                                                                                                       \
+    {                                                                                                                                            \
+        const dim3 grid((nb + 255) / 256, (nq + QB - 1) / QB);                                                                                   \
+        if(metric == M_HAMMING)                                                                                                                  \
+            hipLaunchKernelGGL((k_dense_ham<false, QB>), grid, dim3(256), QB * stride * 4, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, stride, out, ldo); \
+        else                                                                                                                                     \
+            hipLaunchKernelGGL((k_dense_ham<true, QB>), grid, dim3(256), QB * stride * 4, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, stride, out, ldo);  \
+    }
+        if(16 * stride * 4 <= kHamLds) LGPU_DENSE_HAM(16)
+        else if(8 * stride * 4 <= kHamLds) LGPU_DENSE_HAM(8)
+        else if(4 * stride * 4 <= kHamLds) LGPU_DENSE_HAM(4)
+        else if(2 * stride * 4 <= kHamLds) LGPU_DENSE_HAM(2)
+        else LGPU_DENSE_HAM(1)
+#undef LGPU_DENSE_HAM
         return hipGetLastError();
     }
     const uint32_t tiles = ((nq + BM - 1) / BM) * ((nb + BN - 1) / BN);

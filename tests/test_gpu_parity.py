@@ -37,8 +37,6 @@ def rand_rows(rng, n, d, metric):
 @pytest.mark.parametrize("d", [1, 3, 4, 17, 63, 64, 100, 128, 255, 256, 768, 1536, 2000])
 def test_pair_distance_bit_exact_and_within_tolerance(capi, oracle, metric, d):
     rng = np.random.default_rng(d)
-    if metric == "hamming" and d > 256:
-        pytest.skip("hamming rows are at most 2000*32 bits in Lantern; 256 words covers the group sizes")
     a, b = rand_rows(rng, 1, d, metric)[0], rand_rows(rng, 1, d, metric)[0]
     got = capi.distance(a, b, metric)
     assert got == oracle.distance(a, b, metric, oracle.SUM_WAVE64)
@@ -63,6 +61,10 @@ def test_golden_operator_cases_on_device(capi, golden):
     assert capi.cos_dist([0, 0, 1], [0, 0, 0]) == 1.0
     with pytest.raises(capi.LanternGpuError, match="expected equally sized arrays but got arrays with dimensions 2 and 3"):
         capi.cos_dist([1, 1], [0, 1, 0])
+    # integer arrays at Lantern's cap of 2000 elements: one 32-bit word each, 500 chunks
+    rng = np.random.default_rng(2000)
+    a, b = rng.integers(-2 ** 31, 2 ** 31, 2000).astype(np.int32), rng.integers(-2 ** 31, 2 ** 31, 2000).astype(np.int32)
+    assert capi.hamming_dist(a, b) == int(np.unpackbits((a ^ b).view(np.uint8)).sum(dtype=np.int64))
 
 
 @pytest.mark.parametrize("metric", ["l2sq", "cos", "hamming"])
@@ -943,7 +945,8 @@ def test_device_reproduces_the_committed_fixture(capi):
 BLOCK_BOUNDARY_CHUNKS = [1, 7, 8, 9, 15, 16, 17, 23, 24, 25, 31,            # G = 8:  1 .. 4 steps
                          32, 33, 47, 48, 49, 63,                            # G = 16: 2 .. 4 steps
                          64, 65, 95, 96, 97, 127,                           # G = 32: 2 .. 4 steps
-                         128, 129, 191, 192, 193, 255, 256, 257, 383, 385]  # G = 64: 2 .. 7 steps
+                         128, 129, 191, 192, 193, 255, 256, 257, 383, 385,  # G = 64: 2 .. 7 steps
+                         447, 448, 449, 500]                                # the eighth step, up to Lantern's cap (d = 2000; 2000 words)
 
 
 @pytest.mark.parametrize("metric", ["l2sq", "cos", "hamming"])
