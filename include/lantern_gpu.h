@@ -760,6 +760,60 @@ LANTERN_GPU_EXPORT void lantern_gpu_spec_profile(usearch_index_t, int on, unsign
 LANTERN_GPU_EXPORT uint64_t lantern_gpu_graph_checksum(usearch_index_t, usearch_error_t *);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Deleting rows: tombstones, then unlinking them from the graph.              */
+/* PARITY UNPINNED BY THE REFERENCE: its VACUUM resets the labels of the dead rows to 0         */
+/* (delete.c:15-72, INVALID_ELEMENT_LABEL: hnsw.h:40), warns "deletes are currently not         */
+/* implemented ... No memory will be reclaimed" (delete.c:24-25) and leaves the graph as it is;  */
+/* scans drop label 0 after the search returned it (scan.c:296-300; hnsw_delete.out:28-55).      */
+/* Beyond the label reset what follows is a definition of this library.                          */
+/* ------------------------------------------------------------------------------------------ */
+/* ldb_ambulkdelete for the resident copy.  After the flush every search performs, every slot whose label is in labels[0..n) gets
+ * label 0.  The list may be in any order and may hold duplicates, labels no slot carries and 0: none of those counts.  *removed
+ * (may be NULL) = the slots that changed from non-zero to zero; n == 0 is a no-op.  The list is sorted on the device and searched
+ * once per slot.  The call is ordered against launches in flight as an insertion batch is: it waits for the searches in flight, and
+ * searches on other streams wait for it.  Every index kind and form is served (f32, f16, i8, b1, pq expanded and compact,
+ * page-attached mirrors): ONLY labels change -- graph, rows, screen rows and the size stay, so a tombstoned row is still evaluated,
+ * expanded and returned (with label 0) until lantern_gpu_unlink_deleted.  Export, usearch_save* and lantern_gpu_save_stream write
+ * label 0 and a load brings it back.  A filter built with LANTERN_GPU_FILTER_SKIP_DELETED is a snapshot of the labels at its build. */
+LANTERN_GPU_EXPORT void lantern_gpu_remove_labels(usearch_index_t, const usearch_label_t *labels, size_t n, uint64_t *removed,
+                                                  usearch_error_t *);
+/* the slots whose label is 0, however they got it (this call, a file, a page, an import) */
+LANTERN_GPU_EXPORT size_t lantern_gpu_deleted_count(usearch_index_t, usearch_error_t *);
+/* lantern_gpu_unlink_deleted.  Notation: G the graph after the flush; T the slots with label 0; cap(l) = 2M at level 0 and M above;
+ * cut(l) = max(256, 8 cap(l)).
+ *  - If T is empty, or no live slot remains, nothing changes and every stat is 0.
+ *  - Otherwise, for every live node p and every level l <= level(p), with L = p's list at l in stored order:
+ *      if L has no entry in T it stays byte for byte; else
+ *      keep   = the live entries of L in stored order;
+ *      offers = walking L in stored order, every entry t in T contributes the live entries of G's list of t at level l, in stored
+ *               order, skipping p, anything in keep and anything offered before; the walk stops when offers holds cut(l) slots;
+ *      the new list starts as keep, compacted with no holes; every offer c, in that order, is then applied as ONE reverse-link
+ *      request (close p, level l, new_slot c, d = metric(c, p)) exactly as an insertion's reverse link is (usearch
+ *      reconnect_neighbor_nodes_): appended while the list has room, otherwise the cap(l) + 1 candidates are re-pruned by the
+ *      neighbour-selection heuristic in (distance, per-centre tie order) order.
+ *  - All reads are from G: the result does not depend on the order in which lists are processed.
+ *  - Afterwards every list of every t in T is empty at every level.
+ *  - If the entry node is in T, the new entry is the live node of the highest level, the lowest slot among those, and max_level
+ *    becomes that level.
+ *  - Rows, labels, levels, the size, slots, upper blocks, the screen copy and norms do not move: filters, cursors' `seen` sets and
+ *    page maps stay valid.  NO MEMORY IS RECLAIMED (that needs slot reuse).  A second call changes nothing and reports zeros.
+ *  - It does not equal a rebuild of the live rows (DESIGN.md 4.11 says by how much).
+ * The call is a graph mutation, ordered as an insertion batch.  The result is a pure function of the graph: the replicas of a
+ * sharded build each call it and stay identical.  Refused: a page-attached index (its lists would have to go back through
+ * retriever_mut) and a compact pq index (expand it first). */
+typedef struct lantern_gpu_unlink_stats
+{
+    uint64_t tombstones_unlinked; /* slots of T that still had a neighbour of their own */
+    uint64_t lists_repaired;      /* (p, l) lists that held an entry of T */
+    uint64_t offers;              /* reverse-link requests made */
+    uint64_t lists_cut;           /* lists whose offers reached cut(l) */
+    uint64_t request_evals;       /* pair evaluations of the request kernel (one per offer) */
+    uint64_t reprune_evals;       /* pair evaluations of the re-prunes, as the DEVICE counts them (lantern_gpu_counters: >= the sequential count) */
+    uint64_t entry_moved;         /* 1 if the entry node was in T */
+} lantern_gpu_unlink_stats;
+LANTERN_GPU_EXPORT void lantern_gpu_unlink_deleted(usearch_index_t, lantern_gpu_unlink_stats *out /* or NULL */, usearch_error_t *);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Work-sharded index build over the GPUs of one node (the reference's     */
 /* own parallel build is a thread pool on one shared index, server.rs:328-359).  One process or  */
 /* thread per GPU, each with its own usearch_index_t replica.  lantern_gpu_add_sharded is a       */

@@ -77,6 +77,11 @@ class BuildProfile(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("walk_ms", "connect_ms", "group_ms", "revlink_ms", "exchange_ms")] + [("batches", C.c_uint64)]
 
 
+class UnlinkStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("tombstones_unlinked", "lists_repaired", "offers", "lists_cut", "request_evals", "reprune_evals",
+                                          "entry_moved")]
+
+
 EXPORTS = [
     "usearch_init", "usearch_free", "usearch_reserve", "usearch_size", "usearch_capacity", "usearch_dimensions",
     "usearch_add", "usearch_add_external", "usearch_search_ef", "lantern_gpu_cursor_open", "lantern_gpu_cursor_search",
@@ -127,6 +132,8 @@ EXPORTS = [
     "lantern_gpu_last_search_cells",
     # diagnostics of the int8 screen (lantern_gpu.h lantern_gpu_export_screen)
     "lantern_gpu_export_screen", "lantern_gpu_screen_probe",
+    # deleting rows (lantern_gpu.h "Deleting rows")
+    "lantern_gpu_remove_labels", "lantern_gpu_deleted_count", "lantern_gpu_unlink_deleted",
 ]
 # lantern_gpu_query_params: one row {k, ef, skip, reserved} per query (ef 0 = the index's default; reserved must be 0)
 QUERY_PARAMS = np.dtype([("k", np.uint32), ("ef", np.uint32), ("skip", np.uint32), ("reserved", np.uint32)])
@@ -363,6 +370,9 @@ def lib() -> C.CDLL:
         "lantern_scan_server_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "lantern_scan_client_set_filter": (sz, [vp, vp, sz, u32, err]),
         "lantern_scan_client_clear_filter": (None, [vp, err]),
+        "lantern_gpu_remove_labels": (None, [vp, vp, sz, C.POINTER(u64), err]),
+        "lantern_gpu_deleted_count": (sz, [vp, err]),
+        "lantern_gpu_unlink_deleted": (None, [vp, C.POINTER(UnlinkStats), err]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = the library does not export what the header declares
@@ -695,6 +705,24 @@ class GpuIndex:
 
     def checksum(self) -> int:
         return int(_call("lantern_gpu_graph_checksum", self.h))
+
+    def remove_labels(self, labels) -> int:
+        """lantern_gpu_remove_labels: the slots carrying one of `labels` get label 0; returns how many changed."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint64).reshape(-1)
+        removed = C.c_uint64()
+        _call("lantern_gpu_remove_labels", self.h, _ptr(lab) if lab.size else None, lab.size, C.byref(removed))
+        return int(removed.value)
+
+    @property
+    def deleted_count(self) -> int:
+        """Slots whose label is 0, however they got it."""
+        return int(_call("lantern_gpu_deleted_count", self.h))
+
+    def unlink_deleted(self) -> dict:
+        """lantern_gpu_unlink_deleted: take the tombstones out of the graph; returns the call's stats."""
+        st = UnlinkStats()
+        _call("lantern_gpu_unlink_deleted", self.h, C.byref(st))
+        return {n: int(getattr(st, n)) for n, _ in UnlinkStats._fields_}
 
     def search(self, query, k, ef=0, streaming=False):
         """usearch_search_ef: (labels, distances) of length <= k."""

@@ -109,12 +109,13 @@ enum TotalsSlot : int
     kTotSpecProfile = 16,   // [kTotSpecProfileWords] lantern_gpu_spec_profile
     kTotSearchScreen = 48,  // [2] the searches' screen: row evaluations, of which read the f32 row
     kTotInsertScreen = 50,  // [2] k_insert's screen: rows tested, rows rejected
+    kTotUnlink = 52,        // [2] lantern_gpu_unlink_deleted's reverse links: pair evaluations, re-prunes (unlink.hip; not a build counter)
     kTotalsWords = 64       // the block's size
 };
 constexpr int kTotPhaseProfileWords = 8, kTotSpecProfileWords = 32;
 static_assert(kTotSearch + 2 <= kTotInsert && kTotInsert + 2 <= kTotConnect && kTotConnect + 1 <= kTotRevlink && kTotRevlink + 2 <= kTotPhaseProfile &&
                   kTotPhaseProfile + kTotPhaseProfileWords <= kTotSpecProfile && kTotSpecProfile + kTotSpecProfileWords <= kTotSearchScreen &&
-                  kTotSearchScreen + 2 <= kTotInsertScreen && kTotInsertScreen + 2 <= kTotalsWords,
+                  kTotSearchScreen + 2 <= kTotInsertScreen && kTotInsertScreen + 2 <= kTotUnlink && kTotUnlink + 2 <= kTotalsWords,
               "the ranges of Index::d_totals are disjoint and inside the block");
 // k_insert's screened launches (view.screen set) add the rows they put to the int8 screen test, and the rows it rejected, to
 // kTotInsertScreen, reached from InsertArgs::totals: totals[kInsertScreenTotals], [+ 1] (lantern_gpu_insert_screen_stats).

@@ -1197,9 +1197,11 @@ LANTERN_ABI_CATCH(e)
 static size_t client_filter(lantern_scan_client_t *c, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e)
 {
     if(e) *e = nullptr;
-    if(!c || c->fd < 0) { if(e) *e = "lantern_gpu: the scan client is not connected"; return 0; }
+    // the checks of the arguments alone come first: a message that is refused whatever the connection's state is refused without the
+    // handle being read
     if(n && !labels) { if(e) *e = "lantern_gpu: null label array"; return 0; }
     if(n > kMaxFilterLabels) { if(e) *e = "lantern_gpu: too many labels for one filter message (at most 2^24)"; return 0; }
+    if(!c || c->fd < 0) { if(e) *e = "lantern_gpu: the scan client is not connected"; return 0; }
     auto fail = [&](const char *msg) {
         c->err = msg;
         ::close(c->fd);
