@@ -572,6 +572,24 @@ LANTERN_GPU_EXPORT void lantern_gpu_dense_kind_stats(uint64_t launches[3]);
  *      exact-order distance itself and is certified by construction: popcount metrics, native i8); [3] K steps (128 bytes per
  *      row each) per output tile (0: no MFMA contraction).  Returns NULL, or why the input is refused. */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_dense(const int64_t in[4], uint32_t out[4]);
+/* Everything an exact k-NN call (lantern_gpu_exact_search, _assign_to_clusters, PQ encoding) decides before it touches the device,
+ * without one (a pure function; lantern_gpu_plan_dense shows four of its numbers): the call plans with this function and then
+ * launches what the plan lists.
+ * in[7]: [0] metric code (as lantern_gpu_plan_dense)  [1] 16-byte chunks per stored row  [2] base rows  [3] queries  [4] k (1..240)
+ *   [5] LANTERN_GPU_DENSE_NATIVE (-1: unset)  [6] LANTERN_GPU_DENSE_FUSED (-1: unset)
+ * out[34]: [0] operand kind 0 / 1 / 2 (f32, f16, i8)  [1] the rows are dequantised to f32 for the contraction: 0 no, 1 from f16, 2 from i8
+ *   [2] chunks of a row as the contraction reads it  [3] a popcount metric  [4] the pre-selection's keys are exact: nothing to certify
+ *   [5] the dims the certificate is told  [6] K steps per output tile  [7] kk = k + 16 survivors per query  [8] base rows per launch
+ *   [9] queries per launch  [10] seed columns  [11] candidate keys per query  [12] fused, after the rule: asked for, not a popcount
+ *   metric, more base rows than seed columns  [13] leading dimension of the distance matrix
+ *   then ten byte counts as (low word, high word): [14] the block of norms, best lists and flags  [16] the distance matrix
+ *   [18] the candidate lists (0 unless fused)  [20] the queries' f32 copy  [22] one chunk of base rows' f32 copy (0: no copy)
+ *   and offsets: [24] query norms, [26] base norms, [28] best lists (8-byte aligned), [30] flags inside [14]; [32] counters inside [18]
+ * steps: the contraction launches in order (chunk of base rows by chunk, query tile by query tile, plain before fused), up to cap
+ *   of them: [0] queries  [1] base rows  [2] 1: the fused epilogue (folded in by k_select over the candidate lists), 0: the matrix
+ *   (k_select over its rows)  [3] the first base row.  *n_steps: how many there are, whatever cap is.
+ * Returns NULL, or why the input is refused (a null array, a field out of range, rows that do not fit 32 bits). */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_exact_knn(const int64_t in[7], uint32_t out[34], uint32_t steps[][4], size_t cap, size_t *n_steps);
 
 /* Diagnostic for the measurement harness: the memory objects every query of a launch asks for, in order (rows evaluated, adjacency
  * lists read) -- the input of the cache model behind bench.py's roofline.frac_dram_model (lantern_amd/tools/cache_model.c).

@@ -91,7 +91,7 @@ EXPORTS = [
     "lantern_gpu_version", "lantern_gpu_device_count",
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
-    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_distance_gather",
+    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
     "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
@@ -235,6 +235,7 @@ def lib() -> C.CDLL:
         "lantern_gpu_exact_knn_stats": (None, [C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "lantern_gpu_dense_kind_stats": (None, [vp]),
         "lantern_gpu_plan_dense": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_plan_exact_knn": (C.c_char_p, [vp, vp, vp, sz, vp]),
         "lantern_gpu_distance_gather": (None, [vp, vp, vp, sz, vp, err]),
         "lantern_gpu_spec_profile": (None, [vp, i32, vp, err]),
         "lantern_gpu_search_unique_rows": (None, [vp, i32, C.POINTER(u64), err]),
@@ -491,6 +492,31 @@ def plan_dense(mcode, chunks, rows, native=-1):
     if why is not None:
         raise LanternGpuError(why.decode())
     return {"kind": int(out[0]), "copy_bytes": int(out[1]), "dims": int(out[2]), "k_steps": int(out[3])}
+
+
+# lantern_gpu_plan_exact_knn's out[], in order (include/lantern_gpu.h): 32-bit fields, then byte counts and offsets as (low, high)
+PLAN_EXACT_KNN_WORDS = ("kind", "copy", "fchunks", "bits", "exact_keys", "dims", "k_steps", "kk", "chunk_rows", "qtile", "seed_cols", "cand_cap", "fused", "ldd")
+PLAN_EXACT_KNN_SIZES = ("aux_bytes", "dd_bytes", "cand_bytes", "fq_bytes", "fb_bytes", "qn_off", "bn_off", "best_off", "flag_off", "cnt_off")
+
+
+def plan_exact_knn(mcode, chunks, nb, nq, k, native=-1, fused=-1):
+    """lantern_gpu_plan_exact_knn: what an exact k-NN of nq queries over nb stored rows decides before it touches the device (host
+    arithmetic, no device): {PLAN_EXACT_KNN_WORDS and _SIZES name: value, "n_steps", "steps": [(queries, base rows, fused, first base row), ...]},
+    the contraction launches in order (the first 2^20 of them).  native / fused = the values of LANTERN_GPU_DENSE_NATIVE / _FUSED (-1: unset)."""
+    pin = np.array([mcode, chunks, nb, nq, k, native, fused], np.int64)
+    out, count = np.zeros(len(PLAN_EXACT_KNN_WORDS) + 2 * len(PLAN_EXACT_KNN_SIZES), np.uint32), C.c_size_t(0)
+    why = lib().lantern_gpu_plan_exact_knn(_ptr(pin), _ptr(out), None, 0, C.byref(count))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    cap = min(count.value, 1 << 20)  # ("n_steps" says how many there are)
+    steps = np.zeros((max(cap, 1), 4), np.uint32)
+    lib().lantern_gpu_plan_exact_knn(_ptr(pin), _ptr(out), _ptr(steps), cap, C.byref(count))
+    plan = dict(zip(PLAN_EXACT_KNN_WORDS, (int(x) for x in out)))
+    pairs = out[len(PLAN_EXACT_KNN_WORDS):].astype(np.uint64)
+    plan.update(zip(PLAN_EXACT_KNN_SIZES, (int(lo) | int(hi) << 32 for lo, hi in zip(pairs[0::2], pairs[1::2]))))
+    plan["n_steps"] = int(count.value)
+    plan["steps"] = [(int(s[0]), int(s[1]), bool(s[2]), int(s[3])) for s in steps[:cap]]
+    return plan
 
 
 def l2sq_dist(a, b) -> float:

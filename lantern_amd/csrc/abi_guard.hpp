@@ -21,6 +21,7 @@ inline void abi_fail(std::nullptr_t, const char *) {}
 constexpr const char *kAbiOom = "lantern_gpu: out of host memory";
 constexpr const char *kAbiTooLarge = "lantern_gpu: requested size exceeds what can be allocated";
 constexpr const char *kAbiException = "lantern_gpu: internal error (C++ exception stopped at the C boundary)";
+constexpr const char *kNoDevice = "lantern_gpu: no HIP device available (this library has no CPU fallback)";
 constexpr const char *kStrideMismatch = "lantern_gpu: the query row stride does not match the index's stored row stride (lantern_gpu_row_bytes)";
 constexpr const char *kKindMismatch = "lantern_gpu: scalar kind of the queries does not match the index";
 

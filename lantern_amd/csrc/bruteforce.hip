@@ -388,7 +388,7 @@ __global__ void __launch_bounds__(256, 2) k_dense_f32(const float *Q, uint32_t n
 }
 
 // hamming (COSB1: the cosine of the {0, 1} vectors, device_common.hpp M_COS_B1): QB queries in LDS per workgroup, one base row per thread.
-// QB is launch_dense's: 16 while 16 rows fit 64 KB of LDS (rows of up to 1024 words), halved per doubling of the width beyond
+// QB is launch_contraction's: 16 while 16 rows fit 64 KB of LDS (rows of up to 1024 words), halved per doubling of the width beyond
 template <bool COSB1, int QB = 16>
 __global__ void __launch_bounds__(256) k_dense_ham(const uint32_t *Q, uint32_t nq, const uint32_t *B, uint32_t nb, uint32_t stride /* words */,
                                                    float *out, uint32_t ldo)
@@ -762,17 +762,18 @@ hipError_t launch_dequant_f16(const uint4 *src, size_t nchunks, uint4 *dst, hipS
 }
 
 // ---------------------------------------------------------------------------------------------------
-hipError_t launch_row_norms(const uint4 *rows, uint32_t n, uint32_t chunks, float *out, hipStream_t stream)
+hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream)
 {
+    if(kind != 0) return launch_norms_native(kind, metric, rows, n, chunks, (uint32_t *)out, stream);
     if(n == 0) return hipSuccess;
     const int G_ = group_lanes_for(chunks);
     uint32_t  blocks = (uint32_t)(((uint64_t)n * G_ + 255) / 256);
     if(blocks > 16384) blocks = 16384;
     switch(G_) {
-        case 64: hipLaunchKernelGGL((k_row_norms<64>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, out); break;
-        case 32: hipLaunchKernelGGL((k_row_norms<32>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, out); break;
-        case 16: hipLaunchKernelGGL((k_row_norms<16>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, out); break;
-        default: hipLaunchKernelGGL((k_row_norms<8>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, out);
+        case 64: hipLaunchKernelGGL((k_row_norms<64>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, (float *)out); break;
+        case 32: hipLaunchKernelGGL((k_row_norms<32>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, (float *)out); break;
+        case 16: hipLaunchKernelGGL((k_row_norms<16>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, (float *)out); break;
+        default: hipLaunchKernelGGL((k_row_norms<8>), dim3(blocks), dim3(256), 0, stream, rows, n, chunks, (float *)out);
     }
     return hipGetLastError();
 }
@@ -791,11 +792,15 @@ uint32_t dense_grid(uint32_t tiles)
     return tiles < g ? tiles : g;
 }
 
-hipError_t launch_dense(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const float *qn,
-                        const float *bn, float *out, uint32_t ldo, hipStream_t stream)
+// the f32 / bit rows' half of launch_contraction.  FUSED: the top-kk filter in the tile epilogue (l2sq / cos): candidates go to
+// tk.cand / tk.cnt, see k_dense_f32
+template <bool FUSED>
+static hipError_t launch_f32(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk &tk, hipStream_t stream)
 {
+    const uint32_t nq = o.nq, nb = o.nb, stride = o.chunks * 4;
+    const int      metric = o.metric;
     if(nq == 0 || nb == 0) return hipSuccess;
-    const uint32_t stride = chunks * 4;
+    if(FUSED && metric != M_L2SQ && metric != M_COS) return hipErrorInvalidValue;
     if(metric == M_HAMMING || metric == M_COS_B1) {
         // the query block stays within the 64 KB of dynamic LDS a launch may ask for without an opt-in: 16 queries of up to 1024 words,
         // then 8, 4, 2, 1; a row that does not fit alone (more than 16384 words) is refused before anything is launched
@@ -805,9 +810,9 @@ hipError_t launch_dense(int metric, const uint4 *Q, uint32_t nq, const uint4 *B,
     {                                                                                                                                            \
         const dim3 grid((nb + 255) / 256, (nq + QB - 1) / QB);                                                                                   \
         if(metric == M_HAMMING)                                                                                                                  \
-            hipLaunchKernelGGL((k_dense_ham<false, QB>), grid, dim3(256), QB * stride * 4, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, stride, out, ldo); \
+            hipLaunchKernelGGL((k_dense_ham<false, QB>), grid, dim3(256), QB * stride * 4, stream, (const uint32_t *)o.Q, nq, (const uint32_t *)o.B, nb, stride, out, ldo); \
         else                                                                                                                                     \
-            hipLaunchKernelGGL((k_dense_ham<true, QB>), grid, dim3(256), QB * stride * 4, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, stride, out, ldo);  \
+            hipLaunchKernelGGL((k_dense_ham<true, QB>), grid, dim3(256), QB * stride * 4, stream, (const uint32_t *)o.Q, nq, (const uint32_t *)o.B, nb, stride, out, ldo);  \
     }
         if(16 * stride * 4 <= kHamLds) LGPU_DENSE_HAM(16)
         else if(8 * stride * 4 <= kHamLds) LGPU_DENSE_HAM(8)
@@ -818,33 +823,20 @@ hipError_t launch_dense(int metric, const uint4 *Q, uint32_t nq, const uint4 *B,
         return hipGetLastError();
     }
     const uint32_t tiles = ((nq + BM - 1) / BM) * ((nb + BN - 1) / BN);
-    const DenseTopk none = { nullptr, 0, nullptr, nullptr, 0, 0 };
     if(metric == M_L2SQ)
-        hipLaunchKernelGGL((k_dense_f32<M_L2SQ>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const float *)Q, nq, (const float *)B, nb, stride, qn, bn,
-                           out, ldo, none);
+        hipLaunchKernelGGL((k_dense_f32<M_L2SQ, FUSED>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const float *)o.Q, nq, (const float *)o.B, nb, stride,
+                           (const float *)o.qn, (const float *)o.bn, out, ldo, tk);
     else
-        hipLaunchKernelGGL((k_dense_f32<M_COS>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const float *)Q, nq, (const float *)B, nb, stride, qn, bn,
-                           out, ldo, none);
+        hipLaunchKernelGGL((k_dense_f32<M_COS, FUSED>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const float *)o.Q, nq, (const float *)o.B, nb, stride,
+                           (const float *)o.qn, (const float *)o.bn, out, ldo, tk);
     return hipGetLastError();
 }
 
-// the contraction with the top-kk filter fused into its epilogue (l2sq / cos): candidates go to cand / cnt, see k_dense_f32
-hipError_t launch_dense_topk(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const float *qn,
-                             const float *bn, const uint64_t *best, uint32_t kk, uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t c_base,
-                             hipStream_t stream)
+hipError_t launch_contraction(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream)
 {
-    if(nq == 0 || nb == 0) return hipSuccess;
-    if(metric != M_L2SQ && metric != M_COS) return hipErrorInvalidValue;
-    const uint32_t  stride = chunks * 4;
-    const uint32_t  tiles = ((nq + BM - 1) / BM) * ((nb + BN - 1) / BN);
-    const DenseTopk tk = { best, kk, cand, cnt, cap, c_base };
-    if(metric == M_L2SQ)
-        hipLaunchKernelGGL((k_dense_f32<M_L2SQ, true>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const float *)Q, nq, (const float *)B, nb, stride, qn,
-                           bn, (float *)nullptr, 0u, tk);
-    else
-        hipLaunchKernelGGL((k_dense_f32<M_COS, true>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const float *)Q, nq, (const float *)B, nb, stride, qn,
-                           bn, (float *)nullptr, 0u, tk);
-    return hipGetLastError();
+    if(o.kind != 0) return launch_contraction_native(o, out, ldo, topk, stream);
+    const DenseTopk none = { nullptr, 0, nullptr, nullptr, 0, 0 };
+    return !topk ? launch_f32<false>(o, out, ldo, none, stream) : launch_f32<true>(o, (float *)nullptr, 0u, *topk, stream);
 }
 
 hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t ncols, uint32_t c_base, uint64_t *best, uint32_t kk,

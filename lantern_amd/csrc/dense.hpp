@@ -1,0 +1,61 @@
+// dense.hpp -- the dense path's host side (dense.cpp): the exact k-NN as a pure plan and one run of it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace lgpu {
+
+// the environment switches of the exact k-NN, as values (dense_env reads both on every call -- in-process tests set them between calls)
+struct DenseEnv
+{
+    int native = -1;  // LANTERN_GPU_DENSE_NATIVE: 0 -- f16 / i8 rows are contracted on an f32 copy, else as they are stored; -1: absent (kDenseNativeDefault)
+    int fused = -1;   // LANTERN_GPU_DENSE_FUSED: 0 -- always the unfused path (A/B, tests); -1: absent
+};
+DenseEnv dense_env();
+
+// one contraction launch of an exact k-NN: queries [q0, q0 + nqt) against base rows [col0, col0 + cols).  fused == 0: the matrix goes
+// to dd and launch_select folds it into the queries' best lists; 1: the fused epilogue, then launch_select_candidates
+struct KnnStep
+{
+    uint32_t q0, nqt, col0, cols, fused;
+};
+// Everything an exact k-NN call decides before it touches the device; lantern_gpu_plan_exact_knn shows it without one.
+struct ExactKnnPlan
+{
+    // the call's own numbers
+    int      mcode = 0;
+    uint32_t chunks = 0, k = 0;
+    size_t   nb = 0, nq = 0;
+    // the operands (lantern_gpu_plan_dense projects these)
+    int      kind = 0;            // DenseOperands::kind: 0 f32 (or bit) rows, 1 / 2 f16 / i8 rows as stored
+    int      copy = 0;            // the rows are dequantised to f32 for the contraction: 0 no, 1 from f16, 2 from i8
+    uint32_t fchunks = 0;         // 16-byte chunks of a row as the contraction reads it
+    bool     bits = false;        // a popcount metric: no MFMA contraction, no norms, never fused
+    bool     exact_keys = false;  // the pre-selection ranks on the exact-order distance itself: nothing to certify
+    uint32_t dims = 0;            // the dims the certificate is told (0 iff exact_keys)
+    uint32_t k_steps = 0;         // K steps (128 bytes of a row each) per output tile
+    size_t   fb_bytes = 0;        // the f32 copy of one chunk of base rows (0: no copy)
+    // the launches and their buffers
+    uint32_t kk = 0;                                     // survivors per query, k + 16: re-ranked in exact order, then cut to k
+    uint32_t chunk_rows = 0, qtile = 0, seed_cols = 0;    // base rows and queries per launch; the columns that give every query a radius
+    uint32_t cand_cap = 0;                                // fused: candidate keys per query
+    bool     fused = false;                               // asked for, not a popcount metric, and more than seed_cols rows
+    uint32_t ldd = 0;                                     // leading dimension of dd
+    size_t   aux_bytes = 0, dd_bytes = 0, cand_bytes = 0, fq_bytes = 0;  // the pooled blocks (cand: 0 unless fused); the queries' f32 copy
+    size_t   qn_off = 0, bn_off = 0, best_off = 0, flag_off = 0;         // inside aux: norms, the best lists (8-byte aligned), the certificate's flags
+    size_t   cnt_off = 0, over_off = 0;                                  // inside cand, behind the lists: their counters, the overflow word
+    // the ordered contraction steps: chunk-major, query-tile-minor, plain before fused; computed by index, so a plan allocates nothing
+    size_t  n_steps = 0;
+    KnnStep step(size_t i) const;
+};
+// pure: no HIP runtime call, no getenv.  native / fused: DenseEnv's.  NULL, or why the call is refused (static text)
+const char *plan_exact_knn(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, int native, int fused, ExactKnnPlan &p);
+
+// Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row).
+// Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].
+bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k, uint32_t *d_slots,
+                      float *d_dists, hipStream_t st);
+
+}  // namespace lgpu

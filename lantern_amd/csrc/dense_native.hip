@@ -401,7 +401,7 @@ __global__ void __launch_bounds__(256, 2) k_dense_native(const uint32_t *Q, uint
 }
 
 // ---------------------------------------------------------------------------------------------------
-hipError_t launch_row_norms_native(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, uint32_t *out, hipStream_t stream)
+hipError_t launch_norms_native(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, uint32_t *out, hipStream_t stream)
 {
     if(n == 0) return hipSuccess;
     if(kind != KIND_F16 && kind != KIND_I8) return hipErrorInvalidValue;
@@ -423,40 +423,30 @@ hipError_t launch_row_norms_native(int kind, int metric, const uint4 *rows, uint
 }
 
 template <bool FUSED>
-static hipError_t launch_native(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
-                                const uint32_t *bn, float *out, uint32_t ldo, const DenseTopk &tk, hipStream_t stream)
+static hipError_t launch_native(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk &tk, hipStream_t stream)
 {
-    if(nq == 0 || nb == 0) return hipSuccess;
-    if((metric != M_L2SQ && metric != M_COS) || (kind != KIND_F16 && kind != KIND_I8)) return hipErrorInvalidValue;
-    const uint32_t stride = chunks * 4;
-    const uint32_t tiles = ((nq + BM - 1) / BM) * ((nb + BN - 1) / BN);
+    if(o.nq == 0 || o.nb == 0) return hipSuccess;
+    if((o.metric != M_L2SQ && o.metric != M_COS) || (o.kind != KIND_F16 && o.kind != KIND_I8)) return hipErrorInvalidValue;
+    const uint32_t stride = o.chunks * 4;
+    const uint32_t tiles = ((o.nq + BM - 1) / BM) * ((o.nb + BN - 1) / BN);
 #define DN(KK, MM)                                                                                                                          \
-    hipLaunchKernelGGL((k_dense_native<KK, MM, FUSED>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const uint32_t *)Q, nq, (const uint32_t *)B, nb, \
-                       stride, qn, bn, out, ldo, tk)
-    if(kind == KIND_F16) {
-        if(metric == M_L2SQ) DN(KIND_F16, M_L2SQ);
+    hipLaunchKernelGGL((k_dense_native<KK, MM, FUSED>), dim3(dense_grid(tiles)), dim3(256), 0, stream, (const uint32_t *)o.Q, o.nq, (const uint32_t *)o.B, \
+                       o.nb, stride, (const uint32_t *)o.qn, (const uint32_t *)o.bn, out, ldo, tk)
+    if(o.kind == KIND_F16) {
+        if(o.metric == M_L2SQ) DN(KIND_F16, M_L2SQ);
         else DN(KIND_F16, M_COS);
     } else {
-        if(metric == M_L2SQ) DN(KIND_I8, M_L2SQ);
+        if(o.metric == M_L2SQ) DN(KIND_I8, M_L2SQ);
         else DN(KIND_I8, M_COS);
     }
 #undef DN
     return hipGetLastError();
 }
 
-hipError_t launch_dense_native(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
-                               const uint32_t *bn, float *out, uint32_t ldo, hipStream_t stream)
+hipError_t launch_contraction_native(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream)
 {
     const DenseTopk none = { nullptr, 0, nullptr, nullptr, 0, 0 };
-    return launch_native<false>(kind, metric, Q, nq, B, nb, chunks, qn, bn, out, ldo, none, stream);
-}
-
-hipError_t launch_dense_native_topk(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
-                                    const uint32_t *bn, const uint64_t *best, uint32_t kk, uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t c_base,
-                                    hipStream_t stream)
-{
-    const DenseTopk tk = { best, kk, cand, cnt, cap, c_base };
-    return launch_native<true>(kind, metric, Q, nq, B, nb, chunks, qn, bn, (float *)nullptr, 0u, tk, stream);
+    return !topk ? launch_native<false>(o, out, ldo, none, stream) : launch_native<true>(o, (float *)nullptr, 0u, *topk, stream);
 }
 
 }  // namespace lgpu

@@ -2,6 +2,7 @@
 // persistent grid.  bruteforce.hip (k_dense_f32: f32 rows) and dense_native.hip (k_dense_native: f16 / i8 rows) include it.
 #pragma once
 #include <cstdint>
+#include <hip/hip_runtime.h>
 
 namespace lgpu {
 
@@ -27,5 +28,10 @@ constexpr int DENSE_WGS_PER_CU = 2;  // 67 KB of LDS each
 
 // persistent grid of the contractions: DENSE_WGS_PER_CU workgroups per CU of the current device (fewer if there are fewer tiles)
 uint32_t dense_grid(uint32_t tiles);
+
+// dense_native.hip's half of launch_contraction / launch_norms (kernels.hpp; bruteforce.hip hands it every kind but 0)
+struct DenseOperands;
+hipError_t launch_contraction_native(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream);
+hipError_t launch_norms_native(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, uint32_t *out, hipStream_t stream);
 
 }  // namespace lgpu

@@ -18,11 +18,8 @@
 #include <time.h>
 
 #include "comm.hpp"
+#include "dense.hpp"
 #include "host_util.hpp"
-
-// the exact k-NN building block (fp32-MFMA contraction + exact re-rank), defined with the C ABI below
-static bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k,
-                             uint32_t *d_slots, float *d_dists, hipStream_t st);
 
 // The HIP runtime multiplexes a process's streams onto FOUR hardware queues by default (GPU_MAX_HW_QUEUES); streams that share a queue
 // run their kernels one after the other.  This library keeps up to eight search launches in flight on streams of their own (the lanes of
@@ -35,8 +32,6 @@ static bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, si
 // other HIP users in it); lantern_scan_server_start warns on stderr when it runs more lanes than the setting gives queues.
 
 namespace lgpu {
-
-static const char *kNoDevice = "lantern_gpu: no HIP device available (this library has no CPU fallback)";
 
 const char *set_err(Index *ix, const std::string &msg)
 {
@@ -164,7 +159,7 @@ bool pq_encode_rows(Index *ix, size_t first, size_t count)
     bool ok = hipMalloc((void **)&d_sub, count * (size_t)sub_floats * 4) == hipSuccess && hipMalloc((void **)&d_near, count * 8) == hipSuccess;
     for(uint32_t sv = 0; ok && sv < ix->pq_S; ++sv) {
         ok = ok && launch_pq_take((const float *)ix->d_vec, row_floats, (uint32_t)first, (uint32_t)count, sv, ix->pq_subdim, sub_floats, d_sub, ix->stream) == hipSuccess;
-        ok = ok && ::exact_knn_device(ix->metric, sub_chunks, (const uint4 *)(ix->d_centers + (size_t)sv * ix->pq_C * sub_floats), ix->pq_C, (const uint4 *)d_sub,
+        ok = ok && exact_knn_device(ix->metric, sub_chunks, (const uint4 *)(ix->d_centers + (size_t)sv * ix->pq_C * sub_floats), ix->pq_C, (const uint4 *)d_sub,
                                     count, 1, d_near, (float *)(d_near + count), ix->stream);
         ok = ok && launch_pq_put((float *)ix->d_vec, row_floats, (uint32_t)first, (uint32_t)count, sv, ix->pq_subdim, ix->pq_S, d_near, ix->d_codebook,
                                  (uint32_t)ix->opts.dimensions, ix->d_codes, ix->stream) == hipSuccess;
@@ -1862,74 +1857,7 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
-// ---- distances ------------------------------------------------------------------------------------
-
-namespace {
-std::atomic<uint64_t> g_dense_kind[ 3 ];  // MFMA contraction launches of the process by operand kind: f32, f16, i8 (lantern_gpu_dense_kind_stats)
-}
-
-static bool metric_ok(usearch_metric_kind_t m) { return m == usearch_metric_cos_k || m == usearch_metric_l2sq_k || m == usearch_metric_hamming_k; }
-
-void lantern_gpu_distance_matrix(const void *a, size_t na, const void *b, size_t nb, usearch_scalar_kind_t kind, size_t dims,
-                                 usearch_metric_kind_t metric, int exact_order, float *out, usearch_error_t *e)
-try {
-    CLEAR(e);
-    if(!metric_ok(metric)) { FAIL(e, "lantern_gpu: unsupported metric kind (expected cos, l2sq or hamming)"); return; }
-    const bool ham = metric == usearch_metric_hamming_k;
-    // f16 / i8: rows of IEEE halves / int8 as an index of that storage holds them, under cos / l2sq (upstream usearch_distance takes them)
-    const bool h16 = kind == usearch_scalar_f16_k, s8 = kind == usearch_scalar_i8_k;
-    if(ham != (kind == usearch_scalar_b1_k) || (!ham && kind != usearch_scalar_f32_k && !h16 && !s8)) { FAIL(e, "lantern_gpu: scalar kind does not fit the metric"); return; }
-    if(!a || !b || !out || dims == 0) { FAIL(e, "lantern_gpu: bad arguments"); return; }
-    if(lantern_gpu_device_count() <= 0) { FAIL(e, kNoDevice); return; }
-    if(na == 0 || nb == 0) return;
-    const size_t in_bytes = ham ? (dims + 7) / 8 : h16 ? dims * 2 : s8 ? dims : dims * 4;
-    const size_t chunks = (in_bytes + 15) / 16, row = chunks * 16;
-    const int    mcode = (int)metric + (h16 ? M_F16 : s8 ? M_I8 : 0), dkind = h16 ? 1 : s8 ? 2 : 0;
-    std::vector<char> ha(na * row, 0), hb(nb * row, 0);
-    for(size_t i = 0; i < na; ++i) std::memcpy(&ha[ i * row ], (const char *)a + i * in_bytes, in_bytes);
-    for(size_t i = 0; i < nb; ++i) std::memcpy(&hb[ i * row ], (const char *)b + i * in_bytes, in_bytes);
-    void *da = nullptr, *db = nullptr, *dout = nullptr, *dn = nullptr;
-    bool  ok = hipMalloc(&da, na * row) == hipSuccess && hipMalloc(&db, nb * row) == hipSuccess &&
-              hipMalloc(&dout, na * nb * 4) == hipSuccess && hipMalloc(&dn, (na + nb) * 4) == hipSuccess;
-    ok = ok && hipMemcpy(da, ha.data(), na * row, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(db, hb.data(), nb * row, hipMemcpyHostToDevice) == hipSuccess;
-    if(exact_order) {
-        ok = ok && launch_pairs(mcode, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks,
-                                (float *)dout, nullptr) == hipSuccess;
-    } else if(dkind) {  // the dense contraction on the stored operand type (dense_native.hip)
-        uint32_t *an = (uint32_t *)dn, *bnn = an + na;
-        ok = ok && launch_row_norms_native(dkind, (int)metric, (const uint4 *)da, (uint32_t)na, (uint32_t)chunks, an, nullptr) == hipSuccess;
-        ok = ok && launch_row_norms_native(dkind, (int)metric, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, bnn, nullptr) == hipSuccess;
-        ok = ok && launch_dense_native(dkind, (int)metric, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, an, bnn,
-                                       (float *)dout, (uint32_t)nb, nullptr) == hipSuccess;
-        ++g_dense_kind[ dkind ];
-    } else {  // the dense contraction: fp32 MFMA for l2sq / cos
-        float *an = (float *)dn, *bnn = an + na;
-        if(!ham) {
-            ok = ok && launch_row_norms((const uint4 *)da, (uint32_t)na, (uint32_t)chunks, an, nullptr) == hipSuccess;
-            ok = ok && launch_row_norms((const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, bnn, nullptr) == hipSuccess;
-            ++g_dense_kind[ 0 ];
-        }
-        ok = ok && launch_dense((int)metric, (const uint4 *)da, (uint32_t)na, (const uint4 *)db, (uint32_t)nb, (uint32_t)chunks, an, bnn,
-                                (float *)dout, (uint32_t)nb, nullptr) == hipSuccess;
-    }
-    ok = ok && hipMemcpy(out, dout, na * nb * 4, hipMemcpyDeviceToHost) == hipSuccess;
-    if(da) (void)hipFree(da);
-    if(db) (void)hipFree(db);
-    if(dout) (void)hipFree(dout);
-    if(dn) (void)hipFree(dn);
-    if(!ok) FAIL(e, "lantern_gpu: HIP failure in distance_matrix");
-}
-LANTERN_ABI_CATCH_VOID(e)
-
-float usearch_distance(const void *a, const void *b, usearch_scalar_kind_t kind, size_t dims, usearch_metric_kind_t metric,
-                       usearch_error_t *e)
-try {
-    float out = 0.f;
-    lantern_gpu_distance_matrix(a, 1, b, 1, kind, dims, metric, 1, &out, e);
-    return out;
-}
-LANTERN_ABI_CATCH(e)
+// ---- gathered distances (the dense path -- distance matrices, the SQL-callable distances, the exact k-NN: dense.cpp) ----------------
 
 void lantern_gpu_distance_gather(usearch_index_t h, const void *query, const uint32_t *slots, size_t n, float *out,
                                  usearch_error_t *e)
@@ -1964,448 +1892,6 @@ try {
     if(!ok) FAIL(e, "lantern_gpu: HIP failure in distance_gather");
 }
 LANTERN_ABI_CATCH_VOID(e)
-
-// Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row):
-// fp32-MFMA contraction in chunks of 64k base rows + running top-(k+16) + exact-order re-rank, then per query the certificate
-// that the top-(k+16) held the exact answer; the refused queries are recomputed in exact order.
-// Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].
-// `fused`: the f32 contractions (l2sq / cos) keep their distance matrix to themselves -- the tile epilogue appends what can still
-// enter a query's top-kk to a candidate list, folded in after every launch -- once the first kSeedCols columns have given every
-// query a radius the ordinary way.  *overflowed: a candidate list ran out of room (adversarially ordered rows): the caller repeats
-// the search unfused.
-static const size_t kSeedCols = 4096, kCandCap = 4096;
-// lantern_gpu_dense_profile: HIP events around every launch of the fp32-MFMA contraction inside the exact k-NN (bench.py's
-// c3_dense_exact_knn leg: the duration of steady full-chunk launches apart from the cold first ones and the partial last chunk).
-// Off unless asked for; a process-wide diagnostic, not part of any index's state.
-namespace {
-struct DenseLaunch { hipEvent_t a = nullptr, b = nullptr; uint32_t rows = 0, cols = 0, fused = 0; };
-struct DenseProfile
-{
-    std::mutex               mu;
-    bool                     on = false;
-    std::vector<DenseLaunch> launches;
-} g_dense_profile;
-struct DenseTimer  // records event `a` now and `b` on destruction, on the launch stream
-{
-    DenseLaunch l;
-    hipStream_t st;
-    bool        armed = false;
-    DenseTimer(hipStream_t s, uint32_t rows, uint32_t cols, bool fused) : st(s)
-    {
-        if(!g_dense_profile.on) return;
-        if(hipEventCreate(&l.a) != hipSuccess || hipEventCreate(&l.b) != hipSuccess) { (void)hipGetLastError(); return; }
-        l.rows = rows; l.cols = cols; l.fused = fused;
-        armed = hipEventRecord(l.a, st) == hipSuccess;
-    }
-    ~DenseTimer()
-    {
-        if(!armed) return;
-        (void)hipEventRecord(l.b, st);
-        std::lock_guard<std::mutex> g(g_dense_profile.mu);
-        g_dense_profile.launches.push_back(l);
-    }
-};
-}  // namespace
-
-// The exact k-NN's device temporaries (norms + best lists, the seed-column matrix, the candidate lists) come from a small grow-only pool
-// per device instead of hipMalloc / hipFree per call -- a free synchronises the device, and a 1024 x 1M x 768 call made five of them:
-// about a millisecond of a 13.6 ms call.  Blocks above 64 MB (the whole-chunk matrix of the unfused path, the f32 copies of quantised
-// rows) are still allocated per call.  One exact k-NN at a time per device holds the pool (the calls are bandwidth- or MFMA-bound on
-// the whole chip: nothing is lost by not overlapping them).
-namespace {
-struct KnnPool
-{
-    std::mutex mu;
-    void      *p[ 3 ] = { nullptr, nullptr, nullptr };
-    size_t     bytes[ 3 ] = { 0, 0, 0 };
-};
-KnnPool g_knn_pool[ 16 ];
-constexpr size_t kKnnPoolMax = (size_t)64 << 20;
-
-struct KnnBlock  // pooled if small, allocated for the call otherwise; released by the destructor
-{
-    void *ptr = nullptr;
-    bool  own = false;
-    bool get(KnnPool *pool, int which, size_t need)
-    {
-        if(need == 0) need = 16;
-        if(pool && need <= kKnnPoolMax) {
-            if(pool->bytes[ which ] < need) {
-                if(pool->p[ which ]) (void)hipFree(pool->p[ which ]);
-                pool->p[ which ] = nullptr;
-                pool->bytes[ which ] = 0;
-                if(hipMalloc(&pool->p[ which ], need) != hipSuccess) { (void)hipGetLastError(); return false; }
-                pool->bytes[ which ] = need;
-            }
-            ptr = pool->p[ which ];
-            return true;
-        }
-        own = hipMalloc(&ptr, need) == hipSuccess;
-        if(!own) { (void)hipGetLastError(); ptr = nullptr; }
-        return own;
-    }
-    ~KnnBlock() { if(own && ptr) (void)hipFree(ptr); }
-};
-}  // namespace
-
-// ---- which contraction an exact k-NN runs: host arithmetic, shared by exact_knn_device_impl and the tests ---------------------
-// Rows stored as f16 / i8 are contracted as they are stored (dense_native.hip) unless LANTERN_GPU_DENSE_NATIVE says otherwise;
-// kDenseNativeDefault is what an unset switch means (set by the measurement rule recorded there).
-static const int      kDenseNativeDefault = 1;
-static const size_t   kDenseChunkRows = 65536;  // base rows per contraction launch
-const char *lantern_gpu_plan_dense(const int64_t in[ 4 ], uint32_t out[ 4 ])
-{
-    if(!in || !out) return "lantern_gpu: null plan array";
-    if(in[ 0 ] < 0 || in[ 0 ] > 0x7FFFFFFF || in[ 1 ] <= 0 || in[ 1 ] > (int64_t)1 << 20 || in[ 2 ] < 0) return "lantern_gpu: bad plan input";
-    const int      mcode = (int)in[ 0 ], base = mcode_base(mcode);
-    const uint32_t chunks = (uint32_t)in[ 1 ];
-    const bool     f16 = mcode_is_f16(mcode), i8 = mcode_is_i8(mcode), bits = base == M_HAMMING || base == M_COS_B1;
-    const bool     native = (f16 || i8) && !bits && (in[ 3 ] < 0 ? kDenseNativeDefault : (int)in[ 3 ]) != 0;
-    const uint32_t fchunks = native ? chunks : i8 ? chunks * 4 : f16 ? chunks * 2 : chunks;
-    const uint64_t copy = (f16 || i8) && !native ? (uint64_t)std::min<int64_t>(in[ 2 ], (int64_t)kDenseChunkRows) * fchunks * 16 : 0;
-    if(copy > 0xFFFFFFFFull) return "lantern_gpu: the f32 copy of a chunk of rows does not fit the plan";
-    out[ 0 ] = !native ? 0u : f16 ? 1u : 2u;
-    out[ 1 ] = (uint32_t)copy;
-    // the certificate's dims: f32 scalars contracted; native f16 -- twice the halves contracted; 0 -- keys are exact
-    out[ 2 ] = bits || (native && i8) ? 0u : native ? chunks * 16 : fchunks * 4;
-    out[ 3 ] = bits ? 0u : (fchunks * 4 + 31) / 32;
-    return nullptr;
-}
-
-void lantern_gpu_dense_kind_stats(uint64_t launches[ 3 ])
-{
-    if(!launches) return;
-    for(int i = 0; i < 3; ++i) launches[ i ] = g_dense_kind[ i ].load();
-}
-
-// certified: one flag per query (1: the certificate of DESIGN.md 4.5 holds -- the result is the exact answer; 0: the caller
-// recomputes the query in exact order, exact_knn_fallback)
-static bool exact_knn_device_impl(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k,
-                                  uint32_t *d_slots, float *d_dists, hipStream_t st, bool fused, bool *overflowed, std::vector<uint32_t> &certified)
-try {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    KnnPool *const               pool = (dev >= 0 && dev < 16) ? &g_knn_pool[ dev ] : nullptr;
-    std::unique_lock<std::mutex> pool_lock;
-    if(pool) pool_lock = std::unique_lock<std::mutex>(pool->mu);
-    KnnBlock b_aux, b_dd, b_cand;
-    // kk = k plus a margin: the MFMA distances (|q|^2 + |b|^2 - 2 q.b) differ from the exact-order ones in the
-    // last bits, so the survivors are re-ranked exactly and only then cut to k
-    const uint32_t kk = (uint32_t)k + 16;
-    // column chunk.  [r3] 65536 columns x 1024 queries are 4096 tiles = 5.33 rounds of the 768 workgroups the contraction keeps
-    // resident (three per CU): the last round runs a third full.  98304 columns (6144 tiles = 8 rounds) were tried: l2sq 14.9 -> 14.5 ms
-    // per 1024 x 1M x 768 call, but cosine 15.4 -> 20.1 ms (the fused call repeated itself unfused), so the chunk stays.
-    const size_t   QT = 1024, CH = std::min<size_t>(nb, kDenseChunkRows);
-    // which contraction, what it allocates and what the certificate is told: lantern_gpu_plan_dense, read per call
-    const char    *env_native = std::getenv("LANTERN_GPU_DENSE_NATIVE");
-    const int64_t  plan_in[ 4 ] = { mcode, chunks, (int64_t)nb, env_native ? std::atoi(env_native) : -1 };
-    uint32_t       plan[ 4 ] = { 0, 0, 0, 0 };
-    if(lantern_gpu_plan_dense(plan_in, plan) != nullptr) return false;
-    const int      kind = (int)plan[ 0 ];  // 0: the f32 contraction (on a copy, for quantised rows), 1 / 2: f16 / i8 rows as they are stored
-    const bool     i8 = mcode_is_i8(mcode);
-    const bool     f16 = (mcode_is_f16(mcode) || i8) && !kind;  // quantised storage on the dequantised path: the contraction runs on an f32 copy
-    const int      base_metric = mcode_base(mcode);
-    const bool bits = base_metric == M_HAMMING || base_metric == M_COS_B1;  // popcount metrics: no MFMA contraction, no row norms
-    const bool exact_keys = plan[ 2 ] == 0;  // the pre-selection ranks on the exact-order distance itself (popcounts, native i8): nothing to certify
-    if(bits || nb <= kSeedCols) fused = false;
-    const uint32_t fchunks = kind ? chunks : i8 ? chunks * 4 : f16 ? chunks * 2 : chunks;  // chunks of the rows fed to the contraction
-    auto dequant = [&](const uint4 *src, size_t nchunks, uint4 *dst) { return i8 ? launch_dequant_i8(src, nchunks, dst, st) : launch_dequant_f16(src, nchunks, dst, st); };
-    auto norms = [&](const uint4 *rows, size_t n, float *out) {
-        return kind ? launch_row_norms_native(kind, base_metric, rows, (uint32_t)n, fchunks, (uint32_t *)out, st) : launch_row_norms(rows, (uint32_t)n, fchunks, out, st);
-    };
-    char  *aux = nullptr;
-    float *dd = nullptr;
-    uint4 *fq = nullptr, *fb = nullptr;  // f32 copies of f16 rows (queries; one chunk of base rows)
-    uint64_t *cand = nullptr;            // fused: [min(nq, QT)][kCandCap] keys, then the counters and the overflow flag
-    const size_t nqt_max = std::min(nq, QT);
-    // the distance matrix of the unfused launches: a whole chunk, or only the seed columns
-    bool ok = b_aux.get(pool, 0, (nq + nb) * 4 + 8 + nq * kk * 8 + (nq + 1) * 4) && b_dd.get(pool, 1, nqt_max * (fused ? kSeedCols : CH) * 4);
-    aux = (char *)b_aux.ptr;
-    dd = (float *)b_dd.ptr;
-    if(ok && fused) {
-        ok = b_cand.get(pool, 2, nqt_max * kCandCap * 8 + nqt_max * 4 + 16);
-        cand = (uint64_t *)b_cand.ptr;
-        ok = ok && hipMemsetAsync((char *)cand + nqt_max * kCandCap * 8, 0, nqt_max * 4 + 16, st) == hipSuccess;
-    }
-    uint32_t *ccnt = cand ? (uint32_t *)((char *)cand + nqt_max * kCandCap * 8) : nullptr, *cover = ccnt ? ccnt + nqt_max : nullptr;
-    if(ok && f16)
-        ok = hipMalloc((void **)&fq, nq * (size_t)fchunks * 16) == hipSuccess && hipMalloc((void **)&fb, std::max<size_t>(plan[ 1 ], 16)) == hipSuccess &&
-             dequant(d_q, nq * (size_t)chunks, fq) == hipSuccess;
-    if(ok) {
-        float    *qn = (float *)aux, *bn = qn + nq;
-        uint64_t *best = (uint64_t *)(aux + (nq + nb) * 4 + ((nq + nb) % 2) * 4);
-        const uint4 *qv = f16 ? fq : d_q;
-        const uint32_t ldd = (uint32_t)(fused ? kSeedCols : CH);
-        ok = ok && hipMemsetAsync(best, 0xFF, nq * kk * 8, st) == hipSuccess;
-        if(!bits) ok = ok && norms(qv, nq, qn) == hipSuccess;
-        if(!bits && !f16) ok = ok && norms(d_base, nb, bn) == hipSuccess;
-        for(size_t c0 = 0; ok && c0 < nb; c0 += CH) {
-            const size_t nc = std::min(CH, nb - c0);
-            const uint4 *bv = d_base + c0 * chunks;
-            if(f16) {
-                ok = ok && dequant(d_base + c0 * chunks, nc * (size_t)chunks, fb) == hipSuccess;
-                ok = ok && launch_row_norms(fb, (uint32_t)nc, fchunks, bn + c0, st) == hipSuccess;
-                bv = fb;
-            }
-            // the columns of this chunk that go the ordinary way: all of them, or (fused) the seed columns of the first chunk
-            const size_t plain = !fused ? nc : (c0 == 0 ? std::min(nc, kSeedCols) : 0);
-            for(size_t q0 = 0; ok && q0 < nq; q0 += QT) {
-                const size_t nqt = std::min(QT, nq - q0);
-                if(plain) {
-                    {
-                        DenseTimer t(st, (uint32_t)nqt, (uint32_t)plain, false);
-                        if(kind)
-                            ok = ok && launch_dense_native(kind, base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv, (uint32_t)plain, fchunks, (const uint32_t *)(qn + q0),
-                                                           (const uint32_t *)(bn + c0), dd, ldd, st) == hipSuccess;
-                        else
-                            ok = ok && launch_dense(base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv, (uint32_t)plain, fchunks, qn + q0, bn + c0, dd, ldd, st) == hipSuccess;
-                        if(!bits) ++g_dense_kind[ kind ];
-                    }
-                    ok = ok && launch_select(dd, ldd, (uint32_t)nqt, (uint32_t)plain, (uint32_t)c0, best + q0 * kk, kk, st) == hipSuccess;
-                }
-                if(plain < nc) {
-                    {
-                        DenseTimer t(st, (uint32_t)nqt, (uint32_t)(nc - plain), true);
-                        if(kind)
-                            ok = ok && launch_dense_native_topk(kind, base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv + plain * fchunks, (uint32_t)(nc - plain), fchunks,
-                                                                (const uint32_t *)(qn + q0), (const uint32_t *)(bn + c0 + plain), best + q0 * kk, kk, cand, ccnt,
-                                                                (uint32_t)kCandCap, (uint32_t)(c0 + plain), st) == hipSuccess;
-                        else
-                            ok = ok && launch_dense_topk(base_metric, qv + q0 * fchunks, (uint32_t)nqt, bv + plain * fchunks, (uint32_t)(nc - plain), fchunks, qn + q0,
-                                                         bn + c0 + plain, best + q0 * kk, kk, cand, ccnt, (uint32_t)kCandCap, (uint32_t)(c0 + plain), st) == hipSuccess;
-                        ++g_dense_kind[ kind ];
-                    }
-                    ok = ok && launch_select_candidates((uint32_t)nqt, best + q0 * kk, kk, cand, ccnt, (uint32_t)kCandCap, cover, st) == hipSuccess;
-                }
-            }
-        }
-        ok = ok && launch_rerank(mcode, d_q, (uint32_t)nq, d_base, chunks, best, kk, (uint32_t)k, d_slots, d_dists, st) == hipSuccess;
-        // the certificate: 4 bytes per query to the host, behind the synchronisation the call makes anyway.  The popcount metrics
-        // rank on the exact-order distance itself (the same integer arithmetic): their pre-selection is exact by construction.
-        uint32_t *flag = (uint32_t *)(best + nq * kk);
-        certified.assign(nq + 1, exact_keys ? 1u : 0u);
-        certified[ nq ] = 0;
-        if(!exact_keys) {
-            ok = ok && hipMemsetAsync(flag + nq, 0, 4, st) == hipSuccess;
-            ok = ok && launch_certify(base_metric, best, kk, d_dists, (uint32_t)k, qn, (uint32_t)nq, bn, (uint32_t)nb, plan[ 2 ], flag, st) == hipSuccess;
-            ok = ok && hipMemcpyAsync(certified.data(), flag, (nq + 1) * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-        }
-        uint32_t over = 0;
-        if(fused) ok = ok && hipMemcpyAsync(&over, cover, 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-        ok = ok && hipStreamSynchronize(st) == hipSuccess;
-        if(overflowed) *overflowed = over != 0;
-        if(ok && certified[ nq ])  // a cosine row norm outside the bound's range: nothing is certified
-            std::fill(certified.begin(), certified.end() - 1, 0u);
-        certified.resize(nq);
-    }
-    if(!ok) (void)hipStreamSynchronize(st);  // nothing queued may still name the pooled blocks when the pool's lock is released
-    if(fq) (void)hipFree(fq);
-    if(fb) (void)hipFree(fb);
-    return ok;
-}
-LANTERN_ABI_CATCH(nullptr)
-
-// lantern_gpu_exact_knn_stats: queries of every exact k-NN of the process, how many the certificate passed, how many took the
-// exact-order fallback
-namespace {
-std::atomic<uint64_t> g_knn_queries{ 0 }, g_knn_certified{ 0 }, g_knn_fallback{ 0 };
-}
-
-// The queries the certificate refused, recomputed in the pair kernel's exact order over every base row: their rows gathered,
-// k_pairs + k_select (top-k by (exact distance, slot)) per block of kFallbackQ queries and chunk of base rows, the keys written
-// over their rows of the result.  nf x nb exact-order evaluations: rare (adversarial data), not fast.
-static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t k, const std::vector<uint32_t> &qidx,
-                               uint32_t *d_slots, float *d_dists, hipStream_t st)
-{
-    const size_t nf = qidx.size(), CH = std::min<size_t>(nb, 65536), kFallbackQ = 256, nfb = std::min(nf, kFallbackQ);
-    void *d_idx = nullptr, *d_rows = nullptr, *d_best = nullptr, *d_dd = nullptr;
-    bool  ok = hipMalloc(&d_idx, nf * 4) == hipSuccess && hipMalloc(&d_rows, nf * (size_t)chunks * 16) == hipSuccess &&
-              hipMalloc(&d_best, nf * k * 8) == hipSuccess && hipMalloc(&d_dd, nfb * CH * 4) == hipSuccess;
-    ok = ok && hipMemcpyAsync(d_idx, qidx.data(), nf * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok = ok && hipMemsetAsync(d_best, 0xFF, nf * k * 8, st) == hipSuccess;
-    ok = ok && launch_gather_rows(d_q, chunks, (const uint32_t *)d_idx, (uint32_t)nf, (uint4 *)d_rows, st) == hipSuccess;
-    for(size_t c0 = 0; ok && c0 < nb; c0 += CH) {
-        const size_t nc = std::min(CH, nb - c0);
-        for(size_t f0 = 0; ok && f0 < nf; f0 += kFallbackQ) {
-            const size_t nft = std::min(kFallbackQ, nf - f0);
-            ok = ok && launch_pairs(mcode, (const uint4 *)d_rows + f0 * chunks, (uint32_t)nft, d_base + c0 * chunks, (uint32_t)nc, chunks, (float *)d_dd,
-                                    st) == hipSuccess;
-            ok = ok && launch_select((const float *)d_dd, (uint32_t)nc, (uint32_t)nft, (uint32_t)nc, (uint32_t)c0, (uint64_t *)d_best + f0 * k, (uint32_t)k,
-                                     st) == hipSuccess;
-        }
-    }
-    ok = ok && launch_emit_topk((const uint64_t *)d_best, (uint32_t)k, (const uint32_t *)d_idx, (uint32_t)nf, d_slots, d_dists, st) == hipSuccess;
-    ok = ok && hipStreamSynchronize(st) == hipSuccess;
-    if(!ok) (void)hipStreamSynchronize(st);
-    for(void *p : { d_idx, d_rows, d_best, d_dd })
-        if(p) (void)hipFree(p);
-    return ok;
-}
-
-static bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k,
-                             uint32_t *d_slots, float *d_dists, hipStream_t st)
-try {
-    const char *env = std::getenv("LANTERN_GPU_DENSE_FUSED");  // =0: always the unfused path (A/B, tests)
-    const bool  want_fused = !(env && std::atoi(env) == 0);
-    bool                  over = false;
-    std::vector<uint32_t> certified;
-    if(!exact_knn_device_impl(mcode, chunks, d_base, nb, d_q, nq, k, d_slots, d_dists, st, want_fused, &over, certified)) return false;
-    if(over && !exact_knn_device_impl(mcode, chunks, d_base, nb, d_q, nq, k, d_slots, d_dists, st, false, nullptr, certified)) return false;
-    std::vector<uint32_t> refused;
-    for(size_t q = 0; q < nq; ++q)
-        if(!certified[ q ]) refused.push_back((uint32_t)q);
-    g_knn_queries += nq;
-    g_knn_certified += nq - refused.size();
-    g_knn_fallback += refused.size();
-    return refused.empty() || exact_knn_fallback(mcode, chunks, d_base, nb, d_q, k, refused, d_slots, d_dists, st);
-}
-LANTERN_ABI_CATCH(nullptr)
-
-void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t *certified, uint64_t *fallback)
-{
-    if(queries) *queries = g_knn_queries.load();
-    if(certified) *certified = g_knn_certified.load();
-    if(fallback) *fallback = g_knn_fallback.load();
-}
-
-void lantern_gpu_exact_search(usearch_index_t h, const void *queries, size_t nq, size_t k, uint32_t *slots, float *distances,
-                              usearch_error_t *e)
-try {
-    CLEAR(e);
-    Index *ix = H(h, e);
-    if(!ix || nq == 0 || k == 0) return;
-    if(k > 240) { FAIL(e, "lantern_gpu: exact_search supports k <= 240"); return; }
-    std::lock_guard<std::mutex> g(ix->mu);
-    if(!flush_locked(ix) || !pq_expand_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
-    const size_t n = ix->n, row_words = (size_t)ix->chunks * 4;
-    if(n == 0) {
-        for(size_t i = 0; i < nq * k; ++i) { slots[ i ] = EMPTY; distances[ i ] = INFINITY; }
-        return;
-    }
-    const int    qkind = (ix->scalar == usearch_scalar_b1_k && !ix->b1_from_f32) ? usearch_scalar_b1_k : usearch_scalar_f32_k;  // queries arrive as f32 / bits
-    const size_t in_bytes = input_bytes(ix, qkind);
-    std::vector<uint32_t> padded(nq * row_words);
-    for(size_t i = 0; i < nq; ++i) pad_row(ix, (const char *)queries + i * in_bytes, qkind, &padded[ i * row_words ]);
-    uint4 *dq = (uint4 *)scratch(ix, kScratchCallIn, nq * row_words * 4);
-    char  *dout = (char *)scratch(ix, kScratchCallOut, nq * k * 8 + 64);
-    if(!dq || !dout) { FAIL(e, ix->err.c_str()); return; }
-    uint32_t *d_slots = (uint32_t *)dout;
-    float    *d_dists = (float *)(d_slots + nq * k);
-    hipStream_t st = ix->stream;
-    bool ok = hipMemcpyAsync(dq, padded.data(), nq * row_words * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok = ok && exact_knn_device(ix->mcode, ix->chunks, ix->d_vec, n, dq, nq, k, d_slots, d_dists, st);
-    ok = ok && hipMemcpy(slots, d_slots, nq * k * 4, hipMemcpyDeviceToHost) == hipSuccess;
-    ok = ok && hipMemcpy(distances, d_dists, nq * k * 4, hipMemcpyDeviceToHost) == hipSuccess;
-    if(!ok) FAIL(e, "lantern_gpu: HIP failure in exact_search");
-}
-LANTERN_ABI_CATCH_VOID(e)
-
-// on != 0: start recording (forgets earlier records).  on == 0: stop, wait for the recorded launches and write up to `cap` of them:
-// ms[i] = duration of launch i (HIP events on its stream), rows[i] x cols[i] = its queries x base rows, fused[i] = 1 for the
-// launch with the fused top-k epilogue.  Returns the number of recorded launches.
-size_t lantern_gpu_dense_profile(int on, float *ms, uint32_t *rows, uint32_t *cols, uint32_t *fused, size_t cap)
-try {
-    std::vector<DenseLaunch> got;
-    {
-        std::lock_guard<std::mutex> g(g_dense_profile.mu);
-        if(on) {
-            for(auto &l : g_dense_profile.launches) { (void)hipEventDestroy(l.a); (void)hipEventDestroy(l.b); }
-            g_dense_profile.launches.clear();
-            g_dense_profile.on = true;
-            return 0;
-        }
-        g_dense_profile.on = false;
-        got.swap(g_dense_profile.launches);
-    }
-    for(size_t i = 0; i < got.size(); ++i) {
-        float t = 0.0f;
-        if(hipEventSynchronize(got[ i ].b) != hipSuccess || hipEventElapsedTime(&t, got[ i ].a, got[ i ].b) != hipSuccess) { (void)hipGetLastError(); t = -1.0f; }
-        if(i < cap) {
-            if(ms) ms[ i ] = t;
-            if(rows) rows[ i ] = got[ i ].rows;
-            if(cols) cols[ i ] = got[ i ].cols;
-            if(fused) fused[ i ] = got[ i ].fused;
-        }
-        (void)hipEventDestroy(got[ i ].a);
-        (void)hipEventDestroy(got[ i ].b);
-    }
-    return got.size();
-}
-LANTERN_ABI_CATCH(nullptr)
-
-// PQ k-means assignment (product_quantization.c:80-124 assign_to_clusters): the one dense N x k contraction in
-// Lantern's C code -- N x k usearch_distance calls there, one fp32-MFMA pass + exact re-rank here.
-void lantern_gpu_assign_to_clusters(const float *dataset, size_t n, size_t row_dims, size_t subvector_start, size_t subvector_dim,
-                                    const float *centers, size_t k, usearch_metric_kind_t metric, uint32_t *out_cluster,
-                                    float *out_distance, usearch_error_t *e)
-try {
-    CLEAR(e);
-    if(metric != usearch_metric_cos_k && metric != usearch_metric_l2sq_k) { FAIL(e, "lantern_gpu: assign_to_clusters needs cos or l2sq"); return; }
-    if(!dataset || !centers || !out_cluster || subvector_dim == 0 || subvector_start + subvector_dim > row_dims || k == 0) {
-        FAIL(e, "lantern_gpu: bad arguments");
-        return;
-    }
-    if(lantern_gpu_device_count() <= 0) { FAIL(e, kNoDevice); return; }
-    if(n == 0) return;
-    const size_t chunks = (subvector_dim + 3) / 4, rw = chunks * 4;
-    std::vector<float> hp(n * rw, 0.f), hc(k * rw, 0.f);
-    for(size_t i = 0; i < n; ++i) std::memcpy(&hp[ i * rw ], dataset + i * row_dims + subvector_start, subvector_dim * 4);
-    for(size_t j = 0; j < k; ++j) std::memcpy(&hc[ j * rw ], centers + j * subvector_dim, subvector_dim * 4);
-    void *dp = nullptr, *dc = nullptr, *dout = nullptr;
-    bool  ok = hipMalloc(&dp, hp.size() * 4) == hipSuccess && hipMalloc(&dc, hc.size() * 4) == hipSuccess &&
-              hipMalloc(&dout, n * 8) == hipSuccess;
-    ok = ok && hipMemcpy(dp, hp.data(), hp.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipMemcpy(dc, hc.data(), hc.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    // first minimum wins (strict `<` in the reference loop) == smallest (distance, index)
-    ok = ok && exact_knn_device((int)metric, (uint32_t)chunks, (const uint4 *)dc, k, (const uint4 *)dp, n, 1, (uint32_t *)dout,
-                                (float *)((uint32_t *)dout + n), nullptr);
-    ok = ok && hipMemcpy(out_cluster, dout, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
-    if(out_distance) ok = ok && hipMemcpy(out_distance, (uint32_t *)dout + n, n * 4, hipMemcpyDeviceToHost) == hipSuccess;
-    if(dp) (void)hipFree(dp);
-    if(dc) (void)hipFree(dc);
-    if(dout) (void)hipFree(dout);
-    if(!ok) FAIL(e, "lantern_gpu: HIP failure in assign_to_clusters");
-}
-LANTERN_ABI_CATCH_VOID(e)
-
-// ---- SQL-callable semantics (hnsw.c:296-405) ---------------------------------------------------------
-
-static thread_local char g_dim_msg[ 160 ];
-
-static bool same_dims(int a_dim, int b_dim, usearch_error_t *e)
-try {
-    if(a_dim == b_dim) return true;
-    // hnsw.c:301-303
-    std::snprintf(g_dim_msg, sizeof(g_dim_msg), "expected equally sized arrays but got arrays with dimensions %d and %d", a_dim, b_dim);
-    FAIL(e, g_dim_msg);
-    return false;
-}
-LANTERN_ABI_CATCH(e)
-
-float lantern_l2sq_dist(const float *a, int a_dim, const float *b, int b_dim, usearch_error_t *e)
-try {
-    CLEAR(e);
-    if(!same_dims(a_dim, b_dim, e)) return 0.f;
-    return usearch_distance(a, b, usearch_scalar_f32_k, (size_t)a_dim, usearch_metric_l2sq_k, e);
-}
-LANTERN_ABI_CATCH(e)
-
-float lantern_cos_dist(const float *a, int a_dim, const float *b, int b_dim, usearch_error_t *e)
-try {
-    CLEAR(e);
-    if(!same_dims(a_dim, b_dim, e)) return 0.f;
-    return usearch_distance(a, b, usearch_scalar_f32_k, (size_t)a_dim, usearch_metric_cos_k, e);
-}
-LANTERN_ABI_CATCH(e)
-
-int32_t lantern_hamming_dist(const int32_t *a, int a_dim, const int32_t *b, int b_dim, usearch_error_t *e)
-try {
-    CLEAR(e);
-    if(!same_dims(a_dim, b_dim, e)) return 0;
-    // hnsw.c:317-319: dims = a_dim * sizeof(int32) * CHAR_BIT bits; result cast to int32 (hnsw.c:375)
-    return (int32_t)usearch_distance(a, b, usearch_scalar_b1_k, (size_t)a_dim * 32, usearch_metric_hamming_k, e);
-}
-LANTERN_ABI_CATCH(e)
 
 // ---- metadata / counters / graph exchange --------------------------------------------------------------
 

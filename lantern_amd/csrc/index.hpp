@@ -387,6 +387,7 @@ struct InsertEnv
     bool debug_groups = false;   // LANTERN_GPU_DEBUG_GROUPS is present
 };
 InsertEnv insert_env();
+// (the exact k-NN's two switches, LANTERN_GPU_DENSE_NATIVE and _DENSE_FUSED, as values: DenseEnv / dense_env, dense.hpp)
 struct Comm;
 // Row-sharded build (index.cpp add_row_sharded_locked): where a batch's level-0 candidates come from
 struct RowShard

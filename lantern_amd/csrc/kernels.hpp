@@ -273,23 +273,29 @@ hipError_t launch_pairs(int metric, const uint4 *a, uint32_t na, const uint4 *b,
                         hipStream_t stream);
 
 // dense contraction + exact k-NN building blocks (bruteforce.hip)
-hipError_t launch_row_norms(const uint4 *rows, uint32_t n, uint32_t chunks, float *out, hipStream_t stream);
 hipError_t launch_dequant_f16(const uint4 *src, size_t nchunks, uint4 *dst, hipStream_t stream);
 hipError_t launch_dequant_i8(const uint4 *src, size_t nchunks, uint4 *dst, hipStream_t stream);
-hipError_t launch_dense(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const float *qn,
-                        const float *bn, float *out, uint32_t ldo, hipStream_t stream);
-hipError_t launch_dense_topk(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const float *qn,
-                             const float *bn, const uint64_t *best, uint32_t kk, uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t c_base,
-                             hipStream_t stream);
-// the same contraction on rows STORED as f16 (kind 1) or i8 (kind 2), on the MFMAs of that operand type (dense_native.hip).
-// Norms as 32-bit words: f16 -- the f32 |x|^2; i8 -- the exact int32 sum of squares (l2sq) or the bits of its IEEE root (cos).
-// The i8 outputs are the pair kernel's distances bit for bit.
-hipError_t launch_row_norms_native(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, uint32_t *out, hipStream_t stream);
-hipError_t launch_dense_native(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
-                               const uint32_t *bn, float *out, uint32_t ldo, hipStream_t stream);
-hipError_t launch_dense_native_topk(int kind, int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t nb, uint32_t chunks, const uint32_t *qn,
-                                    const uint32_t *bn, const uint64_t *best, uint32_t kk, uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t c_base,
-                                    hipStream_t stream);
+// The dense contraction out[i * ldo + j] ~ metric(Q[i], B[j]) on rows of `chunks` uint4.  kind is the plan's operand kind
+// (lantern_gpu_plan_exact_knn): 0 -- f32 rows on the fp32 MFMA (k_dense_f32), or bit rows under the popcount metrics (k_dense_ham, which
+// reads no norms); 1 / 2 -- rows STORED as f16 / i8, on the MFMAs of that operand type (k_dense_native, dense_native.hip).  metric is
+// the base metric.  qn / bn: one 32-bit word per row, as launch_norms wrote them for the same kind and metric: f32 and f16 rows -- the
+// f32 |x|^2; i8 -- the exact int32 sum of squares (l2sq) or the bits of its IEEE root (cos).  The i8 outputs are the pair kernel's
+// distances bit for bit.  Refused with hipErrorInvalidValue: another kind, a metric the kind has no kernel for, a Hamming row over
+// 16384 words.
+struct DenseOperands
+{
+    int          kind, metric;
+    const uint4 *Q;
+    uint32_t     nq;
+    const uint4 *B;
+    uint32_t     nb, chunks;
+    const void  *qn, *bn;
+};
+struct DenseTopk;  // dense_tile.hpp
+// topk == NULL: the matrix goes to out (leading dimension ldo).  Otherwise out and ldo are unused: the tile epilogue appends what can
+// still enter a query's running top-kk to the candidate lists of *topk (l2sq / cos only)
+hipError_t launch_contraction(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream);
+hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream);
 hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, const uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t *overflow,
                                     hipStream_t stream);
 hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t ncols, uint32_t c_base, uint64_t *best, uint32_t kk,

@@ -4,6 +4,7 @@
 // traffic / barriers -- were built from this harness with macros that are gone again: profiles/r03_dense_variants.md has
 // their numbers.)
 #include "../../lantern_amd/csrc/bruteforce.hip"
+#include "../../lantern_amd/csrc/dense_native.hip"  // (the other half of launch_contraction)
 #include <cstdio>
 #include <vector>
 #include <random>
@@ -26,14 +27,13 @@ int main()
     CK(hipMemcpy(Q, hq.data(), hq.size() * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(B, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
     CK(hipMemset(best, 0, (size_t)nq * kk * 8));  // ordered distance 0 = below every real distance: nothing is appended
     CK(hipMemset(cnt, 0, nq * 4));
-    CK(lgpu::launch_row_norms((const uint4 *)Q, nq, dim / 4, qn, 0)); CK(lgpu::launch_row_norms((const uint4 *)B, nb, dim / 4, bn, 0));
+    CK(lgpu::launch_norms(0, lgpu::M_COS, (const uint4 *)Q, nq, dim / 4, qn, 0)); CK(lgpu::launch_norms(0, lgpu::M_COS, (const uint4 *)B, nb, dim / 4, bn, 0));
+    const lgpu::DenseOperands ops = { 0, lgpu::M_COS, (const uint4 *)Q, nq, (const uint4 *)B, nb, dim / 4, qn, bn };
+    const lgpu::DenseTopk     tk = { best, kk, cand, cnt, cap, 0 };
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for(int fused = 0; fused < 2; ++fused) {
-        auto go = [&]() {
-            return fused ? lgpu::launch_dense_topk(lgpu::M_COS, (const uint4 *)Q, nq, (const uint4 *)B, nb, dim / 4, qn, bn, best, kk, cand, cnt, cap, 0, 0)
-                         : lgpu::launch_dense(lgpu::M_COS, (const uint4 *)Q, nq, (const uint4 *)B, nb, dim / 4, qn, bn, out, nb, 0);
-        };
+        auto go = [&]() { return lgpu::launch_contraction(ops, out, nb, fused ? &tk : nullptr, 0); };
         for(int i = 0; i < 5; ++i) CK(go());
         CK(hipDeviceSynchronize());
         const int reps = 40;

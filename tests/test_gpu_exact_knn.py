@@ -1,4 +1,4 @@
-"""The exact k-NN (lantern_gpu_exact_search, _assign_to_clusters, PQ encoding: index.cpp exact_knn_device) against a brute force
+"""The exact k-NN (lantern_gpu_exact_search, _assign_to_clusters, PQ encoding: dense.cpp exact_knn_device) against a brute force
 in the pair kernel's reduction order, on data where the fp32-MFMA pre-selection's distances are rounding noise: a large common
 offset with a small spread, near-duplicate groups larger than k + 16, ties beyond the survivors, lattices, scaled copies under
 cosine, popcount ties.  Ids and distance bits must be identical; the referee itself is checked against float64.  Also: the
@@ -148,7 +148,7 @@ def run_case(capi, oracle, cores, monkeypatch, family, metric, n, d, nq, k, stor
 
 def range_refusals(metric, rows, queries, k, dk, dims):
     """how many of the call's queries k_certify's RANGE rules refuse whatever the contraction found (tests/exact_knn_bound.py certify with
-    tau = +inf).  Read off index.cpp exact_knn_device_impl / bruteforce.hip k_certify: one cosine ROW norm^2 outside [2^-60, 2^60] raises
+    tau = +inf).  Read off dense.cpp exact_knn_run / bruteforce.hip k_certify: one cosine ROW norm^2 outside [2^-60, 2^60] raises
     flag[nq] and the host clears every query's certificate -- all of the call's queries; a QUERY norm out of range, |q|^2 >= 2^120 and the
     l2sq rule (2 qa + sqrt(dup))^2 >= 2^120 are tested per query and refuse that query alone -- and only where the survivor list is full:
     with fewer than kk = k + 16 rows every row is a survivor and k_certify passes the query before it looks at a norm (certify's tau =
