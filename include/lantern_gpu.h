@@ -814,7 +814,8 @@ LANTERN_GPU_EXPORT size_t lantern_gpu_deleted_count(usearch_index_t, usearch_err
  *  - If the entry node is in T, the new entry is the live node of the highest level, the lowest slot among those, and max_level
  *    becomes that level.
  *  - Rows, labels, levels, the size, slots, upper blocks, the screen copy and norms do not move: filters, cursors' `seen` sets and
- *    page maps stay valid.  NO MEMORY IS RECLAIMED (that needs slot reuse).  A second call changes nothing and reports zeros.
+ *    page maps stay valid.  The unlink itself reclaims no memory: lantern_gpu_compact_deleted (below) does.  A second call changes
+ *    nothing and reports zeros.
  *  - It does not equal a rebuild of the live rows (DESIGN.md 4.11 says by how much).
  * The call is a graph mutation, ordered as an insertion batch.  The result is a pure function of the graph: the replicas of a
  * sharded build each call it and stay identical.  Refused: a page-attached index (its lists would have to go back through
@@ -830,6 +831,56 @@ typedef struct lantern_gpu_unlink_stats
     uint64_t entry_moved;         /* 1 if the entry node was in T */
 } lantern_gpu_unlink_stats;
 LANTERN_GPU_EXPORT void lantern_gpu_unlink_deleted(usearch_index_t, lantern_gpu_unlink_stats *out /* or NULL */, usearch_error_t *);
+/* lantern_gpu_compact_deleted: reclaims the tombstones' slots.  Notation as above; n the size after the flush.
+ *  - After the flush the call does exactly what lantern_gpu_unlink_deleted does (its stats: `unlink`).  Then, with T the slots of
+ *    label 0 and live = n - |T|: map[s] = the number of live slots below s for a live s, map[s] = 0xFFFFFFFF for s in T.  The
+ *    renumbering is STABLE: live slots keep their relative order.
+ *  - If T is empty nothing changes, every stat is 0, `capacity` is ignored and the epoch (below) does not move; slot_map receives
+ *    the identity.
+ *  - Otherwise, for every live s, slot map[s] of the new index carries what slot s carried: row, label, level, cached norm, the code
+ *    bytes of an expanded pq index, the int8 screen row and its (s, r) metadata, all bit for bit.  Every list of s at every level
+ *    keeps its stored order with every entry e replaced by map[e]; the 0xFFFFFFFF padding stays padding.  upper_off becomes the
+ *    exclusive prefix sum of `level` over the new slots (a node of level 0 carries the running sum, which nothing dereferences;
+ *    an insertion writes 0xFFFFFFFF there) and the upper blocks are copied from wherever they were.  entry = map[entry], max_level
+ *    is unchanged, the size is live.
+ *  - live == 0 (everything deleted: the case the unlink skips) leaves an empty index: size 0, no entry, max_level -1.
+ *  - usearch_capacity becomes max(live, capacity).  The old arrays are FREED: lantern_gpu_memory_usage falls to what the new capacity
+ *    costs (the upper blocks to exactly the live ones).  The arrays sized by capacity that are allocated on first use (visited bitmaps
+ *    of every launch slot, the diagnostics bitmap of lantern_gpu_search_unique_rows) are dropped; the re-prune state is not moved but
+ *    reset before its next use.
+ *  - ALL OR NOTHING: the new arrays are built in fresh allocations beside the old ones and swapped in after the last kernel has
+ *    succeeded, so the transient peak is old + new (+ 20 bytes per old slot for the map).  If an allocation fails the error names the
+ *    bytes needed; if an entry of a live list maps to 0xFFFFFFFF (impossible after an unlink; the list kernel counts them) the error
+ *    says how many.  Either way the index stays exactly as the unlink left it.
+ *  - slot_map (may be NULL) receives map[0..n).
+ *  - SLOTS CHANGE MEANING, so the index counts its compactions that moved something (the epoch).  A filter remembers the epoch of its
+ *    build and is refused in another ("the index was compacted since the filter was built"), whatever the size has become since.  A
+ *    cursor (lantern_gpu_cursor_*, lantern_scan) whose `seen` set is not empty and comes from another epoch is refused on a
+ *    streaming continuation ("the index was compacted: rescan"); a non-streaming search starts it afresh.  usearch_search_ef's own
+ *    continuation state is renumbered through map and goes on.  A scan-service connection remembers labels, not slots: it goes on too.
+ *  - NOT A REBUILD: the result is the unlinked graph renumbered and nothing more; every search answers with the same labels, distance
+ *    bits and counters as before the call (candidates are ordered by (distance, slot) and the order of the live slots is kept).
+ *    Re-prunes and insertions that follow break exact distance ties by tie_mix(slot, centre) over the NEW slots, so from then on the
+ *    graph may differ, among exactly tied candidates only, from what the uncompacted index would have grown into.
+ * The call is a graph mutation, ordered as an insertion batch, and a pure function of the graph: the replicas of a sharded build each
+ * call it and stay identical.  Refused: a page-attached index and a compact pq index (expand it first). */
+typedef struct lantern_gpu_compact_stats
+{
+    lantern_gpu_unlink_stats unlink;   /* the unlink the call performs first (all zero if there was nothing to unlink) */
+    uint64_t rows_before, rows_after;                 /* usearch_size before / after */
+    uint64_t upper_blocks_before, upper_blocks_after;
+    uint64_t bytes_before, bytes_after;               /* lantern_gpu_memory_usage row_bytes + other_bytes */
+    uint64_t bytes_moved;                             /* bytes the compaction kernels wrote */
+} lantern_gpu_compact_stats;
+LANTERN_GPU_EXPORT void lantern_gpu_compact_deleted(usearch_index_t, size_t capacity, uint32_t *slot_map /* [rows_before] or NULL */,
+                                                    lantern_gpu_compact_stats *out /* or NULL */, usearch_error_t *);
+/* diagnostics: HIP-event times, in ms, of the last call that moved rows: out[0] all its kernels (map, rows, screen, codes, lists, metadata),
+ * out[1] the row kernel over the vector block alone (what scripts/bench_compact.py holds against a device-to-device copy) */
+LANTERN_GPU_EXPORT void lantern_gpu_last_compact_ms(usearch_index_t, float *out /* [2] */, usearch_error_t *);
+/* the same arithmetic without a device (pure: no HIP call, no index): map as above, upper_off_new[j] = the levels of the live slots
+ * below new slot j, *live and *upper_blocks their totals.  Every output may be NULL. */
+LANTERN_GPU_EXPORT void lantern_gpu_plan_compact(const uint64_t *labels, const uint8_t *levels, size_t n, uint32_t *slot_map /* [n] */,
+                                                 uint32_t *upper_off_new /* [live] */, uint64_t *live, uint64_t *upper_blocks, usearch_error_t *);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Work-sharded index build over the GPUs of one node (the reference's     */

@@ -82,6 +82,11 @@ class UnlinkStats(C.Structure):
                                           "entry_moved")]
 
 
+class CompactStats(C.Structure):
+    _fields_ = [("unlink", UnlinkStats)] + [(n, C.c_uint64) for n in ("rows_before", "rows_after", "upper_blocks_before", "upper_blocks_after",
+                                                                      "bytes_before", "bytes_after", "bytes_moved")]
+
+
 EXPORTS = [
     "usearch_init", "usearch_free", "usearch_reserve", "usearch_size", "usearch_capacity", "usearch_dimensions",
     "usearch_add", "usearch_add_external", "usearch_search_ef", "lantern_gpu_cursor_open", "lantern_gpu_cursor_search",
@@ -133,7 +138,7 @@ EXPORTS = [
     # diagnostics of the int8 screen (lantern_gpu.h lantern_gpu_export_screen)
     "lantern_gpu_export_screen", "lantern_gpu_screen_probe",
     # deleting rows (lantern_gpu.h "Deleting rows")
-    "lantern_gpu_remove_labels", "lantern_gpu_deleted_count", "lantern_gpu_unlink_deleted",
+    "lantern_gpu_remove_labels", "lantern_gpu_deleted_count", "lantern_gpu_unlink_deleted", "lantern_gpu_compact_deleted", "lantern_gpu_plan_compact", "lantern_gpu_last_compact_ms",
 ]
 # lantern_gpu_query_params: one row {k, ef, skip, reserved} per query (ef 0 = the index's default; reserved must be 0)
 QUERY_PARAMS = np.dtype([("k", np.uint32), ("ef", np.uint32), ("skip", np.uint32), ("reserved", np.uint32)])
@@ -374,6 +379,9 @@ def lib() -> C.CDLL:
         "lantern_gpu_remove_labels": (None, [vp, vp, sz, C.POINTER(u64), err]),
         "lantern_gpu_deleted_count": (sz, [vp, err]),
         "lantern_gpu_unlink_deleted": (None, [vp, C.POINTER(UnlinkStats), err]),
+        "lantern_gpu_compact_deleted": (None, [vp, sz, vp, C.POINTER(CompactStats), err]),
+        "lantern_gpu_last_compact_ms": (None, [vp, vp, err]),
+        "lantern_gpu_plan_compact": (None, [vp, vp, sz, vp, vp, C.POINTER(u64), C.POINTER(u64), err]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = the library does not export what the header declares
@@ -749,6 +757,22 @@ class GpuIndex:
         st = UnlinkStats()
         _call("lantern_gpu_unlink_deleted", self.h, C.byref(st))
         return {n: int(getattr(st, n)) for n, _ in UnlinkStats._fields_}
+
+    def compact_deleted(self, capacity=0):
+        """lantern_gpu_compact_deleted: unlink, then renumber the live slots and free the tombstones' memory.  Returns (stats, slot_map):
+        the call's stats (`unlink`: the unlink's own) and old slot -> new slot, 0xFFFFFFFF for a deleted row."""
+        st = CompactStats()
+        slot_map = np.zeros(len(self), dtype=np.uint32)  # (len() flushes: the size the call will see)
+        _call("lantern_gpu_compact_deleted", self.h, int(capacity), _ptr(slot_map) if slot_map.size else None, C.byref(st))
+        out = {n: int(getattr(st, n)) for n, _ in CompactStats._fields_ if n != "unlink"}
+        out["unlink"] = {n: int(getattr(st.unlink, n)) for n, _ in UnlinkStats._fields_}
+        return out, slot_map
+
+    def last_compact_ms(self):
+        """(ms of all kernels, ms of the row kernel over the vector block) of the last compact_deleted() that moved rows"""
+        out = np.zeros(2, dtype=np.float32)
+        _call("lantern_gpu_last_compact_ms", self.h, _ptr(out))
+        return float(out[0]), float(out[1])
 
     def search(self, query, k, ef=0, streaming=False):
         """usearch_search_ef: (labels, distances) of length <= k."""
@@ -1307,6 +1331,18 @@ def level_for(seed: int, slot: int, M: int) -> int:
 def plan_batch(size: int, max_level: int, pending_levels, max_batch: int, min_ratio: int) -> int:
     lv = np.ascontiguousarray(pending_levels, dtype=np.int32)
     return int(lib().lantern_gpu_plan_batch(size, max_level, _ptr(lv), lv.size, max_batch, min_ratio))
+
+
+def plan_compact(labels, levels):
+    """lantern_gpu_plan_compact (no device): (slot_map [n], upper_off_new [live], live, upper_blocks) of a compaction of these slots."""
+    lab = np.ascontiguousarray(labels, dtype=np.uint64).reshape(-1)
+    lev = np.ascontiguousarray(levels, dtype=np.uint8).reshape(-1)
+    assert lab.size == lev.size
+    slot_map, upper_off = np.zeros(lab.size, dtype=np.uint32), np.zeros(max(lab.size, 1), dtype=np.uint32)
+    live, blocks = C.c_uint64(), C.c_uint64()
+    _call("lantern_gpu_plan_compact", _ptr(lab) if lab.size else None, _ptr(lev) if lev.size else None, lab.size, _ptr(slot_map) if lab.size else None,
+          _ptr(upper_off), C.byref(live), C.byref(blocks))
+    return slot_map, upper_off[:int(live.value)], int(live.value), int(blocks.value)
 
 
 # a row of lantern_gpu_last_search_cells, in order (include/lantern_gpu.h)

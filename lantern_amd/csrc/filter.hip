@@ -91,6 +91,7 @@ static Filter *filter_new(Index *ix)
     f->ix = ix;
     f->device = ix->device;
     f->n = ix->n;
+    f->epoch = ix->epoch;
     f->words = ((std::max<size_t>(ix->n, 1) + 31) / 32 + 3) / 4 * 4;
     if(hipMalloc((void **)&f->d_bits, f->words * 4) != hipSuccess || hipMemset(f->d_bits, 0, f->words * 4) != hipSuccess) {
         set_err(ix, "lantern_gpu: out of device memory (filter bitmap)");
@@ -258,6 +259,8 @@ static std::string filter_mismatch(const Index *ix, const Filter *f)
 {
     if(f->ix != ix)
         return "lantern_gpu: the filter belongs to another index (built over " + std::to_string(f->n) + " rows; this index holds " + std::to_string(ix->n) + ")";
+    if(f->epoch != ix->epoch)  // (before the size: a delete / compact / add sequence may bring the size back)
+        return "lantern_gpu: stale filter: the index was compacted since the filter was built (its slots name other rows now; build the filter again)";
     if(f->n != ix->n)
         return "lantern_gpu: stale filter: built when the index held " + std::to_string(f->n) + " rows, it now holds " + std::to_string(ix->n) +
                " (build the filter again)";
@@ -629,7 +632,7 @@ static bool filtered_each_params_locked(Index *ix, const EachParamsPlan &plan, c
 static size_t cursor_search_filtered_locked(Index *ix, const Filter *f, Cursor *cur, const void *query, int kind, size_t k, size_t ef, bool streaming,
                                             uint64_t *labels, float *distances)
 {
-    if(!streaming) cur->seen.clear();
+    if(!cursor_epoch_ok(ix, cur, streaming)) return 0;
     if(ix->n == 0 || k == 0) return 0;
     const size_t want = std::max<size_t>(1, std::min(cur->seen.size() + k, std::max<size_t>(f->count, 1)));
     const size_t row = (size_t)ix->chunks * 16;

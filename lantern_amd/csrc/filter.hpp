@@ -21,6 +21,7 @@ struct Filter
     Index    *ix = nullptr;
     int       device = 0;
     size_t    n = 0;                // the index's size when the filter was built
+    uint64_t  epoch = 0;            // ... and its Index::epoch: a compaction renumbers the slots (lantern_gpu_compact_deleted)
     size_t    words = 0;            // 32-bit words of the bitmap (whole multiples of 4)
     uint32_t *d_bits = nullptr;     // [words]: bit s of word s / 32 = slot s is allowed; bits >= n are zero
     uint32_t *d_slots = nullptr;    // [count]: the allowed slots, ascending (the exact path's work list)

@@ -145,6 +145,14 @@ bool rows_stored(Index *ix, size_t first, size_t count)
     return true;
 }
 
+void index_memory_bytes(const Index *ix, size_t &row_bytes, size_t &other_bytes)
+{
+    const size_t cap = ix->cap;
+    row_bytes = ix->pq_compact ? std::max<size_t>(ix->n, 1) * ix->pq_S16 : (ix->d_vec ? cap * (size_t)ix->chunks * 16 : 0);
+    other_bytes = cap * ((size_t)ix->M0 * 4 + 8 + 1 + 4 + 4) + ix->upper_cap * ((size_t)ix->M * 4 + 4) + (ix->d_norm2 ? cap * 4 : 0) +
+                  (ix->pq ? cap * (size_t)ix->pq_S : 0) + (ix->d_screen ? cap * ((size_t)screen_chunks_for(ix->chunks) * 16 + 8) : 0);
+}
+
 // ---- product quantisation -------------------------------------------------------------------------------------------
 // Rows [first, first + count) of the vector block hold the caller's f32 vectors: replace each by its quantisation.
 // Per subvector the nearest centroid under the index metric, the first minimum winning -- the rule of the reference's
@@ -865,7 +873,7 @@ bool flush_locked(Index *ix)
 size_t search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, size_t k, size_t ef, bool streaming, uint64_t *labels,
                          float *distances)
 {
-    if(!streaming) cur->seen.clear();
+    if(!cursor_epoch_ok(ix, cur, streaming)) return 0;
     if(ix->n == 0 || k == 0) return 0;
     const size_t want = std::min(cur->seen.size() + k, ix->n);  // enough to find k unseen ones
     const size_t row = (size_t)ix->chunks * 16;
@@ -920,6 +928,15 @@ size_t search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, si
     uint32_t got;
     std::memcpy(&got, host + want * 16, 4);
     return take_unseen(cur, (const uint64_t *)host, (const float *)(host + want * 8), (const uint32_t *)(host + want * 12), got, k, labels, distances);
+}
+
+bool cursor_epoch_ok(Index *ix, Cursor *cur, bool streaming)
+{
+    if(!streaming) cur->seen.clear();
+    if(cur->seen.empty()) cur->epoch = ix->epoch;
+    if(cur->epoch == ix->epoch) return true;
+    set_err(ix, "lantern_gpu: the index was compacted: rescan (the cursor's rows were handed out under slot numbers that no longer hold)");
+    return false;
 }
 
 size_t take_unseen(Cursor *cur, const uint64_t *labels, const float *dists, const uint32_t *slots, uint32_t got, size_t k, uint64_t *out_labels,
@@ -2325,11 +2342,10 @@ try {
     Index *ix = H(h, e);
     if(!ix) return;
     std::lock_guard<std::mutex> g(ix->mu);
-    const size_t cap = ix->cap;
-    if(row_bytes) *row_bytes = ix->pq_compact ? std::max<size_t>(ix->n, 1) * ix->pq_S16 : (ix->d_vec ? cap * (size_t)ix->chunks * 16 : 0);
-    if(other_bytes)
-        *other_bytes = cap * ((size_t)ix->M0 * 4 + 8 + 1 + 4 + 4) + ix->upper_cap * ((size_t)ix->M * 4 + 4) + (ix->d_norm2 ? cap * 4 : 0) +
-                       (ix->pq ? cap * (size_t)ix->pq_S : 0) + (ix->d_screen ? cap * ((size_t)screen_chunks_for(ix->chunks) * 16 + 8) : 0);
+    size_t rows = 0, other = 0;
+    index_memory_bytes(ix, rows, other);
+    if(row_bytes) *row_bytes = rows;
+    if(other_bytes) *other_bytes = other;
 }
 LANTERN_ABI_CATCH_VOID(e)
 

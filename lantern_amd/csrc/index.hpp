@@ -22,6 +22,7 @@ namespace lgpu {
 struct Cursor
 {
     std::unordered_set<uint32_t> seen;
+    uint64_t                     epoch = 0;  // Index::epoch when `seen` was started: slots of another epoch name other rows (cursor_epoch_ok)
 };
 
 constexpr int kIndexLanes = 8;  // Index::kLanes, Index::kSearchSlots
@@ -97,6 +98,9 @@ struct Index
     uint32_t entry = EMPTY;
     int      max_level = -1;
     size_t   upper_blocks = 0, upper_cap = 0;
+    // bumped by every lantern_gpu_compact_deleted that moved a row: slots mean other rows afterwards, so whatever remembers slots -- a
+    // Filter, a Cursor's `seen` -- records the epoch it was made in and is refused in another
+    uint64_t epoch = 0;
 
     // ---- HBM ---------------------------------------------------------------------------------------
     uint4    *d_vec = nullptr;
@@ -158,6 +162,7 @@ struct Index
     size_t                  trace_nq = 0, trace_cap = 0;
     bool                    trace_on = false;
     float                   last_gather_ms = 0.f;   // kernel time of the last lantern_gpu_distance_gather launch (HIP events on the index stream)
+    float                   last_compact_ms[ 2 ] = {};  // the last compaction that moved rows: all its kernels; k_compact_rows over the vector block alone (lantern_gpu_last_compact_ms)
     int                     last_search_grid = 0;   // workgroups of the last unfiltered search launch, whatever its path (lantern_gpu_last_search_grid)
     std::deque<ProfBatch>   prof_pending;
     std::vector<hipEvent_t> prof_free;
@@ -281,6 +286,9 @@ bool      batch_download(const HostBatch &b);  // queue d_out -> staging
 void      batch_unpack(const HostBatch &b, size_t first, size_t count, uint64_t *labels, float *distances, uint32_t *counts /* or NULL */);  // staged rows -> the caller's arrays
 // under ix->mu throughout: the answers down, the wait, the caller's arrays; false -> ix->err (`what` if nothing more specific is there)
 bool      batch_finish_locked(Index *ix, const HostBatch &b, bool ok, const char *what, uint64_t *labels, float *distances, uint32_t *counts);
+// Before a search on behalf of `cur` (ix->mu held): a non-streaming call starts the scan over; an empty `seen` set adopts the index's
+// epoch; slots remembered in an earlier epoch are refused (false -> ix->err: "the index was compacted: rescan")
+bool      cursor_epoch_ok(Index *ix, Cursor *cur, bool streaming);
 // the first k of `got` results whose slot `cur` has not handed out before, recorded in cur->seen as they are taken; returns how many
 size_t    take_unseen(Cursor *cur, const uint64_t *labels, const float *dists, const uint32_t *slots, uint32_t got, size_t k, uint64_t *out_labels,
                       float *out_dists);
@@ -427,6 +435,7 @@ bool        search_params_locked(Index *ix, const uint4 *d_queries, size_t nq, c
 size_t      search_one_locked(Index *ix, Cursor *cur, const void *query, int kind, size_t k, size_t ef, bool streaming,
                               uint64_t *labels, float *distances);
 // usearch_size of the index: for a mirror, the header's count plus what was inserted since
+void        index_memory_bytes(const Index *ix, size_t &row_bytes, size_t &other_bytes);  // lantern_gpu_memory_usage's two numbers (ix->mu held)
 inline size_t logical_size(const Index *ix) { return ix->page_mode ? ix->page_declared + (ix->n - ix->page_attach_n) : ix->n; }
 void        prof_resolve(Index *ix, size_t keep);          // fold finished batches' event times into ix->prof
 bool        order_launch(Index *ix, hipStream_t stream);   // before an insert batch (exclusive use of the index)

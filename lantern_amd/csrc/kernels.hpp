@@ -180,6 +180,37 @@ hipError_t launch_batch_layout(const uint8_t *levels, uint32_t b, uint32_t M, ui
 hipError_t launch_stage_small(const void *rows, const uint64_t *labels, const uint32_t *upper_off, const uint8_t *levels, uint32_t count, uint32_t chunks,
                               void *d_rows, uint64_t *d_labels, uint32_t *d_upper_off, uint8_t *d_levels, hipStream_t stream);
 
+// ---- compaction (compact.hip; lantern_gpu_compact_deleted) -------------------------------------------------------
+// The renumbering of n old slots, all in device memory.  Every array but src_of holds n + 1 words: word n of `map` is the number of live
+// slots, word n of `uoff` the upper blocks they own.
+struct CompactMap
+{
+    uint32_t *flags;   // [n + 1] scan input: 1 for a live slot (label != 0), 0 for a tombstone and at n
+    uint32_t *lv;      // [n + 1] scan input: a live slot's level, 0 for a tombstone and at n
+    uint32_t *map;     // [n + 1] old slot -> new slot (the live slots below it), EMPTY for a tombstone
+    uint32_t *uoff;    // [n + 1] old slot -> the first upper block of its new slot (the levels of the live slots below it)
+    uint32_t *src_of;  // [live]  new slot -> old slot
+    void     *temp;    // rocPRIM temporary storage
+    size_t    temp_bytes;
+};
+size_t     compact_temp_bytes(size_t n);
+hipError_t launch_compact_map(const uint64_t *labels, const uint8_t *levels, size_t n, const CompactMap &m, hipStream_t stream);
+// dst row j = src row src_of[j] for j < live, rows of row_bytes each (16-byte units where row_bytes is a multiple of 16, bytes otherwise)
+hipError_t launch_compact_rows(const void *src, void *dst, const uint32_t *src_of, size_t live, size_t row_bytes, int num_cus, hipStream_t stream);
+// level 0 (old_levels == NULL): list j of W entries = list src_of[j] through the map.  Upper levels: the level[src_of[j]] blocks of W
+// entries at old_uoff[src_of[j]] -> the blocks at m.uoff[src_of[j]].  *dangling += the entries that are neither EMPTY nor mapped.
+hipError_t launch_compact_lists(const uint32_t *old_nbr, uint32_t *new_nbr, const CompactMap &m, uint32_t n_old, size_t live, uint32_t W,
+                                const uint8_t *old_levels, const uint32_t *old_uoff, unsigned long long *dangling, int num_cus, hipStream_t stream);
+struct CompactMeta
+{
+    const uint64_t *labels;  uint64_t *new_labels;
+    const uint8_t  *levels;  uint8_t  *new_levels;
+    const float    *norm2;   float    *new_norm2;        // or NULL
+    const float2   *screen_meta; float2 *new_screen_meta; // or NULL
+    uint32_t       *new_upper_off;
+};
+hipError_t launch_compact_meta(const CompactMeta &a, const CompactMap &m, size_t live, hipStream_t stream);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device, size reached) instead of on every launch:
 // a driver call of microseconds that a lone query or a one-row insertion would repeat every time.  `cache` is a static of the
 // launcher's expansion for ONE instantiation: zero-initialised, [device ordinal] = the largest size set so far.

@@ -388,6 +388,192 @@ static bool unlink_locked(Index *ix, lantern_gpu_unlink_stats &st)
     return true;
 }
 
+// ---- compaction (kernels: compact.hip) ------------------------------------------------------------------------------------------
+// The arithmetic of the renumbering on the host: what lantern_gpu_plan_compact shows and what the device's two scans must agree with.
+static void plan_compact_host(const uint64_t *labels, const uint8_t *levels, size_t n, uint32_t *slot_map, uint32_t *upper_off_new, uint64_t &live,
+                              uint64_t &blocks)
+{
+    live = blocks = 0;
+    for(size_t s = 0; s < n; ++s) {
+        if(labels[ s ] == 0) {
+            if(slot_map) slot_map[ s ] = EMPTY;
+            continue;
+        }
+        if(slot_map) slot_map[ s ] = (uint32_t)live;
+        if(upper_off_new) upper_off_new[ live ] = (uint32_t)blocks;
+        ++live;
+        blocks += levels[ s ];
+    }
+}
+
+// the device arrays of an index that grow with its capacity, as reserve_locked sizes and fills them
+struct CompactArrays
+{
+    uint4    *vec = nullptr, *screen = nullptr;
+    float    *norm2 = nullptr, *radius0 = nullptr, *radius_upper = nullptr;
+    float2   *screen_meta = nullptr;
+    uint8_t  *codes = nullptr, *levels = nullptr;
+    uint64_t *labels = nullptr;
+    uint32_t *nbr0 = nullptr, *upper_off = nullptr, *upper_nbr = nullptr;
+    void     *temp = nullptr;  // the map's block (CompactMap)
+    void release()
+    {
+        void *all[] = { vec, screen, norm2, radius0, radius_upper, screen_meta, codes, levels, labels, nbr0, upper_off, upper_nbr, temp };
+        for(void *p : all)
+            if(p) (void)hipFree(p);
+        *this = CompactArrays();
+    }
+};
+
+static const char *kCompactFailed = "lantern_gpu: HIP failure while compacting the index";
+
+// The caller holds ix->mu, has flushed, has refused the index forms the compaction does not serve and has unlinked.  `dead` > 0.
+// false -> ix->err, and the index is exactly as it was: the new arrays are built beside the old ones and swapped in after the last
+// kernel has succeeded (transient peak: old + new + 20 bytes per old slot for the map).
+static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lantern_gpu_compact_stats &st)
+{
+    const size_t n = ix->n;
+    uint64_t     live = 0, blocks = 0;
+    plan_compact_host(ix->labels.data(), ix->levels.data(), n, nullptr, nullptr, live, blocks);
+    const size_t newcap = std::max<size_t>((size_t)live, capacity);
+    if(newcap >= 0x7FFFFFFFull) { set_err(ix, "lantern_gpu: capacity above 2^31-1 slots is not supported"); return false; }
+    const size_t row = (size_t)ix->chunks * 16, srow = ix->d_screen ? (size_t)screen_chunks_for(ix->chunks) * 16 : 0, codes = ix->pq ? ix->pq_S : 0;
+    const size_t M0 = ix->M0, M = ix->M;
+    const size_t temp_bytes = compact_temp_bytes(n), words = n + 1;
+    const size_t map_bytes = 5 * words * 4 + ((temp_bytes + 63) & ~(size_t)63) + 64;
+    // what one slot costs in the arrays sized by capacity (lantern_gpu_memory_usage's terms)
+    const size_t per_slot = row + srow + (srow ? 8 : 0) + codes + M0 * 4 + 8 + 1 + 4 + 4 + (ix->d_norm2 ? 4 : 0);
+    const size_t need = newcap * per_slot + (size_t)blocks * (M * 4 + 4) + map_bytes;
+    size_t rb = 0, ob = 0;
+    index_memory_bytes(ix, rb, ob);
+    st.rows_before = n;
+    st.upper_blocks_before = ix->upper_blocks;
+    st.bytes_before = rb + ob;
+
+    CompactArrays a;
+    auto          take = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 16)) == hipSuccess; };
+    bool got = take(&a.temp, map_bytes) && take((void **)&a.labels, newcap * 8) && take((void **)&a.levels, newcap) && take((void **)&a.nbr0, newcap * M0 * 4) &&
+               take((void **)&a.upper_off, newcap * 4) && take((void **)&a.radius0, newcap * 4) && take((void **)&a.upper_nbr, (size_t)blocks * M * 4) &&
+               take((void **)&a.radius_upper, (size_t)blocks * 4) && take((void **)&a.vec, newcap * row);
+    if(got && ix->d_norm2) got = take((void **)&a.norm2, newcap * 4);
+    if(got && srow) got = take((void **)&a.screen, newcap * srow) && take((void **)&a.screen_meta, newcap * 8);
+    if(got && codes) got = take((void **)&a.codes, newcap * codes);
+    if(!got) {
+        a.release();
+        set_err(ix, "lantern_gpu: out of device memory: the compaction builds the new arrays beside the old ones and needs " + std::to_string(need) +
+                        " bytes for them; the index is unchanged");
+        return false;
+    }
+    auto fail = [&](const std::string &msg) {
+        (void)hipStreamSynchronize(ix->stream);
+        a.release();
+        set_err(ix, msg);
+        return false;
+    };
+    CompactMap m;
+    m.flags = (uint32_t *)a.temp;
+    m.lv = m.flags + words;
+    m.map = m.lv + words;
+    m.uoff = m.map + words;
+    m.src_of = m.uoff + words;
+    m.temp = (void *)(((uintptr_t)(m.src_of + words) + 63) & ~(uintptr_t)63);
+    m.temp_bytes = temp_bytes;
+    unsigned long long *d_dangling = (unsigned long long *)scratch(ix, kScratchCallOut, 64);
+    if(!d_dangling || !order_launch(ix, ix->stream)) return fail(kCompactFailed);  // a graph mutation: ordered as an insertion batch
+    hipStream_t q = ix->stream;
+    // the tails beyond the live slots, as reserve_locked fills a grown array
+    bool ok = hipMemsetAsync(d_dangling, 0, 8, q) == hipSuccess && hipMemsetAsync(a.levels, 0, std::max<size_t>(newcap, 16), q) == hipSuccess &&
+              hipMemsetAsync(a.nbr0, 0xFF, std::max<size_t>(newcap * M0 * 4, 16), q) == hipSuccess &&
+              hipMemsetAsync(a.upper_off, 0xFF, std::max<size_t>(newcap * 4, 16), q) == hipSuccess &&
+              hipMemsetAsync(a.radius0, 0xFF, std::max<size_t>(newcap * 4, 16), q) == hipSuccess &&
+              hipMemsetAsync(a.radius_upper, 0xFF, std::max<size_t>((size_t)blocks * 4, 16), q) == hipSuccess;
+    if(ok && a.screen && newcap > live)
+        ok = hipMemsetAsync((char *)a.screen + (size_t)live * srow, 0, (newcap - (size_t)live) * srow, q) == hipSuccess &&
+             hipMemsetAsync(a.screen_meta + live, 0, (newcap - (size_t)live) * 8, q) == hipSuccess;
+    if(ok && a.codes && newcap > live) ok = hipMemsetAsync(a.codes + (size_t)live * codes, 0, (newcap - (size_t)live) * codes, q) == hipSuccess;
+    if(!ok) return fail(kCompactFailed);
+    CompactMeta cm;
+    cm.labels = ix->d_labels, cm.new_labels = a.labels;
+    cm.levels = ix->d_levels, cm.new_levels = a.levels;
+    cm.norm2 = ix->d_norm2, cm.new_norm2 = a.norm2;
+    cm.screen_meta = ix->d_screen_meta, cm.new_screen_meta = a.screen_meta;
+    cm.new_upper_off = a.upper_off;
+    hipEvent_t ev[ 4 ] = {};  // all kernels: [0, 3]; the row kernel over the vector block: [1, 2] (lantern_gpu_last_compact_ms)
+    for(hipEvent_t &x : ev) ok = ok && hipEventCreate(&x) == hipSuccess;
+    auto drop_events = [&] {
+        for(hipEvent_t x : ev)
+            if(x) (void)hipEventDestroy(x);
+    };
+    ok = ok && hipEventRecord(ev[ 0 ], q) == hipSuccess && launch_compact_map(ix->d_labels, ix->d_levels, n, m, q) == hipSuccess &&
+         hipEventRecord(ev[ 1 ], q) == hipSuccess && launch_compact_rows(ix->d_vec, a.vec, m.src_of, (size_t)live, row, ix->num_cus, q) == hipSuccess &&
+         hipEventRecord(ev[ 2 ], q) == hipSuccess &&
+         (!srow || launch_compact_rows(ix->d_screen, a.screen, m.src_of, (size_t)live, srow, ix->num_cus, q) == hipSuccess) &&
+         (!codes || launch_compact_rows(ix->d_codes, a.codes, m.src_of, (size_t)live, codes, ix->num_cus, q) == hipSuccess) &&
+         launch_compact_lists(ix->d_nbr0, a.nbr0, m, (uint32_t)n, (size_t)live, (uint32_t)M0, nullptr, nullptr, d_dangling, ix->num_cus, q) == hipSuccess &&
+         (!blocks || launch_compact_lists(ix->d_upper_nbr, a.upper_nbr, m, (uint32_t)n, (size_t)live, (uint32_t)M, ix->d_levels, ix->d_upper_off, d_dangling,
+                                          ix->num_cus, q) == hipSuccess) &&
+         launch_compact_meta(cm, m, (size_t)live, q) == hipSuccess && hipEventRecord(ev[ 3 ], q) == hipSuccess;
+    if(!ok) { drop_events(); return fail(kCompactFailed); }
+    // the map, the totals of the two scans, the check and the host mirrors of the new slots
+    std::vector<uint32_t> h_map(words), h_uoff((size_t)live);
+    std::vector<uint64_t> h_labels((size_t)live);
+    std::vector<uint8_t>  h_levels((size_t)live);
+    unsigned long long    dangling = 0;
+    uint32_t              d_blocks = 0;
+    ok = hipMemcpyAsync(h_map.data(), m.map, words * 4, hipMemcpyDeviceToHost, q) == hipSuccess &&
+         hipMemcpyAsync(&d_blocks, m.uoff + n, 4, hipMemcpyDeviceToHost, q) == hipSuccess &&
+         hipMemcpyAsync(&dangling, d_dangling, 8, hipMemcpyDeviceToHost, q) == hipSuccess;
+    if(ok && live)
+        ok = hipMemcpyAsync(h_uoff.data(), a.upper_off, (size_t)live * 4, hipMemcpyDeviceToHost, q) == hipSuccess &&
+             hipMemcpyAsync(h_labels.data(), a.labels, (size_t)live * 8, hipMemcpyDeviceToHost, q) == hipSuccess &&
+             hipMemcpyAsync(h_levels.data(), a.levels, (size_t)live, hipMemcpyDeviceToHost, q) == hipSuccess;
+    ok = ok && hipStreamSynchronize(q) == hipSuccess;
+    float ms_all = 0.f, ms_rows = 0.f;
+    if(ok) (void)hipEventElapsedTime(&ms_all, ev[ 0 ], ev[ 3 ]), (void)hipEventElapsedTime(&ms_rows, ev[ 1 ], ev[ 2 ]);
+    drop_events();
+    if(!ok) return fail(kCompactFailed);
+    if(h_map[ n ] != live || d_blocks != blocks) return fail("lantern_gpu: the device's renumbering disagrees with the host's plan; the index is unchanged");
+    if(dangling) return fail("lantern_gpu: " + std::to_string(dangling) + " entries of live lists name a deleted row after the unlink; the index is unchanged");
+    if(live && (ix->entry >= n || h_map[ ix->entry ] == EMPTY)) return fail("lantern_gpu: the entry node is a deleted row after the unlink; the index is unchanged");
+    if(!record_launch(ix, q)) return fail(kCompactFailed);
+
+    // ---- the swap: nothing below can fail ----
+    void *old[] = { ix->d_vec, ix->d_norm2, ix->d_screen, ix->d_screen_meta, ix->d_codes, ix->d_labels, ix->d_levels, ix->d_nbr0, ix->d_upper_off, ix->d_upper_nbr,
+                    ix->d_radius0, ix->d_radius_upper, ix->d_bitmaps, ix->d_touched, a.temp };
+    for(void *p : old)
+        if(p) (void)hipFree(p);
+    for(int sl = 1; sl < Index::kSearchSlots; ++sl)
+        if(ix->slot_bitmaps[ sl ]) (void)hipFree(ix->slot_bitmaps[ sl ]);
+    for(int sl = 0; sl < Index::kSearchSlots; ++sl) ix->slot_bitmaps[ sl ] = nullptr, ix->slot_rows[ sl ] = ix->slot_words[ sl ] = 0;
+    ix->d_bitmaps = nullptr, ix->bitmap_slots = ix->bm_words = 0;  // sized by capacity: allocated again on first use
+    ix->d_touched = nullptr, ix->touched_words = 0;
+    ix->d_vec = a.vec, ix->d_norm2 = a.norm2, ix->d_screen = a.screen, ix->d_screen_meta = a.screen_meta, ix->d_codes = a.codes;
+    ix->d_labels = a.labels, ix->d_levels = a.levels, ix->d_nbr0 = a.nbr0, ix->d_upper_off = a.upper_off, ix->d_upper_nbr = a.upper_nbr;
+    ix->d_radius0 = a.radius0, ix->d_radius_upper = a.radius_upper;
+    ix->radius_stale = true;  // the re-prune state is not moved
+    ix->cap = newcap;
+    ix->upper_cap = ix->upper_blocks = (size_t)blocks;
+    ix->n = (size_t)live;
+    ix->entry = live ? h_map[ ix->entry ] : EMPTY;
+    if(!live) ix->max_level = -1;
+    ix->labels.swap(h_labels);
+    ix->levels.swap(h_levels);
+    ix->upper_off.swap(h_uoff);
+    std::unordered_set<uint32_t> seen;  // usearch_search_ef's own scan goes on: its slots through the map
+    for(uint32_t s : ix->default_cursor.seen)
+        if(s < n && h_map[ s ] != EMPTY) seen.insert(h_map[ s ]);
+    ix->default_cursor.seen.swap(seen);
+    ix->default_cursor.epoch = ++ix->epoch;
+    ix->last_compact_ms[ 0 ] = ms_all, ix->last_compact_ms[ 1 ] = ms_rows;
+    if(slot_map) std::memcpy(slot_map, h_map.data(), n * 4);
+    index_memory_bytes(ix, rb, ob);
+    st.rows_after = live;
+    st.upper_blocks_after = blocks;
+    st.bytes_after = rb + ob;
+    st.bytes_moved = live * (uint64_t)(row + srow + (srow ? 8 : 0) + codes + M0 * 4 + 8 + 1 + 4 + (ix->d_norm2 ? 4 : 0)) + blocks * (uint64_t)(M * 4);
+    return true;
+}
+
 }  // namespace lgpu
 
 using namespace lgpu;
@@ -446,6 +632,72 @@ try {
         return;
     }
     if(out) *out = st;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_compact_deleted(usearch_index_t h, size_t capacity, uint32_t *slot_map, lantern_gpu_compact_stats *out, usearch_error_t *e)
+try {
+    CLEAR(e);
+    lantern_gpu_compact_stats st;
+    std::memset(&st, 0, sizeof(st));
+    if(out) *out = st;
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(ix->page_mode) {
+        FAIL(e, set_err(ix, "lantern_gpu: compaction does not run on a page-attached index: its rows and lists would have to go back through retriever_mut"));
+        return;
+    }
+    if(ix->pq_compact) {
+        FAIL(e, set_err(ix, "lantern_gpu: compaction does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)"));
+        return;
+    }
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    ix->err.clear();
+    if(!unlink_locked(ix, st.unlink)) {
+        if(ix->err.empty()) set_err(ix, kUnlinkFailed);
+        FAIL(e, ix->err.c_str());
+        return;
+    }
+    if(deleted_count_locked(ix) == 0) {  // nothing to reclaim: no stat moves, `capacity` is ignored, the epoch stays
+        if(slot_map)
+            for(size_t s = 0; s < ix->n; ++s) slot_map[ s ] = (uint32_t)s;
+        return;
+    }
+    lantern_gpu_compact_stats moved = st;
+    if(!compact_locked(ix, capacity, slot_map, moved)) {
+        if(ix->err.empty()) set_err(ix, kCompactFailed);
+        FAIL(e, ix->err.c_str());
+        if(out) *out = st;  // the unlink happened
+        return;
+    }
+    if(out) *out = moved;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_last_compact_ms(usearch_index_t h, float *out, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(out) out[ 0 ] = out[ 1 ] = 0.f;
+    Index *ix = H(h, e);
+    if(!ix || !out) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    out[ 0 ] = ix->last_compact_ms[ 0 ], out[ 1 ] = ix->last_compact_ms[ 1 ];
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_plan_compact(const uint64_t *labels, const uint8_t *levels, size_t n, uint32_t *slot_map, uint32_t *upper_off_new, uint64_t *live,
+                              uint64_t *upper_blocks, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(live) *live = 0;
+    if(upper_blocks) *upper_blocks = 0;
+    if(n && (!labels || !levels)) { FAIL(e, "lantern_gpu: null label or level array"); return; }
+    if(n >= 0x7FFFFFFFull) { FAIL(e, "lantern_gpu: capacity above 2^31-1 slots is not supported"); return; }
+    uint64_t l = 0, b = 0;
+    plan_compact_host(labels, levels, n, slot_map, upper_off_new, l, b);
+    if(live) *live = l;
+    if(upper_blocks) *upper_blocks = b;
 }
 LANTERN_ABI_CATCH_VOID(e)
 
