@@ -411,8 +411,41 @@ LANTERN_GPU_EXPORT void lantern_gpu_filter_stats(usearch_index_t, uint64_t *walk
 /* the shape of the last filtered launch on this index (diagnostic; tests assert the regime a launch ran in):
  * out[0] path (1 walk, 2 exact), [1] workgroups, [2] expansion (walk: max(ef, k + skip); exact: k + skip), [3] candidate cap C of the walk
  * (0 on the exact path), [4] LDS visited-set slots of the walk (0 = HBM bitmap only; 0 on the exact path), [5] dynamic LDS bytes per
- * workgroup.  All zero before the first filtered launch and after a call that launched nothing (an empty filter). */
+ * workgroup.  All zero before the first filtered launch and after a call that launched nothing (an empty filter).
+ * A call answered by the dense route (lantern_gpu_set_filter_dense) reports out[0] = 3, out[2] = k + skip and 0 in every other field. */
 LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_launch(usearch_index_t, uint32_t out[6], usearch_error_t *);
+/* THE EXACT PATH'S DENSE ROUTE (DESIGN.md 4.9 "Dense exact path"): a second implementation of the exact path for a batch of queries
+ * behind ONE filter.  The exact pass reads every allowed row once per query; the dense route gathers the allowed rows into contiguous
+ * chunks once per call and contracts them against all the queries on the matrix cores, as lantern_gpu_exact_search does with the whole
+ * index -- top-(k + skip + 16) by the contraction, re-ranked with the walk's per-pair reduction, certified per query, and the queries the
+ * certificate refuses answered by the exact pass itself.  Every output is the exact pass's: slots, distance bits, labels, counts,
+ * D (= allowed), E (= 0), the tails of short rows and the cumulative counters; only the launches differ.  The path rule is untouched:
+ * which filters go exact is still lantern_gpu_set_filter_policy's.
+ * min_queries = 0, THE DEFAULT: off; every call issues the launches it issued before this switch existed.
+ * min_queries = m > 0: a call of lantern_gpu_search_batch_filtered or lantern_gpu_search_batch_filtered_device takes the dense route
+ *   when nq >= m, the path of its queries is exact (forced or by the rule), k + skip <= 240 (the exact k-NN's bound on k) and the index
+ *   is not a compact pq index.  Every other call runs the kernels it runs today: none is refused because of this setting.
+ * The per-query-filter calls, cursors, scans and the scan-side service never take it.
+ * SYNCHRONISATION: a call on the dense route waits for its stream before it returns -- the certificate's flags cross to the host --
+ * so lantern_gpu_search_batch_filtered_device, otherwise asynchronous, is synchronous for such a call (its answers are complete on
+ * return).  The gathered copy is not kept: a filter reused by a later call is gathered again. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_dense(usearch_index_t, size_t min_queries, usearch_error_t *);
+LANTERN_GPU_EXPORT size_t lantern_gpu_filter_dense(usearch_index_t, usearch_error_t *); /* the setting */
+/* since the index was created: out[0] calls answered by the dense route, [1] their queries, [2] of those the certificate passed,
+ * [3] of those recomputed by the exact pass ([1] = [2] + [3]; a call with [3] > 0 also counts one exact launch in lantern_gpu_filter_stats) */
+LANTERN_GPU_EXPORT void lantern_gpu_filter_dense_stats(usearch_index_t, uint64_t out[4], usearch_error_t *);
+/* The dense route's decision and buffers without a device (a pure function; the call itself plans through it).
+ * in[11]: [0] metric code (as lantern_gpu_plan_dense)  [1] 16-byte chunks per stored row  [2] allowed rows of the filter  [3] queries
+ *   [4] k  [5] skip  [6] the min_queries setting  [7] the queries' path is exact (0 / 1)  [8] the index is a compact pq index (0 / 1)
+ *   [9] LANTERN_GPU_DENSE_NATIVE (-1: unset)  [10] LANTERN_GPU_DENSE_FUSED (-1: unset)
+ * out[8]: [0] 1: the call takes the dense route  [1] why not: 0 taken, 1 the setting is 0, 2 nq < min_queries, 3 the path is the walk,
+ *   4 k + skip > 240, 5 a compact pq index, 6 nothing to launch (no allowed row, no query, k = 0)
+ *   and, when taken (0 otherwise): [2] kk = k + skip + 16 survivors per query  [3] rows per gathered chunk
+ *   [4] (low, high) bytes of the gather buffer: one chunk of rows as stored  [6] (low, high) bytes of the gathered rows' norm words
+ *   (0 for bit rows, which carry none)
+ * steps, cap, *n_steps: as lantern_gpu_plan_exact_knn's, and exactly its steps for (metric code, chunks, base rows = allowed, queries,
+ *   k + skip); none when the route is not taken.  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_dense(const int64_t in[11], uint32_t out[8], uint32_t steps[][4], size_t cap, size_t *n_steps);
 /* lantern_gpu_search_batch through a filter (host buffers; the unused tail of a row is label 0 and +inf) */
 LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered(usearch_index_t, const lantern_gpu_filter_t *, const void *queries, size_t nq,
                                                           usearch_scalar_kind_t, size_t k, size_t ef, usearch_label_t *labels,

@@ -126,6 +126,8 @@ EXPORTS = [
     "lantern_scan_client_clear_filter",
     "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
     "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds", "lantern_gpu_set_filter_compact", "lantern_gpu_filter_compact", "lantern_gpu_plan_filtered_compact",
+    # ... the exact path's dense route (lantern_gpu.h "THE EXACT PATH'S DENSE ROUTE")
+    "lantern_gpu_set_filter_dense", "lantern_gpu_filter_dense", "lantern_gpu_filter_dense_stats", "lantern_gpu_plan_filtered_dense",
     # ... with per-query k, ef and skip as well (lantern_gpu.h "PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_filtered_each_params", "lantern_gpu_search_batch_filtered_each_params_lane",
     "lantern_gpu_search_batch_filtered_each_params_device", "lantern_gpu_last_filtered_each_params", "lantern_gpu_plan_filtered_params",
@@ -358,6 +360,10 @@ def lib() -> C.CDLL:
         "lantern_gpu_plan_filtered_params": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_set_filter_seeds": (None, [vp, sz, err]),
         "lantern_gpu_set_filter_compact": (None, [vp, C.c_int, err]),
+        "lantern_gpu_set_filter_dense": (None, [vp, sz, err]),
+        "lantern_gpu_filter_dense": (sz, [vp, err]),
+        "lantern_gpu_filter_dense_stats": (None, [vp, vp, err]),
+        "lantern_gpu_plan_filtered_dense": (C.c_char_p, [vp, vp, vp, sz, vp]),
         "lantern_gpu_filter_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_filtered_compact": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
@@ -468,14 +474,15 @@ def version() -> str:
 
 def dense_profile(on: bool):
     """on=True: record HIP events around every MFMA contraction launch of the exact k-NN (fp32, or f16 / i8 on quantised indexes).  on=False: stop and return the records
-    as a list of dicts {ms, rows, cols, fused} (lantern_gpu_dense_profile)."""
+    as a list of dicts {ms, rows, cols, fused, gather} (lantern_gpu_dense_profile)."""
     if on:
         lib().lantern_gpu_dense_profile(1, None, None, None, None, 0)
         return None
     cap = 4096
     ms, rows, cols, fused = np.zeros(cap, np.float32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
     n = min(int(lib().lantern_gpu_dense_profile(0, _ptr(ms), _ptr(rows), _ptr(cols), _ptr(fused), cap)), cap)
-    return [{"ms": float(ms[i]), "rows": int(rows[i]), "cols": int(cols[i]), "fused": bool(fused[i])} for i in range(n)]
+    # (fused = 2 marks the gather of a chunk of a filter's slot list on the filtered dense route: rows = 0, cols = its rows)
+    return [{"ms": float(ms[i]), "rows": int(rows[i]), "cols": int(cols[i]), "fused": int(fused[i]) == 1, "gather": int(fused[i]) == 2} for i in range(n)]
 
 
 def exact_knn_stats():
@@ -525,6 +532,27 @@ def plan_exact_knn(mcode, chunks, nb, nq, k, native=-1, fused=-1):
     plan["n_steps"] = int(count.value)
     plan["steps"] = [(int(s[0]), int(s[1]), bool(s[2]), int(s[3])) for s in steps[:cap]]
     return plan
+
+
+# lantern_gpu_plan_filtered_dense's out[1], by value
+FILTERED_DENSE_WHY = ("taken", "off", "few_queries", "walk_path", "wide", "compact", "empty")
+
+
+def plan_filtered_dense(mcode, chunks, allowed, nq, k, skip=0, min_queries=0, exact=True, compact=False, native=-1, fused=-1):
+    """lantern_gpu_plan_filtered_dense: whether a single-filter call takes the exact path's dense route, and its buffers (host arithmetic,
+    no device): {"taken", "why" (FILTERED_DENSE_WHY), "kk", "gather_rows", "gather_bytes", "norm_bytes", "n_steps", "steps"}; the steps
+    as plan_exact_knn's."""
+    pin = np.array([mcode, chunks, allowed, nq, k, skip, min_queries, int(bool(exact)), int(bool(compact)), native, fused], np.int64)
+    out, count = np.zeros(8, np.uint32), C.c_size_t(0)
+    why = lib().lantern_gpu_plan_filtered_dense(_ptr(pin), _ptr(out), None, 0, C.byref(count))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    cap = min(count.value, 1 << 20)
+    steps = np.zeros((max(cap, 1), 4), np.uint32)
+    lib().lantern_gpu_plan_filtered_dense(_ptr(pin), _ptr(out), _ptr(steps), cap, C.byref(count))
+    return {"taken": bool(out[0]), "why": FILTERED_DENSE_WHY[int(out[1])], "kk": int(out[2]), "gather_rows": int(out[3]),
+            "gather_bytes": int(out[4]) | int(out[5]) << 32, "norm_bytes": int(out[6]) | int(out[7]) << 32, "n_steps": int(count.value),
+            "steps": [(int(s[0]), int(s[1]), bool(s[2]), int(s[3])) for s in steps[:cap]]}
 
 
 def l2sq_dist(a, b) -> float:
@@ -908,6 +936,20 @@ class GpuIndex:
         """Filtered searches serve this index in its compact pq form too (1), or refuse it (0, the default)."""
         _call("lantern_gpu_set_filter_compact", self.h, int(on))
 
+    def set_filter_dense(self, min_queries):
+        """Single-filter batch calls of at least min_queries queries on the exact path are answered by the dense route (0 = off, the default)."""
+        _call("lantern_gpu_set_filter_dense", self.h, int(min_queries))
+
+    def filter_dense(self):
+        """lantern_gpu_filter_dense: the min_queries setting."""
+        return int(_call("lantern_gpu_filter_dense", self.h))
+
+    def filter_dense_stats(self):
+        out = np.zeros(4, dtype=np.uint64)
+        _call("lantern_gpu_filter_dense_stats", self.h, _ptr(out))
+        calls, queries, certified, recomputed = (int(x) for x in out)
+        return {"calls": calls, "queries": queries, "certified": certified, "recomputed": recomputed}
+
     def filter_compact(self):
         """lantern_gpu_filter_compact: None (the switch is off), or what a filtered search runs on now: "stored", "decode" or "adc"."""
         return {0: None, 1: "stored", 2: "decode", 3: "adc"}[int(_call("lantern_gpu_filter_compact", self.h))]
@@ -929,7 +971,7 @@ class GpuIndex:
         out = np.zeros(6, dtype=np.uint32)
         _call("lantern_gpu_last_filtered_launch", self.h, _ptr(out))
         path, grid, exp, cap, vis, lds = (int(x) for x in out)
-        return {"path": {0: None, 1: "walk", 2: "exact"}[path], "grid": grid, "expansion": exp, "cand_cap": cap, "vis_slots": vis, "lds_bytes": lds}
+        return {"path": {0: None, 1: "walk", 2: "exact", 3: "dense"}[path], "grid": grid, "expansion": exp, "cand_cap": cap, "vis_slots": vis, "lds_bytes": lds}
 
     def search_batch_filtered(self, filt: "Filter", queries, k, ef=0):
         Q = _rows(queries, self.metric)

@@ -3,6 +3,8 @@
 // defined by lantern_cli/src/index_autotune/mod.rs:196-203,239-247).
 //
 //   k_row_norms    ||x||^2 per row (one G-lane group per row, same reduction as the walk)
+//   k_gather_rows_norms  the rows of a slot list gathered into a contiguous chunk, their norm words written in the same pass (the
+//                  filtered exact path's dense route)
 //   k_dense_f32    D[q][c] = metric(Q[q], B[c]) for a 128 x 128 tile per workgroup on fp32 MFMA
 //                  (v_mfma_f32_32x32x2_f32: f32 in, f32 accumulate -- bf16/fp16 would lose the 1e-5
 //                  tolerance ON F32 ROWS; rows that are stored as f16 or i8 lose nothing on the MFMAs of their
@@ -18,6 +20,7 @@
 #include "kernels.hpp"
 #include "walk.hpp"
 #include "dense_tile.hpp"
+#include "row_norms.hpp"
 
 namespace lgpu {
 
@@ -31,16 +34,41 @@ __global__ void __launch_bounds__(256) k_row_norms(const uint4 *rows, uint32_t n
     const uint32_t ngroups = gridDim.x * blockDim.x / G;
     for(uint32_t i = gid; i < n; i += ngroups) {
         const uint4 *r = rows + (size_t)i * chunks;
-        float        s = 0.f;
-        for(uint32_t ch = gl; ch < chunks; ch += G) {
-            uint4 x = r[ ch ];
-            s = __builtin_fmaf(__uint_as_float(x.x), __uint_as_float(x.x), s);
-            s = __builtin_fmaf(__uint_as_float(x.y), __uint_as_float(x.y), s);
-            s = __builtin_fmaf(__uint_as_float(x.z), __uint_as_float(x.z), s);
-            s = __builtin_fmaf(__uint_as_float(x.w), __uint_as_float(x.w), s);
+        NormAcc<0>   acc;
+        for(uint32_t ch = gl; ch < chunks; ch += G) acc.add(r[ ch ]);
+        const uint32_t s = acc.template finish<G>(0);
+        if(gl == G - 1) out[ i ] = __uint_as_float(s);
+    }
+}
+
+// k_gather_rows_norms: rows list[0..n) of src gathered into the contiguous dst, and in the same pass the norm word of each (NormAcc:
+// k_row_norms' arithmetic for the KIND) -- a row is read from HBM once, 2 x row bytes move per row.  One G-lane group per row; the slot
+// is one broadcast load per group; 16 bytes per lane and load, a block of four steps of a row (all of a row of up to 4 G chunks: 1024
+// f32 dims at G = 64) issued before the first is consumed.  norms may be NULL (KIND = kNormNone).
+template <int KIND, int G>
+__global__ void __launch_bounds__(256) k_gather_rows_norms(const uint4 *src, uint32_t chunks, const uint32_t *list, uint32_t n, uint4 *dst, uint32_t *norms,
+                                                           int cosine)
+{
+    const uint32_t gid = (blockIdx.x * blockDim.x + threadIdx.x) / G, gl = threadIdx.x % G;
+    const uint32_t ngroups = gridDim.x * blockDim.x / G;
+    for(uint32_t i = gid; i < n; i += ngroups) {
+        const uint4  *r = src + (size_t)list[ i ] * chunks;
+        uint4        *w = dst + (size_t)i * chunks;
+        NormAcc<KIND> acc;
+        for(uint32_t base = gl; base < chunks; base += 4 * G) {
+            // four steps per block.  A step past the row's end loads the block's first chunk again and is dropped: the loads are
+            // unconditional, so the four are issued together and stay in registers
+            const uint32_t c1 = base + G, c2 = base + 2 * G, c3 = base + 3 * G;
+            const bool     h1 = c1 < chunks, h2 = c2 < chunks, h3 = c3 < chunks;
+            const uint4    x0 = r[ base ], x1 = r[ h1 ? c1 : base ], x2 = r[ h2 ? c2 : base ], x3 = r[ h3 ? c3 : base ];
+            w[ base ] = x0;
+            acc.add(x0);
+            if(h1) { w[ c1 ] = x1; acc.add(x1); }
+            if(h2) { w[ c2 ] = x2; acc.add(x2); }
+            if(h3) { w[ c3 ] = x3; acc.add(x3); }
         }
-        s = group_sum<G>(s);
-        if(gl == G - 1) out[ i ] = s;
+        const uint32_t s = acc.template finish<G>(cosine);
+        if(KIND != kNormNone && gl == G - 1) norms[ i ] = s;
     }
 }
 
@@ -497,10 +525,12 @@ __global__ void __launch_bounds__(256) k_select(const float *dist, uint32_t ldo,
     if(cand && threadIdx.x == 0) cand_cnt[ q ] = 0;
 }
 
-// k_rerank: exact-order distances of the kk survivors, then the k smallest by (distance, slot)
+// k_rerank: exact-order distances of the kk survivors, then the k smallest by (distance, slot).  list == NULL: a key's low word is the
+// row's slot in B.  Otherwise it is a POSITION in the ascending slot list `list` (the rows were contracted as a gathered chunk): the
+// row read is B[list[pos]], the order is (distance, position) -- which is (distance, slot) -- and the emitted slot is list[pos].
 template <int METRIC, int G>
 __global__ void __launch_bounds__(256) k_rerank(const uint4 *Q, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk, uint32_t k,
-                                                uint32_t *out_slots, float *out_dists)
+                                                uint32_t *out_slots, float *out_dists, const uint32_t *list)
 {
     __shared__ uint64_t keys[ 256 ];
     const uint32_t q = blockIdx.x;
@@ -510,15 +540,16 @@ __global__ void __launch_bounds__(256) k_rerank(const uint4 *Q, const uint4 *B, 
     for(uint32_t i = g; i < kk; i += NG) {
         const uint64_t cand = best[ (size_t)q * kk + i ];
         if(cand == ~0ull) continue;
-        const uint32_t slot = (uint32_t)(cand & 0xFFFFFFFFu);
+        const uint32_t pos = (uint32_t)(cand & 0xFFFFFFFFu), slot = list ? list[ pos ] : pos;
         float          d = group_dist<METRIC, G>(Q + (size_t)q * chunks, B + (size_t)slot * chunks, (int)chunks, gl);
-        if(gl == G - 1) keys[ i ] = ((uint64_t)f2ord(d) << 32) | slot;
+        if(gl == G - 1) keys[ i ] = ((uint64_t)f2ord(d) << 32) | pos;
     }
     __syncthreads();
     bitonic_sort_lds(keys, 256);
     for(uint32_t i = tid; i < k; i += T) {
         const uint64_t key = keys[ i ];
-        out_slots[ (size_t)q * k + i ] = key == ~0ull ? EMPTY : (uint32_t)(key & 0xFFFFFFFFu);
+        const uint32_t pos = (uint32_t)(key & 0xFFFFFFFFu);
+        out_slots[ (size_t)q * k + i ] = key == ~0ull ? EMPTY : list ? list[ pos ] : pos;
         out_dists[ (size_t)q * k + i ] = key == ~0ull ? __builtin_inff() : ord2f((uint32_t)(key >> 32));
     }
 }
@@ -761,6 +792,29 @@ hipError_t launch_dequant_f16(const uint4 *src, size_t nchunks, uint4 *dst, hipS
     return hipGetLastError();
 }
 
+// kind: DenseOperands::kind of the rows, or kNormNone (norms unused).  n <= 65536 rows of a chunk: the grid covers them all
+hipError_t launch_gather_rows_norms(int kind, int metric, const uint4 *src, uint32_t chunks, const uint32_t *list, uint32_t n, uint4 *dst, void *norms,
+                                    hipStream_t stream)
+{
+    if(n == 0) return hipSuccess;
+    if(kind < 0 || kind > kNormNone || (kind != kNormNone && !norms)) return hipErrorInvalidValue;
+    const int G_ = group_lanes_for(chunks);
+    uint32_t  blocks = (uint32_t)(((uint64_t)n * G_ + 255) / 256);
+    if(blocks > 16384) blocks = 16384;
+    const int cosine = metric == M_COS ? 1 : 0;
+#define GN(KK, GG) hipLaunchKernelGGL((k_gather_rows_norms<KK, GG>), dim3(blocks), dim3(256), 0, stream, src, chunks, list, n, dst, (uint32_t *)norms, cosine)
+#define GNG(KK) switch(G_) { case 64: GN(KK, 64); break; case 32: GN(KK, 32); break; case 16: GN(KK, 16); break; default: GN(KK, 8); }
+    switch(kind) {
+        case 0: GNG(0); break;
+        case 1: GNG(1); break;
+        case 2: GNG(2); break;
+        default: GNG(kNormNone);
+    }
+#undef GNG
+#undef GN
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------
 hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream)
 {
@@ -857,11 +911,11 @@ hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, co
 }
 
 hipError_t launch_rerank(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
-                         uint32_t k, uint32_t *out_slots, float *out_dists, hipStream_t stream)
+                         uint32_t k, uint32_t *out_slots, float *out_dists, const uint32_t *list, hipStream_t stream)
 {
     if(nq == 0) return hipSuccess;
     const int G_ = group_lanes_for(chunks);
-#define RR(MM, GG) hipLaunchKernelGGL((k_rerank<MM, GG>), dim3(nq), dim3(256), 0, stream, Q, B, chunks, best, kk, k, out_slots, out_dists)
+#define RR(MM, GG) hipLaunchKernelGGL((k_rerank<MM, GG>), dim3(nq), dim3(256), 0, stream, Q, B, chunks, best, kk, k, out_slots, out_dists, list)
 #define RRG(MM) switch(G_) { case 64: RR(MM, 64); break; case 32: RR(MM, 32); break; case 16: RR(MM, 16); break; default: RR(MM, 8); }
     switch(metric) {
         case M_L2SQ: RRG(M_L2SQ); break;

@@ -1,5 +1,6 @@
 // dense.cpp -- the dense path's host side: distance matrices and the SQL-callable distances, and the exact k-NN (exact search, PQ
-// encoding, assign_to_clusters) as a pure plan (plan_exact_knn: lantern_gpu_plan_exact_knn shows it without a device) and one run of it.
+// encoding, assign_to_clusters) as a pure plan (plan_exact_knn: lantern_gpu_plan_exact_knn shows it without a device) and one run of it;
+// the same run over a filter's slot list is the filtered exact path's dense route (plan_filtered_dense, filtered_dense_device).
 // The kernels: bruteforce.hip, dense_native.hip; the two launchers this unit calls them through: kernels.hpp.
 #include "dense.hpp"
 #include "index.hpp"
@@ -44,7 +45,7 @@ struct DenseTimer  // records event `a` now and `b` on destruction, on the launc
     DenseLaunch l;
     hipStream_t st;
     bool        armed = false;
-    DenseTimer(hipStream_t s, uint32_t rows, uint32_t cols, bool fused) : st(s)
+    DenseTimer(hipStream_t s, uint32_t rows, uint32_t cols, uint32_t fused) : st(s)
     {
         if(!g_dense_profile.on) return;
         if(hipEventCreate(&l.a) != hipSuccess || hipEventCreate(&l.b) != hipSuccess) { (void)hipGetLastError(); return; }
@@ -68,11 +69,15 @@ struct DenseTimer  // records event `a` now and `b` on destruction, on the launc
 struct KnnPool
 {
     std::mutex mu;
-    void      *p[ 3 ] = { nullptr, nullptr, nullptr };
-    size_t     bytes[ 3 ] = { 0, 0, 0 };
+    void      *p[ 4 ] = { nullptr, nullptr, nullptr, nullptr };  // (3: a gathered chunk of a run over a slot list, pooled up to kGatherPoolMax)
+    size_t     bytes[ 4 ] = { 0, 0, 0, 0 };
 };
 KnnPool g_knn_pool[ 16 ];
 constexpr size_t kKnnPoolMax = (size_t)64 << 20;
+// The gathered chunk of a run over a slot list is pooled up to a full chunk of 4096-dimensional f32 rows (201 MB at 768-d): the dense
+// route of the filtered exact path answers a call in a fraction of a millisecond at small batches, and a hipMalloc / hipFree of the
+// chunk per call -- the free synchronises the device -- would be a large share of it.  The block stays with the process, as the pool's others.
+constexpr size_t kGatherPoolMax = (size_t)1 << 30;
 
 // every device allocation of this unit: block `which` of a pool if one is given and the block is small, allocated for the call
 // otherwise; released by the destructor
@@ -83,10 +88,10 @@ struct DeviceBlock
     DeviceBlock() = default;
     DeviceBlock(const DeviceBlock &) = delete;
     DeviceBlock &operator=(const DeviceBlock &) = delete;
-    bool get(size_t need, KnnPool *pool = nullptr, int which = 0)
+    bool get(size_t need, KnnPool *pool = nullptr, int which = 0, size_t pool_max = kKnnPoolMax)
     {
         if(need == 0) need = 16;
-        if(pool && need <= kKnnPoolMax) {
+        if(pool && need <= pool_max) {
             if(pool->bytes[ which ] < need) {
                 if(pool->p[ which ]) (void)hipFree(pool->p[ which ]);
                 pool->p[ which ] = nullptr;
@@ -203,36 +208,47 @@ KnnStep ExactKnnPlan::step(size_t i) const
 // One run of a plan.  certified: one flag per query (1: the certificate of DESIGN.md 4.5 holds -- the result is the exact answer; 0: the
 // caller recomputes the query in exact order, exact_knn_fallback).  *overflowed: a candidate list ran out of room (adversarially
 // ordered rows): the caller repeats the search unfused.
-static bool exact_knn_run(const ExactKnnPlan &p, const uint4 *d_base, const uint4 *d_q, uint32_t *d_slots, float *d_dists, hipStream_t st, bool *overflowed,
-                          std::vector<uint32_t> &certified)
+// d_list == NULL: the base rows are d_base[0, nb).  Otherwise they are d_base[d_list[0, nb)], d_list ascending (a filter's slot list):
+// every chunk is gathered into a contiguous block with its norms (k_gather_rows_norms) where the plain run points into d_base, the
+// keys hold positions in the list, and the re-rank reads and emits through it.
+static bool exact_knn_run(const ExactKnnPlan &p, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots, float *d_dists,
+                          hipStream_t st, bool *overflowed, std::vector<uint32_t> &certified)
 try {
     int dev = 0;
     (void)hipGetDevice(&dev);
     KnnPool *const               pool = (dev >= 0 && dev < 16) ? &g_knn_pool[ dev ] : nullptr;
     std::unique_lock<std::mutex> pool_lock;
     if(pool) pool_lock = std::unique_lock<std::mutex>(pool->mu);
-    DeviceBlock b_aux, b_dd, b_cand, b_fq, b_fb;  // (fq, fb: f32 copies of quantised rows -- the queries; one chunk of base rows)
+    DeviceBlock b_aux, b_dd, b_cand, b_fq, b_fb, b_gb;  // (fq, fb: f32 copies of quantised rows -- the queries; one chunk of base rows.  gb: a gathered chunk)
     const uint32_t nq = (uint32_t)p.nq, nb = (uint32_t)p.nb, kk = p.kk, chunks = p.chunks, fchunks = p.fchunks;
     const int      base_metric = mcode_base(p.mcode);
     auto dequant = [&](const uint4 *src, size_t nchunks, uint4 *dst) { return p.copy == 2 ? launch_dequant_i8(src, nchunks, dst, st) : launch_dequant_f16(src, nchunks, dst, st); };
     bool ok = b_aux.get(p.aux_bytes, pool, 0) && b_dd.get(p.dd_bytes, pool, 1);
     if(ok && p.fused) ok = b_cand.get(p.cand_bytes, pool, 2) && hipMemsetAsync(b_cand.as<char>() + p.cnt_off, 0, p.cand_bytes - p.cnt_off, st) == hipSuccess;
     if(ok && p.copy) ok = b_fq.get(p.fq_bytes) && b_fb.get(p.fb_bytes) && dequant(d_q, p.nq * chunks, b_fq.as<uint4>()) == hipSuccess;
+    if(ok && d_list) ok = p.gb_bytes >= (size_t)p.chunk_rows * chunks * 16 && b_gb.get(p.gb_bytes, pool, 3, kGatherPoolMax);
     if(ok) {
         char *const     aux = b_aux.as<char>();
         float *const    dd = b_dd.as<float>(), *qn = (float *)(aux + p.qn_off), *bn = (float *)(aux + p.bn_off);
         uint64_t *const best = (uint64_t *)(aux + p.best_off), *cand = b_cand.as<uint64_t>();
         uint32_t *const flag = (uint32_t *)(aux + p.flag_off);
         uint32_t *const ccnt = p.fused ? (uint32_t *)(b_cand.as<char>() + p.cnt_off) : nullptr, *cover = p.fused ? (uint32_t *)(b_cand.as<char>() + p.over_off) : nullptr;
-        uint4 *const    fb = b_fb.as<uint4>();
+        uint4 *const    fb = b_fb.as<uint4>(), *gb = b_gb.as<uint4>();
+        // the norms a gathered chunk gets in its own pass: the contraction's, unless it reads none or takes them from the f32 copy
+        const int       gather_kind = p.bits || p.copy ? 3 : p.kind;
         const uint4    *qv = p.copy ? b_fq.as<uint4>() : d_q;
         ok = ok && hipMemsetAsync(best, 0xFF, p.nq * kk * 8, st) == hipSuccess;
         if(!p.bits) ok = ok && launch_norms(p.kind, base_metric, qv, nq, fchunks, qn, st) == hipSuccess;
-        if(!p.bits && !p.copy) ok = ok && launch_norms(p.kind, base_metric, d_base, nb, fchunks, bn, st) == hipSuccess;
+        if(!p.bits && !p.copy && !d_list) ok = ok && launch_norms(p.kind, base_metric, d_base, nb, fchunks, bn, st) == hipSuccess;
         size_t si = 0;
         for(size_t c0 = 0; ok && c0 < p.nb; c0 += p.chunk_rows) {
             const size_t nc = std::min<size_t>(p.chunk_rows, p.nb - c0);
             const uint4 *bv = d_base + c0 * chunks;
+            if(d_list) {
+                DenseTimer t(st, 0, (uint32_t)nc, 2u);  // (lantern_gpu_dense_profile: fused = 2 marks a gather, rows = 0)
+                ok = ok && launch_gather_rows_norms(gather_kind, base_metric, d_base, chunks, d_list + c0, (uint32_t)nc, gb, bn + c0, st) == hipSuccess;
+                bv = gb;
+            }
             if(p.copy) {
                 ok = ok && dequant(bv, nc * chunks, fb) == hipSuccess;
                 ok = ok && launch_norms(p.kind, base_metric, fb, (uint32_t)nc, fchunks, bn + c0, st) == hipSuccess;
@@ -244,7 +260,7 @@ try {
                 const DenseOperands o = { p.kind, base_metric, qv + (size_t)s.q0 * fchunks, s.nqt, bv + (s.col0 - c0) * fchunks, s.cols, fchunks, qn + s.q0, bn + s.col0 };
                 const DenseTopk     tk = { mine, kk, cand, ccnt, p.cand_cap, s.col0 };
                 {
-                    DenseTimer t(st, s.nqt, s.cols, s.fused != 0);
+                    DenseTimer t(st, s.nqt, s.cols, s.fused != 0 ? 1u : 0u);
                     ok = ok && launch_contraction(o, dd, p.ldd, s.fused ? &tk : nullptr, st) == hipSuccess;
                     if(!p.bits) ++g_dense_kind[ p.kind ];
                 }
@@ -252,7 +268,7 @@ try {
                 else ok = ok && launch_select(dd, p.ldd, s.nqt, s.cols, s.col0, mine, kk, st) == hipSuccess;
             }
         }
-        ok = ok && launch_rerank(p.mcode, d_q, nq, d_base, chunks, best, kk, p.k, d_slots, d_dists, st) == hipSuccess;
+        ok = ok && launch_rerank(p.mcode, d_q, nq, d_base, chunks, best, kk, p.k, d_slots, d_dists, d_list, st) == hipSuccess;
         // the certificate: 4 bytes per query to the host, behind the synchronisation the call makes anyway.  The popcount metrics
         // rank on the exact-order distance itself (the same integer arithmetic): their pre-selection is exact by construction.
         certified.assign(p.nq + 1, p.exact_keys ? 1u : 0u);
@@ -305,6 +321,61 @@ static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, 
     return ok;
 }
 
+// A plan run to its certificate: once, and once more unfused (planned anew from the plan's own numbers) when a candidate list
+// overflowed.  certified: the flag of every query; refused: the queries without one, which the caller recomputes.
+static bool exact_knn_certified(const ExactKnnPlan &first, int native, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots,
+                                float *d_dists, hipStream_t st, std::vector<uint32_t> &certified, std::vector<uint32_t> &refused)
+{
+    bool over = false;
+    if(!exact_knn_run(first, d_base, d_list, d_q, d_slots, d_dists, st, &over, certified)) return false;
+    if(over) {  // the same call, unfused
+        ExactKnnPlan plan;
+        if(plan_exact_knn(first.mcode, first.chunks, (int64_t)first.nb, (int64_t)first.nq, (int64_t)first.k, native, 0, plan) != nullptr) return false;
+        plan.gb_bytes = first.gb_bytes;
+        if(!exact_knn_run(plan, d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified)) return false;
+    }
+    refused.clear();
+    for(size_t q = 0; q < first.nq; ++q)
+        if(!certified[ q ]) refused.push_back((uint32_t)q);
+    return true;
+}
+
+// ---- the filtered exact path's dense route (filter.hip filtered_search_locked branches on this plan) ----------------------------------
+const char *plan_filtered_dense(int64_t mcode, int64_t chunks, int64_t allowed, int64_t nq, int64_t k, int64_t skip, int64_t min_queries, bool exact,
+                                bool compact, int native, int fused, FilteredDensePlan &p)
+{
+    p = FilteredDensePlan();
+    if(allowed < 0 || nq < 0 || k < 0 || skip < 0 || min_queries < 0 || k > 0xFFFFFFFFll || skip > 0xFFFFFFFFll) return kBadPlan;
+    // the order of the reasons is the order the call meets them in: nothing to do, the switch, the batch, the path, the width, the index
+    if(allowed == 0 || nq == 0 || k == 0) p.why = kDenseEmpty;
+    else if(min_queries == 0) p.why = kDenseOff;
+    else if(nq < min_queries) p.why = kDenseFewQueries;
+    else if(!exact) p.why = kDenseWalkPath;
+    else if(k + skip > 240) p.why = kDenseWide;
+    else if(compact) p.why = kDenseCompact;
+    else p.why = kDenseTaken;
+    if(p.why != kDenseTaken) {  // (the operands are still checked: a bad metric code or row is refused on either side of the decision)
+        ExactKnnPlan o;
+        return plan_operands(mcode, chunks, allowed, native, o);
+    }
+    if(const char *why = plan_exact_knn(mcode, chunks, allowed, nq, k + skip, native, fused, p.knn)) return why;
+    p.gather_rows = p.knn.chunk_rows;
+    p.knn.gb_bytes = (size_t)p.knn.chunk_rows * p.knn.chunks * 16;
+    p.norm_bytes = p.knn.bits ? 0 : p.knn.nb * 4;
+    return nullptr;
+}
+
+bool filtered_dense_device(const FilteredDensePlan &p, int native, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots,
+                           float *d_dists, uint32_t *d_flags, hipStream_t st, std::vector<uint32_t> &refused)
+try {
+    if(p.why != kDenseTaken || !d_list) return false;
+    std::vector<uint32_t> certified;
+    if(!exact_knn_certified(p.knn, native, d_base, d_list, d_q, d_slots, d_dists, st, certified, refused)) return false;
+    // the flags as the host settled them (a cosine norm out of range refuses every query) back to the device, for the answer kernel
+    return hipMemcpyAsync(d_flags, certified.data(), p.knn.nq * 4, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+}
+LANTERN_ABI_CATCH(nullptr)
+
 // fp32- or native-MFMA contraction in chunks of 64k base rows + running top-(k+16) + exact-order re-rank, then per query the certificate
 // that the top-(k+16) held the exact answer; the refused queries are recomputed in exact order.
 bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k, uint32_t *d_slots,
@@ -312,17 +383,9 @@ bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb
 try {
     const DenseEnv        env = dense_env();
     ExactKnnPlan          plan;
-    bool                  over = false;
-    std::vector<uint32_t> certified;
+    std::vector<uint32_t> certified, refused;
     if(plan_exact_knn(mcode, chunks, (int64_t)nb, (int64_t)nq, (int64_t)k, env.native, env.fused, plan) != nullptr) return false;
-    if(!exact_knn_run(plan, d_base, d_q, d_slots, d_dists, st, &over, certified)) return false;
-    if(over) {  // the same call, unfused
-        if(plan_exact_knn(mcode, chunks, (int64_t)nb, (int64_t)nq, (int64_t)k, env.native, 0, plan) != nullptr) return false;
-        if(!exact_knn_run(plan, d_base, d_q, d_slots, d_dists, st, nullptr, certified)) return false;
-    }
-    std::vector<uint32_t> refused;
-    for(size_t q = 0; q < nq; ++q)
-        if(!certified[ q ]) refused.push_back((uint32_t)q);
+    if(!exact_knn_certified(plan, env.native, d_base, nullptr, d_q, d_slots, d_dists, st, certified, refused)) return false;
     g_knn_queries += nq;
     g_knn_certified += nq - refused.size();
     g_knn_fallback += refused.size();
@@ -461,6 +524,31 @@ catch(...) {
     return kAbiException;  // (NULL is this function's "accepted")
 }
 
+const char *lantern_gpu_plan_filtered_dense(const int64_t in[ 11 ], uint32_t out[ 8 ], uint32_t steps[][ 4 ], size_t cap, size_t *n_steps)
+try {
+    if(!in || !out || !n_steps || (cap && !steps)) return "lantern_gpu: null plan array";
+    FilteredDensePlan p;
+    if(const char *why = plan_filtered_dense(in[ 0 ], in[ 1 ], in[ 2 ], in[ 3 ], in[ 4 ], in[ 5 ], in[ 6 ], in[ 7 ] != 0, in[ 8 ] != 0,
+                                             in[ 9 ] < 0 ? -1 : in[ 9 ] != 0, in[ 10 ] < 0 ? -1 : in[ 10 ] != 0, p))
+        return why;
+    const bool     taken = p.why == kDenseTaken;
+    const uint64_t sizes[ 2 ] = { p.knn.gb_bytes, p.norm_bytes };
+    out[ 0 ] = taken ? 1u : 0u;
+    out[ 1 ] = (uint32_t)p.why;
+    out[ 2 ] = p.knn.kk;
+    out[ 3 ] = p.gather_rows;
+    for(int i = 0; i < 2; ++i) { out[ 4 + 2 * i ] = (uint32_t)sizes[ i ]; out[ 5 + 2 * i ] = (uint32_t)(sizes[ i ] >> 32); }
+    for(size_t i = 0; i < p.knn.n_steps && i < cap; ++i) {
+        const KnnStep s = p.knn.step(i);
+        steps[ i ][ 0 ] = s.nqt; steps[ i ][ 1 ] = s.cols; steps[ i ][ 2 ] = s.fused; steps[ i ][ 3 ] = s.col0;
+    }
+    *n_steps = p.knn.n_steps;
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
+
 void lantern_gpu_dense_kind_stats(uint64_t launches[ 3 ])
 {
     if(!launches) return;
@@ -476,7 +564,8 @@ void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t *certified, uint64_
 
 // on != 0: start recording (forgets earlier records).  on == 0: stop, wait for the recorded launches and write up to `cap` of them:
 // ms[i] = duration of launch i (HIP events on its stream), rows[i] x cols[i] = its queries x base rows, fused[i] = 1 for the
-// launch with the fused top-k epilogue.  Returns the number of recorded launches.
+// launch with the fused top-k epilogue, 2 for the gather of a chunk of a slot list (rows[i] = 0, cols[i] its rows).  Returns the number of
+// recorded launches.
 size_t lantern_gpu_dense_profile(int on, float *ms, uint32_t *rows, uint32_t *cols, uint32_t *fused, size_t cap)
 try {
     std::vector<DenseLaunch> got;

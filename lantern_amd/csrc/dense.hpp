@@ -4,6 +4,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace lgpu {
 
@@ -37,6 +38,7 @@ struct ExactKnnPlan
     uint32_t dims = 0;            // the dims the certificate is told (0 iff exact_keys)
     uint32_t k_steps = 0;         // K steps (128 bytes of a row each) per output tile
     size_t   fb_bytes = 0;        // the f32 copy of one chunk of base rows (0: no copy)
+    size_t   gb_bytes = 0;        // a run over a slot list: one gathered chunk of base rows as stored (plan_filtered_dense; 0 otherwise)
     // the launches and their buffers
     uint32_t kk = 0;                                     // survivors per query, k + 16: re-ranked in exact order, then cut to k
     uint32_t chunk_rows = 0, qtile = 0, seed_cols = 0;    // base rows and queries per launch; the columns that give every query a radius
@@ -52,6 +54,34 @@ struct ExactKnnPlan
 };
 // pure: no HIP runtime call, no getenv.  native / fused: DenseEnv's.  NULL, or why the call is refused (static text)
 const char *plan_exact_knn(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, int native, int fused, ExactKnnPlan &p);
+
+// The filtered exact path's dense route (DESIGN.md 4.9 "Dense exact path"): whether a single-filter call takes it, and the exact k-NN
+// it then runs over the filter's `allowed` rows with k := k + skip.  lantern_gpu_plan_filtered_dense shows it without a device.
+enum FilteredDenseWhy : uint32_t
+{
+    kDenseTaken = 0,
+    kDenseOff,        // min_queries == 0
+    kDenseFewQueries, // nq < min_queries
+    kDenseWalkPath,   // the query's path is the walk
+    kDenseWide,       // k + skip > 240
+    kDenseCompact,    // a compact pq index
+    kDenseEmpty       // nothing allowed, or nothing asked for: no launch at all
+};
+struct FilteredDensePlan
+{
+    FilteredDenseWhy why = kDenseOff;
+    ExactKnnPlan     knn;              // taken: plan_exact_knn(mcode, chunks, nb = allowed, nq, k + skip), and knn.gb_bytes
+    uint32_t         gather_rows = 0;  // rows per gathered chunk
+    size_t           norm_bytes = 0;   // the gathered rows' norm words (0: bit rows)
+};
+// pure, as plan_exact_knn.  NULL, or why the input is refused; a call that is not taken is not refused (why != kDenseTaken)
+const char *plan_filtered_dense(int64_t mcode, int64_t chunks, int64_t allowed, int64_t nq, int64_t k, int64_t skip, int64_t min_queries, bool exact,
+                                bool compact, int native, int fused, FilteredDensePlan &p);
+// One run of a taken plan: rows d_base[d_list[0..allowed)] (d_list ascending).  Result (device): slots[nq][k + skip] ascending by
+// (exact-order distance, slot), dists alike, flags[nq] = 1 where the certificate holds; the queries it refuses are listed in
+// `refused` and their rows of the result are not the answer: the caller recomputes them.  Waits for `st`.
+bool filtered_dense_device(const FilteredDensePlan &p, int native, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots,
+                           float *d_dists, uint32_t *d_flags, hipStream_t st, std::vector<uint32_t> &refused);
 
 // Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row).
 // Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].

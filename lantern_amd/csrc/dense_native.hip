@@ -16,6 +16,7 @@
 #include "kernels.hpp"
 #include "walk.hpp"
 #include "dense_tile.hpp"
+#include "row_norms.hpp"
 
 namespace lgpu {
 
@@ -25,6 +26,7 @@ typedef int      nat_i32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 nat_f16x8 __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------------------------------------------
+// (the arithmetic: NormAcc, row_norms.hpp -- shared with k_gather_rows_norms)
 template <int G>
 __global__ void __launch_bounds__(256) k_row_norms_f16(const uint4 *rows, uint32_t n, uint32_t chunks, float *out)
 {
@@ -32,20 +34,10 @@ __global__ void __launch_bounds__(256) k_row_norms_f16(const uint4 *rows, uint32
     const uint32_t ngroups = gridDim.x * blockDim.x / G;
     for(uint32_t i = gid; i < n; i += ngroups) {
         const uint4 *r = rows + (size_t)i * chunks;
-        float        s = 0.f;
-        for(uint32_t ch = gl; ch < chunks; ch += G) {
-            const uint4    x = r[ ch ];
-            const uint32_t w[ 4 ] = { x.x, x.y, x.z, x.w };
-#pragma unroll
-            for(int j = 0; j < 4; ++j) {
-                float lo, hi;
-                unpack_h2(w[ j ], lo, hi);
-                s = __builtin_fmaf(lo, lo, s);
-                s = __builtin_fmaf(hi, hi, s);
-            }
-        }
-        s = group_sum<G>(s);
-        if(gl == G - 1) out[ i ] = s;
+        NormAcc<1>   acc;
+        for(uint32_t ch = gl; ch < chunks; ch += G) acc.add(r[ ch ]);
+        const uint32_t s = acc.template finish<G>(0);
+        if(gl == G - 1) out[ i ] = __uint_as_float(s);
     }
 }
 
@@ -57,16 +49,10 @@ __global__ void __launch_bounds__(256) k_row_norms_i8(const uint4 *rows, uint32_
     const uint32_t ngroups = gridDim.x * blockDim.x / G;
     for(uint32_t i = gid; i < n; i += ngroups) {
         const uint4 *r = rows + (size_t)i * chunks;
-        int          s = 0;
-        for(uint32_t ch = gl; ch < chunks; ch += G) {
-            const uint4 x = r[ ch ];
-            s = dot4_i8(x.x, x.x, s);
-            s = dot4_i8(x.y, x.y, s);
-            s = dot4_i8(x.z, x.z, s);
-            s = dot4_i8(x.w, x.w, s);
-        }
-        const uint32_t a2 = group_sum<G>((uint32_t)s);
-        if(gl == G - 1) out[ i ] = cosine ? __float_as_uint(__builtin_sqrtf((float)(int)a2)) : a2;
+        NormAcc<2>   acc;
+        for(uint32_t ch = gl; ch < chunks; ch += G) acc.add(r[ ch ]);
+        const uint32_t s = acc.template finish<G>(cosine);
+        if(gl == G - 1) out[ i ] = s;
     }
 }
 

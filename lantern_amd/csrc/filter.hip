@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "abi_guard.hpp"
+#include "dense.hpp"
 #include "filter.hpp"
 #include "host_trip.hpp"
 #include "index.hpp"
@@ -377,9 +378,88 @@ static int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, h
     return grid;
 }
 
-// The caller holds ix->mu and has flushed.  false -> ix->err.
+// ---- the exact path's dense route (DESIGN.md 4.9 "Dense exact path") ---------------------------------------------------------------
+// k_dense_answers: the exact k-NN's re-ranked rows -- kk = k + skip (slot, distance) entries per query, ascending by (distance, slot) --
+// into a filtered call's outputs, as k_search_exact_allowed closes a query (frame_answer_rows, frame_close): rows [skip, skip + k) as
+// label, distance, slot; tails label 0, +inf, EMPTY; count, D = allowed, E = 0; D added to totals[0].  One thread per answer cell.
+// Queries without a flag are left alone: the per-query launch behind this one answers them.  Every output pointer may be NULL.
+__global__ void __launch_bounds__(256) k_dense_answers(const uint32_t *slots, const float *dists, const uint32_t *flags, uint32_t nq, uint32_t kk, uint32_t k,
+                                                       uint32_t skip, uint32_t allowed, const uint64_t *labels, uint32_t n, uint64_t *out_labels, float *out_dists,
+                                                       uint32_t *out_slots, uint32_t *out_counts, uint64_t *out_D, uint64_t *out_E, unsigned long long *totals)
+{
+    const uint32_t have = allowed < kk ? allowed : kk, got = have <= skip ? 0u : (have - skip < k ? have - skip : k);
+    const size_t   cells = (size_t)nq * k;
+    for(size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t q = (uint32_t)(c / k), i = (uint32_t)(c % k);
+        if(!flags[ q ]) continue;
+        if(i < got) {
+            const size_t   at = (size_t)q * kk + skip + i;
+            const uint32_t slot = slots[ at ];
+            if(out_labels) out_labels[ c ] = slot < n ? labels[ slot ] : 0;  // (every slot of the first `have` entries is a row's)
+            if(out_dists) out_dists[ c ] = dists[ at ];
+            if(out_slots) out_slots[ c ] = slot;
+        } else {
+            if(out_labels) out_labels[ c ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
+            if(out_dists) out_dists[ c ] = __builtin_inff();
+            if(out_slots) out_slots[ c ] = EMPTY;
+        }
+        if(i == 0) {
+            if(out_counts) out_counts[ q ] = got;
+            if(out_D) out_D[ q ] = allowed;
+            if(out_E) out_E[ q ] = 0;
+            if(totals) atomicAdd(&totals[ 0 ], (unsigned long long)allowed);
+        }
+    }
+}
+
+// One single-filter call on the dense route, planned by `plan` (taken).  `a`, `lds`: the exact launch's arguments and carve, which the
+// recomputed queries run with.  Waits for the stream (the certificate's flags cross to the host).
+static bool filtered_dense_locked(Index *ix, const Filter *f, const FilteredDensePlan &plan, int native, const uint4 *d_q, size_t nq, size_t k, size_t skip,
+                                  const SearchOut &out, FilteredArgs &a, size_t lds, hipStream_t stream)
+{
+    static const char *kDenseFailed = "lantern_gpu: HIP failure on the dense route of the filtered exact path";
+    const size_t kk = k + skip, dist_at = nq * kk * 4, flag_at = 2 * dist_at;
+    char *const  blk = (char *)scratch(ix, kScratchDenseAnswers, flag_at + nq * 4);
+    if(!blk) return false;
+    uint32_t *const d_slots = (uint32_t *)blk, *d_flags = (uint32_t *)(blk + flag_at);
+    float *const    d_dists = (float *)(blk + dist_at);
+    if(!order_after_inserts(ix, stream)) return false;
+    std::vector<uint32_t> refused;
+    if(!filtered_dense_device(plan, native, ix->d_vec, f->d_slots, d_q, d_slots, d_dists, d_flags, stream, refused)) return set_err(ix, kDenseFailed), false;
+    if(refused.size() < nq) {
+        const size_t blocks = std::min<size_t>((nq * k + 255) / 256, 16384);
+        hipLaunchKernelGGL(k_dense_answers, dim3((uint32_t)blocks), dim3(256), 0, stream, (const uint32_t *)d_slots, (const float *)d_dists,
+                           (const uint32_t *)d_flags, (uint32_t)nq, (uint32_t)kk, (uint32_t)k, (uint32_t)skip, (uint32_t)f->count, (const uint64_t *)ix->d_labels, (uint32_t)ix->n,
+                           out.labels, out.dists, out.slots, out.counts, out.D, out.E, (unsigned long long *)(ix->d_totals + kTotSearch));
+        if(hipGetLastError() != hipSuccess) return set_err(ix, kDenseFailed), false;
+    }
+    if(!refused.empty()) {
+        // the queries the certificate refused, by k_search_exact_allowed in its per-query form over a selection list of just those: today's
+        // answers by construction.  (The launch counts as an exact launch of lantern_gpu_filter_stats: it is one.)
+        const size_t      nr = refused.size(), off_desc = (nr * 4 + 7) & ~(size_t)7;
+        std::vector<char> tbl(off_desc + nq * sizeof(FilterDesc));
+        std::copy(refused.begin(), refused.end(), (uint32_t *)tbl.data());
+        FilterDesc *const hd = (FilterDesc *)(tbl.data() + off_desc);
+        for(size_t i = 0; i < nq; ++i) hd[ i ] = FilterDesc{ f->d_bits, f->d_slots, (uint32_t)f->count, 0u };
+        a.frame.nq = (uint32_t)nr;
+        const EachTable t{ tbl.data(), tbl.size(), off_desc, 0 };
+        if(filtered_launch(ix, true, a, lds, stream, &t) < 0) return false;  // (pageable staging: the copy completes before this returns)
+    }
+    if(hipStreamSynchronize(stream) != hipSuccess) return set_err(ix, kDenseFailed), false;
+    ix->c_filter_dense[ 0 ] += 1;
+    ix->c_filter_dense[ 1 ] += nq;
+    ix->c_filter_dense[ 2 ] += nq - refused.size();
+    ix->c_filter_dense[ 3 ] += refused.size();
+    const uint32_t shape[ 6 ] = { 3u, 0u, (uint32_t)kk, 0u, 0u, 0u };
+    std::copy(std::begin(shape), std::end(shape), ix->last_filtered);
+    ix->c_search_queries += nq;
+    return true;
+}
+
+// The caller holds ix->mu and has flushed.  false -> ix->err.  batch_call: one of the two single-filter batch entry points, which alone
+// may take the exact path's dense route (lantern_gpu_set_filter_dense); a cursor's search never does.
 static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip, const SearchOut &out,
-                                   hipStream_t stream)
+                                   hipStream_t stream, bool batch_call = false)
 {
     const std::string why = filter_mismatch(ix, f);
     if(!why.empty()) return set_err(ix, why), false;
@@ -400,6 +480,13 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     a.allow_count = (uint32_t)f->count;
     size_t lds = 0;
     if(!filtered_shape(ix, exact, k, skip, exp, a, lds)) return false;
+    if(batch_call && ix->filter_dense_min) {  // the exact path's second implementation: the same answers from the contraction
+        const DenseEnv    env = dense_env();
+        FilteredDensePlan dense;
+        const char *const bad = plan_filtered_dense(ix->mcode, ix->chunks, (int64_t)f->count, (int64_t)nq, (int64_t)k, (int64_t)skip,
+                                                    (int64_t)ix->filter_dense_min, exact, ix->pq_compact, env.native, env.fused, dense);
+        if(!bad && dense.why == kDenseTaken) return filtered_dense_locked(ix, f, dense, env.native, d_q, nq, k, skip, out, a, lds, stream);
+    }
     int grid;
     if(!exact && ix->filter_seeds) {
         // the seeded walk exists in the per-query form only: every query's descriptor is this filter, the selection list the identity
@@ -800,6 +887,37 @@ try {
 }
 LANTERN_ABI_CATCH(e)
 
+void lantern_gpu_set_filter_dense(usearch_index_t h, size_t min_queries, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->filter_dense_min = min_queries;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+size_t lantern_gpu_filter_dense(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    return ix->filter_dense_min;
+}
+LANTERN_ABI_CATCH(e)
+
+void lantern_gpu_filter_dense_stats(usearch_index_t h, uint64_t out[ 4 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::copy(std::begin(ix->c_filter_dense), std::end(ix->c_filter_dense), out);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
 void lantern_gpu_last_filtered_seeds(usearch_index_t h, uint32_t out[ 4 ], usearch_error_t *e)
 try {
     CLEAR(e);
@@ -845,7 +963,7 @@ try {
     if(!ix) return;
     const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
     device_trip(ix, stride_is(query_stride_bytes),
-                [ & ] { return filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream); }, e);
+                [ & ] { return filtered_search_locked(ix, f, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream, true); }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -861,7 +979,7 @@ try {
     if(nq == 0 || k == 0) return;
     if(!queries || !labels || !distances) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
     host_trip_sync(ix, nq, k, 0, queries, (int)kind, kFilteredBatchFailed, nullptr,
-                   [ = ](const HostBatch &b) { return filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream); }, labels,
+                   [ = ](const HostBatch &b) { return filtered_search_locked(ix, f, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, true); }, labels,
                    distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)

@@ -390,13 +390,18 @@ bool record_launch(Index *ix, hipStream_t stream)
     ix->insert_pending = true;
     return true;
 }
-int acquire_search_slot(Index *ix, hipStream_t stream, size_t grid)
+bool order_after_inserts(Index *ix, hipStream_t stream)
 {
     // a search on another stream than the index's own runs behind the insert batches queued there
     if(ix->insert_pending) {
         if(hipEventQuery(ix->insert_done) == hipSuccess) ix->insert_pending = false;
-        else if(stream != ix->stream && hipStreamWaitEvent(stream, ix->insert_done, 0) != hipSuccess) { set_err(ix, "lantern_gpu: hipStreamWaitEvent failed"); return -1; }
+        else if(stream != ix->stream && hipStreamWaitEvent(stream, ix->insert_done, 0) != hipSuccess) { set_err(ix, "lantern_gpu: hipStreamWaitEvent failed"); return false; }
     }
+    return true;
+}
+int acquire_search_slot(Index *ix, hipStream_t stream, size_t grid)
+{
+    if(!order_after_inserts(ix, stream)) return -1;
     int pick = -1;
     for(int s = 0; s < Index::kSearchSlots && pick < 0; ++s)  // the slot this stream used last: the stream orders the two launches
         if(!slot_idle(ix, s) && ix->slot_stream[ s ] == stream) pick = s;

@@ -44,6 +44,9 @@ enum ScratchSlot : int
     // index stream, which runs one call's work after the other's.
     kScratchCallIn,
     kScratchCallOut,
+    // the filtered exact path's dense route: the re-ranked (slot, distance) rows and the certificate's flags of one call, which has
+    // waited for its stream when it returns (under ix->mu): nothing queued reads the block when the next call takes it
+    kScratchDenseAnswers,
     kScratchLanes,                                     // 2 per lane: queries, answers (lantern_gpu_search_batch_lane*)
     kScratchTables = kScratchLanes + 2 * kIndexLanes,  // 1 per launch slot: a per-query filtered launch's selection list + descriptors
     kScratchCount = kScratchTables + kIndexLanes
@@ -231,13 +234,15 @@ struct Index
     size_t   filter_cand_cap = 0;       // 0: max(4 expansion, 256), capped by LDS
     double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
     uint64_t c_filter_walk = 0, c_filter_exact = 0;
+    size_t   filter_dense_min = 0;      // lantern_gpu_set_filter_dense: 0 off; m > 0: single-filter exact-path calls of nq >= m queries take the dense route
+    uint64_t c_filter_dense[ 4 ] = {};  // lantern_gpu_filter_dense_stats: dense calls, their queries, certified, recomputed
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches
     uint32_t last_each_params[ 4 ] = {};  // the last per-query filtered call with per-query parameters: largest walk expansion, largest C, largest k + skip on the exact path, queries with k == 0 (lantern_gpu_last_filtered_each_params)
     uint32_t last_params[ 6 ] = {};  // the last per-query-parameter call: launches, queries per list-placement class (3), largest expansion, any spec shape (lantern_gpu_last_params_launch)
-    uint32_t last_filtered[ 6 ] = {};  // path, grid, expansion, cand_cap, vis_slots, LDS bytes of the last filtered launch (lantern_gpu_last_filtered_launch)
+    uint32_t last_filtered[ 6 ] = {};  // path (3: the dense route, [2] = k + skip, the rest 0), grid, expansion, cand_cap, vis_slots, LDS bytes of the last filtered launch (lantern_gpu_last_filtered_launch)
 
     hipStream_t stream = nullptr;
     int         device = 0;
@@ -440,6 +445,7 @@ inline size_t logical_size(const Index *ix) { return ix->page_mode ? ix->page_de
 void        prof_resolve(Index *ix, size_t keep);          // fold finished batches' event times into ix->prof
 bool        order_launch(Index *ix, hipStream_t stream);   // before an insert batch (exclusive use of the index)
 bool        record_launch(Index *ix, hipStream_t stream);  // behind it
+bool        order_after_inserts(Index *ix, hipStream_t stream);  // work queued on `stream` from here on runs behind the pending insert batches
 int         acquire_search_slot(Index *ix, hipStream_t stream, size_t grid);  // before a search launch: its bitmap slab (< 0: error)
 bool        release_search_slot(Index *ix, int slot, hipStream_t stream);     // behind it
 bool        import_graph_locked(Index *ix, size_t size, const void *vectors, const uint64_t *labels, const uint8_t *levels,

@@ -331,8 +331,13 @@ hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, co
                                     hipStream_t stream);
 hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t ncols, uint32_t c_base, uint64_t *best, uint32_t kk,
                          hipStream_t stream);
+// list: NULL, or the ascending slot list the keys' low words are positions in (k_rerank)
 hipError_t launch_rerank(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
-                         uint32_t k, uint32_t *out_slots, float *out_dists, hipStream_t stream);
+                         uint32_t k, uint32_t *out_slots, float *out_dists, const uint32_t *list, hipStream_t stream);
+// rows list[0..n) of src into the contiguous dst with their norm words, as launch_norms(kind, metric, dst, ...) would write them,
+// in one pass (k_gather_rows_norms).  kind 3: no norms (bit rows, rows dequantised before the contraction), norms may be NULL
+hipError_t launch_gather_rows_norms(int kind, int metric, const uint4 *src, uint32_t chunks, const uint32_t *list, uint32_t n, uint4 *dst, void *norms,
+                                    hipStream_t stream);
 // the exact k-NN's certificate (flag[q] = 1: certified; flag[nq] != 0: a cosine row norm out of the bound's range) and the
 // exact-order fallback's row gather / result scatter (bruteforce.hip)
 hipError_t launch_certify(int metric, const uint64_t *best, uint32_t kk, const float *dists, uint32_t k, const float *qn, uint32_t nq, const float *bn,

@@ -41,6 +41,18 @@ line: the same pq index twice, expanded and compact; per filter (all rows, rando
 (the decodings in HBM), "decode" (rows decoded on the fly) and "adc" (LANTERN_GPU_PQ_ADC=1) -- q/s of the forced walk and of the forced
 exact path (the routines alternated within every repeat, every repeat listed), mean D of the walk, recall@10 of the walk against the
 same routine's exact path, and per routine the interpolated walk / exact crossover as exact_factor = allowed^2 / (ef * n).
+
+    python scripts/bench_filtered.py --dense
+
+measures the exact path's DENSE ROUTE (lantern_gpu_set_filter_dense; DESIGN.md 4.9 "Dense exact path") and prints ONE JSON line: per filter
+(random 50 / 10 / 1 / 0.1 % and the rows of one whole cluster) and per batch size (8192, 1024, 256, 64 queries behind the one filter) the
+wall-clock milliseconds per call of the forced walk, of today's exact pass (setting 0) and of the dense route, alternated within each of
+--reps repeats, every repeat listed, with their medians; recall@10 of the walk against the exact answer; whether the dense route's slots
+equal the exact pass's; the gather and contraction launches of one more dense call (lantern_gpu_dense_profile) and its certified /
+recomputed queries.  Then: a filter of 18 900 rows (today's walk / exact crossover) at 1 .. 256 queries, exact against dense, and the
+smallest batch at which the dense route is not slower; per batch size the allowed count at which the dense route meets the walk
+(log-log interpolation over the random filters) as exact_factor = allowed^2 / (ef * n); one f16 and one i8 index over the same graph
+at 10 %.
 """
 import argparse
 import json
@@ -300,6 +312,99 @@ def compact_legs(a, base, queries, M, efc, ef, k):
             "filters": legs, "crossover": cross}
 
 
+def dense_legs(a, ix, base, cluster, queries, k, ef):
+    """--dense: the exact path's dense route (lantern_gpu_set_filter_dense) against the walk and today's exact pass"""
+    def bench_index(index, q, filters, batches, walk=True):
+        rows = index.device_query_rows(q)
+        dq = hip.Buffer.from_numpy(rows)
+        nq = rows.shape[0]
+        slot, D = hip.Buffer(nq * k * 4), hip.Buffer(nq * 8)
+
+        def call(f, n_q):
+            index.search_batch_filtered_device(f, dq.ptr, rows.strides[0], n_q, k, ef, 0, None, None, slot.ptr, None, D.ptr, None)
+            hip.synchronize()
+
+        modes = {"walk": ("walk", 0), "exact": ("exact", 0), "dense": ("exact", 1)}
+        out = []
+        for name, allowed in filters:
+            f = index.filter_from_bitmap(allowed)
+            for n_q in batches:
+                wall = {m: [] for m in modes if walk or m != "walk"}
+                answers = {}
+                for _ in range(a.reps):  # the legs alternated within every repeat
+                    for m in wall:
+                        index.set_filter_policy(modes[m][0])
+                        index.set_filter_dense(modes[m][1])
+                        slot.upload(np.full(slot.nbytes, 0xA5, dtype=np.uint8))  # (untimed: the answers compared below are this call's own)
+                        hip.synchronize()
+                        t = time.perf_counter()
+                        call(f, n_q)
+                        wall[m].append((time.perf_counter() - t) * 1e3)
+                        answers[m] = slot.download((nq, k), np.uint32)[:min(n_q, a.nq_exact)].copy()
+                leg = {"filter": name, "allowed": int(f.count), "queries": n_q, "wall_ms": wall,
+                       "median_ms": {m: float(np.median(v)) for m, v in wall.items()}}
+                leg["qps"] = {m: n_q / (v / 1e3) for m, v in leg["median_ms"].items()}
+                leg["dense_equals_exact"] = bool(np.array_equal(answers["dense"], answers["exact"]))
+                if walk:
+                    truth = answers["exact"]
+                    leg["walk_recall_at_10"] = float(np.mean([len(set(answers["walk"][i].tolist()) & set(t for t in truth[i].tolist() if t != capi.EMPTY)) /
+                                                              max(1, sum(1 for t in truth[i].tolist() if t != capi.EMPTY)) for i in range(truth.shape[0])]))
+                # one more dense call under the launch profile: the gather and the contraction launch by launch, and the certificate
+                index.set_filter_policy("exact")
+                index.set_filter_dense(1)
+                s0 = index.filter_dense_stats()
+                capi.dense_profile(True)
+                call(f, n_q)
+                prof = capi.dense_profile(False)
+                s1 = index.filter_dense_stats()
+                index.set_filter_dense(0)
+                leg["gather_ms"] = [float(l["ms"]) for l in prof if l["gather"]]
+                leg["gather_rows"] = [int(l["cols"]) for l in prof if l["gather"]]
+                leg["contraction_ms"] = [float(l["ms"]) for l in prof if not l["gather"]]
+                leg["certified"], leg["recomputed"] = s1["certified"] - s0["certified"], s1["recomputed"] - s0["recomputed"]
+                out.append(leg)
+            f.close()
+        index.set_filter_policy("auto")
+        return out
+
+    rng = np.random.default_rng(7)
+    filters = [(f"random {sel}", rng.random(a.n) < sel) for sel in (0.5, 0.1, 0.01, 0.001)] + [("cluster 0", cluster == 0)]
+    batches = [b for b in (8192, 1024, 256, 64) if b <= a.nq]
+    out = {"legs": bench_index(ix, queries, filters, batches)}
+    # where today's crossover lies (18.9 k allowed rows): the smallest batch at which the dense route is not slower than the exact pass
+    at_cross = np.zeros(a.n, dtype=bool)
+    at_cross[rng.choice(a.n, size=min(a.n, 18900), replace=False)] = True
+    out["at_crossover"] = bench_index(ix, queries, [("random 18900 rows", at_cross)], [1, 2, 4, 8, 16, 32, 64, 128, 256], walk=False)
+    ok = [l["queries"] for l in out["at_crossover"] if l["median_ms"]["dense"] <= l["median_ms"]["exact"]]
+    out["smallest_nq_dense_not_slower_at_crossover"] = min(ok) if ok else None
+    # per batch size: the allowed count at which the dense route meets the walk (log-log interpolation over the random filters)
+    meets = {}
+    for b in batches:
+        pts = sorted((np.log(l["allowed"]), np.log(l["median_ms"]["dense"] / l["median_ms"]["walk"])) for l in out["legs"]
+                     if l["queries"] == b and l["filter"].startswith("random"))
+        cross = None
+        for (x0, y0), (x1, y1) in zip(pts, pts[1:]):
+            if y0 <= 0 < y1:
+                cross = float(np.exp(x0 + (x1 - x0) * (-y0) / (y1 - y0)))
+        if cross is None and pts:
+            cross = "above the largest filter" if pts[-1][1] <= 0 else "below the smallest filter"
+        meets[str(b)] = {"allowed": cross, "exact_factor": cross ** 2 / (ef * a.n) if isinstance(cross, float) else None}
+    out["dense_meets_walk"] = meets
+    # quantised rows: the same graph over f16 / i8 rows (the exact path reads no graph; the walk's is the f32 build's), 10 %
+    g = ix.export_graph()
+    tenth = [filters[1]]
+    for storage in ("f16", "i8"):
+        scale = np.float32(1.0)
+        if storage == "i8":  # i8 storage keeps trunc(100 x) in [-100, 100]: rows scaled to fill that range
+            scale = np.float32(0.99 / float(np.abs(base).max()))
+        qix = capi.GpuIndex("l2sq", a.dim, M=ix.M, ef_construction=128, ef=ef, seed=42, quantization=storage)
+        stored = base * scale
+        qix.import_graph(np.trunc(np.clip(stored * np.float32(100), -100, 100)) if storage == "i8" else stored, g)
+        out[storage] = bench_index(qix, queries * scale, tenth, [b for b in (8192, 256) if b <= a.nq])
+        qix.close()
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=1_000_000)
@@ -312,6 +417,7 @@ def main():
     p.add_argument("--nq-each", type=int, default=256)
     p.add_argument("--seeds", default="", help="comma-separated seeds values: the legs of the seeded walk")
     p.add_argument("--compact", action="store_true", help="the legs of filtered search on a compact pq index against its expanded form")
+    p.add_argument("--dense", action="store_true", help="the legs of the exact path's dense route against the walk and today's exact pass")
     p.add_argument("--pq-subvectors", type=int, default=96)
     p.add_argument("--pq-centroids", type=int, default=256)
     a = p.parse_args()
@@ -357,6 +463,11 @@ def main():
 
     out = {"workload": f"clustered {a.n}x{a.dim} f32 l2sq M={M} efc={efc} ef={ef} k={k}", "queries": nq, "queries_exact": a.nq_exact,
            "build_seconds": build_s}
+    if a.dense:
+        out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
+        out.update(dense_legs(a, ix, base, cluster, queries, k, ef))
+        print(json.dumps(out))
+        return
     if a.each_params:
         out["command"] = "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])
         out.update(each_params_legs(a, ix, rows, max(r[0] for r in EACH_PARAMS_ROWS)))
