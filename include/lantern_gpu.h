@@ -446,6 +446,56 @@ LANTERN_GPU_EXPORT void lantern_gpu_filter_dense_stats(usearch_index_t, uint64_t
  * steps, cap, *n_steps: as lantern_gpu_plan_exact_knn's, and exactly its steps for (metric code, chunks, base rows = allowed, queries,
  *   k + skip); none when the route is not taken.  Returns NULL, or why the input is refused. */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_dense(const int64_t in[11], uint32_t out[8], uint32_t steps[][4], size_t cap, size_t *n_steps);
+/* THE DENSE ROUTE FOR PER-QUERY-FILTER CALLS (DESIGN.md 4.9 "Dense exact path, per-query filters"): in a call of
+ * lantern_gpu_search_batch_filtered_each or lantern_gpu_search_batch_filtered_each_device, the exact-path queries that name the same
+ * filter HANDLE form a group, and the groups of at least min_group queries are answered by one segmented run of the exact k-NN: the
+ * groups' slot lists are concatenated into one list (the call's own copy), the dense queries gathered into one block, and a tile of
+ * one group's queries is contracted against that group's rows only -- top-(k + skip + 16) by the contraction, re-ranked with the
+ * walk's per-pair reduction, certified per query.  Every output is what the call gives without the setting: slots, distance bits,
+ * labels, counts, D (= that query's own filter's count), E (= 0), the tails of short rows and the cumulative counters.
+ * A SEPARATE setting from lantern_gpu_set_filter_dense: neither switch turns the other's route on.
+ * min_group = 0, THE DEFAULT: off; every call issues exactly the launches it issues without this switch.
+ * min_group = m > 0: the path rule is untouched -- each query's path is still evaluated from its own filter's count.  Among the
+ *   queries whose path is exact, those sharing a handle are a group (pointer identity, not set equality: two handles over one set are
+ *   two groups).  A group is dense when it has >= m queries, k + skip <= 240, the index is not a compact pq index and the rows of all
+ *   dense groups together fit 32 bits.  Everything else -- walk-path queries, NULL entries, empty filters, smaller groups -- runs
+ *   exactly as without the setting, in the call's at most two per-query launches; the dense queries the certificate refuses join the
+ *   exact launch's list, which answers them as it would have.  No call is refused because of the setting.
+ * lantern_gpu_search_batch_filtered_each_lane, the three _each_params forms, cursors, scans and the scan-side service never take it.
+ * COSINE: a row norm outside the certificate's range in ANY dense group refuses every dense query of the call (they are all
+ *   recomputed by the exact launch): the flag is call-wide.
+ * SYNCHRONISATION: a call with at least one dense group waits for its stream ONCE, after pending insert batches and the dense run and
+ *   before its per-query launches are queued -- the certificate's flags cross to the host -- so
+ *   lantern_gpu_search_batch_filtered_each_device, otherwise asynchronous, is synchronous for such a call up to that point: the dense
+ *   groups' answers are complete on return, the per-query launches behind them are queued on `stream` as always.  The filters'
+ *   lifetime rule is unchanged.
+ * lantern_gpu_last_filtered_each keeps its meaning: [1] counts the dense queries (their path is exact), [5] the per-query kernels'
+ * launches (0 .. 2: 0 when every query of the call was answered by the dense run).  lantern_gpu_filter_dense_stats counts such a call
+ * once, and its dense queries as the single-filter route's. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_dense_each(usearch_index_t, size_t min_group, usearch_error_t *);
+LANTERN_GPU_EXPORT size_t lantern_gpu_filter_dense_each(usearch_index_t, usearch_error_t *); /* the setting */
+/* the dense run of the last per-query-filter call on this index that passed its checks (all zero when it made none): out[0] dense
+ * groups, [1] their queries, [2] of those certified, [3] recomputed by the exact launch, [4] rows gathered (the concatenated list's
+ * length), [5] contraction steps */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each_dense(usearch_index_t, uint32_t out[6], usearch_error_t *);
+/* That route's plan without a device (a pure function; the call itself plans through it).
+ * in[7]: [0] metric code (as lantern_gpu_plan_dense)  [1] 16-byte chunks per stored row  [2] k  [3] skip  [4] the min_group setting
+ *   [5] the index is a compact pq index (0 / 1)  [6] LANTERN_GPU_DENSE_NATIVE (-1: unset)
+ * queries[nq][3]: per query [0] a filter id (-1: a NULL entry; equal ids for equal handles)  [1] that filter's allowed rows
+ *   [2] the query's path is exact (0 / 1)
+ * out[6]: [0] dense groups  [1] dense queries  [2] 0: at least one group is dense; else why none is: 1 the setting is 0,
+ *   2 k + skip > 240, 3 a compact pq index, 4 the dense groups' rows do not fit 32 bits, 5 no handle stands behind min_group
+ *   exact-path queries  [3] kk = k + skip + 16 survivors per query (0: nothing dense)  [4] rows per gathered chunk of the list
+ *   [5] rows of the concatenated list
+ * group[nq]: the dense group of each query, 0xFFFFFFFF: none.  order[nq]: its first out[1] entries are the dense queries as the run
+ *   holds them (original query indices): groups by the first query that names them, a group's queries in call order.
+ * seg[nq + 1]: its first out[0] + 1 entries are the groups' offsets into the concatenated list.
+ * steps[i] = { first dense query, queries (<= 1024), first list position, positions }: one contraction launch -- a tile of ONE
+ *   group's queries against that group's positions inside ONE chunk of 65 536 positions; chunk-major, then by group, then by tile.
+ *   The first `cap` are written, *n_steps is their number.  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_each_dense(const int64_t in[7], const int64_t queries[][3], size_t nq, uint32_t out[6],
+                                                                    uint32_t group[], uint32_t order[], uint32_t seg[], uint32_t steps[][4],
+                                                                    size_t cap, size_t *n_steps);
 /* lantern_gpu_search_batch through a filter (host buffers; the unused tail of a row is label 0 and +inf) */
 LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered(usearch_index_t, const lantern_gpu_filter_t *, const void *queries, size_t nq,
                                                           usearch_scalar_kind_t, size_t k, size_t ef, usearch_label_t *labels,

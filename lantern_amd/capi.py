@@ -128,6 +128,7 @@ EXPORTS = [
     "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds", "lantern_gpu_set_filter_compact", "lantern_gpu_filter_compact", "lantern_gpu_plan_filtered_compact",
     # ... the exact path's dense route (lantern_gpu.h "THE EXACT PATH'S DENSE ROUTE")
     "lantern_gpu_set_filter_dense", "lantern_gpu_filter_dense", "lantern_gpu_filter_dense_stats", "lantern_gpu_plan_filtered_dense",
+    "lantern_gpu_set_filter_dense_each", "lantern_gpu_filter_dense_each", "lantern_gpu_last_filtered_each_dense", "lantern_gpu_plan_filtered_each_dense",
     # ... with per-query k, ef and skip as well (lantern_gpu.h "PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_filtered_each_params", "lantern_gpu_search_batch_filtered_each_params_lane",
     "lantern_gpu_search_batch_filtered_each_params_device", "lantern_gpu_last_filtered_each_params", "lantern_gpu_plan_filtered_params",
@@ -364,6 +365,10 @@ def lib() -> C.CDLL:
         "lantern_gpu_filter_dense": (sz, [vp, err]),
         "lantern_gpu_filter_dense_stats": (None, [vp, vp, err]),
         "lantern_gpu_plan_filtered_dense": (C.c_char_p, [vp, vp, vp, sz, vp]),
+        "lantern_gpu_set_filter_dense_each": (None, [vp, sz, err]),
+        "lantern_gpu_filter_dense_each": (sz, [vp, err]),
+        "lantern_gpu_last_filtered_each_dense": (None, [vp, vp, err]),
+        "lantern_gpu_plan_filtered_each_dense": (C.c_char_p, [vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]),
         "lantern_gpu_filter_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_filtered_compact": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
@@ -553,6 +558,32 @@ def plan_filtered_dense(mcode, chunks, allowed, nq, k, skip=0, min_queries=0, ex
     return {"taken": bool(out[0]), "why": FILTERED_DENSE_WHY[int(out[1])], "kk": int(out[2]), "gather_rows": int(out[3]),
             "gather_bytes": int(out[4]) | int(out[5]) << 32, "norm_bytes": int(out[6]) | int(out[7]) << 32, "n_steps": int(count.value),
             "steps": [(int(s[0]), int(s[1]), bool(s[2]), int(s[3])) for s in steps[:cap]]}
+
+
+# lantern_gpu_plan_filtered_each_dense's out[2], by value
+FILTERED_EACH_DENSE_WHY = ("taken", "off", "wide", "compact", "too_many_rows", "no_group")
+
+
+def plan_filtered_each_dense(mcode, chunks, k, skip, min_group, ids, counts, exact, compact=False, native=-1):
+    """lantern_gpu_plan_filtered_each_dense: which queries of a per-query-filter call form dense groups, and the segmented run's steps
+    (host arithmetic, no device).  ids[i]: -1 for a NULL entry, equal for equal handles; counts[i]: that filter's allowed rows;
+    exact[i]: the query's path is exact.  {"why" (FILTERED_EACH_DENSE_WHY), "groups", "queries", "kk", "gather_rows", "rows",
+    "group": [nq], "order": [queries], "seg": [groups + 1], "n_steps", "steps": [(q0, nqt, col0, cols), ...]}."""
+    nq = len(ids)
+    pin = np.array([mcode, chunks, k, skip, min_group, int(bool(compact)), native], np.int64)
+    per = np.ascontiguousarray(np.stack([np.asarray(ids, np.int64), np.asarray(counts, np.int64), np.asarray(exact, np.int64)], axis=1)) if nq else np.zeros((1, 3), np.int64)
+    out, count = np.zeros(6, np.uint32), C.c_size_t(0)
+    group, order, seg = np.zeros(max(nq, 1), np.uint32), np.zeros(max(nq, 1), np.uint32), np.zeros(nq + 1, np.uint32)
+    why = lib().lantern_gpu_plan_filtered_each_dense(_ptr(pin), _ptr(per), nq, _ptr(out), _ptr(group), _ptr(order), _ptr(seg), None, 0, C.byref(count))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    cap = min(count.value, 1 << 20)
+    steps = np.zeros((max(cap, 1), 4), np.uint32)
+    lib().lantern_gpu_plan_filtered_each_dense(_ptr(pin), _ptr(per), nq, _ptr(out), _ptr(group), _ptr(order), _ptr(seg), _ptr(steps), cap, C.byref(count))
+    groups, queries = int(out[0]), int(out[1])
+    return {"why": FILTERED_EACH_DENSE_WHY[int(out[2])], "groups": groups, "queries": queries, "kk": int(out[3]), "gather_rows": int(out[4]), "rows": int(out[5]),
+            "group": [int(x) for x in group[:nq]], "order": [int(x) for x in order[:queries]], "seg": [int(x) for x in seg[:groups + 1]] if groups else [],
+            "n_steps": int(count.value), "steps": [tuple(int(x) for x in s) for s in steps[:cap]]}
 
 
 def l2sq_dist(a, b) -> float:
@@ -949,6 +980,21 @@ class GpuIndex:
         _call("lantern_gpu_filter_dense_stats", self.h, _ptr(out))
         calls, queries, certified, recomputed = (int(x) for x in out)
         return {"calls": calls, "queries": queries, "certified": certified, "recomputed": recomputed}
+
+    def set_filter_dense_each(self, min_group):
+        """In search_batch_filtered_each / _each_device, min_group exact-path queries behind one filter handle take the dense route (0 = off, the default)."""
+        _call("lantern_gpu_set_filter_dense_each", self.h, int(min_group))
+
+    def filter_dense_each(self):
+        """lantern_gpu_filter_dense_each: the min_group setting."""
+        return int(_call("lantern_gpu_filter_dense_each", self.h))
+
+    def last_filtered_each_dense(self):
+        """The dense run of the last per-query filtered call on this index (lantern_gpu_last_filtered_each_dense)."""
+        out = np.zeros(6, dtype=np.uint32)
+        _call("lantern_gpu_last_filtered_each_dense", self.h, _ptr(out))
+        groups, queries, certified, recomputed, rows, steps = (int(x) for x in out)
+        return {"groups": groups, "queries": queries, "certified": certified, "recomputed": recomputed, "rows": rows, "steps": steps}
 
     def filter_compact(self):
         """lantern_gpu_filter_compact: None (the switch is off), or what a filtered search runs on now: "stored", "decode" or "adc"."""

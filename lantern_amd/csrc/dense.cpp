@@ -1,6 +1,8 @@
 // dense.cpp -- the dense path's host side: distance matrices and the SQL-callable distances, and the exact k-NN (exact search, PQ
 // encoding, assign_to_clusters) as a pure plan (plan_exact_knn: lantern_gpu_plan_exact_knn shows it without a device) and one run of it;
-// the same run over a filter's slot list is the filtered exact path's dense route (plan_filtered_dense, filtered_dense_device).
+// the same run over a filter's slot list is the filtered exact path's dense route (plan_filtered_dense, filtered_dense_device), and over
+// the concatenated lists of a per-query-filter call's groups, segment by segment, that call's (plan_filtered_each_dense,
+// filtered_each_dense_device).
 // The kernels: bruteforce.hip, dense_native.hip; the two launchers this unit calls them through: kernels.hpp.
 #include "dense.hpp"
 #include "index.hpp"
@@ -13,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 
 namespace lgpu {
 
@@ -205,21 +208,43 @@ KnnStep ExactKnnPlan::step(size_t i) const
     return { (uint32_t)q0, (uint32_t)std::min<size_t>(qtile, nq - q0), (uint32_t)(c0 + first), (uint32_t)(cols ? cols : nc - first), fused && !cols ? 1u : 0u };
 }
 
+// the steps of a plan that contracts every query with every row, as the list a run executes
+static std::vector<KnnStep> plan_steps(const ExactKnnPlan &p)
+{
+    std::vector<KnnStep> steps(p.n_steps);
+    for(size_t i = 0; i < p.n_steps; ++i) steps[ i ] = p.step(i);
+    return steps;
+}
+
 // One run of a plan.  certified: one flag per query (1: the certificate of DESIGN.md 4.5 holds -- the result is the exact answer; 0: the
 // caller recomputes the query in exact order, exact_knn_fallback).  *overflowed: a candidate list ran out of room (adversarially
 // ordered rows): the caller repeats the search unfused.
 // d_list == NULL: the base rows are d_base[0, nb).  Otherwise they are d_base[d_list[0, nb)], d_list ascending (a filter's slot list):
 // every chunk is gathered into a contiguous block with its norms (k_gather_rows_norms) where the plain run points into d_base, the
 // keys hold positions in the list, and the re-rank reads and emits through it.
-static bool exact_knn_run(const ExactKnnPlan &p, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots, float *d_dists,
-                          hipStream_t st, bool *overflowed, std::vector<uint32_t> &certified)
+// steps: the contraction launches, chunk-major, none across a chunk of p.chunk_rows rows -- plan_steps(p) for the two plans that
+// contract every query with every row, EachDensePlan::steps for the segmented run (a query's keys then come from its own segment of
+// the list only; everything behind the contractions is per query and runs unchanged).
+// queued: NULL, or what the caller queues behind the certificate and in front of the wait, given the device flags (NULL: exact keys).
+static bool exact_knn_run(const ExactKnnPlan &p, const std::vector<KnnStep> &steps, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q,
+                          uint32_t *d_slots, float *d_dists, hipStream_t st, bool *overflowed, std::vector<uint32_t> &certified,
+                          const EachDenseAnswers *queued = nullptr)
 try {
     int dev = 0;
     (void)hipGetDevice(&dev);
     KnnPool *const               pool = (dev >= 0 && dev < 16) ? &g_knn_pool[ dev ] : nullptr;
     std::unique_lock<std::mutex> pool_lock;
     if(pool) pool_lock = std::unique_lock<std::mutex>(pool->mu);
+    // An exception (bad_alloc in a host vector) behind queued launches unwinds through here: destroyed before the lock and the blocks,
+    // this waits for the stream first, so that nothing queued names a pooled or freed block when the next run takes the pool.
+    struct SyncOnUnwind
+    {
+        hipStream_t st;
+        int         live = std::uncaught_exceptions();
+        ~SyncOnUnwind() { if(std::uncaught_exceptions() > live) (void)hipStreamSynchronize(st); }
+    };
     DeviceBlock b_aux, b_dd, b_cand, b_fq, b_fb, b_gb;  // (fq, fb: f32 copies of quantised rows -- the queries; one chunk of base rows.  gb: a gathered chunk)
+    const SyncOnUnwind sync_on_unwind{ st };  // (declared last: destroyed first)
     const uint32_t nq = (uint32_t)p.nq, nb = (uint32_t)p.nb, kk = p.kk, chunks = p.chunks, fchunks = p.fchunks;
     const int      base_metric = mcode_base(p.mcode);
     auto dequant = [&](const uint4 *src, size_t nchunks, uint4 *dst) { return p.copy == 2 ? launch_dequant_i8(src, nchunks, dst, st) : launch_dequant_f16(src, nchunks, dst, st); };
@@ -254,8 +279,8 @@ try {
                 ok = ok && launch_norms(p.kind, base_metric, fb, (uint32_t)nc, fchunks, bn + c0, st) == hipSuccess;
                 bv = fb;
             }
-            for(; ok && si < p.n_steps && p.step(si).col0 < c0 + nc; ++si) {
-                const KnnStep       s = p.step(si);
+            for(; ok && si < steps.size() && steps[ si ].col0 < c0 + nc; ++si) {
+                const KnnStep       s = steps[ si ];
                 uint64_t *const     mine = best + (size_t)s.q0 * kk;
                 const DenseOperands o = { p.kind, base_metric, qv + (size_t)s.q0 * fchunks, s.nqt, bv + (s.col0 - c0) * fchunks, s.cols, fchunks, qn + s.q0, bn + s.col0 };
                 const DenseTopk     tk = { mine, kk, cand, ccnt, p.cand_cap, s.col0 };
@@ -280,6 +305,7 @@ try {
         }
         uint32_t over = 0;
         if(p.fused) ok = ok && hipMemcpyAsync(&over, cover, 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+        if(queued) ok = ok && (*queued)(p.exact_keys ? nullptr : flag);
         ok = ok && hipStreamSynchronize(st) == hipSuccess;
         if(overflowed) *overflowed = over != 0;
         if(ok && certified[ p.nq ])  // a cosine row norm outside the bound's range: nothing is certified
@@ -327,12 +353,12 @@ static bool exact_knn_certified(const ExactKnnPlan &first, int native, const uin
                                 float *d_dists, hipStream_t st, std::vector<uint32_t> &certified, std::vector<uint32_t> &refused)
 {
     bool over = false;
-    if(!exact_knn_run(first, d_base, d_list, d_q, d_slots, d_dists, st, &over, certified)) return false;
+    if(!exact_knn_run(first, plan_steps(first), d_base, d_list, d_q, d_slots, d_dists, st, &over, certified)) return false;
     if(over) {  // the same call, unfused
         ExactKnnPlan plan;
         if(plan_exact_knn(first.mcode, first.chunks, (int64_t)first.nb, (int64_t)first.nq, (int64_t)first.k, native, 0, plan) != nullptr) return false;
         plan.gb_bytes = first.gb_bytes;
-        if(!exact_knn_run(plan, d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified)) return false;
+        if(!exact_knn_run(plan, plan_steps(plan), d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified)) return false;
     }
     refused.clear();
     for(size_t q = 0; q < first.nq; ++q)
@@ -373,6 +399,84 @@ try {
     if(!exact_knn_certified(p.knn, native, d_base, d_list, d_q, d_slots, d_dists, st, certified, refused)) return false;
     // the flags as the host settled them (a cosine norm out of range refuses every query) back to the device, for the answer kernel
     return hipMemcpyAsync(d_flags, certified.data(), p.knn.nq * 4, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+}
+LANTERN_ABI_CATCH(nullptr)
+
+// ---- the same route for a per-query-filter call: the groups of queries sharing a filter handle, one segmented run -------------------
+const char *plan_filtered_each_dense(int64_t mcode, int64_t chunks, int64_t k, int64_t skip, int64_t min_group, bool compact, int native, const int64_t *ids,
+                                     const int64_t *counts, const uint8_t *exact, size_t nq, EachDensePlan &p)
+{
+    p = EachDensePlan();
+    if(k < 0 || skip < 0 || min_group < 0 || k > 0xFFFFFFFFll || skip > 0xFFFFFFFFll || nq > 0xFFFFFFFFull || (nq && (!ids || !counts || !exact))) return kBadPlan;
+    for(size_t i = 0; i < nq; ++i)
+        if(ids[ i ] < -1 || counts[ i ] < 0 || counts[ i ] > 0xFFFFFFFFll) return kBadPlan;
+    {  // (the operands are checked on either side of the decision, as plan_filtered_dense does)
+        ExactKnnPlan o;
+        if(const char *why = plan_operands(mcode, chunks, 0, native, o)) return why;
+    }
+    p.group.assign(nq, 0xFFFFFFFFu);
+    // the call-level reasons in the order the call meets them: the switch, the width, the index
+    if(min_group == 0) return p.why = kEachDenseOff, nullptr;
+    if(k + skip > 240) return p.why = kEachDenseWide, nullptr;
+    if(compact) return p.why = kEachDenseCompact, nullptr;
+    p.why = kEachDenseNoGroup;
+    if(k == 0) return nullptr;
+    // the exact-path queries behind a non-empty filter by (id, call order): a run of one id of at least min_group queries is a group
+    std::vector<uint32_t> cand;
+    for(size_t i = 0; i < nq; ++i)
+        if(exact[ i ] && ids[ i ] >= 0 && counts[ i ] > 0) cand.push_back((uint32_t)i);
+    std::stable_sort(cand.begin(), cand.end(), [&](uint32_t x, uint32_t y) { return ids[ x ] < ids[ y ]; });
+    std::vector<std::pair<uint32_t, uint32_t>> runs;  // (first position in cand, length), then ordered by the first query: cand[first]
+    for(size_t a = 0, b; a < cand.size(); a = b) {
+        for(b = a + 1; b < cand.size() && ids[ cand[ b ] ] == ids[ cand[ a ] ]; ++b) {}
+        if((int64_t)(b - a) >= min_group) runs.push_back({ (uint32_t)a, (uint32_t)(b - a) });
+    }
+    if(runs.empty()) return nullptr;
+    std::sort(runs.begin(), runs.end(), [&](const auto &x, const auto &y) { return cand[ x.first ] < cand[ y.first ]; });
+    uint64_t rows = 0;
+    for(const auto &r : runs) rows += (uint64_t)counts[ cand[ r.first ] ];
+    if(rows > 0xFFFFFFFFull) return p.why = kEachDenseTooMany, nullptr;
+    p.qoff.push_back(0);
+    p.seg.push_back(0);
+    for(size_t g = 0; g < runs.size(); ++g) {
+        for(uint32_t j = 0; j < runs[ g ].second; ++j) {
+            const uint32_t q = cand[ runs[ g ].first + j ];
+            p.group[ q ] = (uint32_t)g;
+            p.order.push_back(q);
+        }
+        p.qoff.push_back((uint32_t)p.order.size());
+        p.seg.push_back(p.seg.back() + (uint32_t)counts[ cand[ runs[ g ].first ] ]);
+    }
+    if(const char *why = plan_exact_knn(mcode, chunks, (int64_t)rows, (int64_t)p.order.size(), k + skip, native, 0, p.knn)) {
+        p = EachDensePlan();
+        return why;
+    }
+    p.why = kEachDenseTaken;
+    p.gather_rows = p.knn.chunk_rows;
+    p.knn.gb_bytes = (size_t)p.knn.chunk_rows * p.knn.chunks * 16;
+    size_t g_lo = 0;  // the first group that reaches into the chunk
+    for(uint64_t c0 = 0; c0 < rows; c0 += p.knn.chunk_rows) {
+        const uint64_t c1 = std::min<uint64_t>(rows, c0 + p.knn.chunk_rows);
+        while(p.seg[ g_lo + 1 ] <= c0) ++g_lo;
+        for(size_t g = g_lo; g < runs.size() && p.seg[ g ] < c1; ++g) {
+            const uint32_t col0 = (uint32_t)std::max<uint64_t>(p.seg[ g ], c0), cols = (uint32_t)std::min<uint64_t>(p.seg[ g + 1 ], c1) - col0;
+            for(uint32_t q0 = p.qoff[ g ]; q0 < p.qoff[ g + 1 ]; q0 += p.knn.qtile)
+                p.steps.push_back({ q0, std::min(p.knn.qtile, p.qoff[ g + 1 ] - q0), col0, cols, 0u });
+        }
+    }
+    return nullptr;
+}
+
+bool filtered_each_dense_device(const EachDensePlan &p, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots, float *d_dists,
+                                hipStream_t st, const EachDenseAnswers &answers, std::vector<uint32_t> &refused)
+try {
+    if(p.why != kEachDenseTaken || !d_list) return false;
+    std::vector<uint32_t> certified;
+    if(!exact_knn_run(p.knn, p.steps, d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified, &answers)) return false;
+    refused.clear();
+    for(size_t q = 0; q < certified.size(); ++q)
+        if(!certified[ q ]) refused.push_back((uint32_t)q);
+    return true;
 }
 LANTERN_ABI_CATCH(nullptr)
 
@@ -543,6 +647,38 @@ try {
         steps[ i ][ 0 ] = s.nqt; steps[ i ][ 1 ] = s.cols; steps[ i ][ 2 ] = s.fused; steps[ i ][ 3 ] = s.col0;
     }
     *n_steps = p.knn.n_steps;
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
+
+const char *lantern_gpu_plan_filtered_each_dense(const int64_t in[ 7 ], const int64_t queries[][ 3 ], size_t nq, uint32_t out[ 6 ], uint32_t group[],
+                                                 uint32_t order[], uint32_t seg[], uint32_t steps[][ 4 ], size_t cap, size_t *n_steps)
+try {
+    if(!in || !out || !n_steps || (cap && !steps) || (nq && (!queries || !group || !order || !seg))) return "lantern_gpu: null plan array";
+    std::vector<int64_t> ids(nq), counts(nq);
+    std::vector<uint8_t> exact(nq);
+    for(size_t i = 0; i < nq; ++i) { ids[ i ] = queries[ i ][ 0 ]; counts[ i ] = queries[ i ][ 1 ]; exact[ i ] = queries[ i ][ 2 ] != 0; }
+    EachDensePlan p;
+    if(const char *why = plan_filtered_each_dense(in[ 0 ], in[ 1 ], in[ 2 ], in[ 3 ], in[ 4 ], in[ 5 ] != 0, in[ 6 ] < 0 ? -1 : in[ 6 ] != 0, ids.data(),
+                                                  counts.data(), exact.data(), nq, p))
+        return why;
+    const bool taken = p.why == kEachDenseTaken;
+    out[ 0 ] = (uint32_t)p.groups();
+    out[ 1 ] = (uint32_t)p.order.size();
+    out[ 2 ] = (uint32_t)p.why;
+    out[ 3 ] = taken ? p.knn.kk : 0u;
+    out[ 4 ] = p.gather_rows;
+    out[ 5 ] = taken ? p.seg.back() : 0u;
+    std::copy(p.group.begin(), p.group.end(), group);
+    std::copy(p.order.begin(), p.order.end(), order);
+    std::copy(p.seg.begin(), p.seg.end(), seg);
+    for(size_t i = 0; i < p.steps.size() && i < cap; ++i) {
+        const KnnStep &s = p.steps[ i ];
+        steps[ i ][ 0 ] = s.q0; steps[ i ][ 1 ] = s.nqt; steps[ i ][ 2 ] = s.col0; steps[ i ][ 3 ] = s.cols;
+    }
+    *n_steps = p.steps.size();
     return nullptr;
 }
 catch(...) {

@@ -4,6 +4,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 namespace lgpu {
@@ -82,6 +83,47 @@ const char *plan_filtered_dense(int64_t mcode, int64_t chunks, int64_t allowed, 
 // `refused` and their rows of the result are not the answer: the caller recomputes them.  Waits for `st`.
 bool filtered_dense_device(const FilteredDensePlan &p, int native, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots,
                            float *d_dists, uint32_t *d_flags, hipStream_t st, std::vector<uint32_t> &refused);
+
+// The dense route of a PER-QUERY-FILTER call (DESIGN.md 4.9 "Dense exact path, per-query filters"): the exact-path queries that share
+// a filter handle form a group; the groups of at least min_group queries are answered by ONE segmented run of the exact k-NN -- group
+// g's queries against group g's rows only.  lantern_gpu_plan_filtered_each_dense shows the plan without a device.
+enum EachDenseWhy : uint32_t
+{
+    kEachDenseTaken = 0,
+    kEachDenseOff,       // min_group == 0
+    kEachDenseWide,      // k + skip > 240
+    kEachDenseCompact,   // a compact pq index
+    kEachDenseTooMany,   // the dense groups' rows, concatenated, do not fit 32 bits
+    kEachDenseNoGroup    // no filter handle stands behind min_group exact-path queries (or nothing asked for)
+};
+struct EachDensePlan
+{
+    EachDenseWhy          why = kEachDenseOff;
+    std::vector<uint32_t> group;  // [nq] the dense group of a query, 0xFFFFFFFF: none (it runs as without the setting)
+    std::vector<uint32_t> order;  // the dense queries as the run holds them: groups by the first query that names them, a group's queries in call order
+    std::vector<uint32_t> qoff;   // [groups + 1] group g's queries are order[qoff[g], qoff[g + 1])
+    std::vector<uint32_t> seg;    // [groups + 1] group g's rows are positions [seg[g], seg[g + 1]) of the concatenated slot list L
+    // plan_exact_knn(mcode, chunks, nb = seg.back(), nq = order.size(), k + skip), unfused, with gb_bytes: the run's buffers.  Its own
+    // n_steps / step() are the unsegmented run's and are not used: the run executes `steps`
+    ExactKnnPlan          knn;
+    uint32_t              gather_rows = 0;  // rows per gathered chunk of L
+    // a tile (<= qtile) of one group's queries against that group's positions inside one chunk of L: chunk-major, then by group, then
+    // by tile; q0 in `order` coordinates, col0 in L coordinates
+    std::vector<KnnStep>  steps;
+    size_t groups() const { return qoff.empty() ? 0 : qoff.size() - 1; }
+};
+// pure, as plan_exact_knn.  Per query i: ids[i] -- -1 for a NULL entry, else equal for equal handles; counts[i] -- its filter's allowed
+// rows; exact[i] -- its path is exact.  NULL, or why the input is refused; a call without a dense group is not refused.
+const char *plan_filtered_each_dense(int64_t mcode, int64_t chunks, int64_t k, int64_t skip, int64_t min_group, bool compact, int native, const int64_t *ids,
+                                     const int64_t *counts, const uint8_t *exact, size_t nq, EachDensePlan &p);
+// One run of a taken plan.  d_list: L; d_q: the dense queries' rows, gathered in the plan's order.  Result (device), per dense query:
+// slots[k + skip] ascending by (exact-order distance, slot), dists alike.  `answers`, queued behind the certificate and in front of
+// the run's ONE wait for `st`, is given the device flags -- [q] 1: certified, [nq] != 0: a cosine row norm of ANY segment is outside the
+// certificate's range, which refuses every query of the run -- or NULL: every query is certified (exact keys).  `refused`: the
+// dense queries (positions in the plan's order) whose rows of the result are not the answer; the caller recomputes them.
+using EachDenseAnswers = std::function<bool(const uint32_t *d_flags)>;
+bool filtered_each_dense_device(const EachDensePlan &p, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots, float *d_dists,
+                                hipStream_t st, const EachDenseAnswers &answers, std::vector<uint32_t> &refused);
 
 // Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row).
 // Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].

@@ -514,6 +514,124 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     return true;
 }
 
+// ---- the dense route of a per-query-filter call (DESIGN.md 4.9 "Dense exact path, per-query filters") -----------------------------
+// k_concat_slot_lists: the dense groups' slot lists, each a filter's own, into the call's one list L -- group g at positions
+// [seg[g], seg[g + 1]).  One thread per position: its group by binary search over seg (strictly ascending: no group is empty), its
+// slot from that group's list.
+__global__ void __launch_bounds__(256) k_concat_slot_lists(const uint32_t *const *lists, const uint32_t *seg, uint32_t groups, uint32_t *out)
+{
+    const uint32_t total = seg[ groups ];
+    for(size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (size_t)gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = groups;  // seg[lo] <= p < seg[hi]
+        while(hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if(seg[ mid ] <= p) lo = mid; else hi = mid;
+        }
+        out[ p ] = lists[ lo ][ p - seg[ lo ] ];
+    }
+}
+
+// k_dense_each_answers: k_dense_answers for the segmented run -- dense query q (its re-ranked row: kk = k + skip entries) is the
+// call's query orig[q] and stands behind a filter of allowed[q] rows: its cells go to the row of orig[q], D = allowed[q].  flags ==
+// NULL: every query is certified; else flags[q] says so, and flags[nq] != 0 (a cosine row norm out of the certificate's range, in any
+// segment) refuses them all.  The refused queries' rows are left alone: the per-query launch behind this one answers them.
+__global__ void __launch_bounds__(256) k_dense_each_answers(const uint32_t *slots, const float *dists, const uint32_t *flags, const uint32_t *orig,
+                                                            const uint32_t *allowed, uint32_t nq, uint32_t kk, uint32_t k, uint32_t skip, const uint64_t *labels,
+                                                            uint32_t n, uint64_t *out_labels, float *out_dists, uint32_t *out_slots, uint32_t *out_counts,
+                                                            uint64_t *out_D, uint64_t *out_E, unsigned long long *totals)
+{
+    if(flags && flags[ nq ]) return;
+    const size_t cells = (size_t)nq * k;
+    for(size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells; c += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t q = (uint32_t)(c / k), i = (uint32_t)(c % k);
+        if(flags && !flags[ q ]) continue;
+        const uint32_t al = allowed[ q ], have = al < kk ? al : kk, got = have <= skip ? 0u : (have - skip < k ? have - skip : k);
+        const uint32_t oq = orig[ q ];
+        const size_t   o = (size_t)oq * k + i;
+        if(i < got) {
+            const size_t   at = (size_t)q * kk + skip + i;
+            const uint32_t slot = slots[ at ];
+            if(out_labels) out_labels[ o ] = slot < n ? labels[ slot ] : 0;  // (every slot of the first `have` entries is a row's)
+            if(out_dists) out_dists[ o ] = dists[ at ];
+            if(out_slots) out_slots[ o ] = slot;
+        } else {
+            if(out_labels) out_labels[ o ] = 0;  // INVALID_ELEMENT_LABEL (hnsw.h:40)
+            if(out_dists) out_dists[ o ] = __builtin_inff();
+            if(out_slots) out_slots[ o ] = EMPTY;
+        }
+        if(i == 0) {
+            if(out_counts) out_counts[ oq ] = got;
+            if(out_D) out_D[ oq ] = al;
+            if(out_E) out_E[ oq ] = 0;
+            if(totals) atomicAdd(&totals[ 0 ], (unsigned long long)al);
+        }
+    }
+}
+
+// The dense groups of one per-query-filter call, planned by `plan` (taken): L, the tables and the gathered queries into the dense
+// scratch block, the segmented run with the answer kernel queued in front of its wait.  refused: the call's queries (original
+// indices) the certificate refused, which the call's exact launch answers.  Waits for the stream, once.
+static bool filtered_each_dense_locked(Index *ix, const Filter *const *filters, const EachDensePlan &plan, const uint4 *d_q, size_t k, size_t skip,
+                                       const SearchOut &out, hipStream_t stream, std::vector<uint32_t> &refused)
+{
+    static const char *kDenseFailed = "lantern_gpu: HIP failure on the dense route of a per-query filtered call";
+    const size_t nqd = plan.order.size(), groups = plan.groups(), total = plan.seg.back(), kk = k + skip, row = (size_t)ix->chunks * 16;
+    auto         up = [](size_t x, size_t a) { return (x + a - 1) / a * a; };
+    // host tables, one copy: orig[nqd] | allowed[nqd] | seg[groups + 1] | lists[groups] (8-byte aligned)
+    const size_t          t_orig = 0, t_allowed = nqd * 4, t_seg = 2 * nqd * 4, t_lists = up(t_seg + (groups + 1) * 4, 8), t_bytes = t_lists + groups * 8;
+    std::vector<uint64_t> tbl(t_bytes / 8);
+    char *const           ht = (char *)tbl.data();
+    uint32_t *const       h_orig = (uint32_t *)(ht + t_orig), *h_allowed = (uint32_t *)(ht + t_allowed);
+    const uint32_t      **h_lists = (const uint32_t **)(ht + t_lists);
+    std::copy(plan.order.begin(), plan.order.end(), h_orig);
+    std::copy(plan.seg.begin(), plan.seg.end(), (uint32_t *)(ht + t_seg));
+    for(size_t g = 0; g < groups; ++g) {
+        const Filter *f = filters[ plan.order[ plan.qoff[ g ] ] ];
+        h_lists[ g ] = f->d_slots;
+        for(uint32_t j = plan.qoff[ g ]; j < plan.qoff[ g + 1 ]; ++j) h_allowed[ j ] = (uint32_t)f->count;
+    }
+    // the device block: tables | L | gathered queries | slots | dists
+    const size_t b_list = up(t_bytes, 16), b_q = up(b_list + total * 4, 16), b_slots = b_q + nqd * row, b_dists = b_slots + nqd * kk * 4;
+    char *const  blk = (char *)scratch(ix, kScratchDenseAnswers, b_dists + nqd * kk * 4);
+    if(!blk) return false;
+    uint32_t *const d_orig = (uint32_t *)(blk + t_orig), *d_allowed = (uint32_t *)(blk + t_allowed), *d_seg = (uint32_t *)(blk + t_seg);
+    uint32_t *const d_list = (uint32_t *)(blk + b_list), *d_slots = (uint32_t *)(blk + b_slots);
+    float *const    d_dists = (float *)(blk + b_dists);
+    uint4 *const    d_gq = (uint4 *)(blk + b_q);
+    if(!order_after_inserts(ix, stream)) return false;
+    bool ok = hipMemcpyAsync(blk, ht, t_bytes, hipMemcpyHostToDevice, stream) == hipSuccess;
+    if(ok) {
+        const size_t blocks = std::min<size_t>((total + 255) / 256, 16384);
+        hipLaunchKernelGGL(k_concat_slot_lists, dim3((uint32_t)blocks), dim3(256), 0, stream, (const uint32_t *const *)(blk + t_lists), (const uint32_t *)d_seg,
+                           (uint32_t)groups, d_list);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && launch_gather_rows(d_q, ix->chunks, d_orig, (uint32_t)nqd, d_gq, stream) == hipSuccess;
+    const EachDenseAnswers answers = [ & ](const uint32_t *d_flags) {
+        const size_t blocks = std::min<size_t>((nqd * k + 255) / 256, 16384);
+        hipLaunchKernelGGL(k_dense_each_answers, dim3((uint32_t)blocks), dim3(256), 0, stream, (const uint32_t *)d_slots, (const float *)d_dists, d_flags,
+                           (const uint32_t *)d_orig, (const uint32_t *)d_allowed, (uint32_t)nqd, (uint32_t)kk, (uint32_t)k, (uint32_t)skip,
+                           (const uint64_t *)ix->d_labels, (uint32_t)ix->n, out.labels, out.dists, out.slots, out.counts, out.D, out.E,
+                           (unsigned long long *)(ix->d_totals + kTotSearch));
+        return hipGetLastError() == hipSuccess;
+    };
+    std::vector<uint32_t> refused_at;
+    ok = ok && filtered_each_dense_device(plan, ix->d_vec, d_list, d_gq, d_slots, d_dists, stream, answers, refused_at);
+    if(!ok) {
+        (void)hipStreamSynchronize(stream);  // (nothing queued may still read the host tables or the block)
+        return set_err(ix, kDenseFailed), false;
+    }
+    refused.clear();
+    for(uint32_t at : refused_at) refused.push_back(plan.order[ at ]);
+    ix->c_filter_dense[ 0 ] += 1;
+    ix->c_filter_dense[ 1 ] += nqd;
+    ix->c_filter_dense[ 2 ] += nqd - refused.size();
+    ix->c_filter_dense[ 3 ] += refused.size();
+    const uint32_t shape[ 6 ] = { (uint32_t)groups, (uint32_t)nqd, (uint32_t)(nqd - refused.size()), (uint32_t)refused.size(), (uint32_t)total, (uint32_t)plan.steps.size() };
+    std::copy(std::begin(shape), std::end(shape), ix->last_each_dense);
+    return true;
+}
+
 // ---- the per-query form: filters[i] is query i's filter ------------------------------------------------------------------------
 // bytes of the host block filtered_each_locked stages its selection lists and descriptor table in
 // (`params`: with the per-query-parameter form's rows)
@@ -592,10 +710,16 @@ static bool each_launches(Index *ix, const Filter *const *filters, size_t nq, co
 // walk launch), where a descriptor with count 0 gives the empty answer without touching a row.
 // `h_tbl`: a page-locked block of each_table_bytes(nq) that stays untouched until the stream work is done, or NULL (pageable
 // staging: the copies then complete before this returns).  false -> ix->err; nothing has been launched unless the failure is HIP's.
+// dense_call: one of the two entry points that may send groups of exact-path queries sharing a filter handle through the dense route
+// (lantern_gpu_set_filter_dense_each): those queries leave the exact list, the dense run answers them in front of the launches, and
+// the ones its certificate refuses come back into the exact list.  The lane form never does.  With a dense group the sentence above
+// holds up to the dense run only: when a launch behind it is then refused for a reason that is not HIP's (a scratch block, a launch
+// slot), the call fails with the certified dense queries' rows already written and their D already in the cumulative counter.
 static bool filtered_each_locked(Index *ix, const Filter *const *filters, const uint4 *d_q, size_t nq, size_t k, size_t ef, size_t skip,
-                                 const SearchOut &out, hipStream_t stream, char *h_tbl)
+                                 const SearchOut &out, hipStream_t stream, char *h_tbl, bool dense_call = false)
 {
     if(!each_filters_ok(ix, filters, nq)) return false;
+    std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);
     if(nq == 0 || k == 0) return true;
     const size_t ef_sel = ef ? ef : ix->ef;
     const size_t exp = std::max(ef_sel, k + skip);
@@ -608,17 +732,38 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
         (filter_takes_exact(ix, f, ef_sel) ? exact : walk).push_back((uint32_t)i);
     }
     const uint32_t n_walk = (uint32_t)walk.size(), n_exact = (uint32_t)exact.size(), n_empty = (uint32_t)empty.size();
-    // the exact group's queries differ in length by orders of magnitude: longest first, so that the launch's tail is a short one
-    std::stable_sort(exact.begin(), exact.end(), [&](uint32_t x, uint32_t y) { return filters[ x ]->count > filters[ y ]->count; });
-    std::vector<uint32_t> &host = (exact.empty() && !walk.empty()) ? walk : exact;
-    host.insert(host.end(), empty.begin(), empty.end());
 
+    // the launches' carves, and their refusals, by the lists as the path rule left them: the dense route below changes neither
     const FilteredArgs base = filtered_args(ix, d_q, k, skip, out);
     FilteredArgs aw = base, ae = base;
     aw.seeds = (uint32_t)ix->filter_seeds;  // (an unfiltered entry has no slot list: it runs the unseeded walk in the same launch)
     size_t       lds_w = 0, lds_e = 0;
     if(!walk.empty() && !filtered_shape(ix, false, k, skip, exp, aw, lds_w)) return false;
-    if(!exact.empty() && !filtered_shape(ix, true, k, skip, exp, ae, lds_e)) return false;
+    if((!exact.empty() || (walk.empty() && !empty.empty())) && !filtered_shape(ix, true, k, skip, exp, ae, lds_e)) return false;
+
+    if(dense_call && ix->filter_dense_each_min && !exact.empty()) {
+        const DenseEnv       env = dense_env();
+        std::vector<int64_t> ids(nq), counts(nq);
+        std::vector<uint8_t> is_exact(nq, 0);
+        for(size_t i = 0; i < nq; ++i) {
+            ids[ i ] = filters[ i ] ? (int64_t)(uintptr_t)filters[ i ] : -1;  // (a handle's address is a user-space one: never negative)
+            counts[ i ] = filters[ i ] ? (int64_t)filters[ i ]->count : 0;
+        }
+        for(uint32_t q : exact) is_exact[ q ] = 1;
+        EachDensePlan     dense;
+        const char *const bad = plan_filtered_each_dense(ix->mcode, ix->chunks, (int64_t)k, (int64_t)skip, (int64_t)ix->filter_dense_each_min, ix->pq_compact,
+                                                         env.native, ids.data(), counts.data(), is_exact.data(), nq, dense);
+        if(!bad && dense.why == kEachDenseTaken) {
+            std::vector<uint32_t> refused;
+            if(!filtered_each_dense_locked(ix, filters, dense, d_q, k, skip, out, stream, refused)) return false;
+            exact.erase(std::remove_if(exact.begin(), exact.end(), [&](uint32_t q) { return dense.group[ q ] != 0xFFFFFFFFu; }), exact.end());
+            exact.insert(exact.end(), refused.begin(), refused.end());
+        }
+    }
+    // the exact group's queries differ in length by orders of magnitude: longest first, so that the launch's tail is a short one
+    std::stable_sort(exact.begin(), exact.end(), [&](uint32_t x, uint32_t y) { return filters[ x ]->count > filters[ y ]->count; });
+    std::vector<uint32_t> &host = (exact.empty() && !walk.empty()) ? walk : exact;
+    host.insert(host.end(), empty.begin(), empty.end());
 
     const EachCounts c{ n_walk, n_exact, n_unfiltered, n_empty };
     return each_launches(ix, filters, nq, walk, exact, aw, lds_w, ae, lds_e, nullptr, c, stream, h_tbl);
@@ -697,6 +842,7 @@ static bool each_params_plan_locked(Index *ix, const Filter *const *filters, con
 static bool filtered_each_params_locked(Index *ix, const EachParamsPlan &plan, const Filter *const *filters, const uint4 *d_q, size_t nq, size_t k_stride,
                                         const SearchOut &out, hipStream_t stream, char *h_tbl)
 {
+    std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);  // (a per-query-filter call that makes no dense run)
     if(nq == 0) return true;
     const uint32_t shape[ 4 ] = { plan.sw.exp, plan.sw.cand_cap, plan.se.exp, plan.n_k0 };
     std::copy(std::begin(shape), std::end(shape), ix->last_each_params);
@@ -918,6 +1064,37 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
+void lantern_gpu_set_filter_dense_each(usearch_index_t h, size_t min_group, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->filter_dense_each_min = min_group;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+size_t lantern_gpu_filter_dense_each(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    return ix->filter_dense_each_min;
+}
+LANTERN_ABI_CATCH(e)
+
+void lantern_gpu_last_filtered_each_dense(usearch_index_t h, uint32_t out[ 6 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return;
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    std::lock_guard<std::mutex> g(ix->mu);
+    std::copy(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), out);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
 void lantern_gpu_last_filtered_seeds(usearch_index_t h, uint32_t out[ 4 ], usearch_error_t *e)
 try {
     CLEAR(e);
@@ -1005,7 +1182,7 @@ try {
     if(!ix) return;
     const SearchOut out{ d_labels, d_distances, d_slots, d_counts, d_D, d_E };
     device_trip(ix, stride_is(query_stride_bytes), [ & ] {
-        return filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream, nullptr);
+        return filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)d_queries, nq, k, ef, skip, out, (hipStream_t)stream, nullptr, true);
     }, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
@@ -1015,10 +1192,10 @@ static auto each_validate(const lantern_gpu_filter_t *const *filters, size_t nq)
 {
     return [ = ](Index *ix) { return each_filters_ok(ix, (const Filter *const *)filters, nq); };
 }
-static auto each_launch(Index *ix, const lantern_gpu_filter_t *const *filters, size_t nq, size_t k, size_t ef)
+static auto each_launch(Index *ix, const lantern_gpu_filter_t *const *filters, size_t nq, size_t k, size_t ef, bool dense_call)
 {
     return [ = ](const HostBatch &b) {
-        return filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra());
+        return filtered_each_locked(ix, (const Filter *const *)filters, (const uint4 *)b.d_q, nq, k, ef, 0, b.out(b.d_out), b.stream, b.h_extra(), dense_call);
     };
 }
 
@@ -1031,8 +1208,8 @@ try {
     if(!ix) return;
     if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null query or result pointer"); return; }
-    host_trip_sync(ix, nq, k, each_table_bytes(nq), queries, (int)kind, kFilteredBatchFailed, each_validate(filters, nq), each_launch(ix, filters, nq, k, ef),
-                   labels, distances, counts, e);
+    host_trip_sync(ix, nq, k, each_table_bytes(nq), queries, (int)kind, kFilteredBatchFailed, each_validate(filters, nq),
+                   each_launch(ix, filters, nq, k, ef, true), labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -1048,7 +1225,7 @@ try {
     if(!kind_accepted(ix, (int)kind)) { FAIL(e, kKindMismatch); return; }
     if(nq && k && (!queries || !labels || !distances)) { FAIL(e, "lantern_gpu: null buffer"); return; }
     host_trip_lane(ix, lane, nq, k, each_table_bytes(nq), queries, (int)kind, kFilteredBatchFailed, each_validate(filters, nq),
-                   each_launch(ix, filters, nq, k, ef), labels, distances, counts, e);
+                   each_launch(ix, filters, nq, k, ef, false), labels, distances, counts, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

@@ -45,7 +45,9 @@ enum ScratchSlot : int
     kScratchCallIn,
     kScratchCallOut,
     // the filtered exact path's dense route: the re-ranked (slot, distance) rows and the certificate's flags of one call, which has
-    // waited for its stream when it returns (under ix->mu): nothing queued reads the block when the next call takes it
+    // waited for its stream when it returns (under ix->mu): nothing queued reads the block when the next call takes it.  A
+    // per-query-filter call's dense groups keep their concatenated slot list, tables and gathered queries here too: everything that
+    // reads them is queued in front of that call's one wait
     kScratchDenseAnswers,
     kScratchLanes,                                     // 2 per lane: queries, answers (lantern_gpu_search_batch_lane*)
     kScratchTables = kScratchLanes + 2 * kIndexLanes,  // 1 per launch slot: a per-query filtered launch's selection list + descriptors
@@ -236,6 +238,8 @@ struct Index
     uint64_t c_filter_walk = 0, c_filter_exact = 0;
     size_t   filter_dense_min = 0;      // lantern_gpu_set_filter_dense: 0 off; m > 0: single-filter exact-path calls of nq >= m queries take the dense route
     uint64_t c_filter_dense[ 4 ] = {};  // lantern_gpu_filter_dense_stats: dense calls, their queries, certified, recomputed
+    size_t   filter_dense_each_min = 0;  // lantern_gpu_set_filter_dense_each: 0 off; m > 0: in a per-query-filter call, m exact-path queries behind one filter handle take the dense route
+    uint32_t last_each_dense[ 6 ] = {};  // lantern_gpu_last_filtered_each_dense: dense groups, their queries, certified, recomputed, rows gathered, contraction steps
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)

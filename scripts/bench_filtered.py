@@ -53,6 +53,18 @@ recomputed queries.  Then: a filter of 18 900 rows (today's walk / exact crossov
 smallest batch at which the dense route is not slower; per batch size the allowed count at which the dense route meets the walk
 (log-log interpolation over the random filters) as exact_factor = allowed^2 / (ef * n); one f16 and one i8 index over the same graph
 at 10 %.
+
+    python scripts/bench_filtered.py --each-dense
+
+measures the dense route of the PER-QUERY-FILTER call (lantern_gpu_set_filter_dense_each; DESIGN.md 4.9 "Dense exact path, per-query
+filters") and prints ONE JSON line: the rows imported under an empty graph (the exact path reads none), the path forced exact, --nq
+queries interleaved over disjoint filters -- 8 filters x 1024 queries (n / 8 rows each), 128 x 64 (n / 128 rows), 2048 x 4 (500 rows) and
+one filter of n / 10 rows behind every query -- and per case the wall-clock milliseconds of the same per-query call (device synchronised)
+with the setting at 0 and at 2, alternated within each of --reps repeats after one warming repeat (and each timed call behind one untimed
+call of its own mode), every repeat listed, with their medians; for the one-filter case also the single-filter dense route (fused) on
+the same group; the dense run's diagnostic; whether the slots equal those of the setting at 0.  Run from a checkout of an earlier
+commit, the same script times that build's call ("setting_0" only): the A/B against the parent commit is two processes, alternated by the caller; --setting-0-only makes this build's process do the
+same (no dense call between its timed calls).  scripts/merge_each_dense_ab.py assembles the processes' lines into the profile file.
 """
 import argparse
 import json
@@ -405,6 +417,76 @@ def dense_legs(a, ix, base, cluster, queries, k, ef):
     return out
 
 
+def each_dense_legs(a, base, queries, k, ef):
+    """--each-dense: the per-query-filter call with groups of queries behind shared filters, path forced exact (module docstring)"""
+    n, nq = a.n, a.nq
+    # the exact path reads no graph: the rows are imported under an empty one (no build)
+    g = {"levels": np.zeros(n, np.uint8), "nbr0": np.full((n, 8), 0xFFFFFFFF, np.uint32), "upper_off": np.full(n, 0xFFFFFFFF, np.uint32),
+         "upper_nbr": np.zeros((0, 4), np.uint32), "labels": np.arange(n, dtype=np.uint64) + 1, "entry_slot": 0, "max_level": 0}
+    ix = capi.GpuIndex("l2sq", a.dim, M=4, ef_construction=8, ef=ef, seed=42)
+    ix.import_graph(base, g)
+    ix.set_filter_policy("exact")
+    # (the same script times a build from before the setting: "setting_0" only; --setting-0-only: this build, the setting never touched)
+    has_setting = hasattr(ix, "set_filter_dense_each") and not a.setting_0_only
+    rows = ix.device_query_rows(queries)
+    dq = hip.Buffer.from_numpy(rows)
+    slot, D = hip.Buffer(nq * k * 4), hip.Buffer(nq * 8)
+    perm = np.random.default_rng(7).permutation(n)
+    cases = [("8 filters x 1024 queries", 8, n // 8), ("128 filters x 64 queries", 128, n // 128), ("2048 filters x 4 queries", 2048, min(500, n // 2048)),
+             ("1 filter x 8192 queries at 10 %", 1, n // 10)]
+    out = []
+    for name, parts, rows_each in cases:
+        filters = []
+        for p in range(parts):  # disjoint sets, as tenants are
+            allowed = np.zeros(n, dtype=bool)
+            allowed[perm[p * rows_each:(p + 1) * rows_each]] = True
+            filters.append(ix.filter_from_bitmap(allowed))
+        F = capi.GpuIndex._filter_array([filters[i % parts] for i in range(nq)], nq)  # interleaved: query i stands behind filter i mod parts
+
+        def each_call():
+            ix.search_batch_filtered_each_device(F, dq.ptr, rows.strides[0], nq, k, ef, 0, None, None, slot.ptr, None, D.ptr, None)
+            hip.synchronize()
+
+        def single_call():
+            ix.search_batch_filtered_device(filters[0], dq.ptr, rows.strides[0], nq, k, ef, 0, None, None, slot.ptr, None, D.ptr, None)
+            hip.synchronize()
+
+        modes = {"setting_0": (0, 0, each_call)}
+        if has_setting:
+            modes["setting_on"] = (2, 0, each_call)
+            if parts == 1:
+                modes["single_filter_dense"] = (0, 1, single_call)  # the fused single-filter route on the same group: the price of running unfused
+        wall, answers, diag = {m: [] for m in modes}, {}, {}
+        for rep in range(a.reps + 1):  # (repeat 0 warms every mode -- the pooled blocks are allocated there -- and is not listed)
+            for m, (each_min, single_min, call) in modes.items():
+                if has_setting:
+                    ix.set_filter_dense_each(each_min)
+                ix.set_filter_dense(single_min)
+                if rep:
+                    call()  # (untimed: every timed call follows a call of its own mode, whatever the modes alternated with are)
+                slot.upload(np.full(slot.nbytes, 0xA5, dtype=np.uint8))
+                hip.synchronize()
+                t = time.perf_counter()
+                call()
+                ms = (time.perf_counter() - t) * 1e3
+                if rep:
+                    wall[m].append(ms)
+                answers[m] = slot.download((nq, k), np.uint32)[:a.nq_exact].copy()
+                if m == "setting_on":
+                    diag = ix.last_filtered_each_dense()
+        ix.set_filter_dense(0)
+        if has_setting:
+            ix.set_filter_dense_each(0)
+        leg = {"case": name, "filters": parts, "rows_per_filter": int(filters[0].count), "queries": nq, "wall_ms": wall,
+               "median_ms": {m: float(np.median(v)) for m, v in wall.items()}, "dense_run": diag,
+               "answers_equal": {m: bool(np.array_equal(answers[m], answers["setting_0"])) for m in modes}}
+        out.append(leg)
+        for f in filters:
+            f.close()
+    ix.close()
+    return {"each_dense": out, "reps": a.reps, "has_setting": has_setting, "min_group": 2}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--n", type=int, default=1_000_000)
@@ -418,6 +500,8 @@ def main():
     p.add_argument("--seeds", default="", help="comma-separated seeds values: the legs of the seeded walk")
     p.add_argument("--compact", action="store_true", help="the legs of filtered search on a compact pq index against its expanded form")
     p.add_argument("--dense", action="store_true", help="the legs of the exact path's dense route against the walk and today's exact pass")
+    p.add_argument("--each-dense", action="store_true", help="the legs of the per-query-filter call's dense route (groups of queries behind shared filters)")
+    p.add_argument("--setting-0-only", action="store_true", help="--each-dense: time the setting at 0 only and never touch it, as a build without it does")
     p.add_argument("--pq-subvectors", type=int, default=96)
     p.add_argument("--pq-centroids", type=int, default=256)
     a = p.parse_args()
@@ -429,6 +513,11 @@ def main():
     if a.compact:
         out = {"command": "python scripts/bench_filtered.py " + " ".join(sys.argv[1:])}
         out.update(compact_legs(a, base, queries, M, efc, ef, k))
+        print(json.dumps(out))
+        return
+    if a.each_dense:
+        out = {"command": "python scripts/bench_filtered.py " + " ".join(sys.argv[1:]), "workload": f"clustered {a.n}x{a.dim} f32 l2sq k={k}, path forced exact"}
+        out.update(each_dense_legs(a, base, queries, k, ef))
         print(json.dumps(out))
         return
     ix = capi.GpuIndex("l2sq", a.dim, M=M, ef_construction=efc, ef=ef, seed=42)
