@@ -33,6 +33,12 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 #ifndef LGPU_SCREEN_LIST_PREFETCH
 #define LGPU_SCREEN_LIST_PREFETCH 1
 #endif
+// the descent of the launches that screen (SCREEN instantiations of greedy_descent) puts its upper-level rows to the screen as well: 1 = off
+// unless LANTERN_GPU_SCREEN_DESCENT=1 asks, 2 = on unless LANTERN_GPU_SCREEN_DESCENT=0 asks (search_plan.cpp: SearchArgs::screen_descent
+// carries the launch's choice; DESIGN.md 4.3 has the measurement).  Every other walk keeps the unscreened descent.
+#ifndef LGPU_SCREEN_DESCENT
+#define LGPU_SCREEN_DESCENT 2
+#endif
 #ifndef LGPU_ROW_BLOCK1
 #define LGPU_ROW_BLOCK1 4
 #endif

@@ -338,6 +338,7 @@ struct SearchEnv
     int  spec = 0, spec_waves = 0, wide_rows = -1, waves_per_cu = 0;      // their values; 0, -1, 0: absent
     bool adc_spec = false, pq_adc = false, lds_list = false;  // != 0
     int  screen_list_prefetch = -1;                                       // LANTERN_GPU_SCREEN_LIST_PREFETCH (read on every call): 0 / 1, -1: absent
+    int  screen_descent = -1;                                             // LANTERN_GPU_SCREEN_DESCENT (read on every call): 0 / 1, -1: absent
 };
 SearchEnv search_env();
 // what the shape rules read: the index's fields by their Index names, the call, the environment.  `each`: the launch is ONE CLASS of a
@@ -366,6 +367,7 @@ struct SearchPlan
     size_t      lds = 0;             // dynamic LDS of a workgroup
     uint32_t    screen_lds = 0;      // ... of which the query's int8 planes (screen_query_lds_bytes): != 0 iff the launch screens
     uint32_t    list_prefetch = 0;   // SearchArgs::list_prefetch: only ever set in a launch that screens
+    uint32_t    screen_descent = 0;  // SearchArgs::screen_descent: likewise (not among lantern_gpu_plan_search's outputs: the launch's shape does not depend on it)
     bool        took_spec = false;   // a latency-bound shape
     const char *refusal = nullptr;   // NULL: accepted; else the error text, and only `expansion` above is meaningful
 };

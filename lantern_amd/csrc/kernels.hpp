@@ -65,7 +65,8 @@ struct SearchArgs
     const uint4    *qparams;     // [caller's batch] {k, expansion, skip, 0} by position; `k`, `skip` above are unused, `ef` is the list's largest expansion
     uint32_t        k_stride;    // width of an answer row
     uint32_t        list_prefetch;  // the launches that screen: request the front's neighbour list one hop ahead (walk.hpp search_level_reg; LGPU_SCREEN_LIST_PREFETCH)
-};                               // launch's queries by phase: pop | list + visited | distances | merge | descent | whole query
+    uint32_t        screen_descent; // the launches that screen: the descent's upper-level rows go through the screen too (walk.hpp greedy_descent; LGPU_SCREEN_DESCENT)
+};                             // launch's queries by phase: pop | list + visited | distances | merge | descent | whole query
 
 // one reverse-link request produced by the insert pass: add `new_slot` to `close`'s list at `level`
 struct LinkReq

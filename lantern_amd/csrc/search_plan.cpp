@@ -19,6 +19,7 @@ SearchEnv search_env()
     // search_level_reg; identical results -- the switch exists for A/B timing and for the parity test that runs both)
     if(const char *ll = std::getenv("LANTERN_GPU_LDS_LIST")) e.lds_list = std::atoi(ll) != 0;
     if(const char *lp = std::getenv("LANTERN_GPU_SCREEN_LIST_PREFETCH")) e.screen_list_prefetch = std::atoi(lp) != 0;
+    if(const char *sd = std::getenv("LANTERN_GPU_SCREEN_DESCENT")) e.screen_descent = std::atoi(sd) != 0;
     static const int  wide_env = std::getenv("LANTERN_GPU_WIDE_ROWS") ? std::atoi(std::getenv("LANTERN_GPU_WIDE_ROWS")) : -1;
     static const int  forced = std::getenv("LANTERN_GPU_WAVES_PER_CU") ? std::atoi(std::getenv("LANTERN_GPU_WAVES_PER_CU")) : 0;
     e.wide_rows = wide_env, e.waves_per_cu = forced;
@@ -148,6 +149,8 @@ SearchPlan plan_search(const SearchPlanIn &in)
     // dependent round trips; lists of at most 64 entries (one per lane of the visit wave)
     p.list_prefetch = screened && LGPU_SCREEN_LIST_PREFETCH != 0 && in.M0 <= 64 &&
                       (env.screen_list_prefetch >= 0 ? env.screen_list_prefetch != 0 : LGPU_SCREEN_LIST_PREFETCH >= 2);
+    // the descent's rows through the screen as well (walk.hpp greedy_descent): a choice of the launches that screen, no part of their shape
+    p.screen_descent = screened && (env.screen_descent >= 0 ? env.screen_descent != 0 : LGPU_SCREEN_DESCENT >= 2);
     if(p.lds > 160 * 1024) { p.refusal = "lantern_gpu: ef/k exceed the 160 KiB LDS budget of the search kernel"; return p; }
     p.path = pqd ? kSearchPqd : spec == 0 ? kSearchClassic : spec == 1 ? kSearchSpec1 : kSearchSpec2;
     p.spec = spec, p.took_spec = spec != 0;
@@ -184,7 +187,7 @@ static bool search_launch(Index *ix, const SearchPlan &p, const uint4 *d_queries
     a.done = done, a.done_flags = done_flags;
     a.lds_list = p.lds_list, a.wide_rows = p.wide_rows;
     a.spec = p.spec, a.spec_prefetch = p.spec_prefetch, a.spec_cache = p.spec_cache;
-    a.list_prefetch = p.list_prefetch;
+    a.list_prefetch = p.list_prefetch, a.screen_descent = p.screen_descent;
     hipError_t e = hipSuccess;
     if(!p.screen_lds) a.view.screen = nullptr, a.view.screen_meta = nullptr, a.view.screen_chunks = 0;  // no planes' block: the launch does not screen
     if(adc || pqd) a.view.vec = (const uint4 *)ix->d_codes16;

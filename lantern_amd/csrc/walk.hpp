@@ -29,7 +29,7 @@ enum { S_POS = 0, S_NNEW, S_CNT, S_ANY, S_BAD, S_CUR, S_CURD, S_CHANGED, S_VISCN
        S_FRONT = 16, S_WORST = 20,  // two u64 each (by hop parity): search_level_reg's hand-off from the list wave to the visit wave
        S_MASK = 24,                 // two u64 (by hop parity): walk_spec.hpp's "which neighbours of the hop were new"
        S_SCALARS = 28,
-       // search_level_reg's int8 screen, in slots that walk leaves alone: the screened hop's survivor count, the walk's rejected rows,
+       // the int8 screen of search_level_reg and of the screened greedy_descent, in slots that walk leaves alone: the screened hop's survivor count, the walk's rejected rows,
        // and (set by k_search before the walk) two u64: View::screen and View::screen_meta -- in LDS rather than in scalar registers,
        // which the hop loop has none of to spare
        S_NSURV = S_ANY0, S_NREJ = S_ANY1, S_SCREEN = S_MASK,
@@ -42,7 +42,7 @@ struct WalkLds
     uint64_t *keys;     // current list   (ef_cap)
     uint64_t *keys2;    // merge target   (ef_cap)
     uint64_t *newkeys;  // keys of this hop's new neighbours (cap_max)
-    uint64_t *sorted;   // the same, sorted                  (cap_max); search_level_reg: the screened hop's survivors (u32)
+    uint64_t *sorted;   // the same, sorted                  (cap_max); search_level_reg, greedy_descent: the screened hop's / step's survivors (u32)
     uint32_t *newids;   // unvisited neighbour slots         (cap_max)
     int      *scal;     // S_* scalars
     uint32_t *vis;      // visited hash set (vis_slots entries, any multiple of 4; 0 = the HBM bitmap only)
@@ -300,12 +300,27 @@ template <int L> __device__ __forceinline__ int quad_lower_bound(const uint64_t 
 
 // ---- search_for_one_: greedy descent over levels (begin, end] ---------------------------------------
 // Returns the closest slot (same value in every thread).  D counts distance evaluations.
-template <int METRIC, int G, bool PROF = false>
-__device__ uint32_t greedy_descent(const View &v, WalkLds &s, uint32_t start, int begin_level, int end_level, uint32_t &D)
+//
+// SCREEN (k_search's screened instantiations: search_kernel.hpp), in a launch that carved the planes' block (s.scal[S_SCREEN] set) and
+// asks for it (screen_descent = SearchArgs::screen_descent): a step's listed rows go through the int8 screen of the level-0 hops
+// (hop_distances_screened below, as it stands) at radius = the best distance when the step starts, and only the rows it cannot reject are
+// read in f32 -- all of a step's survivors requested before the first is consumed (hop_distances: two rows per group), by the chain
+// of group_dist_n, same bits.  A rejected row's f32 distance is strictly above that radius; the scan takes a row only if it is strictly
+// below the running best, which is never above the radius: the rejected row could not have been taken, and nothing else changes.  D
+// counts every listed row; the rejected ones go to s.scal[S_NREJ] with the hops' (lantern_gpu_search_screen_stats).
+// LDS, screened step: the distances are the 64-bit keys of the hop (s.newkeys[i] = make_key(d, id); ~0 for a rejected row, whose
+// key_dist is a NaN: below nothing) instead of floats in the same words; the survivors' positions are in s.sorted; S_NSURV / S_NREJ
+// (= S_ANY0 / S_ANY1, which only the LDS-list walk uses) and S_SCREEN (= S_MASK, walk_spec.hpp's) share no word with S_NNEW, S_CUR,
+// S_CURD, S_CHANGED.
+template <int METRIC, int G> __device__ __forceinline__ void descent_distances_screened(const View &v, WalkLds &s, int nn, float qn2);  // (behind hop_distances_screened)
+template <int METRIC, int G, bool PROF = false, bool SCREEN = false>
+__device__ uint32_t greedy_descent(const View &v, WalkLds &s, uint32_t start, int begin_level, int end_level, uint32_t &D, uint32_t screen_descent = 0)
 {
+    static_assert(!SCREEN || ((METRIC == M_L2SQ || METRIC == M_COS) && !PROF), "the screen serves the f32 l2sq and cosine walks");
     const int tid = threadIdx.x, T = blockDim.x, g = tid / G, gl = tid % G, NG = T / G;
     float *newd = (float *)s.newkeys;  // reuse: one f32 per neighbour
     const float qn2 = __int_as_float(s.scal[ S_QN2 ]);
+    const bool  screen_on = SCREEN && screen_descent != 0 && ((const uint64_t *)&s.scal[ S_SCREEN ])[ 0 ] != 0;
     if(g == 0) {
         float d = group_dist_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, start), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, start));
         if(gl == G - 1) { s.scal[ S_CUR ] = (int)start; s.scal[ S_CURD ] = __float_as_int(d); mark_touched<PROF>(s, start); }
@@ -328,10 +343,16 @@ __device__ uint32_t greedy_descent(const View &v, WalkLds &s, uint32_t start, in
                     if(i < cap) s.newids[ i ] = nb;
                     count += (int)__popcll(__ballot(nb != EMPTY));
                 }
-                if(tid == 0) s.scal[ S_NNEW ] = count;
+                if(tid == 0) {
+                    s.scal[ S_NNEW ] = count;
+                    if constexpr(SCREEN) s.scal[ S_NSURV ] = 0;  // (the previous step's survivor count was read two barriers ago)
+                }
             }
             __syncthreads();
             const int nn = s.scal[ S_NNEW ];
+            if(screen_on) {
+                if constexpr(SCREEN) descent_distances_screened<METRIC, G>(v, s, nn, qn2);
+            } else
             for(int i = g; i < nn; i += NG) {
                 const uint32_t id = s.newids[ i ];
                 float d = group_dist_n<METRIC, G>(walk_query<METRIC>(s), row_of_m<METRIC>(v, id), (int)v.chunks, gl, qn2, row_norm<METRIC>(v, id));
@@ -344,8 +365,10 @@ __device__ uint32_t greedy_descent(const View &v, WalkLds &s, uint32_t start, in
                 float    best = __int_as_float(s.scal[ S_CURD ]);
                 uint32_t bslot = cur;
                 int      changed = 0;
-                for(int i = 0; i < nn; ++i)
-                    if(newd[ i ] < best) { best = newd[ i ]; bslot = s.newids[ i ]; changed = 1; }
+                for(int i = 0; i < nn; ++i) {
+                    const float d = screen_on ? key_dist(s.newkeys[ i ]) : newd[ i ];
+                    if(d < best) { best = d; bslot = s.newids[ i ]; changed = 1; }
+                }
                 s.scal[ S_CUR ] = (int)bslot;
                 s.scal[ S_CURD ] = __float_as_int(best);
                 s.scal[ S_CHANGED ] = changed;
@@ -663,6 +686,16 @@ __device__ __forceinline__ int hop_distances_screened(const View &v, WalkLds &s,
         if constexpr(TALLY) s.scal[ S_NTEST ] += nnew;
     }
     return ns;
+}
+
+// A screened step of greedy_descent: the keys of the nn listed rows in s.newids -> s.newkeys, ~0 for the rows the screen rejects at
+// radius = the best distance so far (S_CURD; the slot bits of the radius are not read), the exact key for every other row -- the
+// survivors' rows all requested before the first is consumed.  S_NSURV is zero on entry.
+template <int METRIC, int G> __device__ __forceinline__ void descent_distances_screened(const View &v, WalkLds &s, int nn, float qn2)
+{
+    const uint64_t radius = make_key(__int_as_float(s.scal[ S_CURD ]), 0u);
+    const int      ns = hop_distances_screened<METRIC, G, 2>(v, s, nn, radius, qn2);
+    hop_distances<METRIC, G, 2, false, true>(v, s, ns, qn2, ~0ull, nullptr, (const uint32_t *)s.sorted);
 }
 
 template <int METRIC, int G, bool PROF = false, int ROWS = 2>
