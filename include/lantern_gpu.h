@@ -355,7 +355,8 @@ LANTERN_GPU_EXPORT size_t lantern_gpu_last_search_cells(uint32_t *cells, size_t 
  * NULL entry of the per-query form has no slot list, runs the walk of 2 and still is, bit for bit.  Deleted rows carry label 0 (hnsw.h:40); the reference skips them only after a search has returned them (scan.c:296-300)
  * and gives up streaming after 1000 rows (scan.c:249-252), so a selective predicate applied after the index scan returns fewer
  * than LIMIT rows -- a filter makes the walk itself look for allowed rows.
- * A filter is refused (an error naming both sizes) on another index, or once the index has grown: it is never extended. */
+ * A filter is refused (an error naming both sizes) on another index, or once the index has grown: it is never extended implicitly:
+ * lantern_gpu_filter_extend. */
 typedef struct lantern_gpu_filter lantern_gpu_filter_t;
 #define LANTERN_GPU_FILTER_SKIP_DELETED 1u /* also disallow every slot whose label is 0 */
 /* allowed iff the slot's label is in labels[0..n) (any order, duplicates allowed): sorted and searched on the device -- the form a
@@ -368,6 +369,31 @@ LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_from_slot_bitmap(use
 LANTERN_GPU_EXPORT size_t lantern_gpu_filter_count(const lantern_gpu_filter_t *, usearch_error_t *); /* allowed slots */
 LANTERN_GPU_EXPORT size_t lantern_gpu_filter_resident_bytes(const lantern_gpu_filter_t *, usearch_error_t *); /* device memory it holds */
 LANTERN_GPU_EXPORT void   lantern_gpu_filter_free(lantern_gpu_filter_t *);
+/* A FILTER'S LIFE CYCLE (DESIGN.md 4.9 "Filter life cycle").  Filters are immutable: each call below returns a NEW handle and only
+ * reads its operands, which stay valid handles -- stale for searches as before -- until the caller frees them.  Nothing extends a
+ * filter behind the caller's back: a search through a stale filter is refused as ever.  The argument checks (flags, op, NULLs, the
+ * filter handles) are made before the device is used. */
+#define LANTERN_GPU_FILTER_EXTEND_ALL 2u   /* extend only: every new slot is allowed (labels must be NULL, n 0) */
+/* The filter `f` brought to the index's size after the flush every search performs: bits [0, f->n) as in f (a snapshot: rows
+ * deleted since stay as f has them); a slot s in [f->n, size) is allowed iff its label is in labels[0..n) -- or, under EXTEND_ALL,
+ * always -- and, under SKIP_DELETED, its label is not 0.  f->n == size gives an equal copy.  Refused: another index's filter, a
+ * filter from before a compaction (the message a search gives: its slots name other rows now, and it is not remapped), unknown
+ * flags, labels == NULL with n > 0. */
+LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_extend(usearch_index_t, const lantern_gpu_filter_t *f, const usearch_label_t *labels,
+                                                                   size_t n, uint32_t flags, usearch_error_t *);
+#define LANTERN_GPU_FILTER_AND 0
+#define LANTERN_GPU_FILTER_OR 1
+#define LANTERN_GPU_FILTER_ANDNOT 2        /* a and not b */
+/* Both operands must pass the check a search applies to a filter today (this index, its current size and epoch). */
+LANTERN_GPU_EXPORT lantern_gpu_filter_t *lantern_gpu_filter_combine(usearch_index_t, const lantern_gpu_filter_t *a, const lantern_gpu_filter_t *b,
+                                                                    int op, usearch_error_t *);
+/* Diagnostics: the bitmap (n_words >= ceil(f->n / 32), else refused; words past the filter's own are written as zero) and / or the
+ * first min(cap, count) allowed slots in list order; either pointer may be NULL.  Needs only a live handle: a stale filter can still
+ * be read.  Returns the count. */
+/* the index's size when the filter was built: its bitmap spans ceil(rows / 32) words (a stale filter answers too) */
+LANTERN_GPU_EXPORT size_t lantern_gpu_filter_rows(const lantern_gpu_filter_t *f, usearch_error_t *);
+LANTERN_GPU_EXPORT size_t lantern_gpu_filter_export(const lantern_gpu_filter_t *f, uint32_t *words, size_t n_words, uint32_t *slots, size_t cap,
+                                                    usearch_error_t *);
 /* path: 0 auto, 1 walk, 2 exact.  cand_cap = C (0: max(4 expansion, 256), capped by LDS; below expansion it is raised to it).
  * Auto takes the exact path when allowed^2 <= exact_factor * ef * n, ef the caller's or else the index's: a walk under a filter of
  * selectivity s evaluates about D / s rows, the exact path `allowed`.  The rule does not depend on k or skip, so it is stable
@@ -1177,8 +1203,9 @@ LANTERN_GPU_EXPORT lantern_scan_server_t *lantern_scan_server_start_filtered_fn(
                                                                                 lantern_scan_filter_free_fn, lantern_batch_search_each_fn,
                                                                                 void *ctx, size_t vec_bytes, const char *host, int port,
                                                                                 size_t max_batch, unsigned max_wait_us, usearch_error_t *);
-/* filters set (clears not counted), requests searched through a filter, per-query-filter calls made, the largest number of DISTINCT
- * filters one such call carried, device bytes of the filters resident now */
+/* filters set (clears not counted; an extension -- lantern_scan_client_extend_filter -- is not counted either: it rebuilds a filter
+ * that was counted when it was set, and shows in resident_bytes only), requests searched through a filter, per-query-filter calls
+ * made, the largest number of DISTINCT filters one such call carried, device bytes of the filters resident now */
 /* MIXED BATCHES THROUGH AN INJECTED BACK END (tests of the dispatcher; a host that shards queries over several GPUs): the batch
  * search with (k, ef, skip) per query -- answer rows k_stride wide, as lantern_gpu_search_batch_params.  The unfiltered requests of a
  * batch that carry more than one distinct (k, ef) go to it in one call; a batch with one shared (k, ef) goes to the plain function. */
@@ -1228,6 +1255,14 @@ LANTERN_GPU_EXPORT size_t lantern_scan_client_search_next(lantern_scan_client_t 
 LANTERN_GPU_EXPORT size_t lantern_scan_client_set_filter(lantern_scan_client_t *, const usearch_label_t *labels, size_t n, uint32_t flags,
                                                          usearch_error_t *);
 LANTERN_GPU_EXPORT void   lantern_scan_client_clear_filter(lantern_scan_client_t *, usearch_error_t *);
+/* Extend this connection's filter to the served index's present size (lantern_gpu_filter_extend on the server: the "LSRX" message):
+ * the rows it has stay as they are, a row added since is allowed iff its label is in labels[0 .. n) -- or, under
+ * LANTERN_GPU_FILTER_EXTEND_ALL (n must be 0), always; LANTERN_GPU_FILTER_SKIP_DELETED as above.  Returns the allowed rows.  Unlike
+ * set_filter it KEEPS the connection's current scan: a continuation goes on where it stood.  On an error -- the connection has no
+ * filter, the index was compacted since -- nothing changes.  Only lantern_scan_server_start serves the message: the injected back ends
+ * of the *_fn forms have no extension hook and answer it with an error frame (the connection survives, its filter stays in force). */
+LANTERN_GPU_EXPORT size_t lantern_scan_client_extend_filter(lantern_scan_client_t *, const usearch_label_t *labels, size_t n, uint32_t flags,
+                                                            usearch_error_t *);
 LANTERN_GPU_EXPORT void   lantern_scan_client_close(lantern_scan_client_t *);
 
 /* ------------------------------------------------------------------------------------------ */

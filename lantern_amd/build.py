@@ -18,7 +18,7 @@ OUT_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 LIB = os.path.join(OUT_DIR, "liblantern_gpu.so")
 
-SOURCES = ["search_kernel.hip", "search_spec_kernel.hip", "search_adc_kernel.hip", "search_filtered_kernel.hip", "search_filtered_pq_kernel.hip", "search_each_kernel.hip", "search_each_spec_kernel.hip", "filter.hip", "insert_kernel.hip", "insert_spec_kernel.hip", "kernels.hip", "screen_probe_kernel.hip", "bruteforce.hip", "dense_native.hip", "grouping.hip", "unlink.hip", "compact.hip", "index.cpp", "dense.cpp", "insert_batch.cpp", "search_plan.cpp", "comm.cpp", "usearch_file.cpp", "scan_shim.cpp", "index_server.cpp", "scan_server.cpp", "mirror_cache.cpp", "node_tape.cpp"]
+SOURCES = ["search_kernel.hip", "search_spec_kernel.hip", "search_adc_kernel.hip", "search_filtered_kernel.hip", "search_filtered_pq_kernel.hip", "search_each_kernel.hip", "search_each_spec_kernel.hip", "filter.hip", "filter_ops.hip", "insert_kernel.hip", "insert_spec_kernel.hip", "kernels.hip", "screen_probe_kernel.hip", "bruteforce.hip", "dense_native.hip", "grouping.hip", "unlink.hip", "compact.hip", "index.cpp", "dense.cpp", "insert_batch.cpp", "search_plan.cpp", "comm.cpp", "usearch_file.cpp", "scan_shim.cpp", "index_server.cpp", "scan_server.cpp", "mirror_cache.cpp", "node_tape.cpp"]
 # every header under csrc/ is a dependency of every object (globbed, so a new header cannot be forgotten)
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + ["../../include/lantern_gpu.h"]
 # -ffp-contract=off: every fma in the kernels is explicit, so the reduction tree is exactly the

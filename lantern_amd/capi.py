@@ -124,6 +124,8 @@ EXPORTS = [
     "lantern_gpu_cursor_search_filtered", "lantern_scan_set_filter",
     "lantern_gpu_filter_resident_bytes", "lantern_scan_server_start_filtered_fn", "lantern_scan_server_filter_stats", "lantern_scan_client_set_filter",
     "lantern_scan_client_clear_filter",
+    # ... a filter's life cycle (lantern_gpu.h "A FILTER'S LIFE CYCLE")
+    "lantern_gpu_filter_extend", "lantern_gpu_filter_combine", "lantern_gpu_filter_export", "lantern_gpu_filter_rows", "lantern_scan_client_extend_filter",
     "lantern_gpu_search_batch_filtered_each", "lantern_gpu_search_batch_filtered_each_device", "lantern_gpu_search_batch_filtered_each_lane", "lantern_gpu_last_filtered_each",
     "lantern_gpu_set_filter_seeds", "lantern_gpu_last_filtered_seeds", "lantern_gpu_set_filter_compact", "lantern_gpu_filter_compact", "lantern_gpu_plan_filtered_compact",
     # ... the exact path's dense route (lantern_gpu.h "THE EXACT PATH'S DENSE ROUTE")
@@ -159,6 +161,8 @@ def query_params(params) -> np.ndarray:
 
 
 FILTER_SKIP_DELETED = 1  # LANTERN_GPU_FILTER_SKIP_DELETED
+FILTER_EXTEND_ALL = 2  # LANTERN_GPU_FILTER_EXTEND_ALL
+FILTER_OPS = {"and": 0, "or": 1, "andnot": 2}  # LANTERN_GPU_FILTER_AND / _OR / _ANDNOT
 FILTER_PATHS = {"auto": 0, "walk": 1, "exact": 2}
 
 # int fn(void *ctx, const void *queries, size_t nq, size_t vec_bytes, size_t k, size_t ef, u64 *labels, f32 *dists, u32 *counts, const char **err)
@@ -387,6 +391,11 @@ def lib() -> C.CDLL:
         "lantern_scan_server_filter_stats": (None, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "lantern_scan_client_set_filter": (sz, [vp, vp, sz, u32, err]),
         "lantern_scan_client_clear_filter": (None, [vp, err]),
+        "lantern_scan_client_extend_filter": (sz, [vp, vp, sz, u32, err]),
+        "lantern_gpu_filter_extend": (vp, [vp, vp, vp, sz, u32, err]),
+        "lantern_gpu_filter_combine": (vp, [vp, vp, vp, i32, err]),
+        "lantern_gpu_filter_export": (sz, [vp, vp, sz, vp, sz, err]),
+        "lantern_gpu_filter_rows": (sz, [vp, err]),
         "lantern_gpu_remove_labels": (None, [vp, vp, sz, C.POINTER(u64), err]),
         "lantern_gpu_deleted_count": (sz, [vp, err]),
         "lantern_gpu_unlink_deleted": (None, [vp, C.POINTER(UnlinkStats), err]),
@@ -1651,6 +1660,47 @@ class Filter:
     def count(self) -> int:
         return int(_call("lantern_gpu_filter_count", self.h))
 
+    @property
+    def resident_bytes(self) -> int:
+        return int(_call("lantern_gpu_filter_resident_bytes", self.h))
+
+    @property
+    def rows(self) -> int:
+        """the index's size when the filter was built"""
+        return int(_call("lantern_gpu_filter_rows", self.h))
+
+    def extend(self, labels=None, all_new=False, skip_deleted=False) -> "Filter":
+        """lantern_gpu_filter_extend: a NEW filter of the index's present size -- this one's bits, and the rows added since whose
+        label is in `labels` (all_new: every one of them).  This filter is only read."""
+        L = np.ascontiguousarray([] if labels is None else labels, dtype=np.uint64).ravel()
+        flags = (FILTER_EXTEND_ALL if all_new else 0) | (FILTER_SKIP_DELETED if skip_deleted else 0)
+        h = _call("lantern_gpu_filter_extend", self.index.h, self.h, _ptr(L) if L.size else None, L.size, flags)
+        return Filter(self.index, h)
+
+    def combine(self, other: "Filter", op) -> "Filter":
+        """lantern_gpu_filter_combine: a NEW filter, this one "and" / "or" / "andnot" (or 0 / 1 / 2) `other`; also `&`, `|`, `-`."""
+        h = _call("lantern_gpu_filter_combine", self.index.h, self.h, other.h, FILTER_OPS.get(op, op))
+        return Filter(self.index, h)
+
+    def __and__(self, other):
+        return self.combine(other, "and")
+
+    def __or__(self, other):
+        return self.combine(other, "or")
+
+    def __sub__(self, other):
+        return self.combine(other, "andnot")
+
+    def export(self):
+        """lantern_gpu_filter_export: (bitmap_words, slots) -- the bitmap over the filter's rows, rounded up to the device's multiple
+        of 4 words (those past ceil(rows / 32) are zero), and the allowed slots in list order.  A stale filter can still be read."""
+        count = self.count
+        words = np.zeros(((max(self.rows, 1) + 31) // 32 + 3) // 4 * 4, dtype=np.uint32)
+        slots = np.zeros(count, dtype=np.uint32)
+        got = _call("lantern_gpu_filter_export", self.h, _ptr(words), words.size, _ptr(slots) if count else None, count)
+        assert int(got) == count
+        return words, slots
+
     def close(self):
         if getattr(self, "h", None):
             lib().lantern_gpu_filter_free(self.h)
@@ -1907,6 +1957,13 @@ class ScanClient:
         """This connection's filter: the rows whose label is in `labels` (an empty list allows nothing).  Returns the allowed rows."""
         L = np.ascontiguousarray(labels, dtype=np.uint64).ravel()
         return int(_call("lantern_scan_client_set_filter", self.c, _ptr(L) if L.size else None, L.size, FILTER_SKIP_DELETED if skip_deleted else 0))
+
+    def extend_filter(self, labels=None, all_new=False, skip_deleted=False) -> int:
+        """The connection's filter brought to the served index's present size: a row added since is allowed iff its label is in
+        `labels` (all_new: always).  The connection's scan goes on.  Returns the allowed rows."""
+        L = np.ascontiguousarray([] if labels is None else labels, dtype=np.uint64).ravel()
+        flags = (FILTER_EXTEND_ALL if all_new else 0) | (FILTER_SKIP_DELETED if skip_deleted else 0)
+        return int(_call("lantern_scan_client_extend_filter", self.c, _ptr(L) if L.size else None, L.size, flags))
 
     def clear_filter(self):
         _call("lantern_scan_client_clear_filter", self.c)

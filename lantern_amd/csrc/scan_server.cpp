@@ -19,6 +19,13 @@
 //             in the list (lantern_gpu_filter_from_labels).  flags: bit 0 = LANTERN_GPU_FILTER_SKIP_DELETED, bit 31 = CLEAR (count must
 //             be 0: the connection is unfiltered again).  An empty list without CLEAR is a valid filter that allows nothing.
 //   server -> u32 "LSRP", u32 status 0, u32 0, u64 allowed rows -- or the error frame above (status != 0: u32 length, message)
+//   client -> u32 0x5852534C ("LSRX"), u32 flags, u64 count, count x u64 labels: EXTEND THE CONNECTION'S FILTER to the served index's
+//             present size (lantern_gpu_filter_extend): the rows the filter has stay as they are; a row added since is allowed iff its
+//             label is in the list.  flags: bit 0 = LANTERN_GPU_FILTER_SKIP_DELETED, bit 1 = LANTERN_GPU_FILTER_EXTEND_ALL (every new
+//             row is allowed; count must be 0).  The layout, the limits and the reply are "LSRF"'s.  Unlike "LSRF", an "LSRX" answered
+//             with status 0 KEEPS the connection's hand-out history: the scan goes on, and the rows already handed out are still
+//             allowed.  A connection without a filter gets an error frame, and so does every connection of an injected back end
+//             (the *_fn forms have no extension hook; only lantern_scan_server_start serves the message); the connection survives.
 // The filter belongs to the CONNECTION, like the continuation state: every later "LSRQ" / "LSRC" of the connection is searched
 // through it, until it is replaced, cleared or the connection closes (the server then releases it).  A filter message that is
 // answered with status 0 ends the connection's current scan (its hand-out history is dropped); one that is answered with an error
@@ -28,7 +35,7 @@
 // error frame after its payload has been read, and the connection survives.  A back end without filters
 // (lantern_scan_server_start_fn) answers every filter message with an error frame; the connection survives.  A filter gone stale
 // (the served index grew) makes the connection's searches come back as error frames carrying the library's message until the
-// backend sends its filter again.
+// backend sends its filter again -- or extends it ("LSRX"), which sends only the new rows' labels.
 // Filters are built and released on a thread of their own (device allocation and a sort: milliseconds), never on an I/O thread;
 // a large message is read in slices between which the I/O thread serves its other connections.
 // A connection carries one request at a time (a backend runs one scan step at a time) and stays open across requests.
@@ -83,7 +90,7 @@
 
 namespace {
 
-constexpr uint32_t REQ_MAGIC = 0x5152534Cu, CONT_MAGIC = 0x4352534Cu, REP_MAGIC = 0x5052534Cu, FILTER_MAGIC = 0x4652534Cu;
+constexpr uint32_t REQ_MAGIC = 0x5152534Cu, CONT_MAGIC = 0x4352534Cu, REP_MAGIC = 0x5052534Cu, FILTER_MAGIC = 0x4652534Cu, EXTEND_MAGIC = 0x5852534Cu;
 constexpr uint32_t FILTER_CLEAR = 0x80000000u;            // flags of a filter message: bit 31 (bit 0: LANTERN_GPU_FILTER_SKIP_DELETED)
 constexpr uint64_t kMaxFilterLabels = (uint64_t)1 << 24;  // labels per filter message (128 MiB of payload)
 constexpr size_t   kFilterSlice = (size_t)1 << 20;        // bytes of a filter message one visit of an I/O thread reads
@@ -156,6 +163,7 @@ struct Conn
     void                *filter = nullptr;
     uint64_t             filter_bytes = 0;
     uint32_t             fflags = 0;  // the outstanding filter message: its flags (its labels are in `vec`)
+    bool                 fextend = false;  // ... and whether it is an "LSRX": the filter extended, not replaced
     uint64_t             t_read = 0, t_closed = 0;  // ns: its request was read / its batch closed (lantern_scan_server_timing)
     // this connection's scan: labels handed out since its last fresh request, and how many label-0 rows among them
     std::unordered_set<uint64_t> seen;
@@ -196,6 +204,10 @@ struct lantern_scan_server
     lantern_scan_filter_make_fn  f_make = nullptr;
     lantern_scan_filter_free_fn  f_free = nullptr;
     lantern_batch_search_each_fn f_each = nullptr;
+    // "LSRX": the back end's filter brought to its index's present size, as a NEW filter (make's outputs).  The device index alone has it
+    typedef void *(*filter_extend_fn)(void *ctx, void *filter, const uint64_t *labels, size_t n, uint32_t flags, uint64_t *allowed, uint64_t *resident_bytes,
+                                      const char **err);
+    filter_extend_fn f_extend = nullptr;
     // mixed batches: the back end's search with (k, ef, skip) per query (NULL: a back end without one -- a batch then goes out as one
     // call per distinct (k, ef)).  The device index has it under LANTERN_SCAN_MIXED=1.
     lantern_batch_search_params_fn f_params = nullptr;
@@ -254,6 +266,16 @@ void *default_filter_make(void *ctx, const uint64_t *labels, size_t n, uint32_t 
     usearch_error_t       e = nullptr;
     lantern_gpu_filter_t *f = lantern_gpu_filter_from_labels(s->index, labels, n, flags, &e);
     if(!f) { *err = e ? e : "lantern_scan_server: cannot build the filter"; return nullptr; }
+    *allowed = lantern_gpu_filter_count(f, &e);
+    *bytes = lantern_gpu_filter_resident_bytes(f, &e);
+    return f;
+}
+void *default_filter_extend(void *ctx, void *filter, const uint64_t *labels, size_t n, uint32_t flags, uint64_t *allowed, uint64_t *bytes, const char **err)
+{
+    lantern_scan_server  *s = (lantern_scan_server *)ctx;
+    usearch_error_t       e = nullptr;
+    lantern_gpu_filter_t *f = lantern_gpu_filter_extend(s->index, (const lantern_gpu_filter_t *)filter, labels, n, flags, &e);
+    if(!f) { *err = e ? e : "lantern_scan_server: cannot extend the filter"; return nullptr; }
     *allowed = lantern_gpu_filter_count(f, &e);
     *bytes = lantern_gpu_filter_resident_bytes(f, &e);
     return f;
@@ -348,7 +370,7 @@ int read_request(lantern_scan_server *s, Conn *c)
         if(c->in.size() >= 16) {
             uint32_t magic, nbytes;
             std::memcpy(&magic, c->in.data(), 4);
-            is_filter = magic == FILTER_MAGIC;
+            is_filter = magic == FILTER_MAGIC || magic == EXTEND_MAGIC;
             if(is_filter) {
                 uint64_t count;
                 std::memcpy(&count, c->in.data() + 8, 8);
@@ -374,14 +396,26 @@ int read_request(lantern_scan_server *s, Conn *c)
         else if(errno != EINTR) return -1;
     }
     if(is_filter) {
-        uint32_t flags;
+        uint32_t magic, flags;
         uint64_t count;
+        std::memcpy(&magic, c->in.data(), 4);
         std::memcpy(&flags, c->in.data() + 4, 4);
         std::memcpy(&count, c->in.data() + 8, 8);
         const size_t len = 16 + (size_t)count * 8;
         c->vec.assign(c->in.begin() + 16, c->in.begin() + (ptrdiff_t)len);
         c->in.erase(c->in.begin(), c->in.begin() + (ptrdiff_t)len);
         c->in.shrink_to_fit();
+        if(magic == EXTEND_MAGIC) {
+            constexpr uint32_t known = (uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED | (uint32_t)LANTERN_GPU_FILTER_EXTEND_ALL;
+            if((flags & ~known) || ((flags & LANTERN_GPU_FILTER_EXTEND_ALL) && count))
+                return reply_error(c->fd, "lantern_scan_server: bad extension flags (bit 0: skip deleted rows; bit 1: every new row, with no labels)") ? 0 : -1;
+            if(!s->f_extend)
+                return reply_error(c->fd, "lantern_scan_server: this back end cannot extend a filter (only lantern_scan_server_start serves \"LSRX\")") ? 0 : -1;
+            c->fflags = flags;
+            c->fextend = true;
+            return 2;
+        }
+        c->fextend = false;
         if((flags & ~(FILTER_CLEAR | (uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED)) || ((flags & FILTER_CLEAR) && count))
             return reply_error(c->fd, "lantern_scan_server: bad filter flags (bit 0: skip deleted rows; bit 31: clear, with no labels)") ? 0 : -1;
         if(!s->f_make)
@@ -535,9 +569,11 @@ void filter_loop(lantern_scan_server *s)
         d.c = c;
         void    *made = nullptr;
         uint64_t allowed = 0, bytes = 0;
-        if(!(c->fflags & FILTER_CLEAR)) {
+        if(c->fextend && !c->filter) d.error = "lantern_scan_server: the connection has no filter to extend (send it first: \"LSRF\")";
+        else if(!(c->fflags & FILTER_CLEAR)) {
             const char *err = nullptr;
-            made = s->f_make(s->fn_ctx, (const uint64_t *)c->vec.data(), c->vec.size() / 8, c->fflags & ~FILTER_CLEAR, &allowed, &bytes, &err);
+            made = c->fextend ? s->f_extend(s->fn_ctx, c->filter, (const uint64_t *)c->vec.data(), c->vec.size() / 8, c->fflags, &allowed, &bytes, &err)
+                              : s->f_make(s->fn_ctx, (const uint64_t *)c->vec.data(), c->vec.size() / 8, c->fflags & ~FILTER_CLEAR, &allowed, &bytes, &err);
             if(!made) d.error = err ? err : "lantern_scan_server: cannot build the filter";
             else if(s->filter_resident.load() - c->filter_bytes + bytes > s->filter_budget) {
                 s->f_free(s->fn_ctx, made);
@@ -555,9 +591,11 @@ void filter_loop(lantern_scan_server *s)
             c->filter = made;
             c->filter_bytes = made ? bytes : 0;
             s->filter_resident += c->filter_bytes;
-            if(made) s->n_filters_set += 1;
-            c->seen.clear();  // the connection's scan is over
-            c->seen_zero = 0;
+            if(made && !c->fextend) s->n_filters_set += 1;
+            if(!c->fextend) {  // the connection's scan is over -- an extension keeps it: the rows handed out are still allowed
+                c->seen.clear();
+                c->seen_zero = 0;
+            }
             const uint32_t head[ 3 ] = { REP_MAGIC, 0u, 0u };
             d.raw.resize(20);
             std::memcpy(d.raw.data(), head, 12);
@@ -936,6 +974,7 @@ try {
     s->f_make = default_filter_make;
     s->f_free = default_filter_free;
     s->f_each = default_search_each;
+    s->f_extend = default_filter_extend;
     // mixed batches in one call: LANTERN_SCAN_MIXED=1 (=0: one call per distinct (k, ef), as before).  The switch is the A/B lever of
     // scripts/scan_mixed_ab.py and defaults to OFF until that A/B has been taken (the rule that decides it).
     constexpr bool kMixedByDefault = false;
@@ -1193,8 +1232,9 @@ try {
 }
 LANTERN_ABI_CATCH(e)
 
-// the connection's filter: the rows whose label is in labels[0 .. n) (n = 0: a filter that allows nothing); returns the allowed rows
-static size_t client_filter(lantern_scan_client_t *c, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e)
+// the connection's filter: the rows whose label is in labels[0 .. n) (n = 0: a filter that allows nothing); returns the allowed rows.
+// magic: FILTER_MAGIC sets it, EXTEND_MAGIC extends the one the connection has by the new rows among the labels
+static size_t client_filter(lantern_scan_client_t *c, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e, uint32_t magic = FILTER_MAGIC)
 {
     if(e) *e = nullptr;
     // the checks of the arguments alone come first: a message that is refused whatever the connection's state is refused without the
@@ -1209,7 +1249,7 @@ static size_t client_filter(lantern_scan_client_t *c, const usearch_label_t *lab
         if(e) *e = c->err.c_str();
         return (size_t)0;
     };
-    const uint32_t head[ 2 ] = { FILTER_MAGIC, flags };
+    const uint32_t head[ 2 ] = { magic, flags };
     const uint64_t count = n;
     if(!write_all(c->fd, head, 8) || !write_all(c->fd, &count, 8) || (n && !write_all(c->fd, labels, n * 8))) return fail("lantern_gpu: the scan server went away");
     uint32_t rep[ 3 ];
@@ -1230,6 +1270,20 @@ size_t lantern_scan_client_set_filter(lantern_scan_client_t *c, const usearch_la
 try {
     if(flags & ~(uint32_t)LANTERN_GPU_FILTER_SKIP_DELETED) { if(e) *e = "lantern_gpu: unknown filter flags (only LANTERN_GPU_FILTER_SKIP_DELETED is defined)"; return 0; }
     return client_filter(c, labels, n, flags, e);
+}
+LANTERN_ABI_CATCH(e)
+
+size_t lantern_scan_client_extend_filter(lantern_scan_client_t *c, const usearch_label_t *labels, size_t n, uint32_t flags, usearch_error_t *e)
+try {
+    if(flags & ~(uint32_t)(LANTERN_GPU_FILTER_SKIP_DELETED | LANTERN_GPU_FILTER_EXTEND_ALL)) {
+        if(e) *e = "lantern_gpu: unknown filter flags (an extension takes LANTERN_GPU_FILTER_SKIP_DELETED and LANTERN_GPU_FILTER_EXTEND_ALL)";
+        return 0;
+    }
+    if((flags & LANTERN_GPU_FILTER_EXTEND_ALL) && n) {
+        if(e) *e = "lantern_gpu: LANTERN_GPU_FILTER_EXTEND_ALL allows every new slot: it takes no labels (n 0)";
+        return 0;
+    }
+    return client_filter(c, labels, n, flags, e, EXTEND_MAGIC);
 }
 LANTERN_ABI_CATCH(e)
 
