@@ -161,7 +161,11 @@ LANTERN_GPU_EXPORT metadata_t usearch_index_metadata(usearch_index_t, usearch_er
 LANTERN_GPU_EXPORT void usearch_save(usearch_index_t, const char *path, usearch_error_t *);
 /* build.c:679 */
 LANTERN_GPU_EXPORT void usearch_save_buffer(usearch_index_t, char *buffer, size_t length, usearch_error_t *);
-/* Rust Index::load_from_buffer (external_index_server_test.rs:271-314) / usearch_load */
+/* Rust Index::load_from_buffer (external_index_server_test.rs:271-314) / usearch_load.  The file is untrusted: a header that does not
+ * match the index options, a node count the length cannot hold, an entry slot, top level, neighbour count or neighbour slot out of
+ * range, a truncated or corrupt node tape, an upper-level list naming a node that does not reach that level and -- on a pq index
+ * with fewer than 256 centroids -- a code byte >= num_centroids ("a pq code names a centroid the codebook does not have") are refused
+ * before anything reaches the device, and the index stays empty.  usearch_view_mem_lazy holds the pages to the same checks. */
 LANTERN_GPU_EXPORT void usearch_load(usearch_index_t, const char *path, usearch_error_t *);
 LANTERN_GPU_EXPORT void usearch_load_buffer(usearch_index_t, const char *buffer, size_t length, usearch_error_t *);
 LANTERN_GPU_EXPORT size_t usearch_serialized_length(usearch_index_t, usearch_error_t *);

@@ -1031,6 +1031,14 @@ bool import_graph_locked(Index *ix, size_t size, const void *vectors, const uint
 {
     if(ix->n || !ix->pend_labels.empty()) { set_err(ix, "lantern_gpu: import needs an empty index"); return false; }
     if(size == 0) return true;
+    // the codes of a file or of the pages are as untrusted as their counts: k_pq_decode and the ADC table index the codebook with
+    // them, and a codebook of fewer than 256 centroids ends before a byte can -- checked here, before anything is copied or launched
+    if(ix->pq && vectors_are_codes && ix->pq_C < 256) {
+        const uint8_t *codes = (const uint8_t *)vectors;
+        const size_t   total = size * (size_t)ix->pq_S;
+        for(size_t i = 0; i < total; ++i)
+            if(codes[ i ] >= ix->pq_C) { set_err(ix, "lantern_gpu: a pq code names a centroid the codebook does not have"); return false; }
+    }
     if(!pq_expand_locked(ix)) return false;  // an empty index that was compacted has no row block: the import writes rows
     size_t blocks = 0;
     for(size_t i = 0; i < size; ++i) blocks += levels[ i ];

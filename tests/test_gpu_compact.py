@@ -70,8 +70,8 @@ def compact_and_check(capi, ix, fresh, capacity=0):
     return after, want_rows, slot_map, st
 
 
-def run_case(capi, metric, storage, d, M, n, dead, pq=False, also_without_unlink=False):
-    base = make_rows(metric, d, n, d + M)
+def run_case(capi, metric, storage, d, M, n, dead, pq=False, also_without_unlink=False, base=None):
+    base = make_rows(metric, d, n, d + M) if base is None else base
     kw = pq_kw(base) if pq else {}
     quant = "f32" if pq else storage
     dead = np.unique(np.asarray(dead, dtype=np.int64))
@@ -95,6 +95,7 @@ CASES = [
     ("l2sq", "f32", 3, 4, 700), ("cos", "f32", 16, 2, 1000), ("l2sq", "f32", 100, 4, 777), ("cos", "f32", 300, 16, 800),
     ("l2sq", "f32", 512, 16, 600), ("cos", "f32", 768, 4, 800), ("l2sq", "f16", 64, 4, 1000), ("cos", "i8", 100, 16, 1000),
     ("hamming", "f32", 24, 4, 1000),
+    ("l2sq", "f32", 64, 33, 1500),  # lists of W = 66 (and 33 above) in k_compact_lists: a tile of 256 entries ends inside a list
 ]
 
 
@@ -103,6 +104,33 @@ def test_compacted_graph_is_the_restatement(capi, metric, storage, d, M, n):
     ix, _, (after, _, _, _) = run_case(capi, metric, storage, d, M, n, random_share(n, 0.3), also_without_unlink=(d == 16))
     if d >= 512:
         assert ix.export_screen()["row_bytes"] > 0  # the case is about the screen
+
+
+def hubs_neighbours(capi, base, hub, M):
+    """every row a hub's list names, the hubs themselves kept: their lists empty out and are refilled from the offers"""
+    g = build(capi, "l2sq", "f32", base, M).export_graph()
+    named = np.unique(np.concatenate([g["nbr0"][s][g["nbr0"][s] != EMPTY] for s in hub]))
+    return np.setdiff1d(named, hub)
+
+
+@pytest.mark.parametrize("pattern", ["30 % of the other rows", "the hubs' neighbours"])
+def test_compacted_graph_with_lists_of_130(capi, pattern):
+    """tests/test_gpu_long_lists.py's hubs at M = 65: W = 130 (and 65 above) in k_compact_lists -- a list spans two tiles of 256
+    entries -- after the unlink of tests/test_gpu_delete.py's hubs case, and after one that takes every neighbour of every hub."""
+    from tests.test_gpu_long_lists import hubs
+
+    n, d, M = 1200, 128, 65
+    base, hub = hubs(n, d, 8, d + M)
+    rest = np.setdiff1d(np.arange(n), hub)
+    dead = rest[random_share(rest.size, 0.3)] if pattern.startswith("30") else hubs_neighbours(capi, base, hub, M)
+    assert dead.size > 0 and not np.intersect1d(dead, hub).size
+    ix, _, (after, _, slot_map, _) = run_case(capi, "l2sq", "f32", d, M, n, dead, base=base)
+    live = n - np.unique(dead).size
+    assert (slot_map == EMPTY).sum() == np.unique(dead).size and len(ix) == live
+    for key in ("nbr0", "upper_nbr"):  # no dangling entry: a list names live rows of the new numbering or is padding, padding last
+        named = after[key] != EMPTY
+        assert (after[key][named] < live).all() and not (named[:, 1:] & ~named[:, :-1]).any(), key
+    assert (after["nbr0"][slot_map[hub]] != EMPTY).any(axis=1).all()  # the hubs are linked again
 
 
 def test_compacted_pq_index_codes_follow_the_map(capi):

@@ -50,27 +50,31 @@ def graphs_equal(a, b):
     assert (a["entry_slot"], a["max_level"]) == (b["entry_slot"], b["max_level"])
 
 
-def remove_and_unlink(capi, oracle, metric, storage, base, M, dead_slots):
-    """Build, remove, unlink; every comparison with the restatement and every invariant.  Returns what the follow-up tests use."""
+def remove_and_unlink(capi, oracle, metric, storage, base, M, dead_slots, **kw):
+    """Build (kw: a pq codebook), remove, unlink; every comparison with the restatement and every invariant.  Returns what the
+    follow-up tests use; "want_stats" are the restatement's own (reprunes, max_kept: what the device does not count)."""
     n = base.shape[0]
-    ix = build(capi, metric, storage, base, M)
+    ix = build(capi, metric, storage, base, M, **kw)
     dead_slots = np.unique(np.asarray(dead_slots, dtype=np.int64))
     assert ix.remove_labels(dead_slots + 1) == dead_slots.size and ix.deleted_count == dead_slots.size
-    before = ix.export_graph()
+    before = ix.export_graph(with_vectors=bool(ix.pq_S))
     assert np.array_equal(np.flatnonzero(before["labels"] == 0), dead_slots)
-    rows_s, _, ometric, mode = (base, None, "hamming", oracle.SUM_SEQ) if metric == "hamming" else stored_rows(oracle, storage, metric, base, base[:1])
+    if ix.pq_S:  # an expanded pq index is the f32 index of its decoded rows (tests/test_gpu_quantized_indexes.py)
+        rows_s, ometric, mode = before.pop("vectors"), metric, oracle.SUM_WAVE64
+    else:
+        rows_s, _, ometric, mode = (base, None, "hamming", oracle.SUM_SEQ) if metric == "hamming" else stored_rows(oracle, storage, metric, base, base[:1])
     dist = unlink_ref.pair_matrix(oracle, rows_s, ometric, mode, 8)
     want, wst = unlink_ref.unlink(before, dist, M)
     st = ix.unlink_deleted()
     after = ix.export_graph()
-    print(f"{metric} {storage} {base.shape} M={M} dead={dead_slots.size}: {st}")
+    print(f"{metric} {storage} {base.shape} M={M} dead={dead_slots.size}: {st}; the restatement: reprunes {wst['reprunes']} max_kept {wst['max_kept']}")
     graphs_equal(after, want)
     assert {k: st[k] for k in unlink_ref.STATS} == {k: wst[k] for k in unlink_ref.STATS}
     assert (st["reprune_evals"] > 0) == (wst["reprunes"] > 0)
     unlink_ref.check_invariants(before, after, M)
     sum_before = ix.checksum()
     assert all(v == 0 for v in ix.unlink_deleted().values()) and ix.checksum() == sum_before  # a second call changes nothing
-    return dict(ix=ix, after=after, rows=rows_s, ometric=ometric, mode=mode, stats=st, dead=dead_slots)
+    return dict(ix=ix, after=after, rows=rows_s, ometric=ometric, mode=mode, stats=st, want_stats=wst, dead=dead_slots)
 
 
 def random_share(n, share, seed=5):
@@ -185,15 +189,57 @@ CASES = [
     ("l2sq", "f32", 768, 16, 1500, 0.90), ("cos", "f32", 768, 4, 800, 0.30), ("l2sq", "f32", 768, 2, 600, 0.30), ("cos", "f32", 768, 16, 900, 0.01),
     ("l2sq", "f16", 64, 4, 1000, 0.30), ("cos", "f16", 64, 16, 1000, 0.90), ("l2sq", "i8", 64, 2, 1000, 0.30), ("cos", "i8", 64, 16, 1000, 0.30),
     ("hamming", "f32", 24, 4, 1000, 0.30), ("hamming", "f32", 24, 16, 1000, 0.90),
+    # The unlink hands its offers to the build's grouping pass and launch_revlink (kernels.hip), with inputs no build produces: no radius
+    # on record and up to cut(cap) requests per list.  One case per reverse-link class the cases above do not reach; the restatement's
+    # re-prunes on the oracle's build of the same rows (the device's graph: same batch plan) are next to each case.
+    # k_revlink_pairs at 4, 6 and 8 chunks per lane (d = 1021: 256 chunks; 1536: 384; 2000: 500)
+    ("l2sq", "f32", 1021, 4, 800, 0.30), ("cos", "f32", 1021, 4, 800, 0.30),   # 704, 1210 re-prunes
+    ("l2sq", "f32", 1536, 4, 700, 0.30), ("cos", "f32", 1536, 4, 700, 0.30),   # 696, 1045
+    ("l2sq", "f32", 2000, 4, 600, 0.30), ("cos", "f32", 2000, 4, 600, 0.30),   # 631, 903
+    ("l2sq", "f32", 512, 40, 600, 0.30),    # the generic k_revlink (82 rows of 2 KiB do not fit the staged kernel): 493, the longest kept list 80
+    ("l2sq", "f32", 64, 32, 1500, 0.30),    # k_revlink_staged without chain mode, cap 64: 1956, max_kept 64
+    ("l2sq", "f32", 64, 33, 1500, 0.30),    # ... cap 66, the heuristic's second kept slot per lane: 2137, max_kept 66
+    ("hamming", "f32", 560, 24, 700, 0.30),  # 140 chunks, cap 48: staged, in chain mode, on wide bit rows: 2981
+    ("l2sq", "b1", 200, 4, 1000, 0.30), ("cos", "b1", 200, 4, 1000, 0.30),  # sign-bit rows (hamming / cos_b1 on 7 words): 1644, 1237
 ]
+MIN_MAX_KEPT = {33: 64, 65: 128}  # M -> what the longest list a re-prune of the restatement left must exceed: kpos[1], kpos[2] of k_revlink_staged
 
 
 @pytest.mark.parametrize("metric,storage,d,M,n,share", CASES)
 def test_unlink_equals_the_restatement(capi, oracle, metric, storage, d, M, n, share):
     base = make_rows(metric, d, n, d + M)
     r = remove_and_unlink(capi, oracle, metric, storage, base, M, random_share(n, share))
-    if M <= 4 and share >= 0.3:
+    if share >= 0.3 and (M <= 4 or M >= 24):
         assert r["stats"]["reprune_evals"] > 0  # full lists: the re-prune path ran
+    if M in MIN_MAX_KEPT:  # on the restatement alone
+        assert r["want_stats"]["max_kept"] > MIN_MAX_KEPT[M], r["want_stats"]
+
+
+def test_unlink_on_hubs_with_lists_of_130(capi, oracle):
+    """tests/test_gpu_long_lists.py's hubs at M = 65 (cap 130: k_revlink_staged, the heuristic's third kept slot per lane).  The
+    tombstones are 30 % of the rows that are not hubs, so the hubs' full lists lose about 39 entries each and are offered the
+    neighbours of those.  Measured on the restatement over the oracle's build: 6787 re-prunes, max_kept 130."""
+    from tests.test_gpu_long_lists import hubs
+
+    n, d, M = 1200, 128, 65
+    base, hub = hubs(n, d, 8, d + M)
+    rest = np.setdiff1d(np.arange(n), hub)
+    r = remove_and_unlink(capi, oracle, "l2sq", "f32", base, M, rest[random_share(rest.size, 0.3)])
+    assert r["want_stats"]["max_kept"] > MIN_MAX_KEPT[M], r["want_stats"]
+    assert r["stats"]["reprune_evals"] > 0
+
+
+def test_unlink_on_an_expanded_pq_index(capi, oracle):
+    """pq rows (S = 8, C = 32, d = 64): the expanded index holds the decodings, and the unlink is the restatement over those --
+    the exported vectors, in the f32 order (SUM_WAVE64) --, not only a count of tombstones."""
+    from tests.test_gpu_quantized_indexes import make_codebook
+
+    n, d, M = 1000, 64, 4
+    base = make_rows("l2sq", d, n, d + M)
+    cb = make_codebook(np.random.default_rng(0), base, 8, 32)
+    r = remove_and_unlink(capi, oracle, "l2sq", "f32", base, M, random_share(n, 0.3), pq_codebook=cb, num_subvectors=8)
+    assert r["ix"].pq_S == 8 and not np.array_equal(r["rows"], base)
+    assert r["stats"]["reprune_evals"] > 0
 
 
 def test_unlink_entry_node_isolated_node_and_adjacent_tombstones(capi, oracle):
@@ -218,31 +264,49 @@ def test_unlink_with_identical_rows(capi, oracle):
         remove_and_unlink(capi, oracle, metric, "f32", base, M, dead)
 
 
-def cut_case(oracle):
+def cut_case(oracle, M=16, d=100, n=1500):
     """M 16: cut(0) = 256 offers need a list most of whose 32 entries are tombstones with mostly live lists of their own.  A random
     share s of deletions gives a list about 1024 s (1 - s) candidates before duplicates -- at most 256, 92 at 90 % -- so it never
     reaches the cut; deleting only the neighbours of a few nodes does.  The restatement on the oracle's build (the device's graph:
-    same batch plan) says how many lists are cut."""
-    n, d, M = 1500, 100, 16
-    base = make_rows("l2sq", d, n, 41)
+    same batch plan) says how many lists are cut.
+    M 17 and 32: cut(0) = 8 x 2 M = 272 and 512, the other branch of unlink_cut; there the neighbours of the three longest level-0
+    lists go (a stable argsort of the lengths), those three nodes stay."""
     ora = oracle.OracleIndex("l2sq", d, M=M, ef_construction=EFC, ef=EF, seed=11, sum_mode=oracle.SUM_WAVE64)
-    ora.add_planned(np.arange(n, dtype=np.uint64) + 1, base, 256, 16)
-    g = ora.export_graph()
-    full = [s for s in range(n) if len(unlink_ref.get_list(g, s, 0, M)) == 2 * M][:3]
+    if M == 16:
+        base = make_rows("l2sq", d, n, 41)
+        ora.add_planned(np.arange(n, dtype=np.uint64) + 1, base, 256, 16)
+        g = ora.export_graph()
+        full = [s for s in range(n) if len(unlink_ref.get_list(g, s, 0, M)) == 2 * M][:3]
+    else:
+        base = make_rows("l2sq", d, n, d + M)
+        ora.add_planned(np.arange(n, dtype=np.uint64) + 1, base, 256, 16)
+        g = ora.export_graph()
+        full = [int(s) for s in np.argsort(-(g["nbr0"] != unlink_ref.EMPTY).sum(axis=1), kind="stable")[:3]]
     dead = np.unique(np.concatenate([unlink_ref.get_list(g, s, 0, M) for s in full]))
     return base, np.setdiff1d(dead, full)
 
 
-def test_unlink_cuts_the_offers_at_256(capi, oracle):
-    base, dead = cut_case(oracle)
-    r = remove_and_unlink(capi, oracle, "l2sq", "f32", base, 16, dead)
+# M, d, n, cut(0), and on the oracle's graph: the lists the restatement cuts, its re-prunes
+CUT_CASES = [(16, 100, 1500, 256, None, None), (17, 64, 1500, 272, 3, 2616), (32, 64, 1500, 512, 3, 1759)]
+
+
+@pytest.mark.parametrize("M,d,n,cut,lists_cut,reprunes", CUT_CASES, ids=[f"M{c[0]}" for c in CUT_CASES])
+def test_unlink_cuts_the_offers_at_256(capi, oracle, M, d, n, cut, lists_cut, reprunes):
+    """... or at 8 cap, whichever is more"""
+    assert unlink_ref.cut_of(0, M) == cut
+    base, dead = cut_case(oracle, M, d, n)
+    r = remove_and_unlink(capi, oracle, "l2sq", "f32", base, M, dead)
     assert r["stats"]["lists_cut"] > 0
+    if lists_cut is not None:  # (the restatement ran on the device's graph: the oracle's, if the build is right)
+        assert (r["want_stats"]["lists_cut"], r["want_stats"]["reprunes"]) == (lists_cut, reprunes)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the graph still works
 # ---------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("metric,storage,d,M", [("l2sq", "f32", 768, 16), ("cos", "f16", 64, 4)])
+# d = 1021, M = 4: k_revlink_pairs, whose re-prunes keep a state across batches (the radii on record) -- the unlink resets it, and the
+# 300 rows added afterwards build on the reset; d = 64, M = 32: lists of 64 (k_revlink_staged without chain mode) before and after
+@pytest.mark.parametrize("metric,storage,d,M", [("l2sq", "f32", 768, 16), ("cos", "f16", 64, 4), ("l2sq", "f32", 1021, 4), ("l2sq", "f32", 64, 32)])
 def test_unlinked_graph_searches_and_grows_as_the_oracle_on_the_same_graph(capi, oracle, metric, storage, d, M):
     from lantern_amd import hip
 

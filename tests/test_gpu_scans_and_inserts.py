@@ -362,6 +362,40 @@ def test_corrupt_files_are_refused_not_trusted(capi):
     struct.pack_into("<I", bad, off + 10 + (4 + 2 * M * 6) + 4, flat)
     with pytest.raises(capi.LanternGpuError, match="does not reach that level"):
         load(bad)
+    # the code bytes of a pq file index the codebook on the device (k_pq_decode, the ADC table): with fewer than 256 centroids a byte
+    # can name one the codebook does not have.  The refusal comes before anything is copied or launched, and the index stays empty
+    from tests.test_gpu_quantized_indexes import make_codebook
+
+    d, S = 64, 8
+    sample = rng.standard_normal((300, d), dtype=np.float32)  # (256 centroids are sampled from at least as many rows)
+    rows = sample[:200]
+    for C in (32, 256):
+        cb = make_codebook(np.random.default_rng(C), sample, S, C)
+        kw = dict(M=M, ef_construction=16, seed=3, pq_codebook=cb, num_subvectors=S)
+        pq = capi.GpuIndex("l2sq", d, **kw)
+        pq.add_many(np.arange(200) + 1, rows)
+        blob, g = pq.save_buffer(), pq.export_graph()
+        again = capi.GpuIndex("l2sq", d, **kw)
+        again.load_buffer(blob)
+        assert again.checksum() == pq.checksum()
+        off = 136  # the codes of node 57: behind its lists
+        for i in range(57):
+            off += 10 + (4 + 2 * M * 6) + int(g["levels"][i]) * (4 + M * 6) + S
+        off += 10 + (4 + 2 * M * 6) + int(g["levels"][57]) * (4 + M * 6)
+        assert blob[off:off + S] == pq.export_codes()[57].tobytes()
+        for byte in (32, 255):
+            bad = bytearray(blob)
+            bad[off + 3] = byte
+            fresh = capi.GpuIndex("l2sq", d, **kw)
+            if C == 256:  # every byte value names a centroid
+                fresh.load_buffer(bytes(bad))
+                assert len(fresh) == 200 and fresh.export_codes()[57][3] == byte
+                continue
+            with pytest.raises(capi.LanternGpuError, match="a pq code names a centroid the codebook does not have"):
+                fresh.load_buffer(bytes(bad))
+            assert len(fresh) == 0
+            fresh.load_buffer(blob)  # ... and still loads the sound file
+            assert fresh.checksum() == pq.checksum()
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -72,7 +72,7 @@ def unlink(graph, dist, M):
     drow = dist if callable(dist) else (lambda a: dist[a])
     out = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in graph.items()}
     stats = {k: 0 for k in STATS}
-    stats["reprunes"] = 0
+    stats["reprunes"] = stats["max_kept"] = 0
     labels, levels = graph["labels"], graph["levels"]
     n = len(labels)
     dead = np.asarray(labels) == 0
@@ -101,7 +101,9 @@ def unlink(graph, dist, M):
             new = list(keep)
             dp = drow(p)
             for c in offers:
-                stats["reprunes"] += reverse_link(new, cap, p, c, dp[c], drow)
+                if reverse_link(new, cap, p, c, dp[c], drow):
+                    stats["reprunes"] += 1
+                    stats["max_kept"] = max(stats["max_kept"], len(new))  # the longest list a re-prune left
             set_list(out, p, level, M, new)
             stats["lists_repaired"] += 1
             stats["offers"] += len(offers)
