@@ -662,6 +662,29 @@ LANTERN_GPU_EXPORT void lantern_gpu_set_search_shape(usearch_index_t, int waves_
  * lantern_gpu_exact_knn_stats).  k <= 240. */
 LANTERN_GPU_EXPORT void lantern_gpu_exact_search(usearch_index_t, const void *queries, size_t nq, size_t k,
                                                  uint32_t *slots, float *distances, usearch_error_t *);
+/* COMPACT PQ INDEXES (DESIGN.md 4.5 "Compact pq indexes").  on = 0, THE DEFAULT: lantern_gpu_exact_search on a compact pq index decodes
+ * every row back first (lantern_gpu_pq_expand: rows x dimensions f32, 24 x the code bytes at 768 / 96) and leaves the index expanded.
+ * on = 1: a compact index whose rows can be decoded on the fly (subvectors of whole 16-byte chunks, l2sq / cos) is answered FROM ITS
+ * CODE ROWS and stays compact: the contraction builds its tiles from the centroid tables (k_dense_pq), norms, re-rank and the
+ * exact-order fallback decode what they read, and no f32 copy of the rows is allocated (the fallback, when the certificate refuses a
+ * query, decodes one chunk of up to 65536 rows at a time).  The answer is the expanded index's: the same slots and distance bits,
+ * the same guarantee.  A compact index whose rows cannot be decoded on the fly is expanded as with 0.  on other than 0 or 1 is refused.
+ * On an index that is not compact the setting changes nothing. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_exact_compact(usearch_index_t, int on, usearch_error_t *);
+/* diagnostic: 0 the switch is off; else what lantern_gpu_exact_search does on the index as it stands now: 1 it reads stored rows (a
+ * compact index is expanded first), 2 it runs on the code rows */
+LANTERN_GPU_EXPORT int lantern_gpu_exact_compact(usearch_index_t, usearch_error_t *);
+/* The decision above without a device (a pure function; the entry point decides through it).
+ * in[10]: [0] the index's metric code (as lantern_gpu_plan_dense)  [1] 16-byte chunks of a DECODED row  [2] rows  [3] queries  [4] k
+ *         [5] the switch  [6] the index is compact  [7] its decode-on-the-fly inverse (0: subvectors are not whole chunks)
+ *         [8] bytes of a code row in device memory  [9] LANTERN_GPU_DENSE_FUSED (< 0: unset)
+ * out[10]: [0] 1: the call runs on the code rows  [1] why not: 0 it does, 1 the switch is off, 2 the index is not compact, 3 its rows
+ *          cannot be decoded on the fly, 4 the metric  [2] the contraction's operand kind (4: code rows; lantern_gpu_plan_exact_knn's
+ *          kind)  [3] the metric code the run is planned with (the index's + 600)  [4..5] bytes the certified run allocates on the
+ *          device (lantern_gpu_plan_exact_knn's aux + dd + cand: no copy of the rows)  [6..7] the one decoded chunk the exact-order
+ *          fallback allocates if it runs  [8..9] not taken, compact: the f32 row block the call decodes the index into.  Byte counts
+ *          as (low, high) words.  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_exact_compact(const int64_t in[10], uint32_t out[10]);
 
 /* Diagnostic for the measurement harness: HIP events around every launch of the MFMA contraction (k_dense_f32; k_dense_native on
  * f16 / i8 indexes) inside
@@ -678,9 +701,10 @@ LANTERN_GPU_EXPORT void lantern_gpu_exact_knn_stats(uint64_t *queries, uint64_t 
  * lantern_gpu_exact_search / _assign_to_clusters / PQ encoding and lantern_gpu_distance_matrix(exact_order = 0). */
 LANTERN_GPU_EXPORT void lantern_gpu_dense_kind_stats(uint64_t launches[3]);
 /* Which contraction an exact k-NN call runs -- host arithmetic only; the call itself takes its decisions from this function.
- * in:  [0] the index's internal metric code (metric, + 100 for f16 storage, + 200 for i8), [1] 16-byte chunks per stored row,
+ * in:  [0] the index's internal metric code (metric, + 100 for f16 storage, + 200 for i8; + 600: the code rows of a compact pq
+ *      index decoded on the fly, lantern_gpu_set_exact_compact), [1] 16-byte chunks per stored (+ 600: decoded) row,
  *      [2] base rows, [3] the value of LANTERN_GPU_DENSE_NATIVE (-1: unset).
- * out: [0] operand kind 0 / 1 / 2 (f32, f16, i8); [1] bytes of the f32 copy of one chunk of base rows the call allocates (0
+ * out: [0] operand kind 0 / 1 / 2 (f32, f16, i8), 4 (code rows: metric code + 600); [1] bytes of the f32 copy of one chunk of base rows the call allocates (0
  *      when the rows are contracted as stored); [2] the `dims` handed to the certificate (0: the pre-selection ranks on the
  *      exact-order distance itself and is certified by construction: popcount metrics, native i8); [3] K steps (128 bytes per
  *      row each) per output tile (0: no MFMA contraction).  Returns NULL, or why the input is refused. */
@@ -828,8 +852,8 @@ LANTERN_GPU_EXPORT void lantern_gpu_export_codes(usearch_index_t, uint8_t *codes
  * distance computation over the code bytes: a per-query table of partial sums (subvector x centroid) in LDS, num_subvectors
  * table entries added per row (lantern_amd/csrc/search_adc_kernel.hip; summation order defined there and restated by the
  * oracle -- distances agree with the decoded-row path to 1e-5 relative, not bit for bit: PARITY UNPINNED BY THE REFERENCE).
- * Anything that needs rows again (usearch_add, the exact search, an export with vectors) decodes them back first, as does
- * lantern_gpu_pq_expand.  LANTERN_GPU_PQ_COMPACT=1 compacts a pq index right after it is loaded or mirrored. */
+ * Anything that needs rows again (usearch_add, an export with vectors; the exact search unless lantern_gpu_set_exact_compact lets it
+ * run on the code rows) decodes them back first, as does lantern_gpu_pq_expand.  LANTERN_GPU_PQ_COMPACT=1 compacts a pq index right after it is loaded or mirrored. */
 LANTERN_GPU_EXPORT void lantern_gpu_pq_compact(usearch_index_t, usearch_error_t *);
 LANTERN_GPU_EXPORT void lantern_gpu_pq_expand(usearch_index_t, usearch_error_t *);
 /* HBM held by the index: the vector block (the code rows of a compact pq index) | adjacency, labels, levels, norms, codes */

@@ -96,7 +96,7 @@ EXPORTS = [
     "lantern_gpu_version", "lantern_gpu_device_count",
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
-    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
+    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_set_exact_compact", "lantern_gpu_exact_compact", "lantern_gpu_plan_exact_compact", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
     "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
@@ -248,6 +248,9 @@ def lib() -> C.CDLL:
         "lantern_gpu_dense_kind_stats": (None, [vp]),
         "lantern_gpu_plan_dense": (C.c_char_p, [vp, vp]),
         "lantern_gpu_plan_exact_knn": (C.c_char_p, [vp, vp, vp, sz, vp]),
+        "lantern_gpu_set_exact_compact": (None, [vp, C.c_int, err]),
+        "lantern_gpu_exact_compact": (C.c_int, [vp, err]),
+        "lantern_gpu_plan_exact_compact": (C.c_char_p, [vp, vp]),
         "lantern_gpu_distance_gather": (None, [vp, vp, vp, sz, vp, err]),
         "lantern_gpu_spec_profile": (None, [vp, i32, vp, err]),
         "lantern_gpu_search_unique_rows": (None, [vp, i32, C.POINTER(u64), err]),
@@ -546,6 +549,22 @@ def plan_exact_knn(mcode, chunks, nb, nq, k, native=-1, fused=-1):
     plan["n_steps"] = int(count.value)
     plan["steps"] = [(int(s[0]), int(s[1]), bool(s[2]), int(s[3])) for s in steps[:cap]]
     return plan
+
+
+# lantern_gpu_plan_exact_compact's out[1], by value
+EXACT_COMPACT_WHY = ("taken", "off", "expanded", "no_decode", "metric")
+
+
+def plan_exact_compact(mcode, chunks, nb, nq, k, on, compact, pqd_inv, code_row_bytes, fused=-1):
+    """lantern_gpu_plan_exact_compact: whether exact_search on a pq index answers from the code rows (host arithmetic, no device):
+    {"taken", "why" (EXACT_COMPACT_WHY), "kind", "mcode", "run_bytes", "fallback_bytes", "expand_bytes"}."""
+    pin, out = np.array([mcode, chunks, nb, nq, k, int(on), int(compact), pqd_inv, code_row_bytes, fused], np.int64), np.zeros(10, np.uint32)
+    why = lib().lantern_gpu_plan_exact_compact(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    size = lambda i: int(out[i]) | int(out[i + 1]) << 32
+    return {"taken": bool(out[0]), "why": EXACT_COMPACT_WHY[int(out[1])], "kind": int(out[2]), "mcode": int(out[3]), "run_bytes": size(4),
+            "fallback_bytes": size(6), "expand_bytes": size(8)}
 
 
 # lantern_gpu_plan_filtered_dense's out[1], by value
@@ -945,6 +964,14 @@ class GpuIndex:
         dists = np.zeros((Q.shape[0], k), dtype=np.float32)
         _call("lantern_gpu_exact_search", self.h, _ptr(Q), Q.shape[0], k, _ptr(slots), _ptr(dists))
         return slots, dists
+
+    def set_exact_compact(self, on):
+        """exact_search answers this index in its compact pq form from the code rows and leaves it compact (1), or expands it (0, the default)."""
+        _call("lantern_gpu_set_exact_compact", self.h, int(on))
+
+    def exact_compact(self):
+        """lantern_gpu_exact_compact: 0 the switch is off, 1 exact_search reads stored rows (a compact index is expanded), 2 it runs on the code rows."""
+        return int(_call("lantern_gpu_exact_compact", self.h))
 
     # ---- filtered search (lantern_gpu.h "Filtered search") ----
     def filter_from_labels(self, labels, skip_deleted=False) -> "Filter":

@@ -816,8 +816,9 @@ hipError_t launch_gather_rows_norms(int kind, int metric, const uint4 *src, uint
 }
 
 // ---------------------------------------------------------------------------------------------------
-hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream)
+hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream, const DensePqRows *pq)
 {
+    if(kind == kDensePq) return pq ? launch_norms_pq(*pq, rows, n, chunks, (float *)out, stream) : hipErrorInvalidValue;
     if(kind != 0) return launch_norms_native(kind, metric, rows, n, chunks, (uint32_t *)out, stream);
     if(n == 0) return hipSuccess;
     const int G_ = group_lanes_for(chunks);
@@ -888,6 +889,7 @@ static hipError_t launch_f32(const DenseOperands &o, float *out, uint32_t ldo, c
 
 hipError_t launch_contraction(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream)
 {
+    if(o.kind == kDensePq) return launch_contraction_pq(o, out, ldo, topk, stream);
     if(o.kind != 0) return launch_contraction_native(o, out, ldo, topk, stream);
     const DenseTopk none = { nullptr, 0, nullptr, nullptr, 0, 0 };
     return !topk ? launch_f32<false>(o, out, ldo, none, stream) : launch_f32<true>(o, (float *)nullptr, 0u, *topk, stream);
@@ -911,9 +913,10 @@ hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, co
 }
 
 hipError_t launch_rerank(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
-                         uint32_t k, uint32_t *out_slots, float *out_dists, const uint32_t *list, hipStream_t stream)
+                         uint32_t k, uint32_t *out_slots, float *out_dists, const uint32_t *list, hipStream_t stream, const DensePqRows *pq)
 {
     if(nq == 0) return hipSuccess;
+    if(mcode_is_pqd(metric)) return pq && !list ? launch_rerank_pq(metric, *pq, Q, nq, B, chunks, best, kk, k, out_slots, out_dists, stream) : hipErrorInvalidValue;
     const int G_ = group_lanes_for(chunks);
 #define RR(MM, GG) hipLaunchKernelGGL((k_rerank<MM, GG>), dim3(nq), dim3(256), 0, stream, Q, B, chunks, best, kk, k, out_slots, out_dists, list)
 #define RRG(MM) switch(G_) { case 64: RR(MM, 64); break; case 32: RR(MM, 32); break; case 16: RR(MM, 16); break; default: RR(MM, 8); }

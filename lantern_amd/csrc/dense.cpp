@@ -3,7 +3,7 @@
 // the same run over a filter's slot list is the filtered exact path's dense route (plan_filtered_dense, filtered_dense_device), and over
 // the concatenated lists of a per-query-filter call's groups, segment by segment, that call's (plan_filtered_each_dense,
 // filtered_each_dense_device).
-// The kernels: bruteforce.hip, dense_native.hip; the two launchers this unit calls them through: kernels.hpp.
+// The kernels: bruteforce.hip, dense_native.hip, dense_pq.hip (the code rows of a compact pq index: plan_exact_compact); the two launchers this unit calls them through: kernels.hpp.
 #include "dense.hpp"
 #include "index.hpp"
 #include "abi_guard.hpp"
@@ -140,7 +140,7 @@ static const char *plan_operands(int64_t mcode_in, int64_t chunks_in, int64_t nb
     const bool f16 = mcode_is_f16(p.mcode), i8 = mcode_is_i8(p.mcode);
     p.bits = base == M_HAMMING || base == M_COS_B1;
     const bool native_on = (f16 || i8) && !p.bits && (native < 0 ? kDenseNativeDefault : (int)native) != 0;
-    p.kind = !native_on ? 0 : f16 ? 1 : 2;
+    p.kind = mcode_is_pqd(p.mcode) ? kDensePq : !native_on ? 0 : f16 ? 1 : 2;  // (code rows decode to f32: dims, k_steps and the certificate are kind 0's)
     p.copy = native_on ? 0 : f16 ? 1 : i8 ? 2 : 0;
     p.fchunks = native_on ? p.chunks : i8 ? p.chunks * 4 : f16 ? p.chunks * 2 : p.chunks;
     const uint64_t copy_bytes = p.copy ? (uint64_t)std::min<int64_t>(nb, (int64_t)kDenseChunkRows) * p.fchunks * 16 : 0;
@@ -226,10 +226,12 @@ static std::vector<KnnStep> plan_steps(const ExactKnnPlan &p)
 // contract every query with every row, EachDensePlan::steps for the segmented run (a query's keys then come from its own segment of
 // the list only; everything behind the contractions is per query and runs unchanged).
 // queued: NULL, or what the caller queues behind the certificate and in front of the wait, given the device flags (NULL: exact keys).
+// pq (p.kind == kDensePq, d_list NULL): d_base is code rows; a row's stride is pq->row_bytes, everything else is the f32 rows' run.
 static bool exact_knn_run(const ExactKnnPlan &p, const std::vector<KnnStep> &steps, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q,
                           uint32_t *d_slots, float *d_dists, hipStream_t st, bool *overflowed, std::vector<uint32_t> &certified,
-                          const EachDenseAnswers *queued = nullptr)
+                          const EachDenseAnswers *queued = nullptr, const DensePqRows *pq = nullptr)
 try {
+    if((p.kind == kDensePq) != (pq != nullptr) || (pq && d_list)) return false;
     int dev = 0;
     (void)hipGetDevice(&dev);
     KnnPool *const               pool = (dev >= 0 && dev < 16) ? &g_knn_pool[ dev ] : nullptr;
@@ -247,6 +249,8 @@ try {
     const SyncOnUnwind sync_on_unwind{ st };  // (declared last: destroyed first)
     const uint32_t nq = (uint32_t)p.nq, nb = (uint32_t)p.nb, kk = p.kk, chunks = p.chunks, fchunks = p.fchunks;
     const int      base_metric = mcode_base(p.mcode);
+    const size_t   row_bytes = pq ? pq->row_bytes : (size_t)chunks * 16;  // of a base row as d_base holds it
+    auto rows_at = [&](const uint4 *b, size_t r) { return (const uint4 *)((const char *)b + r * row_bytes); };
     auto dequant = [&](const uint4 *src, size_t nchunks, uint4 *dst) { return p.copy == 2 ? launch_dequant_i8(src, nchunks, dst, st) : launch_dequant_f16(src, nchunks, dst, st); };
     bool ok = b_aux.get(p.aux_bytes, pool, 0) && b_dd.get(p.dd_bytes, pool, 1);
     if(ok && p.fused) ok = b_cand.get(p.cand_bytes, pool, 2) && hipMemsetAsync(b_cand.as<char>() + p.cnt_off, 0, p.cand_bytes - p.cnt_off, st) == hipSuccess;
@@ -263,12 +267,12 @@ try {
         const int       gather_kind = p.bits || p.copy ? 3 : p.kind;
         const uint4    *qv = p.copy ? b_fq.as<uint4>() : d_q;
         ok = ok && hipMemsetAsync(best, 0xFF, p.nq * kk * 8, st) == hipSuccess;
-        if(!p.bits) ok = ok && launch_norms(p.kind, base_metric, qv, nq, fchunks, qn, st) == hipSuccess;
-        if(!p.bits && !p.copy && !d_list) ok = ok && launch_norms(p.kind, base_metric, d_base, nb, fchunks, bn, st) == hipSuccess;
+        if(!p.bits) ok = ok && launch_norms(pq ? 0 : p.kind, base_metric, qv, nq, fchunks, qn, st) == hipSuccess;  // (the queries of a run over code rows are f32 rows)
+        if(!p.bits && !p.copy && !d_list) ok = ok && launch_norms(p.kind, base_metric, d_base, nb, fchunks, bn, st, pq) == hipSuccess;
         size_t si = 0;
         for(size_t c0 = 0; ok && c0 < p.nb; c0 += p.chunk_rows) {
             const size_t nc = std::min<size_t>(p.chunk_rows, p.nb - c0);
-            const uint4 *bv = d_base + c0 * chunks;
+            const uint4 *bv = rows_at(d_base, c0);
             if(d_list) {
                 DenseTimer t(st, 0, (uint32_t)nc, 2u);  // (lantern_gpu_dense_profile: fused = 2 marks a gather, rows = 0)
                 ok = ok && launch_gather_rows_norms(gather_kind, base_metric, d_base, chunks, d_list + c0, (uint32_t)nc, gb, bn + c0, st) == hipSuccess;
@@ -282,18 +286,19 @@ try {
             for(; ok && si < steps.size() && steps[ si ].col0 < c0 + nc; ++si) {
                 const KnnStep       s = steps[ si ];
                 uint64_t *const     mine = best + (size_t)s.q0 * kk;
-                const DenseOperands o = { p.kind, base_metric, qv + (size_t)s.q0 * fchunks, s.nqt, bv + (s.col0 - c0) * fchunks, s.cols, fchunks, qn + s.q0, bn + s.col0 };
+                const DenseOperands o = { p.kind, base_metric, qv + (size_t)s.q0 * fchunks, s.nqt, pq ? rows_at(bv, s.col0 - c0) : bv + (s.col0 - c0) * fchunks, s.cols, fchunks,
+                                          qn + s.q0, bn + s.col0, pq ? *pq : DensePqRows{} };
                 const DenseTopk     tk = { mine, kk, cand, ccnt, p.cand_cap, s.col0 };
                 {
                     DenseTimer t(st, s.nqt, s.cols, s.fused != 0 ? 1u : 0u);
                     ok = ok && launch_contraction(o, dd, p.ldd, s.fused ? &tk : nullptr, st) == hipSuccess;
-                    if(!p.bits) ++g_dense_kind[ p.kind ];
+                    if(!p.bits && p.kind < 3) ++g_dense_kind[ p.kind ];
                 }
                 if(s.fused) ok = ok && launch_select_candidates(s.nqt, mine, kk, cand, ccnt, p.cand_cap, cover, st) == hipSuccess;
                 else ok = ok && launch_select(dd, p.ldd, s.nqt, s.cols, s.col0, mine, kk, st) == hipSuccess;
             }
         }
-        ok = ok && launch_rerank(p.mcode, d_q, nq, d_base, chunks, best, kk, p.k, d_slots, d_dists, d_list, st) == hipSuccess;
+        ok = ok && launch_rerank(p.mcode, d_q, nq, d_base, chunks, best, kk, p.k, d_slots, d_dists, d_list, st, pq) == hipSuccess;
         // the certificate: 4 bytes per query to the host, behind the synchronisation the call makes anyway.  The popcount metrics
         // rank on the exact-order distance itself (the same integer arithmetic): their pre-selection is exact by construction.
         certified.assign(p.nq + 1, p.exact_keys ? 1u : 0u);
@@ -320,12 +325,18 @@ LANTERN_ABI_CATCH(nullptr)
 // The queries the certificate refused, recomputed in the pair kernel's exact order over every base row: their rows gathered,
 // k_pairs + k_select (top-k by (exact distance, slot)) per block of kFallbackQ queries and chunk of base rows, the keys written
 // over their rows of the result.  nf x nb exact-order evaluations: rare (adversarial data), not fast.
+// pq: d_base is code rows -- every chunk of them is decoded into a block of its own first (CH rows: the one f32 copy this unit ever
+// makes of a compact index's rows, and only here), and the pair kernel runs on it under the base metric.
 static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t k, const std::vector<uint32_t> &qidx,
-                               uint32_t *d_slots, float *d_dists, hipStream_t st)
+                               uint32_t *d_slots, float *d_dists, hipStream_t st, const DensePqRows *pq = nullptr)
 {
     const size_t nf = qidx.size(), CH = std::min(nb, kDenseChunkRows), kFallbackQ = 256, nfb = std::min(nf, kFallbackQ);
-    DeviceBlock  b_idx, b_rows, b_best, b_dd;
+    DeviceBlock  b_idx, b_rows, b_best, b_dd, b_dec;
     bool         ok = b_idx.get(nf * 4) && b_rows.get(nf * (size_t)chunks * 16) && b_best.get(nf * k * 8) && b_dd.get(nfb * CH * 4);
+    if(pq) {
+        ok = ok && b_dec.get(CH * (size_t)chunks * 16);
+        mcode = mcode_base(mcode);
+    }
     uint32_t *const d_idx = b_idx.as<uint32_t>();
     uint4 *const    d_rows = b_rows.as<uint4>();
     uint64_t *const d_best = b_best.as<uint64_t>();
@@ -335,9 +346,14 @@ static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, 
     ok = ok && launch_gather_rows(d_q, chunks, d_idx, (uint32_t)nf, d_rows, st) == hipSuccess;
     for(size_t c0 = 0; ok && c0 < nb; c0 += CH) {
         const size_t nc = std::min(CH, nb - c0);
+        const uint4 *bv = d_base + c0 * chunks;
+        if(pq) {
+            ok = ok && launch_pq_decode_rows(*pq, (const uint4 *)((const char *)d_base + c0 * pq->row_bytes), (uint32_t)nc, chunks, b_dec.as<uint4>(), st) == hipSuccess;
+            bv = b_dec.as<uint4>();
+        }
         for(size_t f0 = 0; ok && f0 < nf; f0 += kFallbackQ) {
             const size_t nft = std::min(kFallbackQ, nf - f0);
-            ok = ok && launch_pairs(mcode, d_rows + f0 * chunks, (uint32_t)nft, d_base + c0 * chunks, (uint32_t)nc, chunks, d_dd, st) == hipSuccess;
+            ok = ok && launch_pairs(mcode, d_rows + f0 * chunks, (uint32_t)nft, bv, (uint32_t)nc, chunks, d_dd, st) == hipSuccess;
             ok = ok && launch_select(d_dd, (uint32_t)nc, (uint32_t)nft, (uint32_t)nc, (uint32_t)c0, d_best + f0 * k, (uint32_t)k, st) == hipSuccess;
         }
     }
@@ -350,15 +366,16 @@ static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, 
 // A plan run to its certificate: once, and once more unfused (planned anew from the plan's own numbers) when a candidate list
 // overflowed.  certified: the flag of every query; refused: the queries without one, which the caller recomputes.
 static bool exact_knn_certified(const ExactKnnPlan &first, int native, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots,
-                                float *d_dists, hipStream_t st, std::vector<uint32_t> &certified, std::vector<uint32_t> &refused)
+                                float *d_dists, hipStream_t st, std::vector<uint32_t> &certified, std::vector<uint32_t> &refused,
+                                const DensePqRows *pq = nullptr)
 {
     bool over = false;
-    if(!exact_knn_run(first, plan_steps(first), d_base, d_list, d_q, d_slots, d_dists, st, &over, certified)) return false;
+    if(!exact_knn_run(first, plan_steps(first), d_base, d_list, d_q, d_slots, d_dists, st, &over, certified, nullptr, pq)) return false;
     if(over) {  // the same call, unfused
         ExactKnnPlan plan;
         if(plan_exact_knn(first.mcode, first.chunks, (int64_t)first.nb, (int64_t)first.nq, (int64_t)first.k, native, 0, plan) != nullptr) return false;
         plan.gb_bytes = first.gb_bytes;
-        if(!exact_knn_run(plan, plan_steps(plan), d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified)) return false;
+        if(!exact_knn_run(plan, plan_steps(plan), d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified, nullptr, pq)) return false;
     }
     refused.clear();
     for(size_t q = 0; q < first.nq; ++q)
@@ -483,19 +500,43 @@ LANTERN_ABI_CATCH(nullptr)
 // fp32- or native-MFMA contraction in chunks of 64k base rows + running top-(k+16) + exact-order re-rank, then per query the certificate
 // that the top-(k+16) held the exact answer; the refused queries are recomputed in exact order.
 bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k, uint32_t *d_slots,
-                      float *d_dists, hipStream_t st)
+                      float *d_dists, hipStream_t st, const DensePqRows *pq)
 try {
     const DenseEnv        env = dense_env();
     ExactKnnPlan          plan;
     std::vector<uint32_t> certified, refused;
     if(plan_exact_knn(mcode, chunks, (int64_t)nb, (int64_t)nq, (int64_t)k, env.native, env.fused, plan) != nullptr) return false;
-    if(!exact_knn_certified(plan, env.native, d_base, nullptr, d_q, d_slots, d_dists, st, certified, refused)) return false;
+    if(!exact_knn_certified(plan, env.native, d_base, nullptr, d_q, d_slots, d_dists, st, certified, refused, pq)) return false;
     g_knn_queries += nq;
     g_knn_certified += nq - refused.size();
     g_knn_fallback += refused.size();
-    return refused.empty() || exact_knn_fallback(mcode, chunks, d_base, nb, d_q, k, refused, d_slots, d_dists, st);
+    return refused.empty() || exact_knn_fallback(mcode, chunks, d_base, nb, d_q, k, refused, d_slots, d_dists, st, pq);
 }
 LANTERN_ABI_CATCH(nullptr)
+
+// ---- lantern_gpu_exact_search on a compact pq index --------------------------------------------------------------------------------
+const char *plan_exact_compact(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, bool on, bool compact, uint32_t pqd_inv, uint32_t pq_S16,
+                               int fused, ExactCompactPlan &p)
+{
+    p = ExactCompactPlan();
+    if(mcode < 0 || mcode > 0x7FFFFFFF || chunks <= 0 || chunks > (int64_t)1 << 20 || nb < 0 || nb > 0xFFFFFFFFll || (compact && (pq_S16 == 0 || pq_S16 % 16 != 0)))
+        return kBadPlan;
+    // the order of the reasons is the order the call meets them in: the switch, the index's form, its rows, its metric
+    if(!on) p.why = kExactCompactOff;
+    else if(!compact) p.why = kExactCompactExpanded;
+    else if(pqd_inv == 0) p.why = kExactCompactNoDecode;
+    else if(mcode != M_L2SQ && mcode != M_COS) p.why = kExactCompactMetric;
+    else p.why = kExactCompactTaken;
+    if(p.why != kExactCompactTaken) {
+        if(compact) p.expand_bytes = (size_t)std::max<int64_t>(nb, 1) * (size_t)chunks * 16;  // pq_expand_locked's block
+        return nullptr;
+    }
+    p.mcode = (int)mcode + M_PQD;
+    if(const char *why = plan_exact_knn(p.mcode, chunks, nb, nq, k, -1, fused, p.knn)) return why;
+    p.run_bytes = p.knn.aux_bytes + p.knn.dd_bytes + p.knn.cand_bytes + p.knn.fq_bytes + p.knn.fb_bytes + p.knn.gb_bytes;  // (the last three: 0)
+    p.fallback_bytes = (size_t)p.knn.chunk_rows * p.knn.chunks * 16;
+    return nullptr;
+}
 
 }  // namespace lgpu
 
@@ -685,6 +726,27 @@ catch(...) {
     return kAbiException;
 }
 
+const char *lantern_gpu_plan_exact_compact(const int64_t in[ 10 ], uint32_t out[ 10 ])
+try {
+    if(!in || !out) return "lantern_gpu: null plan array";
+    if(in[ 7 ] < 0 || in[ 7 ] > 0xFFFFFFFFll || in[ 8 ] < 0 || in[ 8 ] > 0xFFFFFFFFll) return kBadPlan;
+    ExactCompactPlan p;
+    if(const char *why = plan_exact_compact(in[ 0 ], in[ 1 ], in[ 2 ], in[ 3 ], in[ 4 ], in[ 5 ] != 0, in[ 6 ] != 0, (uint32_t)in[ 7 ], (uint32_t)in[ 8 ],
+                                            in[ 9 ] < 0 ? -1 : in[ 9 ] != 0, p))
+        return why;
+    const bool     taken = p.why == kExactCompactTaken;
+    const uint64_t sizes[ 3 ] = { p.run_bytes, p.fallback_bytes, p.expand_bytes };
+    out[ 0 ] = taken ? 1u : 0u;
+    out[ 1 ] = (uint32_t)p.why;
+    out[ 2 ] = (uint32_t)p.knn.kind;
+    out[ 3 ] = (uint32_t)p.mcode;
+    for(int i = 0; i < 3; ++i) { out[ 4 + 2 * i ] = (uint32_t)sizes[ i ]; out[ 5 + 2 * i ] = (uint32_t)(sizes[ i ] >> 32); }
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
+
 void lantern_gpu_dense_kind_stats(uint64_t launches[ 3 ])
 {
     if(!launches) return;
@@ -734,6 +796,36 @@ LANTERN_ABI_CATCH(nullptr)
 
 // ---- the exact k-NN's entry points ----------------------------------------------------------------------------------------------------
 
+// lantern_gpu_exact_compact's value for the index as it stands (ix->mu held): 0 the switch is off, 1 the call runs on stored rows (a
+// compact index is expanded for it), 2 it runs on the code rows -- plan_exact_compact's decision
+static int exact_compact_state(const Index *ix)
+{
+    ExactCompactPlan p;
+    if(plan_exact_compact(ix->mcode, ix->chunks, 0, 0, 1, ix->exact_compact, ix->pq_compact, ix->pqd_inv, ix->pq_S16, -1, p) != nullptr) return ix->exact_compact ? 1 : 0;
+    return p.why == kExactCompactOff ? 0 : p.why == kExactCompactTaken ? 2 : 1;
+}
+
+void lantern_gpu_set_exact_compact(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) { FAIL(e, "lantern_gpu: exact_compact must be 0 (a compact pq index is expanded) or 1 (answered from its code rows)"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->exact_compact = on != 0;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_exact_compact(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    return exact_compact_state(ix);
+}
+LANTERN_ABI_CATCH(e)
+
 void lantern_gpu_exact_search(usearch_index_t h, const void *queries, size_t nq, size_t k, uint32_t *slots, float *distances,
                               usearch_error_t *e)
 try {
@@ -742,7 +834,11 @@ try {
     if(!ix || nq == 0 || k == 0) return;
     if(k > 240) { FAIL(e, "lantern_gpu: exact_search supports k <= 240"); return; }
     std::lock_guard<std::mutex> g(ix->mu);
-    if(!flush_locked(ix) || !pq_expand_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    // a compact pq index under lantern_gpu_set_exact_compact answers from its code rows and stays compact; every other one gets its rows back first
+    const bool on_codes = exact_compact_state(ix) == 2;
+    if(!on_codes && !pq_expand_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
+    const DensePqRows pq = { (const uint4 *)ix->d_centers, ix->pq_subdim / 4, ix->pq_C, ix->pqd_inv, ix->pq_S16 };
     const size_t n = ix->n, row_words = (size_t)ix->chunks * 4;
     if(n == 0) {
         for(size_t i = 0; i < nq * k; ++i) { slots[ i ] = EMPTY; distances[ i ] = INFINITY; }
@@ -759,7 +855,8 @@ try {
     float    *d_dists = (float *)(d_slots + nq * k);
     hipStream_t st = ix->stream;
     bool ok = hipMemcpyAsync(dq, padded.data(), nq * row_words * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    ok = ok && exact_knn_device(ix->mcode, ix->chunks, ix->d_vec, n, dq, nq, k, d_slots, d_dists, st);
+    if(on_codes) ok = ok && exact_knn_device(ix->mcode + M_PQD, ix->chunks, (const uint4 *)ix->d_codes16, n, dq, nq, k, d_slots, d_dists, st, &pq);
+    else ok = ok && exact_knn_device(ix->mcode, ix->chunks, ix->d_vec, n, dq, nq, k, d_slots, d_dists, st);
     ok = ok && hipMemcpy(slots, d_slots, nq * k * 4, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(distances, d_dists, nq * k * 4, hipMemcpyDeviceToHost) == hipSuccess;
     if(!ok) FAIL(e, "lantern_gpu: HIP failure in exact_search");

@@ -31,7 +31,7 @@ struct ExactKnnPlan
     uint32_t chunks = 0, k = 0;
     size_t   nb = 0, nq = 0;
     // the operands (lantern_gpu_plan_dense projects these)
-    int      kind = 0;            // DenseOperands::kind: 0 f32 (or bit) rows, 1 / 2 f16 / i8 rows as stored
+    int      kind = 0;            // DenseOperands::kind: 0 f32 (or bit) rows, 1 / 2 f16 / i8 rows as stored, kDensePq (4) the code rows of a compact pq index (mcode M_*_PQD)
     int      copy = 0;            // the rows are dequantised to f32 for the contraction: 0 no, 1 from f16, 2 from i8
     uint32_t fchunks = 0;         // 16-byte chunks of a row as the contraction reads it
     bool     bits = false;        // a popcount metric: no MFMA contraction, no norms, never fused
@@ -127,7 +127,32 @@ bool filtered_each_dense_device(const EachDensePlan &p, const uint4 *d_base, con
 
 // Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row).
 // Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].
+// pq (mcode M_L2SQ_PQD / M_COS_PQD): d_base is the CODE rows of a compact pq index, pq->row_bytes each, and `chunks` those of a decoded
+// row; nothing of nb x chunks x 16 bytes is allocated (lantern_gpu_set_exact_compact).
+struct DensePqRows;
 bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k, uint32_t *d_slots,
-                      float *d_dists, hipStream_t st);
+                      float *d_dists, hipStream_t st, const DensePqRows *pq = nullptr);
+
+// lantern_gpu_exact_search on a compact pq index (DESIGN.md 4.5 "Compact pq indexes"): does the call run on the code rows, and if not
+// why.  lantern_gpu_plan_exact_compact shows it without a device; the entry point and lantern_gpu_exact_compact decide through it.
+enum ExactCompactWhy : uint32_t
+{
+    kExactCompactTaken = 0,
+    kExactCompactOff,        // lantern_gpu_set_exact_compact is 0
+    kExactCompactExpanded,   // the index is not compact: stored rows, as ever
+    kExactCompactNoDecode,   // subvectors that are not whole 16-byte chunks (pqd_inv == 0): the call expands the index
+    kExactCompactMetric      // not l2sq / cos over f32 rows
+};
+struct ExactCompactPlan
+{
+    ExactCompactWhy why = kExactCompactOff;
+    int             mcode = 0;           // taken: the decoding metric code the run is planned with
+    ExactKnnPlan    knn;                 // taken: the run
+    size_t          run_bytes = 0;       // taken: every device byte the certified run allocates (aux + dd + cand)
+    size_t          fallback_bytes = 0;  // taken: one decoded chunk of base rows, allocated only if the certificate refuses a query
+    size_t          expand_bytes = 0;    // not taken on a compact index: the f32 row block the call decodes into (nb rows)
+};
+const char *plan_exact_compact(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, bool on, bool compact, uint32_t pqd_inv, uint32_t pq_S16,
+                               int fused, ExactCompactPlan &p);
 
 }  // namespace lgpu

@@ -1,5 +1,6 @@
 // dense_tile.hpp -- what the two dense contractions share: the output tile, the fused epilogue's argument block and the
-// persistent grid.  bruteforce.hip (k_dense_f32: f32 rows) and dense_native.hip (k_dense_native: f16 / i8 rows) include it.
+// persistent grid.  bruteforce.hip (k_dense_f32: f32 rows), dense_native.hip (k_dense_native: f16 / i8 rows) and dense_pq.hip
+// (k_dense_pq: the code rows of a compact pq index) include it.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -26,6 +27,25 @@ struct DenseTopk
 
 constexpr int DENSE_WGS_PER_CU = 2;  // 67 KB of LDS each
 
+// the metric epilogue of one output of the f32 contractions, from the dot product and the tile's norm words (Ns): l2sq --
+// |q|^2 + |b|^2 - 2 q.b, clamped at 0; cos -- the norms hold 1 / sqrt(|x|^2) (dense_inv_norm; 0 stays 0) and the reference's zero-norm
+// rules test for that.  k_dense_pq (dense_pq.hip) calls these; k_dense_f32 keeps the copy it was measured with (the same expressions).
+template <bool L2SQ> __device__ __forceinline__ float dense_tile_norm(float n2)
+{
+    if(L2SQ) return n2;
+    return n2 == 0.f ? 0.f : 1.f / __builtin_sqrtf(n2);
+}
+template <bool L2SQ> __device__ __forceinline__ float dense_tile_dist(float dot, float nq2, float nb2)
+{
+    if(L2SQ) {
+        const float d = nq2 + nb2 - 2.f * dot;
+        return d < 0.f ? 0.f : d;
+    }
+    if(nq2 == 0.f && nb2 == 0.f) return 0.f;
+    if(nq2 == 0.f || nb2 == 0.f) return 1.f;
+    return 1.f - dot * (nq2 * nb2);
+}
+
 // persistent grid of the contractions: DENSE_WGS_PER_CU workgroups per CU of the current device (fewer if there are fewer tiles)
 uint32_t dense_grid(uint32_t tiles);
 
@@ -33,5 +53,11 @@ uint32_t dense_grid(uint32_t tiles);
 struct DenseOperands;
 hipError_t launch_contraction_native(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream);
 hipError_t launch_norms_native(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, uint32_t *out, hipStream_t stream);
+// dense_pq.hip's: the code rows of a compact pq index (kind kDensePq; o.pq / pq say how a row decodes)
+struct DensePqRows;
+hipError_t launch_contraction_pq(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream);
+hipError_t launch_norms_pq(const DensePqRows &pq, const uint4 *rows, uint32_t n, uint32_t chunks, float *out, hipStream_t stream);
+hipError_t launch_rerank_pq(int metric, const DensePqRows &pq, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
+                            uint32_t k, uint32_t *out_slots, float *out_dists, hipStream_t stream);
 
 }  // namespace lgpu

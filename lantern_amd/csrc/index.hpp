@@ -241,6 +241,7 @@ struct Index
     size_t   filter_dense_each_min = 0;  // lantern_gpu_set_filter_dense_each: 0 off; m > 0: in a per-query-filter call, m exact-path queries behind one filter handle take the dense route
     uint32_t last_each_dense[ 6 ] = {};  // lantern_gpu_last_filtered_each_dense: dense groups, their queries, certified, recomputed, rows gathered, contraction steps
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
+    bool     exact_compact = false;     // lantern_gpu_set_exact_compact: lantern_gpu_exact_search answers a compact pq index from its code rows (default: it expands)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches

@@ -314,6 +314,16 @@ hipError_t launch_dequant_i8(const uint4 *src, size_t nchunks, uint4 *dst, hipSt
 // f32 |x|^2; i8 -- the exact int32 sum of squares (l2sq) or the bits of its IEEE root (cos).  The i8 outputs are the pair kernel's
 // distances bit for bit.  Refused with hipErrorInvalidValue: another kind, a metric the kind has no kernel for, a Hamming row over
 // 16384 words.
+// kind kDensePq -- B is the CODE rows of a compact pq index (pq.row_bytes each, nb of them) and `chunks` the chunks of a DECODED row:
+// k_dense_pq (dense_pq.hip) builds its B tiles from the centroid tables, chunk for chunk what PqdRow (device_common.hpp) returns, so
+// the matrix is k_dense_f32's over the decoded rows, bit for bit.  Q, qn, bn: as kind 0 (bn by launch_norms with the same pq).
+constexpr int kDensePq = 4;  // (3 is row_norms.hpp's kNormNone)
+struct DensePqRows
+{
+    const uint4 *centers;    // [S][C][cps] Index::d_centers
+    uint32_t     cps, C, inv;  // View::pq_cps, pq_C, pq_inv
+    uint32_t     row_bytes;  // View::pq_row_bytes
+};
 struct DenseOperands
 {
     int          kind, metric;
@@ -322,19 +332,24 @@ struct DenseOperands
     const uint4 *B;
     uint32_t     nb, chunks;
     const void  *qn, *bn;
+    DensePqRows  pq = {};  // kind kDensePq only
 };
 struct DenseTopk;  // dense_tile.hpp
 // topk == NULL: the matrix goes to out (leading dimension ldo).  Otherwise out and ldo are unused: the tile epilogue appends what can
 // still enter a query's running top-kk to the candidate lists of *topk (l2sq / cos only)
 hipError_t launch_contraction(const DenseOperands &o, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream);
-hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream);
+// pq: kind kDensePq only -- rows are code rows, chunks those of a decoded row; the words are launch_norms(0, ..)'s over the decoded rows
+hipError_t launch_norms(int kind, int metric, const uint4 *rows, uint32_t n, uint32_t chunks, void *out, hipStream_t stream, const DensePqRows *pq = nullptr);
 hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, const uint64_t *cand, uint32_t *cnt, uint32_t cap, uint32_t *overflow,
                                     hipStream_t stream);
 hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t ncols, uint32_t c_base, uint64_t *best, uint32_t kk,
                          hipStream_t stream);
-// list: NULL, or the ascending slot list the keys' low words are positions in (k_rerank)
+// list: NULL, or the ascending slot list the keys' low words are positions in (k_rerank).  pq (metric M_*_PQD, list NULL): B is code
+// rows, decoded on the fly (k_rerank_pq, dense_pq.hip)
 hipError_t launch_rerank(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
-                         uint32_t k, uint32_t *out_slots, float *out_dists, const uint32_t *list, hipStream_t stream);
+                         uint32_t k, uint32_t *out_slots, float *out_dists, const uint32_t *list, hipStream_t stream, const DensePqRows *pq = nullptr);
+// code rows [0, n) decoded into dst[n][chunks] (the exact-order fallback of a compact pq index: k_pairs then runs on f32 rows)
+hipError_t launch_pq_decode_rows(const DensePqRows &pq, const uint4 *rows, uint32_t n, uint32_t chunks, uint4 *dst, hipStream_t stream);
 // rows list[0..n) of src into the contiguous dst with their norm words, as launch_norms(kind, metric, dst, ...) would write them,
 // in one pass (k_gather_rows_norms).  kind 3: no norms (bit rows, rows dequantised before the contraction), norms may be NULL
 hipError_t launch_gather_rows_norms(int kind, int metric, const uint4 *src, uint32_t chunks, const uint32_t *list, uint32_t n, uint4 *dst, void *norms,
