@@ -18,7 +18,7 @@ OUT_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 LIB = os.path.join(OUT_DIR, "liblantern_gpu.so")
 
-SOURCES = ["search_kernel.hip", "search_spec_kernel.hip", "search_adc_kernel.hip", "search_filtered_kernel.hip", "search_filtered_pq_kernel.hip", "search_each_kernel.hip", "search_each_spec_kernel.hip", "filter.hip", "filter_ops.hip", "insert_kernel.hip", "insert_spec_kernel.hip", "kernels.hip", "screen_probe_kernel.hip", "bruteforce.hip", "dense_native.hip", "dense_pq.hip", "grouping.hip", "unlink.hip", "compact.hip", "index.cpp", "dense.cpp", "insert_batch.cpp", "search_plan.cpp", "comm.cpp", "usearch_file.cpp", "scan_shim.cpp", "index_server.cpp", "scan_server.cpp", "mirror_cache.cpp", "node_tape.cpp"]
+SOURCES = ["search_kernel.hip", "search_spec_kernel.hip", "search_adc_kernel.hip", "search_filtered_kernel.hip", "search_filtered_pq_kernel.hip", "search_each_kernel.hip", "search_each_spec_kernel.hip", "filter.hip", "filtered_plan.cpp", "filtered_search.cpp", "filtered_dense.hip", "filter_ops.hip", "insert_kernel.hip", "insert_spec_kernel.hip", "kernels.hip", "screen_probe_kernel.hip", "bruteforce.hip", "dense_native.hip", "dense_pq.hip", "grouping.hip", "unlink.hip", "compact.hip", "index.cpp", "dense.cpp", "insert_batch.cpp", "search_plan.cpp", "comm.cpp", "usearch_file.cpp", "scan_shim.cpp", "index_server.cpp", "scan_server.cpp", "mirror_cache.cpp", "node_tape.cpp"]
 # every header under csrc/ is a dependency of every object (globbed, so a new header cannot be forgotten)
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + ["../../include/lantern_gpu.h"]
 # -ffp-contract=off: every fma in the kernels is explicit, so the reduction tree is exactly the
@@ -26,7 +26,8 @@ HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + ["../../in
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-x", "hip"]
 # per source, behind FLAGS.  dense_pq.hip: no packed-f32 VALU instructions -- the two scalar IEEE operations they stand for give the same bits
-EXTRA_FLAGS = {"dense_pq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"dense_pq.hip": NO_PACKED_F32, "filtered_dense.hip": NO_PACKED_F32}  # (filtered_dense.hip: its kernels copy floats, no arithmetic)
 
 
 def _hipcc() -> str:

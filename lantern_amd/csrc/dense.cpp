@@ -383,7 +383,7 @@ static bool exact_knn_certified(const ExactKnnPlan &first, int native, const uin
     return true;
 }
 
-// ---- the filtered exact path's dense route (filter.hip filtered_search_locked branches on this plan) ----------------------------------
+// ---- the filtered exact path's dense route (filtered_search.cpp filtered_search_locked branches on this plan) ----------------------------------
 const char *plan_filtered_dense(int64_t mcode, int64_t chunks, int64_t allowed, int64_t nq, int64_t k, int64_t skip, int64_t min_queries, bool exact,
                                 bool compact, int native, int fused, FilteredDensePlan &p)
 {

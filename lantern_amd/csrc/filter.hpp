@@ -1,6 +1,6 @@
 // filter.hpp -- filtered k-NN search: the allow-set over the slots of one index and the two kernels that honour it
-// (search_filtered_kernel.hip: the filtered graph walk and the exact pass over the allowed rows; filter.hip: building a filter and
-// the entry points).  Semantics: include/lantern_gpu.h "Filtered search" and DESIGN.md 4.9.
+// (search_filtered_kernel.hip: the filtered graph walk and the exact pass over the allowed rows; filter.hip: building a filter;
+// filtered_plan.cpp: the plan of a call; filtered_search.cpp: its launches and the entry points).  Semantics: include/lantern_gpu.h "Filtered search" and DESIGN.md 4.9.
 #pragma once
 #include <cstddef>
 #include <cstdint>

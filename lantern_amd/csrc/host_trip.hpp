@@ -1,6 +1,6 @@
 // host_trip.hpp -- the three trips a batched search takes through the host, each written once (index.hpp "HostBatch").
 //
-// An entry point (lantern_gpu_search_batch*: index.cpp, filter.hip) refuses what it refuses, looks its handles up and makes ONE of
+// An entry point (lantern_gpu_search_batch*: index.cpp, filtered_search.cpp) refuses what it refuses, looks its handles up and makes ONE of
 // these calls with its launch as a callable: `bool(const HostBatch &b)` for the two host trips -- it reads b.d_q, b.out(b.d_out),
 // b.stream and b.h_extra() -- and `bool()` for the device trip; false -> ix->err.  `failed` is the error text of a HIP failure that
 // left nothing more specific in ix->err.

@@ -231,7 +231,7 @@ struct Index
     // ---- counters ----------------------------------------------------------------------------------
     uint64_t c_search_queries = 0, c_add_vectors = 0, c_add_batches = 0;
 
-    // ---- filtered search (filter.hip): the path policy (lantern_gpu_set_filter_policy) and which path each launch took
+    // ---- filtered search (filtered_search.cpp): the path policy (lantern_gpu_set_filter_policy) and which path each launch took
     int      filter_path = 0;           // 0 auto, 1 walk, 2 exact
     size_t   filter_cand_cap = 0;       // 0: max(4 expansion, 256), capped by LDS
     double   filter_exact_factor = 5.6;  // auto: exact iff allowed^2 <= factor * ef * n; the measured crossover
@@ -468,7 +468,7 @@ bool   deserialize(Index *ix, const char *buf, size_t len);
 
 }  // namespace lgpu
 
-// one scan's share of the streaming contract (lantern_gpu_cursor_*: index.cpp, filter.hip)
+// one scan's share of the streaming contract (lantern_gpu_cursor_*: index.cpp, filtered_search.cpp)
 struct lantern_gpu_cursor
 {
     lgpu::Index *ix;

@@ -15,7 +15,7 @@ size_t filtered_exact_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_
 hipError_t launch_search_filtered(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream)
 {
     const size_t lds = filtered_walk_lds_bytes(a.view.chunks, a.exp, a.cand_cap, a.view.M0, a.frame.vis_slots);
-    if((a.seeds || a.qparams) && !a.descs) return hipErrorInvalidValue;  // the seeded walk and the per-query parameters exist in the per-query form only (filter.hip builds the table)
+    if((a.seeds || a.qparams) && !a.descs) return hipErrorInvalidValue;  // the seeded walk and the per-query parameters exist in the per-query form only (filtered_search.cpp builds the table)
     LGPU_DISPATCH(metric, a.view.chunks, LGPU_FILTERED_WALK_FORMS);
     return hipGetLastError();
 }

@@ -5,7 +5,7 @@ tests/test_gpu_env_switches.py runs it once with the default environment and onc
 The filtered leg: a selective walk (10 % allowed), the exact path, and the same walk with two workgroups serving the whole batch, so that
 LANTERN_GPU_VIS_UNDO = 0 / 16 runs the filtered walk's clear-at-the-end path with a next walk behind it in the same bitmap, and
 LANTERN_GPU_TICKETS / WAVES_PER_CU reach the filtered kernels' hand-out and grid.  LANTERN_GPU_VIS_SLOTS does NOT reach the filtered walk
-(filter.hip sizes its LDS visited set from the launch's LDS alone), so those switches are result-neutral there by construction; the
+(filtered_plan.cpp sizes its LDS visited set from the launch's LDS alone), so those switches are result-neutral there by construction; the
 bitmap-only filtered walk is entered through the candidate cap instead (tests/test_gpu_filtered_regimes.py)."""
 import hashlib
 import json

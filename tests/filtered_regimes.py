@@ -19,7 +19,7 @@ from lantern_amd import synth
 from tests import filtered_walk_ref as ref
 
 UNDO_WORDS = 8192  # device_common.hpp kVisUndoWords
-VIS_SLOTS = 2048   # filter.hip filtered_search_locked: the LDS visited set of a walk that fits its LDS target
+VIS_SLOTS = 2048   # filtered_plan.cpp walk_carve: the LDS visited set of a walk that fits its LDS target
 N, DIM, M, EFC, EF, K, NQ = 30000, 64, 16, 64, 64, 10, 48
 BITMAP_ONLY_CAP = 4096  # a candidate cap whose `next` list alone (64 KiB) pushes the LDS visited set out: vis_slots == 0
 PLAIN_EF = 400          # an unfiltered search that visits more rows than its own LDS set holds (it reads the bitmap too)

@@ -164,6 +164,41 @@ def test_a_query_over_the_budget_refuses_the_call_and_is_named():
     assert why == WALK_TEXT + " (params[2])"
 
 
+def test_parameters_past_32_bits_are_refused_not_wrapped():
+    """The expansion and k + skip are clamped to 2^20 keys -- far past the budget -- before they are narrowed to the 32 bits of a launch's
+    fields: 2^32 + 1 is refused as what it is, never planned as the 1 it would wrap to.  (A parameter row holds 32-bit words, so the
+    sums are what passes 32 bits here; the uniform calls, whose k, ef and skip are size_t, go through the same clamp.)"""
+    top = 2**32 - 1
+    assert plan([-1], [(1, 1, 0)])[2] is None and plan([30], [(1, 0, 0)], path=2)[2] is None  # what the wrapped values would ask for
+    _, _, why = plan([-1], [(1, top, 0)])  # ef alone
+    assert why == WALK_TEXT + " (params[0])"
+    _, _, why = plan([-1], [(2, 1, top)])  # k + skip = 2^32 + 1 on the walk path: the expansion
+    assert why == WALK_TEXT + " (params[0])"
+    _, _, why = plan([30], [(2, 0, top)], path=2)  # k + skip = 2^32 + 1 on the forced exact path
+    assert why == EXACT_TEXT + " (params[0])"
+    _, _, why = plan([30], [(top, 0, 2)], path=2)
+    assert why == EXACT_TEXT + " (params[0])"
+    # the clamp itself is refused on both paths, and is the least it could be: 2^20 keys of 8 bytes are 8 MiB
+    assert plan([-1], [(1, 2**20, 0)])[2] == WALK_TEXT + " (params[0])"
+    assert plan([30], [(2**20, 0, 0)], path=2)[2] == EXACT_TEXT + " (params[0])"
+
+
+def test_a_plan_of_riders_alone_launches_nothing_whatever_they_ask_for():
+    """The rider rule through the plan: no query in either launch, no carve, every position 0 -- and the riders of a batch that does launch
+    stand behind the exact list, or behind the walk list when nothing is exact."""
+    for counts, params in (([0, 0], [(5, 64, 2)] * 2), ([0, -1, 700], [(5, 64, 2), (0, 64, 2), (0, 0, 0)]), ([0], [(2**32 - 1, 2**32 - 1, 2**32 - 1)])):
+        per, launch, why = plan(counts, params)
+        assert why is None
+        assert all(q == {"path": 0, "expansion": 0, "cand_cap": 0, "position": 0} for q in per)
+        assert launch["walk"] == dict.fromkeys(launch["walk"], 0) and launch["exact"] == dict.fromkeys(launch["exact"], 0)
+    per, launch, _ = plan([0, 30, 0, -1], [(5, 64, 2)] * 4)
+    assert [q["path"] for q in per] == [0, 2, 0, 1] and [q["position"] for q in per] == [1, 0, 2, 0]
+    assert (launch["walk"]["queries"], launch["exact"]["queries"]) == (1, 3)
+    per, launch, _ = plan([0, 30, 0, -1], [(5, 64, 2)] * 4, path=1)
+    assert [q["path"] for q in per] == [0, 1, 0, 1] and [q["position"] for q in per] == [2, 0, 3, 1]
+    assert (launch["walk"]["queries"], launch["exact"]["queries"]) == (4, 0)
+
+
 def walk_base_formula(b0, e):
     """B(e) = B(0) + 2 ceil16(8 e): the header's formula, B(0) read off the function."""
     return b0 + 2 * ((8 * e + 15) // 16 * 16)

@@ -349,7 +349,7 @@ def test_filtered_search_on_wide_halves(capi, oracle, metric, d):
     gpu, g, dist, queries = instance(capi, oracle, "f16", metric, d, M, None, n, nq, ef)
     dev = EachDev(gpu, queries, k)
     u = np.random.default_rng(7).random(n)
-    # the rule (filter.hip): exact iff allowed^2 <= 5.6 ef n, i.e. up to 598 allowed rows here
+    # the rule (filtered_plan.cpp): exact iff allowed^2 <= 5.6 ef n, i.e. up to 598 allowed rows here
     sets = [u < 0.8, u < 0.1, None]
     assert sets[0].sum() ** 2 > 5.6 * ef * n >= sets[1].sum() ** 2 and sets[1].sum() > k
     filt = [None if a is None else gpu.filter_from_bitmap(a) for a in sets]

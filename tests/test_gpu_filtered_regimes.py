@@ -19,7 +19,7 @@ from tests.test_gpu_filtered_search import Dev, rows, same
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT_CAP = 256  # filter.hip: max(4 expansion, 256) at ef = 64
+DEFAULT_CAP = 256  # filtered_plan.cpp: max(4 expansion, 256) at ef = 64
 
 
 @pytest.fixture(scope="module")

@@ -144,7 +144,7 @@ def test_filtered_search_and_the_file_at_the_cap(capi, oracle, monkeypatch, fami
     dist = ref.distance_matrix(oracle, rows, queries, "hamming", oracle.SUM_WAVE64)
     u = np.random.default_rng(7).random(N)
     wide, narrow = u < 0.8, u < 0.1
-    # the rule (filter.hip): exact iff allowed^2 <= 5.6 ef n, i.e. up to 259 allowed rows here
+    # the rule (filtered_plan.cpp): exact iff allowed^2 <= 5.6 ef n, i.e. up to 259 allowed rows here
     assert wide.sum() ** 2 > 5.6 * EF * N >= narrow.sum() ** 2 and narrow.sum() > K + 3
     dev = Dev(gpu, queries, K)
     try:
