@@ -852,11 +852,38 @@ LANTERN_GPU_EXPORT void lantern_gpu_export_codes(usearch_index_t, uint8_t *codes
  * distance computation over the code bytes: a per-query table of partial sums (subvector x centroid) in LDS, num_subvectors
  * table entries added per row (lantern_amd/csrc/search_adc_kernel.hip; summation order defined there and restated by the
  * oracle -- distances agree with the decoded-row path to 1e-5 relative, not bit for bit: PARITY UNPINNED BY THE REFERENCE).
- * Anything that needs rows again (usearch_add, an export with vectors; the exact search unless lantern_gpu_set_exact_compact lets it
- * run on the code rows) decodes them back first, as does lantern_gpu_pq_expand.  LANTERN_GPU_PQ_COMPACT=1 compacts a pq index right after it is loaded or mirrored. */
+ * Anything that needs rows again (an export with vectors; usearch_add unless lantern_gpu_set_add_compact, and the exact search unless
+ * lantern_gpu_set_exact_compact, lets it run on the code rows) decodes them back first, as does lantern_gpu_pq_expand.
+ * LANTERN_GPU_PQ_COMPACT=1 compacts a pq index right after it is loaded or mirrored. */
 LANTERN_GPU_EXPORT void lantern_gpu_pq_compact(usearch_index_t, usearch_error_t *);
 LANTERN_GPU_EXPORT void lantern_gpu_pq_expand(usearch_index_t, usearch_error_t *);
-/* HBM held by the index: the vector block (the code rows of a compact pq index) | adjacency, labels, levels, norms, codes */
+/* ADDING TO A COMPACT PQ INDEX (DESIGN.md 4.7 "Compact pq indexes: adding").  on = 0, THE DEFAULT: usearch_add, lantern_gpu_add_many,
+ * lantern_gpu_add_with_level and usearch_reserve on a compact pq index decode every row back first (capacity x dimensions f32) and leave
+ * the index expanded.  on = 1: a compact index whose rows can be decoded on the fly (subvectors of whole 16-byte chunks, l2sq / cos)
+ * takes them FROM ITS CODE ROWS and stays compact: the caller's rows are quantised through a staging block of at most 65536 rows, the
+ * insertion kernels decode the stored rows they evaluate (the arithmetic of the expanded index, bit for bit), the code rows grow with
+ * the capacity, and no block of capacity x row bytes is allocated.  Codes, graph, searches and a later lantern_gpu_pq_expand are those
+ * of the same adds on the expanded index.  Collective adds (lantern_gpu_add_sharded, _add_row_sharded), page-attached mirrors
+ * (usearch_add_external) and indexes whose rows cannot be decoded on the fly expand as with 0.  on other than 0 or 1 is refused. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_add_compact(usearch_index_t, int on, usearch_error_t *);
+/* diagnostic: 0 the switch is off; 1 it is on but the next add would still expand the index (or the index is not compact); 2 the next
+ * add is served from the code rows */
+LANTERN_GPU_EXPORT int lantern_gpu_add_compact(usearch_index_t, usearch_error_t *);
+/* The decision above without a device (a pure function; adds and reserves decide through it).
+ * in[16]: [0] the index's metric code  [1] 16-byte chunks of a DECODED row  [2] level-0 list length (2 x connectivity)
+ *         [3] ef_construction  [4] rows of the call (0: a reserve)  [5] the index's capacity  [6] compute units  [7] waves of the insertion
+ *         walk  [8] the switch  [9] the index is compact  [10] its decode-on-the-fly inverse (0: subvectors are not whole chunks)
+ *         [11] bytes of a code row in device memory  [12] a collective add  [13] a page-attached mirror  [14] LANTERN_GPU_LDS_LIST  [15] 0
+ * out[12]: [0] 1: served from the code rows  [1] why not: 0 it is, 1 the switch is off, 2 the index is not compact, 3 its rows cannot
+ *          be decoded on the fly, 4 the metric, 5 a collective add, 6 a page-attached mirror, 7 no launch shape serves the
+ *          configuration  [2] the metric code of the insertion launches (the index's + 600)  [3] rows of one staging piece
+ *          [4..5] bytes of the staging block  [6..7] not served, compact: the f32 row block the call decodes the index into
+ *          [8] dynamic LDS of the k_insert launch  [9] its LDS visited-set slots  [10] keys per lane of its register list (0: the LDS
+ *          list)  [11] lanes per row.  Byte counts as (low, high) words.  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_add_compact(const int64_t in[16], uint32_t out[12]);
+/* HBM held by the index: the vector block (the code rows of a compact pq index) | adjacency, labels, levels, norms, codes.  A compact
+ * pq index: row_bytes counts the code rows IN USE, size x the code row stride; after a reserve or an add under
+ * lantern_gpu_set_add_compact the block itself holds capacity rows, zero filled beyond the size. */
 /* bytes of one stored row in device memory = the row stride of `d_queries` in lantern_gpu_search_batch_device: the vector zero padded
  * to whole 16-byte chunks, and bit rows of 65 .. 127 bytes (768 bits: quant_bits = 1 at 768 dimensions, hamming over integer[24]) to 128 --
  * one cache line per row instead of a line and a piece of the next (usearch_storage.cpp:29-31 sizes the ON-TAPE vector; this is HBM only) */

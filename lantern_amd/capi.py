@@ -97,7 +97,7 @@ EXPORTS = [
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
     "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_set_exact_compact", "lantern_gpu_exact_compact", "lantern_gpu_plan_exact_compact", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
-    "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
+    "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_set_add_compact", "lantern_gpu_add_compact", "lantern_gpu_plan_add_compact", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
     "lantern_gpu_export_codes",
@@ -251,6 +251,9 @@ def lib() -> C.CDLL:
         "lantern_gpu_set_exact_compact": (None, [vp, C.c_int, err]),
         "lantern_gpu_exact_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_exact_compact": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_set_add_compact": (None, [vp, C.c_int, err]),
+        "lantern_gpu_add_compact": (C.c_int, [vp, err]),
+        "lantern_gpu_plan_add_compact": (C.c_char_p, [vp, vp]),
         "lantern_gpu_distance_gather": (None, [vp, vp, vp, sz, vp, err]),
         "lantern_gpu_spec_profile": (None, [vp, i32, vp, err]),
         "lantern_gpu_search_unique_rows": (None, [vp, i32, C.POINTER(u64), err]),
@@ -565,6 +568,26 @@ def plan_exact_compact(mcode, chunks, nb, nq, k, on, compact, pqd_inv, code_row_
     size = lambda i: int(out[i]) | int(out[i + 1]) << 32
     return {"taken": bool(out[0]), "why": EXACT_COMPACT_WHY[int(out[1])], "kind": int(out[2]), "mcode": int(out[3]), "run_bytes": size(4),
             "fallback_bytes": size(6), "expand_bytes": size(8)}
+
+
+# lantern_gpu_plan_add_compact's out[1], by value
+ADD_COMPACT_WHY = ("served", "off", "expanded", "no_decode", "metric", "collective", "pages", "shape")
+
+
+def plan_add_compact(mcode, chunks, M0, efc, rows, cap, on, compact, pqd_inv, code_row_bytes, collective=False, pages=False, lds_list=False,
+                     num_cus=256, waves=4):
+    """lantern_gpu_plan_add_compact: whether an add of `rows` rows (0: a reserve) to a pq index is served from its code rows and leaves it
+    compact (host arithmetic, no device): {"served", "why" (ADD_COMPACT_WHY), "mcode", "stage_rows", "stage_bytes", "expand_bytes", "lds",
+    "vis_slots", "kpl", "lanes"}."""
+    pin = np.array([mcode, chunks, M0, efc, rows, cap, num_cus, waves, int(on), int(compact), pqd_inv, code_row_bytes, int(collective), int(pages),
+                    int(lds_list), 0], np.int64)
+    out = np.zeros(12, np.uint32)
+    why = lib().lantern_gpu_plan_add_compact(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    size = lambda i: int(out[i]) | int(out[i + 1]) << 32
+    return {"served": bool(out[0]), "why": ADD_COMPACT_WHY[int(out[1])], "mcode": int(out[2]), "stage_rows": int(out[3]), "stage_bytes": size(4),
+            "expand_bytes": size(6), "lds": int(out[8]), "vis_slots": int(out[9]), "kpl": int(out[10]), "lanes": int(out[11])}
 
 
 # lantern_gpu_plan_filtered_dense's out[1], by value
@@ -972,6 +995,14 @@ class GpuIndex:
     def exact_compact(self):
         """lantern_gpu_exact_compact: 0 the switch is off, 1 exact_search reads stored rows (a compact index is expanded), 2 it runs on the code rows."""
         return int(_call("lantern_gpu_exact_compact", self.h))
+
+    def set_add_compact(self, on):
+        """adds and reserves leave this index in its compact pq form, served from the code rows (1), or expand it first (0, the default)."""
+        _call("lantern_gpu_set_add_compact", self.h, int(on))
+
+    def add_compact(self):
+        """lantern_gpu_add_compact: 0 the switch is off, 1 the next add would still expand the index, 2 it is served from the code rows."""
+        return int(_call("lantern_gpu_add_compact", self.h))
 
     # ---- filtered search (lantern_gpu.h "Filtered search") ----
     def filter_from_labels(self, labels, skip_deleted=False) -> "Filter":

@@ -653,7 +653,36 @@ struct PqdRow
         const uint32_t code = codes[ sv ];
         return centers[ ((size_t)sv * C + code) * cps + off ];
     }
+    // operator[] in its two dependent halves, for the loops that fetch a block of chunks (pqd_load below)
+    __device__ __forceinline__ uint32_t code_of(int ch) const { return codes[ ((uint32_t)ch * inv) >> 16 ]; }
+    __device__ __forceinline__ uint4    chunk_of(int ch, uint32_t code) const
+    {
+        const uint32_t sv = ((uint32_t)ch * inv) >> 16, off = (uint32_t)ch - sv * cps;
+        return centers[ ((size_t)sv * C + code) * cps + off ];
+    }
 };
+// Chunks lane, lane + stride, ... (N of them; zeros beyond `chunks`) of a decoded row into registers: the N code bytes are requested
+// first, then the N table reads -- two dependent round trips for the block, not 2 N.  Which subvector and offset a chunk falls into
+// does not depend on the row: in a loop over rows that arithmetic is loop-invariant.
+template <int N> __device__ __forceinline__ void pqd_load(const PqdRow &r, int lane, int stride, int chunks, uint4 (&v)[ N ])
+{
+    uint32_t code[ N ];
+#pragma unroll
+    for(int c = 0; c < N; ++c) code[ c ] = lane + stride * c < chunks ? r.code_of(lane + stride * c) : 0u;
+#pragma unroll
+    for(int c = 0; c < N; ++c) v[ c ] = lane + stride * c < chunks ? r.chunk_of(lane + stride * c, code[ c ]) : make_uint4(0, 0, 0, 0);
+}
+// One decoded row into an LDS row by the T threads of a workgroup (chunks tid, tid + T, ...): per pass a thread's two code bytes, then
+// its two table reads
+__device__ __forceinline__ void pqd_stage(const PqdRow &r, uint4 *dst, int tid, int T, int chunks)
+{
+    for(int base = tid; base < chunks; base += 2 * T) {
+        uint4 v[ 2 ];
+        pqd_load<2>(r, base, T, chunks, v);
+        dst[ base ] = v[ 0 ];
+        if(base + T < chunks) dst[ base + T ] = v[ 1 ];
+    }
+}
 template <int METRIC> __device__ __forceinline__ auto row_of_m(const View &v, uint32_t slot)
 {
     if constexpr(METRIC >= M_PQD) return PqdRow{ (const uint8_t *)v.vec + (size_t)slot * v.pq_row_bytes, v.pq_centers, v.pq_cps, v.pq_C, v.pq_inv };

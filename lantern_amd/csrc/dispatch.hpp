@@ -31,3 +31,10 @@
         else if(metric == M_COS_PQD) LGPU_DISPATCH_G(G_, M_COS_PQD, CALL)     \
         else return hipErrorInvalidValue;                                     \
     } while(0)
+
+// the kernels that read stored rows of either form (the insertion kernels): the stored metrics, or the two decoding ones
+#define LGPU_DISPATCH_ROWS(metric, chunks, CALL)                              \
+    do {                                                                      \
+        if(mcode_is_pqd(metric)) PQD_G(metric, chunks, CALL);                 \
+        else LGPU_DISPATCH(metric, chunks, CALL);                             \
+    } while(0)

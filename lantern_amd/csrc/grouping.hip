@@ -182,6 +182,17 @@ __global__ void __launch_bounds__(256) k_pq_put(float *rows, uint32_t row_floats
     rows[ (size_t)(first + i) * row_floats + (size_t)s * subdim + j ] = codebook[ (size_t)c * dims + (size_t)s * subdim + j ];
     if(j == 0) codes[ (size_t)(first + i) * S + s ] = (uint8_t)c;
 }
+// put for a COMPACT index (lantern_gpu_set_add_compact): the code byte into both code arrays -- codes[first + i][s] at stride S, what files
+// and exports carry, and codes16[first + i][s] at the padded stride S16 the walks read -- and no decoding anywhere
+__global__ void __launch_bounds__(256) k_pq_put_codes(uint32_t first, uint32_t count, uint32_t s, uint32_t S, uint32_t S16, const uint32_t *nearest, uint8_t *codes,
+                                                      uint8_t *codes16)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= count) return;
+    const uint8_t c = (uint8_t)nearest[ i ];
+    codes[ (size_t)(first + i) * S + s ] = c;
+    codes16[ (size_t)(first + i) * S16 + s ] = c;
+}
 // decode: row(first + i) = concatenation of the centroids its codes name
 __global__ void __launch_bounds__(256) k_pq_decode(float *rows, uint32_t row_floats, uint32_t first, uint32_t count, uint32_t subdim, uint32_t S,
                                                    const float *codebook, uint32_t dims, const uint8_t *codes)
@@ -256,6 +267,14 @@ hipError_t launch_pq_put(float *rows, uint32_t row_floats, uint32_t first, uint3
     const uint64_t threads = (uint64_t)count * subdim;
     hipLaunchKernelGGL(k_pq_put, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, rows, row_floats, first, count, s, subdim, S, nearest, codebook,
                        dims, codes);
+    return hipGetLastError();
+}
+hipError_t launch_pq_put_codes(uint32_t first, uint32_t count, uint32_t s, uint32_t S, uint32_t S16, const uint32_t *nearest, uint8_t *codes, uint8_t *codes16,
+                               hipStream_t stream)
+{
+    if(count == 0) return hipSuccess;
+    if(s >= S || S > S16) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pq_put_codes, dim3((count + 255) / 256), dim3(256), 0, stream, first, count, s, S, S16, nearest, codes, codes16);
     return hipGetLastError();
 }
 hipError_t launch_pq_decode(float *rows, uint32_t row_floats, uint32_t first, uint32_t count, uint32_t subdim, uint32_t S, const float *codebook, uint32_t dims,

@@ -95,16 +95,35 @@ View Index::view() const
     v.n = (uint32_t)n;
     v.entry = entry;
     v.max_level = max_level;
+    if(pq_compact && pqd_inv) {  // a compact pq index whose rows decode on the fly (device_common.hpp PqdRow): the rows are the code rows
+        v.vec = (const uint4 *)d_codes16;
+        v.pq_centers = (const uint4 *)d_centers;
+        v.pq_cps = pq_subdim / 4;
+        v.pq_C = pq_C;
+        v.pq_inv = pqd_inv;
+        v.pq_row_bytes = pq_S16;
+    }
     return v;
 }
 
-static bool reserve_locked(Index *ix, size_t newcap)
+// keep_compact: the caller went through plan_add_compact and it serves the call -- a compact pq index grows its CODE rows and d_vec
+// stays absent.  Otherwise growing means adding: a compact pq index gets its rows back first.
+static bool reserve_locked(Index *ix, size_t newcap, bool keep_compact = false)
 {
-    if(newcap <= ix->cap) return true;
+    if(newcap <= ix->cap && !(keep_compact && ix->pq_compact && ix->codes16_cap < ix->cap)) return true;
+    newcap = std::max(newcap, ix->cap);
     if(newcap >= 0x7FFFFFFFull) { set_err(ix, "lantern_gpu: capacity above 2^31-1 slots is not supported"); return false; }
-    if(!pq_expand_locked(ix)) return false;  // growing means adding: a compact pq index gets its rows back first
+    keep_compact = keep_compact && ix->pq_compact;
+    if(!keep_compact && !pq_expand_locked(ix)) return false;
     const size_t oc = ix->cap, row = (size_t)ix->chunks * 16;
-    if(!dev_grow(ix, (void **)&ix->d_vec, oc * row, newcap * row, -1)) return false;
+    if(keep_compact) {  // (pq_compact_locked sized the code rows by n: the first compact reserve brings them up to the capacity)
+        // (codes16_cap may already exceed newcap: a reserve that grew the code rows and then failed on a later array left cap behind)
+        if(ix->codes16_cap < newcap) {
+            if(!dev_grow(ix, (void **)&ix->d_codes16, ix->codes16_cap * ix->pq_S16, newcap * ix->pq_S16, 0)) return false;  // zero: the padding the ADC table walk relies on
+            ix->codes16_cap = newcap;
+        }
+        if(newcap == oc) return true;
+    } else if(!dev_grow(ix, (void **)&ix->d_vec, oc * row, newcap * row, -1)) return false;
     if(mcode_base(ix->mcode) == M_COS && !mcode_is_i8(ix->mcode) && !dev_grow(ix, (void **)&ix->d_norm2, oc * 4, newcap * 4, -1)) return false;
     if(ix->screen) {
         const size_t srow = (size_t)screen_chunks_for(ix->chunks) * 16;
@@ -179,6 +198,39 @@ bool pq_encode_rows(Index *ix, size_t first, size_t count)
     return ok;
 }
 
+// The same quantisation for a COMPACT index (plan_add_compact served the call): `count` f32 rows of the CALLER (host memory, row_floats
+// each) become the code rows of slots [first, first + count) without passing through d_vec.  The rows are staged in a scratch block in
+// pieces of at most kAddCompactStageRows (201 MB at 768-d: the only f32 rows the call ever holds on the device); per subvector the
+// nearest centroid is found exactly as above -- launch_pq_take + exact_knn_device, first minimum under the index metric -- and
+// k_pq_put_codes writes the byte into d_codes and d_codes16.  No decoding is written.  Returns after the stream drained (the caller's
+// buffer is borrowed).
+static bool pq_encode_codes(Index *ix, const float *h_rows, size_t first, size_t count)
+{
+    const uint32_t sub_chunks = (ix->pq_subdim + 3) / 4, sub_floats = sub_chunks * 4, row_floats = ix->chunks * 4;
+    const size_t   piece = std::min(count, kAddCompactStageRows);
+    float    *d_stage = nullptr, *d_sub = nullptr;
+    uint32_t *d_near = nullptr;
+    bool ok = hipMalloc((void **)&d_stage, piece * (size_t)row_floats * 4) == hipSuccess && hipMalloc((void **)&d_sub, piece * (size_t)sub_floats * 4) == hipSuccess &&
+              hipMalloc((void **)&d_near, piece * 8) == hipSuccess;
+    if(!ok) set_err(ix, "lantern_gpu: out of device memory (staging rows for a compact pq index)");
+    for(size_t at = 0; ok && at < count; at += piece) {
+        const size_t m = std::min(piece, count - at);
+        ok = hipMemcpyAsync(d_stage, h_rows + at * row_floats, m * (size_t)row_floats * 4, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
+        for(uint32_t sv = 0; ok && sv < ix->pq_S; ++sv) {
+            ok = ok && launch_pq_take(d_stage, row_floats, 0, (uint32_t)m, sv, ix->pq_subdim, sub_floats, d_sub, ix->stream) == hipSuccess;
+            ok = ok && exact_knn_device(ix->metric, sub_chunks, (const uint4 *)(ix->d_centers + (size_t)sv * ix->pq_C * sub_floats), ix->pq_C, (const uint4 *)d_sub, m,
+                                        1, d_near, (float *)(d_near + m), ix->stream);
+            ok = ok && launch_pq_put_codes((uint32_t)(first + at), (uint32_t)m, sv, ix->pq_S, ix->pq_S16, d_near, ix->d_codes, ix->d_codes16, ix->stream) == hipSuccess;
+        }
+        ok = ok && hipStreamSynchronize(ix->stream) == hipSuccess;  // the next piece overwrites the block
+        if(!ok) set_err(ix, "lantern_gpu: HIP failure while quantising vectors");
+    }
+    if(d_stage) (void)hipFree(d_stage);
+    if(d_sub) (void)hipFree(d_sub);
+    if(d_near) (void)hipFree(d_near);
+    return ok;
+}
+
 bool pq_decode_rows(Index *ix, size_t first, size_t count)
 {
     if(!ix->pq || count == 0) return true;
@@ -188,7 +240,8 @@ bool pq_decode_rows(Index *ix, size_t first, size_t count)
 }
 
 // A pq index needs its decodings only to ADD (the walk of a new node, the selection heuristic and the re-prunes evaluate
-// stored row against stored row).  A read-mostly index -- the scan-side mirror of a built index -- drops them: num_subvectors
+// stored row against stored row) -- and not even then where lantern_gpu_set_add_compact lets the insertion kernels decode the
+// code rows they read (plan_add_compact, insert_batch.cpp).  A read-mostly index -- the scan-side mirror of a built index -- drops them: num_subvectors
 // bytes per row stay resident (10M x 768 at 96 subvectors: 0.96 GB instead of 30.7 GB) and searches evaluate rows by ADC.
 // ceil(2^16 / cps) if (chunk * that) >> 16 == chunk / cps for every chunk of a row (checked, not assumed), else 0
 static uint32_t pqd_inverse(uint32_t cps, uint32_t chunks)
@@ -221,6 +274,7 @@ bool pq_compact_locked(Index *ix)
     HIPCHK(ix, hipMemset(ix->d_codes16, 0, rows * S16));
     if(ix->n) HIPCHK(ix, hipMemcpy2D(ix->d_codes16, S16, ix->d_codes, ix->pq_S, ix->pq_S, ix->n, hipMemcpyDeviceToDevice));
     ix->pq_S16 = S16;
+    ix->codes16_cap = rows;  // (a reserve that keeps the index compact grows it to the capacity: reserve_locked)
     // rows decoded on the fly (device_common.hpp PqdRow) need subvectors of whole 16-byte chunks
     ix->pqd_inv = ix->pq_subdim % 4 == 0 && ix->pq_subdim >= 4 ? pqd_inverse(ix->pq_subdim / 4, ix->chunks) : 0;
     if(ix->d_vec) { HIPCHK(ix, hipFree(ix->d_vec)); ix->d_vec = nullptr; }
@@ -249,6 +303,7 @@ bool pq_expand_locked(Index *ix)
     }
     ix->pq_compact = false;
     if(ix->d_codes16) { (void)hipFree(ix->d_codes16); ix->d_codes16 = nullptr; }
+    ix->codes16_cap = 0;
     return true;
 }
 
@@ -490,7 +545,7 @@ struct StagedMeta
     std::vector<uint8_t>  l8;
     std::vector<uint32_t> uo;
 };
-static bool stage_meta(Index *ix, const int *levels_in, size_t count, StagedMeta &s)
+static bool stage_meta(Index *ix, const int *levels_in, size_t count, StagedMeta &s, bool keep_compact = false)
 {
     const size_t first = ix->n;
     s.lv.resize(count);
@@ -503,7 +558,9 @@ static bool stage_meta(Index *ix, const int *levels_in, size_t count, StagedMeta
         s.uo[ i ] = s.lv[ i ] > 0 ? (uint32_t)blocks : EMPTY;
         blocks += (size_t)s.lv[ i ];
     }
-    if(first + count > ix->cap && !reserve_locked(ix, std::max(ix->cap * 2, first + count))) return false;
+    if(first + count > ix->cap && !reserve_locked(ix, std::max(ix->cap * 2, first + count), keep_compact)) return false;
+    // (a compact index that stays compact: its code rows were sized by n at compaction -- room for the new slots within the capacity)
+    if(keep_compact && first + count > ix->codes16_cap && !reserve_locked(ix, ix->cap, true)) return false;
     return reserve_upper(ix, blocks);
 }
 
@@ -581,14 +638,22 @@ static size_t insert_rows(Index *ix, const uint64_t *labels, const int *levels_i
     *ok_out = true;
     if(count == 0) return 0;
     auto fail = [&]() { *ok_out = false; return (size_t)0; };
-    if(!pq_expand_locked(ix)) return fail();  // a compact pq index gets its decodings back before anything is added
+    // a compact pq index gets its decodings back before anything is added -- unless lantern_gpu_set_add_compact is on and the plan serves
+    // the call from the code rows (plan_add_compact, insert_batch.cpp): then d_vec stays absent from here to the end of the batches
+    const bool on_codes = plan_add_compact(add_compact_in(ix, count, false)).why == kAddCompactServed;
+    if(!on_codes && !pq_expand_locked(ix)) return fail();
     const size_t first = ix->n, row_words = (size_t)ix->chunks * 4;
     // ---- levels and upper-block offsets of everything, then ONE upload of rows and metadata: an unlinked
     // node is unreachable, so its row may sit in the table before its batch runs
     StagedMeta s;
-    if(!stage_meta(ix, levels_in, count, s)) return fail();
+    if(!stage_meta(ix, levels_in, count, s, on_codes)) return fail();
     bool up = true, staged = false;
-    if(raw_f32) {
+    if(on_codes) {
+        // the caller's f32 rows become code bytes through a staging block (pq_encode_codes: it drains the stream); a cosine index takes the new
+        // slots' norm words from the code rows -- k_fill_norms' chain and tree over the decoded chunks, the expanded twin's words
+        if(!pq_encode_codes(ix, (const float *)rows, first, count)) return fail();
+        if(ix->d_norm2) up = launch_fill_norms(ix->mcode + M_PQD, ix->view(), (uint32_t)first, (uint32_t)count, ix->d_norm2, ix->stream) == hipSuccess;
+    } else if(raw_f32) {
         up = upload_f32_as_stored(ix, rows, count, (uint32_t *)ix->d_vec + first * row_words);
     } else if(count <= 64 && count * (row_words * 4 + 16) <= kStageBytes && stage_buffer(ix)) {
         // a handful of rows: one kernel reads them and their metadata from the page-locked, device-mapped block (the block is next
@@ -616,8 +681,10 @@ static size_t insert_rows(Index *ix, const uint64_t *labels, const int *levels_i
     // would land the failed rows in slots the host considers free
     auto fail_staged = [&]() { if(staged) (void)hipStreamSynchronize(ix->stream); return fail(); };
     if(!up) { set_err(ix, "lantern_gpu: HIP failure uploading vectors"); return fail_staged(); }
-    if(!pq_encode_rows(ix, first, count)) return fail_staged();  // pq = true: the rows become their decodings, the codes go beside them
-    if(!rows_stored(ix, first, count)) return fail_staged();
+    if(!on_codes) {
+        if(!pq_encode_rows(ix, first, count)) return fail_staged();  // pq = true: the rows become their decodings, the codes go beside them
+        if(!rows_stored(ix, first, count)) return fail_staged();
+    }
     const size_t done = run_batches(ix, labels, s, count, nullptr, ok_out);
     if(!*ok_out && staged) (void)hipStreamSynchronize(ix->stream);
     return done;
@@ -628,7 +695,7 @@ static size_t insert_rows(Index *ix, const uint64_t *labels, const int *levels_i
 // is replicated: 1M x 1536 f32 is 6.1 GB of 288), then the batches run work-sharded (run_batch).
 bool add_sharded_locked(Index *ix, Comm *comm, const uint64_t *labels, const void *vectors, size_t n_shard, int kind_in)
 {
-    if(!flush_locked(ix)) return false;
+    if(!flush_locked(ix) || !pq_expand_locked(ix)) return false;  // (a collective add writes rows: a compact pq index expands, plan_add_compact)
     const int    W = comm->world, R = comm->rank;
     const size_t row = (size_t)ix->chunks * 16, first = ix->n;
     // ---- shard sizes; all replicas must be in the same state
@@ -1248,7 +1315,8 @@ try {
     Index *ix = H(h, e);
     if(!ix) return;
     std::lock_guard<std::mutex> g(ix->mu);
-    if(!reserve_locked(ix, capacity)) FAIL(e, ix->err.c_str());
+    // (a compact pq index under lantern_gpu_set_add_compact grows its code rows and stays compact: plan_add_compact)
+    if(!reserve_locked(ix, capacity, plan_add_compact(add_compact_in(ix, 0, false)).why == kAddCompactServed)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
 
@@ -2336,6 +2404,60 @@ try {
     if(!pq_expand_locked(ix)) FAIL(e, ix->err.c_str());
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+// Adds that leave a compact pq index compact (include/lantern_gpu.h; plan_add_compact, insert_batch.cpp)
+void lantern_gpu_set_add_compact(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) { FAIL(e, "lantern_gpu: add_compact must be 0 (an add expands a compact pq index) or 1 (it is served from the code rows)"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->add_compact = on != 0;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_add_compact(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!ix->add_compact) return 0;
+    return plan_add_compact(add_compact_in(ix, 1, false)).why == kAddCompactServed ? 2 : 1;
+}
+LANTERN_ABI_CATCH(e)
+
+const char *lantern_gpu_plan_add_compact(const int64_t in[ 16 ], uint32_t out[ 12 ])
+try {
+    if(!in || !out) return "lantern_gpu: null plan array";
+    static const char *bad = "lantern_gpu: bad plan input";
+    // metric, chunks, M0, efc, rows, capacity, CUs, waves, inverse, code row bytes: the ranges the index itself keeps
+    if(in[ 0 ] < 0 || in[ 0 ] > 0x7FFFFFFF || in[ 1 ] <= 0 || in[ 1 ] > (int64_t)1 << 20 || in[ 2 ] < 2 || in[ 2 ] > 512 || in[ 3 ] < 1 || in[ 3 ] > 0xFFFFFFFFll ||
+       in[ 4 ] < 0 || in[ 5 ] < 0 || in[ 6 ] < 1 || in[ 6 ] > 0xFFFF || in[ 7 ] < 1 || in[ 7 ] > 16 || in[ 10 ] < 0 || in[ 10 ] > 0xFFFFFFFFll ||
+       in[ 11 ] < 16 || in[ 11 ] > 128 || in[ 11 ] % 16 != 0)
+        return bad;
+    AddCompactIn s;
+    s.mcode = (int)in[ 0 ]; s.chunks = (uint32_t)in[ 1 ]; s.M0 = (uint32_t)in[ 2 ]; s.efc = (uint32_t)in[ 3 ]; s.rows = (size_t)in[ 4 ]; s.cap = (size_t)in[ 5 ];
+    s.num_cus = (int)in[ 6 ]; s.waves = (int)in[ 7 ]; s.on = in[ 8 ] != 0; s.compact = in[ 9 ] != 0; s.pqd_inv = (uint32_t)in[ 10 ]; s.pq_S16 = (uint32_t)in[ 11 ];
+    s.collective = in[ 12 ] != 0; s.pages = in[ 13 ] != 0; s.lds_list = in[ 14 ] != 0;
+    const AddCompactPlan p = plan_add_compact(s);
+    const bool     served = p.why == kAddCompactServed;
+    const uint64_t sizes[ 2 ] = { p.stage_bytes, p.expand_bytes };
+    out[ 0 ] = served ? 1u : 0u;
+    out[ 1 ] = (uint32_t)p.why;
+    out[ 2 ] = (uint32_t)p.mcode;
+    out[ 3 ] = (uint32_t)p.stage_rows;
+    for(int i = 0; i < 2; ++i) { out[ 4 + 2 * i ] = (uint32_t)sizes[ i ]; out[ 5 + 2 * i ] = (uint32_t)(sizes[ i ] >> 32); }
+    out[ 8 ] = served ? (uint32_t)p.insert.lds : 0u;
+    out[ 9 ] = served ? p.insert.vis_slots : 0u;
+    out[ 10 ] = served ? (uint32_t)insert_kpl(s.efc, s.lds_list) : 0u;  // k_insert's KPL: keys per lane of the register list, 0 the LDS list
+    out[ 11 ] = served ? (uint32_t)group_lanes_for(s.chunks) : 0u;
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
 
 // HBM held by the index: the vector block (or the code rows of a compact pq index) | everything else that grows with the
 // number of nodes (adjacency, labels, levels, norms, re-prune state, codes)

@@ -94,7 +94,8 @@ struct Index
     // ADC over the code rows (search_adc_kernel.hip); whatever needs rows again -- an insert, the exact search -- decodes
     // them back first (pq_expand_locked)
     bool     pq_compact = false;
-    uint8_t *d_codes16 = nullptr;        // [n][pq_S16]: the code rows zero padded to whole 16-byte chunks
+    uint8_t *d_codes16 = nullptr;        // [codes16_cap][pq_S16]: the code rows zero padded to whole 16-byte chunks (rows beyond n: all zero)
+    size_t   codes16_cap = 0;            // rows d_codes16 holds: n at compaction, the index's capacity once a reserve grew it compact
     uint32_t pq_S16 = 0;
     uint32_t pqd_inv = 0;                // compact form: the checked multiply-shift inverse of chunks-per-subvector (0: decode-on-the-fly not possible -> the ADC table walk)
 
@@ -242,6 +243,7 @@ struct Index
     uint32_t last_each_dense[ 6 ] = {};  // lantern_gpu_last_filtered_each_dense: dense groups, their queries, certified, recomputed, rows gathered, contraction steps
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     bool     exact_compact = false;     // lantern_gpu_set_exact_compact: lantern_gpu_exact_search answers a compact pq index from its code rows (default: it expands)
+    bool     add_compact = false;       // lantern_gpu_set_add_compact: adds and reserves leave a compact pq index compact where plan_add_compact serves them (default: they expand)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches
@@ -396,6 +398,40 @@ struct InsertPlan
     const char *refusal = nullptr;
 };
 InsertPlan plan_insert(const InsertPlanIn &in);  // pure: no HIP runtime call, no Index, no getenv, no allocation
+// ---- adds to a COMPACT pq index (lantern_gpu_set_add_compact): served from the code rows -- the batch is encoded from a
+// staging block, the insertion kernels run their M_*_PQD instantiations, the index stays compact -- or the index is expanded first, and
+// why.  Pure as plan_insert; lantern_gpu_plan_add_compact shows it without a device, insert_rows / usearch_reserve decide through it.
+enum AddCompactWhy : int
+{
+    kAddCompactServed = 0,
+    kAddCompactOff,         // lantern_gpu_set_add_compact is 0
+    kAddCompactExpanded,    // the index is not compact
+    kAddCompactNoDecode,    // pqd_inv == 0: ADC rows have no row-against-row distance
+    kAddCompactMetric,      // not f32 l2sq / cos
+    kAddCompactCollective,  // lantern_gpu_add_sharded / _add_row_sharded
+    kAddCompactPages,       // a page-attached mirror (usearch_add_external writes the node's vector back)
+    kAddCompactShape        // no M_*_PQD launch shape serves the configuration (plan_insert refuses it)
+};
+struct AddCompactIn
+{
+    int      mcode = 0, num_cus = 0, waves = 0;
+    uint32_t chunks = 0, M0 = 0, efc = 0;  // chunks of a DECODED row
+    bool     on = false, compact = false, collective = false, pages = false, lds_list = false;
+    uint32_t pqd_inv = 0, pq_S16 = 0;
+    size_t   cap = 0, rows = 0;            // the index's capacity; the rows of the call (0: a reserve)
+};
+struct AddCompactPlan
+{
+    AddCompactWhy why = kAddCompactOff;
+    int           mcode = 0;         // served: the metric code of the insertion launches (the index's + M_PQD)
+    size_t        stage_rows = 0;    // served: rows of one staging piece (<= kAddCompactStageRows)
+    size_t        stage_bytes = 0;   // served: the staging block -- the call's only allocation that holds f32 rows
+    size_t        expand_bytes = 0;  // not served, compact: the f32 row block the call decodes the index into
+    InsertPlan    insert;            // served: the k_insert launch of a batch of stage_rows rows (never lone, never screened)
+};
+constexpr size_t kAddCompactStageRows = 65536;  // the dense path's chunk: 201 MB at 768-d
+AddCompactPlan plan_add_compact(const AddCompactIn &in);
+AddCompactIn   add_compact_in(const Index *ix, size_t rows, bool collective);  // the index's fields and the call
 extern const bool kInsertScreenByDefault;  // the initial mode of Index::insert_screen where LANTERN_GPU_INSERT_SCREEN does not say
 // the environment switches of a batch, as values (insert_env, insert_batch.cpp, says which is read once per process and which on every batch)
 struct InsertEnv

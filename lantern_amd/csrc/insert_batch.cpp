@@ -107,6 +107,51 @@ InsertPlan plan_insert(const InsertPlanIn &in)
     return p;
 }
 
+// Whether an add (or, rows = 0, a reserve) on a pq index is served from its code rows (index.hpp AddCompactPlan).  The reasons in the
+// order a caller can change them.  Served: the batches run k_insert / k_connect / k_revlink_* in their M_*_PQD instantiations, G by the
+// DECODED row -- the register list (efc <= 128) and the LDS list both exist; the lone walk k_insert_spec does not, so a handful of rows
+// takes k_insert (the same graph: DESIGN.md 4.4) -- and a configuration whose k_insert launch plan_insert refuses expands instead.
+AddCompactPlan plan_add_compact(const AddCompactIn &in)
+{
+    AddCompactPlan p;
+    const int base = in.mcode;
+    if(!in.on) p.why = kAddCompactOff;
+    else if(!in.compact) p.why = kAddCompactExpanded;
+    else if(in.pqd_inv == 0) p.why = kAddCompactNoDecode;
+    else if(base != M_L2SQ && base != M_COS) p.why = kAddCompactMetric;
+    else if(in.collective) p.why = kAddCompactCollective;
+    else if(in.pages) p.why = kAddCompactPages;
+    else {
+        InsertPlanIn pin;
+        pin.mcode = base + M_PQD, pin.num_cus = in.num_cus, pin.waves = in.waves;
+        pin.chunks = in.chunks, pin.M0 = in.M0, pin.efc = in.efc;
+        pin.rows = std::min(std::max<size_t>(in.rows, 1), kAddCompactStageRows);
+        pin.lds_list = in.lds_list;
+        p.insert = plan_insert(pin);
+        p.why = p.insert.refusal || p.insert.lone || p.insert.screened || in.chunks > 4096 ? kAddCompactShape : kAddCompactServed;
+    }
+    if(p.why == kAddCompactServed) {
+        p.mcode = base + M_PQD;
+        p.stage_rows = std::min(in.rows, kAddCompactStageRows);
+        p.stage_bytes = p.stage_rows * (size_t)in.chunks * 16;
+    } else if(in.compact) {
+        p.expand_bytes = std::max<size_t>(in.cap, 1) * (size_t)in.chunks * 16;  // pq_expand_locked's block
+    }
+    return p;
+}
+
+AddCompactIn add_compact_in(const Index *ix, size_t rows, bool collective)
+{
+    AddCompactIn in;
+    in.mcode = ix->mcode, in.num_cus = ix->num_cus, in.waves = ix->insert_waves;
+    in.chunks = ix->chunks, in.M0 = ix->M0, in.efc = ix->efc;
+    in.on = ix->add_compact, in.compact = ix->pq_compact, in.collective = collective, in.pages = ix->page_mode;
+    in.lds_list = search_env().lds_list;
+    in.pqd_inv = ix->pqd_inv, in.pq_S16 = ix->pq_S16;
+    in.cap = ix->cap, in.rows = rows;
+    return in;
+}
+
 // Row-sharded build (index.cpp add_row_sharded_locked, step 2): a batch's level-0 candidates from the shards' graphs
 static bool row_shard_candidates(Index *ix, const RowShard &rs, size_t first, size_t b, const uint32_t *d_link_off, uint64_t *d_tops, uint32_t *d_top_count)
 {
@@ -195,8 +240,11 @@ bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowShard *r
 
     // the launch's shape: plan_insert (above).  The batch's switches as values (insert_env, above: which is read when)
     const InsertEnv env = insert_env();
+    // a compact pq index (insert_rows got here through plan_add_compact): the view's rows are the code rows, every kernel of the batch
+    // runs its decoding instantiation
+    const int mc = ix->pq_compact ? ix->mcode + M_PQD : ix->mcode;
     InsertPlanIn pin;
-    pin.mcode = ix->mcode, pin.num_cus = ix->num_cus, pin.waves = ix->insert_waves;
+    pin.mcode = mc, pin.num_cus = ix->num_cus, pin.waves = ix->insert_waves;
     pin.chunks = ix->chunks, pin.M0 = ix->M0, pin.efc = ix->efc;
     pin.rows = b_hi - b_lo;
     pin.screen_table = ix->d_screen && ix->d_screen_meta;
@@ -234,9 +282,9 @@ bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowShard *r
     ia.vis_slots = ip.vis_slots;
     ia.totals = ix->d_totals + kTotInsert;  // (a screened launch: and [kInsertScreenTotals..+1] from there)
     ia.ticket = next_ticket(ix, b_hi - b_lo, grid, ix->stream);
-    if(ins_spec) HIPCHK(ix, launch_insert_spec(ix->mcode, ia, ins_waves, grid, ix->stream));
+    if(ins_spec) HIPCHK(ix, launch_insert_spec(mc, ia, ins_waves, grid, ix->stream));
     else {
-        HIPCHK(ix, launch_insert(ix->mcode, ia, ix->insert_waves, grid, ix->stream));
+        HIPCHK(ix, launch_insert(mc, ia, ix->insert_waves, grid, ix->stream));
         (ip.screened ? ix->insert_launches_screened : ix->insert_launches_plain) += 1;
     }
     if(rs && !row_shard_candidates(ix, *rs, first, b, d_link_off, d_tops, d_top_count)) return false;  // level 0: from the shards' graphs
@@ -254,7 +302,7 @@ bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowShard *r
     ca.top_count = d_top_count;
     ca.links = d_links;
     ca.totals = ix->d_totals + kTotConnect;
-    HIPCHK(ix, launch_connect(ix->mcode, ca, ix->stream));
+    HIPCHK(ix, launch_connect(mc, ca, ix->stream));
     prof_mark(ix, 2);
 
     if(split) {
@@ -327,7 +375,7 @@ bool run_batch(Index *ix, size_t b, const int *lv, Comm *comm, const RowShard *r
     }
     ra.radius0 = use_state ? ix->d_radius0 : nullptr;
     ra.radius_upper = use_state ? ix->d_radius_upper : nullptr;
-    HIPCHK(ix, launch_revlink(ix->mcode, ra, (char *)d_work + 16, (uint32_t *)d_work, ix->num_cus, ix->stream, true));
+    HIPCHK(ix, launch_revlink(mc, ra, (char *)d_work + 16, (uint32_t *)d_work, ix->num_cus, ix->stream, true));
     prof_mark(ix, 4);
     if(split) {
         // exchange 2: the adjacency rows the ranks re-wrote, one record [close, level, list[0..M0)] per group.

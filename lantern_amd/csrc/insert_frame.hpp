@@ -28,8 +28,10 @@ __device__ __forceinline__ uint32_t *insert_bind(const InsertArgs &a, WalkLds &s
 template <int METRIC, bool SCREEN = false>
 __device__ __forceinline__ void insert_stage(const int tid, const int T, const InsertArgs &a, WalkLds &s, uint32_t me, uint32_t item0, int target, uint32_t chunks)
 {
-    const uint4 *own = row_of(a.view, me);
-    for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = own[ i ];
+    const auto own = row_of_m<METRIC>(a.view, me);
+    if constexpr(METRIC >= M_PQD) pqd_stage(own, s.q, tid, T, (int)chunks);  // a compact pq index: the row is decoded here, once; the walk reads s.q
+    else
+        for(uint32_t i = tid; i < chunks; i += T) s.q[ i ] = own[ i ];
     for(uint32_t i = tid; i <= (uint32_t)target; i += T) a.top_count[ item0 + i ] = 0;  // levels above max_level stay empty
     if(tid == 0) s.scal[ S_QN2 ] = __float_as_int(row_norm<METRIC>(a.view, me));     // the "query" is a stored row
     if constexpr(SCREEN) {

@@ -70,7 +70,7 @@ hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, h
     // (a view with a screen: the launch screens -- insert_batch.cpp passes the screen only where plan_insert planned the planes' block)
     const bool   screened = a.view.screen != nullptr;
     const size_t lds = insert_lds_bytes(a.view.chunks, a.efc, a.view.M0, a.vis_slots) + (screened ? screen_query_lds_bytes(a.view.chunks) : 0);
-    const int    kpl = a.lds_list ? 0 : a.efc <= 64 ? 1 : a.efc <= 128 ? 2 : 0;
+    const int    kpl = insert_kpl(a.efc, a.lds_list != 0);
 #define LGPU_LAUNCH_INSERT(...) LGPU_LAUNCH_LDS((k_insert<__VA_ARGS__>), grid, 64 * waves, lds, stream, a)
 #define CALL(MM, GG)                               \
     {                                              \
@@ -87,7 +87,8 @@ hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, h
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }
-    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+    // the code rows of a compact pq index (M_*_PQD: insert_stage decodes the own row, the walk decodes what it evaluates): the three list forms
+    LGPU_DISPATCH_ROWS(metric, a.view.chunks, CALL);
 #undef CALL
 #undef LGPU_LAUNCH_INSERT
     return hipGetLastError();

@@ -82,11 +82,15 @@ __global__ void __launch_bounds__(256) k_connect(ConnectArgs a)
             for(int i = tid; i < n; i += T) { kid[ i ] = r.sid[ i ]; kd[ i ] = r.sd[ i ]; }
         } else {
             auto load_row = [&](uint32_t slot, uint4 (&v)[ CPLC ]) {
-                const uint4 *row = row_of(a.view, slot);
+                const auto row = row_of_m<METRIC>(a.view, slot);
+                if constexpr(METRIC >= M_PQD) {  // a compact pq index: the row is decoded as it enters the registers
+                    pqd_load<CPLC>(row, gl, G, chunks, v);
+                } else {
 #pragma unroll
-                for(int c = 0; c < CPLC; ++c) {
-                    const int ch = gl + G * c;
-                    v[ c ] = ch < chunks ? row[ ch ] : make_uint4(0, 0, 0, 0);
+                    for(int c = 0; c < CPLC; ++c) {
+                        const int ch = gl + G * c;
+                        v[ c ] = ch < chunks ? row[ ch ] : make_uint4(0, 0, 0, 0);
+                    }
                 }
             };
             uint4 kept[ KPG ][ CPLC ], cur[ CPLC ], nxt[ CPLC ];
@@ -215,7 +219,7 @@ __global__ void __launch_bounds__(256) k_revlink(RevlinkArgs a)
         }
         if(!have_d) {  // distances of the original entries to `close`, once
             for(int i = g; i < c0; i += NG) {
-                float d = group_dist_n<METRIC, G>(row_of(a.view, close), row_of(a.view, r.cid[ i ]), (int)a.view.chunks, gl,
+                float d = group_dist_n<METRIC, G>(row_of_m<METRIC>(a.view, close), row_of_m<METRIC>(a.view, r.cid[ i ]), (int)a.view.chunks, gl,
                                                   row_norm<METRIC>(a.view, close), row_norm<METRIC>(a.view, r.cid[ i ]));
                 if(gl == G - 1) r.cd[ i ] = d;
             }
@@ -395,7 +399,9 @@ __global__ void __launch_bounds__(512) k_revlink_staged(RevlinkArgs a, const Rev
             }
             __syncthreads();
             const int xrow = s.scal[ 1 ];
-            for(int ch = tid; ch < chunks; ch += T) s.rows[ (size_t)xrow * chunks + ch ] = row_of(a.view, vnew)[ ch ];
+            if constexpr(METRIC >= M_PQD) pqd_stage(row_of_m<METRIC>(a.view, vnew), s.rows + (size_t)xrow * chunks, tid, T, chunks);
+            else
+                for(int ch = tid; ch < chunks; ch += T) s.rows[ (size_t)xrow * chunks + ch ] = row_of(a.view, vnew)[ ch ];
             __syncthreads();
             const float xn = row_norm<METRIC>(a.view, vnew);
             for(int i = g; i < c; i += NG) {  // d(x, entry i), one G-lane group per entry
@@ -449,13 +455,32 @@ __global__ void __launch_bounds__(512) k_revlink_staged(RevlinkArgs a, const Rev
             const int total = (n + 1) * chunks;
             for(int base = tid; base < total; base += T * 8) {
                 uint4 v[ 8 ];
+                if constexpr(METRIC >= M_PQD) {
+                    // a compact pq index: each row is decoded once, into its LDS row -- the eight code bytes first, then the eight table reads
+                    uint32_t slot[ 8 ], code[ 8 ];
+                    int      chn[ 8 ];
 #pragma unroll
-                for(int u = 0; u < 8; ++u) {
-                    const int idx = base + u * T;
-                    if(idx < total) {
-                        const int      r = idx / chunks, ch = idx - r * chunks;
-                        const uint32_t slot = r < n ? s.cid[ r ] : close;
-                        v[ u ] = row_of(a.view, slot)[ ch ];
+                    for(int u = 0; u < 8; ++u) {
+                        const int idx = base + u * T;
+                        if(idx < total) {
+                            const int r = idx / chunks;
+                            chn[ u ] = idx - r * chunks;
+                            slot[ u ] = r < n ? s.cid[ r ] : close;
+                            code[ u ] = row_of_m<METRIC>(a.view, slot[ u ]).code_of(chn[ u ]);
+                        }
+                    }
+#pragma unroll
+                    for(int u = 0; u < 8; ++u)
+                        if(base + u * T < total) v[ u ] = row_of_m<METRIC>(a.view, slot[ u ]).chunk_of(chn[ u ], code[ u ]);
+                } else {
+#pragma unroll
+                    for(int u = 0; u < 8; ++u) {
+                        const int idx = base + u * T;
+                        if(idx < total) {
+                            const int      r = idx / chunks, ch = idx - r * chunks;
+                            const uint32_t slot = r < n ? s.cid[ r ] : close;
+                            v[ u ] = row_of(a.view, slot)[ ch ];
+                        }
                     }
                 }
 #pragma unroll
@@ -610,11 +635,15 @@ __global__ void __launch_bounds__(512, CPL <= 3 ? 4 : 2) k_revlink_pairs(Revlink
     const int      chunks = (int)a.view.chunks;
     uint32_t       pairs = 0, reprunes = 0;
     auto load_row = [&](uint32_t slot, uint4 (&v)[ CPL ]) {
-        const uint4 *row = row_of(a.view, slot);
+        const auto row = row_of_m<METRIC>(a.view, slot);
+        if constexpr(METRIC >= M_PQD) {  // a compact pq index: decoded as the row enters the wave's registers
+            pqd_load<CPL>(row, lane, 64, chunks, v);
+        } else {
 #pragma unroll
-        for(int c = 0; c < CPL; ++c) {
-            const int ch = lane + 64 * c;
-            v[ c ] = ch < chunks ? row[ ch ] : make_uint4(0, 0, 0, 0);
+            for(int c = 0; c < CPL; ++c) {
+                const int ch = lane + 64 * c;
+                v[ c ] = ch < chunks ? row[ ch ] : make_uint4(0, 0, 0, 0);
+            }
         }
     };
     auto order_key = [](float d, uint32_t id, uint32_t centre) { return ((uint64_t)f2ord(d) << 32) | tie_mix(id, centre); };
@@ -893,7 +922,7 @@ __global__ void __launch_bounds__(256) k_fill_norms(View v, uint32_t first, uint
     const uint32_t gid = (blockIdx.x * blockDim.x + threadIdx.x) / G, gl = threadIdx.x % G;
     const uint32_t ngroups = gridDim.x * blockDim.x / G;
     for(uint32_t i = gid; i < count; i += ngroups) {
-        const float n2 = group_norm<METRIC, G>(row_of(v, first + i), (int)v.chunks, (int)gl);
+        const float n2 = group_norm<METRIC, G>(row_of_m<METRIC>(v, first + i), (int)v.chunks, (int)gl);
         if(gl == G - 1) norm2[ first + i ] = n2;
     }
 }
@@ -1048,7 +1077,7 @@ hipError_t launch_connect(int metric, const ConnectArgs &a, hipStream_t stream)
         else if(a.view.chunks <= 384) hipLaunchKernelGGL((k_connect<MM, GG == 64 ? 64 : GG, GG == 64 ? 6 : 4>), dim3(a.items), dim3(256), lds, stream, a); \
         else hipLaunchKernelGGL((k_connect<MM, GG == 64 ? 64 : GG, GG == 64 ? 8 : 4>), dim3(a.items), dim3(256), lds, stream, a); \
     }
-    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+    LGPU_DISPATCH_ROWS(metric, a.view.chunks, CALL);
 #undef CALL
     return hipGetLastError();
 }
@@ -1086,6 +1115,8 @@ hipError_t launch_revlink(int metric, const RevlinkArgs &a, void *work, uint32_t
             case M_HAMMING: PAIRS(M_HAMMING); break;
             case M_L2SQ_F16: PAIRS(M_L2SQ_F16); break;
             case M_COS_F16: PAIRS(M_COS_F16); break;
+            case M_L2SQ_PQD: PAIRS(M_L2SQ_PQD); break;  // the code rows of a compact pq index, by the DECODED row's chunks
+            case M_COS_PQD: PAIRS(M_COS_PQD); break;
             default: return hipErrorInvalidValue;
         }
 #undef PAIRS
@@ -1099,14 +1130,14 @@ hipError_t launch_revlink(int metric, const RevlinkArgs &a, void *work, uint32_t
         if(e != hipSuccess) return e;
         hipLaunchKernelGGL(k_revlink_append, dim3(append_grid), dim3(256), 0, stream, a, (RevWork *)work, work_count);
 #define CALL(MM, GG) LGPU_LAUNCH_LDS((k_revlink_staged<MM, GG>), std::min<uint32_t>((uint32_t)(num_cus * staged_per_cu), a.max_groups), 512, staged, stream, a, (const RevWork *)work, work_count)
-        LGPU_DISPATCH(metric, a.view.chunks, CALL);
+        LGPU_DISPATCH_ROWS(metric, a.view.chunks, CALL);
 #undef CALL
         return hipGetLastError();
     }
     const size_t lds = refine_lds_bytes(a.view.M0 + 1) + S_SCALARS * 4;
     const int    ggrid = (int)std::min<uint32_t>(a.max_groups, (uint32_t)num_cus * 8);
 #define CALL(MM, GG) hipLaunchKernelGGL((k_revlink<MM, GG>), dim3(ggrid), dim3(256), lds, stream, a)
-    LGPU_DISPATCH(metric, a.view.chunks, CALL);
+    LGPU_DISPATCH_ROWS(metric, a.view.chunks, CALL);
 #undef CALL
     return hipGetLastError();
 }
@@ -1137,13 +1168,14 @@ hipError_t launch_apply_lists(const View &v, const uint32_t *records, uint32_t n
 
 hipError_t launch_fill_norms(int metric, const View &v, uint32_t first, uint32_t count, float *norm2, hipStream_t stream)
 {
-    if(count == 0 || (metric != M_COS && metric != M_COS_F16)) return hipSuccess;
+    if(count == 0 || (metric != M_COS && metric != M_COS_F16 && metric != M_COS_PQD)) return hipSuccess;
     const int G_ = group_lanes_for(v.chunks);
     uint32_t  blocks = (uint32_t)(((uint64_t)count * G_ + 255) / 256);
     if(blocks > 16384) blocks = 16384;
 #define FN(MM, GG) hipLaunchKernelGGL((k_fill_norms<MM, GG>), dim3(blocks), dim3(256), 0, stream, v, first, count, norm2)
 #define FNG(MM) switch(G_) { case 64: FN(MM, 64); break; case 32: FN(MM, 32); break; case 16: FN(MM, 16); break; default: FN(MM, 8); }
-    if(metric == M_COS) FNG(M_COS) else FNG(M_COS_F16)
+    // (M_COS_PQD: the view's rows are code rows -- the chain and tree of the expanded row over its decoded chunks, the same words)
+    if(metric == M_COS) FNG(M_COS) else if(metric == M_COS_PQD) FNG(M_COS_PQD) else FNG(M_COS_F16)
 #undef FNG
 #undef FN
     return hipGetLastError();

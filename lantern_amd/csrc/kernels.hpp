@@ -253,6 +253,8 @@ size_t     search_spec_lds_bytes(uint32_t M0, uint32_t prefetch, uint32_t cache_
 hipError_t launch_search_adc(int metric, const SearchArgs &a, int waves, int grid, hipStream_t stream);  // metric = M_L2SQ_ADC / M_COS_ADC
 size_t     search_adc_lds_bytes(uint32_t code_chunks, uint32_t qchunks, uint32_t ef_cap, uint32_t M0, uint32_t vis_slots);
 hipError_t launch_insert(int metric, const InsertArgs &a, int waves, int grid, hipStream_t stream);
+// k_insert's KPL for a launch: keys per lane of wave 0's register list, 0 = the LDS list (launch_insert; lantern_gpu_plan_add_compact reports it)
+inline int insert_kpl(uint32_t efc, bool lds_list) { return lds_list ? 0 : efc <= 64 ? 1 : efc <= 128 ? 2 : 0; }
 // a handful of insertions (ldb_aminsert, the first batches of a build): level 0 by the lone-query walk (f32 l2sq / cos, efc <= 128)
 bool       insert_spec_supported(int metric, uint32_t efc, uint32_t M0);
 size_t     insert_spec_lds_bytes(uint32_t chunks, uint32_t efc, uint32_t M0, uint32_t vis_slots, uint32_t prefetch, uint32_t cache_entries);
@@ -277,6 +279,9 @@ hipError_t launch_pq_take(const float *rows, uint32_t row_floats, uint32_t first
                           float *sub, hipStream_t stream);
 hipError_t launch_pq_put(float *rows, uint32_t row_floats, uint32_t first, uint32_t count, uint32_t s, uint32_t subdim, uint32_t S, const uint32_t *nearest,
                          const float *codebook, uint32_t dims, uint8_t *codes, hipStream_t stream);
+// a compact index: nearest[i] as the code byte of subvector s of slot first + i, into codes (stride S) and codes16 (stride S16); no decoding is written
+hipError_t launch_pq_put_codes(uint32_t first, uint32_t count, uint32_t s, uint32_t S, uint32_t S16, const uint32_t *nearest, uint8_t *codes, uint8_t *codes16,
+                               hipStream_t stream);
 hipError_t launch_pq_decode(float *rows, uint32_t row_floats, uint32_t first, uint32_t count, uint32_t subdim, uint32_t S, const float *codebook, uint32_t dims,
                             const uint8_t *codes, hipStream_t stream);
 
