@@ -526,6 +526,33 @@ LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each_dense(usearch_index_t, ui
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_each_dense(const int64_t in[7], const int64_t queries[][3], size_t nq, uint32_t out[6],
                                                                     uint32_t group[], uint32_t order[], uint32_t seg[], uint32_t steps[][4],
                                                                     size_t cap, size_t *n_steps);
+/* THAT RUN, BATCHED (DESIGN.md 4.9 "Dense exact path, per-query filters: batched"): the run above launches one contraction and one
+ * selection per step, which a call of many small groups pays for step by step.  With this setting at 1 the steps of one gathered chunk
+ * are packed into BATCHES -- consecutive steps, greedily in plan order, whose distance blocks together fit the run's matrix block --
+ * and a batch is ONE segmented contraction launch (a table of tiles: 32 queries x 256 rows for a step of at most 32 queries, 128 x
+ * 128 otherwise) and ONE selection launch.  Everything behind the contractions -- the re-rank, the certificate, the answers, the
+ * refused queries -- is the run's as it is, so every output is bit for bit what the call gives with the setting at 0.
+ * on = 0, THE DEFAULT: the call issues exactly the launches it issues without this switch.  It means something only where
+ *   lantern_gpu_set_filter_dense_each takes groups.
+ * Served: f32 rows under l2sq / cos.  f16 / i8 rows (contracted as stored or dequantised) and the popcount metrics take the per-step
+ *   run; the plan says so (out[0] below); it is never an error. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_dense_each_batched(usearch_index_t, int on, usearch_error_t *);
+LANTERN_GPU_EXPORT int lantern_gpu_filter_dense_each_batched(usearch_index_t, usearch_error_t *); /* the setting */
+/* the launches of the dense run of the last per-query-filter call (all zero when it made none): out[0] contraction launches,
+ * [1] selection launches, [2] batches (0: the per-step run), [3] tiles that took the skinny shape */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_each_dense_launches(usearch_index_t, uint32_t out[4], usearch_error_t *);
+/* The batches without a device (a pure function; the call plans through it).
+ * in[8]: [0..6] as lantern_gpu_plan_filtered_each_dense's  [7] the capacity of a batch in floats (0: the run's own matrix block)
+ * queries, nq: as lantern_gpu_plan_filtered_each_dense's
+ * out[4]: [0] 0: the run is batched; else why not: 1 the call makes no dense run, 2 not f32 rows under l2sq / cos, 3 rows of more
+ *   than 65 536 chunks  [1] skinny tiles of the call  [2] 128 x 128 tiles  [3] the capacity in floats
+ * batches[i] = { first step, steps, floats of their packed blocks, tiles }; steps[i] = { the offset of step i's block inside its
+ *   batch's packed matrix (row-major, one row per query of the step, leading dimension = the step's positions), its skinny tiles, its
+ *   128 x 128 tiles }, i as in lantern_gpu_plan_filtered_each_dense's steps.  The first bcap / scap are written.
+ * Returns NULL, or why the input is refused (a capacity that one step alone exceeds is). */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_each_dense_batches(const int64_t in[8], const int64_t queries[][3], size_t nq, uint32_t out[4],
+                                                                            uint32_t batches[][4], size_t bcap, size_t *n_batches, uint32_t steps[][3],
+                                                                            size_t scap, size_t *n_steps);
 /* lantern_gpu_search_batch through a filter (host buffers; the unused tail of a row is label 0 and +inf) */
 LANTERN_GPU_EXPORT void lantern_gpu_search_batch_filtered(usearch_index_t, const lantern_gpu_filter_t *, const void *queries, size_t nq,
                                                           usearch_scalar_kind_t, size_t k, size_t ef, usearch_label_t *labels,

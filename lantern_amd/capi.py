@@ -131,6 +131,8 @@ EXPORTS = [
     # ... the exact path's dense route (lantern_gpu.h "THE EXACT PATH'S DENSE ROUTE")
     "lantern_gpu_set_filter_dense", "lantern_gpu_filter_dense", "lantern_gpu_filter_dense_stats", "lantern_gpu_plan_filtered_dense",
     "lantern_gpu_set_filter_dense_each", "lantern_gpu_filter_dense_each", "lantern_gpu_last_filtered_each_dense", "lantern_gpu_plan_filtered_each_dense",
+    "lantern_gpu_set_filter_dense_each_batched", "lantern_gpu_filter_dense_each_batched", "lantern_gpu_last_filtered_each_dense_launches",
+    "lantern_gpu_plan_filtered_each_dense_batches",
     # ... with per-query k, ef and skip as well (lantern_gpu.h "PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_filtered_each_params", "lantern_gpu_search_batch_filtered_each_params_lane",
     "lantern_gpu_search_batch_filtered_each_params_device", "lantern_gpu_last_filtered_each_params", "lantern_gpu_plan_filtered_params",
@@ -379,6 +381,10 @@ def lib() -> C.CDLL:
         "lantern_gpu_filter_dense_each": (sz, [vp, err]),
         "lantern_gpu_last_filtered_each_dense": (None, [vp, vp, err]),
         "lantern_gpu_plan_filtered_each_dense": (C.c_char_p, [vp, vp, sz, vp, vp, vp, vp, vp, sz, vp]),
+        "lantern_gpu_set_filter_dense_each_batched": (None, [vp, C.c_int, err]),
+        "lantern_gpu_filter_dense_each_batched": (C.c_int, [vp, err]),
+        "lantern_gpu_last_filtered_each_dense_launches": (None, [vp, vp, err]),
+        "lantern_gpu_plan_filtered_each_dense_batches": (C.c_char_p, [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "lantern_gpu_filter_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_filtered_compact": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
@@ -635,6 +641,29 @@ def plan_filtered_each_dense(mcode, chunks, k, skip, min_group, ids, counts, exa
     return {"why": FILTERED_EACH_DENSE_WHY[int(out[2])], "groups": groups, "queries": queries, "kk": int(out[3]), "gather_rows": int(out[4]), "rows": int(out[5]),
             "group": [int(x) for x in group[:nq]], "order": [int(x) for x in order[:queries]], "seg": [int(x) for x in seg[:groups + 1]] if groups else [],
             "n_steps": int(count.value), "steps": [tuple(int(x) for x in s) for s in steps[:cap]]}
+
+
+# lantern_gpu_plan_filtered_each_dense_batches' out[0], by value
+FILTERED_EACH_DENSE_BATCHES_WHY = ("taken", "no_run", "operands", "wide_row")
+
+
+def plan_filtered_each_dense_batches(mcode, chunks, k, skip, min_group, ids, counts, exact, compact=False, native=-1, capacity=0):
+    """lantern_gpu_plan_filtered_each_dense_batches: the batches of the segmented run's steps (host arithmetic, no device).  The inputs
+    are plan_filtered_each_dense's, and capacity: the floats a batch may pack (0: the run's own matrix block).  {"why"
+    (FILTERED_EACH_DENSE_BATCHES_WHY), "skinny", "big" (tiles of the call), "capacity", "batches": [(first step, steps, floats, tiles),
+    ...], "steps": [(block offset, skinny tiles, big tiles), ...]}."""
+    nq = len(ids)
+    pin = np.array([mcode, chunks, k, skip, min_group, int(bool(compact)), native, capacity], np.int64)
+    per = np.ascontiguousarray(np.stack([np.asarray(ids, np.int64), np.asarray(counts, np.int64), np.asarray(exact, np.int64)], axis=1)) if nq else np.zeros((1, 3), np.int64)
+    out, nb, ns = np.zeros(4, np.uint32), C.c_size_t(0), C.c_size_t(0)
+    why = lib().lantern_gpu_plan_filtered_each_dense_batches(_ptr(pin), _ptr(per), nq, _ptr(out), None, 0, C.byref(nb), None, 0, C.byref(ns))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    bcap, scap = nb.value, ns.value
+    batches, steps = np.zeros((max(bcap, 1), 4), np.uint32), np.zeros((max(scap, 1), 3), np.uint32)
+    lib().lantern_gpu_plan_filtered_each_dense_batches(_ptr(pin), _ptr(per), nq, _ptr(out), _ptr(batches), bcap, C.byref(nb), _ptr(steps), scap, C.byref(ns))
+    return {"why": FILTERED_EACH_DENSE_BATCHES_WHY[int(out[0])], "skinny": int(out[1]), "big": int(out[2]), "capacity": int(out[3]),
+            "batches": [tuple(int(x) for x in b) for b in batches[:bcap]], "steps": [tuple(int(x) for x in s) for s in steps[:scap]]}
 
 
 def l2sq_dist(a, b) -> float:
@@ -1055,6 +1084,21 @@ class GpuIndex:
     def filter_dense_each(self):
         """lantern_gpu_filter_dense_each: the min_group setting."""
         return int(_call("lantern_gpu_filter_dense_each", self.h))
+
+    def set_filter_dense_each_batched(self, on):
+        """The dense groups' run launches one segmented contraction and one selection per batch of steps instead of one per step (0 = off, the default)."""
+        _call("lantern_gpu_set_filter_dense_each_batched", self.h, int(on))
+
+    def filter_dense_each_batched(self):
+        """lantern_gpu_filter_dense_each_batched: the setting."""
+        return int(_call("lantern_gpu_filter_dense_each_batched", self.h))
+
+    def last_filtered_each_dense_launches(self):
+        """The launches of the last per-query filtered call's dense run (lantern_gpu_last_filtered_each_dense_launches)."""
+        out = np.zeros(4, dtype=np.uint32)
+        _call("lantern_gpu_last_filtered_each_dense_launches", self.h, _ptr(out))
+        contractions, selections, batches, skinny = (int(x) for x in out)
+        return {"contractions": contractions, "selections": selections, "batches": batches, "skinny_tiles": skinny}
 
     def last_filtered_each_dense(self):
         """The dense run of the last per-query filtered call on this index (lantern_gpu_last_filtered_each_dense)."""

@@ -8,6 +8,7 @@
 #include "index.hpp"
 #include "abi_guard.hpp"
 #include "dense_tile.hpp"
+#include "dense_seg.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -229,9 +230,13 @@ static std::vector<KnnStep> plan_steps(const ExactKnnPlan &p)
 // pq (p.kind == kDensePq, d_list NULL): d_base is code rows; a row's stride is pq->row_bytes, everything else is the f32 rows' run.
 static bool exact_knn_run(const ExactKnnPlan &p, const std::vector<KnnStep> &steps, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q,
                           uint32_t *d_slots, float *d_dists, hipStream_t st, bool *overflowed, std::vector<uint32_t> &certified,
-                          const EachDenseAnswers *queued = nullptr, const DensePqRows *pq = nullptr)
+                          const EachDenseAnswers *queued = nullptr, const DensePqRows *pq = nullptr, EachDenseRun *run = nullptr)
 try {
     if((p.kind == kDensePq) != (pq != nullptr) || (pq && d_list)) return false;
+    // the batched form of the segmented run: one contraction and one selection launch per batch, from the call's two device tables
+    const EachDenseBatches *const seg = run && run->batches && run->batches->why == kEachBatchTaken ? run->batches : nullptr;
+    if(seg && (!d_list || p.kind != 0 || p.copy || p.bits || !run->d_tiles || !run->d_queries || seg->off.size() != steps.size())) return false;
+    size_t bi = 0;  // the next batch
     int dev = 0;
     (void)hipGetDevice(&dev);
     KnnPool *const               pool = (dev >= 0 && dev < 16) ? &g_knn_pool[ dev ] : nullptr;
@@ -283,8 +288,20 @@ try {
                 ok = ok && launch_norms(p.kind, base_metric, fb, (uint32_t)nc, fchunks, bn + c0, st) == hipSuccess;
                 bv = fb;
             }
+            for(; seg && ok && bi < seg->batches.size() && steps[ seg->batches[ bi ].step0 ].col0 < c0 + nc; ++bi) {
+                const EachDenseBatch &b = seg->batches[ bi ];
+                ok = ok && launch_dense_seg(base_metric, (const float *)qv, (const float *)bv, fchunks * 4, qn, bn + c0, dd, run->d_tiles + b.tile0, b.tiles, st) == hipSuccess;
+                ok = ok && launch_select_seg(dd, run->d_queries + b.query0, b.queries, best, kk, st) == hipSuccess;
+                ++g_dense_kind[ 0 ];
+                si += b.n_steps;
+                run->launches[ 0 ] += 1;
+                run->launches[ 1 ] += 1;
+                run->launches[ 2 ] += 1;
+                run->launches[ 3 ] += b.skinny;
+            }
             for(; ok && si < steps.size() && steps[ si ].col0 < c0 + nc; ++si) {
                 const KnnStep       s = steps[ si ];
+                if(run) { run->launches[ 0 ] += 1; run->launches[ 1 ] += 1; }
                 uint64_t *const     mine = best + (size_t)s.q0 * kk;
                 const DenseOperands o = { p.kind, base_metric, qv + (size_t)s.q0 * fchunks, s.nqt, pq ? rows_at(bv, s.col0 - c0) : bv + (s.col0 - c0) * fchunks, s.cols, fchunks,
                                           qn + s.q0, bn + s.col0, pq ? *pq : DensePqRows{} };
@@ -484,12 +501,67 @@ const char *plan_filtered_each_dense(int64_t mcode, int64_t chunks, int64_t k, i
     return nullptr;
 }
 
+// ---- the batches of that run: greedy, in plan order, never across a chunk ------------------------------------------------------------
+const char *plan_each_dense_batches(const EachDensePlan &p, uint64_t dd_floats, EachDenseBatches &b)
+{
+    b = EachDenseBatches();
+    if(p.why != kEachDenseTaken) return nullptr;
+    const ExactKnnPlan &k = p.knn;
+    if(k.kind != 0 || k.copy != 0 || k.bits || (k.mcode != M_L2SQ && k.mcode != M_COS)) return b.why = kEachBatchOperands, nullptr;
+    if(k.chunks > 65536) return b.why = kEachBatchWideRow, nullptr;
+    b.capacity = std::min<uint64_t>(dd_floats ? dd_floats : k.dd_bytes / 4, 0xFFFFFFFFull);  // (a block's offset is 32 bits)
+    const size_t n = p.steps.size();
+    b.off.resize(n);
+    b.skinny.resize(n);
+    b.big.resize(n);
+    for(size_t i = 0; i < n; ++i) {
+        const KnnStep &s = p.steps[ i ];
+        const uint64_t floats = (uint64_t)s.nqt * s.cols;
+        if(floats > b.capacity) {
+            b = EachDenseBatches();
+            return "lantern_gpu: a step of the dense run does not fit the capacity alone";
+        }
+        const bool thin = s.nqt <= kSegSkinnyQ;
+        b.skinny[ i ] = thin ? (s.cols + kSegSkinnyCols - 1) / kSegSkinnyCols : 0u;
+        b.big[ i ] = thin ? 0u : ((s.nqt + kSegBigQ - 1) / kSegBigQ) * ((s.cols + kSegBigCols - 1) / kSegBigCols);
+        const bool open = !b.batches.empty() && b.batches.back().floats + floats <= b.capacity &&
+                          p.steps[ b.batches.back().step0 ].col0 / k.chunk_rows == s.col0 / k.chunk_rows;
+        if(!open) {
+            const size_t t0 = b.tiles(), q0 = b.queries();
+            b.batches.push_back({ (uint32_t)i, 0u, 0u, (uint32_t)t0, 0u, 0u, (uint32_t)q0, 0u });
+        }
+        EachDenseBatch &at = b.batches.back();
+        b.off[ i ] = at.floats;
+        at.n_steps += 1;
+        at.floats += (uint32_t)floats;
+        at.tiles += b.skinny[ i ] + b.big[ i ];
+        at.skinny += b.skinny[ i ];
+        at.queries += s.nqt;
+    }
+    b.why = kEachBatchTaken;
+    return nullptr;
+}
+
+void each_dense_seg_tables(const EachDensePlan &p, const EachDenseBatches &b, SegTile *tiles, SegQuery *queries)
+{
+    for(size_t i = 0; i < p.steps.size(); ++i) {
+        const KnnStep &s = p.steps[ i ];
+        const uint32_t off = b.off[ i ], col0 = s.col0 % p.knn.chunk_rows;  // (inside its gathered chunk)
+        const uint32_t tq = b.skinny[ i ] ? kSegSkinnyQ : kSegBigQ, tc = b.skinny[ i ] ? kSegSkinnyCols : kSegBigCols;
+        for(uint32_t c = 0; c < s.cols; c += tc)
+            for(uint32_t q = 0; q < s.nqt; q += tq)
+                *tiles++ = { s.q0 + q, std::min(tq, s.nqt - q), col0 + c, std::min(tc, s.cols - c), off + q * s.cols + c, s.cols, b.skinny[ i ] ? 0u : 1u, 0u };
+        for(uint32_t q = 0; q < s.nqt; ++q) *queries++ = { off + q * s.cols, s.cols, s.col0, s.q0 + q };
+    }
+}
+
 bool filtered_each_dense_device(const EachDensePlan &p, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots, float *d_dists,
-                                hipStream_t st, const EachDenseAnswers &answers, std::vector<uint32_t> &refused)
+                                hipStream_t st, const EachDenseAnswers &answers, std::vector<uint32_t> &refused, EachDenseRun *run)
 try {
     if(p.why != kEachDenseTaken || !d_list) return false;
     std::vector<uint32_t> certified;
-    if(!exact_knn_run(p.knn, p.steps, d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified, &answers)) return false;
+    if(run) std::fill(std::begin(run->launches), std::end(run->launches), 0u);
+    if(!exact_knn_run(p.knn, p.steps, d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified, &answers, nullptr, run)) return false;
     refused.clear();
     for(size_t q = 0; q < certified.size(); ++q)
         if(!certified[ q ]) refused.push_back((uint32_t)q);
@@ -720,6 +792,37 @@ try {
         steps[ i ][ 0 ] = s.q0; steps[ i ][ 1 ] = s.nqt; steps[ i ][ 2 ] = s.col0; steps[ i ][ 3 ] = s.cols;
     }
     *n_steps = p.steps.size();
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
+
+const char *lantern_gpu_plan_filtered_each_dense_batches(const int64_t in[ 8 ], const int64_t queries[][ 3 ], size_t nq, uint32_t out[ 4 ], uint32_t batches[][ 4 ],
+                                                         size_t bcap, size_t *n_batches, uint32_t steps[][ 3 ], size_t scap, size_t *n_steps)
+try {
+    if(!in || !out || !n_batches || !n_steps || (bcap && !batches) || (scap && !steps) || (nq && !queries)) return "lantern_gpu: null plan array";
+    if(in[ 7 ] < 0) return kBadPlan;
+    std::vector<int64_t> ids(nq), counts(nq);
+    std::vector<uint8_t> exact(nq);
+    for(size_t i = 0; i < nq; ++i) { ids[ i ] = queries[ i ][ 0 ]; counts[ i ] = queries[ i ][ 1 ]; exact[ i ] = queries[ i ][ 2 ] != 0; }
+    EachDensePlan p;
+    if(const char *why = plan_filtered_each_dense(in[ 0 ], in[ 1 ], in[ 2 ], in[ 3 ], in[ 4 ], in[ 5 ] != 0, in[ 6 ] < 0 ? -1 : in[ 6 ] != 0, ids.data(),
+                                                  counts.data(), exact.data(), nq, p))
+        return why;
+    EachDenseBatches b;
+    if(const char *why = plan_each_dense_batches(p, (uint64_t)in[ 7 ], b)) return why;
+    out[ 0 ] = (uint32_t)b.why;
+    out[ 1 ] = out[ 2 ] = 0;
+    for(size_t i = 0; i < b.off.size(); ++i) { out[ 1 ] += b.skinny[ i ]; out[ 2 ] += b.big[ i ]; }
+    out[ 3 ] = (uint32_t)std::min<uint64_t>(b.capacity, 0xFFFFFFFFull);
+    for(size_t i = 0; i < b.batches.size() && i < bcap; ++i) {
+        const EachDenseBatch &x = b.batches[ i ];
+        batches[ i ][ 0 ] = x.step0; batches[ i ][ 1 ] = x.n_steps; batches[ i ][ 2 ] = x.floats; batches[ i ][ 3 ] = x.tiles;
+    }
+    for(size_t i = 0; i < b.off.size() && i < scap; ++i) { steps[ i ][ 0 ] = b.off[ i ]; steps[ i ][ 1 ] = b.skinny[ i ]; steps[ i ][ 2 ] = b.big[ i ]; }
+    *n_batches = b.batches.size();
+    *n_steps = b.off.size();
     return nullptr;
 }
 catch(...) {

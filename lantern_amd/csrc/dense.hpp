@@ -116,6 +116,50 @@ struct EachDensePlan
 // rows; exact[i] -- its path is exact.  NULL, or why the input is refused; a call without a dense group is not refused.
 const char *plan_filtered_each_dense(int64_t mcode, int64_t chunks, int64_t k, int64_t skip, int64_t min_group, bool compact, int native, const int64_t *ids,
                                      const int64_t *counts, const uint8_t *exact, size_t nq, EachDensePlan &p);
+// The batched form of that run (DESIGN.md 4.9 "Dense exact path, per-query filters: batched"): a BATCH is a run of consecutive steps
+// of one gathered chunk whose blocks, packed one behind the other, fit the run's dd block; one k_dense_seg launch contracts every
+// tile of a batch and one k_select_seg launch folds its blocks into the best lists (dense_seg.hip).  Step s's block is row-major, one
+// row per query of the step, leading dimension = the step's columns.  lantern_gpu_plan_filtered_each_dense_batches shows the plan.
+enum EachBatchWhy : uint32_t
+{
+    kEachBatchTaken = 0,
+    kEachBatchNoRun,     // the call makes no dense run (EachDensePlan::why says why)
+    kEachBatchOperands,  // not f32 rows under l2sq / cos contracted as stored: f16 / i8 rows (native or dequantised), popcount metrics
+    kEachBatchWideRow    // rows of more than 65 536 chunks: a tile's byte offsets would leave 31 bits
+};
+struct EachDenseBatch
+{
+    uint32_t step0, n_steps, floats;  // steps [step0, step0 + n_steps) of EachDensePlan::steps; the floats of their packed blocks
+    uint32_t tile0, tiles, skinny;    // its entries of the call's tile table; how many of them are skinny tiles
+    uint32_t query0, queries;         // its entries of the call's selection table: one per (step, query)
+};
+struct EachDenseBatches
+{
+    EachBatchWhy                why = kEachBatchNoRun;
+    uint64_t                    capacity = 0;        // floats a batch may pack
+    std::vector<EachDenseBatch> batches;             // in plan order; none crosses a chunk
+    std::vector<uint32_t>       off, skinny, big;    // per step: its block's offset inside its batch's packed matrix, its tiles in each shape
+    size_t tiles() const { return batches.empty() ? 0 : batches.back().tile0 + batches.back().tiles; }
+    size_t queries() const { return batches.empty() ? 0 : batches.back().query0 + batches.back().queries; }
+};
+// pure, as plan_filtered_each_dense.  dd_floats: the capacity, 0: the plan's own dd block (every step fits that one alone).  NULL, or
+// why the input is refused (a capacity that a step alone exceeds); a run that is not batched is not refused (why != kEachBatchTaken)
+const char *plan_each_dense_batches(const EachDensePlan &p, uint64_t dd_floats, EachDenseBatches &b);
+// the two device tables of a taken batch plan, for the whole call: tiles [tiles()] (entries of a step adjacent, column tile major) and
+// selection entries [queries()]
+struct SegTile;
+struct SegQuery;
+void each_dense_seg_tables(const EachDensePlan &p, const EachDenseBatches &b, SegTile *tiles, SegQuery *queries);
+// what a run is given beside its plan, and what it reports: batches NULL (or not taken) -- the per-step run; else the batched one, from
+// the two tables on the device.  launches: lantern_gpu_last_filtered_each_dense_launches' four words
+struct EachDenseRun
+{
+    const EachDenseBatches *batches = nullptr;
+    const SegTile          *d_tiles = nullptr;
+    const SegQuery         *d_queries = nullptr;
+    uint32_t                launches[ 4 ] = {};
+};
+
 // One run of a taken plan.  d_list: L; d_q: the dense queries' rows, gathered in the plan's order.  Result (device), per dense query:
 // slots[k + skip] ascending by (exact-order distance, slot), dists alike.  `answers`, queued behind the certificate and in front of
 // the run's ONE wait for `st`, is given the device flags -- [q] 1: certified, [nq] != 0: a cosine row norm of ANY segment is outside the
@@ -123,7 +167,7 @@ const char *plan_filtered_each_dense(int64_t mcode, int64_t chunks, int64_t k, i
 // dense queries (positions in the plan's order) whose rows of the result are not the answer; the caller recomputes them.
 using EachDenseAnswers = std::function<bool(const uint32_t *d_flags)>;
 bool filtered_each_dense_device(const EachDensePlan &p, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots, float *d_dists,
-                                hipStream_t st, const EachDenseAnswers &answers, std::vector<uint32_t> &refused);
+                                hipStream_t st, const EachDenseAnswers &answers, std::vector<uint32_t> &refused, EachDenseRun *run = nullptr);
 
 // Exact k-NN of nq device-resident query rows over nb device-resident base rows (both `chunks` uint4 per row).
 // Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "filtered_search.hpp"
+#include "dense_seg.hpp"
 
 namespace lgpu {
 
@@ -126,14 +127,22 @@ bool filtered_each_dense_locked(Index *ix, const Filter *const *filters, const E
     static const char *kDenseFailed = "lantern_gpu: HIP failure on the dense route of a per-query filtered call";
     const size_t nqd = plan.order.size(), groups = plan.groups(), total = plan.seg.back(), kk = k + skip, row = (size_t)ix->chunks * 16;
     auto         up = [](size_t x, size_t a) { return (x + a - 1) / a * a; };
-    // host tables, one copy: orig[nqd] | allowed[nqd] | seg[groups + 1] | lists[groups] (8-byte aligned)
-    const size_t          t_orig = 0, t_allowed = nqd * 4, t_seg = 2 * nqd * 4, t_lists = up(t_seg + (groups + 1) * 4, 8), t_bytes = t_lists + groups * 8;
+    // lantern_gpu_set_filter_dense_each_batched: the run's batches (not taken -- f16 / i8 rows, popcount metrics: the per-step run)
+    EachDenseBatches batches;
+    if(ix->filter_dense_each_batched && plan_each_dense_batches(plan, 0, batches) != nullptr) return set_err(ix, kDenseFailed), false;
+    const bool   batched = batches.why == kEachBatchTaken;
+    const size_t n_tiles = batched ? batches.tiles() : 0, n_sel = batched ? batches.queries() : 0;
+    // host tables, one copy: orig[nqd] | allowed[nqd] | seg[groups + 1] | lists[groups] (8-byte aligned) | batched: the tile table (32
+    // bytes per tile) | the selection table (16 per step and query)
+    const size_t t_orig = 0, t_allowed = nqd * 4, t_seg = 2 * nqd * 4, t_lists = up(t_seg + (groups + 1) * 4, 8), t_tiles = up(t_lists + groups * 8, 16);
+    const size_t t_sel = t_tiles + n_tiles * sizeof(SegTile), t_bytes = t_sel + n_sel * sizeof(SegQuery);
     std::vector<uint64_t> tbl(t_bytes / 8);
     char *const           ht = (char *)tbl.data();
     uint32_t *const       h_orig = (uint32_t *)(ht + t_orig), *h_allowed = (uint32_t *)(ht + t_allowed);
     const uint32_t      **h_lists = (const uint32_t **)(ht + t_lists);
     std::copy(plan.order.begin(), plan.order.end(), h_orig);
     std::copy(plan.seg.begin(), plan.seg.end(), (uint32_t *)(ht + t_seg));
+    if(batched) each_dense_seg_tables(plan, batches, (SegTile *)(ht + t_tiles), (SegQuery *)(ht + t_sel));
     for(size_t g = 0; g < groups; ++g) {
         const Filter *f = filters[ plan.order[ plan.qoff[ g ] ] ];
         h_lists[ g ] = f->d_slots;
@@ -165,7 +174,13 @@ bool filtered_each_dense_locked(Index *ix, const Filter *const *filters, const E
         return hipGetLastError() == hipSuccess;
     };
     std::vector<uint32_t> refused_at;
-    ok = ok && filtered_each_dense_device(plan, ix->d_vec, d_list, d_gq, d_slots, d_dists, stream, answers, refused_at);
+    EachDenseRun run;
+    if(batched) {
+        run.batches = &batches;
+        run.d_tiles = (const SegTile *)(blk + t_tiles);
+        run.d_queries = (const SegQuery *)(blk + t_sel);
+    }
+    ok = ok && filtered_each_dense_device(plan, ix->d_vec, d_list, d_gq, d_slots, d_dists, stream, answers, refused_at, &run);
     if(!ok) {
         (void)hipStreamSynchronize(stream);  // (nothing queued may still read the host tables or the block)
         return set_err(ix, kDenseFailed), false;
@@ -178,6 +193,7 @@ bool filtered_each_dense_locked(Index *ix, const Filter *const *filters, const E
     ix->c_filter_dense[ 3 ] += refused.size();
     const uint32_t shape[ 6 ] = { (uint32_t)groups, (uint32_t)nqd, (uint32_t)(nqd - refused.size()), (uint32_t)refused.size(), (uint32_t)total, (uint32_t)plan.steps.size() };
     std::copy(std::begin(shape), std::end(shape), ix->last_each_dense);
+    std::copy(std::begin(run.launches), std::end(run.launches), ix->last_each_dense_launches);
     return true;
 }
 

@@ -273,6 +273,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
 {
     if(!each_filters_ok(ix, filters, nq)) return false;
     std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);
+    std::fill(std::begin(ix->last_each_dense_launches), std::end(ix->last_each_dense_launches), 0u);
     if(nq == 0 || k == 0) return true;
     const std::vector<int64_t> counts = each_counts(filters, nq);
     FilteredCallPlan           plan;
@@ -321,7 +322,8 @@ static bool each_params_plan_locked(Index *ix, const Filter *const *filters, con
 static bool filtered_each_params_locked(Index *ix, const FilteredCallPlan &plan, const Filter *const *filters, const uint4 *d_q, size_t nq, size_t k_stride,
                                         const SearchOut &out, hipStream_t stream, char *h_tbl)
 {
-    std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);  // (a per-query-filter call that makes no dense run)
+    std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);
+    std::fill(std::begin(ix->last_each_dense_launches), std::end(ix->last_each_dense_launches), 0u);  // (a per-query-filter call that makes no dense run)
     if(nq == 0) return true;
     const uint32_t shape[ 4 ] = { plan.sw.exp, plan.sw.cand_cap, plan.se.exp, plan.n_k0 };
     std::copy(std::begin(shape), std::end(shape), ix->last_each_params);
@@ -504,6 +506,30 @@ void lantern_gpu_last_filtered_each_dense(usearch_index_t h, uint32_t out[ 6 ], 
 try {
     CLEAR(e);
     record_out(h, &Index::last_each_dense, out, e);
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+void lantern_gpu_set_filter_dense_each_batched(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) { FAIL(e, "lantern_gpu: filter_dense_each_batched must be 0 (one launch per step) or 1 (one per batch)"); return; }
+    with_locked(h, e, [ & ](Index *ix) { ix->filter_dense_each_batched = on != 0; });
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_filter_dense_each_batched(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    int on = 0;
+    with_locked(h, e, [ & ](Index *ix) { on = ix->filter_dense_each_batched ? 1 : 0; });
+    return on;
+}
+LANTERN_ABI_CATCH(e)
+
+void lantern_gpu_last_filtered_each_dense_launches(usearch_index_t h, uint32_t out[ 4 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    record_out(h, &Index::last_each_dense_launches, out, e);
 }
 LANTERN_ABI_CATCH_VOID(e)
 

@@ -240,6 +240,8 @@ struct Index
     size_t   filter_dense_min = 0;      // lantern_gpu_set_filter_dense: 0 off; m > 0: single-filter exact-path calls of nq >= m queries take the dense route
     uint64_t c_filter_dense[ 4 ] = {};  // lantern_gpu_filter_dense_stats: dense calls, their queries, certified, recomputed
     size_t   filter_dense_each_min = 0;  // lantern_gpu_set_filter_dense_each: 0 off; m > 0: in a per-query-filter call, m exact-path queries behind one filter handle take the dense route
+    bool     filter_dense_each_batched = false;  // lantern_gpu_set_filter_dense_each_batched: the dense groups' run launches one contraction and one selection per batch of steps
+    uint32_t last_each_dense_launches[ 4 ] = {};  // lantern_gpu_last_filtered_each_dense_launches: contraction launches, selection launches, batches, skinny tiles
     uint32_t last_each_dense[ 6 ] = {};  // lantern_gpu_last_filtered_each_dense: dense groups, their queries, certified, recomputed, rows gathered, contraction steps
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     bool     exact_compact = false;     // lantern_gpu_set_exact_compact: lantern_gpu_exact_search answers a compact pq index from its code rows (default: it expands)

@@ -428,6 +428,7 @@ def each_dense_legs(a, base, queries, k, ef):
     ix.set_filter_policy("exact")
     # (the same script times a build from before the setting: "setting_0" only; --setting-0-only: this build, the setting never touched)
     has_setting = hasattr(ix, "set_filter_dense_each") and not a.setting_0_only
+    has_batched = has_setting and hasattr(ix, "set_filter_dense_each_batched")
     rows = ix.device_query_rows(queries)
     dq = hip.Buffer.from_numpy(rows)
     slot, D = hip.Buffer(nq * k * 4), hip.Buffer(nq * 8)
@@ -451,16 +452,20 @@ def each_dense_legs(a, base, queries, k, ef):
             ix.search_batch_filtered_device(filters[0], dq.ptr, rows.strides[0], nq, k, ef, 0, None, None, slot.ptr, None, D.ptr, None)
             hip.synchronize()
 
-        modes = {"setting_0": (0, 0, each_call)}
+        modes = {"setting_0": (0, 0, 0, each_call)}
         if has_setting:
-            modes["setting_on"] = (2, 0, each_call)
+            modes["setting_on"] = (2, 0, 0, each_call)
+            if has_batched:
+                modes["setting_on_batched"] = (2, 0, 1, each_call)  # one segmented contraction and one selection per batch of steps
             if parts == 1:
-                modes["single_filter_dense"] = (0, 1, single_call)  # the fused single-filter route on the same group: the price of running unfused
-        wall, answers, diag = {m: [] for m in modes}, {}, {}
+                modes["single_filter_dense"] = (0, 1, 0, single_call)  # the fused single-filter route on the same group: the price of running unfused
+        wall, answers, diag, launches = {m: [] for m in modes}, {}, {}, {}
         for rep in range(a.reps + 1):  # (repeat 0 warms every mode -- the pooled blocks are allocated there -- and is not listed)
-            for m, (each_min, single_min, call) in modes.items():
+            for m, (each_min, single_min, batched, call) in modes.items():
                 if has_setting:
                     ix.set_filter_dense_each(each_min)
+                if has_batched:
+                    ix.set_filter_dense_each_batched(batched)
                 ix.set_filter_dense(single_min)
                 if rep:
                     call()  # (untimed: every timed call follows a call of its own mode, whatever the modes alternated with are)
@@ -474,11 +479,15 @@ def each_dense_legs(a, base, queries, k, ef):
                 answers[m] = slot.download((nq, k), np.uint32)[:a.nq_exact].copy()
                 if m == "setting_on":
                     diag = ix.last_filtered_each_dense()
+                if has_batched and each_min:
+                    launches[m] = ix.last_filtered_each_dense_launches()
         ix.set_filter_dense(0)
+        if has_batched:
+            ix.set_filter_dense_each_batched(0)
         if has_setting:
             ix.set_filter_dense_each(0)
         leg = {"case": name, "filters": parts, "rows_per_filter": int(filters[0].count), "queries": nq, "wall_ms": wall,
-               "median_ms": {m: float(np.median(v)) for m, v in wall.items()}, "dense_run": diag,
+               "median_ms": {m: float(np.median(v)) for m, v in wall.items()}, "dense_run": diag, "launches": launches,
                "answers_equal": {m: bool(np.array_equal(answers[m], answers["setting_0"])) for m in modes}}
         out.append(leg)
         for f in filters:
