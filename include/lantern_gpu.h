@@ -1010,7 +1010,7 @@ LANTERN_GPU_EXPORT size_t lantern_gpu_deleted_count(usearch_index_t, usearch_err
  *  - It does not equal a rebuild of the live rows (DESIGN.md 4.11 says by how much).
  * The call is a graph mutation, ordered as an insertion batch.  The result is a pure function of the graph: the replicas of a
  * sharded build each call it and stay identical.  Refused: a page-attached index (its lists would have to go back through
- * retriever_mut) and a compact pq index (expand it first). */
+ * retriever_mut) and a compact pq index (expand it first) unless lantern_gpu_set_delete_compact (below) serves it. */
 typedef struct lantern_gpu_unlink_stats
 {
     uint64_t tombstones_unlinked; /* slots of T that still had a neighbour of their own */
@@ -1054,7 +1054,8 @@ LANTERN_GPU_EXPORT void lantern_gpu_unlink_deleted(usearch_index_t, lantern_gpu_
  *    Re-prunes and insertions that follow break exact distance ties by tie_mix(slot, centre) over the NEW slots, so from then on the
  *    graph may differ, among exactly tied candidates only, from what the uncompacted index would have grown into.
  * The call is a graph mutation, ordered as an insertion batch, and a pure function of the graph: the replicas of a sharded build each
- * call it and stay identical.  Refused: a page-attached index and a compact pq index (expand it first). */
+ * call it and stay identical.  Refused: a page-attached index and a compact pq index (expand it first) unless
+ * lantern_gpu_set_delete_compact (below) serves it. */
 typedef struct lantern_gpu_compact_stats
 {
     lantern_gpu_unlink_stats unlink;   /* the unlink the call performs first (all zero if there was nothing to unlink) */
@@ -1072,6 +1073,34 @@ LANTERN_GPU_EXPORT void lantern_gpu_last_compact_ms(usearch_index_t, float *out 
  * below new slot j, *live and *upper_blocks their totals.  Every output may be NULL. */
 LANTERN_GPU_EXPORT void lantern_gpu_plan_compact(const uint64_t *labels, const uint8_t *levels, size_t n, uint32_t *slot_map /* [n] */,
                                                  uint32_t *upper_off_new /* [live] */, uint64_t *live, uint64_t *upper_blocks, usearch_error_t *);
+/* COMPACT PQ INDEXES (DESIGN.md 4.11, 4.12 "Compact pq indexes").  on = 0, THE DEFAULT: lantern_gpu_unlink_deleted and
+ * lantern_gpu_compact_deleted refuse a compact pq index ("... does not run on a compact pq index: expand it first").  on = 1: where the
+ * index's rows can be decoded on the fly (f32 l2sq or cos, subvectors of whole 16-byte chunks) both calls run on its CODE rows and leave
+ * it compact.  The unlink's request pass decodes p once and reads the offers' code rows (k_unlink_requests_pqd, csrc/unlink.hip); the
+ * reverse links run the decoding kernels of lantern_gpu_set_add_compact.  The compaction moves the code rows (num_subvectors bytes per
+ * row, and the padded copy the walks read, which holds the new capacity, zero filled beyond the live rows), the norms of a cosine index
+ * and everything else as above; no block of capacity x dimensions f32 is allocated, the transient peak is old + new of CODE rows, and
+ * lantern_gpu_memory_usage reports live x the code row stride afterwards.  Graph, stats, slot_map, epoch and a later
+ * lantern_gpu_pq_expand are those of the same calls on the expanded index.  A compact index that is not served is refused with a text
+ * that says why; it is never expanded silently.  A page-attached index stays refused.  on other than 0 or 1 is refused. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_delete_compact(usearch_index_t, int on, usearch_error_t *);
+/* diagnostic: 0 the switch is off; 1 it is on but the two calls would not run on this index's code rows (or the index is not compact);
+ * 2 they are served from the code rows */
+LANTERN_GPU_EXPORT int lantern_gpu_delete_compact(usearch_index_t, usearch_error_t *);
+/* The decision above and the compaction's byte arithmetic without a device (a pure function; the two calls decide through it).
+ * in[16]: [0] the index's metric code  [1] 16-byte chunks of a DECODED row  [2] level-0 list length (2 x connectivity)  [3] connectivity
+ *         [4] the switch  [5] the index is compact  [6] its decode inverse (0: rows cannot be decoded on the fly)  [7] bytes of a padded
+ *         code row  [8] num_subvectors  [9] the capacity now  [10] rows the padded code block holds now  [11] upper blocks allocated now
+ *         [12] live rows  [13] their upper blocks  [14] the call's `capacity`  [15] unused.
+ * out[16]: [0] served  [1] why: 0 served, 1 the switch is off, 2 not compact (stored rows, as ever), 3 rows cannot be decoded on the fly,
+ *          4 not f32 l2sq / cos, 5 the request kernel's LDS exceeds what a launch may request -- in the order the calls meet them
+ *          [2] the metric code of the request and reverse-link launches  [3] lanes per row  [4] dynamic LDS of the request kernel
+ *          [5] offers whose code rows one LDS block holds  [6..7] bytes of the arrays the index holds now  [8..9] of the new arrays
+ *          [10..11] after the call (lantern_gpu_memory_usage's sum)  [12..13] the transient peak, old + new (the map's 20 bytes per old
+ *          slot come on top) -- rows counted as code rows: num_subvectors bytes and the padded stride, never chunks x 16
+ *          [14..15] not served, compact: the f32 row block lantern_gpu_pq_expand would allocate.  Byte counts as (low, high) words.
+ * Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_delete_compact(const int64_t in[16], uint32_t out[16]);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Work-sharded index build over the GPUs of one node (the reference's     */

@@ -97,7 +97,7 @@ EXPORTS = [
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
     "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_set_exact_compact", "lantern_gpu_exact_compact", "lantern_gpu_plan_exact_compact", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
-    "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_set_add_compact", "lantern_gpu_add_compact", "lantern_gpu_plan_add_compact", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
+    "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_set_add_compact", "lantern_gpu_add_compact", "lantern_gpu_plan_add_compact", "lantern_gpu_set_delete_compact", "lantern_gpu_delete_compact", "lantern_gpu_plan_delete_compact", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
     "lantern_gpu_export_codes",
@@ -256,6 +256,9 @@ def lib() -> C.CDLL:
         "lantern_gpu_set_add_compact": (None, [vp, C.c_int, err]),
         "lantern_gpu_add_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_add_compact": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_set_delete_compact": (None, [vp, C.c_int, err]),
+        "lantern_gpu_delete_compact": (C.c_int, [vp, err]),
+        "lantern_gpu_plan_delete_compact": (C.c_char_p, [vp, vp]),
         "lantern_gpu_distance_gather": (None, [vp, vp, vp, sz, vp, err]),
         "lantern_gpu_spec_profile": (None, [vp, i32, vp, err]),
         "lantern_gpu_search_unique_rows": (None, [vp, i32, C.POINTER(u64), err]),
@@ -594,6 +597,27 @@ def plan_add_compact(mcode, chunks, M0, efc, rows, cap, on, compact, pqd_inv, co
     size = lambda i: int(out[i]) | int(out[i + 1]) << 32
     return {"served": bool(out[0]), "why": ADD_COMPACT_WHY[int(out[1])], "mcode": int(out[2]), "stage_rows": int(out[3]), "stage_bytes": size(4),
             "expand_bytes": size(6), "lds": int(out[8]), "vis_slots": int(out[9]), "kpl": int(out[10]), "lanes": int(out[11])}
+
+
+# lantern_gpu_plan_delete_compact's out[1], by value
+DELETE_COMPACT_WHY = ("served", "off", "stored", "no_decode", "metric", "shape")
+
+
+def plan_delete_compact(mcode, chunks, M0, M, on, compact, pqd_inv, code_row_bytes, num_subvectors, cap=0, code_rows=0, upper_cap=0, live=0,
+                        upper_blocks=0, capacity=0):
+    """lantern_gpu_plan_delete_compact: whether unlink_deleted / compact_deleted run on a pq index's code rows and leave it compact, and
+    the compaction's bytes with the rows counted as code rows (host arithmetic, no device): {"served", "why" (DELETE_COMPACT_WHY), "mcode",
+    "lanes", "lds", "block_offers", "old_bytes", "new_bytes", "after_bytes", "peak_bytes", "expand_bytes"}."""
+    pin = np.array([mcode, chunks, M0, M, int(on), int(compact), pqd_inv, code_row_bytes, num_subvectors, cap, code_rows, upper_cap, live, upper_blocks,
+                    capacity, 0], np.int64)
+    out = np.zeros(16, np.uint32)
+    why = lib().lantern_gpu_plan_delete_compact(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    size = lambda i: int(out[i]) | int(out[i + 1]) << 32
+    return {"served": bool(out[0]), "why": DELETE_COMPACT_WHY[int(out[1])], "mcode": int(out[2]), "lanes": int(out[3]), "lds": int(out[4]),
+            "block_offers": int(out[5]), "old_bytes": size(6), "new_bytes": size(8), "after_bytes": size(10), "peak_bytes": size(12),
+            "expand_bytes": size(14)}
 
 
 # lantern_gpu_plan_filtered_dense's out[1], by value
@@ -1032,6 +1056,14 @@ class GpuIndex:
     def add_compact(self):
         """lantern_gpu_add_compact: 0 the switch is off, 1 the next add would still expand the index, 2 it is served from the code rows."""
         return int(_call("lantern_gpu_add_compact", self.h))
+
+    def set_delete_compact(self, on):
+        """unlink_deleted and compact_deleted run on this index's code rows in its compact pq form and leave it compact (1), or refuse it (0, the default)."""
+        _call("lantern_gpu_set_delete_compact", self.h, int(on))
+
+    def delete_compact(self):
+        """lantern_gpu_delete_compact: 0 the switch is off, 1 the two calls would not run on this index's code rows, 2 they are served from them."""
+        return int(_call("lantern_gpu_delete_compact", self.h))
 
     # ---- filtered search (lantern_gpu.h "Filtered search") ----
     def filter_from_labels(self, labels, skip_deleted=False) -> "Filter":

@@ -246,6 +246,7 @@ struct Index
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     bool     exact_compact = false;     // lantern_gpu_set_exact_compact: lantern_gpu_exact_search answers a compact pq index from its code rows (default: it expands)
     bool     add_compact = false;       // lantern_gpu_set_add_compact: adds and reserves leave a compact pq index compact where plan_add_compact serves them (default: they expand)
+    bool     delete_compact = false;    // lantern_gpu_set_delete_compact: unlink and compaction serve a compact pq index from its code rows where plan_delete_compact does (default: refused)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)
     uint32_t last_each[ 6 ] = {};  // the last per-query filtered call: queries on the walk path, on the exact path, unfiltered, empty; distinct filters; launches
@@ -434,6 +435,38 @@ struct AddCompactPlan
 constexpr size_t kAddCompactStageRows = 65536;  // the dense path's chunk: 201 MB at 768-d
 AddCompactPlan plan_add_compact(const AddCompactIn &in);
 AddCompactIn   add_compact_in(const Index *ix, size_t rows, bool collective);  // the index's fields and the call
+// ---- unlink and compaction on a COMPACT pq index (lantern_gpu_set_delete_compact): served from the code rows --
+// the request pass and the reverse-link kernels run their M_*_PQD forms, the compaction moves d_codes and d_codes16 -- or refused, and
+// why: the reasons in the order the call meets them.  Pure (unlink.hip); lantern_gpu_plan_delete_compact shows it without a device.
+enum DeleteCompactWhy : int
+{
+    kDeleteCompactServed = 0,
+    kDeleteCompactOff,       // lantern_gpu_set_delete_compact is 0: a compact index is refused as ever
+    kDeleteCompactStored,    // the index is not compact: stored rows, as ever
+    kDeleteCompactNoDecode,  // pqd_inv == 0: ADC rows have no row-against-row distance
+    kDeleteCompactMetric,    // not f32 l2sq / cos
+    kDeleteCompactShape      // the request kernel's LDS (lists, p's decoded row, one block of code rows) exceeds what a launch may request
+};
+struct DeleteCompactIn
+{
+    int      mcode = 0;
+    uint32_t chunks = 0, M0 = 0, M = 0;  // chunks of a DECODED row
+    bool     on = false, compact = false;
+    uint32_t pqd_inv = 0, pq_S16 = 0, pq_S = 0;
+    size_t   cap = 0, codes16_cap = 0, upper_cap = 0;  // the arrays the index holds now
+    size_t   live = 0, blocks = 0, capacity = 0;       // the compaction: live rows, their upper blocks, the call's capacity
+};
+struct DeleteCompactPlan
+{
+    DeleteCompactWhy why = kDeleteCompactOff;
+    int      mcode = 0;      // served: the metric code of the request and reverse-link launches (the index's + M_PQD)
+    int      lanes = 0;      // served: lanes per decoded row
+    uint32_t block = 0;      // served: offers whose code rows one LDS block holds
+    size_t   lds = 0;        // served: dynamic LDS of k_unlink_requests_pqd
+    size_t   old_bytes = 0, new_bytes = 0, after_bytes = 0, peak_bytes = 0;  // served: the compaction's arrays, rows counted as CODE rows
+    size_t   expand_bytes = 0;  // not served, compact: the f32 row block lantern_gpu_pq_expand would allocate
+};
+DeleteCompactPlan plan_delete_compact(const DeleteCompactIn &in);
 extern const bool kInsertScreenByDefault;  // the initial mode of Index::insert_screen where LANTERN_GPU_INSERT_SCREEN does not say
 // the environment switches of a batch, as values (insert_env, insert_batch.cpp, says which is read once per process and which on every batch)
 struct InsertEnv

@@ -10,6 +10,8 @@
 //       k_unlink_count     one workgroup per work item: keep / offers in LDS, the number of offers (sizes the request array)
 //       k_unlink_requests  the same, then metric(offer, p) by the walk's row routine (one request per offer, in offer order) and
 //                          the stripped list written in place
+//       k_unlink_requests_pqd  the same on a COMPACT pq index (lantern_gpu_set_delete_compact): p decoded once into LDS, the offers'
+//                          code rows copied to LDS a block at a time, the distances formed from LDS bytes and centroid-table reads
 //       k_unlink_clear     every tombstone's own lists emptied
 //
 // Why the stripped list goes straight into the adjacency: a work item (p, l) reads p's list at l and the lists of the TOMBSTONES
@@ -208,6 +210,92 @@ __global__ void __launch_bounds__(256) k_unlink_requests(View v, const uint64_t 
     }
 }
 
+// ---- the request kernel over CODE rows: a compact pq index under lantern_gpu_set_delete_compact ---------------------------------------
+// Instantiating the loop above over PqdRow would decode p again for every pair of offers and pay two dependent round trips per row
+// block (the code bytes, then the table reads).  Here p is decoded ONCE per work item into an LDS row, as insert_stage does for a new
+// node, and the offers' code rows -- the list is complete before the first distance -- are copied into LDS a block at a time in one
+// coalesced pass of uint4 loads.  The distance loop then forms its table offsets from LDS bytes and issues only the centroid-table
+// reads: one dependent trip per row block.  The arithmetic is group_dist2_n's over the same chunks, so a request's d has the bits of
+// k_unlink_requests on the expanded index.
+//   LDS: unlink_carve's arrays | p's decoded row [chunks] uint4 | the code rows of one block of offers [block][pq_row_bytes]
+constexpr uint32_t kUnlinkCodeBlockBytes = 32 * 1024;  // of code rows in LDS at a time
+constexpr uint32_t kUnlinkBlockOffers = 256;           // ... and at most a copy pass of one row per thread: 256 offers at 128-byte rows
+constexpr size_t   kUnlinkPqdMaxLds = 64 * 1024;       // what a launch may request without opting in to more
+// offers per block: even (the distance loop takes them in pairs), 0 where not even two code rows fit
+__host__ __device__ inline uint32_t unlink_code_block(uint32_t row_bytes)
+{
+    const uint32_t b = row_bytes ? kUnlinkCodeBlockBytes / row_bytes : 0u;
+    return b > kUnlinkBlockOffers ? kUnlinkBlockOffers : b & ~1u;
+}
+__host__ __device__ inline size_t unlink_pqd_lds_bytes(uint32_t M0, uint32_t chunks, uint32_t row_bytes)
+{
+    return unlink_lds_bytes(M0) + (size_t)chunks * 16 + (size_t)unlink_code_block(row_bytes) * row_bytes;
+}
+// PqdRow with the code bytes in LDS: chunk ch is chunk ch % cps of centroid codes[ch / cps] of subvector ch / cps
+struct PqdLdsRow
+{
+    const uint8_t *codes;
+    const uint4   *centers;
+    uint32_t       cps, C, inv;
+    __device__ __forceinline__ uint4 operator[](int ch) const
+    {
+        const uint32_t sv = ((uint32_t)ch * inv) >> 16, off = (uint32_t)ch - sv * cps;
+        return centers[ ((size_t)sv * C + codes[ sv ]) * cps + off ];
+    }
+};
+
+template <int METRIC, int G>
+__global__ void __launch_bounds__(256) k_unlink_requests_pqd(View v, const uint64_t *labels, const uint2 *items, const uint64_t *off, uint32_t first,
+                                                             uint32_t count, LinkReq *reqs, uint32_t block)
+{
+    static_assert(METRIC >= M_PQD, "the decoding metrics only");
+    const UnlinkLds s = unlink_carve(v.M0);
+    uint4          *prow = (uint4 *)(lgpu_smem + unlink_lds_bytes(v.M0));
+    uint4          *cblk = prow + v.chunks;
+    const uint32_t  units = v.pq_row_bytes / 16;  // uint4 per code row
+    const int       tid = (int)threadIdx.x, g = tid / G, gl = tid % G;
+    constexpr int   NG = 256 / G;
+    for(uint32_t it = first + blockIdx.x; it < first + count; it += gridDim.x) {
+        const uint32_t p = items[ it ].x;
+        const int      level = (int)items[ it ].y;
+        uint32_t       cap, nkeep, noff;
+        unlink_collect(v, labels, p, level, s, cap, nkeep, noff);
+        uint32_t *list = neighbors_of(v, p, level, cap);
+        for(uint32_t i = (uint32_t)tid; i < cap; i += 256) list[ i ] = i < nkeep ? s.keep[ i ] : EMPTY;  // compacted, no holes
+        LinkReq    *out = reqs + (size_t)(off[ it ] - off[ first ]);
+        const float pn = row_norm<METRIC>(v, p);
+        if(noff) pqd_stage(row_of_m<METRIC>(v, p), prow, tid, 256, (int)v.chunks);  // p, decoded once
+        for(uint32_t b0 = 0; b0 < noff; b0 += block) {
+            const uint32_t nb = noff - b0 < block ? noff - b0 : block, total = nb * units;
+            __syncthreads();  // p's row is staged; the previous block's code rows have been read
+#pragma unroll 4
+            for(uint32_t u = (uint32_t)tid; u < total; u += 256) {  // consecutive threads: consecutive 16 bytes of one code row, then the next offer's
+                const uint32_t o = u / units, w = u - o * units;
+                cblk[ u ] = v.vec[ (size_t)s.offers[ b0 + o ] * units + w ];
+            }
+            __syncthreads();
+            for(uint32_t o = 2 * (uint32_t)g; o < nb; o += 2 * NG) {
+                const bool      two = o + 1 < nb;
+                const uint32_t  c0 = s.offers[ b0 + o ], c1 = two ? s.offers[ b0 + o + 1 ] : c0;
+                const PqdLdsRow r0{ (const uint8_t *)(cblk + (size_t)o * units), v.pq_centers, v.pq_cps, v.pq_C, v.pq_inv };
+                const PqdLdsRow r1{ (const uint8_t *)(cblk + (size_t)(two ? o + 1 : o) * units), v.pq_centers, v.pq_cps, v.pq_C, v.pq_inv };
+                float           d0, d1;
+                group_dist2_n<METRIC, G>((const uint4 *)prow, r0, r1, (int)v.chunks, gl, pn, row_norm<METRIC>(v, c0), row_norm<METRIC>(v, c1), d0, d1);
+                if(gl == G - 1) {
+                    LinkReq r;
+                    r.close = p, r.level = (uint32_t)level, r.new_slot = c0, r.d = d0;
+                    out[ b0 + o ] = r;
+                    if(two) {
+                        r.new_slot = c1, r.d = d1;
+                        out[ b0 + o + 1 ] = r;
+                    }
+                }
+            }
+        }
+        __syncthreads();  // the next item reuses the LDS
+    }
+}
+
 __global__ void __launch_bounds__(256) k_unlink_clear(View v, const uint64_t *labels, uint32_t *cleared)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -226,11 +314,77 @@ __global__ void __launch_bounds__(256) k_unlink_clear(View v, const uint64_t *la
 static hipError_t launch_unlink_requests(int metric, const View &v, const uint64_t *labels, const uint2 *items, const uint64_t *off, uint32_t first,
                                          uint32_t count, LinkReq *reqs, int grid, hipStream_t stream)
 {
+    if(mcode_is_pqd(metric)) {  // a compact pq index: the view's rows are the code rows
+        const uint32_t block = unlink_code_block(v.pq_row_bytes);
+        const size_t   lds_pqd = unlink_pqd_lds_bytes(v.M0, v.chunks, v.pq_row_bytes);
+        if(!v.pq_centers || v.pq_inv == 0 || v.pq_row_bytes % 16 != 0 || block < 2 || lds_pqd > kUnlinkPqdMaxLds) return hipErrorInvalidValue;
+#define CALL(MM, GG) hipLaunchKernelGGL((k_unlink_requests_pqd<MM, GG>), dim3(grid), dim3(256), lds_pqd, stream, v, labels, items, off, first, count, reqs, block)
+        PQD_G(metric, v.chunks, CALL);
+#undef CALL
+        return hipGetLastError();
+    }
     const size_t lds = unlink_lds_bytes(v.M0);
 #define CALL(MM, GG) hipLaunchKernelGGL((k_unlink_requests<MM, GG>), dim3(grid), dim3(256), lds, stream, v, labels, items, off, first, count, reqs)
     LGPU_DISPATCH(metric, v.chunks, CALL);
 #undef CALL
     return hipGetLastError();
+}
+
+// Whether the unlink and the compaction serve a pq index from its code rows (index.hpp DeleteCompactPlan), and the compaction's byte
+// arithmetic with the rows counted as CODE rows: d_codes at stride pq_S and d_codes16 at stride pq_S16, never chunks x 16.
+DeleteCompactPlan plan_delete_compact(const DeleteCompactIn &in)
+{
+    DeleteCompactPlan p;
+    if(!in.on) p.why = kDeleteCompactOff;
+    else if(!in.compact) p.why = kDeleteCompactStored;
+    else if(in.pqd_inv == 0) p.why = kDeleteCompactNoDecode;
+    else if(in.mcode != M_L2SQ && in.mcode != M_COS) p.why = kDeleteCompactMetric;
+    else if(in.pq_S16 == 0 || in.pq_S16 % 16 != 0 || unlink_code_block(in.pq_S16) < 2 || unlink_pqd_lds_bytes(in.M0, in.chunks, in.pq_S16) > kUnlinkPqdMaxLds)
+        p.why = kDeleteCompactShape;
+    else p.why = kDeleteCompactServed;
+    if(p.why != kDeleteCompactServed) {
+        if(in.compact) p.expand_bytes = std::max<size_t>(in.cap, 1) * (size_t)in.chunks * 16;  // pq_expand_locked's block
+        return p;
+    }
+    p.mcode = in.mcode + M_PQD;
+    p.lanes = group_lanes_for(in.chunks);
+    p.block = unlink_code_block(in.pq_S16);
+    p.lds = unlink_pqd_lds_bytes(in.M0, in.chunks, in.pq_S16);
+    // per slot of capacity: level-0 list, label, level, upper_off, radius0, the cosine norm, the code row at stride pq_S
+    const size_t slot = (size_t)in.M0 * 4 + 8 + 1 + 4 + 4 + (in.mcode == M_COS ? 4 : 0) + in.pq_S, blk = (size_t)in.M * 4 + 4;
+    const size_t newcap = std::max(in.live, in.capacity);
+    p.old_bytes = in.cap * slot + in.upper_cap * blk + in.codes16_cap * in.pq_S16;
+    p.new_bytes = newcap * slot + in.blocks * blk + std::max<size_t>(newcap, 1) * in.pq_S16;  // d_codes16 holds the capacity, zero filled beyond the live rows
+    p.after_bytes = newcap * slot + in.blocks * blk + std::max<size_t>(in.live, 1) * in.pq_S16;  // lantern_gpu_memory_usage: the code rows IN USE
+    p.peak_bytes = p.old_bytes + p.new_bytes;
+    return p;
+}
+
+static DeleteCompactIn delete_compact_in(const Index *ix, size_t live, size_t blocks, size_t capacity)
+{
+    DeleteCompactIn in;
+    in.mcode = ix->mcode, in.chunks = ix->chunks, in.M0 = ix->M0, in.M = ix->M;
+    in.on = ix->delete_compact, in.compact = ix->pq_compact;
+    in.pqd_inv = ix->pqd_inv, in.pq_S16 = ix->pq_S16, in.pq_S = ix->pq_S;
+    in.cap = ix->cap, in.codes16_cap = ix->codes16_cap, in.upper_cap = ix->upper_cap;
+    in.live = live, in.blocks = blocks, in.capacity = capacity;
+    return in;
+}
+// What the two calls answer for a compact pq index the plan does not serve (`what`: "unlink" / "compaction"); the index is never expanded
+// silently.  With the switch off: the text of before the switch existed.
+static std::string delete_compact_refusal(const char *what, DeleteCompactWhy why)
+{
+    const std::string head = std::string("lantern_gpu: ") + what + " does not run on ";
+    switch(why) {
+        case kDeleteCompactNoDecode:
+            return head + "this compact pq index from its code rows: its subvectors are not whole 16-byte chunks, so its rows have no row-against-row "
+                          "distance; expand it first (lantern_gpu_pq_expand)";
+        case kDeleteCompactMetric: return head + "this compact pq index from its code rows: they serve f32 l2sq and cos only; expand it first (lantern_gpu_pq_expand)";
+        case kDeleteCompactShape:
+            return head + "this compact pq index from its code rows: the request kernel's LDS (lists, a decoded row, a block of code rows) exceeds 64 KiB; "
+                          "expand it first (lantern_gpu_pq_expand)";
+        default: return head + "a compact pq index: expand it first (lantern_gpu_pq_expand)";
+    }
 }
 
 static const char *kUnlinkFailed = "lantern_gpu: HIP failure while unlinking deleted rows";
@@ -290,6 +444,8 @@ static bool unlink_locked(Index *ix, lantern_gpu_unlink_stats &st)
     uint32_t *d_counts = (uint32_t *)(blk + at_counts), *d_ctr = (uint32_t *)(blk + at_ctr);
     if(!order_launch(ix, ix->stream)) return false;  // a graph mutation: ordered as an insertion batch
     const View v = ix->view();
+    // a compact pq index (the caller went through plan_delete_compact): the view's rows are the code rows, the kernels that read rows decode
+    const int  mc = ix->pq_compact ? ix->mcode + M_PQD : ix->mcode;
     HIPCHK(ix, hipMemsetAsync(d_ctr, 0, 16, ix->stream));
     HIPCHK(ix, hipMemsetAsync(ix->d_totals + kTotUnlink, 0, 16, ix->stream));
     hipLaunchKernelGGL(k_unlink_flag, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ix->stream, v, (const uint64_t *)ix->d_labels, d_items, d_ctr);
@@ -345,7 +501,7 @@ static bool unlink_locked(Index *ix, lantern_gpu_unlink_stats &st)
         for(size_t r = 0; r + 1 < bounds.size(); ++r) {
             const uint32_t a = bounds[ r ], b = bounds[ r + 1 ];
             const uint32_t nreq = (uint32_t)(off[ b ] - off[ a ]);
-            HIPCHK(ix, launch_unlink_requests(ix->mcode, v, ix->d_labels, d_items, d_off, a, b - a, d_links,
+            HIPCHK(ix, launch_unlink_requests(mc, v, ix->d_labels, d_items, d_off, a, b - a, d_links,
                                               (int)std::min<size_t>(b - a, (size_t)ix->num_cus * 32), ix->stream));
             if(nreq == 0) continue;
             // the build's own grouping pass and reverse-link kernels, on lists without holes
@@ -358,7 +514,7 @@ static bool unlink_locked(Index *ix, lantern_gpu_unlink_stats &st)
             ra.reqs = d_reqs;
             ra.totals = ix->d_totals + kTotUnlink;  // a range of its own: lantern_gpu_counters' build counters do not move
             ra.radius0 = ra.radius_upper = nullptr;  // no list here is as a re-prune left it; the state is reset before its next use
-            HIPCHK(ix, launch_revlink(ix->mcode, ra, (char *)d_work + 16, (uint32_t *)d_work, ix->num_cus, ix->stream, true));
+            HIPCHK(ix, launch_revlink(mc, ra, (char *)d_work + 16, (uint32_t *)d_work, ix->num_cus, ix->stream, true));
         }
     }
     ix->radius_stale = true;
@@ -412,13 +568,13 @@ struct CompactArrays
     uint4    *vec = nullptr, *screen = nullptr;
     float    *norm2 = nullptr, *radius0 = nullptr, *radius_upper = nullptr;
     float2   *screen_meta = nullptr;
-    uint8_t  *codes = nullptr, *levels = nullptr;
+    uint8_t  *codes = nullptr, *codes16 = nullptr, *levels = nullptr;  // codes16: a compact pq index's rows (and then no vec)
     uint64_t *labels = nullptr;
     uint32_t *nbr0 = nullptr, *upper_off = nullptr, *upper_nbr = nullptr;
     void     *temp = nullptr;  // the map's block (CompactMap)
     void release()
     {
-        void *all[] = { vec, screen, norm2, radius0, radius_upper, screen_meta, codes, levels, labels, nbr0, upper_off, upper_nbr, temp };
+        void *all[] = { vec, screen, norm2, radius0, radius_upper, screen_meta, codes, codes16, levels, labels, nbr0, upper_off, upper_nbr, temp };
         for(void *p : all)
             if(p) (void)hipFree(p);
         *this = CompactArrays();
@@ -429,7 +585,7 @@ static const char *kCompactFailed = "lantern_gpu: HIP failure while compacting t
 
 // The caller holds ix->mu, has flushed, has refused the index forms the compaction does not serve and has unlinked.  `dead` > 0.
 // false -> ix->err, and the index is exactly as it was: the new arrays are built beside the old ones and swapped in after the last
-// kernel has succeeded (transient peak: old + new + 20 bytes per old slot for the map).
+// kernel has succeeded (transient peak: old + new + 20 bytes per old slot for the map; a compact pq index: of CODE rows, plan_delete_compact).
 static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lantern_gpu_compact_stats &st)
 {
     const size_t n = ix->n;
@@ -437,12 +593,15 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
     plan_compact_host(ix->labels.data(), ix->levels.data(), n, nullptr, nullptr, live, blocks);
     const size_t newcap = std::max<size_t>((size_t)live, capacity);
     if(newcap >= 0x7FFFFFFFull) { set_err(ix, "lantern_gpu: capacity above 2^31-1 slots is not supported"); return false; }
-    const size_t row = (size_t)ix->chunks * 16, srow = ix->d_screen ? (size_t)screen_chunks_for(ix->chunks) * 16 : 0, codes = ix->pq ? ix->pq_S : 0;
+    // A compact pq index (the caller went through plan_delete_compact): its rows are the code rows -- d_codes16 at stride pq_S16, holding
+    // the new capacity and zero filled beyond the live rows (the padding the ADC table walk relies on), beside d_codes -- and no d_vec.
+    const size_t c16 = ix->pq_compact ? ix->pq_S16 : 0, c16_rows = std::max<size_t>(newcap, 1);
+    const size_t row = c16 ? 0 : (size_t)ix->chunks * 16, srow = ix->d_screen ? (size_t)screen_chunks_for(ix->chunks) * 16 : 0, codes = ix->pq ? ix->pq_S : 0;
     const size_t M0 = ix->M0, M = ix->M;
     const size_t temp_bytes = compact_temp_bytes(n), words = n + 1;
     const size_t map_bytes = 5 * words * 4 + ((temp_bytes + 63) & ~(size_t)63) + 64;
     // what one slot costs in the arrays sized by capacity (lantern_gpu_memory_usage's terms)
-    const size_t per_slot = row + srow + (srow ? 8 : 0) + codes + M0 * 4 + 8 + 1 + 4 + 4 + (ix->d_norm2 ? 4 : 0);
+    const size_t per_slot = row + c16 + srow + (srow ? 8 : 0) + codes + M0 * 4 + 8 + 1 + 4 + 4 + (ix->d_norm2 ? 4 : 0);
     const size_t need = newcap * per_slot + (size_t)blocks * (M * 4 + 4) + map_bytes;
     size_t rb = 0, ob = 0;
     index_memory_bytes(ix, rb, ob);
@@ -454,7 +613,7 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
     auto          take = [&](void **p, size_t bytes) { return hipMalloc(p, std::max<size_t>(bytes, 16)) == hipSuccess; };
     bool got = take(&a.temp, map_bytes) && take((void **)&a.labels, newcap * 8) && take((void **)&a.levels, newcap) && take((void **)&a.nbr0, newcap * M0 * 4) &&
                take((void **)&a.upper_off, newcap * 4) && take((void **)&a.radius0, newcap * 4) && take((void **)&a.upper_nbr, (size_t)blocks * M * 4) &&
-               take((void **)&a.radius_upper, (size_t)blocks * 4) && take((void **)&a.vec, newcap * row);
+               take((void **)&a.radius_upper, (size_t)blocks * 4) && (c16 ? take((void **)&a.codes16, c16_rows * c16) : take((void **)&a.vec, newcap * row));
     if(got && ix->d_norm2) got = take((void **)&a.norm2, newcap * 4);
     if(got && srow) got = take((void **)&a.screen, newcap * srow) && take((void **)&a.screen_meta, newcap * 8);
     if(got && codes) got = take((void **)&a.codes, newcap * codes);
@@ -491,7 +650,12 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
         ok = hipMemsetAsync((char *)a.screen + (size_t)live * srow, 0, (newcap - (size_t)live) * srow, q) == hipSuccess &&
              hipMemsetAsync(a.screen_meta + live, 0, (newcap - (size_t)live) * 8, q) == hipSuccess;
     if(ok && a.codes && newcap > live) ok = hipMemsetAsync(a.codes + (size_t)live * codes, 0, (newcap - (size_t)live) * codes, q) == hipSuccess;
+    if(ok && a.codes16 && c16_rows > live) ok = hipMemsetAsync(a.codes16 + (size_t)live * c16, 0, (c16_rows - (size_t)live) * c16, q) == hipSuccess;
     if(!ok) return fail(kCompactFailed);
+    // the rows: the vector block, or a compact pq index's padded code rows through the same 16-byte-unit copy (pq_S16 is a multiple of 16)
+    const void  *rows_old = c16 ? (const void *)ix->d_codes16 : (const void *)ix->d_vec;
+    void        *rows_new = c16 ? (void *)a.codes16 : (void *)a.vec;
+    const size_t rows_stride = c16 ? c16 : row;
     CompactMeta cm;
     cm.labels = ix->d_labels, cm.new_labels = a.labels;
     cm.levels = ix->d_levels, cm.new_levels = a.levels;
@@ -505,7 +669,7 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
             if(x) (void)hipEventDestroy(x);
     };
     ok = ok && hipEventRecord(ev[ 0 ], q) == hipSuccess && launch_compact_map(ix->d_labels, ix->d_levels, n, m, q) == hipSuccess &&
-         hipEventRecord(ev[ 1 ], q) == hipSuccess && launch_compact_rows(ix->d_vec, a.vec, m.src_of, (size_t)live, row, ix->num_cus, q) == hipSuccess &&
+         hipEventRecord(ev[ 1 ], q) == hipSuccess && launch_compact_rows(rows_old, rows_new, m.src_of, (size_t)live, rows_stride, ix->num_cus, q) == hipSuccess &&
          hipEventRecord(ev[ 2 ], q) == hipSuccess &&
          (!srow || launch_compact_rows(ix->d_screen, a.screen, m.src_of, (size_t)live, srow, ix->num_cus, q) == hipSuccess) &&
          (!codes || launch_compact_rows(ix->d_codes, a.codes, m.src_of, (size_t)live, codes, ix->num_cus, q) == hipSuccess) &&
@@ -538,7 +702,7 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
     if(!record_launch(ix, q)) return fail(kCompactFailed);
 
     // ---- the swap: nothing below can fail ----
-    void *old[] = { ix->d_vec, ix->d_norm2, ix->d_screen, ix->d_screen_meta, ix->d_codes, ix->d_labels, ix->d_levels, ix->d_nbr0, ix->d_upper_off, ix->d_upper_nbr,
+    void *old[] = { ix->d_vec, c16 ? ix->d_codes16 : nullptr, ix->d_norm2, ix->d_screen, ix->d_screen_meta, ix->d_codes, ix->d_labels, ix->d_levels, ix->d_nbr0, ix->d_upper_off, ix->d_upper_nbr,
                     ix->d_radius0, ix->d_radius_upper, ix->d_bitmaps, ix->d_touched, a.temp };
     for(void *p : old)
         if(p) (void)hipFree(p);
@@ -550,6 +714,7 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
     ix->d_vec = a.vec, ix->d_norm2 = a.norm2, ix->d_screen = a.screen, ix->d_screen_meta = a.screen_meta, ix->d_codes = a.codes;
     ix->d_labels = a.labels, ix->d_levels = a.levels, ix->d_nbr0 = a.nbr0, ix->d_upper_off = a.upper_off, ix->d_upper_nbr = a.upper_nbr;
     ix->d_radius0 = a.radius0, ix->d_radius_upper = a.radius_upper;
+    if(c16) ix->d_codes16 = a.codes16, ix->codes16_cap = c16_rows;  // compact before and after
     ix->radius_stale = true;  // the re-prune state is not moved
     ix->cap = newcap;
     ix->upper_cap = ix->upper_blocks = (size_t)blocks;
@@ -570,7 +735,7 @@ static bool compact_locked(Index *ix, size_t capacity, uint32_t *slot_map, lante
     st.rows_after = live;
     st.upper_blocks_after = blocks;
     st.bytes_after = rb + ob;
-    st.bytes_moved = live * (uint64_t)(row + srow + (srow ? 8 : 0) + codes + M0 * 4 + 8 + 1 + 4 + (ix->d_norm2 ? 4 : 0)) + blocks * (uint64_t)(M * 4);
+    st.bytes_moved = live * (uint64_t)(row + c16 + srow + (srow ? 8 : 0) + codes + M0 * 4 + 8 + 1 + 4 + (ix->d_norm2 ? 4 : 0)) + blocks * (uint64_t)(M * 4);
     return true;
 }
 
@@ -620,9 +785,9 @@ try {
         FAIL(e, set_err(ix, "lantern_gpu: unlink does not run on a page-attached index: its lists would have to go back through retriever_mut"));
         return;
     }
-    if(ix->pq_compact) {
-        FAIL(e, set_err(ix, "lantern_gpu: unlink does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)"));
-        return;
+    if(ix->pq_compact) {  // served from the code rows where the switch is on and the plan says so; never expanded silently
+        const DeleteCompactWhy why = plan_delete_compact(delete_compact_in(ix, 0, 0, 0)).why;
+        if(why != kDeleteCompactServed) { FAIL(e, set_err(ix, delete_compact_refusal("unlink", why))); return; }
     }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
@@ -649,8 +814,8 @@ try {
         return;
     }
     if(ix->pq_compact) {
-        FAIL(e, set_err(ix, "lantern_gpu: compaction does not run on a compact pq index: expand it first (lantern_gpu_pq_expand)"));
-        return;
+        const DeleteCompactWhy why = plan_delete_compact(delete_compact_in(ix, 0, 0, 0)).why;
+        if(why != kDeleteCompactServed) { FAIL(e, set_err(ix, delete_compact_refusal("compaction", why))); return; }
     }
     if(!flush_locked(ix)) { FAIL(e, ix->err.c_str()); return; }
     ix->err.clear();
@@ -674,6 +839,61 @@ try {
     if(out) *out = moved;
 }
 LANTERN_ABI_CATCH_VOID(e)
+
+// Unlink and compaction that leave a compact pq index compact (include/lantern_gpu.h; plan_delete_compact above)
+void lantern_gpu_set_delete_compact(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) {
+        FAIL(e, "lantern_gpu: delete_compact must be 0 (unlink and compaction refuse a compact pq index) or 1 (they are served from the code rows)");
+        return;
+    }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->delete_compact = on != 0;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_delete_compact(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!ix->delete_compact) return 0;
+    return plan_delete_compact(delete_compact_in(ix, 0, 0, 0)).why == kDeleteCompactServed ? 2 : 1;
+}
+LANTERN_ABI_CATCH(e)
+
+const char *lantern_gpu_plan_delete_compact(const int64_t in[ 16 ], uint32_t out[ 16 ])
+try {
+    if(!in || !out) return "lantern_gpu: null plan array";
+    // metric, chunks, lists, inverse, code row bytes, subvectors, capacities and counts: the ranges the index itself keeps
+    if(in[ 0 ] < 0 || in[ 0 ] > 0x7FFFFFFF || in[ 1 ] <= 0 || in[ 1 ] > (int64_t)1 << 20 || in[ 2 ] < 2 || in[ 2 ] > 512 || in[ 3 ] < 1 || in[ 3 ] > in[ 2 ] ||
+       in[ 6 ] < 0 || in[ 6 ] > 0xFFFFFFFFll || in[ 7 ] < 16 || in[ 7 ] > 128 || in[ 7 ] % 16 != 0 || in[ 8 ] < 1 || in[ 8 ] > in[ 7 ])
+        return "lantern_gpu: bad plan input";
+    for(int i = 9; i < 15; ++i)
+        if(in[ i ] < 0 || in[ i ] > (int64_t)1 << 40) return "lantern_gpu: bad plan input";  // (the byte sums stay far inside 64 bits)
+    DeleteCompactIn s;
+    s.mcode = (int)in[ 0 ]; s.chunks = (uint32_t)in[ 1 ]; s.M0 = (uint32_t)in[ 2 ]; s.M = (uint32_t)in[ 3 ]; s.on = in[ 4 ] != 0; s.compact = in[ 5 ] != 0;
+    s.pqd_inv = (uint32_t)in[ 6 ]; s.pq_S16 = (uint32_t)in[ 7 ]; s.pq_S = (uint32_t)in[ 8 ];
+    s.cap = (size_t)in[ 9 ]; s.codes16_cap = (size_t)in[ 10 ]; s.upper_cap = (size_t)in[ 11 ]; s.live = (size_t)in[ 12 ]; s.blocks = (size_t)in[ 13 ];
+    s.capacity = (size_t)in[ 14 ];
+    const DeleteCompactPlan p = plan_delete_compact(s);
+    const uint64_t sizes[ 5 ] = { p.old_bytes, p.new_bytes, p.after_bytes, p.peak_bytes, p.expand_bytes };
+    out[ 0 ] = p.why == kDeleteCompactServed ? 1u : 0u;
+    out[ 1 ] = (uint32_t)p.why;
+    out[ 2 ] = (uint32_t)p.mcode;
+    out[ 3 ] = (uint32_t)p.lanes;
+    out[ 4 ] = (uint32_t)p.lds;
+    out[ 5 ] = p.block;
+    for(int i = 0; i < 5; ++i) { out[ 6 + 2 * i ] = (uint32_t)sizes[ i ]; out[ 7 + 2 * i ] = (uint32_t)(sizes[ i ] >> 32); }
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
 
 void lantern_gpu_last_compact_ms(usearch_index_t h, float *out, usearch_error_t *e)
 try {
