@@ -908,6 +908,35 @@ LANTERN_GPU_EXPORT int lantern_gpu_add_compact(usearch_index_t, usearch_error_t 
  *          [8] dynamic LDS of the k_insert launch  [9] its LDS visited-set slots  [10] keys per lane of its register list (0: the LDS
  *          list)  [11] lanes per row.  Byte counts as (low, high) words.  Returns NULL, or why the input is refused. */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_add_compact(const int64_t in[16], uint32_t out[12]);
+/* QUANTISING ROWS IN ONE LAUNCH (DESIGN.md 4.7 "Encoding in one launch").  Every code byte of a pq index is the nearest centroid of a
+ * subvector under the index metric, the first minimum winning.  on = 0, THE DEFAULT: one pass per subvector (the subvector copied out,
+ * an exact k-NN with k = 1 against the centroids, the answer written back).  on = 1: where the shape is served -- l2sq / cos, subvectors
+ * of at most 32 scalars, at most 256 centroids -- a piece of rows becomes ALL its code bytes in one launch of k_pq_encode, which
+ * evaluates every (subvector, centroid) pair in the pair kernel's summation order and keeps the smallest (distance, centroid): the same
+ * bytes, bit for bit.  Builds, loads of raw rows, collective adds and adds to a compact index (lantern_gpu_set_add_compact) all encode
+ * through it; a shape that is not served runs the passes as with 0 and is never an error.  on other than 0 or 1 is refused. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_pq_encode_fused(usearch_index_t, int on, usearch_error_t *);
+/* diagnostic: 0 the switch is off; 1 it is on but this index's rows are still encoded by the passes (or it is not a pq index); 2 they are
+ * encoded by k_pq_encode */
+LANTERN_GPU_EXPORT int lantern_gpu_pq_encode_fused(usearch_index_t, usearch_error_t *);
+/* The decision above without a device (a pure function).
+ * in[8]:  [0] metric (usearch_metric_kind_t)  [1] dimensions  [2] num_subvectors (divides the dimensions)  [3] num_centroids
+ *         [4] rows of one launch  [5] the switch  [6..7] 0
+ * out[8]: [0] 1: served  [1] why not: 0 it is, 1 the switch is off, 2 the metric, 3 a subvector of more than 32 scalars, 4 more than 256
+ *         centroids, 5 one subvector's centroids and one wave of rows do not fit the LDS of a launch  [2] subvectors of a strip
+ *         [3] [4] the grid: blocks of 256 rows x strips  [5] dynamic LDS of a workgroup  [6] launches per piece  [7] 16-byte chunks of a
+ *         zero-padded subvector.  [2..7] are 0 unless served.  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_pq_encode(const int64_t in[8], uint32_t out[8]);
+/* The last encode made by the calling thread (an add, a load of raw rows, lantern_gpu_pq_encode): out[4] = pieces of rows staged or
+ * taken, k_pq_encode launches, per-subvector passes, rows. */
+LANTERN_GPU_EXPORT void lantern_gpu_last_pq_encode(uint32_t out[4]);
+/* quantize_table (lantern.sql:256-395) without an index: codes[n][num_subvectors] of n rows of `dimensions` f32 under `metric` (cos or
+ * l2sq), and, unless NULL, out_distance[n][num_subvectors], the distance of every subvector to the centroid it took.  codebook:
+ * num_centroids rows of `dimensions` floats, as usearch_init takes it.  The bytes are those an index with that codebook stores
+ * for the rows.  Rows go through staging pieces of at most 65536; always one launch per piece where the shape is served. */
+LANTERN_GPU_EXPORT void lantern_gpu_pq_encode(const float *rows, size_t n, size_t dimensions, const float *codebook, size_t num_subvectors,
+                                              size_t num_centroids, usearch_metric_kind_t metric, uint8_t *codes, float *out_distance,
+                                              usearch_error_t *);
 /* HBM held by the index: the vector block (the code rows of a compact pq index) | adjacency, labels, levels, norms, codes.  A compact
  * pq index: row_bytes counts the code rows IN USE, size x the code row stride; after a reserve or an add under
  * lantern_gpu_set_add_compact the block itself holds capacity rows, zero filled beyond the size. */

@@ -146,6 +146,8 @@ EXPORTS = [
     "lantern_gpu_export_screen", "lantern_gpu_screen_probe",
     # deleting rows (lantern_gpu.h "Deleting rows")
     "lantern_gpu_remove_labels", "lantern_gpu_deleted_count", "lantern_gpu_unlink_deleted", "lantern_gpu_compact_deleted", "lantern_gpu_plan_compact", "lantern_gpu_last_compact_ms",
+    # quantising rows in one launch (lantern_gpu.h "QUANTISING ROWS IN ONE LAUNCH")
+    "lantern_gpu_set_pq_encode_fused", "lantern_gpu_pq_encode_fused", "lantern_gpu_plan_pq_encode", "lantern_gpu_last_pq_encode", "lantern_gpu_pq_encode",
 ]
 # lantern_gpu_query_params: one row {k, ef, skip, reserved} per query (ef 0 = the index's default; reserved must be 0)
 QUERY_PARAMS = np.dtype([("k", np.uint32), ("ef", np.uint32), ("skip", np.uint32), ("reserved", np.uint32)])
@@ -256,6 +258,11 @@ def lib() -> C.CDLL:
         "lantern_gpu_set_add_compact": (None, [vp, C.c_int, err]),
         "lantern_gpu_add_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_add_compact": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_set_pq_encode_fused": (None, [vp, C.c_int, err]),
+        "lantern_gpu_pq_encode_fused": (C.c_int, [vp, err]),
+        "lantern_gpu_plan_pq_encode": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_last_pq_encode": (None, [vp]),
+        "lantern_gpu_pq_encode": (None, [vp, sz, sz, vp, sz, sz, i32, vp, vp, err]),
         "lantern_gpu_set_delete_compact": (None, [vp, C.c_int, err]),
         "lantern_gpu_delete_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_delete_compact": (C.c_char_p, [vp, vp]),
@@ -597,6 +604,43 @@ def plan_add_compact(mcode, chunks, M0, efc, rows, cap, on, compact, pqd_inv, co
     size = lambda i: int(out[i]) | int(out[i + 1]) << 32
     return {"served": bool(out[0]), "why": ADD_COMPACT_WHY[int(out[1])], "mcode": int(out[2]), "stage_rows": int(out[3]), "stage_bytes": size(4),
             "expand_bytes": size(6), "lds": int(out[8]), "vis_slots": int(out[9]), "kpl": int(out[10]), "lanes": int(out[11])}
+
+
+# lantern_gpu_plan_pq_encode's out[1], by value
+PQ_ENCODE_WHY = ("served", "off", "metric", "subdim", "centroids", "lds")
+
+
+def plan_pq_encode(metric, dims, num_subvectors, num_centroids, rows=65536, on=True):
+    """lantern_gpu_plan_pq_encode: whether rows of this shape are quantised by one k_pq_encode launch per piece (host arithmetic, no
+    device): {"served", "why" (PQ_ENCODE_WHY), "strip", "grid", "lds", "launches", "chunks"}."""
+    pin = np.array([METRICS.get(metric, metric), dims, num_subvectors, num_centroids, rows, int(on), 0, 0], np.int64)
+    out = np.zeros(8, np.uint32)
+    why = lib().lantern_gpu_plan_pq_encode(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    return {"served": bool(out[0]), "why": PQ_ENCODE_WHY[int(out[1])], "strip": int(out[2]), "grid": (int(out[3]), int(out[4])), "lds": int(out[5]),
+            "launches": int(out[6]), "chunks": int(out[7])}
+
+
+def last_pq_encode():
+    """lantern_gpu_last_pq_encode: the calling thread's last encode as {"pieces", "fused", "passes", "rows"}."""
+    out = np.zeros(4, np.uint32)
+    lib().lantern_gpu_last_pq_encode(_ptr(out))
+    return dict(zip(("pieces", "fused", "passes", "rows"), (int(v) for v in out)))
+
+
+def pq_encode(rows, codebook, num_subvectors, metric, distances=True):
+    """lantern_gpu_pq_encode (quantize_table without an index): (codes[n][num_subvectors] u8, distances[n][num_subvectors] f32 or None) of
+    f32 rows under the codebook [num_centroids][dims], the layout GpuIndex takes it in."""
+    X = np.ascontiguousarray(rows, dtype=np.float32)
+    B = np.ascontiguousarray(codebook, dtype=np.float32)
+    if X.ndim != 2 or B.ndim != 2 or X.shape[1] != B.shape[1]:
+        raise LanternGpuError("pq_encode: rows and codebook must be 2-d with the same dimensions")
+    codes = np.zeros((X.shape[0], int(num_subvectors)), dtype=np.uint8)
+    dist = np.zeros(codes.shape, dtype=np.float32) if distances else None
+    _call("lantern_gpu_pq_encode", _ptr(X), X.shape[0], X.shape[1], _ptr(B), int(num_subvectors), B.shape[0], METRICS.get(metric, metric), _ptr(codes),
+          _ptr(dist))
+    return codes, dist
 
 
 # lantern_gpu_plan_delete_compact's out[1], by value
@@ -1056,6 +1100,15 @@ class GpuIndex:
     def add_compact(self):
         """lantern_gpu_add_compact: 0 the switch is off, 1 the next add would still expand the index, 2 it is served from the code rows."""
         return int(_call("lantern_gpu_add_compact", self.h))
+
+    def set_pq_encode_fused(self, on):
+        """rows of this pq index are quantised by one k_pq_encode launch per piece where the shape is served (1), or by one nearest-centroid
+        pass per subvector (0, the default): the same bytes."""
+        _call("lantern_gpu_set_pq_encode_fused", self.h, int(on))
+
+    def pq_encode_fused(self):
+        """lantern_gpu_pq_encode_fused: 0 the switch is off, 1 this index's rows are still encoded by the passes, 2 by k_pq_encode."""
+        return int(_call("lantern_gpu_pq_encode_fused", self.h))
 
     def set_delete_compact(self, on):
         """unlink_deleted and compact_deleted run on this index's code rows in its compact pq form and leave it compact (1), or refuse it (0, the default)."""

@@ -181,9 +181,25 @@ bool pq_encode_rows(Index *ix, size_t first, size_t count)
 {
     if(!ix->pq || count == 0) return true;
     const uint32_t sub_chunks = (ix->pq_subdim + 3) / 4, sub_floats = sub_chunks * 4, row_floats = ix->chunks * 4;
+    PqEncodeRecord &rec = last_pq_encode();
+    rec = PqEncodeRecord{ 1u, 0u, 0u, (uint32_t)count };
+    if(plan_pq_encode(ix->metric, ix->pq_S * ix->pq_subdim, ix->pq_S, ix->pq_C, count, ix->pq_encode_fused).why == kPqEncodeServed) {
+        // lantern_gpu_set_pq_encode_fused: every code byte of the rows in one launch, then the decodings over the same slots -- the
+        // centroid values k_pq_put copies subvector by subvector (the rows' padding is zero before and after)
+        const PqEncodeArgs a = { (const float *)ix->d_vec + first * row_floats, row_floats, (uint32_t)count, (uint32_t)first, ix->pq_subdim, ix->pq_S, ix->pq_C,
+                                 ix->d_centers, ix->d_codes, nullptr, 0u, nullptr };
+        rec.fused = 1;
+        const bool done = launch_pq_encode(ix->metric, a, ix->stream) == hipSuccess &&
+                          launch_pq_decode((float *)ix->d_vec, row_floats, (uint32_t)first, (uint32_t)count, ix->pq_subdim, ix->pq_S, ix->d_codebook,
+                                           (uint32_t)ix->opts.dimensions, ix->d_codes, ix->stream) == hipSuccess &&
+                          hipStreamSynchronize(ix->stream) == hipSuccess;
+        if(!done) set_err(ix, "lantern_gpu: HIP failure while quantising vectors");
+        return done;
+    }
     float    *d_sub = nullptr;
     uint32_t *d_near = nullptr;
     bool ok = hipMalloc((void **)&d_sub, count * (size_t)sub_floats * 4) == hipSuccess && hipMalloc((void **)&d_near, count * 8) == hipSuccess;
+    rec.passes = ix->pq_S;
     for(uint32_t sv = 0; ok && sv < ix->pq_S; ++sv) {
         ok = ok && launch_pq_take((const float *)ix->d_vec, row_floats, (uint32_t)first, (uint32_t)count, sv, ix->pq_subdim, sub_floats, d_sub, ix->stream) == hipSuccess;
         ok = ok && exact_knn_device(ix->metric, sub_chunks, (const uint4 *)(ix->d_centers + (size_t)sv * ix->pq_C * sub_floats), ix->pq_C, (const uint4 *)d_sub,
@@ -208,15 +224,26 @@ static bool pq_encode_codes(Index *ix, const float *h_rows, size_t first, size_t
 {
     const uint32_t sub_chunks = (ix->pq_subdim + 3) / 4, sub_floats = sub_chunks * 4, row_floats = ix->chunks * 4;
     const size_t   piece = std::min(count, kAddCompactStageRows);
+    // lantern_gpu_set_pq_encode_fused: a piece is ONE k_pq_encode launch that writes both code arrays; no d_sub, no d_near
+    const bool fused = plan_pq_encode(ix->metric, ix->pq_S * ix->pq_subdim, ix->pq_S, ix->pq_C, piece, ix->pq_encode_fused).why == kPqEncodeServed;
+    PqEncodeRecord &rec = last_pq_encode();
+    rec = PqEncodeRecord{ 0u, 0u, 0u, (uint32_t)count };
     float    *d_stage = nullptr, *d_sub = nullptr;
     uint32_t *d_near = nullptr;
-    bool ok = hipMalloc((void **)&d_stage, piece * (size_t)row_floats * 4) == hipSuccess && hipMalloc((void **)&d_sub, piece * (size_t)sub_floats * 4) == hipSuccess &&
-              hipMalloc((void **)&d_near, piece * 8) == hipSuccess;
+    bool ok = hipMalloc((void **)&d_stage, piece * (size_t)row_floats * 4) == hipSuccess;
+    if(!fused) ok = ok && hipMalloc((void **)&d_sub, piece * (size_t)sub_floats * 4) == hipSuccess && hipMalloc((void **)&d_near, piece * 8) == hipSuccess;
     if(!ok) set_err(ix, "lantern_gpu: out of device memory (staging rows for a compact pq index)");
     for(size_t at = 0; ok && at < count; at += piece) {
         const size_t m = std::min(piece, count - at);
         ok = hipMemcpyAsync(d_stage, h_rows + at * row_floats, m * (size_t)row_floats * 4, hipMemcpyHostToDevice, ix->stream) == hipSuccess;
-        for(uint32_t sv = 0; ok && sv < ix->pq_S; ++sv) {
+        ++rec.pieces;
+        if(fused) {
+            const PqEncodeArgs a = { d_stage, row_floats, (uint32_t)m, (uint32_t)(first + at), ix->pq_subdim, ix->pq_S, ix->pq_C, ix->d_centers, ix->d_codes,
+                                     ix->d_codes16, ix->pq_S16, nullptr };
+            ok = ok && launch_pq_encode(ix->metric, a, ix->stream) == hipSuccess;
+            ++rec.fused;
+        } else rec.passes += ix->pq_S;
+        for(uint32_t sv = 0; ok && !fused && sv < ix->pq_S; ++sv) {
             ok = ok && launch_pq_take(d_stage, row_floats, 0, (uint32_t)m, sv, ix->pq_subdim, sub_floats, d_sub, ix->stream) == hipSuccess;
             ok = ok && exact_knn_device(ix->metric, sub_chunks, (const uint4 *)(ix->d_centers + (size_t)sv * ix->pq_C * sub_floats), ix->pq_C, (const uint4 *)d_sub, m,
                                         1, d_near, (float *)(d_near + m), ix->stream);
@@ -2458,6 +2485,29 @@ try {
 catch(...) {
     return kAbiException;
 }
+
+// Rows quantised by one launch per piece (include/lantern_gpu.h; plan_pq_encode, pq_encode.hip)
+void lantern_gpu_set_pq_encode_fused(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) { FAIL(e, "lantern_gpu: pq_encode_fused must be 0 (one nearest-centroid pass per subvector) or 1 (one launch per piece where the shape is served)"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->pq_encode_fused = on != 0;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_pq_encode_fused(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if(!ix->pq_encode_fused) return 0;
+    return ix->pq && plan_pq_encode(ix->metric, ix->pq_S * ix->pq_subdim, ix->pq_S, ix->pq_C, 1, true).why == kPqEncodeServed ? 2 : 1;
+}
+LANTERN_ABI_CATCH(e)
 
 // HBM held by the index: the vector block (or the code rows of a compact pq index) | everything else that grows with the
 // number of nodes (adjacency, labels, levels, norms, re-prune state, codes)

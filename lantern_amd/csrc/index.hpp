@@ -246,6 +246,7 @@ struct Index
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     bool     exact_compact = false;     // lantern_gpu_set_exact_compact: lantern_gpu_exact_search answers a compact pq index from its code rows (default: it expands)
     bool     add_compact = false;       // lantern_gpu_set_add_compact: adds and reserves leave a compact pq index compact where plan_add_compact serves them (default: they expand)
+    bool     pq_encode_fused = false;   // lantern_gpu_set_pq_encode_fused: rows are quantised by one k_pq_encode launch per piece where plan_pq_encode serves the shape (default: the per-subvector passes)
     bool     delete_compact = false;    // lantern_gpu_set_delete_compact: unlink and compaction serve a compact pq index from its code rows where plan_delete_compact does (default: refused)
     size_t   filter_seeds = 0;          // lantern_gpu_set_filter_seeds: 0 off; > 0: the walk path starts from that many allowed rows
     uint32_t last_seeds[ 4 ] = {};      // lantern_gpu_last_filtered_seeds: [1] S' of the last single-filter walk launch, [2] [3] the last call's seeded / unseeded walk queries ([0] is filter_seeds)

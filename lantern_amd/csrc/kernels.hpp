@@ -285,6 +285,49 @@ hipError_t launch_pq_put_codes(uint32_t first, uint32_t count, uint32_t s, uint3
 hipError_t launch_pq_decode(float *rows, uint32_t row_floats, uint32_t first, uint32_t count, uint32_t subdim, uint32_t S, const float *codebook, uint32_t dims,
                             const uint8_t *codes, hipStream_t stream);
 
+// ---- the fused encoder (pq_encode.hip; DESIGN.md 4.7 "Encoding in one launch"): k_pq_encode turns a block of f32 rows into ALL their code
+// bytes -- per (row, subvector) the centroid of the smallest make_key(D, c), D the pair kernel's exact-order distance of the zero-padded
+// subvector -- in one launch: take + exact k-NN + put of every subvector, bit for bit.  plan_pq_encode (pure: no HIP call, no getenv)
+// says whether a shape is served and how the launch is cut; a shape that is not served keeps the per-subvector passes.
+enum PqEncodeWhy : int
+{
+    kPqEncodeServed = 0,
+    kPqEncodeOff,        // the switch is 0 (lantern_gpu_set_pq_encode_fused)
+    kPqEncodeMetric,     // not l2sq / cos
+    kPqEncodeSubdim,     // a subvector of more than 32 scalars: more than one chunk per lane of the pair kernel's 8-lane group
+    kPqEncodeCentroids,  // more than 256 centroids: the code is a byte
+    kPqEncodeLds         // one subvector's centroid table and one wave of rows exceed kPqEncodeLdsMax
+};
+constexpr uint32_t kPqEncodeRows = 256;       // rows of a workgroup: one per thread
+constexpr size_t   kPqEncodeLdsMax = 65536;   // dynamic LDS a launch may ask for without opting in
+struct PqEncodePlan
+{
+    PqEncodeWhy why = kPqEncodeOff;
+    uint32_t    SC = 0;          // served: 16-byte chunks of a zero-padded subvector (k_pq_encode's template argument)
+    uint32_t    T = 0;           // served: subvectors of a strip
+    uint32_t    grid_x = 0, grid_y = 0;  // served: blocks of kPqEncodeRows rows x strips
+    size_t      lds = 0;         // served: the strip's centroid tables + its floats of kPqEncodeRows rows
+    uint32_t    launches = 0;    // served: launches per piece (1)
+};
+// dims = S x the subvector's scalars; rows = the rows of one launch
+PqEncodePlan plan_pq_encode(int metric, uint32_t dims, uint32_t S, uint32_t C, size_t rows, bool on);
+struct PqEncodeArgs
+{
+    const float *rows;        // [count][row_floats]: row i becomes the code row of slot first + i
+    uint32_t     row_floats, count, first;
+    uint32_t     subdim, S, C;
+    const float *centers;     // [S][C][SC * 4] the per-subvector centroid tables, zero padded (Index::d_centers)
+    uint8_t     *codes;       // codes[first + i][sv] at stride S
+    uint8_t     *codes16;     // NULL, or the same byte at stride S16 (the padding is not written)
+    uint32_t     S16;
+    float       *out_distance;  // NULL, or out_distance[i][sv] = the winning D
+};
+// hipErrorInvalidValue where plan_pq_encode does not serve the shape
+hipError_t launch_pq_encode(int metric, const PqEncodeArgs &a, hipStream_t stream);
+// the last encode of the calling thread (lantern_gpu_last_pq_encode): pieces staged, k_pq_encode launches, per-subvector passes, rows
+struct PqEncodeRecord { uint32_t pieces = 0, fused = 0, passes = 0, rows = 0; };
+PqEncodeRecord &last_pq_encode();
+
 // f32 rows -> the stored rows of an f16 / i8 / b1 index, on the device (the rules of pad_row, element for element)
 hipError_t launch_merge_parts(const uint64_t *labels, const float *dists, uint32_t world, uint32_t nq, uint32_t k, uint64_t *out_labels,
                               float *out_dists, uint32_t *out_counts, hipStream_t stream);
