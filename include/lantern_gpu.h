@@ -712,6 +712,25 @@ LANTERN_GPU_EXPORT int lantern_gpu_exact_compact(usearch_index_t, usearch_error_
  *          fallback allocates if it runs  [8..9] not taken, compact: the f32 row block the call decodes the index into.  Byte counts
  *          as (low, high) words.  Returns NULL, or why the input is refused. */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_exact_compact(const int64_t in[10], uint32_t out[10]);
+/* ADC PRE-SELECTION (DESIGN.md 4.5 "Compact pq indexes: ADC pre-selection").  max_queries = 0, THE DEFAULT: a call that runs on the code
+ * rows pre-selects with k_dense_pq, as before this switch existed.  max_queries = m > 0: such a call of at most m queries builds one
+ * table per query (subvector x centroid partial distances, the ADC walk's entries) and pre-selects by scanning the code rows against
+ * them (k_scan_adc: one LDS lookup and one add per code byte) -- bound by the code bytes, not by the matrix pipe, at small batches.
+ * Everything behind the pre-selection is unchanged (selection, exact-order re-rank, certificate, fallback), so the answer is still the
+ * expanded index's: the same slots and distance bits, the same guarantee; the index stays compact.  Calls of more queries, indexes the
+ * code-row path does not serve, more than 128 subvectors and tables over 256 MB run as with 0: none is refused.  Negative: refused. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_exact_adc(usearch_index_t, int64_t max_queries, usearch_error_t *);
+LANTERN_GPU_EXPORT int64_t lantern_gpu_exact_adc(usearch_index_t, usearch_error_t *); /* the setting */
+/* The decision above without a device (a pure function; the entry point decides through it).
+ * in[13]: [0..9] lantern_gpu_plan_exact_compact's  [10] the max_queries setting  [11] the index's subvectors  [12] its centroids
+ * out[8]: [0] 1: the call scans  [1] why not: 0 it does, 1 the setting is 0, 2 the call does not run on the code rows, 3 more queries
+ *         than the setting, 4 the shape (subvectors > 128, centroids > 256, subvectors that do not fill the row), 5 the tables exceed
+ *         256 MB; and, when taken (0 otherwise): [2] T, queries of a scanning workgroup  [3] its threads  [4] its LDS bytes (T tables)
+ *         [5] rows of a table (subvectors rounded up to 16)  [6..7] (low, high) bytes of the call's table block.
+ * Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_exact_adc(const int64_t in[13], uint32_t out[8]);
+/* of the process: out[0] table-building launches (one per scanning run), out[1] scan launches (one per contraction step) */
+LANTERN_GPU_EXPORT void lantern_gpu_exact_adc_stats(uint64_t out[2]);
 
 /* Diagnostic for the measurement harness: HIP events around every launch of the MFMA contraction (k_dense_f32; k_dense_native on
  * f16 / i8 indexes) inside

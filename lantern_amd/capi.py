@@ -96,7 +96,7 @@ EXPORTS = [
     "lantern_gpu_version", "lantern_gpu_device_count",
     "lantern_gpu_set_seed", "lantern_gpu_set_add_batch", "lantern_gpu_add_many", "lantern_gpu_flush",
     "lantern_gpu_add_with_level", "lantern_gpu_search_batch", "lantern_gpu_search_batch_device", "lantern_gpu_search_batch_device_strided",
-    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_set_exact_compact", "lantern_gpu_exact_compact", "lantern_gpu_plan_exact_compact", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
+    "lantern_gpu_set_search_shape", "lantern_gpu_exact_search", "lantern_gpu_set_exact_compact", "lantern_gpu_exact_compact", "lantern_gpu_plan_exact_compact", "lantern_gpu_set_exact_adc", "lantern_gpu_exact_adc", "lantern_gpu_plan_exact_adc", "lantern_gpu_exact_adc_stats", "lantern_gpu_dense_profile", "lantern_gpu_exact_knn_stats", "lantern_gpu_dense_kind_stats", "lantern_gpu_plan_dense", "lantern_gpu_plan_exact_knn", "lantern_gpu_distance_gather",
     "lantern_gpu_host_alloc", "lantern_gpu_host_free", "lantern_gpu_save_stream", "lantern_gpu_pq_compact", "lantern_gpu_pq_expand", "lantern_gpu_set_add_compact", "lantern_gpu_add_compact", "lantern_gpu_plan_add_compact", "lantern_gpu_set_delete_compact", "lantern_gpu_delete_compact", "lantern_gpu_plan_delete_compact", "lantern_gpu_memory_usage", "lantern_gpu_spec_profile", "lantern_gpu_search_unique_rows", "lantern_gpu_search_row_trace", "lantern_gpu_last_search_grid", "lantern_gpu_last_gather_ms", "lantern_gpu_search_screen_stats",
     "lantern_gpu_set_insert_screen", "lantern_gpu_insert_screen_stats", "lantern_gpu_plan_insert",
     "lantern_gpu_distance_matrix", "lantern_gpu_assign_to_clusters", "lantern_gpu_graph_info_get", "lantern_gpu_export_graph", "lantern_gpu_import_graph",
@@ -255,6 +255,10 @@ def lib() -> C.CDLL:
         "lantern_gpu_set_exact_compact": (None, [vp, C.c_int, err]),
         "lantern_gpu_exact_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_exact_compact": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_set_exact_adc": (None, [vp, C.c_int64, err]),
+        "lantern_gpu_exact_adc": (C.c_int64, [vp, err]),
+        "lantern_gpu_plan_exact_adc": (C.c_char_p, [vp, vp]),
+        "lantern_gpu_exact_adc_stats": (None, [vp]),
         "lantern_gpu_set_add_compact": (None, [vp, C.c_int, err]),
         "lantern_gpu_add_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_add_compact": (C.c_char_p, [vp, vp]),
@@ -584,6 +588,29 @@ def plan_exact_compact(mcode, chunks, nb, nq, k, on, compact, pqd_inv, code_row_
     size = lambda i: int(out[i]) | int(out[i + 1]) << 32
     return {"taken": bool(out[0]), "why": EXACT_COMPACT_WHY[int(out[1])], "kind": int(out[2]), "mcode": int(out[3]), "run_bytes": size(4),
             "fallback_bytes": size(6), "expand_bytes": size(8)}
+
+
+# lantern_gpu_plan_exact_adc's out[1], by value
+EXACT_ADC_WHY = ("taken", "off", "not_compact", "many_queries", "shape", "budget")
+
+
+def plan_exact_adc(mcode, chunks, nb, nq, k, on, compact, pqd_inv, code_row_bytes, max_queries, subvectors, centroids, fused=-1):
+    """lantern_gpu_plan_exact_adc: whether an exact_search on the code rows pre-selects by table lookups (host arithmetic, no device):
+    {"taken", "why" (EXACT_ADC_WHY), "T", "block", "lds_bytes", "S16", "table_bytes"}."""
+    pin = np.array([mcode, chunks, nb, nq, k, int(on), int(compact), pqd_inv, code_row_bytes, fused, max_queries, subvectors, centroids], np.int64)
+    out = np.zeros(8, np.uint32)
+    why = lib().lantern_gpu_plan_exact_adc(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    return {"taken": bool(out[0]), "why": EXACT_ADC_WHY[int(out[1])], "T": int(out[2]), "block": int(out[3]), "lds_bytes": int(out[4]), "S16": int(out[5]),
+            "table_bytes": int(out[6]) | int(out[7]) << 32}
+
+
+def exact_adc_stats():
+    """lantern_gpu_exact_adc_stats: the process's {"tables", "scans"} launches of the ADC pre-selection."""
+    out = np.zeros(2, np.uint64)
+    lib().lantern_gpu_exact_adc_stats(_ptr(out))
+    return {"tables": int(out[0]), "scans": int(out[1])}
 
 
 # lantern_gpu_plan_add_compact's out[1], by value
@@ -1092,6 +1119,14 @@ class GpuIndex:
     def exact_compact(self):
         """lantern_gpu_exact_compact: 0 the switch is off, 1 exact_search reads stored rows (a compact index is expanded), 2 it runs on the code rows."""
         return int(_call("lantern_gpu_exact_compact", self.h))
+
+    def set_exact_adc(self, max_queries):
+        """exact_search calls of at most max_queries queries on the code rows pre-select by table lookups (0, the default: never)."""
+        _call("lantern_gpu_set_exact_adc", self.h, int(max_queries))
+
+    def exact_adc(self):
+        """lantern_gpu_exact_adc: the setting."""
+        return int(_call("lantern_gpu_exact_adc", self.h))
 
     def set_add_compact(self, on):
         """adds and reserves leave this index in its compact pq form, served from the code rows (1), or expand it first (0, the default)."""

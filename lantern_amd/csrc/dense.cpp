@@ -3,7 +3,8 @@
 // the same run over a filter's slot list is the filtered exact path's dense route (plan_filtered_dense, filtered_dense_device), and over
 // the concatenated lists of a per-query-filter call's groups, segment by segment, that call's (plan_filtered_each_dense,
 // filtered_each_dense_device).
-// The kernels: bruteforce.hip, dense_native.hip, dense_pq.hip (the code rows of a compact pq index: plan_exact_compact); the two launchers this unit calls them through: kernels.hpp.
+// The kernels: bruteforce.hip, dense_native.hip, dense_pq.hip (the code rows of a compact pq index: plan_exact_compact), dense_adc.hip (the same rows by table
+// lookups: plan_exact_adc); the launchers this unit calls them through: kernels.hpp.
 #include "dense.hpp"
 #include "index.hpp"
 #include "abi_guard.hpp"
@@ -33,6 +34,7 @@ std::atomic<uint64_t> g_dense_kind[ 3 ];  // MFMA contraction launches of the pr
 // lantern_gpu_exact_knn_stats: queries of every exact k-NN of the process, how many the certificate passed, how many took the
 // exact-order fallback
 std::atomic<uint64_t> g_knn_queries{ 0 }, g_knn_certified{ 0 }, g_knn_fallback{ 0 };
+std::atomic<uint64_t> g_adc_tables{ 0 }, g_adc_scans{ 0 };  // lantern_gpu_exact_adc_stats: k_adc_tables and k_scan_adc launches of the process
 
 // lantern_gpu_dense_profile: HIP events around every launch of the fp32-MFMA contraction inside the exact k-NN (bench.py's
 // c3_dense_exact_knn leg: the duration of steady full-chunk launches apart from the cold first ones and the partial last chunk).
@@ -73,8 +75,8 @@ struct DenseTimer  // records event `a` now and `b` on destruction, on the launc
 struct KnnPool
 {
     std::mutex mu;
-    void      *p[ 4 ] = { nullptr, nullptr, nullptr, nullptr };  // (3: a gathered chunk of a run over a slot list, pooled up to kGatherPoolMax)
-    size_t     bytes[ 4 ] = { 0, 0, 0, 0 };
+    void      *p[ 5 ] = {};  // (3: a gathered chunk of a run over a slot list, pooled up to kGatherPoolMax; 4: the tables of an ADC pre-selection, up to kAdcTablesMax)
+    size_t     bytes[ 5 ] = {};
 };
 KnnPool g_knn_pool[ 16 ];
 constexpr size_t kKnnPoolMax = (size_t)64 << 20;
@@ -228,11 +230,12 @@ static std::vector<KnnStep> plan_steps(const ExactKnnPlan &p)
 // the list only; everything behind the contractions is per query and runs unchanged).
 // queued: NULL, or what the caller queues behind the certificate and in front of the wait, given the device flags (NULL: exact keys).
 // pq (p.kind == kDensePq, d_list NULL): d_base is code rows; a row's stride is pq->row_bytes, everything else is the f32 rows' run.
+// adc (pq only): the queries' tables are built once behind the norms, and every step of the SAME list goes to the scan.
 static bool exact_knn_run(const ExactKnnPlan &p, const std::vector<KnnStep> &steps, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q,
                           uint32_t *d_slots, float *d_dists, hipStream_t st, bool *overflowed, std::vector<uint32_t> &certified,
-                          const EachDenseAnswers *queued = nullptr, const DensePqRows *pq = nullptr, EachDenseRun *run = nullptr)
+                          const EachDenseAnswers *queued = nullptr, const DensePqRows *pq = nullptr, EachDenseRun *run = nullptr, const ExactAdcPlan *adc = nullptr)
 try {
-    if((p.kind == kDensePq) != (pq != nullptr) || (pq && d_list)) return false;
+    if((p.kind == kDensePq) != (pq != nullptr) || (pq && d_list) || (adc && (!pq || adc->why != kExactAdcTaken))) return false;
     // the batched form of the segmented run: one contraction and one selection launch per batch, from the call's two device tables
     const EachDenseBatches *const seg = run && run->batches && run->batches->why == kEachBatchTaken ? run->batches : nullptr;
     if(seg && (!d_list || p.kind != 0 || p.copy || p.bits || !run->d_tiles || !run->d_queries || seg->off.size() != steps.size())) return false;
@@ -250,7 +253,7 @@ try {
         int         live = std::uncaught_exceptions();
         ~SyncOnUnwind() { if(std::uncaught_exceptions() > live) (void)hipStreamSynchronize(st); }
     };
-    DeviceBlock b_aux, b_dd, b_cand, b_fq, b_fb, b_gb;  // (fq, fb: f32 copies of quantised rows -- the queries; one chunk of base rows.  gb: a gathered chunk)
+    DeviceBlock b_aux, b_dd, b_cand, b_fq, b_fb, b_gb, b_tab;  // (fq, fb: f32 copies of quantised rows -- the queries; one chunk of base rows.  gb: a gathered chunk.  tab: ADC tables)
     const SyncOnUnwind sync_on_unwind{ st };  // (declared last: destroyed first)
     const uint32_t nq = (uint32_t)p.nq, nb = (uint32_t)p.nb, kk = p.kk, chunks = p.chunks, fchunks = p.fchunks;
     const int      base_metric = mcode_base(p.mcode);
@@ -261,6 +264,9 @@ try {
     if(ok && p.fused) ok = b_cand.get(p.cand_bytes, pool, 2) && hipMemsetAsync(b_cand.as<char>() + p.cnt_off, 0, p.cand_bytes - p.cnt_off, st) == hipSuccess;
     if(ok && p.copy) ok = b_fq.get(p.fq_bytes) && b_fb.get(p.fb_bytes) && dequant(d_q, p.nq * chunks, b_fq.as<uint4>()) == hipSuccess;
     if(ok && d_list) ok = p.gb_bytes >= (size_t)p.chunk_rows * chunks * 16 && b_gb.get(p.gb_bytes, pool, 3, kGatherPoolMax);
+    // (the plan's table rows are the launchers': the subvectors that fill a decoded row, rounded up to 16)
+    if(ok && adc) ok = pq->cps != 0 && adc->S16 == (p.chunks / pq->cps + 15) / 16 * 16 && adc->table_bytes >= p.nq * adc_table_bytes(adc->S16) &&
+                       b_tab.get(adc->table_bytes, pool, 4, kAdcTablesMax);
     if(ok) {
         char *const     aux = b_aux.as<char>();
         float *const    dd = b_dd.as<float>(), *qn = (float *)(aux + p.qn_off), *bn = (float *)(aux + p.bn_off);
@@ -273,7 +279,14 @@ try {
         const uint4    *qv = p.copy ? b_fq.as<uint4>() : d_q;
         ok = ok && hipMemsetAsync(best, 0xFF, p.nq * kk * 8, st) == hipSuccess;
         if(!p.bits) ok = ok && launch_norms(pq ? 0 : p.kind, base_metric, qv, nq, fchunks, qn, st) == hipSuccess;  // (the queries of a run over code rows are f32 rows)
-        if(!p.bits && !p.copy && !d_list) ok = ok && launch_norms(p.kind, base_metric, d_base, nb, fchunks, bn, st, pq) == hipSuccess;
+        // (the l2sq scan's key is the sum itself, and the l2sq certificate bounds |b| from the query: nobody would read the rows' norms)
+        const bool scan_l2 = adc && base_metric == M_L2SQ;
+        if(!p.bits && !p.copy && !d_list && !scan_l2) ok = ok && launch_norms(p.kind, base_metric, d_base, nb, fchunks, bn, st, pq) == hipSuccess;
+        const float *const tab = b_tab.as<float>();
+        if(adc) {
+            ok = ok && launch_adc_tables(base_metric, qv, nq, fchunks, *pq, b_tab.as<float>(), st) == hipSuccess;
+            ++g_adc_tables;
+        }
         size_t si = 0;
         for(size_t c0 = 0; ok && c0 < p.nb; c0 += p.chunk_rows) {
             const size_t nc = std::min<size_t>(p.chunk_rows, p.nb - c0);
@@ -308,7 +321,11 @@ try {
                 const DenseTopk     tk = { mine, kk, cand, ccnt, p.cand_cap, s.col0 };
                 {
                     DenseTimer t(st, s.nqt, s.cols, s.fused != 0 ? 1u : 0u);
-                    ok = ok && launch_contraction(o, dd, p.ldd, s.fused ? &tk : nullptr, st) == hipSuccess;
+                    if(adc) {
+                        ok = ok && launch_contraction_adc(o, tab + (size_t)s.q0 * adc->S16 * ADC_LUT_STRIDE, dd, p.ldd, s.fused ? &tk : nullptr, st) == hipSuccess;
+                        ++g_adc_scans;
+                    } else
+                        ok = ok && launch_contraction(o, dd, p.ldd, s.fused ? &tk : nullptr, st) == hipSuccess;
                     if(!p.bits && p.kind < 3) ++g_dense_kind[ p.kind ];
                 }
                 if(s.fused) ok = ok && launch_select_candidates(s.nqt, mine, kk, cand, ccnt, p.cand_cap, cover, st) == hipSuccess;
@@ -384,15 +401,15 @@ static bool exact_knn_fallback(int mcode, uint32_t chunks, const uint4 *d_base, 
 // overflowed.  certified: the flag of every query; refused: the queries without one, which the caller recomputes.
 static bool exact_knn_certified(const ExactKnnPlan &first, int native, const uint4 *d_base, const uint32_t *d_list, const uint4 *d_q, uint32_t *d_slots,
                                 float *d_dists, hipStream_t st, std::vector<uint32_t> &certified, std::vector<uint32_t> &refused,
-                                const DensePqRows *pq = nullptr)
+                                const DensePqRows *pq = nullptr, const ExactAdcPlan *adc = nullptr)
 {
     bool over = false;
-    if(!exact_knn_run(first, plan_steps(first), d_base, d_list, d_q, d_slots, d_dists, st, &over, certified, nullptr, pq)) return false;
+    if(!exact_knn_run(first, plan_steps(first), d_base, d_list, d_q, d_slots, d_dists, st, &over, certified, nullptr, pq, nullptr, adc)) return false;
     if(over) {  // the same call, unfused
         ExactKnnPlan plan;
         if(plan_exact_knn(first.mcode, first.chunks, (int64_t)first.nb, (int64_t)first.nq, (int64_t)first.k, native, 0, plan) != nullptr) return false;
         plan.gb_bytes = first.gb_bytes;
-        if(!exact_knn_run(plan, plan_steps(plan), d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified, nullptr, pq)) return false;
+        if(!exact_knn_run(plan, plan_steps(plan), d_base, d_list, d_q, d_slots, d_dists, st, nullptr, certified, nullptr, pq, nullptr, adc)) return false;
     }
     refused.clear();
     for(size_t q = 0; q < first.nq; ++q)
@@ -572,13 +589,13 @@ LANTERN_ABI_CATCH(nullptr)
 // fp32- or native-MFMA contraction in chunks of 64k base rows + running top-(k+16) + exact-order re-rank, then per query the certificate
 // that the top-(k+16) held the exact answer; the refused queries are recomputed in exact order.
 bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k, uint32_t *d_slots,
-                      float *d_dists, hipStream_t st, const DensePqRows *pq)
+                      float *d_dists, hipStream_t st, const DensePqRows *pq, const ExactAdcPlan *adc)
 try {
     const DenseEnv        env = dense_env();
     ExactKnnPlan          plan;
     std::vector<uint32_t> certified, refused;
     if(plan_exact_knn(mcode, chunks, (int64_t)nb, (int64_t)nq, (int64_t)k, env.native, env.fused, plan) != nullptr) return false;
-    if(!exact_knn_certified(plan, env.native, d_base, nullptr, d_q, d_slots, d_dists, st, certified, refused, pq)) return false;
+    if(!exact_knn_certified(plan, env.native, d_base, nullptr, d_q, d_slots, d_dists, st, certified, refused, pq, adc)) return false;
     g_knn_queries += nq;
     g_knn_certified += nq - refused.size();
     g_knn_fallback += refused.size();
@@ -607,6 +624,31 @@ const char *plan_exact_compact(int64_t mcode, int64_t chunks, int64_t nb, int64_
     if(const char *why = plan_exact_knn(p.mcode, chunks, nb, nq, k, -1, fused, p.knn)) return why;
     p.run_bytes = p.knn.aux_bytes + p.knn.dd_bytes + p.knn.cand_bytes + p.knn.fq_bytes + p.knn.fb_bytes + p.knn.gb_bytes;  // (the last three: 0)
     p.fallback_bytes = (size_t)p.knn.chunk_rows * p.knn.chunks * 16;
+    return nullptr;
+}
+
+// ---- the same call's pre-selection by table lookups ---------------------------------------------------------------------------------
+const char *plan_exact_adc(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, bool on, bool compact, uint32_t pqd_inv, uint32_t pq_S16, int fused,
+                           int64_t max_queries, int64_t S, int64_t C, ExactAdcPlan &p)
+{
+    p = ExactAdcPlan();
+    if(max_queries < 0 || S < 0 || C < 0 || S > 0xFFFFFFFFll || C > 0xFFFFFFFFll) return kBadPlan;
+    ExactCompactPlan c;
+    if(const char *why = plan_exact_compact(mcode, chunks, nb, nq, k, on, compact, pqd_inv, pq_S16, fused, c)) return why;
+    const uint32_t S16 = (uint32_t)std::min<int64_t>((S + 15) / 16 * 16, 0xFFFFFFF0ll);
+    // the order of the reasons is the order the call meets them in: the switch, the code rows, the batch, the tables' shape, their size
+    if(max_queries == 0) p.why = kExactAdcOff;
+    else if(c.why != kExactCompactTaken) p.why = kExactAdcNotCompact;
+    else if(nq > max_queries) p.why = kExactAdcManyQueries;
+    else if(S == 0 || C == 0 || S16 > 128 || S16 > pq_S16 || C > ADC_LUT_STRIDE || chunks % S != 0 || adc_scan_T(S16) == 0) p.why = kExactAdcShape;
+    else if((uint64_t)nq * adc_table_bytes(S16) > kAdcTablesMax) p.why = kExactAdcBudget;
+    else p.why = kExactAdcTaken;
+    if(p.why != kExactAdcTaken) return nullptr;
+    p.S16 = S16;
+    p.T = adc_scan_T(S16);
+    p.block = kAdcScanBlock;
+    p.lds_bytes = p.T * adc_table_bytes(S16);
+    p.table_bytes = (size_t)nq * adc_table_bytes(S16);
     return nullptr;
 }
 
@@ -850,6 +892,35 @@ catch(...) {
     return kAbiException;
 }
 
+const char *lantern_gpu_plan_exact_adc(const int64_t in[ 13 ], uint32_t out[ 8 ])
+try {
+    if(!in || !out) return "lantern_gpu: null plan array";
+    if(in[ 7 ] < 0 || in[ 7 ] > 0xFFFFFFFFll || in[ 8 ] < 0 || in[ 8 ] > 0xFFFFFFFFll) return kBadPlan;
+    ExactAdcPlan p;
+    if(const char *why = plan_exact_adc(in[ 0 ], in[ 1 ], in[ 2 ], in[ 3 ], in[ 4 ], in[ 5 ] != 0, in[ 6 ] != 0, (uint32_t)in[ 7 ], (uint32_t)in[ 8 ],
+                                        in[ 9 ] < 0 ? -1 : in[ 9 ] != 0, in[ 10 ], in[ 11 ], in[ 12 ], p))
+        return why;
+    out[ 0 ] = p.why == kExactAdcTaken ? 1u : 0u;
+    out[ 1 ] = (uint32_t)p.why;
+    out[ 2 ] = p.T;
+    out[ 3 ] = p.block;
+    out[ 4 ] = (uint32_t)p.lds_bytes;
+    out[ 5 ] = p.S16;
+    out[ 6 ] = (uint32_t)p.table_bytes;
+    out[ 7 ] = (uint32_t)((uint64_t)p.table_bytes >> 32);
+    return nullptr;
+}
+catch(...) {
+    return kAbiException;
+}
+
+void lantern_gpu_exact_adc_stats(uint64_t out[ 2 ])
+{
+    if(!out) return;
+    out[ 0 ] = g_adc_tables.load();
+    out[ 1 ] = g_adc_scans.load();
+}
+
 void lantern_gpu_dense_kind_stats(uint64_t launches[ 3 ])
 {
     if(!launches) return;
@@ -919,6 +990,27 @@ try {
 }
 LANTERN_ABI_CATCH_VOID(e)
 
+void lantern_gpu_set_exact_adc(usearch_index_t h, int64_t max_queries, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(max_queries < 0) { FAIL(e, "lantern_gpu: exact_adc must be 0 (off) or the largest batch that pre-selects by table lookups"); return; }
+    Index *ix = H(h, e);
+    if(!ix) return;
+    std::lock_guard<std::mutex> g(ix->mu);
+    ix->exact_adc = max_queries;
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int64_t lantern_gpu_exact_adc(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    Index *ix = H(h, e);
+    if(!ix) return 0;
+    std::lock_guard<std::mutex> g(ix->mu);
+    return ix->exact_adc;
+}
+LANTERN_ABI_CATCH(e)
+
 int lantern_gpu_exact_compact(usearch_index_t h, usearch_error_t *e)
 try {
     CLEAR(e);
@@ -958,7 +1050,11 @@ try {
     float    *d_dists = (float *)(d_slots + nq * k);
     hipStream_t st = ix->stream;
     bool ok = hipMemcpyAsync(dq, padded.data(), nq * row_words * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-    if(on_codes) ok = ok && exact_knn_device(ix->mcode + M_PQD, ix->chunks, (const uint4 *)ix->d_codes16, n, dq, nq, k, d_slots, d_dists, st, &pq);
+    // ... and pre-selects by table lookups where lantern_gpu_set_exact_adc and plan_exact_adc say so (a refused plan input: the contraction, as ever)
+    ExactAdcPlan adc;
+    const bool   scan = on_codes && plan_exact_adc(ix->mcode, ix->chunks, (int64_t)n, (int64_t)nq, (int64_t)k, ix->exact_compact, ix->pq_compact, ix->pqd_inv, ix->pq_S16,
+                                                   dense_env().fused, ix->exact_adc, ix->pq_S, ix->pq_C, adc) == nullptr && adc.why == kExactAdcTaken;
+    if(on_codes) ok = ok && exact_knn_device(ix->mcode + M_PQD, ix->chunks, (const uint4 *)ix->d_codes16, n, dq, nq, k, d_slots, d_dists, st, &pq, scan ? &adc : nullptr);
     else ok = ok && exact_knn_device(ix->mcode, ix->chunks, ix->d_vec, n, dq, nq, k, d_slots, d_dists, st);
     ok = ok && hipMemcpy(slots, d_slots, nq * k * 4, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(distances, d_dists, nq * k * 4, hipMemcpyDeviceToHost) == hipSuccess;

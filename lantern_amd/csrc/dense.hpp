@@ -173,9 +173,11 @@ bool filtered_each_dense_device(const EachDensePlan &p, const uint4 *d_base, con
 // Result (device): slots[nq][k] ascending by (exact-order distance, slot), dists[nq][k].
 // pq (mcode M_L2SQ_PQD / M_COS_PQD): d_base is the CODE rows of a compact pq index, pq->row_bytes each, and `chunks` those of a decoded
 // row; nothing of nb x chunks x 16 bytes is allocated (lantern_gpu_set_exact_compact).
+// adc (pq only; NULL or a taken plan_exact_adc): every contraction step pre-selects by table lookups (k_scan_adc) instead of k_dense_pq.
 struct DensePqRows;
+struct ExactAdcPlan;
 bool exact_knn_device(int mcode, uint32_t chunks, const uint4 *d_base, size_t nb, const uint4 *d_q, size_t nq, size_t k, uint32_t *d_slots,
-                      float *d_dists, hipStream_t st, const DensePqRows *pq = nullptr);
+                      float *d_dists, hipStream_t st, const DensePqRows *pq = nullptr, const ExactAdcPlan *adc = nullptr);
 
 // lantern_gpu_exact_search on a compact pq index (DESIGN.md 4.5 "Compact pq indexes"): does the call run on the code rows, and if not
 // why.  lantern_gpu_plan_exact_compact shows it without a device; the entry point and lantern_gpu_exact_compact decide through it.
@@ -198,5 +200,31 @@ struct ExactCompactPlan
 };
 const char *plan_exact_compact(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, bool on, bool compact, uint32_t pqd_inv, uint32_t pq_S16,
                                int fused, ExactCompactPlan &p);
+
+// The same call's pre-selection by table lookups (DESIGN.md 4.5 "Compact pq indexes: ADC pre-selection"; lantern_gpu_set_exact_adc):
+// does a call that runs on the code rows scan them against per-query tables (k_scan_adc, dense_adc.hip) instead of contracting them
+// (k_dense_pq), and if not why.  lantern_gpu_plan_exact_adc shows it without a device; the entry point decides through it.
+enum ExactAdcWhy : uint32_t
+{
+    kExactAdcTaken = 0,
+    kExactAdcOff,          // lantern_gpu_set_exact_adc is 0
+    kExactAdcNotCompact,   // plan_exact_compact does not take the call: there are no code rows to scan
+    kExactAdcManyQueries,  // nq above the switch's value
+    kExactAdcShape,        // more than 128 subvectors or 256 centroids, or subvectors that do not fill the row
+    kExactAdcBudget        // the queries' tables exceed kAdcTablesMax
+};
+constexpr size_t kAdcTablesMax = (size_t)256 << 20;  // 2730 queries at 96 subvectors; pooled, so it stays with the process
+struct ExactAdcPlan
+{
+    ExactAdcWhy why = kExactAdcOff;
+    uint32_t    S16 = 0;          // taken (as all below): rows of a query's table -- the subvectors rounded up to 16
+    uint32_t    T = 0;            // queries of a scanning workgroup: the largest of 4, 2, 1 whose tables fit kAdcScanLdsMax
+    uint32_t    block = 0;        // its threads
+    size_t      lds_bytes = 0;    // its dynamic LDS: the T tables
+    size_t      table_bytes = 0;  // the call's table block: [nq][S16][ADC_LUT_STRIDE] f32
+};
+// the arguments of plan_exact_compact, then the switch's value, the index's subvectors and centroids
+const char *plan_exact_adc(int64_t mcode, int64_t chunks, int64_t nb, int64_t nq, int64_t k, bool on, bool compact, uint32_t pqd_inv, uint32_t pq_S16, int fused,
+                           int64_t max_queries, int64_t S, int64_t C, ExactAdcPlan &p);
 
 }  // namespace lgpu

@@ -245,6 +245,7 @@ struct Index
     uint32_t last_each_dense[ 6 ] = {};  // lantern_gpu_last_filtered_each_dense: dense groups, their queries, certified, recomputed, rows gathered, contraction steps
     bool     filter_compact = false;    // lantern_gpu_set_filter_compact: filtered searches serve this index in its compact pq form too (default: refused)
     bool     exact_compact = false;     // lantern_gpu_set_exact_compact: lantern_gpu_exact_search answers a compact pq index from its code rows (default: it expands)
+    int64_t  exact_adc = 0;             // lantern_gpu_set_exact_adc: such a call of at most this many queries pre-selects by table lookups (0: never)
     bool     add_compact = false;       // lantern_gpu_set_add_compact: adds and reserves leave a compact pq index compact where plan_add_compact serves them (default: they expand)
     bool     pq_encode_fused = false;   // lantern_gpu_set_pq_encode_fused: rows are quantised by one k_pq_encode launch per piece where plan_pq_encode serves the shape (default: the per-subvector passes)
     bool     delete_compact = false;    // lantern_gpu_set_delete_compact: unlink and compaction serve a compact pq index from its code rows where plan_delete_compact does (default: refused)

@@ -392,6 +392,26 @@ hipError_t launch_select_candidates(uint32_t nq, uint64_t *best, uint32_t kk, co
                                     hipStream_t stream);
 hipError_t launch_select(const float *dist, uint32_t ldo, uint32_t nq, uint32_t ncols, uint32_t c_base, uint64_t *best, uint32_t kk,
                          hipStream_t stream);
+// ---- ADC pre-selection on the code rows (dense_adc.hip; DESIGN.md 4.5 "Compact pq indexes: ADC pre-selection") ------------------------
+// A query's table is [S16][ADC_LUT_STRIDE] f32, S16 = the subvectors rounded up to 16 (NOT the rows' stride, which may be wider); a
+// workgroup of k_scan_adc keeps T of them in LDS: the largest of 4, 2, 1 that fits kAdcScanLdsMax (0: none does)
+constexpr size_t   kAdcScanLdsMax = 160 * 1024, kAdcScanLdsSpare = 1024;  // (the spare KB: a launch never asks for the CU's whole LDS)
+constexpr uint32_t kAdcScanBlock = 1024;  // threads of a scanning workgroup (profiles/dense_adc_kernel_resources.md)
+inline size_t      adc_table_bytes(uint32_t S16) { return (size_t)S16 * ADC_LUT_STRIDE * 4; }
+inline uint32_t    adc_scan_T(uint32_t S16)
+{
+    for(uint32_t T = 4; T != 0; T /= 2)
+        if(T * adc_table_bytes(S16) + kAdcScanLdsSpare <= kAdcScanLdsMax) return T;
+    return 0;
+}
+// tables[q] of the nq f32 query rows Q (`chunks` chunks each, as the contraction reads them), by adc_build_table (adc_stage.hpp):
+// the entries have the ADC walk's bits.  metric: the base metric (l2sq / cos); pq: the index's centroid tables
+hipError_t launch_adc_tables(int metric, const uint4 *Q, uint32_t nq, uint32_t chunks, const DensePqRows &pq, float *tables, hipStream_t stream);
+// launch_contraction's two output forms for kind kDensePq from table lookups instead of the MFMA: key(q, row) = the sum of the row's
+// table entries in ascending subvector order (cos: through the contraction's epilogue).  tables: those of o's first query.  o.Q is
+// not read; o.qn (cos), o.bn (cos), o.pq, o.chunks as launch_contraction's.  Refused with hipErrorInvalidValue before any launch:
+// another kind or metric, more than 128 subvectors or 256 centroids, a table that does not fit the LDS alone
+hipError_t launch_contraction_adc(const DenseOperands &o, const float *tables, float *out, uint32_t ldo, const DenseTopk *topk, hipStream_t stream);
 // list: NULL, or the ascending slot list the keys' low words are positions in (k_rerank).  pq (metric M_*_PQD, list NULL): B is code
 // rows, decoded on the fly (k_rerank_pq, dense_pq.hip)
 hipError_t launch_rerank(int metric, const uint4 *Q, uint32_t nq, const uint4 *B, uint32_t chunks, const uint64_t *best, uint32_t kk,
