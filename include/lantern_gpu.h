@@ -476,6 +476,30 @@ LANTERN_GPU_EXPORT void lantern_gpu_filter_dense_stats(usearch_index_t, uint64_t
  * steps, cap, *n_steps: as lantern_gpu_plan_exact_knn's, and exactly its steps for (metric code, chunks, base rows = allowed, queries,
  *   k + skip); none when the route is not taken.  Returns NULL, or why the input is refused. */
 LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_dense(const int64_t in[11], uint32_t out[8], uint32_t steps[][4], size_t cap, size_t *n_steps);
+/* THE SCREENED EXACT PASS (DESIGN.md 4.9 "Screened exact pass"): the exact path's kernel reads every allowed row in f32 for every query.
+ * On an index that holds the int8 screen copy of its rows (f32 rows under l2sq / cos, 509 to 2000 dimensions: the walks' screen,
+ * DESIGN.md 4.3) a second kernel fills its list of k + skip keys as today, then BOUNDS every further allowed row on its screen row and
+ * reads the f32 row only where the bound cannot put it strictly outside the list's radius.  Every output is the exact pass's: slots,
+ * distance bits, labels, counts, D (= allowed), E (= 0); only the rows read differ.
+ * on = 0, THE DEFAULT: every launch is the one issued before this switch existed.
+ * on = 1: every exact launch -- of the single-filter calls, the per-query-filter calls with or without per-query parameters, cursors and
+ *   scans through them -- is the screened kernel's where the index qualifies; where it does not (another metric or scalar kind, rows
+ *   outside 509 - 2000 dimensions, no screen copy, a compact pq index) the launch is today's.  None is refused because of this setting.
+ *   The dense routes keep precedence over the queries their switches take. */
+LANTERN_GPU_EXPORT void lantern_gpu_set_filter_screen(usearch_index_t, int on, usearch_error_t *);
+LANTERN_GPU_EXPORT int lantern_gpu_filter_screen(usearch_index_t, usearch_error_t *); /* the setting */
+/* the last filtered call on this index (waits for the device): out[0] its exact launches that screened, and over their queries
+ * [1] rows put to the bound, [2] rows the bound rejected, [3] f32 rows read (while filling the list: unbounded; then [1] - [2]).
+ * All zero after a call whose exact launch did not screen: the unscreened kernel counts nothing. */
+LANTERN_GPU_EXPORT void lantern_gpu_last_filtered_screen(usearch_index_t, uint64_t out[4], usearch_error_t *);
+/* Whether an exact launch screens, without a device (a pure function; the call itself plans through it).
+ * in[6]: [0] the setting  [1] metric code (as lantern_gpu_plan_dense)  [2] 16-byte chunks per stored row  [3] the index holds the
+ *   screen copy (0 / 1)  [4] the index is a compact pq index (0 / 1)  [5] k + skip, the launch's largest
+ * out[4]: [0] 1: the launch screens  [1] why not, in the order a call meets the reasons: 0 taken, 1 the setting is 0, 2 not f32 rows
+ *   under l2sq / cos, 3 rows of fewer than 128 chunks (the screen is built for 509 - 2000 dimensions), 4 no screen copy, 5 a compact
+ *   pq index, 6 a list of k + skip keys that fits today's carve of the 160 KiB and not this one  and, when taken (0 otherwise): [2] dynamic LDS bytes per workgroup (512 threads): the exact pass's carve at 16 rows per
+ *   round + the query's screen block + the survivor queue  [3] workgroups per CU.  Returns NULL, or why the input is refused. */
+LANTERN_GPU_EXPORT const char *lantern_gpu_plan_filtered_screen(const int64_t in[6], uint32_t out[4]);
 /* THE DENSE ROUTE FOR PER-QUERY-FILTER CALLS (DESIGN.md 4.9 "Dense exact path, per-query filters"): in a call of
  * lantern_gpu_search_batch_filtered_each or lantern_gpu_search_batch_filtered_each_device, the exact-path queries that name the same
  * filter HANDLE form a group, and the groups of at least min_group queries are answered by one segmented run of the exact k-NN: the

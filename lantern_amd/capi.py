@@ -133,6 +133,8 @@ EXPORTS = [
     "lantern_gpu_set_filter_dense_each", "lantern_gpu_filter_dense_each", "lantern_gpu_last_filtered_each_dense", "lantern_gpu_plan_filtered_each_dense",
     "lantern_gpu_set_filter_dense_each_batched", "lantern_gpu_filter_dense_each_batched", "lantern_gpu_last_filtered_each_dense_launches",
     "lantern_gpu_plan_filtered_each_dense_batches",
+    # ... the screened exact pass (lantern_gpu.h "THE SCREENED EXACT PASS")
+    "lantern_gpu_set_filter_screen", "lantern_gpu_filter_screen", "lantern_gpu_last_filtered_screen", "lantern_gpu_plan_filtered_screen",
     # ... with per-query k, ef and skip as well (lantern_gpu.h "PER-QUERY FILTERS WITH PER-QUERY k, ef AND skip")
     "lantern_gpu_search_batch_filtered_each_params", "lantern_gpu_search_batch_filtered_each_params_lane",
     "lantern_gpu_search_batch_filtered_each_params_device", "lantern_gpu_last_filtered_each_params", "lantern_gpu_plan_filtered_params",
@@ -399,6 +401,10 @@ def lib() -> C.CDLL:
         "lantern_gpu_filter_dense_each_batched": (C.c_int, [vp, err]),
         "lantern_gpu_last_filtered_each_dense_launches": (None, [vp, vp, err]),
         "lantern_gpu_plan_filtered_each_dense_batches": (C.c_char_p, [vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
+        "lantern_gpu_set_filter_screen": (None, [vp, C.c_int, err]),
+        "lantern_gpu_filter_screen": (C.c_int, [vp, err]),
+        "lantern_gpu_last_filtered_screen": (None, [vp, vp, err]),
+        "lantern_gpu_plan_filtered_screen": (C.c_char_p, [vp, vp]),
         "lantern_gpu_filter_compact": (C.c_int, [vp, err]),
         "lantern_gpu_plan_filtered_compact": (C.c_char_p, [vp, vp, vp, sz, vp, vp]),
         "lantern_gpu_last_filtered_seeds": (None, [vp, vp, err]),
@@ -710,6 +716,20 @@ def plan_filtered_dense(mcode, chunks, allowed, nq, k, skip=0, min_queries=0, ex
     return {"taken": bool(out[0]), "why": FILTERED_DENSE_WHY[int(out[1])], "kk": int(out[2]), "gather_rows": int(out[3]),
             "gather_bytes": int(out[4]) | int(out[5]) << 32, "norm_bytes": int(out[6]) | int(out[7]) << 32, "n_steps": int(count.value),
             "steps": [(int(s[0]), int(s[1]), bool(s[2]), int(s[3])) for s in steps[:cap]]}
+
+
+# lantern_gpu_plan_filtered_screen's out[1], by value: the reasons in the order a call meets them
+FILTERED_SCREEN_WHY = ("taken", "off", "metric", "width", "no_table", "compact", "lds")
+
+
+def plan_filtered_screen(on, mcode, chunks, table=True, compact=False, kk=10):
+    """lantern_gpu_plan_filtered_screen: whether an exact launch of a filtered call is the screened kernel's (host arithmetic, no device):
+    {"taken", "why" (FILTERED_SCREEN_WHY), "lds", "per_cu"}.  kk: the launch's largest k + skip."""
+    pin, out = np.array([int(on), mcode, chunks, int(bool(table)), int(bool(compact)), kk], np.int64), np.zeros(4, np.uint32)
+    why = lib().lantern_gpu_plan_filtered_screen(_ptr(pin), _ptr(out))
+    if why is not None:
+        raise LanternGpuError(why.decode())
+    return {"taken": bool(out[0]), "why": FILTERED_SCREEN_WHY[int(out[1])], "lds": int(out[2]), "per_cu": int(out[3])}
 
 
 # lantern_gpu_plan_filtered_each_dense's out[2], by value
@@ -1226,6 +1246,22 @@ class GpuIndex:
         _call("lantern_gpu_last_filtered_each_dense", self.h, _ptr(out))
         groups, queries, certified, recomputed, rows, steps = (int(x) for x in out)
         return {"groups": groups, "queries": queries, "certified": certified, "recomputed": recomputed, "rows": rows, "steps": steps}
+
+    def set_filter_screen(self, on):
+        """Exact launches of later filtered searches bound allowed rows on the int8 screen copy before reading them in f32 where the index
+        qualifies (1), or run today's kernel (0, the default)."""
+        _call("lantern_gpu_set_filter_screen", self.h, int(on))
+
+    def filter_screen(self):
+        """lantern_gpu_filter_screen: the setting."""
+        return int(_call("lantern_gpu_filter_screen", self.h))
+
+    def last_filtered_screen(self):
+        """lantern_gpu_last_filtered_screen: the last filtered call's exact launches that screened, rows bounded, rows rejected, f32 rows read."""
+        out = np.zeros(4, dtype=np.uint64)
+        _call("lantern_gpu_last_filtered_screen", self.h, _ptr(out))
+        launches, bounded, rejected, f32_rows = (int(x) for x in out)
+        return {"launches": launches, "bounded": bounded, "rejected": rejected, "f32_rows": f32_rows}
 
     def filter_compact(self):
         """lantern_gpu_filter_compact: None (the switch is off), or what a filtered search runs on now: "stored", "decode" or "adc"."""

@@ -76,5 +76,13 @@ hipError_t launch_search_exact_allowed(int metric, const FilteredArgs &a, int wa
 hipError_t launch_search_filtered_pq(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
 hipError_t launch_search_exact_allowed_pq(int metric, const FilteredArgs &a, int waves, int grid, hipStream_t stream);
 uint32_t   filtered_adc_lds_chunks(uint32_t code_chunks, uint32_t qchunks);  // the ADC table's chunks (code_chunks x 16 KiB) + the raw query row's
+// the screened exact pass (search_filtered_screen_kernel.hip: k_exact_allowed_screened; f32 l2sq / cos rows of an index with the int8
+// screen copy, view.screen and view.screen_meta set): workgroups of kFilterScreenThreads, rows_per_round = 2 * kFilterScreenThreads / 64.
+// The carve, pure host arithmetic: the exact pass's + the query's screen block + the survivor queue.
+constexpr int      kFilterScreenThreads = 512;
+constexpr uint32_t kFilterScreenRound = kFilterScreenThreads / 8;  // slot-list entries of a screen round: eight lanes per screen row
+uint32_t   filtered_screen_queue_slots(uint32_t rows_per_round);  // the survivor queue's ring: a power of two >= rows_per_round - 1 + a screen round
+size_t     filtered_exact_screen_lds_bytes(uint32_t chunks, uint32_t kk, uint32_t rows_per_round);
+hipError_t launch_exact_allowed_screened(int metric, const FilteredArgs &a, int grid, hipStream_t stream);
 
 }  // namespace lgpu

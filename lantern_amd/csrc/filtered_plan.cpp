@@ -23,10 +23,30 @@ static const char *kJointOverBudget =
     "lantern_gpu: the queries fit the 160 KiB LDS budget of the filtered search kernel one by one, but the largest expansion and the largest "
     "candidate cap of the batch do not fit together: split the batch";
 
-// the exact launch's carve for a list of kk keys
+// whether the exact launch of this index is the screened kernel's (search_filtered_screen_kernel.hip), or the first reason it is not
+FilterScreenWhy filter_screen_why(const FilterPlanIn &p, size_t kk)
+{
+    if(!p.screen_on) return kFilterScreenOff;
+    if(p.mcode != M_L2SQ && p.mcode != M_COS) return kFilterScreenMetric;
+    if(!screen_rows_for(p.chunks)) return kFilterScreenWidth;
+    if(!p.screen_table) return kFilterScreenNoTable;
+    if(p.pq_compact || p.adc_code_chunks) return kFilterScreenCompact;
+    // (a list that fits today's carve and not this one keeps today's kernel: the switch refuses nothing)
+    if(filtered_exact_screen_lds_bytes(p.chunks, (uint32_t)kk, 2 * kFilterScreenThreads / 64) > kFilteredLds) return kFilterScreenLds;
+    return kFilterScreenTaken;
+}
+int filtered_screen_per_cu(size_t lds) { return (int)std::max<size_t>(1, std::min<size_t>(kFilterScreenPerCuMax, kFilteredLds / std::max<size_t>(lds, 1))); }
+// the exact launch's carve for a list of kk keys: today's kernel's, or -- the one place where an exact launch becomes the screened one --
+// the screened kernel's (512 threads, so twice the rows per f32 round; + the query's screen block and the survivor queue)
 static void exact_carve(const FilterPlanIn &p, size_t kk, FilteredShape &s)
 {
     s.exp = (uint32_t)kk;
+    s.screened = filter_screen_why(p, kk) == kFilterScreenTaken;
+    if(s.screened) {
+        s.rows_per_round = (uint32_t)(2 * kFilterScreenThreads / 64);
+        s.lds = filtered_exact_screen_lds_bytes(p.chunks, s.exp, s.rows_per_round);
+        return;
+    }
     s.rows_per_round = (uint32_t)(2 * 64 * kFilteredWaves / plan_lanes(p));
     s.lds = filtered_exact_lds_bytes(plan_lds_chunks(p), s.exp, s.rows_per_round);
 }
@@ -176,6 +196,21 @@ try {
 }
 catch(...) {
     return "lantern_gpu: out of memory planning a filtered search";
+}
+
+const char *lantern_gpu_plan_filtered_screen(const int64_t in[ 6 ], uint32_t out[ 4 ])
+{
+    if(!in || !out) return "lantern_gpu: null array";
+    if(in[ 2 ] < 1 || in[ 2 ] > 500) return "lantern_gpu: a stored row has 1 to 500 chunks";
+    if(in[ 5 ] < 1 || in[ 5 ] > ((int64_t)1 << 20)) return "lantern_gpu: k + skip must be 1 to 2^20";
+    FilterPlanIn p{};
+    p.chunks = (uint32_t)in[ 2 ];
+    p.screen_on = in[ 0 ] != 0, p.mcode = (int)in[ 1 ], p.screen_table = in[ 3 ] != 0, p.pq_compact = in[ 4 ] != 0;
+    const FilterScreenWhy why = filter_screen_why(p, (size_t)in[ 5 ]);
+    const bool            taken = why == kFilterScreenTaken;
+    const size_t          lds = taken ? filtered_exact_screen_lds_bytes(p.chunks, (uint32_t)in[ 5 ], 2 * kFilterScreenThreads / 64) : 0;
+    out[ 0 ] = taken, out[ 1 ] = (uint32_t)why, out[ 2 ] = (uint32_t)lds, out[ 3 ] = taken ? (uint32_t)filtered_screen_per_cu(lds) : 0u;
+    return nullptr;
 }
 
 const char *lantern_gpu_plan_filtered_compact(const int64_t in[ 9 ], const int64_t counts[], const lantern_gpu_query_params params[], size_t nq,

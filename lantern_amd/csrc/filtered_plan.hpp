@@ -29,13 +29,36 @@ struct FilterPlanIn
     // a compact pq index served by ADC (search_filtered_pq_kernel.hip): 16-byte chunks of a code row, 1..8; `chunks` is then the raw query
     // row's.  0: rows of `chunks` chunks, stored -- or decoded on the fly, whose shape is the expanded index's
     uint32_t adc_code_chunks = 0;
+    // the screened exact pass (lantern_gpu_set_filter_screen): the switch, and what decides whether an exact launch of this index can take
+    // it -- the metric code, whether the int8 screen copy is there, whether the index is in its compact pq form
+    bool screen_on = false;
+    int  mcode = 0;
+    bool screen_table = false, pq_compact = false;
 };
+
+// whether an exact launch screens (search_filtered_screen_kernel.hip), and if not why: the reasons in the order a call meets them
+// (lantern_gpu_plan_filtered_screen's out[1])
+enum FilterScreenWhy : int
+{
+    kFilterScreenTaken = 0,
+    kFilterScreenOff,      // the switch is 0
+    kFilterScreenMetric,   // not f32 rows under l2sq / cos
+    kFilterScreenWidth,    // rows the screen is not built for (screen_rows_for: fewer than 128 chunks)
+    kFilterScreenNoTable,  // the index holds no screen copy
+    kFilterScreenCompact,  // a compact pq index: today's kernels over its code rows
+    kFilterScreenLds       // k + skip keys fit today's carve but not the screened one
+};
+FilterScreenWhy filter_screen_why(const FilterPlanIn &p, size_t kk);  // kk: the launch's largest k + skip
+// workgroups of the screened launch that a CU holds: by its LDS, and two by its registers (512 threads of at most 128 VGPRs)
+constexpr size_t kFilterScreenPerCuMax = 2;
+int              filtered_screen_per_cu(size_t lds);
 
 // exp, cand_cap, vis_slots / rows_per_round and the LDS bytes of one launch
 struct FilteredShape
 {
     uint32_t exp = 0, cand_cap = 0, vis_slots = 0, rows_per_round = 0;
     size_t   lds = 0;
+    bool     screened = false;  // the exact launch only: k_exact_allowed_screened, whose carve `lds` then is
 };
 
 // the queries of a call by what becomes of them (lantern_gpu_last_filtered_each [0..4)); `empty`: every rider

@@ -25,6 +25,7 @@ static FilterPlanIn filter_plan_in(const Index *ix)
 {
     FilterPlanIn p{ ix->chunks, ix->M0, ix->n, ix->ef, ix->filter_path, ix->filter_cand_cap, ix->filter_exact_factor, ix->filter_seeds };
     if(compact_adc(ix)) p.adc_code_chunks = ix->pq_S16 / 16;
+    p.screen_on = ix->filter_screen, p.mcode = ix->mcode, p.screen_table = ix->d_screen && ix->d_screen_meta, p.pq_compact = ix->pq_compact;
     return p;
 }
 
@@ -69,6 +70,8 @@ static void shape_into(const FilteredShape &s, FilteredArgs &a, size_t &lds)
 {
     a.exp = s.exp, a.cand_cap = s.cand_cap, a.rows_per_round = s.rows_per_round, a.frame.vis_slots = s.vis_slots;
     lds = s.lds;
+    // no screen block in the carve: the launch does not screen (filtered_launch reads the choice here, as search_plan.cpp's launches do)
+    if(!s.screened) a.view.screen = nullptr, a.view.screen_meta = nullptr, a.view.screen_chunks = 0;
 }
 
 // the empty answer in every row of a call, kw wide, with no launch
@@ -103,8 +106,10 @@ EachTables each_tables(const Index *ix, char *blk, size_t nq, const Filter *cons
 
 int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, hipStream_t stream, const EachTable *tbl)
 {
-    const int per_cu = filtered_per_cu(lds);
-    const int grid = search_grid(ix, a.frame.nq, kFilteredWaves, kFilteredWaves * per_cu);
+    const bool screened = exact && a.view.screen;  // (shape_into: the plan's choice)
+    const int  waves = screened ? kFilterScreenThreads / 64 : kFilteredWaves;
+    const int  per_cu = screened ? filtered_screen_per_cu(lds) : filtered_per_cu(lds);
+    const int  grid = search_grid(ix, a.frame.nq, waves, waves * per_cu);
     const int slot = acquire_search_slot(ix, stream, (size_t)grid);
     if(slot < 0) return -1;
     if(tbl) {
@@ -123,7 +128,15 @@ int filtered_launch(Index *ix, bool exact, FilteredArgs &a, size_t lds, hipStrea
     a.frame.undo_cap = vis_undo_cap();
     a.frame.ticket = next_ticket(ix, a.frame.nq, grid, stream);
     hipError_t e;
-    if(ix->pq_compact) {
+    if(screened) {
+        // lantern_gpu_last_filtered_screen: the call's first screened launch starts its counters from zero, on the launch's own stream
+        if(ix->last_screen_launches == 0 && hipMemsetAsync(ix->d_totals + kTotFilterScreen, 0, 3 * sizeof(unsigned long long), stream) != hipSuccess) {
+            set_err(ix, "lantern_gpu: HIP failure (memset)");
+            return -1;
+        }
+        ix->last_screen_launches += 1;
+        e = launch_exact_allowed_screened(ix->mcode, a, grid, stream);
+    } else if(ix->pq_compact) {
         const int metric = ix->metric + (a.adc_centers ? M_ADC : M_PQD);
         e = exact ? launch_search_exact_allowed_pq(metric, a, kFilteredWaves, grid, stream) : launch_search_filtered_pq(metric, a, kFilteredWaves, grid, stream);
     } else {
@@ -152,6 +165,7 @@ static bool filtered_search_locked(Index *ix, const Filter *f, const uint4 *d_q,
     if(!filtered_index_ok(ix)) return false;
     if(nq == 0 || k == 0) return true;
     std::fill(std::begin(ix->last_seeds), std::end(ix->last_seeds), 0u);
+    ix->last_screen_launches = 0;
     const int64_t     count = (int64_t)f->count;
     FilteredCallPlan  plan;
     const std::string bad = plan_filtered_paths(filter_plan_in(ix), &count, 1, nullptr, FilteredAsk{ k, ef, skip }, false, plan);
@@ -274,6 +288,7 @@ static bool filtered_each_locked(Index *ix, const Filter *const *filters, const 
     if(!each_filters_ok(ix, filters, nq)) return false;
     std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);
     std::fill(std::begin(ix->last_each_dense_launches), std::end(ix->last_each_dense_launches), 0u);
+    ix->last_screen_launches = 0;
     if(nq == 0 || k == 0) return true;
     const std::vector<int64_t> counts = each_counts(filters, nq);
     FilteredCallPlan           plan;
@@ -324,6 +339,7 @@ static bool filtered_each_params_locked(Index *ix, const FilteredCallPlan &plan,
 {
     std::fill(std::begin(ix->last_each_dense), std::end(ix->last_each_dense), 0u);
     std::fill(std::begin(ix->last_each_dense_launches), std::end(ix->last_each_dense_launches), 0u);  // (a per-query-filter call that makes no dense run)
+    ix->last_screen_launches = 0;
     if(nq == 0) return true;
     const uint32_t shape[ 4 ] = { plan.sw.exp, plan.sw.cand_cap, plan.se.exp, plan.n_k0 };
     std::copy(std::begin(shape), std::end(shape), ix->last_each_params);
@@ -462,6 +478,40 @@ try {
     return served;
 }
 LANTERN_ABI_CATCH(e)
+
+void lantern_gpu_set_filter_screen(usearch_index_t h, int on, usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(on != 0 && on != 1) { FAIL(e, "lantern_gpu: filter_screen must be 0 (today's exact pass) or 1 (screened where the index qualifies)"); return; }
+    with_locked(h, e, [ & ](Index *ix) { ix->filter_screen = on != 0; });
+}
+LANTERN_ABI_CATCH_VOID(e)
+
+int lantern_gpu_filter_screen(usearch_index_t h, usearch_error_t *e)
+try {
+    CLEAR(e);
+    int on = 0;
+    with_locked(h, e, [ & ](Index *ix) { on = ix->filter_screen ? 1 : 0; });
+    return on;
+}
+LANTERN_ABI_CATCH(e)
+
+void lantern_gpu_last_filtered_screen(usearch_index_t h, uint64_t out[ 4 ], usearch_error_t *e)
+try {
+    CLEAR(e);
+    if(!out) { FAIL(e, "lantern_gpu: null output array"); return; }
+    out[ 0 ] = out[ 1 ] = out[ 2 ] = out[ 3 ] = 0;
+    with_locked(h, e, [ & ](Index *ix) {
+        if(ix->last_screen_launches == 0) return;  // (the unscreened launch writes nothing: the counters are an earlier call's)
+        unsigned long long t[ 3 ] = {};
+        if(hipDeviceSynchronize() != hipSuccess || hipMemcpy(t, ix->d_totals + kTotFilterScreen, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) {
+            FAIL(e, "lantern_gpu: HIP failure reading the screen counters");
+            return;
+        }
+        out[ 0 ] = ix->last_screen_launches, out[ 1 ] = t[ 0 ], out[ 2 ] = t[ 1 ], out[ 3 ] = t[ 2 ];
+    });
+}
+LANTERN_ABI_CATCH_VOID(e)
 
 void lantern_gpu_set_filter_dense(usearch_index_t h, size_t min_queries, usearch_error_t *e)
 try {

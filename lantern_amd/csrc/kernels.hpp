@@ -111,9 +111,14 @@ enum TotalsSlot : int
     kTotSearchScreen = 48,  // [2] the searches' screen: row evaluations, of which read the f32 row
     kTotInsertScreen = 50,  // [2] k_insert's screen: rows tested, rows rejected
     kTotUnlink = 52,        // [2] lantern_gpu_unlink_deleted's reverse links: pair evaluations, re-prunes (unlink.hip; not a build counter)
+    kTotFilterScreen = 54,  // [3] the screened filtered exact pass of the last call: rows bounded, rows rejected, f32 rows read
     kTotalsWords = 64       // the block's size
 };
 constexpr int kTotPhaseProfileWords = 8, kTotSpecProfileWords = 32;
+static_assert(kTotUnlink + 2 <= kTotFilterScreen && kTotFilterScreen + 3 <= kTotalsWords, "the ranges of Index::d_totals are disjoint and inside the block");
+// k_exact_allowed_screened (search_filtered_screen_kernel.hip) reaches kTotFilterScreen from FilteredArgs::frame.totals, as k_insert
+// reaches its screen counters below: the argument block of the unscreened filtered kernels stays as it was.
+constexpr int kFilterScreenTotals = kTotFilterScreen - kTotSearch;
 static_assert(kTotSearch + 2 <= kTotInsert && kTotInsert + 2 <= kTotConnect && kTotConnect + 1 <= kTotRevlink && kTotRevlink + 2 <= kTotPhaseProfile &&
                   kTotPhaseProfile + kTotPhaseProfileWords <= kTotSpecProfile && kTotSpecProfile + kTotSpecProfileWords <= kTotSearchScreen &&
                   kTotSearchScreen + 2 <= kTotInsertScreen && kTotInsertScreen + 2 <= kTotUnlink && kTotUnlink + 2 <= kTotalsWords,
